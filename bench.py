@@ -14,11 +14,17 @@ every rank decodes its own `--batch` images; the only cross-rank traffic is a gl
                                                          the ranks (1 250 per GPU at N = 8), each rank feeding its share
                                                          through a per-GPU image queue (strong scaling)
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries: `roofline` (+ `roofline_other_stage`; `two_launches` when the step is
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`, ...); it checks nothing and measures nothing else.  With --full the line also holds `parity` (the outputs
+held to the CPU oracle) and, at N = 1: `roofline` (+ `roofline_other_stage`; `two_launches` when the step is
 one fused launch), `cpu_baseline` (the C oracle on this host's cores + the reference's own timing from the build
 container), `idct_only` (BASELINE configs[1]), `progressive` (BASELINE configs[4]: 1024 x 1080p progressive),
 `gpu_segmented`, `stage2_exact_only_ms`, `single_file_latency`, `mixed_content`, `without_restart_markers`,
 `host_bytes_to_device_pixels`.
+
+    python bench.py --dump-outputs DIR                   after the timed steps, what the last step left for a caller, as
+                                                         float32 / float64 .npy files (rank 0; dump_outputs below): two builds run with
+                                                         the same arguments decode the same inputs and can be compared file by file
 """
 import argparse
 import hashlib
@@ -66,6 +72,36 @@ def images_not_matching_the_oracle(raws, fetch, layout_name: str = "xmajor", w: 
         return None if np.array_equal(got, ref) else i
     with ThreadPoolExecutor(max_workers=workers or max(1, min(os.cpu_count() or 1, 32))) as ex:
         return sorted(i for i in ex.map(one, range(len(raws))) if i is not None)
+
+
+DUMP_SAMPLE = 1 << 21          # pixel bytes sampled over the whole batch output
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, d_rgb, n_images: int, status, layout_name: str):
+    """What a caller of the timed path receives after its last step, as float32 / float64 .npy files in `out_dir` (50 MB at the
+    default workload): `rgb_image_first.npy` — the batch's first image whole, in the layout's shape ((W, H, 3) x-major, (H, W, 3)
+    row-major); `rgb_sample.npy` — DUMP_SAMPLE bytes of the n_images-image RGB output at fixed, seeded positions
+    (`rgb_sample_index.npy`, float64: flat byte offsets into the batch's output), so that every image has its say; `status.npy` —
+    the per-image status codes (0 = decoded).  `d_rgb` is the device output buffer (uint8), read after the stream is idle."""
+    import numpy as np
+    import torch
+    per = W * H * 3
+    total = n_images * per
+    torch.cuda.synchronize()
+    flat = d_rgb[:total]
+    if total <= DUMP_SAMPLE:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=DUMP_SAMPLE, replace=False))
+    sample = flat[torch.from_numpy(pos).to(d_rgb.device)].cpu().numpy()
+    shape = (W, H, 3) if layout_name == "xmajor" else (H, W, 3)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "rgb_image_first.npy", flat[:per].cpu().numpy().reshape(shape).astype(np.float32))
+    np.save(out / "rgb_sample.npy", sample.astype(np.float32))
+    np.save(out / "rgb_sample_index.npy", pos.astype(np.float64))
+    np.save(out / "status.npy", np.asarray(status, dtype=np.float32)[:n_images])
 
 
 def timed_executes(torch, plan, stream, out_ptr, reps: int, warm_s: float = 1.0, warm_min: int = 3, tune: int = 4):
@@ -455,8 +491,13 @@ def main():
     ap.add_argument("--restart-interval", type=int, default=120,
                     help="MCUs per restart segment of the synthetic files (120 = one MCU row = BASELINE configs[2]; 0 = no DRI: "
                          "one segment per image, decoded through the synchronisation passes)")
-    ap.add_argument("--parity-images", type=int, default=0, help="distinct images held to the oracle after the timed region (0 = all of them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip cpu_baseline and the side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity against the oracle, per-launch times and rooflines, and at N = 1 the CPU baseline "
+                         "and the side measurements (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/*.npy (float32 / float64, < 64 MB; see dump_outputs)")
+    ap.add_argument("--parity-images", type=int, default=0, help="--full: distinct images held to the oracle after the timed region (0 = all of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and the side measurements")
     ap.add_argument("--no-progressive", action="store_true")
     ap.add_argument("--backend", default="gloo", choices=["gloo", "nccl"],
                     help="process group for the barrier / MAX of timings (gloo: nothing of this job needs RCCL)")
@@ -464,6 +505,8 @@ def main():
     ap.add_argument("--tune-placement", type=int, default=4,
                     help="coefficient stores the plan tries before the timed region (mj_plan_tune_placement; 1 = keep what the allocator gave)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher of N ranks.  It has not imported torch and has not
         # touched the GPU; the ranks are CHILD processes (no exec of a process that initialised HIP), and rank 0's JSON line is
@@ -605,10 +648,19 @@ def main():
     dt = max_over_ranks(dt, dev if (world > 1 and args.backend == "nccl") else None)
     images_all_ranks = int(sum_over_ranks(float(n_mine), dev if (world > 1 and args.backend == "nccl") else None))
 
+    # ---- what the last timed step left, before anything else runs on the GPU
+    if rank == 0 and args.dump_outputs:
+        if queue_mode:          # the share's last plan of the last pass: its pixels stay in their slot until `depth` more plans are submitted
+            k_last = len(queue.batches) - 1
+            dump_outputs(args.dump_outputs, queue.out_tensor(queue.slot_of(k_last)), queue.batches[k_last][3],
+                         queue.statuses[k_last], args.layout)
+        else:
+            dump_outputs(args.dump_outputs, d_rgb, args.batch, plan.read(rgb=False)["status"], args.layout)
+
     # ---- per-launch times (HIP events on the launch stream) for the roofline objects, taken NOW: the parity check below leaves
     # the GPU idle for seconds, and launches timed in the first second after such a pause came out 2-4x too long (clocks)
     stage_times = None
-    if rank == 0 and not queue_mode:
+    if rank == 0 and not queue_mode and args.full:
         plan.time_stages(2, d_rgb.data_ptr())           # (the stages' own kernels have not run yet when the step is one fused launch)
         launch_clock = None
         if plan.stage1_form() & B.MJ_FORM_FUSED:
@@ -626,10 +678,10 @@ def main():
     # ---- parity of what was just timed, outside the timed region.  One plan: EVERY distinct image of the rank's batch against
     # the oracle (a pool of host threads), every replica against its first instance on the device, every image's status.
     # Queue mode: every distinct image of rank 0's first and last plan against the oracle, every plan's statuses. -------------
-    parity = "unchecked"
+    parity = "unchecked" if args.full else "unchecked (bench.py --full holds the outputs to the oracle)"
     per = W * H * 3
 
-    if queue_mode:
+    if args.full and queue_mode:
         status_bad = queue.bad
         if rank == 0:
             # rank 0's first and last plan once more, every distinct image of each against the oracle (the timed passes' statuses
@@ -648,7 +700,7 @@ def main():
             ok = ok and not bad_q and queue.bad == status_bad
             parity = (f"bit-exact vs oracle: every distinct image of rank 0's first and last plan ({checked} images), every plan's statuses ok"
                       if ok else f"MISMATCH (images {bad_q[:8]}, plans with a status not ok: {queue.bad})")
-    else:
+    elif args.full:
         out = plan.read(rgb=False)
         status_bad = int(np.count_nonzero(out["status"]))
         if rank == 0:
@@ -705,7 +757,7 @@ def main():
     # through memory, written by the walk and read back by the same CU —, `roofline_other_stage` what runs in front of it
     # (stage 0), and `two_launches` the same plan's stages launched separately (mj_plan_execute_stage1 / _stage2), each
     # with its own roofline: stage 2 alone is the kernel BASELINE.json's 40 % target is about.
-    if rank == 0 and not queue_mode:
+    if rank == 0 and not queue_mode and args.full:
         fused = bool(plan.stage1_form() & B.MJ_FORM_FUSED)
         front_ms, main_ms, s1_ms, s2_ms = stage_times
         copy_gbs = None
@@ -777,9 +829,10 @@ def main():
         else:
             line["roofline"], line["roofline_other_stage"] = (r1, r2) if s1_ms >= s2_ms else (r2, r1)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    side = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if side:
         line["cpu_baseline"] = cpu_baseline(raws[:64])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not queue_mode and args.restart_interval == 120:
+    if side and not queue_mode and args.restart_interval == 120:
         if plan is not None:
             try:
                 line["pipelined"] = pipelined_side(ctx, dev, torch, prep, d_blob, plan, d_rgb)

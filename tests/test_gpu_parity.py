@@ -1710,7 +1710,7 @@ def test_config4_sharded_queue_two_ranks_on_one_gpu():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--share-gpu", "--total-images", "50", "--queue-batch", "8",
-           "--distinct", "6", "--steps", "2", "--warmup", "1"]
+           "--distinct", "6", "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1728,7 +1728,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--batch", "64",
-           "--distinct", "8", "--no-cpu-baseline"]
+           "--distinct", "8", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT), env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -1736,6 +1736,43 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak"
     assert line["config"]["images_per_gpu"] == 64 and line["parity"].startswith("bit-exact")
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline only, for exactly --steps timed steps; --dump-outputs leaves the
+    last step's output as float32 / float64 .npy files under 64 MB — the first image whole and a seeded sample of the batch —,
+    each byte of which must be the oracle's."""
+    import json
+    import subprocess
+    import sys
+    from oracle import oracle
+    from tools import synth
+    n, nd, W, H = 8, 4, 1920, 1080
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--batch", str(n), "--distinct", str(nd),
+           "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - n * W * H / 1e6 / (line["ms_per_step"] * 1e-3)) < 0.01 * line["value"]
+    assert line["parity"].startswith("unchecked")
+    assert not {"roofline", "cpu_baseline", "progressive", "idct_only"} & set(line)
+    files = {p.name: np.load(p) for p in out_dir.glob("*.npy")}
+    assert set(files) == {"rgb_image_first.npy", "rgb_sample.npy", "rgb_sample_index.npy", "status.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in out_dir.glob("*.npy")) <= 64 << 20
+    assert files["status.npy"].shape == (n,) and not files["status.npy"].any()
+    blob, offs = synth.synth_batch(nd, 0, W, H, 85, "420", 120)          # bench.py's inputs on rank 0
+    refs = [oracle.decode(blob[int(offs[i]):int(offs[i + 1])].tobytes())["rgb"] for i in range(nd)]
+    assert np.array_equal(files["rgb_image_first.npy"], refs[0].astype(np.float32))
+    pos = files["rgb_sample_index.npy"].astype(np.int64)
+    per = W * H * 3
+    assert pos.shape == files["rgb_sample.npy"].shape and 0 <= pos.min() and pos.max() < n * per and len(np.unique(pos // per)) == n
+    flat = np.stack([r.reshape(-1) for r in refs])
+    assert np.array_equal(files["rgb_sample.npy"], flat[(pos // per) % nd, pos % per].astype(np.float32))
 
 
 def _idct_blocks_through_stage2(dec, blocks_xy, layout, cols=2048):
@@ -1915,7 +1952,8 @@ def test_config4_one_ranks_share_at_size():
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--total-images", "1250", "--distinct", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--total-images", "1250", "--distinct", "64", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,14 +6,14 @@ O=$R/gpurun_out
 ( time bash "$R/tools/profile_round.sh" "$TAG" > /dev/null 2>&1 ) 2> "$O/profile_round_time_$TAG.txt"
 mkdir -p "$O/prog_$TAG"
 ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prog_$TAG/stats" -- python3 "$R/tools/prog_batch_probe.py" 1024 > "$O/prog_$TAG/stats.log" 2>&1 )
-( cd "$R" && timeout 600 python3 bench.py --total-images 1250 --no-cpu-baseline --no-progressive > "$O/config4_1gpu_share_$TAG.json" 2> "$O/config4_1gpu_share_$TAG.err" )
-( cd "$R" && timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --share-gpu --total-images 2500 --no-cpu-baseline --no-progressive > "$O/config4_2rank_sharegpu_$TAG.json" 2> "$O/config4_2rank_sharegpu_$TAG.err" )
+( cd "$R" && timeout 600 python3 bench.py --total-images 1250 --full --no-cpu-baseline --no-progressive > "$O/config4_1gpu_share_$TAG.json" 2> "$O/config4_1gpu_share_$TAG.err" )
+( cd "$R" && timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --share-gpu --total-images 2500 --full --no-cpu-baseline --no-progressive > "$O/config4_2rank_sharegpu_$TAG.json" 2> "$O/config4_2rank_sharegpu_$TAG.err" )
 bash "$R/tools/layout_sweep.sh" > /dev/null 2>&1
 ( cd "$R" && timeout 300 python3 tools/stage_probe.py --mixed --distinct 256 "" MJ_SEG_ORDER=blob MJ_SEG_ORDER=binned MJ_SEG_ORDER=striped MJ_HUFFMAN=lanes11 > "$O/mixed_orders_$TAG.txt" 2>&1 )
 ( cd "$R" && timeout 300 python3 tools/generic_layout_probe.py > "$O/generic_layouts_$TAG.txt" 2>&1 )
 ( cd "$R" && timeout 300 python3 tools/prog_batch_probe.py 16 256 512 768 1024 2048 > "$O/prog_sweep_$TAG.txt" 2>&1 )
 ( cd "$R" && timeout 300 python3 tools/e2e_probe.py > "$O/e2e_$TAG.txt" 2>&1 )
-( cd "$R" && timeout 600 python3 bench.py --gpus 2 --share-gpu --steps 20 --warmup 3 --no-cpu-baseline --no-progressive > "$O/bench_gpus2_sharegpu_$TAG.json" 2> "$O/bench_gpus2_sharegpu_$TAG.err" )
+( cd "$R" && timeout 600 python3 bench.py --gpus 2 --share-gpu --steps 20 --warmup 3 --full --no-cpu-baseline --no-progressive > "$O/bench_gpus2_sharegpu_$TAG.json" 2> "$O/bench_gpus2_sharegpu_$TAG.err" )
 ( cd "$R" && bash tools/nodri_stats.sh 256 > "$O/nodri_stats_$TAG.txt" 2>&1 )
 ( cd "$R" && timeout 300 python3 tools/stage_probe.py --ri 0 --batch 1 --distinct 1 "" > "$O/nodri_sizes_$TAG.txt" 2>&1; for n in 16 64 256 1024; do timeout 300 python3 tools/stage_probe.py --ri 0 --batch $n --distinct 16 "" MJ_SYNC_COUNT=classic 2>&1 | tail -2 | sed "s/^/$n files: /" >> "$O/nodri_sizes_$TAG.txt"; done )
 ( cd "$R" && timeout 200 python3 tools/single_file_probe.py 120 > "$O/single_file_$TAG.txt" 2>&1 )
