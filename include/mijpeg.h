@@ -187,6 +187,26 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
 
 /* ---- plan: upload once, execute many times (bench.py times mj_plan_execute only) ------------------ */
 int mj_plan_create(mj_context *ctx, const mj_batch *batch, mj_plan **out);
+/* Region-of-interest decode: a plan whose output for image i is the window rois[i] of the image — x along image_width,
+ * y along image_height — and nothing else.  rois: host, batch->n_images entries; NULL = whole images (then the same as
+ * mj_plan_create, except that the plan never takes the fused launch).  Window i in the plan's layout:
+ *   MJ_LAYOUT_XMAJOR    full[x:x+width, y:y+height]      of the (W, H, C) image
+ *   MJ_LAYOUT_ROWMAJOR  full_rm[y:y+height, x:x+width]   of the (H, W, C) image
+ *   planar layouts      the same windows, one component after another (greyscale: one component)
+ * Outputs are packed window after window: mj_plan_info.total_pixels / rgb_bytes are sums over the windows and
+ * mj_plan_image_offsets' rgb_off lies in that packing.  A pixel depends only on the MCU that covers it (the reference
+ * upsamples inside the MCU), so a window is bit-exact: the whole image's decode, sliced.
+ * Only the restart segments that hold an MCU of the window are decoded (host-segmented baseline batches list only those;
+ * MJ_FLAG_GPU_SEGMENT batches gather them after the marker scan).  Files without restart markers, progressive and
+ * non-interleaved batches decode every scan whole; stage 2 runs on the windows' MCUs only.
+ * Status: status[i] reports what the DECODED segments found — a damaged restart segment outside the window does not fail
+ * the image (the marker scan of MJ_FLAG_GPU_SEGMENT still checks every marker of the image).
+ * MJ_ERR_INVALID (message naming the image): an empty window or one not inside its image; MJ_FLAG_KEEP_PLANES /
+ * MJ_FLAG_KEEP_IDCT (the seam outputs are whole-image). */
+typedef struct {
+    int32_t x, y, width, height;
+} mj_roi;
+int mj_plan_create_roi(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, mj_plan **out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments

@@ -24,7 +24,7 @@ MJ_FLAG_NO_SYNC = 64
 # every symbol include/mijpeg.h declares (tests check the library exports all of them)
 EXPORTS = (
     "mj_create", "mj_destroy", "mj_last_error", "mj_version", "mj_context_wait_event",
-    "mj_plan_create", "mj_plan_destroy", "mj_plan_get_info", "mj_plan_image_offsets",
+    "mj_plan_create", "mj_plan_create_roi", "mj_plan_destroy", "mj_plan_get_info", "mj_plan_image_offsets",
     "mj_plan_execute", "mj_plan_execute_stage1", "mj_plan_execute_stage2", "mj_plan_sync",
     "mj_plan_device_buffers", "mj_plan_read", "mj_plan_write_coef", "mj_plan_fill_coef",
     "mj_decode_baseline_batch", "mj_idct_batch", "mj_plan_time_stages", "mj_plan_time_execute", "mj_plan_idct_levels", "mj_host_idct_table", "mj_host_assemble", "mj_plan_stage1_form", "mj_set_option", "mj_get_option", "mj_debug_stage1_form", "mj_debug_fused_shape", "mj_debug_count_tables",
@@ -75,6 +75,11 @@ class HostJobC(ctypes.Structure):
                 ("skip", ctypes.c_void_p), ("n_accepted", ctypes.c_int32)]
 
 
+class RoiC(ctypes.Structure):
+    """mj_roi: one image's window (x along image_width, y along image_height)."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
 class PlanInfoC(ctypes.Structure):
     _fields_ = [("total_blocks", ctypes.c_int64), ("total_mcus", ctypes.c_int64), ("total_pixels", ctypes.c_int64),
                 ("rgb_bytes", ctypes.c_int64), ("entropy_bytes", ctypes.c_int64)]
@@ -111,6 +116,7 @@ def load_library():
     L.mj_last_error.restype = ctypes.c_char_p
     L.mj_context_wait_event.argtypes = [vp, vp]
     L.mj_plan_create.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(vp)]
+    L.mj_plan_create_roi.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), ctypes.POINTER(vp)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
     L.mj_plan_get_info.argtypes = [vp, ctypes.POINTER(PlanInfoC)]
@@ -296,13 +302,18 @@ class Context:
 
 
 class Plan:
-    """mj_plan over a prepared batch (see batch.PreparedBatch)."""
+    """mj_plan over a prepared batch (see batch.PreparedBatch).  rois: None, or one (x, y, width, height) per image —
+    a window plan (mj_plan_create_roi) whose output for every image is that window."""
 
-    def __init__(self, ctx: Context, batch_c: BatchC, keepalive):
+    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
-        ctx.check(ctx.lib.mj_plan_create(ctx.handle, ctypes.byref(batch_c), ctypes.byref(h)))
+        if rois is None:
+            ctx.check(ctx.lib.mj_plan_create(ctx.handle, ctypes.byref(batch_c), ctypes.byref(h)))
+        else:
+            arr = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in r)) for r in rois])
+            ctx.check(ctx.lib.mj_plan_create_roi(ctx.handle, ctypes.byref(batch_c), arr, ctypes.byref(h)))
         self.handle = h
         info = PlanInfoC()
         ctx.check(ctx.lib.mj_plan_get_info(h, ctypes.byref(info)))

@@ -336,6 +336,61 @@ def prepare_batch_native(files: Sequence[bytes], layout: int = B.MJ_LAYOUT_XMAJO
                          layout=layout, flags=flags | B.MJ_FLAG_GPU_SEGMENT, shapes=shapes)
 
 
+def _image_dims(raw: bytes) -> Tuple[int, int]:
+    """(width, height) from a file's frame header (SOF0-SOF15 but DHT / JPG / DAC), walking the marker segments in front of
+    it; anything unusual goes through the parser, which raises the reference's exceptions."""
+    pos, n = 2, len(raw)
+    if raw[:2] == b"\xFF\xD8":
+        while pos + 9 <= n and raw[pos] == 0xFF:
+            m = raw[pos + 1]
+            if m == 0xFF:
+                pos += 1
+                continue
+            seg = (raw[pos + 2] << 8) | raw[pos + 3]
+            if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+                return (raw[pos + 7] << 8) | raw[pos + 8], (raw[pos + 5] << 8) | raw[pos + 6]
+            if m == 0xDA or seg < 2:
+                break
+            pos += 2 + seg
+    p = parse_jpeg(raw, headers_only=True)
+    return p.image_width, p.image_height
+
+
+def normalize_rois(rois, dims: Sequence[Tuple[int, int]]) -> Optional[List[Tuple[int, int, int, int]]]:
+    """The windows of a region-of-interest decode, one (x, y, width, height) per file, checked against the files' (width,
+    height) — x along the width, y along the height.  ``rois``: None (whole images: returns None), one (x, y, width, height)
+    for every file, or a sequence of ``len(dims)`` entries, each such a 4-tuple or None (that file's whole image).  Raises
+    ValueError naming the file for a malformed, empty or out-of-image window."""
+    if rois is None:
+        return None
+    n = len(dims)
+
+    def is_window(r) -> bool:
+        return isinstance(r, (tuple, list, np.ndarray)) and len(r) == 4 and all(isinstance(v, (int, np.integer)) for v in r)
+
+    if is_window(rois):
+        entries = [rois] * n
+    else:
+        try:
+            entries = list(rois)
+        except TypeError:
+            raise ValueError("rois must be None, one (x, y, width, height) or one entry per file") from None
+        if len(entries) != n:
+            raise ValueError(f"rois has {len(entries)} entries for {n} files")
+    out = []
+    for i, (r, (w, h)) in enumerate(zip(entries, dims)):
+        if r is None:
+            out.append((0, 0, int(w), int(h)))
+            continue
+        if not is_window(r):
+            raise ValueError(f"file {i}: window {r!r} is not an (x, y, width, height) tuple of integers")
+        x, y, ww, wh = (int(v) for v in r)
+        if ww <= 0 or wh <= 0 or x < 0 or y < 0 or x + ww > w or y + wh > h:
+            raise ValueError(f"file {i}: window (x={x}, y={y}, width={ww}, height={wh}) is empty or not inside the {w}x{h} image")
+        out.append((x, y, ww, wh))
+    return out
+
+
 def raise_for_status(status: np.ndarray):
     bad = np.flatnonzero(status)
     if bad.size:
@@ -400,18 +455,30 @@ class BatchDecoder:
             return wh
         return (3,) + wh if self.layout >= B.MJ_LAYOUT_PLANAR_XMAJOR else wh + (3,)
 
-    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1) -> List[np.ndarray]:
+    @staticmethod
+    def _out_shapes(prep: PreparedBatch, wins=None) -> List[Tuple[int, int, int]]:
+        """(width, height, ncomp) of every image's output: the image, or its window."""
+        if wins is None:
+            return list(prep.shapes)
+        return [(w[2], w[3], nc) for w, (_, _, nc) in zip(wins, prep.shapes)]
+
+    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None) -> List[np.ndarray]:
         out, off = [], 0
-        for (w, h, nc) in prep.shapes:
+        for (w, h, nc) in self._out_shapes(prep, wins):
             n = w * h * nc * per_pixel
             out.append(flat[off:off + n].reshape(self._shape(w, h, nc)))
             off += n
         return out
 
-    def decode(self, files: Sequence[bytes], return_seams: bool = False):
-        """Decode files that may mix sampling layouts (one plan per layout)."""
+    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False):
+        """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
+        None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
+        the window's shape (see :func:`normalize_rois`)."""
+        if rois is not None and return_seams:
+            raise ValueError("rois and return_seams do not go together: the seam outputs are whole-image")
         gpu_segment = self._gpu_segment_for(files)
         parsed = [parse_jpeg(f, headers_only=gpu_segment) for f in files]
+        wins = normalize_rois(rois, [(p.image_width, p.image_height) for p in parsed])
         groups: Dict[tuple, List[int]] = {}
         for i, p in enumerate(parsed):
             check_supported(p)
@@ -425,7 +492,8 @@ class BatchDecoder:
         while work:
             idxs, extra = work.pop(0)
             prep = prepare_batch([files[i] for i in idxs], self.layout, flags | extra, [parsed[i] for i in idxs])
-            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)})
+            sub = [wins[i] for i in idxs] if wins is not None else None
+            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)}, rois=sub)
             try:
                 plan.execute()
                 plan.sync()
@@ -442,7 +510,7 @@ class BatchDecoder:
                     work.append((again, extra | B.MJ_FLAG_NO_SYNC))
                     out["status"][[k for k, i in enumerate(idxs) if i in again]] = 0
                 raise_for_status(out["status"])
-                imgs = self.split_outputs(prep, out["rgb"])
+                imgs = self.split_outputs(prep, out["rgb"], wins=sub)
                 for k, i in enumerate(idxs):
                     if i in redo or i in again:
                         continue
@@ -466,7 +534,7 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def decode_device(self, files: Sequence[bytes], parts: Optional[int] = None):
+    def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -475,15 +543,20 @@ class BatchDecoder:
         front end (``mj_host_assemble``) reads the headers and assembles the batch on host threads; whatever it declines
         takes the Python path below, which raises the reference's exceptions.  A large batch on that route goes as ``parts``
         plans of 256 files or more (up to four) through :meth:`decode_device_iter`, so that one part's upload runs under the
-        assembly of the next and under the kernels of the one before — inside one call the three would otherwise add up."""
+        assembly of the next and under the kernels of the one before — inside one call the three would otherwise add up.
+        ``rois`` as in :meth:`decode`: the windows are checked against the files' headers before any GPU work."""
         import torch
+        wins = None
+        if rois is not None:
+            wins = normalize_rois(rois, [_image_dims(f) for f in files])
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts > 1:
             n = len(files)
             cut = [n * i // parts for i in range(parts + 1)]
             out: List["torch.Tensor"] = []
-            for part in self.decode_device_iter((files[cut[i]:cut[i + 1]] for i in range(parts)), depth=2):
+            for part in self._device_iter(((files[cut[i]:cut[i + 1]], wins[cut[i]:cut[i + 1]] if wins is not None else None)
+                                           for i in range(parts)), depth=2):
                 out += part
             return out
         dev = torch.device("cuda", self.ctx.device)
@@ -541,7 +614,8 @@ class BatchDecoder:
                             d_blob = torch.from_numpy(prep.blob).to(dev)         # (pageable source: the staging buffer is free on return)
                     else:
                         d_blob = torch.from_numpy(prep.blob).to(dev)
-                    plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(idxs)})
+                    plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(idxs)},
+                                  rois=[wins[i] for i in idxs] if wins is not None else None)
                     flying.append((idxs, prep, plan, None, d_blob))
                     d_rgb = torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     flying[-1] = (idxs, prep, plan, d_rgb, d_blob)
@@ -583,8 +657,9 @@ class BatchDecoder:
                         status[[k for k, i in enumerate(idxs) if i in again]] = 0
                     raise_for_status(status)
                     off = 0
+                    shapes = self._out_shapes(prep, [wins[i] for i in idxs] if wins is not None else None)
                     for k, i in enumerate(idxs):
-                        w, h, nc = prep.shapes[k]
+                        w, h, nc = shapes[k]
                         n = w * h * nc
                         if i not in redo and i not in again:
                             results[i] = d_rgb[off:off + n].view(self._shape(w, h, nc))
@@ -606,6 +681,10 @@ class BatchDecoder:
         idled meanwhile: 512 x 1080p took the front end's 4.3 ms PLUS the upload's 6.1 ms per batch; with two the three —
         host threads, copy engine, GPU — run side by side and the batch takes what the slowest of them takes.  Batches the front
         end declines are decoded by :meth:`decode_device` in place, behind everything in flight (no overlap for those)."""
+        yield from self._device_iter(((files, None) for files in batches), depth)
+
+    def _device_iter(self, batches, depth=2):
+        """:meth:`decode_device_iter` over (files, windows or None) pairs (windows: normalize_rois' list for those files)."""
         import collections
         import torch
         dev = torch.device("cuda", self.ctx.device)
@@ -616,7 +695,7 @@ class BatchDecoder:
         turn = 0
         pending = collections.deque()       # ((plan, prep, d_rgb, d_blob), files) of the batches in flight, oldest first
 
-        def finish(job):
+        def finish(job, wins):
             plan, prep, d_rgb, _ = job
             try:
                 plan.sync()
@@ -626,7 +705,7 @@ class BatchDecoder:
                 status[again] = 0                                 # something behind a scan / rounds not settled: those files again, below
                 raise_for_status(status)
                 out, off = [], 0
-                for (w, h, nc) in prep.shapes:
+                for (w, h, nc) in self._out_shapes(prep, wins):
                     n = w * h * nc
                     out.append(d_rgb[off:off + n].view(self._shape(w, h, nc)))
                     off += n
@@ -635,15 +714,16 @@ class BatchDecoder:
                 plan.close()
 
         def collect(job):
-            out, again = finish(job[0])
+            out, again = finish(job[0], job[2])
             if again.size:                                        # only the files concerned take the long way (host parse)
-                redo = self.decode_device([job[1][int(i)] for i in again], parts=1)
+                redo = self.decode_device([job[1][int(i)] for i in again], parts=1,
+                                          rois=[job[2][int(i)] for i in again] if job[2] is not None else None)
                 for i, img in zip(again, redo):
                     out[int(i)] = img
             return out
 
         try:
-            for files in batches:
+            for files, wins in batches:
                 files = list(files)
                 prep = None
                 if self.gpu_segment and self.native_host and files:
@@ -659,13 +739,13 @@ class BatchDecoder:
                 if prep is None:
                     while pending:
                         yield collect(pending.popleft())
-                    yield self.decode_device(files, parts=1)
+                    yield self.decode_device(files, rois=wins, parts=1)
                     continue
                 with torch.cuda.stream(copy_stream):
                     d_blob = pinned[buf][:prep.blob.size].to(dev, non_blocking=True)
                     uploaded[buf] = torch.cuda.Event()
                     uploaded[buf].record(copy_stream)
-                plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(files)})
+                plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(files)}, rois=wins)
                 try:
                     # (both tensors outlive the kernels that touch them: they stay in `pending` until the plan has been collected)
                     d_rgb = torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
@@ -677,7 +757,7 @@ class BatchDecoder:
                 except BaseException:
                     plan.close()
                     raise
-                pending.append(((plan, prep, d_rgb, d_blob), files))
+                pending.append(((plan, prep, d_rgb, d_blob), files, wins))
                 while len(pending) > depth:
                     yield collect(pending.popleft())
             while pending:

@@ -106,7 +106,7 @@ void mj_plan_destroy(mj_plan *p) {
     }
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
     void *ptrs[] = {p->d_blob_owned, p->d_segs, p->d_images, p->d_huff, p->d_lut11, p->d_lut13, p->d_lut12, p->d_by_length, p->d_holder, p->d_xwords, p->d_wg_tabs_lanes, p->d_wg_tabs_count, p->d_stream, p->d_seg_bits, p->d_jobs, p->d_lut11u, p->d_acsegs, p->d_pc_chunks, p->d_pc_tabs, p->d_pc_exit, p->d_pc_outs, p->d_pc_items, p->d_pc_owner, p->d_pc_vsegs, p->d_lutc, p->d_sync_items, p->d_seg_chunk0, p->d_chunks, p->d_stateA, p->d_stateB, p->d_couts, p->d_vsegs, p->d_changed, p->d_pieces, p->d_piece_kept, p->d_pscans, p->d_psegs, p->d_pstates, p->d_psubs, p->d_prog_dsegs, p->d_lut11p, p->d_qt, p->d_mcu_prefix, p->d_job_prefix, p->d_tmp_coef, p->d_coef,
-                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status};
+                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status, p->d_win, p->d_win_mcu_prefix, p->d_segs_full, p->d_seg_gather};
     for (void *q : ptrs)
         if (q) p->ctx->cache.put(q);
     delete p;
@@ -220,8 +220,11 @@ static int stage1_impl(mj_plan *p, void *stream) {
         return MJ_OK;
     }
     if (p->blob_src) MJ_HIP(ctx, hipMemcpyAsync(p->d_blob_owned, p->blob_src, (size_t)p->blob_src_len, hipMemcpyDeviceToDevice, s));
-    if (p->n_jobs)      // restart markers and the end of each scan, found on the GPU
-        MJ_HIP(ctx, mj::launch_scan_markers(s, p->d_blob, p->d_jobs, p->n_jobs, p->d_segs, p->d_status));
+    if (p->n_jobs) {    // restart markers and the end of each scan, found on the GPU
+        // (window plans that need only some of the segments: the scan fills the whole list, the needed ones are gathered)
+        MJ_HIP(ctx, mj::launch_scan_markers(s, p->d_blob, p->d_jobs, p->n_jobs, p->d_segs_full ? p->d_segs_full : p->d_segs, p->d_status));
+        if (p->d_segs_full) MJ_HIP(ctx, mj::launch_gather_segments(s, p->d_segs_full, p->d_seg_gather, p->n_segs, p->d_segs));
+    }
     if (p->use_lanes) {
         if (p->d_pieces)
             MJ_HIP(ctx, mj::launch_destuff_pieces(s, p->d_blob, p->d_segs, p->d_pieces, p->n_pieces, p->d_piece_kept, p->d_stream, p->d_seg_bits));
@@ -301,6 +304,10 @@ static int recon_args(mj_plan *p, uint8_t *rgb_device, mj::ReconArgs &a) {
     a.work_counter = reinterpret_cast<uint32_t *>(p->d_job_prefix + p->n_images + 1); a.chunk_strips = p->chunk_strips;
     a.jobs_per_ticket = p->jobs_per_ticket;
     a.level_counts = reinterpret_cast<unsigned long long *>(p->d_job_prefix + p->n_images + 3);
+    a.win = p->d_win;
+    if (p->windowed) {      // the exact-order and generic kernels number the windows' MCUs
+        a.total_mcus = p->win_total_mcus; a.mcu_prefix = p->d_win_mcu_prefix; a.uniform_geometry = 0;
+    }
     return MJ_OK;
 }
 
@@ -332,7 +339,7 @@ static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
         MJ_HIP(ctx, mj::launch_reconstruct_fast(s, a, p->hmax, p->vmax, p->ncomp, p->transposed, p->d_job_prefix,
                                                p->total_jobs, p->jobs_per_image));
     }
-    if (planar) MJ_HIP(ctx, mj::launch_planes_from_interleaved(s, p->d_images, p->n_images, p->max_pixels, p->d_rgb_tmp, rgb_device));
+    if (planar) MJ_HIP(ctx, mj::launch_planes_from_interleaved(s, p->d_images, p->n_images, p->max_pixels, p->d_rgb_tmp, rgb_device, p->d_win));
     return MJ_OK;
 }
 

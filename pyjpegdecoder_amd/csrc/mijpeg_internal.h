@@ -53,6 +53,14 @@ struct DevImage {
     int64_t pix_off;                  // pixel offset (for the planes output: *ncomp int16 each)
 };
 
+// One image's window of a window plan (mj_plan_create_roi), in the ORIGINAL image's coordinates (x along the width).  The
+// image's output (DevImage::rgb_off, in the packing of the windows) is that window only; stage 2 reconstructs the MCUs of
+// the window's MCU rectangle and nothing else.
+struct DevWindow {
+    int32_t x0, y0, w, h;             // pixels: [x0, x0 + w) x [y0, y0 + h)
+    int32_t mx0, my0, mcw, mch;       // MCU rectangle: first MCU column / row, MCU columns / rows
+};
+
 // One restart segment = the unit of work of one stage-1 wavefront.
 struct DevSegment {
     int64_t begin;        // blob offset of the first entropy-coded byte
@@ -285,6 +293,9 @@ struct ReconArgs {
     int32_t chunk_strips;
     int32_t jobs_per_ticket;     // >= 1
     unsigned long long *level_counts;   // seam-output launches: blocks seen / sent to level 2 / sent to level 3 (mj_plan_idct_levels), per plan
+    // window plans (mj_plan_create_roi): per image, the window stage 2 writes (null: whole images).  The exact-order and generic
+    // kernels then number the windows' MCUs only: total_mcus and mcu_prefix count those, uniform_geometry is 0.
+    const DevWindow *win;
 };
 hipError_t launch_reconstruct(hipStream_t stream, const ReconArgs &a, int hmax, int vmax, int ncomp);
 // any sampling factors 1..4 per component (DevImage::generic): reconstruct.hip
@@ -355,8 +366,12 @@ inline int device_cus() {
     });
 }
 // MJ_LAYOUT_PLANAR_*: every image's interleaved pixels (x-major or row-major, as stage 2 wrote them) -> its three planes
+// (win: window plans — every image's window instead of the image)
 hipError_t launch_planes_from_interleaved(hipStream_t stream, const DevImage *images, int n_images, int64_t max_pixels,
-                                          const uint8_t *interleaved, uint8_t *planar);
+                                          const uint8_t *interleaved, uint8_t *planar, const DevWindow *win = nullptr);
+// window plans of MJ_FLAG_GPU_SEGMENT batches: out[i] = full[idx[i]] — the restart segments the windows need, out of the
+// list the marker scan filled, into the list stages 0 and 1 read
+hipError_t launch_gather_segments(hipStream_t stream, const DevSegment *full, const int32_t *idx, int64_t n, DevSegment *out);
 // dst[0 .. bytes) = src[0 .. bytes), sixteen bytes per lane (bytes a multiple of 16): the plain copy the rooflines are held against
 hipError_t launch_copy16(hipStream_t stream, const void *src, void *dst, int64_t bytes, int variant);     // variant 0 .. copy16_variants() - 1: launch shapes
 int copy16_variants();

@@ -246,6 +246,17 @@ struct mj_plan {
     int16_t *d_idct = nullptr;
     int32_t *d_status = nullptr;
     uint8_t *last_rgb = nullptr;    // where the most recent execute wrote
+    // window plans (mj_plan_create_roi): per image the window stage 2 writes; the exact-order and generic kernels number the
+    // windows' MCUs (win_mcu_prefix: first window MCU of every image + total)
+    bool windowed = false;
+    std::vector<mj::DevWindow> h_win;
+    mj::DevWindow *d_win = nullptr;
+    int64_t *d_win_mcu_prefix = nullptr;
+    int64_t win_total_mcus = 0;
+    // ... of MJ_FLAG_GPU_SEGMENT batches: the marker scan fills every restart segment of the images here, and the ones the
+    // windows need are gathered (d_seg_gather: their indices) into d_segs, which stages 0 and 1 read
+    mj::DevSegment *d_segs_full = nullptr;
+    int32_t *d_seg_gather = nullptr;
 };
 
 // ---- plan_tables.hip: table building (host)

@@ -75,7 +75,8 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
     return MJ_OK;
 }
 
-int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
+// mj_plan_create and mj_plan_create_roi.  roi_plan: a window plan (rois == NULL: every window is the whole image)
+static int plan_create_impl(mj_context *ctx, const mj_batch *b, const mj_roi *rois, bool roi_plan, mj_plan **out) {
     if (!ctx) return MJ_ERR_INVALID;
     if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create: NULL argument");
     *out = nullptr;
@@ -83,6 +84,8 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
     if (b->layout < MJ_LAYOUT_XMAJOR || b->layout > MJ_LAYOUT_PLANAR_ROWMAJOR)
         return fail(ctx, MJ_ERR_INVALID, "mj_plan_create: unknown layout %d", b->layout);
     if (b->n_qt <= 0 || !b->qt) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create: no quantisation tables");
+    if (roi_plan && (b->flags & (MJ_FLAG_KEEP_COEF | MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
+        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_roi: the seam outputs (MJ_FLAG_KEEP_*) are whole-image; a window plan has none");
     MJ_HIP(ctx, hipSetDevice(ctx->device));
 
     mj_plan *p = new mj_plan();
@@ -112,6 +115,12 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
     std::vector<mj::DevScanJob> jobs;      // MJ_FLAG_GPU_SEGMENT: one marker-scan job per image
     std::vector<int64_t> mcu_prefix(b->n_images + 1, 0);
     imgs.resize(b->n_images);
+    // window plans: the windows, the first window MCU of every image, and (MJ_FLAG_GPU_SEGMENT) which of the restart segments the
+    // marker scan fills the windows need
+    std::vector<mj::DevWindow> &wins = p->h_win;
+    std::vector<int64_t> win_prefix;
+    std::vector<int32_t> gather;
+    if (roi_plan) { wins.resize(b->n_images); win_prefix.assign(b->n_images + 1, 0); }
     int64_t blk = 0, mcu = 0, rgb = 0, pix = 0, ent = 0;
     p->uniform = true;
     p->lut_slots = 1;
@@ -145,6 +154,17 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
         if (d.mcu_count_h != (d.width + mw - 1) / mw || d.mcu_count_v != (d.height + mh - 1) / mh)
             return fail(ctx, MJ_ERR_INVALID, "image %d: MCU counts %dx%d do not match %dx%d with %dx%d MCUs", i,
                         d.mcu_count_h, d.mcu_count_v, d.width, d.height, mw, mh);
+        if (roi_plan) {
+            mj::DevWindow &w = wins[i];
+            if (rois) { w.x0 = rois[i].x; w.y0 = rois[i].y; w.w = rois[i].width; w.h = rois[i].height; }
+            else { w.x0 = 0; w.y0 = 0; w.w = d.width; w.h = d.height; }
+            if (w.w <= 0 || w.h <= 0 || w.x0 < 0 || w.y0 < 0 || (int64_t)w.x0 + w.w > d.width || (int64_t)w.y0 + w.h > d.height)
+                return fail(ctx, MJ_ERR_INVALID, "image %d: window (x %d, y %d, width %d, height %d) is empty or not inside the %dx%d image",
+                            i, w.x0, w.y0, w.w, w.h, d.width, d.height);
+            w.mx0 = w.x0 / mw; w.my0 = w.y0 / mh;
+            w.mcw = (w.x0 + w.w - 1) / mw - w.mx0 + 1; w.mch = (w.y0 + w.h - 1) / mh - w.my0 + 1;
+            win_prefix[i + 1] = win_prefix[i] + (int64_t)w.mcw * w.mch;
+        }
         im.width = d.width; im.height = d.height; im.ncomp = d.ncomp;
         p->max_pixels = std::max(p->max_pixels, (int64_t)d.width * d.height);
         im.hmax = hmax; im.vmax = vmax;
@@ -202,28 +222,50 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
             }
             for (int s = 0; s < (int)want; ++s) {
                 mj::DevSegment g{};
+                g.image = i;
+                g.mcu0 = d.restart_interval > 0 ? s * d.restart_interval : 0;
+                g.n_mcu = (int32_t)(d.restart_interval > 0 ? std::min<int64_t>(d.restart_interval, mcus - g.mcu0) : mcus);
+                g.last = s == (int)want - 1;
+                // a window plan decodes a restart segment only where one of its MCUs (raster order; a segment may span rows) lies in
+                // the window's MCU rectangle
+                bool need = true;
+                if (roi_plan) {
+                    const mj::DevWindow &w = wins[i];
+                    const int64_t m0 = g.mcu0, m1 = m0 + g.n_mcu, mch_ = d.mcu_count_h;
+                    need = false;
+                    for (int64_t r = std::max<int64_t>(m0 / mch_, w.my0); r <= std::min<int64_t>((m1 - 1) / mch_, w.my0 + w.mch - 1) && !need; ++r) {
+                        const int64_t c0 = std::max<int64_t>(m0, r * mch_) - r * mch_, c1 = std::min<int64_t>(m1, (r + 1) * mch_) - r * mch_;
+                        need = c0 < w.mx0 + w.mcw && c1 > w.mx0;
+                    }
+                }
                 if (gpu_seg) {
                     g.begin = b->seg_begin[d.first_segment]; g.len = 0;
+                    if (roi_plan && need) gather.push_back((int32_t)segs.size());
                 } else {
                     const int64_t sb = b->seg_begin[d.first_segment + s], se = b->seg_end[d.first_segment + s];
                     if (sb < 0 || se < sb || se > b->blob_len || se - sb > 0x7fff0000)
                         return fail(ctx, MJ_ERR_INVALID, "image %d segment %d: bad byte range [%lld, %lld)", i, s, (long long)sb, (long long)se);
                     g.begin = sb; g.len = (int32_t)(se - sb);
+                    if (!need) continue;
                     ent += se - sb;
                 }
-                g.image = i;
-                g.mcu0 = d.restart_interval > 0 ? s * d.restart_interval : 0;
-                g.n_mcu = (int32_t)(d.restart_interval > 0 ? std::min<int64_t>(d.restart_interval, mcus - g.mcu0) : mcus);
-                g.last = s == (int)want - 1;
                 segs.push_back(g);
             }
         }
         blk += mcus * im.blocks_per_mcu;
         mcu += mcus;
-        rgb += (int64_t)d.width * d.height * d.ncomp;
-        pix += (int64_t)d.width * d.height;
+        const int64_t opix = roi_plan ? (int64_t)wins[i].w * wins[i].h : (int64_t)d.width * d.height;     // (window plans: the window's)
+        rgb += opix * d.ncomp;
+        pix += opix;
     }
     mcu_prefix[b->n_images] = mcu;
+    // MJ_FLAG_GPU_SEGMENT window plans: stages 0 and 1 get the needed segments only (gathered behind the marker scan, which fills
+    // the whole list); where every segment is needed there is nothing to gather
+    std::vector<mj::DevSegment> full_segs;
+    if (roi_plan && !jobs.empty() && gather.size() < segs.size()) {
+        full_segs.swap(segs);
+        for (int32_t k : gather) segs.push_back(full_segs[(size_t)k]);
+    }
     mj::ProgScans prog_scans;      // progressive batches: plan_progressive.hip
     int rc0;
     if (prog && (rc0 = mj::plan_progressive_scans(ctx, b, p, prog_scans, ent)) != MJ_OK) return rc0;
@@ -248,9 +290,12 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
         // else equal pieces of one.  Jobs are numbered image by image; the kernel's ticket counter is the (zero) word behind
         // the prefix.
         const int tm = p->generic ? 1 : mj::fast_tile_mcus(p->hmax, p->vmax, p->ncomp, p->transposed);
+        // (window plans: strips run down the MCU columns of the windows' MCU rectangles)
+        auto kcols = [&](int i) { return roi_plan ? (p->transposed ? wins[i].mch : wins[i].mcw) : (p->transposed ? imgs[i].mcu_count_v : imgs[i].mcu_count_h); };
+        auto krows = [&](int i) { return roi_plan ? (p->transposed ? wins[i].mcw : wins[i].mch) : (p->transposed ? imgs[i].mcu_count_h : imgs[i].mcu_count_v); };
         int max_spc = 1;
         for (int i = 0; i < b->n_images; ++i) {
-            const int rows = p->transposed ? imgs[i].mcu_count_h : imgs[i].mcu_count_v;
+            const int rows = krows(i);
             max_spc = std::max(max_spc, (rows + tm - 1) / tm);
         }
         const int pieces_max = (max_spc + 23) / 24;
@@ -259,8 +304,8 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
         std::vector<int64_t> tp(b->n_images + 1, 0);
         for (int i = 0; i < b->n_images; ++i) {
             // strips run down the MCU columns of the image the kernel sees (the transposed one for row-major plans)
-            const int cols = p->transposed ? imgs[i].mcu_count_v : imgs[i].mcu_count_h;
-            const int rows = p->transposed ? imgs[i].mcu_count_h : imgs[i].mcu_count_v;
+            const int cols = kcols(i);
+            const int rows = krows(i);
             const int spc = (rows + tm - 1) / tm;
             tp[i + 1] = tp[i] + (int64_t)cols * ((spc + p->chunk_strips - 1) / p->chunk_strips);
         }
@@ -535,6 +580,7 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
             int want_cons = 8, want_cons_x = 6;
             bool allow = true;
             if (const char *e = mj::opt("MJ_FUSED")) allow = atoi(e) != 0;
+            if (roi_plan) allow = false;             // (window plans: stage 0, stage 1 and the window stage 2)
             if (const char *e = mj::opt("MJ_FUSED_CONSUMERS")) want_cons = want_cons_x = atoi(e);
             int luma13 = -1;                                     // MJ_FUSED_LUMA13: 0 / 1 overrides which form keeps component 0's table at 13 bits
             if (const char *e = mj::opt("MJ_FUSED_LUMA13")) luma13 = atoi(e);
@@ -604,6 +650,10 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
             }
         }
         if ((rc = upload(ctx, &p->d_segs, segs.data(), segs.size())) != MJ_OK) return rc;
+        if (!full_segs.empty()) {
+            if ((rc = upload(ctx, &p->d_segs_full, full_segs.data(), full_segs.size())) != MJ_OK) return rc;
+            if ((rc = upload(ctx, &p->d_seg_gather, gather.data(), gather.size())) != MJ_OK) return rc;
+        }
         if (!jobs.empty()) {
             if (prog) return fail(ctx, MJ_ERR_INVALID, "MJ_FLAG_GPU_SEGMENT is for baseline batches");
             if ((rc = upload(ctx, &p->d_jobs, jobs.data(), jobs.size())) != MJ_OK) return rc;
@@ -651,12 +701,24 @@ int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) {
     // plan's first use waits (on the host) for this event, or the tail of the 6 GB clear could land after the first
     // blocks the first execute writes.  Not waiting here lets a serving loop create the next batch's plan while this
     // context's stream is still busy with the current batch.
+    if (roi_plan) {
+        p->windowed = true;
+        p->win_total_mcus = win_prefix[b->n_images];
+        if ((rc = upload(ctx, &p->d_win, wins.data(), wins.size())) != MJ_OK) return rc;
+        if ((rc = upload(ctx, &p->d_win_mcu_prefix, win_prefix.data(), win_prefix.size())) != MJ_OK) return rc;
+    }
     MJ_HIP(ctx, hipEventCreateWithFlags(&p->ready, hipEventDisableTiming));
     MJ_HIP(ctx, hipEventRecord(p->ready, ctx->setup_stream));
     MJ_HIP(ctx, hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
     guard.p = nullptr;
     *out = p;
     return MJ_OK;
+}
+
+int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) { return plan_create_impl(ctx, b, nullptr, false, out); }
+
+int mj_plan_create_roi(mj_context *ctx, const mj_batch *b, const mj_roi *rois, mj_plan **out) {
+    return plan_create_impl(ctx, b, rois, true, out);
 }
 
 }  // extern "C"

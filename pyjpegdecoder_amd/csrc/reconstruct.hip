@@ -131,7 +131,12 @@ __global__ __launch_bounds__(256) void k_reconstruct(ReconArgs a) {
         }
         const DevImage *im = a.images + img;
         const int W = im->width, H = im->height;
-        const int mcu_y = m / im->mcu_count_h, mcu_x = m - mcu_y * im->mcu_count_h;
+        int mcu_y = m / im->mcu_count_h, mcu_x = m - mcu_y * im->mcu_count_h;
+        const DevWindow *wn = a.win ? a.win + img : nullptr;     // window plans: m counts the window's MCUs
+        if (wn) {
+            mcu_y = wn->my0 + m / wn->mcw; mcu_x = wn->mx0 + (m - (m / wn->mcw) * wn->mcw);
+            m = mcu_y * im->mcu_count_h + mcu_x;
+        }
         const int64_t blk0 = im->block_off + (int64_t)m * G::NB;
         const int16_t *cp = a.coef + blk0 * 64 + src_of_lane;
 
@@ -234,6 +239,19 @@ __global__ __launch_bounds__(256) void k_reconstruct(ReconArgs a) {
         __builtin_amdgcn_wave_barrier();   // all reads of s_mcu done before the next pass overwrites it
 
         // ---- store
+        if (wn) {       // window plans: the pixels inside the window, at their place in it
+            const int ww = wn->w, wh = wn->h;
+#pragma unroll
+            for (int j = 0; j < G::PPL; ++j) {
+                const int x = mcu_x * G::MW + px[j] - wn->x0, y = mcu_y * G::MH + py[j] - wn->y0;
+                if ((unsigned)x < (unsigned)ww && (unsigned)y < (unsigned)wh) {
+                    unsigned char *d = a.rgb + im->rgb_off + (LAYOUT == MJ_LAYOUT_XMAJOR ? (int64_t)x * wh + y : (int64_t)y * ww + x) * NC;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) d[c] = bytes[j * NC + c];
+                }
+            }
+            continue;
+        }
         const int gx0 = mcu_x * G::MW + px[0], gy0 = mcu_y * G::MH + py[0];
         int64_t off0;
         bool full;
@@ -336,7 +354,14 @@ __global__ __launch_bounds__(256) void k_reconstruct_generic(ReconArgs a) {
         const DevImage *im = a.images + img;
         const int W = im->width, H = im->height, bpm = im->blocks_per_mcu;
         const int MW = 8 * im->hmax, MH = 8 * im->vmax;
-        const int mcu_y = m / im->mcu_count_h, mcu_x = m - mcu_y * im->mcu_count_h;
+        int mcu_y = m / im->mcu_count_h, mcu_x = m - mcu_y * im->mcu_count_h;
+        const DevWindow *wn = a.win ? a.win + img : nullptr;     // window plans: m counts the window's MCUs
+        int wx0 = 0, wy0 = 0, ww = W, wh = H;
+        if (wn) {
+            mcu_y = wn->my0 + m / wn->mcw; mcu_x = wn->mx0 + (m - (m / wn->mcw) * wn->mcw);
+            m = mcu_y * im->mcu_count_h + mcu_x;
+            wx0 = wn->x0; wy0 = wn->y0; ww = wn->w; wh = wn->h;
+        }
         const int64_t blk0 = im->block_off + (int64_t)m * bpm;
         __builtin_amdgcn_wave_barrier();   // the previous pass has read its planes
         for (int b = 0; b < bpm; ++b) {
@@ -377,6 +402,7 @@ __global__ __launch_bounds__(256) void k_reconstruct_generic(ReconArgs a) {
             else                            { y = p / MW; x = p - y * MW; }
             const int gx = mcu_x * MW + x, gy = mcu_y * MH + y;
             if (gx >= W || gy >= H) continue;
+            if ((unsigned)(gx - wx0) >= (unsigned)ww || (unsigned)(gy - wy0) >= (unsigned)wh) continue;
             int v3[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c)
@@ -387,7 +413,7 @@ __global__ __launch_bounds__(256) void k_reconstruct_generic(ReconArgs a) {
             }
             int R, Gc, B;
             ycc_to_rgb(v3[0], v3[1], v3[2], R, Gc, B);
-            unsigned char *dst = a.rgb + im->rgb_off + (LAYOUT == MJ_LAYOUT_XMAJOR ? ((int64_t)gx * H + gy) : ((int64_t)gy * W + gx)) * 3;
+            unsigned char *dst = a.rgb + im->rgb_off + (LAYOUT == MJ_LAYOUT_XMAJOR ? ((int64_t)(gx - wx0) * wh + (gy - wy0)) : ((int64_t)(gy - wy0) * ww + (gx - wx0))) * 3;
             dst[0] = (unsigned char)R; dst[1] = (unsigned char)Gc; dst[2] = (unsigned char)B;
         }
     }
@@ -418,9 +444,9 @@ hipError_t launch_reconstruct(hipStream_t stream, const ReconArgs &a, int hmax, 
 // one dword to each plane (an image's pixel count need not be a multiple of four, nor its offset of four bytes: the
 // ragged ends go byte by byte).
 __global__ __launch_bounds__(256) void k_planes_from_interleaved(const DevImage *__restrict__ images, const uint8_t *__restrict__ src,
-                                                                 uint8_t *__restrict__ dst) {
+                                                                 uint8_t *__restrict__ dst, const DevWindow *__restrict__ win) {
     const DevImage im = images[blockIdx.y];
-    const int64_t n = (int64_t)im.width * im.height;
+    const int64_t n = win ? (int64_t)win[blockIdx.y].w * win[blockIdx.y].h : (int64_t)im.width * im.height;     // (window plans: the window)
     const int64_t q = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;        // first of this thread's four pixels
     if (q >= n) return;
     const uint8_t *s = src + im.rgb_off + 3 * q;
@@ -442,12 +468,12 @@ __global__ __launch_bounds__(256) void k_planes_from_interleaved(const DevImage 
 }
 
 hipError_t launch_planes_from_interleaved(hipStream_t stream, const DevImage *images, int n_images, int64_t max_pixels,
-                                          const uint8_t *interleaved, uint8_t *planar) {
+                                          const uint8_t *interleaved, uint8_t *planar, const DevWindow *win) {
     if (n_images == 0 || max_pixels == 0) return hipSuccess;
     for (int i0 = 0; i0 < n_images; i0 += 65535) {          // grid.y limit
         const int ny = n_images - i0 < 65535 ? n_images - i0 : 65535;
         hipLaunchKernelGGL(k_planes_from_interleaved, dim3((unsigned)((max_pixels + 1023) / 1024), (unsigned)ny), dim3(256), 0, stream,
-                           images + i0, interleaved, planar);
+                           images + i0, interleaved, planar, win ? win + i0 : nullptr);
     }
     return hipGetLastError();
 }

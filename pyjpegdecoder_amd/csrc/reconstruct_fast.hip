@@ -44,7 +44,8 @@ using namespace rfast;
 
 // T: the kernel works on the transposed image (x' = y, y' = x) — its x-major output is the row-major image of the
 // original; HS/VS are then the transposed sampling factors, coefficient blocks and tables are stored [u][v].
-template <int HS, int VS, int NC, bool SEAMS, bool T>
+// WIN: a window plan's stage 2 (a.win: per image, the window it writes; strips_worker says how)
+template <int HS, int VS, int NC, bool SEAMS, bool T, bool WIN = false>
 __global__ __launch_bounds__(256, (HS == 4 || VS == 4) ? 2 : 3) void k_reconstruct_fast(ReconArgs a, const int64_t *__restrict__ job_prefix,
                                                           int64_t total_jobs, int jobs_per_image) {
     using G = FGeo<HS, VS, NC>;
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256, (HS == 4 || VS == 4) ? 2 : 3) void k_reconstru
     src.n_tickets = ((uint32_t)total_jobs + src.jpt - 1) / src.jpt;
     src.last_ticket = src.n_tickets + gridDim.x * 4u - 1u;
     src.lane = lane;
-    strips_worker<HS, VS, NC, SEAMS, T>(a, job_prefix, total_jobs, jobs_per_image, smem + wave * G::WAVE_BYTES,
+    strips_worker<HS, VS, NC, SEAMS, T, TicketSource, WIN>(a, job_prefix, total_jobs, jobs_per_image, smem + wave * G::WAVE_BYTES,
                                         reinterpret_cast<const float4 *>(smem + 4 * G::WAVE_BYTES), lane, (int)blockIdx.x, wave, src);
 }
 
@@ -95,6 +96,7 @@ static hipError_t launch_fast_t(hipStream_t stream, const ReconArgs &a, const in
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), G::LDS_BYTES, stream, a, job_prefix, total_jobs, jobs_per_image);
     };
     if (a.planes || a.idct_out) launch(k_reconstruct_fast<HS, VS, NC, true, T>);
+    else if (a.win) launch(k_reconstruct_fast<HS, VS, NC, false, T, true>);       // (window plans have no seam outputs)
     else launch(k_reconstruct_fast<HS, VS, NC, false, T>);
     return hipGetLastError();
 }

@@ -98,6 +98,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // pixel stores — a vector load at the top of the strip loop made every strip wait for the previous strip's stores.
 typedef const DevImage __attribute__((address_space(4))) *ConstImage;
 __device__ __forceinline__ ConstImage cimg(const DevImage *p) { return (ConstImage)(uintptr_t)p; }
+typedef const DevWindow __attribute__((address_space(4))) *ConstWindow;      // (the same for a window plan's window records)
+__device__ __forceinline__ ConstWindow cwin(const DevWindow *p) { return (ConstWindow)(uintptr_t)p; }
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));      // 16-byte store at a dword-aligned address
 // two coefficients at once: the low 16 bits of a 16x16 product are exactly numpy's int16 * int16 wrap (:869)
 __device__ __forceinline__ uint32_t deq2(uint32_t c2, uint32_t q2) {
@@ -336,10 +338,15 @@ __device__ __forceinline__ void fill_weights(float4 *wt, int tid, int nthreads) 
     }
 }
 
-template <int HS, int VS, int NC, bool SEAMS, bool T, class Src>
+// WIN: a window plan (mj_plan_create_roi).  The jobs are strips down the MCU columns of each image's window (a.win, in the
+// kernel's — possibly transposed — geometry), and what lies outside the window, inside the first and last MCU column and row,
+// is not stored: its pieces go to the dump line like the pieces past the right and bottom image edges.  Output columns are
+// the window's (a.win[i].h pixels, or w when transposed), packed window after window.
+template <int HS, int VS, int NC, bool SEAMS, bool T, class Src, bool WIN = false>
 __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t *__restrict__ job_prefix, const int64_t total_jobs, const int jobs_per_image,
                                               unsigned char *wave_lds, const float4 *s_wts, const int lane, const int dump_slot, const int wave_in_wg, Src &src) {
     using G = FGeo<HS, VS, NC>;
+    static_assert(!(WIN && SEAMS), "the seam outputs are whole-image: window plans have none");
     int16_t *s_strip = reinterpret_cast<int16_t *>(wave_lds);
     double *scr = reinterpret_cast<double *>(wave_lds + G::STRIP_BYTES) + (lane >> 3) * 72;      // level 2
     // level 1's 8x8 transpose: element (x, v) of group g at float g*124 + x*16 + v — the ds_read_b128 of lane x is
@@ -359,11 +366,11 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
         const DevImage *im;
         const int16_t *cfirst;           // coefficients of the job's first MCU row, this MCU column
         int row_elems;                   // int16 elements from one MCU row to the next
-        int mcu_x, y_first, n_strips, mcv;
+        int mcu_x, y_first, n_strips, mcv;   // (WIN: mcv = one past the window's last MCU row)
     };
     auto job_of = [&](uint32_t jb) -> Job {
         uint32_t img, r;
-        if (a.uniform_geometry) {
+        if (!WIN && a.uniform_geometry) {
             img = jb / (uint32_t)jobs_per_image;
             r = jb - img * (uint32_t)jobs_per_image;
         } else {
@@ -381,13 +388,20 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
         jo.im = a.images + img;
         // MCU grid of the (possibly transposed) image: mch columns, mcv rows
         const int mch = T ? cimg(jo.im)->mcu_count_v : cimg(jo.im)->mcu_count_h, mcv = T ? cimg(jo.im)->mcu_count_h : cimg(jo.im)->mcu_count_v;
-        const uint32_t spc = (uint32_t)(mcv + G::TMW - 1) / G::TMW;     // strips per MCU column
+        // (WIN: the window's MCU rectangle — its columns kx0.., its rows ky0 .. ky0 + krows - 1)
+        int kx0 = 0, ky0 = 0, krows = mcv;
+        if constexpr (WIN) {
+            const ConstWindow w = cwin(a.win + img);
+            kx0 = T ? w->my0 : w->mx0; ky0 = T ? w->mx0 : w->my0; krows = T ? w->mcw : w->mch;
+        }
+        const uint32_t spc = (uint32_t)(krows + G::TMW - 1) / G::TMW;   // strips per MCU column
         const uint32_t S = (uint32_t)a.chunk_strips, pieces = (spc + S - 1) / S;
-        jo.mcv = mcv;
+        jo.mcv = ky0 + krows;
         jo.mcu_x = __builtin_amdgcn_readfirstlane((int)(r / pieces));
         const uint32_t s0 = (r - (uint32_t)jo.mcu_x * pieces) * S;      // first strip of the piece within its column
+        jo.mcu_x += kx0;
         jo.n_strips = (int)min(S, spc - s0);
-        jo.y_first = (int)s0 * G::TMW;
+        jo.y_first = ky0 + (int)s0 * G::TMW;
         // coefficient blocks are in the ORIGINAL image's MCU raster: stepping down the strip moves one MCU row of the
         // original (or, transposed, one MCU to the right)
         if constexpr (T) {
@@ -465,6 +479,13 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
         const DevImage *im_g = jo.im;
         const ConstImage im = cimg(im_g);
         const int W = T ? im->height : im->width, H = T ? im->width : im->height;
+        // WIN: the window in the kernel's geometry, [wx0, wxe) x [wy0, wye); its columns are wh pixels tall
+        int wx0 = 0, wy0 = 0, wxe = W, wye = H;
+        if constexpr (WIN) {
+            const ConstWindow w = cwin(a.win + (im_g - a.images));
+            wx0 = T ? w->y0 : w->x0; wy0 = T ? w->x0 : w->y0;
+            wxe = wx0 + (T ? w->h : w->w); wye = wy0 + (T ? w->w : w->h);
+        }
         const int mch_o = im->mcu_count_h;              // MCUs per row of the ORIGINAL image (coefficient raster)
         const int mcv_k = jo.mcv;                        // MCU rows of the image the kernel sees
         const int mcu_x = jo.mcu_x;
@@ -492,9 +513,10 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
         const int16_t *cptr = jo.cfirst;            // wave-uniform: the current strip's first MCU row
         int y_first = jo.y_first;
         const int64_t rgb_off = im->rgb_off;
-        const int hnc_i = H * NC;
-        // first byte of this MCU column's pixel columns in the image
-        unsigned char *const col_dst = a.rgb + rgb_off + (int64_t)(mcu_x * G::MW) * hnc_i;
+        const int hnc_i = (WIN ? wye - wy0 : H) * NC;
+        // first byte of this MCU column's pixel columns in the image (WIN: where they would lie in the window's output — in
+        // front of it for columns left of the window, which are never stored)
+        unsigned char *const col_dst = a.rgb + rgb_off + (int64_t)(mcu_x * G::MW - wx0) * hnc_i;
       for (uint32_t si = 0;; ++si) {
         const int n_valid = min(G::TMW, mcv_k - y_first);
         // first block of strip MCU k in the coefficient store
@@ -861,7 +883,7 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
                     }
                 }
                 }   // have
-                const bool active = have && gx < W;
+                const bool active = have && gx < wxe && (!WIN || gx >= wx0);
                 act_m |= active ? 1 << sv : 0;
                 slow_m |= slow ? 1 << sv : 0;
                 rg_m |= rg << (RGB * sv);
@@ -908,7 +930,10 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
                 // predecessor with the same values — so the store stays one 16-byte instruction per piece)
                 constexpr int RUN = G::TMW * NBYTES, NPIECE = G::MW * RUN / 16;
                 const int runv = min(RUN, (H - y_first * G::MH) * NC);
-                const bool staged = runv >= 16 && (hnc_i & 3) == 0 && (rgb_off & 3) == 0 && __ballot((act_m & slow_m) != 0) == 0;
+                // WIN: bytes [rlo, rhi) of a column run lie inside the window; dword-aligned wherever the window's top row is
+                const int rlo = WIN ? max(0, wy0 - y_first * G::MH) * NC : 0, rhi = WIN ? min(RUN, (wye - y_first * G::MH) * NC) : runv;
+                const bool staged = WIN ? rhi - rlo >= 16 && ((hnc_i | (int)rgb_off | wy0 * NC) & 3) == 0 && __ballot((act_m & slow_m) != 0) == 0
+                                        : runv >= 16 && (hnc_i & 3) == 0 && (rgb_off & 3) == 0 && __ballot((act_m & slow_m) != 0) == 0;
                 {
                     static_assert(RUN % 16 == 0 && NBYTES % 8 == 0, "column runs are whole 16-byte pieces");
                     if constexpr (NC == 3) {
@@ -929,8 +954,9 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
                     // mcu_x*MW + c < W), bytes past the bottom edge, piece numbers past the last — become copies of an
                     // existing piece (the same bytes to the same address twice is harmless); a strip that takes the per-lane
                     // stores below sends its NT instructions to this workgroup's dump line instead.
-                    const int ncol = min(G::MW, W - mcu_x * G::MW);
-                    unsigned char *sbase = col_dst + y_first * (G::MH * NC);
+                    const int ncol = min(G::MW, (WIN ? wxe : W) - mcu_x * G::MW);
+                    const int col0 = WIN ? max(0, wx0 - mcu_x * G::MW) : 0;     // (WIN: the window's first column in this MCU column)
+                    unsigned char *sbase = col_dst + (WIN ? (y_first * G::MH - wy0) * NC : y_first * (G::MH * NC));
                     // (the piece geometry is recomputed from the lane number every strip: as loop invariants the compiler
                     // keeps them in registers it does not have, and a spill reload is a vector-memory load that waits —
                     // vmcnt is in order — for the coefficient prefetch and for the previous piece's store)
@@ -941,7 +967,7 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
                     uint4 pv[NT];
                     uint32_t doff[NT];                    // byte offset of piece t from sbase
                     const uint32_t hnc = (uint32_t)hnc_i;
-                    if (runv == RUN && ncol == G::MW) {   // whole runs (wave-uniform; LDS reads may sit behind branches, stores may not)
+                    if (WIN ? rlo == 0 && rhi == RUN && col0 == 0 && ncol == G::MW : runv == RUN && ncol == G::MW) {   // whole runs (wave-uniform; LDS reads may sit behind branches, stores may not)
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {    // all reads first: one LDS round trip, not one per store
                             const int pce = (t * 64 + lane_o) % NPIECE;
@@ -953,8 +979,9 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {
                             const int pce = (t * 64 + lane_o) % NPIECE;
-                            const int c = min((pce * 16) / RUN, ncol - 1);
-                            const int o = min((pce * 16) % RUN, runv - 16);       // dword aligned: runv is a multiple of 4 here
+                            const int c = WIN ? min(max((pce * 16) / RUN, col0), ncol - 1) : min((pce * 16) / RUN, ncol - 1);
+                            const int o = WIN ? min(max((pce * 16) % RUN, rlo), rhi - 16)
+                                              : min((pce * 16) % RUN, runv - 16);       // dword aligned: runv is a multiple of 4 here
                             doff[t] = (uint32_t)c * hnc + (uint32_t)o;
                             const u32x4_a4 v = *reinterpret_cast<const u32x4_a4 *>(s_out + c * RUN + o);
                             pv[t] = make_uint4(v.x, v.y, v.z, v.w);
@@ -980,7 +1007,21 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
                     // the per-lane way (rare: a lane that fp32 cannot decide, an image whose columns are not dword aligned): every
                     // MCU of the lane's turns from its staged bytes — or, where those are not final, through the exact routine
 #pragma unroll
-                    for (int sv = 0; sv < G::SV; ++sv) {
+                    for (int sv = 0; sv < G::SV && WIN; ++sv) {
+                        // WIN: the window's rows of the lane's MCU, byte by byte from its staged run — made exact there first where
+                        // the fast bytes are not final
+                        if (!((act_m >> sv) & 1)) continue;
+                        const int pk = pk0 + sv * G::TML, gy0 = (y_first + pk) * G::MH;
+                        const int r0 = max(0, wy0 - gy0) * NC, r1 = min(G::MH, wye - gy0) * NC;
+                        unsigned char *mine = s_out + (px * G::TMW + pk) * NBYTES;
+                        if (((slow_m >> sv) & 1) || ((rg_m >> (RGB * sv)) & ((1 << RGB) - 1)) != 0)
+                            pixel_run_exact<HS, VS, NC, T>(s_strip + pk * G::MCU_STRIDE, px, mine, G::MH, nullptr, 0);
+                        unsigned char *dst = col_dst + (int64_t)px * hnc_i + (gy0 - wy0) * NC;
+#pragma unroll 1
+                        for (int i = r0; i < r1; ++i) dst[i] = mine[i];
+                    }
+#pragma unroll
+                    for (int sv = 0; sv < G::SV && !WIN; ++sv) {
                         if (!((act_m >> sv) & 1)) continue;
                         const int pk = pk0 + sv * G::TML, gy0 = (y_first + pk) * G::MH, nrows = min(G::MH, H - gy0);
                         unsigned char *dst = col_dst + (int64_t)px * hnc_i + gy0 * NC;

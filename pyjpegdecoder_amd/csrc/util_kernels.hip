@@ -76,4 +76,21 @@ hipError_t launch_permute_blocks(hipStream_t stream, const int16_t *src, int16_t
     hipLaunchKernelGGL(k_permute_blocks, dim3(blocks), dim3(256), 0, stream, src, dst, n_blocks, to_natural, transposed);
     return hipGetLastError();
 }
+// window plans of MJ_FLAG_GPU_SEGMENT batches: the needed restart segments out of the list the marker scan filled
+// (one thread per needed segment; DevSegment is 32 bytes: two 16-byte moves)
+__global__ __launch_bounds__(256) void k_gather_segments(const DevSegment *__restrict__ full, const int32_t *__restrict__ idx, int64_t n,
+                                                         DevSegment *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    static_assert(sizeof(DevSegment) == 32, "DevSegment layout");
+    const uint4 *s = reinterpret_cast<const uint4 *>(full + idx[i]);
+    uint4 *d = reinterpret_cast<uint4 *>(out + i);
+    d[0] = s[0];
+    d[1] = s[1];
+}
+hipError_t launch_gather_segments(hipStream_t stream, const DevSegment *full, const int32_t *idx, int64_t n, DevSegment *out) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_gather_segments, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, full, idx, n, out);
+    return hipGetLastError();
+}
 }  // namespace mj
