@@ -207,6 +207,23 @@ typedef struct {
     int32_t x, y, width, height;
 } mj_roi;
 int mj_plan_create_roi(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, mj_plan **out);
+/* Decode to a fixed size: a window plan (rois != NULL, as mj_plan_create_roi) or a plan of whole images (rois == NULL, as
+ * mj_plan_create) whose output is every image — or window — resized to out_width x out_height: ONE dense array of n_slots images
+ * in the plan's layout,
+ *   MJ_LAYOUT_XMAJOR (n_slots, out_width, out_height, C)    MJ_LAYOUT_PLANAR_XMAJOR   (n_slots, C, out_width, out_height)
+ *   MJ_LAYOUT_ROWMAJOR (n_slots, out_height, out_width, C)  MJ_LAYOUT_PLANAR_ROWMAJOR (n_slots, C, out_height, out_width)
+ * (C = the batch's component count), and mj_plan_info.rgb_bytes = n_slots * out_width * out_height * C is that array's size.
+ * slots: host, n_images entries, image k goes to slot slots[k] < n_slots — several plans can fill one array this way (files of
+ * several kinds are one plan per kind); slots the plan does not name are not touched.  NULL: slot k, and n_slots is ignored.
+ * The resize is Pillow's Image.resize((out_width, out_height), Image.BILINEAR) of the row-major window, byte for byte: integer
+ * taps from triangle weights whose support grows with the scale when shrinking (antialiased), along the width first, then the
+ * height, with an 8-bit image in between (mj_host_resize_table; csrc/resize.hip).  mj_plan_execute runs stage 1, stage 2 — into
+ * a buffer of the files' own sizes that the plan owns — and the resize as its last launch; mj_plan_execute_stage2 includes it.
+ * MJ_ERR_INVALID: a size outside 1..65535, a slot outside n_slots, MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT, and whatever
+ * mj_plan_create_roi refuses; MJ_ERR_UNSUPPORTED: a shrink so strong that one pixel's taps do not fit a workgroup's LDS, or
+ * more output tiles than one launch takes (about 6.8e10: split the batch). */
+int mj_plan_create_resized(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                           const int32_t *slots, int32_t n_slots, mj_plan **out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -295,6 +312,9 @@ int mj_debug_prog_split(int32_t mode, int32_t n_images, int32_t n_bands, int32_t
  * show (a store that still holds the previous execute's blocks of the same files hides exactly that). */
 int mj_plan_fill_coef(mj_plan *plan, int byte_value);
 
+/* Test hook: every byte of a resized plan's intermediate buffer (the un-resized pixels) := byte_value (synchronous). */
+int mj_plan_fill_source(mj_plan *plan, int byte_value);
+
 /* ---- one-shot conveniences ----------------------------------------------------------------------- */
 /* create + execute + sync + read + destroy; rgb_out/status_out host, coef_out may be NULL. */
 int mj_decode_baseline_batch(mj_context *ctx, const mj_batch *batch, uint8_t *rgb_out, int16_t *coef_out,
@@ -310,6 +330,10 @@ int mj_plan_time_stages(mj_plan *plan, int iters, uint8_t *rgb_device, float *st
  * runs in front of it (marker scan with MJ_FLAG_GPU_SEGMENT, stage 0), main_ms = the fused launch.  Any other plan: the two
  * stages as mj_plan_time_stages reports them (front = stage 0+1, main = stage 2). */
 int mj_plan_time_execute(mj_plan *plan, int iters, uint8_t *rgb_device, float *front_ms, float *main_ms);
+
+/* A resized plan's resize launch alone (after an execute: it reads what stage 2 left), `iters` times into rgb_device (NULL: where the
+ * latest execute wrote): ms per launch, and the bytes of un-resized pixels it reads (written bytes: mj_plan_info.rgb_bytes). */
+int mj_plan_time_resize(mj_plan *plan, int iters, uint8_t *rgb_device, float *ms, int64_t *source_bytes);
 
 /* Placement tuning of a plan that is executed many times into ONE output buffer (a service's output slot, a benchmark's step).
  * Where the plan's coefficient store lies relative to that buffer — physically: nothing the virtual addresses show — puts the
@@ -382,6 +406,12 @@ int mj_plan_idct_levels(mj_plan *plan, uint64_t counts[3]);
 /* The IDCT table as the library builds it: 4096 doubles laid out [u*8+v][x*8+y], the transpose of the
  * reference's InverseDCT.idct_table (:1541-1553).  Lets CPU tests pin it bit-for-bit. */
 void mj_host_idct_table(double *tt);
+
+/* The tap table of one axis of a resized plan, as the library builds it (in_size -> out_size entries): output index i is
+ * clip8((2^21 + sum over t < count[i] of taps[i * taps_stride + t] * in[xmin[i] + t]) >> 22); taps behind count[i] are zero.
+ * *ksize = taps a row can hold at most (taps_stride must be at least that).  xmin = count = taps = NULL: only *ksize. */
+int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride,
+                         int32_t *ksize);
 
 /* ---- host front end (no GPU work, no context) -------------------------------------------------------
  * Header parse + batch assembly for the everyday case, on host threads: what pyjpegdecoder_amd/_parse.py

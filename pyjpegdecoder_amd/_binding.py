@@ -29,6 +29,7 @@ EXPORTS = (
     "mj_plan_device_buffers", "mj_plan_read", "mj_plan_write_coef", "mj_plan_fill_coef",
     "mj_decode_baseline_batch", "mj_idct_batch", "mj_plan_time_stages", "mj_plan_time_execute", "mj_plan_idct_levels", "mj_host_idct_table", "mj_host_assemble", "mj_plan_stage1_form", "mj_set_option", "mj_get_option", "mj_debug_stage1_form", "mj_debug_fused_shape", "mj_debug_count_tables",
     "mj_device_copy_rate", "mj_context_launch_clock", "mj_debug_prog_split", "mj_debug_fused_applies", "mj_plan_tune_placement",
+    "mj_plan_create_resized", "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -117,6 +118,10 @@ def load_library():
     L.mj_context_wait_event.argtypes = [vp, vp]
     L.mj_plan_create.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(vp)]
     L.mj_plan_create_roi.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), ctypes.POINTER(vp)]
+    L.mj_plan_create_resized.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(vp)]
+    L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
+    L.mj_plan_time_resize.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
+    L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
     L.mj_plan_get_info.argtypes = [vp, ctypes.POINTER(PlanInfoC)]
@@ -224,6 +229,20 @@ def prog_split_rule(n_images, scans, mode=1, n_bands=68, wave_slots=0, parts=0):
     return out[:n].astype(bool).tolist(), int(po.value)
 
 
+def resize_table(in_size: int, out_size: int):
+    """mj_host_resize_table (host only): (xmin[out_size], count[out_size], taps[out_size, ksize]) int32 — one axis of the
+    resize of ``decode(..., size=...)`` as the library builds it (tools/resize_model.py: axis_table)."""
+    L = load_library()
+    ks = ctypes.c_int32()
+    if L.mj_host_resize_table(in_size, out_size, None, None, None, 0, ctypes.byref(ks)) != MJ_OK:
+        raise ValueError("mj_host_resize_table: sizes must be 1..65535")
+    xmin, count = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
+    taps = np.zeros((out_size, ks.value), dtype=np.int32)
+    if L.mj_host_resize_table(in_size, out_size, _ptr(xmin), _ptr(count), _ptr(taps), ks.value, ctypes.byref(ks)) != MJ_OK:
+        raise ValueError("mj_host_resize_table: bad arguments")
+    return xmin, count, taps
+
+
 class UnknownOption(ValueError):
     """mj_set_option / mj_get_option: no such option in this library."""
 
@@ -303,16 +322,27 @@ class Context:
 
 class Plan:
     """mj_plan over a prepared batch (see batch.PreparedBatch).  rois: None, or one (x, y, width, height) per image —
-    a window plan (mj_plan_create_roi) whose output for every image is that window."""
+    a window plan (mj_plan_create_roi) whose output for every image is that window.  size: None, or (width, height) — a
+    resized plan (mj_plan_create_resized) whose output is one dense array of every image (or window) at that size; slots:
+    with size, (slot of every image, slots of the array) when the plan fills part of a larger array."""
 
-    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None):
+    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
-        if rois is None:
+        arr = None
+        if rois is not None:
+            arr = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in r)) for r in rois])
+        if size is not None:
+            sl, n_slots = None, 0
+            if slots is not None:
+                sl = np.ascontiguousarray(slots[0], dtype=np.int32)
+                n_slots = int(slots[1])
+            ctx.check(ctx.lib.mj_plan_create_resized(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
+                                                     ctypes.byref(h)))
+        elif rois is None:
             ctx.check(ctx.lib.mj_plan_create(ctx.handle, ctypes.byref(batch_c), ctypes.byref(h)))
         else:
-            arr = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in r)) for r in rois])
             ctx.check(ctx.lib.mj_plan_create_roi(ctx.handle, ctypes.byref(batch_c), arr, ctypes.byref(h)))
         self.handle = h
         info = PlanInfoC()
@@ -343,6 +373,16 @@ class Plan:
     def fill_coef(self, byte_value: int):
         """Test hook (mj_plan_fill_coef): poison the coefficient store."""
         self.ctx.check(self.ctx.lib.mj_plan_fill_coef(self.handle, int(byte_value)))
+
+    def fill_source(self, byte_value: int):
+        """Test hook (mj_plan_fill_source): poison a resized plan's intermediate buffer."""
+        self.ctx.check(self.ctx.lib.mj_plan_fill_source(self.handle, int(byte_value)))
+
+    def time_resize(self, iters: int = 10, rgb_device: int = 0):
+        """(ms per resize launch, bytes of un-resized pixels it reads) of a resized plan that has been executed."""
+        ms, nb = ctypes.c_float(), ctypes.c_int64()
+        self.ctx.check(self.ctx.lib.mj_plan_time_resize(self.handle, iters, rgb_device or None, ctypes.byref(ms), ctypes.byref(nb)))
+        return ms.value, nb.value
 
     def read(self, rgb=True, coef=False, planes=False, idct=False):
         out = {}

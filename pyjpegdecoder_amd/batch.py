@@ -336,6 +336,25 @@ def prepare_batch_native(files: Sequence[bytes], layout: int = B.MJ_LAYOUT_XMAJO
                          layout=layout, flags=flags | B.MJ_FLAG_GPU_SEGMENT, shapes=shapes)
 
 
+def _image_info(raw: bytes) -> Tuple[int, int, int]:
+    """:func:`_image_dims` plus the frame's component count: (width, height, components), for a decode to a fixed size."""
+    pos, n = 2, len(raw)
+    if raw[:2] == b"\xFF\xD8":
+        while pos + 10 <= n and raw[pos] == 0xFF:
+            m = raw[pos + 1]
+            if m == 0xFF:
+                pos += 1
+                continue
+            seg = (raw[pos + 2] << 8) | raw[pos + 3]
+            if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+                return (raw[pos + 7] << 8) | raw[pos + 8], (raw[pos + 5] << 8) | raw[pos + 6], raw[pos + 9]
+            if m == 0xDA or seg < 2:
+                break
+            pos += 2 + seg
+    p = parse_jpeg(raw, headers_only=True)
+    return p.image_width, p.image_height, len(p.color_components)
+
+
 def _image_dims(raw: bytes) -> Tuple[int, int]:
     """(width, height) from a file's frame header (SOF0-SOF15 but DHT / JPG / DAC), walking the marker segments in front of
     it; anything unusual goes through the parser, which raises the reference's exceptions."""
@@ -354,6 +373,29 @@ def _image_dims(raw: bytes) -> Tuple[int, int]:
             pos += 2 + seg
     p = parse_jpeg(raw, headers_only=True)
     return p.image_width, p.image_height
+
+
+def normalize_size(size) -> Optional[Tuple[int, int]]:
+    """The (width, height) of a decode to a fixed size: None, or two positive integers (ValueError otherwise)."""
+    if size is None:
+        return None
+    ok = isinstance(size, (tuple, list, np.ndarray)) and len(size) == 2 and all(
+        isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in size)
+    if not ok or int(size[0]) < 1 or int(size[1]) < 1 or int(size[0]) > 65535 or int(size[1]) > 65535:
+        raise ValueError(f"size must be (width, height), two positive integers up to 65535, not {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def one_component_count(ncomps: Sequence[int]) -> int:
+    """The component count the files of a decode to a fixed size share (they fill one array); ValueError naming the first file
+    that differs from file 0.  No files at all: 3 — the empty result then has a colour batch's shape, (0, ..., 3)."""
+    if not ncomps:
+        return 3
+    for i, nc in enumerate(ncomps):
+        if nc != ncomps[0]:
+            raise ValueError(f"file {i}: {nc} colour component(s) where file 0 has {ncomps[0]}: greyscale and colour files do "
+                             f"not share one array; decode them in separate calls")
+    return int(ncomps[0])
 
 
 def normalize_rois(rois, dims: Sequence[Tuple[int, int]]) -> Optional[List[Tuple[int, int, int, int]]]:
@@ -470,15 +512,24 @@ class BatchDecoder:
             off += n
         return out
 
-    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False):
+    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
-        the window's shape (see :func:`normalize_rois`)."""
+        the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
+        on the GPU — Pillow's ``resize(size, Image.BILINEAR)`` of it, byte for byte — and ONE array of shape ``(len(files),) +
+        shape of one image`` instead of a list."""
         if rois is not None and return_seams:
             raise ValueError("rois and return_seams do not go together: the seam outputs are whole-image")
+        size = normalize_size(size)
+        if size is not None and return_seams:
+            raise ValueError("size and return_seams do not go together: the seam outputs are at the files' own sizes")
         gpu_segment = self._gpu_segment_for(files)
         parsed = [parse_jpeg(f, headers_only=gpu_segment) for f in files]
         wins = normalize_rois(rois, [(p.image_width, p.image_height) for p in parsed])
+        dense = None
+        if size is not None:
+            nc = one_component_count([len(p.color_components) for p in parsed])
+            dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=np.uint8)
         groups: Dict[tuple, List[int]] = {}
         for i, p in enumerate(parsed):
             check_supported(p)
@@ -493,7 +544,7 @@ class BatchDecoder:
             idxs, extra = work.pop(0)
             prep = prepare_batch([files[i] for i in idxs], self.layout, flags | extra, [parsed[i] for i in idxs])
             sub = [wins[i] for i in idxs] if wins is not None else None
-            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)}, rois=sub)
+            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)}, rois=sub, size=size)
             try:
                 plan.execute()
                 plan.sync()
@@ -510,6 +561,12 @@ class BatchDecoder:
                     work.append((again, extra | B.MJ_FLAG_NO_SYNC))
                     out["status"][[k for k, i in enumerate(idxs) if i in again]] = 0
                 raise_for_status(out["status"])
+                if dense is not None:
+                    imgs = out["rgb"].reshape((len(idxs),) + dense.shape[1:])
+                    for k, i in enumerate(idxs):
+                        if i not in redo and i not in again:
+                            dense[i] = imgs[k]
+                    continue
                 imgs = self.split_outputs(prep, out["rgb"], wins=sub)
                 for k, i in enumerate(idxs):
                     if i in redo or i in again:
@@ -524,6 +581,8 @@ class BatchDecoder:
                                     "planes": out["planes"][po:po + w * h * nc].reshape(w, h, nc)}
             finally:
                 plan.close()
+        if dense is not None:
+            return dense
         return (results, seams) if return_seams else results
 
     def _staging_for(self, files: Sequence[bytes]) -> np.ndarray:
@@ -534,7 +593,7 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None):
+    def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, _dest=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -544,10 +603,26 @@ class BatchDecoder:
         takes the Python path below, which raises the reference's exceptions.  A large batch on that route goes as ``parts``
         plans of 256 files or more (up to four) through :meth:`decode_device_iter`, so that one part's upload runs under the
         assembly of the next and under the kernels of the one before — inside one call the three would otherwise add up.
-        ``rois`` as in :meth:`decode`: the windows are checked against the files' headers before any GPU work."""
+        ``rois`` as in :meth:`decode`: the windows are checked against the files' headers before any GPU work.
+        ``size=(width, height)``: ONE ``torch.uint8`` tensor of shape ``(len(files),) + shape of one image`` — every image (or
+        window) resized as in :meth:`decode`; files of several kinds are still one plan per kind, and every plan writes its
+        images straight into their slots of that tensor."""
         import torch
         wins = None
-        if rois is not None:
+        size = normalize_size(size)
+        dest = slots = None                     # size=: the one tensor, and the slot of every file in it
+        if size is not None:
+            info = [_image_info(f) for f in files]
+            nc = one_component_count([t[2] for t in info])
+            if rois is not None:
+                wins = normalize_rois(rois, [t[:2] for t in info])
+            if _dest is not None:               # (a second round of some files of a larger call: their slots of its tensor)
+                dest, slots = _dest
+            else:
+                dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=torch.uint8,
+                                   device=torch.device("cuda", self.ctx.device))
+                slots = list(range(len(files)))
+        elif rois is not None:
             wins = normalize_rois(rois, [_image_dims(f) for f in files])
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
@@ -555,10 +630,12 @@ class BatchDecoder:
             n = len(files)
             cut = [n * i // parts for i in range(parts + 1)]
             out: List["torch.Tensor"] = []
-            for part in self._device_iter(((files[cut[i]:cut[i + 1]], wins[cut[i]:cut[i + 1]] if wins is not None else None)
-                                           for i in range(parts)), depth=2):
-                out += part
-            return out
+            for part in self._device_iter(((files[cut[i]:cut[i + 1]], wins[cut[i]:cut[i + 1]] if wins is not None else None,
+                                            (dest, slots[cut[i]:cut[i + 1]]) if dest is not None else None)
+                                           for i in range(parts)), depth=2, size=size):
+                if dest is None:
+                    out += part
+            return out if dest is None else dest
         dev = torch.device("cuda", self.ctx.device)
         results: List[Optional["torch.Tensor"]] = [None] * len(files)
         parsed: Dict[int, ParsedJpeg] = {}
@@ -615,9 +692,10 @@ class BatchDecoder:
                     else:
                         d_blob = torch.from_numpy(prep.blob).to(dev)
                     plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(idxs)},
-                                  rois=[wins[i] for i in idxs] if wins is not None else None)
+                                  rois=[wins[i] for i in idxs] if wins is not None else None, size=size,
+                                  slots=([slots[i] for i in idxs], dest.shape[0]) if dest is not None else None)
                     flying.append((idxs, prep, plan, None, d_blob))
-                    d_rgb = torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
+                    d_rgb = dest if dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     flying[-1] = (idxs, prep, plan, d_rgb, d_blob)
                     # d_rgb comes from torch's caching allocator on torch's CURRENT stream: a block a consumer has just
                     # dropped may still be read by kernels queued there, so the stream that is about to overwrite it waits
@@ -656,6 +734,8 @@ class BatchDecoder:
                         work.append((again, B.MJ_FLAG_NO_SYNC))
                         status[[k for k, i in enumerate(idxs) if i in again]] = 0
                     raise_for_status(status)
+                    if dest is not None:                         # (the plan wrote its slots of the one tensor)
+                        continue
                     off = 0
                     shapes = self._out_shapes(prep, [wins[i] for i in idxs] if wins is not None else None)
                     for k, i in enumerate(idxs):
@@ -667,9 +747,9 @@ class BatchDecoder:
             finally:
                 for item in flying:
                     item[2].close()
-        return results
+        return results if dest is None else dest
 
-    def decode_device_iter(self, batches, depth=2):
+    def decode_device_iter(self, batches, depth=2, size=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -680,11 +760,14 @@ class BatchDecoder:
         in flight (round 5) the host waited for batch k's kernels before it started assembling batch k + 2, and the copy engine
         idled meanwhile: 512 x 1080p took the front end's 4.3 ms PLUS the upload's 6.1 ms per batch; with two the three —
         host threads, copy engine, GPU — run side by side and the batch takes what the slowest of them takes.  Batches the front
-        end declines are decoded by :meth:`decode_device` in place, behind everything in flight (no overlap for those)."""
-        yield from self._device_iter(((files, None) for files in batches), depth)
+        end declines are decoded by :meth:`decode_device` in place, behind everything in flight (no overlap for those).
+        ``size=(width, height)``: one tensor per batch, as :meth:`decode_device` returns it with ``size``."""
+        yield from self._device_iter(((files, None, None) for files in batches), depth, normalize_size(size))
 
-    def _device_iter(self, batches, depth=2):
-        """:meth:`decode_device_iter` over (files, windows or None) pairs (windows: normalize_rois' list for those files)."""
+    def _device_iter(self, batches, depth=2, size=None):
+        """:meth:`decode_device_iter` over (files, windows or None, destination or None) triples (windows: normalize_rois' list
+        for those files; destination, with ``size``: (tensor, slot of every file in it) — None: a tensor of the batch's own,
+        which is what the batch yields)."""
         import collections
         import torch
         dev = torch.device("cuda", self.ctx.device)
@@ -704,6 +787,8 @@ class BatchDecoder:
                 status = status.copy()
                 status[again] = 0                                 # something behind a scan / rounds not settled: those files again, below
                 raise_for_status(status)
+                if size is not None:
+                    return d_rgb, again
                 out, off = [], 0
                 for (w, h, nc) in self._out_shapes(prep, wins):
                     n = w * h * nc
@@ -717,14 +802,25 @@ class BatchDecoder:
             out, again = finish(job[0], job[2])
             if again.size:                                        # only the files concerned take the long way (host parse)
                 redo = self.decode_device([job[1][int(i)] for i in again], parts=1,
-                                          rois=[job[2][int(i)] for i in again] if job[2] is not None else None)
-                for i, img in zip(again, redo):
-                    out[int(i)] = img
+                                          rois=[job[2][int(i)] for i in again] if job[2] is not None else None, size=size,
+                                          _dest=(out, [job[3][int(i)] for i in again]) if size is not None else None)
+                if size is None:
+                    for i, img in zip(again, redo):
+                        out[int(i)] = img
             return out
 
+        def destination(files, dest):
+            """with ``size``: (tensor, slots) a batch's plan writes — the caller's, or a tensor of the batch's own"""
+            if size is None or dest is not None:
+                return dest
+            nc = one_component_count([_image_info(f)[2] for f in files])
+            return (torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=torch.uint8, device=dev),
+                    list(range(len(files))))
+
         try:
-            for files, wins in batches:
+            for files, wins, dest in batches:
                 files = list(files)
+                dest = destination(files, dest)
                 prep = None
                 if self.gpu_segment and self.native_host and files:
                     buf, turn = turn, (turn + 1) % (depth + 1)
@@ -739,16 +835,17 @@ class BatchDecoder:
                 if prep is None:
                     while pending:
                         yield collect(pending.popleft())
-                    yield self.decode_device(files, rois=wins, parts=1)
+                    yield self.decode_device(files, rois=wins, parts=1, size=size, _dest=dest)
                     continue
                 with torch.cuda.stream(copy_stream):
                     d_blob = pinned[buf][:prep.blob.size].to(dev, non_blocking=True)
                     uploaded[buf] = torch.cuda.Event()
                     uploaded[buf].record(copy_stream)
-                plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(files)}, rois=wins)
+                plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(files)}, rois=wins, size=size,
+                              slots=(dest[1], dest[0].shape[0]) if dest is not None else None)
                 try:
                     # (both tensors outlive the kernels that touch them: they stay in `pending` until the plan has been collected)
-                    d_rgb = torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
+                    d_rgb = dest[0] if dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     self.ctx.wait_event(uploaded[buf].cuda_event)
                     ev = torch.cuda.Event()                        # see decode_device: the context's stream waits for whatever
                     ev.record(torch.cuda.current_stream(dev))      # the current stream still does with a recycled block
@@ -757,7 +854,7 @@ class BatchDecoder:
                 except BaseException:
                     plan.close()
                     raise
-                pending.append(((plan, prep, d_rgb, d_blob), files, wins))
+                pending.append(((plan, prep, d_rgb, d_blob), files, wins, dest[1] if dest is not None else None))
                 while len(pending) > depth:
                     yield collect(pending.popleft())
             while pending:

@@ -106,7 +106,7 @@ void mj_plan_destroy(mj_plan *p) {
     }
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
     void *ptrs[] = {p->d_blob_owned, p->d_segs, p->d_images, p->d_huff, p->d_lut11, p->d_lut13, p->d_lut12, p->d_by_length, p->d_holder, p->d_xwords, p->d_wg_tabs_lanes, p->d_wg_tabs_count, p->d_stream, p->d_seg_bits, p->d_jobs, p->d_lut11u, p->d_acsegs, p->d_pc_chunks, p->d_pc_tabs, p->d_pc_exit, p->d_pc_outs, p->d_pc_items, p->d_pc_owner, p->d_pc_vsegs, p->d_lutc, p->d_sync_items, p->d_seg_chunk0, p->d_chunks, p->d_stateA, p->d_stateB, p->d_couts, p->d_vsegs, p->d_changed, p->d_pieces, p->d_piece_kept, p->d_pscans, p->d_psegs, p->d_pstates, p->d_psubs, p->d_prog_dsegs, p->d_lut11p, p->d_qt, p->d_mcu_prefix, p->d_job_prefix, p->d_tmp_coef, p->d_coef,
-                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status, p->d_win, p->d_win_mcu_prefix, p->d_segs_full, p->d_seg_gather};
+                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status, p->d_win, p->d_win_mcu_prefix, p->d_segs_full, p->d_seg_gather, p->d_src, p->d_rz_images, p->d_rz_tabs};
     for (void *q : ptrs)
         if (q) p->ctx->cache.put(q);
     delete p;
@@ -305,9 +305,19 @@ static int recon_args(mj_plan *p, uint8_t *rgb_device, mj::ReconArgs &a) {
     a.jobs_per_ticket = p->jobs_per_ticket;
     a.level_counts = reinterpret_cast<unsigned long long *>(p->d_job_prefix + p->n_images + 3);
     a.win = p->d_win;
+    if (p->resized) a.rgb = p->d_src;      // stage 2 writes the plan's intermediate buffer; resize_launch reads it into last_rgb
     if (p->windowed) {      // the exact-order and generic kernels number the windows' MCUs
         a.total_mcus = p->win_total_mcus; a.mcu_prefix = p->d_win_mcu_prefix; a.uniform_geometry = 0;
     }
+    return MJ_OK;
+}
+
+// a resized plan's last launch: the intermediate pixels, resized, into the output recon_args resolved
+static int resize_launch(mj_plan *p, hipStream_t s) {
+    if (!p->resized) return MJ_OK;
+    mj::ResizeArgs a = p->rz;
+    a.dst = p->last_rgb;
+    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp));
     return MJ_OK;
 }
 
@@ -320,7 +330,8 @@ static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
     rgb_device = p->last_rgb;
     // planar layouts: the kernels write the interleaved image of the same orientation into a plan-owned buffer and a copy
     // kernel separates the components (one extra pass over the pixels; the interleaved layouts are the fast ones)
-    const bool planar = p->layout >= MJ_LAYOUT_PLANAR_XMAJOR && p->ncomp == 3;
+    // (a resized planar plan keeps the interleaved image: the resize launch stores the planes)
+    const bool planar = p->layout >= MJ_LAYOUT_PLANAR_XMAJOR && p->ncomp == 3 && !p->resized;
     if (planar) {
         if (!p->d_rgb_tmp) MJ_HIP(ctx, ctx->cache.get((void **)&p->d_rgb_tmp, (size_t)p->info.rgb_bytes + 16));
         a.rgb = p->d_rgb_tmp;
@@ -340,7 +351,7 @@ static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
                                                p->total_jobs, p->jobs_per_image));
     }
     if (planar) MJ_HIP(ctx, mj::launch_planes_from_interleaved(s, p->d_images, p->n_images, p->max_pixels, p->d_rgb_tmp, rgb_device, p->d_win));
-    return MJ_OK;
+    return resize_launch(p, s);
 }
 
 // Both stages in one launch (fused.hip), for the plans that can (use_fused): the marker scan and stage 0 as in stage1_impl,
@@ -370,7 +381,7 @@ static int fused_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
         mj::dbg_fused_report(ctx->d_dump, p->fused.n_wg);
     }
 #endif
-    return MJ_OK;
+    return resize_launch(p, s);
 }
 
 // one execute's launches: fused where the plan can, else stage 1 then stage 2
@@ -513,6 +524,43 @@ int mj_plan_fill_coef(mj_plan *p, int byte_value) {
     MJ_HIP(ctx, hipMemset(p->d_coef, byte_value & 0xFF, (size_t)p->info.total_blocks * 128));
     MJ_HIP(ctx, hipDeviceSynchronize());
     return MJ_OK;
+}
+
+int mj_plan_fill_source(mj_plan *p, int byte_value) {
+    if (!p) return MJ_ERR_INVALID;
+    mj_context *ctx = p->ctx;
+    if (!p->resized) return fail(ctx, MJ_ERR_INVALID, "mj_plan_fill_source: not a resized plan");
+    if (int rc = plan_ready(p)) return rc;
+    if (p->done_valid) MJ_HIP(ctx, hipEventSynchronize(p->done));
+    MJ_HIP(ctx, hipMemset(p->d_src, byte_value & 0xFF, (size_t)p->src_bytes + 64));
+    MJ_HIP(ctx, hipDeviceSynchronize());
+    return MJ_OK;
+}
+
+int mj_plan_time_resize(mj_plan *p, int iters, uint8_t *rgb_device, float *ms_out, int64_t *source_bytes) {
+    if (!p || iters <= 0 || !ms_out) return MJ_ERR_INVALID;
+    mj_context *ctx = p->ctx;
+    if (!p->resized) return fail(ctx, MJ_ERR_INVALID, "mj_plan_time_resize: not a resized plan");
+    if (!rgb_device && !p->last_rgb) return fail(ctx, MJ_ERR_INVALID, "mj_plan_time_resize: nothing executed yet and no output buffer given");
+    hipStream_t s = ctx->stream;
+    if (int rc = plan_ready(p, s)) return rc;
+    if (rgb_device) p->last_rgb = rgb_device;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    MJ_HIP(ctx, hipEventCreate(&ev.a));
+    MJ_HIP(ctx, hipEventCreate(&ev.b));
+    int rc = resize_launch(p, s);       // warm
+    MJ_HIP(ctx, hipEventRecord(ev.a, s));
+    for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = resize_launch(p, s);
+    MJ_HIP(ctx, hipEventRecord(ev.b, s));
+    MJ_HIP(ctx, hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    MJ_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+    *ms_out = ms / iters;
+    if (source_bytes) *source_bytes = p->src_bytes;
+    return rc != MJ_OK ? rc : mark_done(p, s);
 }
 
 int mj_decode_baseline_batch(mj_context *ctx, const mj_batch *batch, uint8_t *rgb_out, int16_t *coef_out,

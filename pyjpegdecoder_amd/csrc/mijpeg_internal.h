@@ -372,6 +372,29 @@ hipError_t launch_planes_from_interleaved(hipStream_t stream, const DevImage *im
 // window plans of MJ_FLAG_GPU_SEGMENT batches: out[i] = full[idx[i]] — the restart segments the windows need, out of the
 // list the marker scan filled, into the list stages 0 and 1 read
 hipError_t launch_gather_segments(hipStream_t stream, const DevSegment *full, const int32_t *idx, int64_t n, DevSegment *out);
+// ---- resize.hip: decode to a fixed size
+// One image of a resized plan: where its decoded pixels (the image, or its window) lie in the plan's intermediate buffer,
+// their size, its tap tables and where its out_width x out_height pixels go.
+struct DevResizeImage {
+    int64_t src_off;      // bytes, into the intermediate buffer (= DevImage::rgb_off)
+    int64_t dst_off;      // bytes, into the output: slot * out_width * out_height * ncomp
+    int32_t w, h;         // size of the source pixels
+    int32_t xtab, ytab;   // word offsets of its width / height tables in ResizeArgs::tabs
+};
+// (a table: ksize, first source index [out], tap count [out], taps [out][ksize])
+struct ResizeArgs {
+    const uint8_t *src;
+    uint8_t *dst;
+    const DevResizeImage *images;
+    const int32_t *tabs;
+    int32_t n_images, ow, oh, layout;
+    int32_t tr, tc, tiles_x, tiles_y;         // output rows / columns per tile, tiles per image
+    int32_t t_pitch, tab_off, stage_off, stage_bytes, lds_bytes;    // the workgroup's LDS (resize.hip)
+};
+constexpr int64_t kResizeGridX = 1 << 20;      // workgroups along x of the resize launch's grid (the rest along y)
+int resize_axis_ksize(int in_size, int out_size);
+void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride);
+hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp);
 // dst[0 .. bytes) = src[0 .. bytes), sixteen bytes per lane (bytes a multiple of 16): the plain copy the rooflines are held against
 hipError_t launch_copy16(hipStream_t stream, const void *src, void *dst, int64_t bytes, int variant);     // variant 0 .. copy16_variants() - 1: launch shapes
 int copy16_variants();

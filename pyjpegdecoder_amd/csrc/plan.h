@@ -257,6 +257,14 @@ struct mj_plan {
     // windows need are gathered (d_seg_gather: their indices) into d_segs, which stages 0 and 1 read
     mj::DevSegment *d_segs_full = nullptr;
     int32_t *d_seg_gather = nullptr;
+    // resized plans (mj_plan_create_resized): stage 2 writes its interleaved pixels into d_src, the resize launch reads them and
+    // writes the plan's output (info.rgb_bytes is the OUTPUT's size; src_bytes the intermediate's)
+    bool resized = false;
+    uint8_t *d_src = nullptr;
+    int64_t src_bytes = 0;
+    mj::DevResizeImage *d_rz_images = nullptr;
+    int32_t *d_rz_tabs = nullptr;
+    mj::ResizeArgs rz{};
 };
 
 // ---- plan_tables.hip: table building (host)
@@ -270,6 +278,8 @@ bool build_count_tables(const mj_batch *b, const std::vector<int> &role, int W, 
 struct ProgScans { std::vector<DevProgScan> pscans; std::vector<DevProgSeg> psegs; };
 int plan_progressive_scans(mj_context *ctx, const mj_batch *b, mj_plan *p, ProgScans &S, int64_t &entropy_bytes);
 int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, ProgScans &S);
+// ---- plan_create.hip: what mj_plan_create / mj_plan_create_roi do (roi_plan: a window plan)
+int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, bool roi_plan, mj_plan **out);
 }  // namespace mj
 
 // (one definition per translation unit: they return through the caller's frame)

@@ -722,3 +722,7 @@ int mj_plan_create_roi(mj_context *ctx, const mj_batch *b, const mj_roi *rois, m
 }
 
 }  // extern "C"
+
+int mj::plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, bool roi_plan, mj_plan **out) {
+    return plan_create_impl(ctx, b, rois, roi_plan, out);
+}

@@ -1,0 +1,392 @@
+// Decode to a fixed size: the batch's decoded pixels (whole images or windows, as stage 2 packed them) resized to one
+// out_width x out_height, all images in ONE launch, into one dense output.
+//
+// The arithmetic is Pillow's Image.resize(size, BILINEAR) on 8-bit data (tools/resize_model.py restates it): per axis a
+// table of integer taps — triangle-filter weights in doubles, support growing with the scale when shrinking, normalised,
+// rounded to 22 bits: build_resize_axis, host — and per pixel clip8((2^21 + sum taps * in) >> 22).  Two passes with a uint8
+// intermediate image: along the width first, then along the height.  The order and the intermediate rounding are part of the
+// result.  (An axis that does not change goes through the same code: its table is one tap of 2^22, which is the identity.)
+//
+// A workgroup takes one tile of one image's output.  It runs the width pass for the source rows the tile needs into LDS —
+// that IS the intermediate image — then the height pass out of LDS, and stores finished output.  Source bytes are read 16 per
+// lane along the contiguous axis of the source, which differs with the layout:
+//   row-major source (H, W, C): the width pass runs ALONG the contiguous axis.  A wavefront stages one source row segment in
+//     LDS (aligned 16-byte loads) and gathers its taps from there; the height pass then runs across the rows of T.
+//   x-major source (W, H, C):   the width pass runs ACROSS the contiguous axis.  A lane holds 16 consecutive bytes (y, c) of a
+//     column and accumulates the taps' columns straight from global memory (16-byte loads at any alignment: columns start
+//     where they start); the height pass then gathers along the rows of T.
+// Planar plans read the same interleaved source (stage 2 writes it; the plane separation of a plain planar plan is skipped)
+// and only store elsewhere.
+#include <math.h>
+
+#include <map>
+
+#include "plan.h"
+
+namespace mj {
+
+// ---- host: tap tables -----------------------------------------------------------------------------------------------
+// xmin[out], count[out], taps[out][ksize] (zeros behind count); the formulas and their evaluation order are Pillow's
+// (precompute_coeffs + normalize_coeffs_8bpc with the bilinear filter).  Compiled with -ffp-contract=off like everything here.
+int resize_axis_ksize(int in_size, int out_size) {
+    const double scale = (double)in_size / (double)out_size;
+    const double support = 1.0 * (scale < 1.0 ? 1.0 : scale);
+    return (int)ceil(support) * 2 + 1;
+}
+
+void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride) {
+    const double scale = (double)in_size / (double)out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 1.0 * filterscale, ss = 1.0 / filterscale;
+    const int ksize = (int)ceil(support) * 2 + 1;
+    std::vector<double> w((size_t)ksize + 2);
+    for (int xx = 0; xx < out_size; ++xx) {
+        const double center = (xx + 0.5) * scale;
+        int lo = (int)(center - support + 0.5);
+        if (lo < 0) lo = 0;
+        int hi = (int)(center + support + 0.5);
+        if (hi > in_size) hi = in_size;
+        int n = hi - lo;
+        if (n > ksize) n = ksize;
+        double ww = 0.0;
+        for (int x = 0; x < n; ++x) {
+            double a = ((double)(x + lo) - center + 0.5) * ss;
+            if (a < 0.0) a = -a;
+            w[x] = a < 1.0 ? 1.0 - a : 0.0;
+            ww += w[x];
+        }
+        xmin[xx] = lo;
+        count[xx] = n;
+        for (int x = 0; x < taps_stride; ++x) {
+            double v = x < n ? w[x] : 0.0;
+            if (x < n && ww != 0.0) v /= ww;
+            taps[(size_t)xx * taps_stride + x] = x < n ? (int32_t)(v * (double)(1 << 22) + 0.5) : 0;
+        }
+    }
+}
+
+// ---- device ---------------------------------------------------------------------------------------------------------
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+struct AxisTab {
+    const int32_t *lo, *cnt, *k;
+    int ks;
+    __device__ AxisTab(const int32_t *t, int out) : lo(t + 1), cnt(t + 1 + out), k(t + 1 + 2 * out), ks(t[0]) {}
+};
+
+// where output element (ox, oy, c) of an image goes: a.layout is the plan's MJ_LAYOUT_*
+__device__ __forceinline__ int64_t out_index(const ResizeArgs &a, int C, int ox, int oy, int c) {
+    switch (a.layout) {
+        case 0: return ((int64_t)ox * a.oh + oy) * C + c;          // (ow, oh, C)
+        case 1: return ((int64_t)oy * a.ow + ox) * C + c;          // (oh, ow, C)
+        case 2: return ((int64_t)c * a.ow + ox) * a.oh + oy;       // (C, ow, oh)
+        default: return ((int64_t)c * a.oh + oy) * a.ow + ox;      // (C, oh, ow)
+    }
+}
+
+__device__ __forceinline__ unsigned clip8(unsigned acc) {
+    const unsigned v = acc >> 22;
+    return v > 255u ? 255u : v;
+}
+
+// Row-major source.  LDS: T [t_rows][t_pitch] | per output column of the tile: first source column (relative), taps, the
+// taps themselves [tc][ksx] | one staging row per wavefront.
+template <int C>
+__global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int xa = X.lo[ox0], xb = X.lo[ox1 - 1] + X.cnt[ox1 - 1];       // (both bounds grow with the output index)
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, ne = ncols * C;
+    unsigned char *T = smem;
+    int32_t *lx_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *lx_cnt = lx_lo + a.tc, *lx_k = lx_cnt + a.tc;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    unsigned char *stage = smem + a.stage_off + wave * a.stage_bytes;
+    for (int i = tid; i < ncols; i += 256) { lx_lo[i] = (X.lo[ox0 + i] - xa) * C; lx_cnt[i] = X.cnt[ox0 + i]; }
+    for (int i = tid; i < ncols * X.ks; i += 256) lx_k[i] = X.k[(int64_t)ox0 * X.ks + i];
+    __syncthreads();
+    const unsigned char *src = a.src + im.src_off;
+    const int seg = (xb - xa) * C;
+    // width pass: every wavefront takes every fourth source row of the tile
+    for (int r = wave; r < nrows; r += 4) {
+        const unsigned char *row = src + ((int64_t)(ya + r) * im.w + xa) * C;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15);
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(row - mis);
+        const int n16 = (mis + seg + 15) >> 4;
+        for (int j = lane; j < n16; j += 64) reinterpret_cast<u32x4 *>(stage)[j] = p[j];
+        // (the staging row is this wavefront's own: its lanes only have to see each other's LDS writes)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int e = lane; e < ne; e += 64) {
+            const int oxl = e / C, c = e - oxl * C;
+            const unsigned char *s = stage + mis + lx_lo[oxl] + c;
+            const int32_t *k = lx_k + oxl * X.ks;
+            const int n = lx_cnt[oxl];
+            unsigned acc = 1u << 21;
+            for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * C]);
+            T[r * a.t_pitch + e] = (unsigned char)clip8(acc);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    // height pass: consecutive lanes take consecutive bytes of an output row (of a plane's row for planar plans)
+    unsigned char *dst = a.dst + im.dst_off;
+    const int orows = oy1 - oy0, total = orows * ne;
+    const bool planar = a.layout >= 2 && C > 1;
+    for (int i = tid; i < total; i += 256) {
+        int oyl, oxl, c;
+        if (planar) { c = i / (orows * ncols); const int rem = i - c * (orows * ncols); oyl = rem / ncols; oxl = rem - oyl * ncols; }
+        else { oyl = i / ne; const int e = i - oyl * ne; oxl = e / C; c = e - oxl * C; }
+        const int oy = oy0 + oyl;
+        const int n = Y.cnt[oy];
+        const int32_t *k = Y.k + (int64_t)oy * Y.ks;
+        const unsigned char *s = T + (Y.lo[oy] - ya) * a.t_pitch + oxl * C + c;
+        unsigned acc = 1u << 21;
+        for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * a.t_pitch]);
+        dst[out_index(a, C, ox0 + oxl, oy, c)] = (unsigned char)clip8(acc);
+    }
+}
+
+// X-major source.  LDS: T [tc][t_pitch] (one row per output column: the bytes (y, c) of the source rows the tile needs,
+// t_pitch a multiple of 16) | per output row of the tile: first source row (relative), taps, the taps themselves [tr][ksy].
+template <int C>
+__global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, orows = oy1 - oy0;
+    unsigned char *T = smem;
+    int32_t *ly_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *ly_cnt = ly_lo + a.tr, *ly_k = ly_cnt + a.tr;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < orows; i += 256) { ly_lo[i] = (Y.lo[oy0 + i] - ya) * C; ly_cnt[i] = Y.cnt[oy0 + i]; }
+    for (int i = tid; i < orows * Y.ks; i += 256) ly_k[i] = Y.k[(int64_t)oy0 * Y.ks + i];
+    const unsigned char *src = a.src + im.src_off;
+    // width pass: 16 consecutive bytes of a column per lane, the taps' columns one after the other.  (The last chunk of a
+    // column reads up to 15 bytes behind the rows the tile needs — the next column's, or the buffer's padding — into T's
+    // padding, which nothing reads.)
+    const int nch = (nrows * C + 15) >> 4;
+    const int64_t col = (int64_t)im.h * C;
+    for (int i = tid; i < ncols * nch; i += 256) {
+        const int oxl = i / nch, j = i - oxl * nch;
+        const int ox = ox0 + oxl, n = X.cnt[ox];
+        const int32_t *k = X.k + (int64_t)ox * X.ks;
+        const unsigned char *p = src + ((int64_t)X.lo[ox] * im.h + ya) * C + 16 * j;
+        unsigned acc[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) acc[b] = 1u << 21;
+        for (int q = 0; q < n; ++q, p += col) {
+            u32x4 v;
+            __builtin_memcpy(&v, p, 16);
+            const unsigned kq = (unsigned)k[q];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) acc[b] += __umul24(kq, (v[b >> 2] >> (8 * (b & 3))) & 255u);
+        }
+        u32x4 o;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            o[d] = clip8(acc[4 * d]) | clip8(acc[4 * d + 1]) << 8 | clip8(acc[4 * d + 2]) << 16 | clip8(acc[4 * d + 3]) << 24;
+        *reinterpret_cast<u32x4 *>(T + oxl * a.t_pitch + 16 * j) = o;
+    }
+    __syncthreads();
+    // height pass: consecutive lanes take consecutive bytes of an output column (of a plane's column for planar plans)
+    unsigned char *dst = a.dst + im.dst_off;
+    const int ne = orows * C, total = ncols * ne;
+    const bool planar = a.layout >= 2 && C > 1;
+    for (int i = tid; i < total; i += 256) {
+        int oyl, oxl, c;
+        if (planar) { c = i / (orows * ncols); const int rem = i - c * (orows * ncols); oxl = rem / orows; oyl = rem - oxl * orows; }
+        else { oxl = i / ne; const int e = i - oxl * ne; oyl = e / C; c = e - oyl * C; }
+        const int n = ly_cnt[oyl];
+        const int32_t *k = ly_k + oyl * Y.ks;
+        const unsigned char *s = T + oxl * a.t_pitch + ly_lo[oyl] + c;
+        unsigned acc = 1u << 21;
+        for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * C]);
+        dst[out_index(a, C, ox0 + oxl, oy0 + oyl, c)] = (unsigned char)clip8(acc);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp) {
+    if (a.n_images <= 0) return hipSuccess;
+    // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
+    const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
+    const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
+    const bool xmajor = (a.layout & 1) == 0;
+    if (xmajor && ncomp == 3) hipLaunchKernelGGL(k_resize_xmajor<3>, grid, block, a.lds_bytes, stream, a);
+    else if (xmajor) hipLaunchKernelGGL(k_resize_xmajor<1>, grid, block, a.lds_bytes, stream, a);
+    else if (ncomp == 3) hipLaunchKernelGGL(k_resize_rowmajor<3>, grid, block, a.lds_bytes, stream, a);
+    else hipLaunchKernelGGL(k_resize_rowmajor<1>, grid, block, a.lds_bytes, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace mj
+
+// ---- host: mj_plan_create_resized ---------------------------------------------------------------------------------------
+namespace {
+
+struct AxisHost {
+    std::vector<int32_t> lo, cnt;
+    int ks = 0, word_off = 0;
+    // the most source entries a tile of `tile` outputs needs
+    int span(int tile) const {
+        int m = 0;
+        const int out = (int)lo.size();
+        for (int o0 = 0; o0 < out; o0 += tile) {
+            int hi = 0;
+            for (int o = o0; o < std::min(o0 + tile, out); ++o) hi = std::max(hi, lo[o] + cnt[o]);
+            m = std::max(m, hi - lo[o0]);
+        }
+        return m;
+    }
+};
+
+int round16(int64_t v) { return (int)((v + 15) & ~(int64_t)15); }
+
+}  // namespace
+
+extern "C" {
+
+int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride,
+                         int32_t *ksize_out) {
+    if (in_size < 1 || out_size < 1 || in_size > 65535 || out_size > 65535) return MJ_ERR_INVALID;
+    const int ks = mj::resize_axis_ksize(in_size, out_size);
+    if (ksize_out) *ksize_out = ks;
+    if (!xmin && !count && !taps) return MJ_OK;
+    if (!xmin || !count || !taps || taps_stride < ks) return MJ_ERR_INVALID;
+    mj::build_resize_axis(in_size, out_size, xmin, count, taps, taps_stride);
+    return MJ_OK;
+}
+
+int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                           const int32_t *slots, int32_t n_slots, mj_plan **out) {
+    if (!ctx) return MJ_ERR_INVALID;
+    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: NULL argument");
+    *out = nullptr;
+    if (out_width < 1 || out_height < 1 || out_width > 65535 || out_height > 65535)
+        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: output size %d x %d (both must be 1..65535)", out_width, out_height);
+    if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
+        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none");
+    if (!slots) n_slots = b->n_images;
+    for (int i = 0; slots && i < b->n_images; ++i)
+        if (slots[i] < 0 || slots[i] >= n_slots)
+            return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: image %d: slot %d outside the %d slots of the output", i, slots[i], n_slots);
+    mj_plan *p = nullptr;
+    // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
+    if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
+    struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
+    const int C = p->ncomp, n = p->n_images;
+    const int64_t out_image = (int64_t)out_width * out_height * C;
+    // tap tables: one per distinct source size and axis
+    std::map<int, AxisHost> xs, ys;
+    std::vector<int32_t> words;
+    auto axis = [&](std::map<int, AxisHost> &m, int in_size, int out_size) -> const AxisHost & {
+        auto it = m.find(in_size);
+        if (it != m.end()) return it->second;
+        AxisHost &A = m[in_size];
+        A.ks = mj::resize_axis_ksize(in_size, out_size);
+        A.lo.resize(out_size); A.cnt.resize(out_size);
+        std::vector<int32_t> k((size_t)out_size * A.ks);
+        mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks);
+        A.word_off = (int)words.size();
+        words.push_back(A.ks);
+        words.insert(words.end(), A.lo.begin(), A.lo.end());
+        words.insert(words.end(), A.cnt.begin(), A.cnt.end());
+        words.insert(words.end(), k.begin(), k.end());
+        return A;
+    };
+    std::vector<mj::DevResizeImage> ri((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
+        ri[i].src_off = p->h_images[i].rgb_off;
+        ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
+        ri[i].w = w; ri[i].h = h;
+        ri[i].xtab = axis(xs, w, out_width).word_off;
+        ri[i].ytab = axis(ys, h, out_height).word_off;
+        if (words.size() > ((size_t)1 << 28)) return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_resized: the tap tables of this batch are too large");
+    }
+    // (a pure function of the tile: what it takes in LDS and where the parts lie; nothing is kept until a tile is chosen)
+    struct Lds { bool ok; int t_pitch, tab_off, stage_off, stage_bytes, total; };
+    // The tile: what a workgroup's LDS holds (resize.hip's kernels) must fit 64 KB — the intermediate rows of the tile, the
+    // tile's tap tables, the staging rows — for every source size of the batch.  Tiles shrink until it does: a row-major plan
+    // gives up columns first while a row segment stays 2 KB long (its loads run along the rows), then rows; an x-major plan
+    // keeps its rows (its loads run along the columns) and gives up columns.
+    const bool xmajor = (p->layout & 1) == 0;
+    mj::ResizeArgs &a = p->rz;
+    a = mj::ResizeArgs{};
+    int tr = std::min<int>(xmajor ? 32 : 16, out_height), tc = out_width;
+    const int budget = 64 * 1024;
+    auto lds_for = [&](int tr_, int tc_) -> Lds {
+        int sy = 0, sx = 0, ksx = 0, ksy = 0, pitch;
+        for (auto &kv : ys) { sy = std::max(sy, kv.second.span(tr_)); ksy = std::max(ksy, kv.second.ks); }
+        for (auto &kv : xs) { sx = std::max(sx, kv.second.span(tc_)); ksx = std::max(ksx, kv.second.ks); }
+        int64_t t_bytes, tab_bytes, stage = 0;
+        if (xmajor) {
+            pitch = round16((int64_t)sy * C);
+            t_bytes = (int64_t)tc_ * pitch;
+            tab_bytes = ((int64_t)2 * tr_ + (int64_t)tr_ * ksy) * 4;
+        } else {
+            pitch = round16((int64_t)tc_ * C);
+            t_bytes = (int64_t)sy * pitch;
+            tab_bytes = ((int64_t)2 * tc_ + (int64_t)tc_ * ksx) * 4;
+            stage = round16((int64_t)sx * C + 32);
+        }
+        const int64_t total = t_bytes + round16(tab_bytes) + 4 * stage;
+        if (total > budget) return Lds{false, 0, 0, 0, 0, 0};
+        return Lds{true, pitch, (int)t_bytes, (int)(t_bytes + round16(tab_bytes)), (int)stage, (int)total};
+    };
+    auto fits = [&](int tr_, int tc_) { return lds_for(tr_, tc_).ok; };
+    auto seg_bytes = [&](int tc_) { int sx = 0; for (auto &kv : xs) sx = std::max(sx, kv.second.span(tc_)); return sx * C; };
+    while (!fits(tr, tc)) {
+        const bool cols_first = xmajor ? (tc >= 32 || tr == 1) : (seg_bytes(tc) >= 2048 || tr == 1);
+        if (tc > 1 && cols_first) tc = (tc + 1) / 2;
+        else if (tr > 1) tr = (tr + 1) / 2;
+        else return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_resized: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds",
+                         xs.rbegin()->first, ys.rbegin()->first, out_width, out_height);
+    }
+    // (a small batch: more, smaller tiles, so that the chip has something to do)
+    auto n_tiles = [&](int tr_, int tc_) { return (int64_t)n * ((out_height + tr_ - 1) / tr_) * ((out_width + tc_ - 1) / tc_); };
+    while (n_tiles(tr, tc) < 1024 && tr > 4 && fits((tr + 1) / 2, tc)) tr = (tr + 1) / 2;
+    const Lds lds = lds_for(tr, tc);
+    a.tr = tr; a.tc = tc;
+    a.t_pitch = lds.t_pitch; a.tab_off = lds.tab_off; a.stage_off = lds.stage_off; a.stage_bytes = lds.stage_bytes; a.lds_bytes = lds.total;
+    a.tiles_x = (out_width + tc - 1) / tc; a.tiles_y = (out_height + tr - 1) / tr;
+    if (n_tiles(tr, tc) > mj::kResizeGridX * (int64_t)65535)
+        return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_resized: %lld tiles are more than one launch takes; split the batch", (long long)n_tiles(tr, tc));
+    a.n_images = n; a.ow = out_width; a.oh = out_height; a.layout = p->layout;
+    int rc;
+    if ((rc = upload(ctx, &p->d_rz_images, ri.data(), ri.size())) != MJ_OK) return rc;
+    if ((rc = upload(ctx, &p->d_rz_tabs, words.data(), words.size())) != MJ_OK) return rc;
+    // the un-resized pixels: a plan-owned buffer from the context's cache (64 bytes of slack: the kernels' 16-byte loads may
+    // start before and end behind the bytes they use)
+    p->src_bytes = p->info.rgb_bytes;
+    MJ_HIP(ctx, ctx->cache.get((void **)&p->d_src, (size_t)p->src_bytes + 64));
+    a.images = p->d_rz_images; a.tabs = p->d_rz_tabs; a.src = p->d_src;
+    p->info.rgb_bytes = (int64_t)n_slots * out_image;
+    p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
+    p->resized = true;
+    guard.p = nullptr;
+    *out = p;
+    return MJ_OK;
+}
+
+}  // extern "C"
