@@ -224,6 +224,34 @@ int mj_plan_create_roi(mj_context *ctx, const mj_batch *batch, const mj_roi *roi
  * more output tiles than one launch takes (about 6.8e10: split the batch). */
 int mj_plan_create_resized(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
                            const int32_t *slots, int32_t n_slots, mj_plan **out);
+/* Model-ready output: mj_plan_create_resized whose dense array holds, instead of the resized bytes, what a model takes —
+ * elements of `dtype`, normalised, some images mirrored.  Everything mj_plan_create_resized says holds; in addition:
+ *   dtype      MJ_DTYPE_U8: the resized byte itself.  MJ_DTYPE_F32: for a resized byte v of component c, torchvision's
+ *              Normalize(mean, std)(to_tensor(img)) in float32, every operation rounded on its own,
+ *                  y = fl32( fl32( fl32( float(v) / 255.0f ) - mean[c] ) / std[c] )
+ *              (normalize == 0: mean 0, std 1, i.e. v / 255).  MJ_DTYPE_F16 / MJ_DTYPE_BF16: y rounded to nearest even to IEEE
+ *              binary16 / bfloat16.  The resized bytes are those of mj_plan_create_resized: the function is applied to the
+ *              integer result of the two passes, as the height pass stores it (mj_host_normalize_table is its table).
+ *   normalize  0 or 1; with 1, mean[c] and std[c] for the batch's components (the rest ignored), in units of value / 255.
+ *   mirror     NULL, or host, n_images flags: image k with mirror[k] != 0 is stored flipped along its width axis — element
+ *              (x, y, c) of the un-mirrored result goes to column out_width - 1 - x, in whichever layout.  Any dtype.
+ * mj_plan_info.rgb_bytes of such a plan is in BYTES of the chosen type: n_slots * out_width * out_height * C * (1, 2 or 4).  It
+ * is what mj_plan_execute's rgb_device buffer must hold and what mj_plan_read's rgb copies; slot offsets scale likewise.
+ * output == NULL, or {MJ_DTYPE_U8, 0, .., NULL}: exactly mj_plan_create_resized, the same kernels.
+ * MJ_ERR_INVALID (with a message): a dtype that is none of the four, normalize with MJ_DTYPE_U8, a mean that is not finite,
+ * a std that is not finite or not > 0 — checked before anything else is done. */
+#define MJ_DTYPE_U8   0
+#define MJ_DTYPE_F16  1
+#define MJ_DTYPE_BF16 2
+#define MJ_DTYPE_F32  3
+typedef struct {
+    int32_t dtype;              /* MJ_DTYPE_* */
+    int32_t normalize;          /* 0: value / 255 (float types); 1: (value / 255 - mean[c]) / std[c] */
+    float mean[3], std[3];
+    const uint8_t *mirror;      /* NULL, or one flag per image of the batch */
+} mj_output_desc;
+int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                              const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -412,6 +440,11 @@ void mj_host_idct_table(double *tt);
  * *ksize = taps a row can hold at most (taps_stride must be at least that).  xmin = count = taps = NULL: only *ksize. */
 int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride,
                          int32_t *ksize);
+/* The output table of one component of a mj_plan_create_resized_as plan, as the library builds it (host only, no context): out
+ * = 256 elements of `dtype` (MJ_DTYPE_F16 / BF16: 2 bytes each, MJ_DTYPE_F32: 4), element v what resized byte v is stored as with
+ * this mean and std (mean 0, std 1 = no normalisation).  MJ_ERR_INVALID: MJ_DTYPE_U8 or an unknown dtype, NULL, a mean that is
+ * not finite, a std that is not finite or not > 0. */
+int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out);
 
 /* ---- host front end (no GPU work, no context) -------------------------------------------------------
  * Header parse + batch assembly for the everyday case, on host threads: what pyjpegdecoder_amd/_parse.py

@@ -20,6 +20,10 @@ MJ_LAYOUT_XMAJOR, MJ_LAYOUT_ROWMAJOR, MJ_LAYOUT_PLANAR_XMAJOR, MJ_LAYOUT_PLANAR_
 MJ_FLAG_KEEP_COEF, MJ_FLAG_KEEP_PLANES, MJ_FLAG_KEEP_IDCT, MJ_FLAG_EXACT_ONLY, MJ_FLAG_SPEC_REFINE = 1, 2, 4, 8, 16
 MJ_FLAG_GPU_SEGMENT = 32
 MJ_FLAG_NO_SYNC = 64
+MJ_DTYPE_U8, MJ_DTYPE_F16, MJ_DTYPE_BF16, MJ_DTYPE_F32 = 0, 1, 2, 3
+# the element types of a model-ready output (mj_output_desc.dtype) by the name NumPy and torch share
+DTYPES = {"uint8": MJ_DTYPE_U8, "float16": MJ_DTYPE_F16, "bfloat16": MJ_DTYPE_BF16, "float32": MJ_DTYPE_F32}
+DTYPE_BYTES = {"uint8": 1, "float16": 2, "bfloat16": 2, "float32": 4}
 
 # every symbol include/mijpeg.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -30,6 +34,7 @@ EXPORTS = (
     "mj_decode_baseline_batch", "mj_idct_batch", "mj_plan_time_stages", "mj_plan_time_execute", "mj_plan_idct_levels", "mj_host_idct_table", "mj_host_assemble", "mj_plan_stage1_form", "mj_set_option", "mj_get_option", "mj_debug_stage1_form", "mj_debug_fused_shape", "mj_debug_count_tables",
     "mj_device_copy_rate", "mj_context_launch_clock", "mj_debug_prog_split", "mj_debug_fused_applies", "mj_plan_tune_placement",
     "mj_plan_create_resized", "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table",
+    "mj_plan_create_resized_as", "mj_host_normalize_table",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -81,6 +86,12 @@ class RoiC(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+class OutputDescC(ctypes.Structure):
+    """mj_output_desc: element type, normalisation and mirror flags of a model-ready output."""
+    _fields_ = [("dtype", ctypes.c_int32), ("normalize", ctypes.c_int32), ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3),
+                ("mirror", ctypes.c_void_p)]
+
+
 class PlanInfoC(ctypes.Structure):
     _fields_ = [("total_blocks", ctypes.c_int64), ("total_mcus", ctypes.c_int64), ("total_pixels", ctypes.c_int64),
                 ("rgb_bytes", ctypes.c_int64), ("entropy_bytes", ctypes.c_int64)]
@@ -119,6 +130,9 @@ def load_library():
     L.mj_plan_create.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(vp)]
     L.mj_plan_create_roi.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), ctypes.POINTER(vp)]
     L.mj_plan_create_resized.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(vp)]
+    L.mj_plan_create_resized_as.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(OutputDescC),
+                                            ctypes.POINTER(vp)]
+    L.mj_host_normalize_table.argtypes = [i32, ctypes.c_float, ctypes.c_float, vp]
     L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
     L.mj_plan_time_resize.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -243,6 +257,34 @@ def resize_table(in_size: int, out_size: int):
     return xmin, count, taps
 
 
+def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarray:
+    """mj_host_normalize_table (host only): the 256 bit patterns (uint16 for "float16" / "bfloat16", uint32 for "float32") one
+    component's resized bytes 0..255 are stored as with this mean and std (tools/normalize_model.py: table_bits)."""
+    if dtype not in DTYPES or dtype == "uint8":
+        raise ValueError(f"mj_host_normalize_table: no float dtype {dtype!r}")
+    out = np.zeros(256, dtype=np.uint32 if dtype == "float32" else np.uint16)
+    if load_library().mj_host_normalize_table(DTYPES[dtype], float(mean), float(std), _ptr(out)) != MJ_OK:
+        raise ValueError("mj_host_normalize_table: mean must be finite, std finite and > 0")
+    return out
+
+
+def output_desc(output):
+    """(mj_output_desc, what it points to) from (dtype name, mean or None, std or None, mirror flags or None) — mean and std
+    one float per component."""
+    dtype, mean, std, mirror = output
+    d = OutputDescC()
+    d.dtype = DTYPES[dtype]
+    d.normalize = 0 if mean is None else 1
+    for c in range(3):
+        d.mean[c] = float(mean[min(c, len(mean) - 1)]) if mean is not None else 0.0
+        d.std[c] = float(std[min(c, len(std) - 1)]) if std is not None else 1.0
+    flags = None
+    if mirror is not None:
+        flags = np.ascontiguousarray(mirror, dtype=np.uint8)
+        d.mirror = flags.ctypes.data if flags.size else None
+    return d, flags
+
+
 class UnknownOption(ValueError):
     """mj_set_option / mj_get_option: no such option in this library."""
 
@@ -324,9 +366,12 @@ class Plan:
     """mj_plan over a prepared batch (see batch.PreparedBatch).  rois: None, or one (x, y, width, height) per image —
     a window plan (mj_plan_create_roi) whose output for every image is that window.  size: None, or (width, height) — a
     resized plan (mj_plan_create_resized) whose output is one dense array of every image (or window) at that size; slots:
-    with size, (slot of every image, slots of the array) when the plan fills part of a larger array."""
+    with size, (slot of every image, slots of the array) when the plan fills part of a larger array.  output: with size, None
+    (the resized bytes) or (dtype name, mean or None, std or None, mirror flag per image or None) — a model-ready output
+    (mj_plan_create_resized_as): elements of that type, normalised, flagged images mirrored; info.rgb_bytes is then in bytes
+    of that type."""
 
-    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None):
+    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -338,8 +383,17 @@ class Plan:
             if slots is not None:
                 sl = np.ascontiguousarray(slots[0], dtype=np.int32)
                 n_slots = int(slots[1])
-            ctx.check(ctx.lib.mj_plan_create_resized(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
-                                                     ctypes.byref(h)))
+            if output is None:
+                ctx.check(ctx.lib.mj_plan_create_resized(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
+                                                         ctypes.byref(h)))
+            else:
+                desc, flags = output_desc(output)
+                if flags is not None and flags.size != batch_c.n_images:
+                    raise ValueError(f"output: {flags.size} mirror flags for {batch_c.n_images} images")
+                ctx.check(ctx.lib.mj_plan_create_resized_as(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl),
+                                                            n_slots, ctypes.byref(desc), ctypes.byref(h)))
+        elif output is not None:
+            raise ValueError("output needs size: only a resized plan has a dense output")
         elif rois is None:
             ctx.check(ctx.lib.mj_plan_create(ctx.handle, ctypes.byref(batch_c), ctypes.byref(h)))
         else:

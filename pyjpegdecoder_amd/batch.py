@@ -398,6 +398,118 @@ def one_component_count(ncomps: Sequence[int]) -> int:
     return int(ncomps[0])
 
 
+def dtype_name(dtype) -> str:
+    """"uint8", "float16", "bfloat16" or "float32" from such a name or the torch.dtype / numpy.dtype object of that name
+    (ValueError for anything else)."""
+    name = dtype if isinstance(dtype, str) else None
+    if name is None:
+        text = str(dtype)
+        if text.startswith("torch."):
+            name = text[len("torch."):]
+        else:
+            try:
+                name = np.dtype(dtype).name
+            except TypeError:
+                name = text
+    if name not in B.DTYPES:
+        raise ValueError(f"dtype must be one of {', '.join(B.DTYPES)} (a name, a torch.dtype or a numpy.dtype), not {dtype!r}")
+    return name
+
+
+@dataclass
+class OutputSpec:
+    """What a decode to a fixed size stores instead of the resized bytes (:func:`normalize_output`): elements of ``dtype``;
+    ``mean`` / ``std`` one float per component, or both None (value / 255 for a float dtype); ``mirror`` one bool per file of
+    the call, or None."""
+    dtype: str
+    mean: Optional[Tuple[float, ...]] = None
+    std: Optional[Tuple[float, ...]] = None
+    mirror: Optional[List[bool]] = None
+
+    def for_files(self, idxs: Sequence[int]) -> "OutputSpec":
+        """the same output for some files of the call: their flags go with them"""
+        return OutputSpec(self.dtype, self.mean, self.std, [self.mirror[i] for i in idxs] if self.mirror is not None else None)
+
+    def plan_output(self, idxs: Optional[Sequence[int]] = None):
+        """``output`` of :class:`_binding.Plan` for a plan of these files (None: all, in order)"""
+        m = self.mirror if idxs is None or self.mirror is None else [self.mirror[i] for i in idxs]
+        return (self.dtype, self.mean, self.std, m)
+
+    @property
+    def numpy_dtype(self) -> np.dtype:
+        return np.dtype(self.dtype)
+
+    @property
+    def torch_dtype(self):
+        import torch
+        return getattr(torch, self.dtype)
+
+
+def normalize_output(dtype, normalize, mirror, size, n_files: Optional[int] = None, ncomp: Optional[int] = None,
+                     host: bool = False) -> Optional[OutputSpec]:
+    """The model-ready output of a decode to a fixed size, checked: None when the call asks for none (the resized bytes, as
+    without these arguments), else an :class:`OutputSpec`.
+
+    ``dtype``: None, "uint8", "float16", "bfloat16", "float32" or the torch / numpy dtype of that name (``host``: the NumPy
+    route, which has no bfloat16).  ``normalize``: None or (mean, std), each one float or one per component (``ncomp``; a
+    scalar stands for all), in units of value / 255; it needs a float dtype and makes a missing one "float32"; std > 0 and
+    both finite as float32.  ``mirror``: None, one bool, or one bool per file (``n_files``).  All of them need ``size``.
+    ``n_files`` / ``ncomp`` None: not known yet — everything but the lengths is checked.  ValueError otherwise."""
+    if dtype is None and normalize is None and mirror is None:
+        return None
+    if size is None:
+        raise ValueError("dtype, normalize and mirror need size=(width, height): without it the outputs are ragged and stay uint8 "
+                         "(files that share one size: pass that size, which the resize leaves as it is)")
+    name = dtype_name(dtype) if dtype is not None else ("float32" if normalize is not None else "uint8")
+    if host and name == "bfloat16":
+        raise ValueError("dtype bfloat16: NumPy has no such type; decode_device returns torch.bfloat16")
+    mean = std = None
+    if normalize is not None:
+        if name == "uint8":
+            raise ValueError("normalize needs a float dtype (float32, float16 or bfloat16), not uint8")
+        if not isinstance(normalize, (tuple, list)) or len(normalize) != 2:
+            raise ValueError(f"normalize must be (mean, std), not {normalize!r}")
+
+        def per_component(what, v):
+            if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool):
+                vals = [float(v)] * (ncomp or 1)
+            else:
+                try:
+                    vals = [float(x) for x in v]
+                except (TypeError, ValueError):
+                    raise ValueError(f"normalize: {what} must be one float or one per component, not {v!r}") from None
+                if ncomp is not None and len(vals) != ncomp or not vals or len(vals) > 3:
+                    raise ValueError(f"normalize: {what} has {len(vals)} entries for files of {ncomp if ncomp is not None else '1 or 3'} "
+                                     f"component(s)")
+            return vals
+        mean, std = per_component("mean", normalize[0]), per_component("std", normalize[1])
+        with np.errstate(over="ignore"):
+            m32, s32 = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
+        if not np.isfinite(m32).all():
+            raise ValueError(f"normalize: mean must be finite, not {normalize[0]!r}")
+        if not (np.isfinite(s32).all() and (s32 > 0).all()):
+            raise ValueError(f"normalize: std must be finite and > 0 (as float32), not {normalize[1]!r}")
+        mean, std = tuple(mean), tuple(std)
+    flags = None
+    if mirror is not None:
+        def flag(v) -> bool:
+            if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+                return bool(v)
+            raise ValueError(f"mirror must be None, one bool or one bool per file, not {mirror!r}")
+        if isinstance(mirror, (bool, np.bool_)):
+            flags = [bool(mirror)] * (n_files if n_files is not None else 1)
+        else:
+            try:
+                flags = [flag(v) for v in (mirror.tolist() if hasattr(mirror, "tolist") else mirror)]
+            except TypeError:
+                raise ValueError(f"mirror must be None, one bool or one bool per file, not {mirror!r}") from None
+            if n_files is not None and len(flags) != n_files:
+                raise ValueError(f"mirror has {len(flags)} entries for {n_files} files")
+    if name == "uint8" and flags is None:
+        return None
+    return OutputSpec(name, mean, std, flags)
+
+
 def normalize_rois(rois, dims: Sequence[Tuple[int, int]]) -> Optional[List[Tuple[int, int, int, int]]]:
     """The windows of a region-of-interest decode, one (x, y, width, height) per file, checked against the files' (width,
     height) — x along the width, y along the height.  ``rois``: None (whole images: returns None), one (x, y, width, height)
@@ -512,24 +624,28 @@ class BatchDecoder:
             off += n
         return out
 
-    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None):
+    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
         on the GPU — Pillow's ``resize(size, Image.BILINEAR)`` of it, byte for byte — and ONE array of shape ``(len(files),) +
-        shape of one image`` instead of a list."""
+        shape of one image`` instead of a list.  With ``size``, ``dtype`` / ``normalize=(mean, std)`` / ``mirror`` make that array
+        model-ready in the same launch (:func:`normalize_output`): float32 or float16 elements, torchvision's
+        ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes bit for bit, flagged files flipped along the width."""
         if rois is not None and return_seams:
             raise ValueError("rois and return_seams do not go together: the seam outputs are whole-image")
         size = normalize_size(size)
         if size is not None and return_seams:
             raise ValueError("size and return_seams do not go together: the seam outputs are at the files' own sizes")
+        normalize_output(dtype, normalize, mirror, size, host=True)       # (what needs no file: before any is parsed)
         gpu_segment = self._gpu_segment_for(files)
         parsed = [parse_jpeg(f, headers_only=gpu_segment) for f in files]
         wins = normalize_rois(rois, [(p.image_width, p.image_height) for p in parsed])
-        dense = None
+        dense = output = None
         if size is not None:
             nc = one_component_count([len(p.color_components) for p in parsed])
-            dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=np.uint8)
+            output = normalize_output(dtype, normalize, mirror, size, len(files), nc, host=True)
+            dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=output.numpy_dtype if output else np.uint8)
         groups: Dict[tuple, List[int]] = {}
         for i, p in enumerate(parsed):
             check_supported(p)
@@ -544,7 +660,8 @@ class BatchDecoder:
             idxs, extra = work.pop(0)
             prep = prepare_batch([files[i] for i in idxs], self.layout, flags | extra, [parsed[i] for i in idxs])
             sub = [wins[i] for i in idxs] if wins is not None else None
-            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)}, rois=sub, size=size)
+            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)}, rois=sub, size=size,
+                          output=output.plan_output(idxs) if output else None)
             try:
                 plan.execute()
                 plan.sync()
@@ -562,7 +679,7 @@ class BatchDecoder:
                     out["status"][[k for k, i in enumerate(idxs) if i in again]] = 0
                 raise_for_status(out["status"])
                 if dense is not None:
-                    imgs = out["rgb"].reshape((len(idxs),) + dense.shape[1:])
+                    imgs = out["rgb"].view(dense.dtype).reshape((len(idxs),) + dense.shape[1:])
                     for k, i in enumerate(idxs):
                         if i not in redo and i not in again:
                             dense[i] = imgs[k]
@@ -593,7 +710,8 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, _dest=None):
+    def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
+                      mirror=None, _dest=None, _output=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -606,20 +724,28 @@ class BatchDecoder:
         ``rois`` as in :meth:`decode`: the windows are checked against the files' headers before any GPU work.
         ``size=(width, height)``: ONE ``torch.uint8`` tensor of shape ``(len(files),) + shape of one image`` — every image (or
         window) resized as in :meth:`decode`; files of several kinds are still one plan per kind, and every plan writes its
-        images straight into their slots of that tensor."""
+        images straight into their slots of that tensor.
+        ``dtype`` ("uint8", "float32", "float16", "bfloat16" or the torch / numpy dtype), ``normalize=(mean, std)`` and
+        ``mirror`` (one bool, or one per file), all with ``size``: the tensor a model takes, out of the same resize launch — its
+        elements are torchvision's ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes (mean 0, std 1 without
+        ``normalize``), computed in float32 and converted with ``.to(dtype)``, bit for bit; a flagged file's image is the
+        un-flagged result flipped along its width axis (:func:`normalize_output`)."""
         import torch
         wins = None
         size = normalize_size(size)
+        output = _output if _output is not None else normalize_output(dtype, normalize, mirror, size)
         dest = slots = None                     # size=: the one tensor, and the slot of every file in it
         if size is not None:
             info = [_image_info(f) for f in files]
             nc = one_component_count([t[2] for t in info])
+            if _output is None:
+                output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
             if rois is not None:
                 wins = normalize_rois(rois, [t[:2] for t in info])
             if _dest is not None:               # (a second round of some files of a larger call: their slots of its tensor)
                 dest, slots = _dest
             else:
-                dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=torch.uint8,
+                dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=output.torch_dtype if output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
                 slots = list(range(len(files)))
         elif rois is not None:
@@ -631,7 +757,8 @@ class BatchDecoder:
             cut = [n * i // parts for i in range(parts + 1)]
             out: List["torch.Tensor"] = []
             for part in self._device_iter(((files[cut[i]:cut[i + 1]], wins[cut[i]:cut[i + 1]] if wins is not None else None,
-                                            (dest, slots[cut[i]:cut[i + 1]]) if dest is not None else None)
+                                            (dest, slots[cut[i]:cut[i + 1]]) if dest is not None else None,
+                                            output.for_files(range(cut[i], cut[i + 1])) if output else None)
                                            for i in range(parts)), depth=2, size=size):
                 if dest is None:
                     out += part
@@ -693,7 +820,8 @@ class BatchDecoder:
                         d_blob = torch.from_numpy(prep.blob).to(dev)
                     plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(idxs)},
                                   rois=[wins[i] for i in idxs] if wins is not None else None, size=size,
-                                  slots=([slots[i] for i in idxs], dest.shape[0]) if dest is not None else None)
+                                  slots=([slots[i] for i in idxs], dest.shape[0]) if dest is not None else None,
+                                  output=output.plan_output(idxs) if output else None)
                     flying.append((idxs, prep, plan, None, d_blob))
                     d_rgb = dest if dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     flying[-1] = (idxs, prep, plan, d_rgb, d_blob)
@@ -749,7 +877,7 @@ class BatchDecoder:
                     item[2].close()
         return results if dest is None else dest
 
-    def decode_device_iter(self, batches, depth=2, size=None):
+    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -761,13 +889,37 @@ class BatchDecoder:
         idled meanwhile: 512 x 1080p took the front end's 4.3 ms PLUS the upload's 6.1 ms per batch; with two the three —
         host threads, copy engine, GPU — run side by side and the batch takes what the slowest of them takes.  Batches the front
         end declines are decoded by :meth:`decode_device` in place, behind everything in flight (no overlap for those).
-        ``size=(width, height)``: one tensor per batch, as :meth:`decode_device` returns it with ``size``."""
-        yield from self._device_iter(((files, None, None) for files in batches), depth, normalize_size(size))
+        ``size=(width, height)``: one tensor per batch, as :meth:`decode_device` returns it with ``size``; ``dtype`` and
+        ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
+        batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file)."""
+        size = normalize_size(size)
+        per_batch = mirror is not None and not isinstance(mirror, (bool, np.bool_))
+        normalize_output(dtype, normalize, None if per_batch else mirror, size)      # (what needs no file: before any work)
+        if per_batch and size is None:
+            raise ValueError("dtype, normalize and mirror need size=(width, height)")
+        flags = iter(mirror) if per_batch else None
+
+        def triples():
+            for files in batches:
+                files = list(files)
+                m = mirror
+                if flags is not None:
+                    try:
+                        m = next(flags)
+                    except StopIteration:
+                        raise ValueError("mirror yields fewer entries than there are batches") from None
+                out = None
+                if size is not None and (dtype is not None or normalize is not None or m is not None):
+                    nc = one_component_count([_image_info(f)[2] for f in files])
+                    out = normalize_output(dtype, normalize, m, size, len(files), nc)
+                yield files, None, None, out
+        yield from self._device_iter(triples(), depth, size)
 
     def _device_iter(self, batches, depth=2, size=None):
-        """:meth:`decode_device_iter` over (files, windows or None, destination or None) triples (windows: normalize_rois' list
-        for those files; destination, with ``size``: (tensor, slot of every file in it) — None: a tensor of the batch's own,
-        which is what the batch yields)."""
+        """:meth:`decode_device_iter` over (files, windows or None, destination or None, output or None) tuples (windows:
+        normalize_rois' list for those files; destination, with ``size``: (tensor, slot of every file in it) — None: a tensor of
+        the batch's own, which is what the batch yields; output: the batch's :class:`OutputSpec`, its mirror flags one per file
+        of the batch)."""
         import collections
         import torch
         dev = torch.device("cuda", self.ctx.device)
@@ -803,24 +955,25 @@ class BatchDecoder:
             if again.size:                                        # only the files concerned take the long way (host parse)
                 redo = self.decode_device([job[1][int(i)] for i in again], parts=1,
                                           rois=[job[2][int(i)] for i in again] if job[2] is not None else None, size=size,
-                                          _dest=(out, [job[3][int(i)] for i in again]) if size is not None else None)
+                                          _dest=(out, [job[3][int(i)] for i in again]) if size is not None else None,
+                                          _output=job[4].for_files([int(i) for i in again]) if job[4] else None)
                 if size is None:
                     for i, img in zip(again, redo):
                         out[int(i)] = img
             return out
 
-        def destination(files, dest):
+        def destination(files, dest, output):
             """with ``size``: (tensor, slots) a batch's plan writes — the caller's, or a tensor of the batch's own"""
             if size is None or dest is not None:
                 return dest
             nc = one_component_count([_image_info(f)[2] for f in files])
-            return (torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=torch.uint8, device=dev),
-                    list(range(len(files))))
+            return (torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=output.torch_dtype if output else torch.uint8,
+                                device=dev), list(range(len(files))))
 
         try:
-            for files, wins, dest in batches:
+            for files, wins, dest, output in batches:
                 files = list(files)
-                dest = destination(files, dest)
+                dest = destination(files, dest, output)
                 prep = None
                 if self.gpu_segment and self.native_host and files:
                     buf, turn = turn, (turn + 1) % (depth + 1)
@@ -835,14 +988,15 @@ class BatchDecoder:
                 if prep is None:
                     while pending:
                         yield collect(pending.popleft())
-                    yield self.decode_device(files, rois=wins, parts=1, size=size, _dest=dest)
+                    yield self.decode_device(files, rois=wins, parts=1, size=size, _dest=dest, _output=output)
                     continue
                 with torch.cuda.stream(copy_stream):
                     d_blob = pinned[buf][:prep.blob.size].to(dev, non_blocking=True)
                     uploaded[buf] = torch.cuda.Event()
                     uploaded[buf].record(copy_stream)
                 plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(files)}, rois=wins, size=size,
-                              slots=(dest[1], dest[0].shape[0]) if dest is not None else None)
+                              slots=(dest[1], dest[0].shape[0]) if dest is not None else None,
+                              output=output.plan_output() if output else None)
                 try:
                     # (both tensors outlive the kernels that touch them: they stay in `pending` until the plan has been collected)
                     d_rgb = dest[0] if dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
@@ -854,7 +1008,7 @@ class BatchDecoder:
                 except BaseException:
                     plan.close()
                     raise
-                pending.append(((plan, prep, d_rgb, d_blob), files, wins, dest[1] if dest is not None else None))
+                pending.append(((plan, prep, d_rgb, d_blob), files, wins, dest[1] if dest is not None else None, output))
                 while len(pending) > depth:
                     yield collect(pending.popleft())
             while pending:

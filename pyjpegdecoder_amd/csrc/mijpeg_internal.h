@@ -390,11 +390,22 @@ struct ResizeArgs {
     int32_t n_images, ow, oh, layout;
     int32_t tr, tc, tiles_x, tiles_y;         // output rows / columns per tile, tiles per image
     int32_t t_pitch, tab_off, stage_off, stage_bytes, lds_bytes;    // the workgroup's LDS (resize.hip)
+    // the output element (mj_plan_create_resized_as): esize 1 stores the resized byte itself; 2 / 4 store lut[c * 256 + byte],
+    // the byte's float16 / bfloat16 / float32 bit pattern, which every workgroup first copies to lut_off of its LDS
+    // mirror: NULL, or one byte per image, != 0: that image is stored flipped along the width axis, column out_width - 1 - x
+    // (an array of its own, read by the mirror instances only: the image record keeps its 32 bytes, and with them the plain
+    // instances the code they were)
+    const void *lut;
+    const uint8_t *mirror;
+    int32_t esize, lut_off;
 };
 constexpr int64_t kResizeGridX = 1 << 20;      // workgroups along x of the resize launch's grid (the rest along y)
 int resize_axis_ksize(int in_size, int out_size);
 void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride);
 hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp);
+// bits[v] = the bit pattern (in the low esize bytes) of resized byte v as an MJ_DTYPE_F16 / BF16 / F32 element:
+// fl32(fl32(fl32(v) / 255 - mean) / std), then rounded to nearest even into the 16-bit types (tools/normalize_model.py)
+void build_normalize_table(int dtype, float mean, float std, uint32_t *bits);
 // dst[0 .. bytes) = src[0 .. bytes), sixteen bytes per lane (bytes a multiple of 16): the plain copy the rooflines are held against
 hipError_t launch_copy16(hipStream_t stream, const void *src, void *dst, int64_t bytes, int variant);     // variant 0 .. copy16_variants() - 1: launch shapes
 int copy16_variants();

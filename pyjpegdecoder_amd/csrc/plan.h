@@ -264,6 +264,8 @@ struct mj_plan {
     int64_t src_bytes = 0;
     mj::DevResizeImage *d_rz_images = nullptr;
     int32_t *d_rz_tabs = nullptr;
+    uint8_t *d_rz_mirror = nullptr;        // ... with a mirror flag set: one byte per image
+    uint8_t *d_rz_lut = nullptr;           // mj_plan_create_resized_as with a float dtype: the output table (info.rgb_bytes: bytes of that type)
     mj::ResizeArgs rz{};
 };
 

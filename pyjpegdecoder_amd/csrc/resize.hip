@@ -17,6 +17,15 @@
 //     where they start); the height pass then gathers along the rows of T.
 // Planar plans read the same interleaved source (stage 2 writes it; the plane separation of a plain planar plan is skipped)
 // and only store elsewhere.
+//
+// Model-ready output (mj_plan_create_resized_as): the height pass ends in a byte v of component c, and what it stores is a
+// pure function of (c, v) — torchvision's Normalize(mean, std)(to_tensor(img)) in float32, operation by operation, then
+// rounded to nearest even for the 16-bit types (tools/normalize_model.py).  The host evaluates it for the 256 x C pairs
+// (build_normalize_table) and the kernels' 2- and 4-byte instances store lut[c][v] out of LDS: exact by construction, no
+// float arithmetic on the device.  float16 and bfloat16 share the 2-byte instance (the table holds the bits).  Mirror is a
+// per-image flag (ResizeArgs::mirror) of the mirror instances: the element goes to column out_width - 1 - x.  A lane still stores one element
+// and consecutive lanes consecutive elements of the output's contiguous axis, so a wavefront's store is one run of 64, 128
+// or 256 bytes (descending for a mirrored image of a row-major layout); the plain uint8 instances are the code they were.
 #include <math.h>
 
 #include <map>
@@ -91,9 +100,28 @@ __device__ __forceinline__ unsigned clip8(unsigned acc) {
     return v > 255u ? 255u : v;
 }
 
+// the element a finished byte v of component c is stored as: the byte, or its entry of the workgroup's table
+template <typename OutT>
+__device__ __forceinline__ OutT out_value(const OutT *lut, int c, unsigned v) {
+    if constexpr (sizeof(OutT) == 1) return (OutT)v;
+    else return lut[c * 256 + v];
+}
+
+// every workgroup's copy of the plan's table (256 x C elements behind the kernel's other LDS); the caller's barrier follows
+template <int C, typename OutT>
+__device__ __forceinline__ const OutT *stage_lut(const ResizeArgs &a, unsigned char *smem, int tid) {
+    if constexpr (sizeof(OutT) == 1) return nullptr;
+    else {
+        OutT *lut = reinterpret_cast<OutT *>(smem + a.lut_off);
+        const OutT *g = static_cast<const OutT *>(a.lut);
+        for (int i = tid; i < 256 * C; i += 256) lut[i] = g[i];
+        return lut;
+    }
+}
+
 // Row-major source.  LDS: T [t_rows][t_pitch] | per output column of the tile: first source column (relative), taps, the
-// taps themselves [tc][ksx] | one staging row per wavefront.
-template <int C>
+// taps themselves [tc][ksx] | one staging row per wavefront | the output table (2- and 4-byte elements).
+template <int C, typename OutT = unsigned char, bool MIRROR = false>
 __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tiles = a.tiles_x * a.tiles_y;
@@ -113,6 +141,7 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
     unsigned char *stage = smem + a.stage_off + wave * a.stage_bytes;
     for (int i = tid; i < ncols; i += 256) { lx_lo[i] = (X.lo[ox0 + i] - xa) * C; lx_cnt[i] = X.cnt[ox0 + i]; }
     for (int i = tid; i < ncols * X.ks; i += 256) lx_k[i] = X.k[(int64_t)ox0 * X.ks + i];
+    const OutT *lut = stage_lut<C, OutT>(a, smem, tid);
     __syncthreads();
     const unsigned char *src = a.src + im.src_off;
     const int seg = (xb - xa) * C;
@@ -141,8 +170,9 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     __syncthreads();
-    // height pass: consecutive lanes take consecutive bytes of an output row (of a plane's row for planar plans)
-    unsigned char *dst = a.dst + im.dst_off;
+    // height pass: consecutive lanes take consecutive elements of an output row (of a plane's row for planar plans)
+    OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
+    const bool flip = MIRROR && a.mirror[img] != 0;
     const int orows = oy1 - oy0, total = orows * ne;
     const bool planar = a.layout >= 2 && C > 1;
     for (int i = tid; i < total; i += 256) {
@@ -155,13 +185,15 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
         const unsigned char *s = T + (Y.lo[oy] - ya) * a.t_pitch + oxl * C + c;
         unsigned acc = 1u << 21;
         for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * a.t_pitch]);
-        dst[out_index(a, C, ox0 + oxl, oy, c)] = (unsigned char)clip8(acc);
+        const int ox = ox0 + oxl;
+        dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy, c)] = out_value<OutT>(lut, c, clip8(acc));
     }
 }
 
 // X-major source.  LDS: T [tc][t_pitch] (one row per output column: the bytes (y, c) of the source rows the tile needs,
-// t_pitch a multiple of 16) | per output row of the tile: first source row (relative), taps, the taps themselves [tr][ksy].
-template <int C>
+// t_pitch a multiple of 16) | per output row of the tile: first source row (relative), taps, the taps themselves [tr][ksy] |
+// the output table (2- and 4-byte elements).
+template <int C, typename OutT = unsigned char, bool MIRROR = false>
 __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tiles = a.tiles_x * a.tiles_y;
@@ -179,6 +211,7 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
     const int tid = threadIdx.x;
     for (int i = tid; i < orows; i += 256) { ly_lo[i] = (Y.lo[oy0 + i] - ya) * C; ly_cnt[i] = Y.cnt[oy0 + i]; }
     for (int i = tid; i < orows * Y.ks; i += 256) ly_k[i] = Y.k[(int64_t)oy0 * Y.ks + i];
+    const OutT *lut = stage_lut<C, OutT>(a, smem, tid);
     const unsigned char *src = a.src + im.src_off;
     // width pass: 16 consecutive bytes of a column per lane, the taps' columns one after the other.  (The last chunk of a
     // column reads up to 15 bytes behind the rows the tile needs — the next column's, or the buffer's padding — into T's
@@ -207,8 +240,9 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
         *reinterpret_cast<u32x4 *>(T + oxl * a.t_pitch + 16 * j) = o;
     }
     __syncthreads();
-    // height pass: consecutive lanes take consecutive bytes of an output column (of a plane's column for planar plans)
-    unsigned char *dst = a.dst + im.dst_off;
+    // height pass: consecutive lanes take consecutive elements of an output column (of a plane's column for planar plans)
+    OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
+    const bool flip = MIRROR && a.mirror[img] != 0;
     const int ne = orows * C, total = ncols * ne;
     const bool planar = a.layout >= 2 && C > 1;
     for (int i = tid; i < total; i += 256) {
@@ -220,8 +254,19 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
         const unsigned char *s = T + oxl * a.t_pitch + ly_lo[oyl] + c;
         unsigned acc = 1u << 21;
         for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * C]);
-        dst[out_index(a, C, ox0 + oxl, oy0 + oyl, c)] = (unsigned char)clip8(acc);
+        const int ox = ox0 + oxl;
+        dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy0 + oyl, c)] = out_value<OutT>(lut, c, clip8(acc));
     }
+}
+
+// the instance of one output element and mirror mode: source order and component count picked at run time
+template <typename OutT, bool MIRROR>
+void launch_instance(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block) {
+    const bool xmajor = (a.layout & 1) == 0;
+    if (xmajor && ncomp == 3) hipLaunchKernelGGL((k_resize_xmajor<3, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
+    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor<1, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
+    else if (ncomp == 3) hipLaunchKernelGGL((k_resize_rowmajor<3, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
+    else hipLaunchKernelGGL((k_resize_rowmajor<1, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
 }
 
 }  // namespace
@@ -231,12 +276,53 @@ hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp) {
     // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
     const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
-    const bool xmajor = (a.layout & 1) == 0;
-    if (xmajor && ncomp == 3) hipLaunchKernelGGL(k_resize_xmajor<3>, grid, block, a.lds_bytes, stream, a);
-    else if (xmajor) hipLaunchKernelGGL(k_resize_xmajor<1>, grid, block, a.lds_bytes, stream, a);
-    else if (ncomp == 3) hipLaunchKernelGGL(k_resize_rowmajor<3>, grid, block, a.lds_bytes, stream, a);
-    else hipLaunchKernelGGL(k_resize_rowmajor<1>, grid, block, a.lds_bytes, stream, a);
+    // (a plan of mj_plan_create_resized: esize 1, no mirror — the instances that were there before the others)
+    if (a.esize == 4) { if (a.mirror) launch_instance<uint32_t, true>(stream, a, ncomp, grid, block); else launch_instance<uint32_t, false>(stream, a, ncomp, grid, block); }
+    else if (a.esize == 2) { if (a.mirror) launch_instance<uint16_t, true>(stream, a, ncomp, grid, block); else launch_instance<uint16_t, false>(stream, a, ncomp, grid, block); }
+    else if (a.mirror) launch_instance<unsigned char, true>(stream, a, ncomp, grid, block);
+    else launch_instance<unsigned char, false>(stream, a, ncomp, grid, block);
     return hipGetLastError();
+}
+
+// ---- host: the output table -------------------------------------------------------------------------------------------
+namespace {
+
+uint32_t float_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+
+// float32 -> float16, round to nearest even (overflow to infinity, gradual underflow)
+uint16_t half_bits(float f) {
+    const uint32_t x = float_bits(f), sign = (x >> 16) & 0x8000u, m = x & 0x7FFFFFFFu;
+    if (m > 0x7F800000u) return (uint16_t)(sign | 0x7E00u);                 // NaN
+    if (m >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);                // 65520 and above, infinity
+    if (m < 0x38800000u) {
+        // below 2^-14: adding 0.5 leaves the value in units of 2^-24 — float16's subnormal step — in the low mantissa
+        // bits, rounded to nearest even by the addition itself
+        float a;
+        memcpy(&a, &m, 4);
+        volatile float sum = a + 0.5f;
+        return (uint16_t)(sign | (float_bits(sum) - 0x3F000000u));
+    }
+    const uint32_t r = m - 0x38000000u + 0xFFFu + ((m >> 13) & 1u);         // exponent rebias, then half an ulp (ties to even)
+    return (uint16_t)(sign | (r >> 13));
+}
+
+uint16_t bfloat_bits(float f) {
+    const uint32_t x = float_bits(f);
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((x >> 16) | 0x40u);
+    return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16);
+}
+
+}  // namespace
+
+// Every operation a float32 one, each rounded on its own (this library is built with -ffp-contract=off; the volatiles keep
+// a host compiler from carrying more precision between them).
+void build_normalize_table(int dtype, float mean, float std, uint32_t *bits) {
+    for (int v = 0; v < 256; ++v) {
+        volatile float t = (float)v / 255.0f;
+        volatile float d = t - mean;
+        volatile float y = d / std;
+        bits[v] = dtype == MJ_DTYPE_F32 ? float_bits(y) : dtype == MJ_DTYPE_F16 ? half_bits(y) : bfloat_bits(y);
+    }
 }
 
 }  // namespace mj
@@ -262,6 +348,23 @@ struct AxisHost {
 
 int round16(int64_t v) { return (int)((v + 15) & ~(int64_t)15); }
 
+int dtype_size(int dtype) { return dtype == MJ_DTYPE_U8 ? 1 : dtype == MJ_DTYPE_F32 ? 4 : 2; }
+
+// what mj_plan_create_resized_as and mj_host_normalize_table refuse: nullptr when `o` is fine, else the reason
+const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std) {
+    if (dtype != MJ_DTYPE_U8 && dtype != MJ_DTYPE_F16 && dtype != MJ_DTYPE_BF16 && dtype != MJ_DTYPE_F32) return "dtype is none of MJ_DTYPE_U8 / F16 / BF16 / F32";
+    if (!normalize) return nullptr;
+    if (dtype == MJ_DTYPE_U8) return "normalize needs a float dtype (MJ_DTYPE_U8 stores the resized bytes)";
+    for (int c = 0; c < ncomp; ++c) {
+        if (!std::isfinite(mean[c])) return "mean must be finite";
+        if (!std::isfinite(std[c]) || !(std[c] > 0.0f)) return "std must be finite and > 0";
+    }
+    return nullptr;
+}
+
+int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out);
+
 }  // namespace
 
 extern "C" {
@@ -277,25 +380,58 @@ int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32
     return MJ_OK;
 }
 
+int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
+    if (!out || dtype == MJ_DTYPE_U8 || output_fault(dtype, true, 1, &mean, &std)) return MJ_ERR_INVALID;
+    uint32_t bits[256];
+    mj::build_normalize_table(dtype, mean, std, bits);
+    for (int v = 0; v < 256; ++v) {
+        if (dtype == MJ_DTYPE_F32) static_cast<uint32_t *>(out)[v] = bits[v];
+        else static_cast<uint16_t *>(out)[v] = (uint16_t)bits[v];
+    }
+    return MJ_OK;
+}
+
 int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                            const int32_t *slots, int32_t n_slots, mj_plan **out) {
+    return create_resized("mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, nullptr, out);
+}
+
+int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                              const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
+    return create_resized("mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, output, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
+    // the output description first: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
+    // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
+    const int dtype = output ? output->dtype : MJ_DTYPE_U8;
+    const int nc_check = b && b->n_images > 0 && b->images ? (b->images[0].ncomp == 1 ? 1 : 3) : 3;
+    if (output)
+        if (const char *why = output_fault(dtype, output->normalize != 0, nc_check, output->mean, output->std))
+            return fail(ctx, MJ_ERR_INVALID, "%s: output: %s", fn, why);
     if (!ctx) return MJ_ERR_INVALID;
-    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: NULL argument");
+    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
+    const int esize = dtype_size(dtype);
     if (out_width < 1 || out_height < 1 || out_width > 65535 || out_height > 65535)
-        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: output size %d x %d (both must be 1..65535)", out_width, out_height);
+        return fail(ctx, MJ_ERR_INVALID, "%s: output size %d x %d (both must be 1..65535)", fn, out_width, out_height);
     if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
-        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none");
+        return fail(ctx, MJ_ERR_INVALID, "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none", fn);
     if (!slots) n_slots = b->n_images;
     for (int i = 0; slots && i < b->n_images; ++i)
         if (slots[i] < 0 || slots[i] >= n_slots)
-            return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_resized: image %d: slot %d outside the %d slots of the output", i, slots[i], n_slots);
+            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, slots[i], n_slots);
     mj_plan *p = nullptr;
     // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
     if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
     struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
     const int C = p->ncomp, n = p->n_images;
-    const int64_t out_image = (int64_t)out_width * out_height * C;
+    const int64_t out_image = (int64_t)out_width * out_height * C * esize;      // bytes
     // tap tables: one per distinct source size and axis
     std::map<int, AxisHost> xs, ys;
     std::vector<int32_t> words;
@@ -315,19 +451,23 @@ int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *roi
         return A;
     };
     std::vector<mj::DevResizeImage> ri((size_t)n);
+    std::vector<uint8_t> flags((size_t)n, 0);      // mirror, per image
+    int any_mirror = 0;
     for (int i = 0; i < n; ++i) {
         const int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
         ri[i].src_off = p->h_images[i].rgb_off;
         ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
         ri[i].w = w; ri[i].h = h;
+        if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
         ri[i].xtab = axis(xs, w, out_width).word_off;
         ri[i].ytab = axis(ys, h, out_height).word_off;
-        if (words.size() > ((size_t)1 << 28)) return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_resized: the tap tables of this batch are too large");
+        if (words.size() > ((size_t)1 << 28)) return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: the tap tables of this batch are too large", fn);
     }
     // (a pure function of the tile: what it takes in LDS and where the parts lie; nothing is kept until a tile is chosen)
-    struct Lds { bool ok; int t_pitch, tab_off, stage_off, stage_bytes, total; };
+    struct Lds { bool ok; int t_pitch, tab_off, stage_off, stage_bytes, lut_off, total; };
+    const int lut_bytes = esize > 1 ? 256 * C * esize : 0;
     // The tile: what a workgroup's LDS holds (resize.hip's kernels) must fit 64 KB — the intermediate rows of the tile, the
-    // tile's tap tables, the staging rows — for every source size of the batch.  Tiles shrink until it does: a row-major plan
+    // tile's tap tables, the staging rows, the output table of a 2- or 4-byte element — for every source size of the batch.  Tiles shrink until it does: a row-major plan
     // gives up columns first while a row segment stays 2 KB long (its loads run along the rows), then rows; an x-major plan
     // keeps its rows (its loads run along the columns) and gives up columns.
     const bool xmajor = (p->layout & 1) == 0;
@@ -350,9 +490,9 @@ int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *roi
             tab_bytes = ((int64_t)2 * tc_ + (int64_t)tc_ * ksx) * 4;
             stage = round16((int64_t)sx * C + 32);
         }
-        const int64_t total = t_bytes + round16(tab_bytes) + 4 * stage;
-        if (total > budget) return Lds{false, 0, 0, 0, 0, 0};
-        return Lds{true, pitch, (int)t_bytes, (int)(t_bytes + round16(tab_bytes)), (int)stage, (int)total};
+        const int64_t lut_off = t_bytes + round16(tab_bytes) + 4 * stage, total = lut_off + lut_bytes;
+        if (total > budget) return Lds{false, 0, 0, 0, 0, 0, 0};
+        return Lds{true, pitch, (int)t_bytes, (int)(t_bytes + round16(tab_bytes)), (int)stage, (int)lut_off, (int)total};
     };
     auto fits = [&](int tr_, int tc_) { return lds_for(tr_, tc_).ok; };
     auto seg_bytes = [&](int tc_) { int sx = 0; for (auto &kv : xs) sx = std::max(sx, kv.second.span(tc_)); return sx * C; };
@@ -360,7 +500,7 @@ int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *roi
         const bool cols_first = xmajor ? (tc >= 32 || tr == 1) : (seg_bytes(tc) >= 2048 || tr == 1);
         if (tc > 1 && cols_first) tc = (tc + 1) / 2;
         else if (tr > 1) tr = (tr + 1) / 2;
-        else return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_resized: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds",
+        else return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds", fn,
                          xs.rbegin()->first, ys.rbegin()->first, out_width, out_height);
     }
     // (a small batch: more, smaller tiles, so that the chip has something to do)
@@ -369,13 +509,33 @@ int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *roi
     const Lds lds = lds_for(tr, tc);
     a.tr = tr; a.tc = tc;
     a.t_pitch = lds.t_pitch; a.tab_off = lds.tab_off; a.stage_off = lds.stage_off; a.stage_bytes = lds.stage_bytes; a.lds_bytes = lds.total;
+    a.esize = esize; a.lut_off = lds.lut_off;
     a.tiles_x = (out_width + tc - 1) / tc; a.tiles_y = (out_height + tr - 1) / tr;
     if (n_tiles(tr, tc) > mj::kResizeGridX * (int64_t)65535)
-        return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_resized: %lld tiles are more than one launch takes; split the batch", (long long)n_tiles(tr, tc));
+        return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: %lld tiles are more than one launch takes; split the batch", fn, (long long)n_tiles(tr, tc));
     a.n_images = n; a.ow = out_width; a.oh = out_height; a.layout = p->layout;
     int rc;
     if ((rc = upload(ctx, &p->d_rz_images, ri.data(), ri.size())) != MJ_OK) return rc;
     if ((rc = upload(ctx, &p->d_rz_tabs, words.data(), words.size())) != MJ_OK) return rc;
+    if (any_mirror) {       // (no flag set: the instances without mirror)
+        if ((rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) != MJ_OK) return rc;
+        a.mirror = p->d_rz_mirror;
+    }
+    if (esize > 1) {
+        // the output table, [C][256] elements: the host's arithmetic, which the kernels only look up
+        const bool norm = output->normalize != 0;
+        std::vector<uint8_t> lut((size_t)lut_bytes);
+        for (int c = 0; c < C; ++c) {
+            uint32_t bits[256];
+            mj::build_normalize_table(dtype, norm ? output->mean[c] : 0.0f, norm ? output->std[c] : 1.0f, bits);
+            for (int v = 0; v < 256; ++v) {
+                if (esize == 4) memcpy(&lut[((size_t)c * 256 + v) * 4], &bits[v], 4);
+                else { const uint16_t h = (uint16_t)bits[v]; memcpy(&lut[((size_t)c * 256 + v) * 2], &h, 2); }
+            }
+        }
+        if ((rc = upload(ctx, &p->d_rz_lut, lut.data(), lut.size())) != MJ_OK) return rc;
+        a.lut = p->d_rz_lut;
+    }
     // the un-resized pixels: a plan-owned buffer from the context's cache (64 bytes of slack: the kernels' 16-byte loads may
     // start before and end behind the bytes they use)
     p->src_bytes = p->info.rgb_bytes;
@@ -389,4 +549,4 @@ int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *roi
     return MJ_OK;
 }
 
-}  // extern "C"
+}  // namespace
