@@ -337,7 +337,8 @@ def prepare_batch_native(files: Sequence[bytes], layout: int = B.MJ_LAYOUT_XMAJO
 
 
 def _image_info(raw: bytes) -> Tuple[int, int, int]:
-    """:func:`_image_dims` plus the frame's component count: (width, height, components), for a decode to a fixed size."""
+    """(width, height, components) from a file's frame header (SOF0-SOF15 but DHT / JPG / DAC), walking the marker segments
+    in front of it; anything unusual goes through the parser, which raises the reference's exceptions."""
     pos, n = 2, len(raw)
     if raw[:2] == b"\xFF\xD8":
         while pos + 10 <= n and raw[pos] == 0xFF:
@@ -356,23 +357,8 @@ def _image_info(raw: bytes) -> Tuple[int, int, int]:
 
 
 def _image_dims(raw: bytes) -> Tuple[int, int]:
-    """(width, height) from a file's frame header (SOF0-SOF15 but DHT / JPG / DAC), walking the marker segments in front of
-    it; anything unusual goes through the parser, which raises the reference's exceptions."""
-    pos, n = 2, len(raw)
-    if raw[:2] == b"\xFF\xD8":
-        while pos + 9 <= n and raw[pos] == 0xFF:
-            m = raw[pos + 1]
-            if m == 0xFF:
-                pos += 1
-                continue
-            seg = (raw[pos + 2] << 8) | raw[pos + 3]
-            if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
-                return (raw[pos + 7] << 8) | raw[pos + 8], (raw[pos + 5] << 8) | raw[pos + 6]
-            if m == 0xDA or seg < 2:
-                break
-            pos += 2 + seg
-    p = parse_jpeg(raw, headers_only=True)
-    return p.image_width, p.image_height
+    """(width, height) of :func:`_image_info`."""
+    return _image_info(raw)[:2]
 
 
 def normalize_size(size) -> Optional[Tuple[int, int]]:
@@ -432,8 +418,7 @@ class OutputSpec:
 
     def plan_output(self, idxs: Optional[Sequence[int]] = None):
         """``output`` of :class:`_binding.Plan` for a plan of these files (None: all, in order)"""
-        m = self.mirror if idxs is None or self.mirror is None else [self.mirror[i] for i in idxs]
-        return (self.dtype, self.mean, self.std, m)
+        return (self.dtype, self.mean, self.std, self.mirror if idxs is None else self.for_files(idxs).mirror)
 
     @property
     def numpy_dtype(self) -> np.dtype:
@@ -554,6 +539,91 @@ def raise_for_status(status: np.ndarray):
         raise CorruptedJpeg(f"image {i}: {_STATUS_TEXT.get(int(status[i]), 'decode failed')}")
 
 
+@dataclass
+class _Request:
+    """What one call asks of a set of files: the windows (:func:`normalize_rois`' list, or None), ``size``
+    (:func:`normalize_size`'s, or None), the model-ready output (or None) and, with ``size``, the array or tensor the plans
+    write the images into and every file's slot in it (both None: every plan fills a dense array of its own)."""
+    files: Sequence[bytes]
+    wins: Optional[List[Tuple[int, int, int, int]]] = None
+    size: Optional[Tuple[int, int]] = None
+    output: Optional[OutputSpec] = None
+    dest: object = None
+    slots: Optional[List[int]] = None
+
+    def narrow(self, idxs) -> "_Request":
+        """the same request for some of its files: their windows, slots and mirror flags go with them"""
+        idxs = [int(i) for i in idxs]
+
+        def pick(per_file):
+            return [per_file[i] for i in idxs] if per_file is not None else None
+        return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
+                        self.dest, pick(self.slots))
+
+    def plan_kwargs(self) -> dict:
+        """``rois``, ``size``, ``slots`` and ``output`` of :class:`_binding.Plan` for one plan of all its files, in order"""
+        return {"rois": self.wins, "size": self.size,
+                "slots": (self.slots, self.dest.shape[0]) if self.slots is not None else None,
+                "output": self.output.plan_output() if self.output else None}
+
+
+@dataclass
+class _Work:
+    """One plan still to be made: the files (indices into the call's request), how their batch is assembled — ``prep`` (done
+    already), by the native front end, or else by the Python path from the call's parsed headers — and that plan's extra
+    MJ_FLAG_* bits."""
+    idxs: List[int]
+    prep: Optional[PreparedBatch] = None
+    native: bool = False
+    flags: int = 0
+
+
+@dataclass
+class _Flight:
+    """A submitted plan: the request it serves (``idxs``: where its files sit in the call's request, when it serves a part of
+    one), and the tensors its kernels touch, which stay alive here until the plan has been collected."""
+    req: _Request
+    idxs: Optional[List[int]]
+    prep: PreparedBatch
+    plan: B.Plan
+    d_rgb: object = None
+    d_blob: object = None
+
+
+def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], headers_only: bool) -> List[List[int]]:
+    """Files ``idxs`` sorted into one index list per kind — what can share a plan.  Those that ``parsed`` (index -> ParsedJpeg)
+    does not hold yet are parsed into it (``headers_only`` as asked); every one goes through :func:`check_supported`."""
+    groups: Dict[tuple, List[int]] = {}
+    for i in idxs:
+        p = parsed.get(i)
+        if p is None:
+            p = parsed[i] = parse_jpeg(files[i], headers_only=headers_only)
+        check_supported(p)
+        comps = list(p.color_components.values())
+        key = (p.scan_mode, len(comps), p.headers_only, is_scan_list(p), p.headers_only and p.restart_interval > 0) + (tuple((c.horizontal_sampling, c.vertical_sampling) for c in comps) if len(comps) > 1 else ())
+        groups.setdefault(key, []).append(i)
+    return list(groups.values())
+
+
+def _triage(status: np.ndarray, idxs, files: Optional[Sequence[bytes]] = None, parsed: Optional[Dict[int, ParsedJpeg]] = None):
+    """Sort a plan's per-image status (``idxs``: the call's index of every image).  Returns (tail, unconverged): the files the
+    GPU scan handed back (MJ_ST_TAIL: something other than EOI follows the scan — the host finds their segments) and those whose
+    synchronisation rounds had not settled (MJ_ST_UNCONVERGED: the serial walk, MJ_FLAG_NO_SYNC).  Both go round again, so
+    their entries are zeroed before :func:`raise_for_status` sees the rest.  With ``parsed`` (index -> ParsedJpeg of
+    ``files``) the host parse those files' next round needs is stored there first: what the parser raises comes before what
+    the status says."""
+    idxs = np.asarray(idxs)
+    tail = idxs[status == B.MJ_ST_TAIL].tolist()
+    unconverged = idxs[status == B.MJ_ST_UNCONVERGED].tolist()
+    if parsed is not None:
+        for i in tail + [i for i in unconverged if i not in parsed]:
+            parsed[i] = parse_jpeg(files[i])
+            check_supported(parsed[i])
+    status[(status == B.MJ_ST_TAIL) | (status == B.MJ_ST_UNCONVERGED)] = 0
+    raise_for_status(status)
+    return tail, unconverged
+
+
 class BatchDecoder:
     """Decode lists of baseline JPEG files on one GPU.
 
@@ -616,13 +686,21 @@ class BatchDecoder:
             return list(prep.shapes)
         return [(w[2], w[3], nc) for w, (_, _, nc) in zip(wins, prep.shapes)]
 
-    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None) -> List[np.ndarray]:
+    def _views(self, flat, shapes: Sequence[Tuple[int, int, int]], per_pixel: int = 1) -> list:
+        """Per-image views of a flat buffer (NumPy array or torch tensor) that holds images of ``shapes`` back to back."""
         out, off = [], 0
-        for (w, h, nc) in self._out_shapes(prep, wins):
+        for (w, h, nc) in shapes:
             n = w * h * nc * per_pixel
             out.append(flat[off:off + n].reshape(self._shape(w, h, nc)))
             off += n
         return out
+
+    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None) -> List[np.ndarray]:
+        return self._views(flat, self._out_shapes(prep, wins), per_pixel)
+
+    def _plan(self, req: _Request, prep: PreparedBatch, blob_device_ptr: int = 0) -> B.Plan:
+        """The plan of a request whose files are ``prep``'s, in order."""
+        return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs())
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
@@ -639,54 +717,40 @@ class BatchDecoder:
             raise ValueError("size and return_seams do not go together: the seam outputs are at the files' own sizes")
         normalize_output(dtype, normalize, mirror, size, host=True)       # (what needs no file: before any is parsed)
         gpu_segment = self._gpu_segment_for(files)
-        parsed = [parse_jpeg(f, headers_only=gpu_segment) for f in files]
-        wins = normalize_rois(rois, [(p.image_width, p.image_height) for p in parsed])
-        dense = output = None
+        parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
+        req = _Request(files, normalize_rois(rois, [(p.image_width, p.image_height) for p in parsed.values()]), size)
+        dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
-            nc = one_component_count([len(p.color_components) for p in parsed])
-            output = normalize_output(dtype, normalize, mirror, size, len(files), nc, host=True)
-            dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=output.numpy_dtype if output else np.uint8)
-        groups: Dict[tuple, List[int]] = {}
-        for i, p in enumerate(parsed):
-            check_supported(p)
-            comps = list(p.color_components.values())
-            key = (p.scan_mode, len(comps), p.headers_only, is_scan_list(p), p.headers_only and p.restart_interval > 0) + (tuple((c.horizontal_sampling, c.vertical_sampling) for c in comps) if len(comps) > 1 else ())
-            groups.setdefault(key, []).append(i)
+            nc = one_component_count([len(p.color_components) for p in parsed.values()])
+            req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc, host=True)
+            dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         results: List[Optional[np.ndarray]] = [None] * len(files)
         seams: List[Optional[dict]] = [None] * len(files)
         flags = ((B.MJ_FLAG_KEEP_PLANES | B.MJ_FLAG_KEEP_IDCT) if return_seams else 0) | self.base_flags
-        work = [(idxs, 0) for idxs in groups.values()]
+        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment)]
         while work:
-            idxs, extra = work.pop(0)
-            prep = prepare_batch([files[i] for i in idxs], self.layout, flags | extra, [parsed[i] for i in idxs])
-            sub = [wins[i] for i in idxs] if wins is not None else None
-            plan = B.Plan(self.ctx, prep.to_c(), {"prep": prep, "n_images": len(idxs)}, rois=sub, size=size,
-                          output=output.plan_output(idxs) if output else None)
+            item = work.pop(0)
+            idxs, sub = item.idxs, req.narrow(item.idxs)
+            prep = prepare_batch(sub.files, self.layout, flags | item.flags, [parsed[i] for i in idxs])
+            plan = self._plan(sub, prep)
             try:
                 plan.execute()
                 plan.sync()
                 out = plan.read(rgb=True, coef=return_seams, planes=return_seams, idct=return_seams)
-                redo = [i for k, i in enumerate(idxs) if out["status"][k] == B.MJ_ST_TAIL]
-                if redo:                        # the GPU scan met something other than EOI after the scan: host parse
-                    for i in redo:
-                        parsed[i] = parse_jpeg(files[i])
-                        check_supported(parsed[i])
-                    work.append((redo, extra))
-                    out["status"][[k for k, i in enumerate(idxs) if i in redo]] = 0
-                again = [i for k, i in enumerate(idxs) if out["status"][k] == B.MJ_ST_UNCONVERGED]
-                if again:                       # the synchronisation rounds had not settled: the serial walk for these
-                    work.append((again, extra | B.MJ_FLAG_NO_SYNC))
-                    out["status"][[k for k, i in enumerate(idxs) if i in again]] = 0
-                raise_for_status(out["status"])
+                tail, unconverged = _triage(out["status"], idxs, files, parsed)
+                if tail:
+                    work.append(_Work(tail, flags=item.flags))
+                if unconverged:
+                    work.append(_Work(unconverged, flags=item.flags | B.MJ_FLAG_NO_SYNC))
                 if dense is not None:
                     imgs = out["rgb"].view(dense.dtype).reshape((len(idxs),) + dense.shape[1:])
-                    for k, i in enumerate(idxs):
-                        if i not in redo and i not in again:
-                            dense[i] = imgs[k]
-                    continue
-                imgs = self.split_outputs(prep, out["rgb"], wins=sub)
+                else:
+                    imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins)
                 for k, i in enumerate(idxs):
-                    if i in redo or i in again:
+                    if i in tail or i in unconverged:
+                        continue
+                    if dense is not None:
+                        dense[i] = imgs[k]
                         continue
                     results[i] = imgs[k]
                     if return_seams:
@@ -710,15 +774,42 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
+    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror) -> _Request:
+        """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
+        files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
+        decoder's GPU, one slot per file in order."""
+        req = _Request(files, None, size)
+        if size is not None:
+            import torch
+            info = [_image_info(f) for f in files]
+            nc = one_component_count([t[2] for t in info])
+            req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
+            req.wins = normalize_rois(rois, [t[:2] for t in info])
+            req.dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
+                                   device=torch.device("cuda", self.ctx.device))
+            req.slots = list(range(len(files)))
+        elif rois is not None:
+            req.wins = normalize_rois(rois, [_image_dims(f) for f in files])
+        return req
+
+    def _wait_for_current_stream(self, cur):
+        """An output buffer comes from torch's caching allocator on torch's CURRENT stream (``cur``): a block a consumer has
+        just dropped may still be read by kernels queued there, so the stream that is about to overwrite it — here the
+        context's — waits for the current stream first (the allocator only orders reuse within one stream)."""
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        self.ctx.wait_event(ev.cuda_event)
+
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, _dest=None, _output=None):
+                      mirror=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
 
         With ``segment="gpu"`` a batch of everyday baseline files never meets the Python parser: libmijpeg.so's host
         front end (``mj_host_assemble``) reads the headers and assembles the batch on host threads; whatever it declines
-        takes the Python path below, which raises the reference's exceptions.  A large batch on that route goes as ``parts``
+        takes the Python path, which raises the reference's exceptions.  A large batch on that route goes as ``parts``
         plans of 256 files or more (up to four) through :meth:`decode_device_iter`, so that one part's upload runs under the
         assembly of the next and under the kernels of the one before — inside one call the three would otherwise add up.
         ``rois`` as in :meth:`decode`: the windows are checked against the files' headers before any GPU work.
@@ -730,86 +821,63 @@ class BatchDecoder:
         elements are torchvision's ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes (mean 0, std 1 without
         ``normalize``), computed in float32 and converted with ``.to(dtype)``, bit for bit; a flagged file's image is the
         un-flagged result flipped along its width axis (:func:`normalize_output`)."""
-        import torch
-        wins = None
         size = normalize_size(size)
-        output = _output if _output is not None else normalize_output(dtype, normalize, mirror, size)
-        dest = slots = None                     # size=: the one tensor, and the slot of every file in it
-        if size is not None:
-            info = [_image_info(f) for f in files]
-            nc = one_component_count([t[2] for t in info])
-            if _output is None:
-                output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
-            if rois is not None:
-                wins = normalize_rois(rois, [t[:2] for t in info])
-            if _dest is not None:               # (a second round of some files of a larger call: their slots of its tensor)
-                dest, slots = _dest
-            else:
-                dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=output.torch_dtype if output else torch.uint8,
-                                   device=torch.device("cuda", self.ctx.device))
-                slots = list(range(len(files)))
-        elif rois is not None:
-            wins = normalize_rois(rois, [_image_dims(f) for f in files])
+        normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
-        if parts > 1:
-            n = len(files)
-            cut = [n * i // parts for i in range(parts + 1)]
-            out: List["torch.Tensor"] = []
-            for part in self._device_iter(((files[cut[i]:cut[i + 1]], wins[cut[i]:cut[i + 1]] if wins is not None else None,
-                                            (dest, slots[cut[i]:cut[i + 1]]) if dest is not None else None,
-                                            output.for_files(range(cut[i], cut[i + 1])) if output else None)
-                                           for i in range(parts)), depth=2, size=size):
-                if dest is None:
-                    out += part
-            return out if dest is None else dest
+        if parts <= 1:
+            return self._decode_request(req)
+        cut = [len(files) * i // parts for i in range(parts + 1)]
+        out: List["torch.Tensor"] = []
+        for part in self._device_iter((req.narrow(range(cut[i], cut[i + 1])) for i in range(parts)), depth=2):
+            if req.dest is None:
+                out += part
+        return out if req.dest is None else req.dest
+
+    def _decode_request(self, req: _Request):
+        """What :meth:`decode_device` returns for a checked request, decoded as one plan per kind of file — the request's
+        tensor when it has one, else a list of tensors."""
+        import torch
+        files = req.files
         dev = torch.device("cuda", self.ctx.device)
         results: List[Optional["torch.Tensor"]] = [None] * len(files)
         parsed: Dict[int, ParsedJpeg] = {}
-        work: List[Tuple[List[int], Optional[PreparedBatch]]] = []
+        work: List[_Work] = []
         rest: List[int] = []
         gpu_segment = self._gpu_segment_for(files)
         if gpu_segment and self.native_host:
             prep = prepare_batch_native(files, self.layout, self.base_flags, staging=self._staging_for(files))
             if isinstance(prep, PreparedBatch):                   # the everyday case: one pass, one plan
-                work.append((list(range(len(files))), prep))
+                work.append(_Work(list(range(len(files))), prep=prep))
             else:
                 # files of several kinds (sampling layouts; with / without restart markers), or some the front end does not
                 # take (progressive, ...): it sorts them — one native assembly per kind when its turn comes (one staging
                 # buffer), the Python path for the rest
                 groups_n, rest = prepare_batch_native(files, self.layout, self.base_flags, staging=self._staging_for(files), split=True)
-                work += [(idxs, "native") for idxs in groups_n]
+                work += [_Work(idxs, native=True) for idxs in groups_n]
         if not work or rest:
             todo = rest if work else range(len(files))          # everything, unless the front end kept some of it
-            groups: Dict[tuple, List[int]] = {}
-            for i in todo:
-                p = parsed[i] = parse_jpeg(files[i], headers_only=gpu_segment)
-                check_supported(p)
-                comps = list(p.color_components.values())
-                key = (p.scan_mode, len(comps), p.headers_only, is_scan_list(p), p.headers_only and p.restart_interval > 0) + (tuple((c.horizontal_sampling, c.vertical_sampling) for c in comps) if len(comps) > 1 else ())
-                groups.setdefault(key, []).append(i)
             # (first in line: what the front end left over is mostly progressive files, whose decode is a long serial chain
             # the other plans can run beside)
-            work = [(idxs, None) for idxs in groups.values()] + work
+            work = [_Work(idxs) for idxs in _group_by_kind(files, todo, parsed, gpu_segment)] + work
         # Several plans (a batch of several kinds of files): all are submitted before the first is collected, on a few
         # streams in turn, so that small plans share the GPU instead of queueing behind each other's host round trips
         # (mj_plan_sync waits for a plan's own work only).  Files handed back by the GPU scan go round again.
         streams = None
         while work:
-            flying = []
+            flying: List[_Flight] = []
             try:
                 while work:
-                    idxs, prep = work.pop(0)
-                    if isinstance(prep, str):
-                        sub = [files[i] for i in idxs]
-                        prep = prepare_batch_native(sub, self.layout, self.base_flags, staging=self._staging_for(sub))
-                        if not isinstance(prep, PreparedBatch):   # cannot happen for a group the front end just formed
-                            prep = None
-                            for i in idxs:
-                                parsed[i] = parse_jpeg(files[i], headers_only=True)
-                                check_supported(parsed[i])
-                    if prep is None or isinstance(prep, int):
-                        prep = prepare_batch([files[i] for i in idxs], self.layout, self.base_flags | (prep or 0), [parsed[i] for i in idxs])
+                    item = work.pop(0)
+                    sub, prep = req.narrow(item.idxs), item.prep
+                    if item.native:
+                        prep = prepare_batch_native(sub.files, self.layout, self.base_flags, staging=self._staging_for(sub.files))
+                        if not isinstance(prep, PreparedBatch):   # (declined after all: the Python path sorts these files)
+                            work[:0] = [_Work(idxs) for idxs in _group_by_kind(files, item.idxs, parsed, True)]
+                            continue
+                    if prep is None:
+                        prep = prepare_batch(sub.files, self.layout, self.base_flags | item.flags, [parsed[i] for i in item.idxs])
                     if work or flying:
                         # more than one plan: keep off the null stream, whose copies would wait for the other plans' kernels
                         if streams is None:
@@ -818,64 +886,39 @@ class BatchDecoder:
                             d_blob = torch.from_numpy(prep.blob).to(dev)         # (pageable source: the staging buffer is free on return)
                     else:
                         d_blob = torch.from_numpy(prep.blob).to(dev)
-                    plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(idxs)},
-                                  rois=[wins[i] for i in idxs] if wins is not None else None, size=size,
-                                  slots=([slots[i] for i in idxs], dest.shape[0]) if dest is not None else None,
-                                  output=output.plan_output(idxs) if output else None)
-                    flying.append((idxs, prep, plan, None, d_blob))
-                    d_rgb = dest if dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
-                    flying[-1] = (idxs, prep, plan, d_rgb, d_blob)
-                    # d_rgb comes from torch's caching allocator on torch's CURRENT stream: a block a consumer has just
-                    # dropped may still be read by kernels queued there, so the stream that is about to overwrite it waits
-                    # for the current stream first (the allocator only orders reuse within one stream)
+                    flight = _Flight(sub, item.idxs, prep, self._plan(sub, prep, d_blob.data_ptr()), None, d_blob)
+                    flying.append(flight)
+                    d_rgb = flight.d_rgb = req.dest if req.dest is not None else torch.empty(flight.plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     cur = torch.cuda.current_stream(dev)
                     if streams is None:
-                        ev = torch.cuda.Event()
-                        ev.record(cur)
-                        self.ctx.wait_event(ev.cuda_event)
-                        plan.execute(0, d_rgb.data_ptr())                        # the everyday case: one plan, the context's stream
+                        self._wait_for_current_stream(cur)
+                        flight.plan.execute(0, d_rgb.data_ptr())                 # the everyday case: one plan, the context's stream
                     else:
                         # (streams only overlap when they sit on different hardware queues: the package asks the runtime for
                         # eight instead of four, see __init__.py)
                         st = streams[(len(flying) - 1) % 4]
                         st.wait_stream(streams[4])                               # the upload above
-                        st.wait_stream(cur)
+                        st.wait_stream(cur)                                      # (as _wait_for_current_stream, for this stream)
                         d_rgb.record_stream(st)
                         d_blob.record_stream(st)
-                        plan.execute(st.cuda_stream, d_rgb.data_ptr())
-                for idxs, prep, plan, d_rgb, _ in flying:
-                    plan.sync()
-                    status = plan.read(rgb=False)["status"]
-                    redo = [i for k, i in enumerate(idxs) if status[k] == B.MJ_ST_TAIL]
-                    if redo:
-                        for i in redo:
-                            parsed[i] = parse_jpeg(files[i])
-                            check_supported(parsed[i])
-                        work.append((redo, None))
-                        status[[k for k, i in enumerate(idxs) if i in redo]] = 0
-                    again = [i for k, i in enumerate(idxs) if status[k] == B.MJ_ST_UNCONVERGED]
-                    if again:                                    # synchronisation rounds not settled: the serial walk for these
-                        for i in again:
-                            if i not in parsed:
-                                parsed[i] = parse_jpeg(files[i])
-                                check_supported(parsed[i])
-                        work.append((again, B.MJ_FLAG_NO_SYNC))
-                        status[[k for k, i in enumerate(idxs) if i in again]] = 0
-                    raise_for_status(status)
-                    if dest is not None:                         # (the plan wrote its slots of the one tensor)
+                        flight.plan.execute(st.cuda_stream, d_rgb.data_ptr())
+                for flight in flying:
+                    flight.plan.sync()
+                    tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], flight.idxs, files, parsed)
+                    if tail:
+                        work.append(_Work(tail))
+                    if unconverged:
+                        work.append(_Work(unconverged, flags=B.MJ_FLAG_NO_SYNC))
+                    if req.dest is not None:                     # (the plan wrote its slots of the one tensor)
                         continue
-                    off = 0
-                    shapes = self._out_shapes(prep, [wins[i] for i in idxs] if wins is not None else None)
-                    for k, i in enumerate(idxs):
-                        w, h, nc = shapes[k]
-                        n = w * h * nc
-                        if i not in redo and i not in again:
-                            results[i] = d_rgb[off:off + n].view(self._shape(w, h, nc))
-                        off += n
+                    views = self._views(flight.d_rgb, self._out_shapes(flight.prep, flight.req.wins))
+                    for k, i in enumerate(flight.idxs):
+                        if i not in tail and i not in unconverged:
+                            results[i] = views[k]
             finally:
-                for item in flying:
-                    item[2].close()
-        return results if dest is None else dest
+                for flight in flying:
+                    flight.plan.close()
+        return results if req.dest is None else req.dest
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
@@ -888,7 +931,8 @@ class BatchDecoder:
         in flight (round 5) the host waited for batch k's kernels before it started assembling batch k + 2, and the copy engine
         idled meanwhile: 512 x 1080p took the front end's 4.3 ms PLUS the upload's 6.1 ms per batch; with two the three —
         host threads, copy engine, GPU — run side by side and the batch takes what the slowest of them takes.  Batches the front
-        end declines are decoded by :meth:`decode_device` in place, behind everything in flight (no overlap for those).
+        end declines are decoded as :meth:`decode_device` decodes them, in place, behind everything in flight (no overlap for
+        those).
         ``size=(width, height)``: one tensor per batch, as :meth:`decode_device` returns it with ``size``; ``dtype`` and
         ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file)."""
@@ -899,7 +943,7 @@ class BatchDecoder:
             raise ValueError("dtype, normalize and mirror need size=(width, height)")
         flags = iter(mirror) if per_batch else None
 
-        def triples():
+        def requests():
             for files in batches:
                 files = list(files)
                 m = mirror
@@ -908,18 +952,11 @@ class BatchDecoder:
                         m = next(flags)
                     except StopIteration:
                         raise ValueError("mirror yields fewer entries than there are batches") from None
-                out = None
-                if size is not None and (dtype is not None or normalize is not None or m is not None):
-                    nc = one_component_count([_image_info(f)[2] for f in files])
-                    out = normalize_output(dtype, normalize, m, size, len(files), nc)
-                yield files, None, None, out
-        yield from self._device_iter(triples(), depth, size)
+                yield self._device_request(files, None, size, dtype, normalize, m)
+        yield from self._device_iter(requests(), depth)
 
-    def _device_iter(self, batches, depth=2, size=None):
-        """:meth:`decode_device_iter` over (files, windows or None, destination or None, output or None) tuples (windows:
-        normalize_rois' list for those files; destination, with ``size``: (tensor, slot of every file in it) — None: a tensor of
-        the batch's own, which is what the batch yields; output: the batch's :class:`OutputSpec`, its mirror flags one per file
-        of the batch)."""
+    def _device_iter(self, requests, depth=2):
+        """:meth:`decode_device_iter` over checked requests (:meth:`_device_request`'s, or parts of one)."""
         import collections
         import torch
         dev = torch.device("cuda", self.ctx.device)
@@ -928,52 +965,27 @@ class BatchDecoder:
         pinned = [None] * (depth + 1)
         uploaded = [None] * (depth + 1)     # event behind the latest upload out of each pinned buffer
         turn = 0
-        pending = collections.deque()       # ((plan, prep, d_rgb, d_blob), files) of the batches in flight, oldest first
+        pending = collections.deque()       # the batches in flight (_Flight), oldest first
 
-        def finish(job, wins):
-            plan, prep, d_rgb, _ = job
+        def collect(flight):
+            req = flight.req
             try:
-                plan.sync()
-                status = plan.read(rgb=False)["status"]
-                again = np.flatnonzero((status == B.MJ_ST_TAIL) | (status == B.MJ_ST_UNCONVERGED))
-                status = status.copy()
-                status[again] = 0                                 # something behind a scan / rounds not settled: those files again, below
-                raise_for_status(status)
-                if size is not None:
-                    return d_rgb, again
-                out, off = [], 0
-                for (w, h, nc) in self._out_shapes(prep, wins):
-                    n = w * h * nc
-                    out.append(d_rgb[off:off + n].view(self._shape(w, h, nc)))
-                    off += n
-                return out, again
+                flight.plan.sync()
+                tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], np.arange(len(req.files)))
+                out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins))
             finally:
-                plan.close()
-
-        def collect(job):
-            out, again = finish(job[0], job[2])
-            if again.size:                                        # only the files concerned take the long way (host parse)
-                redo = self.decode_device([job[1][int(i)] for i in again], parts=1,
-                                          rois=[job[2][int(i)] for i in again] if job[2] is not None else None, size=size,
-                                          _dest=(out, [job[3][int(i)] for i in again]) if size is not None else None,
-                                          _output=job[4].for_files([int(i) for i in again]) if job[4] else None)
-                if size is None:
+                flight.plan.close()
+            again = sorted(tail + unconverged)
+            if again:                                             # only the files concerned take the long way (host parse)
+                redo = self._decode_request(req.narrow(again))
+                if req.size is None:
                     for i, img in zip(again, redo):
-                        out[int(i)] = img
+                        out[i] = img
             return out
 
-        def destination(files, dest, output):
-            """with ``size``: (tensor, slots) a batch's plan writes — the caller's, or a tensor of the batch's own"""
-            if size is None or dest is not None:
-                return dest
-            nc = one_component_count([_image_info(f)[2] for f in files])
-            return (torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=output.torch_dtype if output else torch.uint8,
-                                device=dev), list(range(len(files))))
-
         try:
-            for files, wins, dest, output in batches:
-                files = list(files)
-                dest = destination(files, dest, output)
+            for req in requests:
+                files = req.files
                 prep = None
                 if self.gpu_segment and self.native_host and files:
                     buf, turn = turn, (turn + 1) % (depth + 1)
@@ -984,38 +996,32 @@ class BatchDecoder:
                         pinned[buf] = torch.empty(need + need // 4, dtype=torch.uint8, pin_memory=True)
                     prep = prepare_batch_native(files, self.layout, self.base_flags, staging=pinned[buf].numpy())
                 if not isinstance(prep, PreparedBatch):           # declined, or several plans' worth: the one-call path sorts it out
-                    prep = None
-                if prep is None:
                     while pending:
                         yield collect(pending.popleft())
-                    yield self.decode_device(files, rois=wins, parts=1, size=size, _dest=dest, _output=output)
+                    yield self._decode_request(req)
                     continue
                 with torch.cuda.stream(copy_stream):
                     d_blob = pinned[buf][:prep.blob.size].to(dev, non_blocking=True)
                     uploaded[buf] = torch.cuda.Event()
                     uploaded[buf].record(copy_stream)
-                plan = B.Plan(self.ctx, prep.to_c(d_blob.data_ptr()), {"prep": prep, "n_images": len(files)}, rois=wins, size=size,
-                              slots=(dest[1], dest[0].shape[0]) if dest is not None else None,
-                              output=output.plan_output() if output else None)
+                plan = self._plan(req, prep, d_blob.data_ptr())
                 try:
                     # (both tensors outlive the kernels that touch them: they stay in `pending` until the plan has been collected)
-                    d_rgb = dest[0] if dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
+                    d_rgb = req.dest if req.dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     self.ctx.wait_event(uploaded[buf].cuda_event)
-                    ev = torch.cuda.Event()                        # see decode_device: the context's stream waits for whatever
-                    ev.record(torch.cuda.current_stream(dev))      # the current stream still does with a recycled block
-                    self.ctx.wait_event(ev.cuda_event)
+                    self._wait_for_current_stream(torch.cuda.current_stream(dev))
                     plan.execute(0, d_rgb.data_ptr())
                 except BaseException:
                     plan.close()
                     raise
-                pending.append(((plan, prep, d_rgb, d_blob), files, wins, dest[1] if dest is not None else None, output))
+                pending.append(_Flight(req, None, prep, plan, d_rgb, d_blob))
                 while len(pending) > depth:
                     yield collect(pending.popleft())
             while pending:
                 yield collect(pending.popleft())
         finally:
             while pending:                                        # (an error, or a consumer that stopped early: nothing stays open)
-                pending.popleft()[0][0].close()
+                pending.popleft().plan.close()
 
     def close(self):
         self.ctx.close()

@@ -172,6 +172,30 @@ def test_argument_rules_need_no_gpu():
     assert spec.numpy_dtype == np.float32 and spec.torch_dtype == torch.float32
 
 
+def test_a_narrowed_request_takes_its_files_arguments_along():
+    """batch._Request.narrow: a request for files 1 and 3 of five carries exactly their windows, slots and mirror flags, and
+    gives _binding.Plan the keyword arguments the per-site slices gave; a request without windows, slots or flags keeps None."""
+    from pyjpegdecoder_amd.batch import _Request, normalize_output
+    files = [bytes([k]) * (k + 1) for k in range(5)]
+    wins = [(k, 2 * k, 8 + k, 9 + k) for k in range(5)]
+    slots = [7, 0, 5, 2, 6]
+    mirror = [True, False, False, True, True]
+    dest = np.empty((9, 4, 6, 3), dtype=np.float32)
+    spec = normalize_output("float32", IMAGENET, mirror, (4, 6), 5, 3)
+    idxs = [1, 3]
+    sub = _Request(files, wins, (4, 6), spec, dest, slots).narrow(idxs)
+    assert sub.files == [files[1], files[3]] and sub.wins == [wins[1], wins[3]] and sub.slots == [0, 2]
+    assert sub.output.mirror == [False, True] and sub.size == (4, 6) and sub.dest is dest
+    assert sub.plan_kwargs() == {"rois": [wins[i] for i in idxs], "size": (4, 6), "slots": ([slots[i] for i in idxs], 9),
+                                 "output": ("float32", IMAGENET[0], IMAGENET[1], [mirror[i] for i in idxs])}
+    assert _Request(files, wins, (4, 6), spec, dest, slots).narrow(np.array([4, 0])).slots == [6, 7]    # (indices from NumPy too)
+    bare = _Request(files).narrow(idxs)
+    assert bare.files == [files[1], files[3]] and (bare.wins, bare.size, bare.output, bare.dest, bare.slots) == (None,) * 5
+    assert bare.plan_kwargs() == {"rois": None, "size": None, "slots": None, "output": None}
+    unflagged = _Request(files, None, (4, 6), normalize_output("float16", None, None, (4, 6), 5, 3)).narrow(idxs)
+    assert unflagged.output.mirror is None and unflagged.plan_kwargs()["output"] == ("float16", None, None, None)
+
+
 def test_entry_point_refuses_a_bad_output_without_a_device(lib):
     """mj_plan_create_resized_as looks at the output description before anything else: MJ_ERR_INVALID with a message (no
     context: mj_last_error(NULL)'s) for a dtype that is none of the four, normalize with MJ_DTYPE_U8, a std <= 0 or not finite, a
