@@ -530,35 +530,41 @@ def normalize_rois(rois, dims: Sequence[Tuple[int, int]]) -> Optional[List[Tuple
     return out
 
 
-def raise_for_status(status: np.ndarray):
+def raise_for_status(status: np.ndarray, index: Optional[Sequence[int]] = None):
+    """Raise for the first image of a plan whose status is not 0.  ``index``: where every image of the plan sits in the
+    caller's list of files (None: the plan is that list) — the message names that position, not the one inside the plan."""
     bad = np.flatnonzero(status)
     if bad.size:
-        i = int(bad[0])
-        if int(status[i]) == B.MJ_ST_INTERNAL:          # not the file's fault (include/mijpeg.h)
+        k = int(bad[0])
+        i = k if index is None else int(index[k])
+        if int(status[k]) == B.MJ_ST_INTERNAL:          # not the file's fault (include/mijpeg.h)
             raise B.BackendError(f"image {i}: a fused launch gave up waiting for its decoder wavefronts (internal error)")
-        raise CorruptedJpeg(f"image {i}: {_STATUS_TEXT.get(int(status[i]), 'decode failed')}")
+        raise CorruptedJpeg(f"image {i}: {_STATUS_TEXT.get(int(status[k]), 'decode failed')}")
 
 
 @dataclass
 class _Request:
     """What one call asks of a set of files: the windows (:func:`normalize_rois`' list, or None), ``size``
     (:func:`normalize_size`'s, or None), the model-ready output (or None) and, with ``size``, the array or tensor the plans
-    write the images into and every file's slot in it (both None: every plan fills a dense array of its own)."""
+    write the images into and every file's slot in it (both None: every plan fills a dense array of its own).  ``index``:
+    where every file sits in the list the caller passed, for the messages of errors (None: this is that list)."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
     output: Optional[OutputSpec] = None
     dest: object = None
     slots: Optional[List[int]] = None
+    index: Optional[List[int]] = None
 
     def narrow(self, idxs) -> "_Request":
-        """the same request for some of its files: their windows, slots and mirror flags go with them"""
+        """the same request for some of its files: their windows, slots, mirror flags and positions in the call go with them"""
         idxs = [int(i) for i in idxs]
+        index = self.index if self.index is not None else range(len(self.files))
 
         def pick(per_file):
             return [per_file[i] for i in idxs] if per_file is not None else None
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots))
+                        self.dest, pick(self.slots), pick(index))
 
     def plan_kwargs(self) -> dict:
         """``rois``, ``size``, ``slots`` and ``output`` of :class:`_binding.Plan` for one plan of all its files, in order"""
@@ -605,8 +611,10 @@ def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], 
     return list(groups.values())
 
 
-def _triage(status: np.ndarray, idxs, files: Optional[Sequence[bytes]] = None, parsed: Optional[Dict[int, ParsedJpeg]] = None):
-    """Sort a plan's per-image status (``idxs``: the call's index of every image).  Returns (tail, unconverged): the files the
+def _triage(status: np.ndarray, idxs, files: Optional[Sequence[bytes]] = None, parsed: Optional[Dict[int, ParsedJpeg]] = None,
+            index: Optional[Sequence[int]] = None):
+    """Sort a plan's per-image status (``idxs``: every image's index in the request the plan is a part of; ``index``: its
+    position in the caller's list, which an error names — None: the same).  Returns (tail, unconverged): the files the
     GPU scan handed back (MJ_ST_TAIL: something other than EOI follows the scan — the host finds their segments) and those whose
     synchronisation rounds had not settled (MJ_ST_UNCONVERGED: the serial walk, MJ_FLAG_NO_SYNC).  Both go round again, so
     their entries are zeroed before :func:`raise_for_status` sees the rest.  With ``parsed`` (index -> ParsedJpeg of
@@ -620,7 +628,7 @@ def _triage(status: np.ndarray, idxs, files: Optional[Sequence[bytes]] = None, p
             parsed[i] = parse_jpeg(files[i])
             check_supported(parsed[i])
     status[(status == B.MJ_ST_TAIL) | (status == B.MJ_ST_UNCONVERGED)] = 0
-    raise_for_status(status)
+    raise_for_status(status, idxs if index is None else index)
     return tail, unconverged
 
 
@@ -904,7 +912,7 @@ class BatchDecoder:
                         flight.plan.execute(st.cuda_stream, d_rgb.data_ptr())
                 for flight in flying:
                     flight.plan.sync()
-                    tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], flight.idxs, files, parsed)
+                    tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], flight.idxs, files, parsed, flight.req.index)
                     if tail:
                         work.append(_Work(tail))
                     if unconverged:
@@ -971,7 +979,7 @@ class BatchDecoder:
             req = flight.req
             try:
                 flight.plan.sync()
-                tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], np.arange(len(req.files)))
+                tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], np.arange(len(req.files)), index=req.index)
                 out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins))
             finally:
                 flight.plan.close()
