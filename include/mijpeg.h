@@ -252,6 +252,26 @@ typedef struct {
 } mj_output_desc;
 int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
                               const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out);
+/* EXIF orientation: plans whose outputs are the images as their Orientation tag (1..8) says they are to be shown — exactly
+ * Pillow's ImageOps.exif_transpose (tools/orient_model.py): 1 as stored, 2 left-right flip, 3 rotated by 180, 4 top-bottom flip,
+ * 5 transposed, 6 ROTATE_270, 7 transverse, 8 ROTATE_90; 5..8 exchange width and height.
+ * orientations: host, one byte per image.  NULL, or all of them 1: exactly the plan mj_plan_create / mj_plan_create_roi /
+ * mj_plan_create_resized(_as) gives for the other arguments.  MJ_ERR_INVALID naming the image for a byte outside 1..8;
+ * MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT are refused (the seam outputs are in stored order).
+ * rois (may be NULL) are windows of the ORIENTED images; the library maps them to the stored images (orient_model.stored_window)
+ * and the plan is a window plan of those: restart segments and MCUs outside them are skipped as ever.
+ *   mj_plan_create_oriented           outputs at the files' own sizes, packed image after image as mj_plan_create's are — an image
+ *     keeps its offset (mj_plan_image_offsets) and its size in bytes; its shape in the plan's layout is the oriented one.
+ *     Stage 2 writes into a plan-owned buffer in stored order and one more launch (csrc/orient.hip) writes every image oriented
+ *     into the caller's output; mj_plan_fill_source / mj_plan_time_resize work on that buffer / launch.
+ *   mj_plan_create_resized_oriented   mj_plan_create_resized_as (output may be NULL) of the oriented images or windows: element by
+ *     element Pillow's resize of the oriented pixels, inside the one resize launch — no extra pass over memory.  output->mirror
+ *     applies after the orientation.  All images of such a plan either exchange width and height (5..8) or do not:
+ *     MJ_ERR_UNSUPPORTED naming the first image that differs from image 0 otherwise (two plans into one array, with slots). */
+int mj_plan_create_oriented(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, const uint8_t *orientations, mj_plan **out);
+int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                    mj_plan **out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -485,6 +505,14 @@ typedef struct {
     int32_t n_accepted;                   /* out: files assembled (= n_files without `skip`)                   */
 } mj_host_job;
 int mj_host_assemble(mj_host_job *job);
+
+/* The EXIF Orientation tag of n_files files on host threads (host only, no context): out[i] = 1..8.  File i is files[i], or —
+ * files == NULL — blob + offsets[i]; lengths[i] bytes either way.  Read: the marker segments in front of the first SOS, the first
+ * APP1 whose payload starts "Exif\0\0", its TIFF header (II or MM), tag 0x0112 of IFD0 as one SHORT.  Declines nothing: 1 when
+ * there is no such tag, its value is outside 1..8, or anything is malformed or truncated; never reads outside a segment.
+ * pyjpegdecoder_amd.exif_orientation is the specification. */
+int mj_host_exif_orientations(const uint8_t *const *files, const uint8_t *blob, const int64_t *offsets, const int64_t *lengths,
+                              int32_t n_files, int32_t n_threads, uint8_t *out);
 
 #ifdef __cplusplus
 }

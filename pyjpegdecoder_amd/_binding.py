@@ -35,6 +35,7 @@ EXPORTS = (
     "mj_device_copy_rate", "mj_context_launch_clock", "mj_debug_prog_split", "mj_debug_fused_applies", "mj_plan_tune_placement",
     "mj_plan_create_resized", "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table",
     "mj_plan_create_resized_as", "mj_host_normalize_table",
+    "mj_plan_create_oriented", "mj_plan_create_resized_oriented", "mj_host_exif_orientations",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -132,6 +133,10 @@ def load_library():
     L.mj_plan_create_resized.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(vp)]
     L.mj_plan_create_resized_as.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(OutputDescC),
                                             ctypes.POINTER(vp)]
+    L.mj_plan_create_oriented.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), vp, ctypes.POINTER(vp)]
+    L.mj_plan_create_resized_oriented.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
+                                                  ctypes.POINTER(OutputDescC), vp, ctypes.POINTER(vp)]
+    L.mj_host_exif_orientations.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.mj_host_normalize_table.argtypes = [i32, ctypes.c_float, ctypes.c_float, vp]
     L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
     L.mj_plan_time_resize.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
@@ -268,6 +273,27 @@ def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarr
     return out
 
 
+def exif_orientations(files, n_threads: int = 0) -> np.ndarray:
+    """mj_host_exif_orientations (host only): the EXIF Orientation tag (1..8) of every file of a list of ``bytes``, uint8 — what
+    ``_parse.exif_orientation`` answers for each, read on host threads."""
+    n = len(files)
+    out = np.ones(n, dtype=np.uint8)
+    if n == 0:
+        return out
+    if not all(type(f) is bytes for f in files):
+        from ._parse import exif_orientation
+        out[:] = [exif_orientation(bytes(f)) for f in files]
+        return out
+    sizes = np.fromiter(map(len, files), dtype=np.int64, count=n)
+    ptrs = (ctypes.c_char_p * n)(*files)
+    if n_threads <= 0:
+        import os
+        n_threads = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+    if load_library().mj_host_exif_orientations(ctypes.cast(ptrs, ctypes.c_void_p), None, None, _ptr(sizes), n, n_threads, _ptr(out)) != MJ_OK:
+        raise BackendError("mj_host_exif_orientations failed")
+    return out
+
+
 def output_desc(output):
     """(mj_output_desc, what it points to) from (dtype name, mean or None, std or None, mirror flags or None) — mean and std
     one float per component."""
@@ -369,9 +395,10 @@ class Plan:
     with size, (slot of every image, slots of the array) when the plan fills part of a larger array.  output: with size, None
     (the resized bytes) or (dtype name, mean or None, std or None, mirror flag per image or None) — a model-ready output
     (mj_plan_create_resized_as): elements of that type, normalised, flagged images mirrored; info.rgb_bytes is then in bytes
-    of that type."""
+    of that type.  orientation: None, or one EXIF orientation 1..8 per image — an oriented plan (mj_plan_create_oriented, with
+    size mj_plan_create_resized_oriented): outputs as the orientation shows the images, rois in oriented coordinates."""
 
-    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None):
+    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -383,7 +410,14 @@ class Plan:
             if slots is not None:
                 sl = np.ascontiguousarray(slots[0], dtype=np.int32)
                 n_slots = int(slots[1])
-            if output is None:
+            if orientation is not None:
+                turns = np.ascontiguousarray(orientation, dtype=np.uint8)
+                desc, flags = output_desc(output) if output is not None else (None, None)
+                if turns.size != batch_c.n_images or (flags is not None and flags.size != batch_c.n_images):
+                    raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
+                ctx.check(ctx.lib.mj_plan_create_resized_oriented(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
+                                                                  ctypes.byref(desc) if desc is not None else None, _ptr(turns), ctypes.byref(h)))
+            elif output is None:
                 ctx.check(ctx.lib.mj_plan_create_resized(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
                                                          ctypes.byref(h)))
             else:
@@ -394,6 +428,11 @@ class Plan:
                                                             n_slots, ctypes.byref(desc), ctypes.byref(h)))
         elif output is not None:
             raise ValueError("output needs size: only a resized plan has a dense output")
+        elif orientation is not None:
+            turns = np.ascontiguousarray(orientation, dtype=np.uint8)
+            if turns.size != batch_c.n_images:
+                raise ValueError(f"orientation: {turns.size} entries for {batch_c.n_images} images")
+            ctx.check(ctx.lib.mj_plan_create_oriented(ctx.handle, ctypes.byref(batch_c), arr, _ptr(turns), ctypes.byref(h)))
         elif rois is None:
             ctx.check(ctx.lib.mj_plan_create(ctx.handle, ctypes.byref(batch_c), ctypes.byref(h)))
         else:

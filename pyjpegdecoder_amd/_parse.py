@@ -210,6 +210,74 @@ class ParsedJpeg:
     headers_only: bool = False       # parse stopped at the SOS (see parse_jpeg)
     log: List[str] = field(default_factory=list)
 
+    @property
+    def exif_orientation(self) -> int:
+        """:func:`exif_orientation` of the file."""
+        return exif_orientation(self.raw)
+
+
+def _tiff_orientation(t: bytes) -> int:
+    """Tag 0x0112 of IFD0 of a TIFF structure, as one SHORT in 1..8; 1 otherwise."""
+    n = len(t)
+    if n < 8 or t[:2] not in (b"II", b"MM"):
+        return 1
+    order = "little" if t[:2] == b"II" else "big"
+
+    def u(p: int, size: int) -> int:
+        return int.from_bytes(t[p:p + size], order)
+    if u(2, 2) != 42:
+        return 1
+    ifd = u(4, 4)
+    if ifd + 2 > n:
+        return 1
+    count = u(ifd, 2)
+    if ifd + 2 + 12 * count > n:
+        return 1
+    for e in range(count):
+        p = ifd + 2 + 12 * e
+        if u(p, 2) != 0x0112:
+            continue
+        if u(p + 2, 2) != 3 or u(p + 4, 4) != 1:
+            return 1
+        v = u(p + 8, 2)
+        return v if 1 <= v <= 8 else 1
+    return 1
+
+
+def exif_orientation(raw: bytes) -> int:
+    """The EXIF Orientation tag of a JPEG file, 1..8 (tools/orient_model.py says what each means).
+
+    Read: the marker segments in front of the first SOS; the first APP1 segment whose payload starts with ``Exif\\0\\0`` (an XMP
+    APP1 is not EXIF); its TIFF header in either byte order (``II`` / ``MM``, magic 42); IFD0's tag 0x0112 as type SHORT, count 1.
+    The answer is 1 when there is no such segment or tag, when the value is outside 1..8, and when anything is malformed or
+    truncated — a segment longer than the file, an IFD offset or entry count that points outside the segment, another type or
+    count.  Never raises, never looks outside the segment.  (``mj_host_exif_orientations`` in libmijpeg.so is its native twin,
+    held to it file by file.)"""
+    n = len(raw)
+    if n < 4 or raw[0] != 0xFF or raw[1] != 0xD8:
+        return 1
+    pos = 2
+    while pos + 4 <= n:
+        if raw[pos] != 0xFF:
+            pos += 1
+            continue
+        m = raw[pos + 1]
+        if m == 0xFF:
+            pos += 1
+            continue
+        if m in (0x00, 0x01) or 0xD0 <= m <= 0xD7:
+            pos += 2
+            continue
+        if m in (0xDA, 0xD9):
+            return 1
+        size = (raw[pos + 2] << 8) | raw[pos + 3]
+        if size < 2 or pos + 2 + size > n:
+            return 1
+        if m == 0xE1 and size >= 8 and raw[pos + 4:pos + 10] == b"Exif\0\0":
+            return _tiff_orientation(bytes(raw[pos + 10:pos + 2 + size]))
+        pos += 2 + size
+    return 1
+
 
 def parse_jpeg(raw: bytes, headers_only: bool = False) -> ParsedJpeg:
     """Walk the file like the reference's constructor does (jpeg_decoder.py:29-110), but instead of

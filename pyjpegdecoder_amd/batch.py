@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _binding as B
-from ._parse import ParsedJpeg, ScanInfo, parse_jpeg
+from ._parse import ParsedJpeg, ScanInfo, exif_orientation, parse_jpeg
 from .errors import CorruptedJpeg, UnsupportedJpeg
 
 _STATUS_TEXT = {
@@ -530,6 +530,62 @@ def normalize_rois(rois, dims: Sequence[Tuple[int, int]]) -> Optional[List[Tuple
     return out
 
 
+_TRANSPOSING = (5, 6, 7, 8)          # EXIF orientations that exchange width and height (tools/orient_model.py)
+
+
+def normalize_orientation(orientation, files: Sequence[bytes]) -> Optional[List[int]]:
+    """The EXIF orientation every file of a call is decoded with, 1..8 each — or None where all of them are 1, which is a call
+    without the argument.  ``orientation``: None; "exif" (every file's own tag, :func:`exif_orientation`; 1 without one); one
+    int 1..8 for every file; or a sequence with one int, "exif" or None per file.  ValueError for anything else."""
+    n = len(files)
+
+    def is_value(v) -> bool:
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and 1 <= int(v) <= 8
+
+    if orientation is None:
+        return None
+    if isinstance(orientation, str):
+        if orientation != "exif":
+            raise ValueError(f"orientation must be None, 'exif', an int 1..8 or one of these per file, not {orientation!r}")
+        turns = B.exif_orientations(files).tolist()
+    elif is_value(orientation):
+        turns = [int(orientation)] * n
+    else:
+        if isinstance(orientation, (int, float, bool, np.number, np.bool_, bytes)):
+            raise ValueError(f"orientation must be None, 'exif', an int 1..8 or one of these per file, not {orientation!r}")
+        try:
+            entries = orientation.tolist() if hasattr(orientation, "tolist") else list(orientation)
+        except TypeError:
+            raise ValueError(f"orientation must be None, 'exif', an int 1..8 or one of these per file, not {orientation!r}") from None
+        if len(entries) != n:
+            raise ValueError(f"orientation has {len(entries)} entries for {n} files")
+        turns = []
+        for i, v in enumerate(entries):
+            if v is None:
+                turns.append(1)
+            elif isinstance(v, str) and v == "exif":
+                turns.append(exif_orientation(bytes(files[i])))
+            elif is_value(v):
+                turns.append(int(v))
+            else:
+                raise ValueError(f"file {i}: orientation {v!r} is none of None, 'exif' and an int 1..8")
+    return turns if any(t != 1 for t in turns) else None
+
+
+def _oriented_dims(dims, orient: Optional[List[int]]):
+    """(width, height) of every file as its orientation shows it."""
+    if orient is None:
+        return list(dims)
+    return [(h, w) if o in _TRANSPOSING else (w, h) for (w, h), o in zip(dims, orient)]
+
+
+def _orient_class(o: int, sized: bool) -> int:
+    """What keeps files of different orientations out of one plan: upright files form the plans they form without the argument
+    (0); with ``size`` the orientations that exchange width and height read their source the other way and are a launch of
+    their own (2), the other turned ones (1)."""
+    return 0 if o == 1 else (2 if sized and o in _TRANSPOSING else 1)
+
+
 def raise_for_status(status: np.ndarray, index: Optional[Sequence[int]] = None):
     """Raise for the first image of a plan whose status is not 0.  ``index``: where every image of the plan sits in the
     caller's list of files (None: the plan is that list) — the message names that position, not the one inside the plan."""
@@ -547,7 +603,8 @@ class _Request:
     """What one call asks of a set of files: the windows (:func:`normalize_rois`' list, or None), ``size``
     (:func:`normalize_size`'s, or None), the model-ready output (or None) and, with ``size``, the array or tensor the plans
     write the images into and every file's slot in it (both None: every plan fills a dense array of its own).  ``index``:
-    where every file sits in the list the caller passed, for the messages of errors (None: this is that list)."""
+    where every file sits in the list the caller passed, for the messages of errors (None: this is that list).  ``orient``:
+    :func:`normalize_orientation`'s list (None: every file as stored); the windows are then windows of the oriented images."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
@@ -555,22 +612,39 @@ class _Request:
     dest: object = None
     slots: Optional[List[int]] = None
     index: Optional[List[int]] = None
+    orient: Optional[List[int]] = None
 
     def narrow(self, idxs) -> "_Request":
-        """the same request for some of its files: their windows, slots, mirror flags and positions in the call go with them"""
+        """the same request for some of its files: their windows, slots, mirror flags, orientations and positions in the call go
+        with them (files that are all upright: no orientations, the request a call without the argument makes)"""
         idxs = [int(i) for i in idxs]
         index = self.index if self.index is not None else range(len(self.files))
 
         def pick(per_file):
             return [per_file[i] for i in idxs] if per_file is not None else None
+        orient = pick(self.orient)
+        if orient is not None and all(o == 1 for o in orient):
+            orient = None
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots), pick(index))
+                        self.dest, pick(self.slots), pick(index), orient)
+
+    def orient_classes(self) -> List[List[int]]:
+        """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
+        if self.orient is None:
+            return [list(range(len(self.files)))]
+        classes: Dict[int, List[int]] = {}
+        for i, o in enumerate(self.orient):
+            classes.setdefault(_orient_class(o, self.size is not None), []).append(i)
+        return list(classes.values())
 
     def plan_kwargs(self) -> dict:
-        """``rois``, ``size``, ``slots`` and ``output`` of :class:`_binding.Plan` for one plan of all its files, in order"""
-        return {"rois": self.wins, "size": self.size,
-                "slots": (self.slots, self.dest.shape[0]) if self.slots is not None else None,
-                "output": self.output.plan_output() if self.output else None}
+        """``rois``, ``size``, ``slots``, ``output`` and ``orientation`` of :class:`_binding.Plan` for one plan of all its files, in order"""
+        kw = {"rois": self.wins, "size": self.size,
+              "slots": (self.slots, self.dest.shape[0]) if self.slots is not None else None,
+              "output": self.output.plan_output() if self.output else None}
+        if self.orient is not None:         # (files as stored: the arguments of a call without orientation)
+            kw["orientation"] = self.orient
+        return kw
 
 
 @dataclass
@@ -596,8 +670,9 @@ class _Flight:
     d_blob: object = None
 
 
-def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], headers_only: bool) -> List[List[int]]:
-    """Files ``idxs`` sorted into one index list per kind — what can share a plan.  Those that ``parsed`` (index -> ParsedJpeg)
+def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], headers_only: bool, turn=None) -> List[List[int]]:
+    """Files ``idxs`` sorted into one index list per kind — what can share a plan (``turn``: index -> :func:`_orient_class`,
+    part of the kind; None: no file is turned).  Those that ``parsed`` (index -> ParsedJpeg)
     does not hold yet are parsed into it (``headers_only`` as asked); every one goes through :func:`check_supported`."""
     groups: Dict[tuple, List[int]] = {}
     for i in idxs:
@@ -606,7 +681,7 @@ def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], 
             p = parsed[i] = parse_jpeg(files[i], headers_only=headers_only)
         check_supported(p)
         comps = list(p.color_components.values())
-        key = (p.scan_mode, len(comps), p.headers_only, is_scan_list(p), p.headers_only and p.restart_interval > 0) + (tuple((c.horizontal_sampling, c.vertical_sampling) for c in comps) if len(comps) > 1 else ())
+        key = (p.scan_mode, len(comps), p.headers_only, is_scan_list(p), p.headers_only and p.restart_interval > 0, turn[i] if turn is not None else 0) + (tuple((c.horizontal_sampling, c.vertical_sampling) for c in comps) if len(comps) > 1 else ())
         groups.setdefault(key, []).append(i)
     return list(groups.values())
 
@@ -688,9 +763,11 @@ class BatchDecoder:
         return (3,) + wh if self.layout >= B.MJ_LAYOUT_PLANAR_XMAJOR else wh + (3,)
 
     @staticmethod
-    def _out_shapes(prep: PreparedBatch, wins=None) -> List[Tuple[int, int, int]]:
-        """(width, height, ncomp) of every image's output: the image, or its window."""
+    def _out_shapes(prep: PreparedBatch, wins=None, orient=None) -> List[Tuple[int, int, int]]:
+        """(width, height, ncomp) of every image's output: the image — as its orientation shows it —, or its window."""
         if wins is None:
+            if orient is not None:
+                return [(h, w, nc) if o in _TRANSPOSING else (w, h, nc) for (w, h, nc), o in zip(prep.shapes, orient)]
             return list(prep.shapes)
         return [(w[2], w[3], nc) for w, (_, _, nc) in zip(wins, prep.shapes)]
 
@@ -703,21 +780,27 @@ class BatchDecoder:
             off += n
         return out
 
-    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None) -> List[np.ndarray]:
-        return self._views(flat, self._out_shapes(prep, wins), per_pixel)
+    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None, orient=None) -> List[np.ndarray]:
+        return self._views(flat, self._out_shapes(prep, wins, orient), per_pixel)
 
     def _plan(self, req: _Request, prep: PreparedBatch, blob_device_ptr: int = 0) -> B.Plan:
         """The plan of a request whose files are ``prep``'s, in order."""
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs())
 
-    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None):
+    def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
+               orientation=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
         on the GPU — Pillow's ``resize(size, Image.BILINEAR)`` of it, byte for byte — and ONE array of shape ``(len(files),) +
         shape of one image`` instead of a list.  With ``size``, ``dtype`` / ``normalize=(mean, std)`` / ``mirror`` make that array
         model-ready in the same launch (:func:`normalize_output`): float32 or float16 elements, torchvision's
-        ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes bit for bit, flagged files flipped along the width."""
+        ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes bit for bit, flagged files flipped along the width.
+        ``orientation``: None (the pixels as stored), "exif" (every file turned as its EXIF Orientation tag says: Pillow's
+        ``ImageOps.exif_transpose``), an int 1..8 for every file, or one of these per file (:func:`normalize_orientation`).
+        Shapes, ``rois`` and ``size`` then all refer to the turned image; ``mirror`` comes after it."""
+        if orientation is not None and return_seams:
+            raise ValueError("orientation and return_seams do not go together: the seam outputs are in stored order")
         if rois is not None and return_seams:
             raise ValueError("rois and return_seams do not go together: the seam outputs are whole-image")
         size = normalize_size(size)
@@ -726,7 +809,10 @@ class BatchDecoder:
         normalize_output(dtype, normalize, mirror, size, host=True)       # (what needs no file: before any is parsed)
         gpu_segment = self._gpu_segment_for(files)
         parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
-        req = _Request(files, normalize_rois(rois, [(p.image_width, p.image_height) for p in parsed.values()]), size)
+        orient = normalize_orientation(orientation, files)
+        req = _Request(files, normalize_rois(rois, _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)), size,
+                       orient=orient)
+        turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
             nc = one_component_count([len(p.color_components) for p in parsed.values()])
@@ -735,7 +821,7 @@ class BatchDecoder:
         results: List[Optional[np.ndarray]] = [None] * len(files)
         seams: List[Optional[dict]] = [None] * len(files)
         flags = ((B.MJ_FLAG_KEEP_PLANES | B.MJ_FLAG_KEEP_IDCT) if return_seams else 0) | self.base_flags
-        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment)]
+        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment, turn)]
         while work:
             item = work.pop(0)
             idxs, sub = item.idxs, req.narrow(item.idxs)
@@ -753,7 +839,7 @@ class BatchDecoder:
                 if dense is not None:
                     imgs = out["rgb"].view(dense.dtype).reshape((len(idxs),) + dense.shape[1:])
                 else:
-                    imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins)
+                    imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins, orient=sub.orient)
                 for k, i in enumerate(idxs):
                     if i in tail or i in unconverged:
                         continue
@@ -782,22 +868,22 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror) -> _Request:
+    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order."""
-        req = _Request(files, None, size)
+        req = _Request(files, None, size, orient=normalize_orientation(orientation, files))
         if size is not None:
             import torch
             info = [_image_info(f) for f in files]
             nc = one_component_count([t[2] for t in info])
             req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
-            req.wins = normalize_rois(rois, [t[:2] for t in info])
+            req.wins = normalize_rois(rois, _oriented_dims([t[:2] for t in info], req.orient))
             req.dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
             req.slots = list(range(len(files)))
         elif rois is not None:
-            req.wins = normalize_rois(rois, [_image_dims(f) for f in files])
+            req.wins = normalize_rois(rois, _oriented_dims([_image_dims(f) for f in files], req.orient))
         return req
 
     def _wait_for_current_stream(self, cur):
@@ -810,7 +896,7 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None):
+                      mirror=None, orientation=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -828,10 +914,14 @@ class BatchDecoder:
         ``mirror`` (one bool, or one per file), all with ``size``: the tensor a model takes, out of the same resize launch — its
         elements are torchvision's ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes (mean 0, std 1 without
         ``normalize``), computed in float32 and converted with ``.to(dtype)``, bit for bit; a flagged file's image is the
-        un-flagged result flipped along its width axis (:func:`normalize_output`)."""
+        un-flagged result flipped along its width axis (:func:`normalize_output`).
+        ``orientation`` as in :meth:`decode`: None, "exif", an int 1..8, or one of these per file.  The tags are read on host
+        threads; turned files are plans of their own (upright ones decode exactly as without the argument), written turned by
+        one more launch per plan — or, with ``size``, by the resize launch itself, whose result is Pillow's resize of the
+        turned image."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
@@ -848,6 +938,17 @@ class BatchDecoder:
         tensor when it has one, else a list of tensors."""
         import torch
         files = req.files
+        classes = req.orient_classes()
+        if len(classes) > 1:
+            # files turned and not (with size: turned in two ways): every class is a request of its own — the upright files the
+            # one a call without orientation makes — into the same tensor, or into the same list
+            merged: List[Optional["torch.Tensor"]] = [None] * len(files)
+            for idxs in classes:
+                part = self._decode_request(req.narrow(idxs))
+                if req.dest is None:
+                    for i, img in zip(idxs, part):
+                        merged[i] = img
+            return merged if req.dest is None else req.dest
         dev = torch.device("cuda", self.ctx.device)
         results: List[Optional["torch.Tensor"]] = [None] * len(files)
         parsed: Dict[int, ParsedJpeg] = {}
@@ -919,7 +1020,7 @@ class BatchDecoder:
                         work.append(_Work(unconverged, flags=B.MJ_FLAG_NO_SYNC))
                     if req.dest is not None:                     # (the plan wrote its slots of the one tensor)
                         continue
-                    views = self._views(flight.d_rgb, self._out_shapes(flight.prep, flight.req.wins))
+                    views = self._views(flight.d_rgb, self._out_shapes(flight.prep, flight.req.wins, flight.req.orient))
                     for k, i in enumerate(flight.idxs):
                         if i not in tail and i not in unconverged:
                             results[i] = views[k]
@@ -928,7 +1029,7 @@ class BatchDecoder:
                     flight.plan.close()
         return results if req.dest is None else req.dest
 
-    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None):
+    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -943,8 +1044,13 @@ class BatchDecoder:
         those).
         ``size=(width, height)``: one tensor per batch, as :meth:`decode_device` returns it with ``size``; ``dtype`` and
         ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
-        batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file)."""
+        batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file).  ``orientation``: None, "exif" or
+        an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes."""
         size = normalize_size(size)
+        turns_per_batch = not (orientation is None or isinstance(orientation, (str, int, np.integer)))
+        if not turns_per_batch:
+            normalize_orientation(orientation, [])                                    # (what needs no file: before any work)
+        turns = iter(orientation) if turns_per_batch else None
         per_batch = mirror is not None and not isinstance(mirror, (bool, np.bool_))
         normalize_output(dtype, normalize, None if per_batch else mirror, size)      # (what needs no file: before any work)
         if per_batch and size is None:
@@ -960,7 +1066,13 @@ class BatchDecoder:
                         m = next(flags)
                     except StopIteration:
                         raise ValueError("mirror yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m)
+                o = orientation
+                if turns is not None:
+                    try:
+                        o = next(turns)
+                    except StopIteration:
+                        raise ValueError("orientation yields fewer entries than there are batches") from None
+                yield self._device_request(files, None, size, dtype, normalize, m, o)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):
@@ -980,7 +1092,7 @@ class BatchDecoder:
             try:
                 flight.plan.sync()
                 tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], np.arange(len(req.files)), index=req.index)
-                out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins))
+                out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins, req.orient))
             finally:
                 flight.plan.close()
             again = sorted(tail + unconverged)
@@ -995,7 +1107,7 @@ class BatchDecoder:
             for req in requests:
                 files = req.files
                 prep = None
-                if self.gpu_segment and self.native_host and files:
+                if self.gpu_segment and self.native_host and files and len(req.orient_classes()) == 1:
                     buf, turn = turn, (turn + 1) % (depth + 1)
                     need = sum(map(len, files)) + 3 * len(files) + 1024
                     if uploaded[buf] is not None:

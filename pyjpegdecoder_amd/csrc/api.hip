@@ -106,7 +106,7 @@ void mj_plan_destroy(mj_plan *p) {
     }
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
     void *ptrs[] = {p->d_blob_owned, p->d_segs, p->d_images, p->d_huff, p->d_lut11, p->d_lut13, p->d_lut12, p->d_by_length, p->d_holder, p->d_xwords, p->d_wg_tabs_lanes, p->d_wg_tabs_count, p->d_stream, p->d_seg_bits, p->d_jobs, p->d_lut11u, p->d_acsegs, p->d_pc_chunks, p->d_pc_tabs, p->d_pc_exit, p->d_pc_outs, p->d_pc_items, p->d_pc_owner, p->d_pc_vsegs, p->d_lutc, p->d_sync_items, p->d_seg_chunk0, p->d_chunks, p->d_stateA, p->d_stateB, p->d_couts, p->d_vsegs, p->d_changed, p->d_pieces, p->d_piece_kept, p->d_pscans, p->d_psegs, p->d_pstates, p->d_psubs, p->d_prog_dsegs, p->d_lut11p, p->d_qt, p->d_mcu_prefix, p->d_job_prefix, p->d_tmp_coef, p->d_coef,
-                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status, p->d_win, p->d_win_mcu_prefix, p->d_segs_full, p->d_seg_gather, p->d_src, p->d_rz_images, p->d_rz_tabs, p->d_rz_lut, p->d_rz_mirror};
+                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status, p->d_win, p->d_win_mcu_prefix, p->d_segs_full, p->d_seg_gather, p->d_src, p->d_rz_images, p->d_rz_tabs, p->d_rz_lut, p->d_rz_mirror, p->d_or_images, p->d_or_prefix};
     for (void *q : ptrs)
         if (q) p->ctx->cache.put(q);
     delete p;
@@ -315,6 +315,12 @@ static int recon_args(mj_plan *p, uint8_t *rgb_device, mj::ReconArgs &a) {
 // a resized plan's last launch: the intermediate pixels, resized, into the output recon_args resolved
 static int resize_launch(mj_plan *p, hipStream_t s) {
     if (!p->resized) return MJ_OK;
+    if (p->orient_only) {       // an oriented plan at the files' own sizes: the orient launch in the resize's place
+        mj::OrientArgs o = p->oa;
+        o.dst = p->last_rgb;
+        MJ_HIP(p->ctx, mj::launch_orient(s, o, p->ncomp));
+        return MJ_OK;
+    }
     mj::ResizeArgs a = p->rz;
     a.dst = p->last_rgb;
     MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp));

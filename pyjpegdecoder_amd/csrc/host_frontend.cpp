@@ -250,3 +250,70 @@ extern "C" int mj_host_assemble(mj_host_job *job) {
     job->n_qt = (int32_t)qt_ids.size();
     return k > 0 ? MJ_OK : MJ_HOST_DECLINED;
 }
+
+// ---- EXIF orientation ----------------------------------------------------------------------------------------------------
+// The native twin of _parse.exif_orientation, which is the specification (tests/test_orientation_host.py holds the two
+// together file by file): the marker segments in front of the first SOS, the first APP1 whose payload starts "Exif\0\0", its
+// TIFF header in either byte order, tag 0x0112 of IFD0 as one SHORT.  1 for everything else; no read outside the segment.
+namespace {
+
+int tiff_orientation(const uint8_t *t, int64_t n) {
+    if (n < 8) return 1;
+    bool le;
+    if (t[0] == 'I' && t[1] == 'I') le = true;
+    else if (t[0] == 'M' && t[1] == 'M') le = false;
+    else return 1;
+    auto u16 = [&](int64_t p) -> int64_t { return le ? t[p] | (t[p + 1] << 8) : (t[p] << 8) | t[p + 1]; };
+    auto u32 = [&](int64_t p) -> int64_t { return le ? u16(p) | (u16(p + 2) << 16) : (u16(p) << 16) | u16(p + 2); };
+    if (u16(2) != 42) return 1;
+    const int64_t ifd = u32(4);
+    if (ifd + 2 > n) return 1;
+    const int64_t count = u16(ifd);
+    if (ifd + 2 + 12 * count > n) return 1;
+    for (int64_t e = 0; e < count; ++e) {
+        const int64_t p = ifd + 2 + 12 * e;
+        if (u16(p) != 0x0112) continue;
+        if (u16(p + 2) != 3 || u32(p + 4) != 1) return 1;
+        const int64_t v = u16(p + 8);
+        return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+}
+
+int exif_orientation(const uint8_t *raw, int64_t n) {
+    if (!raw || n < 4 || raw[0] != 0xFF || raw[1] != 0xD8) return 1;
+    int64_t pos = 2;
+    while (pos + 4 <= n) {
+        if (raw[pos] != 0xFF) { ++pos; continue; }
+        const int m = raw[pos + 1];
+        if (m == 0xFF) { ++pos; continue; }
+        if (m == 0x00 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) { pos += 2; continue; }
+        if (m == 0xDA || m == 0xD9) return 1;
+        const int64_t size = be16(raw + pos + 2);
+        if (size < 2 || pos + 2 + size > n) return 1;
+        if (m == 0xE1 && size >= 8 && memcmp(raw + pos + 4, "Exif\0\0", 6) == 0) return tiff_orientation(raw + pos + 10, size - 8);
+        pos += 2 + size;
+    }
+    return 1;
+}
+
+}  // namespace
+
+extern "C" int mj_host_exif_orientations(const uint8_t *const *files, const uint8_t *blob, const int64_t *offsets, const int64_t *lengths,
+                                         int32_t n_files, int32_t n_threads, uint8_t *out) {
+    if (n_files < 0 || !lengths || !out || (!files && (!blob || !offsets))) return MJ_ERR_INVALID;
+    const int n = n_files;
+    auto part = [&](int begin, int end) {
+        for (int i = begin; i < end; ++i) {
+            const uint8_t *raw = files ? files[i] : blob + offsets[i];
+            out[i] = (uint8_t)(lengths[i] > 0 && (files || offsets[i] >= 0) ? exif_orientation(raw, lengths[i]) : 1);
+        }
+    };
+    int nt = n_threads < 1 ? 1 : std::min(n_threads, 64);
+    nt = std::min(nt, std::max(1, n / 64));         // (a thread is worth starting for some dozens of files)
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(part, (int)((int64_t)n * t / nt), (int)((int64_t)n * (t + 1) / nt));
+    part(0, (int)((int64_t)n / nt));
+    for (auto &t : pool) t.join();
+    return MJ_OK;
+}

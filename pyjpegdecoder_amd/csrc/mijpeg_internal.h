@@ -398,11 +398,35 @@ struct ResizeArgs {
     const void *lut;
     const uint8_t *mirror;
     int32_t esize, lut_off;
+    // oriented plans (mj_plan_create_resized_oriented): 0 = none.  1: `mirror` holds, per image, bit 0 = store at column
+    // out_width - 1 - x, bit 1 = store at row out_height - 1 - y (the image's tap tables are the reversed ones, so the sums are
+    // those of the flipped source; a mirror flag is folded into bit 0).  2: the same, and the images are transposing
+    // orientations: the source is read as the other layout's kernel reads it (the stored rows are the oriented columns)
+    int32_t orient;
 };
 constexpr int64_t kResizeGridX = 1 << 20;      // workgroups along x of the resize launch's grid (the rest along y)
 int resize_axis_ksize(int in_size, int out_size);
 void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride);
 hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp);
+// ---- orient.hip: EXIF orientation at the files' own sizes
+// One image of an oriented plan: its stored-order pixels in the plan's intermediate buffer as rows x len pixels (len along
+// the contiguous axis: row-major plans height x width, x-major plans width x height) and what becomes of them — op bit 0:
+// the destination's rows run backwards, bit 1: its contiguous axis runs backwards, bit 2: rows and columns change places.
+struct DevOrientImage {
+    int64_t src_off, dst_off;     // bytes; an image keeps its place in the packing (orientation keeps the pixel count)
+    int32_t rows, len;
+    int32_t tiles_l;              // tiles along the contiguous axis
+    int32_t op;
+};
+struct OrientArgs {
+    const uint8_t *src;
+    uint8_t *dst;
+    const DevOrientImage *images;
+    const int64_t *tile_prefix;   // [n_images + 1]: first tile of every image, then the total
+    int64_t total_tiles;
+    int32_t n_images, planar;     // planar: the destination holds the components one plane after the other
+};
+hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp);
 // bits[v] = the bit pattern (in the low esize bytes) of resized byte v as an MJ_DTYPE_F16 / BF16 / F32 element:
 // fl32(fl32(fl32(v) / 255 - mean) / std), then rounded to nearest even into the 16-bit types (tools/normalize_model.py)
 void build_normalize_table(int dtype, float mean, float std, uint32_t *bits);

@@ -1,0 +1,145 @@
+// EXIF orientation at the files' own sizes: an oriented plan (mj_plan_create_oriented) decodes into a plan-owned buffer in
+// stored order, as a resized plan does, and ONE launch over all its images writes every image oriented into its packed place
+// in the output.  tools/orient_model.py is the definition: the eight values are a transpose (5..8) followed by reversed
+// columns and / or rows.
+//
+// In memory an image is rows x len pixels, len along the contiguous axis (row-major plans: height x width; x-major plans:
+// width x height), and an orientation is three bits on that array (DevOrientImage::op): the destination's rows backwards,
+// its contiguous axis backwards, rows and columns exchanged.  A workgroup takes one 64 x 64 pixel tile of the source:
+//   in   16-byte loads along the source's contiguous axis (at whatever alignment the tile starts: up to 15 bytes behind the
+//        tile's row are read along, which lie in the row, the next image or the buffer's slack) into LDS rows
+//   out  consecutive lanes store consecutive bytes of a destination row — whole runs of 64 pixels along the destination's
+//        contiguous axis, the source read backwards for a reversed axis and down an LDS column for orientations 5..8.
+// The LDS row pitch is 64 * C + 4 bytes = 49 dwords (colour) or 17 (grey): odd, so that the lanes of a column read — one
+// row apart each — fall into different banks instead of all into one.  Planar plans read the same interleaved source and
+// store one plane after the other.
+#include "plan.h"
+
+namespace mj {
+constexpr int kTile = 64;
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+
+template <int C>
+__global__ __launch_bounds__(256) void k_orient(const OrientArgs a) {
+    constexpr int P = kTile * C + 4;
+    __shared__ __attribute__((aligned(16))) unsigned char T[kTile * P];
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_orient: the grid's tail is idle)
+    if (wg >= a.total_tiles) return;
+    int img = 0, hi = a.n_images - 1;
+    while (img < hi) {                                                    // the last image whose first tile is not behind wg
+        const int mid = (img + hi + 1) >> 1;
+        if (a.tile_prefix[mid] <= wg) img = mid; else hi = mid - 1;
+    }
+    const DevOrientImage im = a.images[img];
+    const int t = (int)(wg - a.tile_prefix[img]);
+    const int tr = t / im.tiles_l, tl = t - tr * im.tiles_l;
+    const int r0 = tr * kTile, l0 = tl * kTile;
+    const int nr = min(kTile, im.rows - r0), nl = min(kTile, im.len - l0);
+    const int tid = threadIdx.x;
+    const unsigned char *src = a.src + im.src_off + ((int64_t)r0 * im.len + l0) * C;
+    const int nch = (nl * C + 15) >> 4;
+    for (int i = tid; i < nr * nch; i += 256) {
+        const int row = i / nch, j = i - row * nch;
+        u32x4 v;
+        __builtin_memcpy(&v, src + (int64_t)row * im.len * C + 16 * j, 16);
+        unsigned *d = reinterpret_cast<unsigned *>(T + row * P + 16 * j);
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    }
+    __syncthreads();
+    const bool swap = (im.op & 4) != 0, back_r = (im.op & 1) != 0, back_l = (im.op & 2) != 0;
+    // the destination: drows x dlen pixels; this tile's part of it is ndr x ndl, first pixel (dr0, dl0)
+    const int drows = swap ? im.len : im.rows, dlen = swap ? im.rows : im.len;
+    const int ndr = swap ? nl : nr, ndl = swap ? nr : nl;
+    const int sr0 = swap ? l0 : r0, sl0 = swap ? r0 : l0;
+    const int dr0 = back_r ? drows - (sr0 + ndr) : sr0, dl0 = back_l ? dlen - (sl0 + ndl) : sl0;
+    unsigned char *dst = a.dst + im.dst_off;
+    const bool planar = a.planar != 0 && C > 1;
+    const int total = ndr * ndl * C;
+    for (int i = tid; i < total; i += 256) {
+        int dr, dl, c;
+        if (planar) { c = i / (ndr * ndl); const int rem = i - c * (ndr * ndl); dr = rem / ndl; dl = rem - dr * ndl; }
+        else { dr = i / (ndl * C); const int e = i - dr * (ndl * C); dl = e / C; c = e - dl * C; }
+        const int ar = back_r ? ndr - 1 - dr : dr, al = back_l ? ndl - 1 - dl : dl;
+        const unsigned char v = T[(swap ? al : ar) * P + (swap ? ar : al) * C + c];
+        const int64_t pix = (int64_t)(dr0 + dr) * dlen + dl0 + dl;
+        if (planar) dst[(int64_t)c * drows * dlen + pix] = v;
+        else dst[pix * C + c] = v;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp) {
+    if (a.n_images <= 0 || a.total_tiles <= 0) return hipSuccess;
+    const int64_t gx = std::min<int64_t>(a.total_tiles, kResizeGridX);
+    const dim3 grid((unsigned)gx, (unsigned)((a.total_tiles + gx - 1) / gx)), block(256);
+    if (ncomp == 3) hipLaunchKernelGGL(k_orient<3>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(k_orient<1>, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace mj
+
+extern "C" int mj_plan_create_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, mj_plan **out) {
+    if (!ctx) return MJ_ERR_INVALID;
+    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: NULL argument");
+    *out = nullptr;
+    bool upright = true;
+    for (int i = 0; orientations && i < b->n_images; ++i) {
+        if (orientations[i] < 1 || orientations[i] > 8)
+            return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: image %d: orientation %d (must be 1..8)", i, (int)orientations[i]);
+        upright = upright && orientations[i] == 1;
+    }
+    if (upright) return rois ? mj_plan_create_roi(ctx, b, rois, out) : mj_plan_create(ctx, b, out);
+    if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
+        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none");
+    if (!b->images) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: NULL argument");
+    std::vector<mj_roi> stored;
+    if (rois) {
+        stored.resize((size_t)b->n_images);
+        for (int i = 0; i < b->n_images; ++i)
+            if (!mj::stored_window(orientations[i], b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
+                return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image",
+                            i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+    }
+    mj_plan *p = nullptr;
+    if (int rc = mj::plan_create_common(ctx, b, rois ? stored.data() : nullptr, rois != nullptr, &p)) return rc;
+    struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
+    const int n = p->n_images;
+    const bool xmajor = (p->layout & 1) == 0;
+    std::vector<mj::DevOrientImage> oi((size_t)n);
+    std::vector<int64_t> prefix((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        const int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
+        const int bits = mj::orient_bits(orientations[i]);
+        const int fx = bits & 1, fy = (bits >> 1) & 1;
+        mj::DevOrientImage &o = oi[(size_t)i];
+        o.src_off = o.dst_off = p->h_images[i].rgb_off;
+        o.rows = xmajor ? w : h; o.len = xmajor ? h : w;
+        o.tiles_l = (o.len + mj::kTile - 1) / mj::kTile;
+        // rows of a row-major array are the image's rows, rows of an x-major array its columns
+        o.op = (bits & 4) | (xmajor ? fx | fy << 1 : fy | fx << 1);
+        prefix[(size_t)i + 1] = prefix[(size_t)i] + (int64_t)o.tiles_l * ((o.rows + mj::kTile - 1) / mj::kTile);
+    }
+    if (prefix[(size_t)n] > mj::kResizeGridX * (int64_t)65535)
+        return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_oriented: %lld tiles are more than one launch takes; split the batch", (long long)prefix[(size_t)n]);
+    int rc;
+    if ((rc = upload(ctx, &p->d_or_images, oi.data(), oi.size())) != MJ_OK) return rc;
+    if ((rc = upload(ctx, &p->d_or_prefix, prefix.data(), prefix.size())) != MJ_OK) return rc;
+    // the stored-order pixels: a plan-owned buffer from the context's cache (64 bytes of slack: a tile row's last 16-byte load
+    // may end behind the bytes it uses)
+    p->src_bytes = p->info.rgb_bytes;
+    MJ_HIP(ctx, ctx->cache.get((void **)&p->d_src, (size_t)p->src_bytes + 64));
+    mj::OrientArgs &a = p->oa;
+    a = mj::OrientArgs{};
+    a.src = p->d_src; a.images = p->d_or_images; a.tile_prefix = p->d_or_prefix; a.total_tiles = prefix[(size_t)n];
+    a.n_images = n; a.planar = p->layout >= MJ_LAYOUT_PLANAR_XMAJOR ? 1 : 0;
+    p->resized = true;
+    p->orient_only = true;
+    guard.p = nullptr;
+    *out = p;
+    return MJ_OK;
+}

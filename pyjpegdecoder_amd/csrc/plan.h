@@ -267,6 +267,12 @@ struct mj_plan {
     uint8_t *d_rz_mirror = nullptr;        // ... with a mirror flag set: one byte per image
     uint8_t *d_rz_lut = nullptr;           // mj_plan_create_resized_as with a float dtype: the output table (info.rgb_bytes: bytes of that type)
     mj::ResizeArgs rz{};
+    // oriented plans at the files' own sizes (mj_plan_create_oriented): `resized` with the orient launch (orient.hip) in the
+    // resize launch's place — stage 2 writes stored-order pixels into d_src, the launch writes them oriented into the output
+    bool orient_only = false;
+    mj::DevOrientImage *d_or_images = nullptr;
+    int64_t *d_or_prefix = nullptr;
+    mj::OrientArgs oa{};
 };
 
 // ---- plan_tables.hip: table building (host)
@@ -282,6 +288,22 @@ int plan_progressive_scans(mj_context *ctx, const mj_batch *b, mj_plan *p, ProgS
 int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, ProgScans &S);
 // ---- plan_create.hip: what mj_plan_create / mj_plan_create_roi do (roi_plan: a window plan)
 int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, bool roi_plan, mj_plan **out);
+// ---- EXIF orientation (tools/orient_model.py): value 1..8 as operations on the row-major image — bit 2: transpose first,
+// then bit 0: reverse the columns, bit 1: reverse the rows
+inline int orient_bits(int o) {
+    static const int bits[9] = {0, 0, 1, 3, 2, 4, 5, 7, 6};
+    return bits[o];
+}
+// the window of the stored width x height image that window r of the oriented image shows (orient_model.stored_window);
+// false: r is empty or not inside the oriented image
+inline bool stored_window(int o, int width, int height, const mj_roi &r, mj_roi *out) {
+    const int bits = orient_bits(o);
+    const int64_t wo = (bits & 4) ? height : width, ho = (bits & 4) ? width : height;
+    if (r.width <= 0 || r.height <= 0 || r.x < 0 || r.y < 0 || (int64_t)r.x + r.width > wo || (int64_t)r.y + r.height > ho) return false;
+    const int x = (bits & 1) ? (int)(wo - r.x - r.width) : r.x, y = (bits & 2) ? (int)(ho - r.y - r.height) : r.y;
+    *out = (bits & 4) ? mj_roi{y, x, r.height, r.width} : mj_roi{x, y, r.width, r.height};
+    return true;
+}
 }  // namespace mj
 
 // (one definition per translation unit: they return through the caller's frame)

@@ -121,7 +121,7 @@ __device__ __forceinline__ const OutT *stage_lut(const ResizeArgs &a, unsigned c
 
 // Row-major source.  LDS: T [t_rows][t_pitch] | per output column of the tile: first source column (relative), taps, the
 // taps themselves [tc][ksx] | one staging row per wavefront | the output table (2- and 4-byte elements).
-template <int C, typename OutT = unsigned char, bool MIRROR = false>
+template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false>
 __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tiles = a.tiles_x * a.tiles_y;
@@ -173,6 +173,8 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
     // height pass: consecutive lanes take consecutive elements of an output row (of a plane's row for planar plans)
     OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
     const bool flip = MIRROR && a.mirror[img] != 0;
+    unsigned turn = 0;      // oriented plans: bit 0 = store at column ow - 1 - x, bit 1 = at row oh - 1 - y
+    if constexpr (ORIENT) turn = a.mirror[img];
     const int orows = oy1 - oy0, total = orows * ne;
     const bool planar = a.layout >= 2 && C > 1;
     for (int i = tid; i < total; i += 256) {
@@ -186,14 +188,15 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
         unsigned acc = 1u << 21;
         for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * a.t_pitch]);
         const int ox = ox0 + oxl;
-        dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy, c)] = out_value<OutT>(lut, c, clip8(acc));
+        if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, clip8(acc));
+        else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy, c)] = out_value<OutT>(lut, c, clip8(acc));
     }
 }
 
 // X-major source.  LDS: T [tc][t_pitch] (one row per output column: the bytes (y, c) of the source rows the tile needs,
 // t_pitch a multiple of 16) | per output row of the tile: first source row (relative), taps, the taps themselves [tr][ksy] |
 // the output table (2- and 4-byte elements).
-template <int C, typename OutT = unsigned char, bool MIRROR = false>
+template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false>
 __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tiles = a.tiles_x * a.tiles_y;
@@ -243,6 +246,8 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
     // height pass: consecutive lanes take consecutive elements of an output column (of a plane's column for planar plans)
     OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
     const bool flip = MIRROR && a.mirror[img] != 0;
+    unsigned turn = 0;      // oriented plans: bit 0 = store at column ow - 1 - x, bit 1 = at row oh - 1 - y
+    if constexpr (ORIENT) turn = a.mirror[img];
     const int ne = orows * C, total = ncols * ne;
     const bool planar = a.layout >= 2 && C > 1;
     for (int i = tid; i < total; i += 256) {
@@ -255,18 +260,20 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
         unsigned acc = 1u << 21;
         for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * C]);
         const int ox = ox0 + oxl;
-        dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy0 + oyl, c)] = out_value<OutT>(lut, c, clip8(acc));
+        if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - (oy0 + oyl) : oy0 + oyl, c)] = out_value<OutT>(lut, c, clip8(acc));
+        else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy0 + oyl, c)] = out_value<OutT>(lut, c, clip8(acc));
     }
 }
 
 // the instance of one output element and mirror mode: source order and component count picked at run time
-template <typename OutT, bool MIRROR>
+template <typename OutT, bool MIRROR, bool ORIENT = false>
 void launch_instance(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block) {
-    const bool xmajor = (a.layout & 1) == 0;
-    if (xmajor && ncomp == 3) hipLaunchKernelGGL((k_resize_xmajor<3, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
-    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor<1, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
-    else if (ncomp == 3) hipLaunchKernelGGL((k_resize_rowmajor<3, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
-    else hipLaunchKernelGGL((k_resize_rowmajor<1, OutT, MIRROR>), grid, block, a.lds_bytes, stream, a);
+    // (transposing orientations: the oriented image's rows are the stored columns — the other layout's way of reading)
+    const bool xmajor = ((a.layout & 1) == 0) != (ORIENT && a.orient == 2);
+    if (xmajor && ncomp == 3) hipLaunchKernelGGL((k_resize_xmajor<3, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
+    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor<1, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
+    else if (ncomp == 3) hipLaunchKernelGGL((k_resize_rowmajor<3, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
+    else hipLaunchKernelGGL((k_resize_rowmajor<1, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
 }
 
 }  // namespace
@@ -276,6 +283,12 @@ hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp) {
     // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
     const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
+    if (a.orient) {     // oriented plans: instances of their own (the per-image byte holds both store flips)
+        if (a.esize == 4) launch_instance<uint32_t, false, true>(stream, a, ncomp, grid, block);
+        else if (a.esize == 2) launch_instance<uint16_t, false, true>(stream, a, ncomp, grid, block);
+        else launch_instance<unsigned char, false, true>(stream, a, ncomp, grid, block);
+        return hipGetLastError();
+    }
     // (a plan of mj_plan_create_resized: esize 1, no mirror — the instances that were there before the others)
     if (a.esize == 4) { if (a.mirror) launch_instance<uint32_t, true>(stream, a, ncomp, grid, block); else launch_instance<uint32_t, false>(stream, a, ncomp, grid, block); }
     else if (a.esize == 2) { if (a.mirror) launch_instance<uint16_t, true>(stream, a, ncomp, grid, block); else launch_instance<uint16_t, false>(stream, a, ncomp, grid, block); }
@@ -363,7 +376,7 @@ const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean
 }
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out);
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, mj_plan **out);
 
 }  // namespace
 
@@ -393,12 +406,25 @@ int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
 
 int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                            const int32_t *slots, int32_t n_slots, mj_plan **out) {
-    return create_resized("mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, nullptr, out);
+    return create_resized("mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, nullptr, nullptr, out);
 }
 
 int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                               const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
-    return create_resized("mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, output, out);
+    return create_resized("mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, output, nullptr, out);
+}
+
+int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                    mj_plan **out) {
+    const char *fn = "mj_plan_create_resized_oriented";
+    bool upright = true;
+    for (int i = 0; orientations && b && i < b->n_images; ++i) {
+        if (orientations[i] < 1 || orientations[i] > 8)
+            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
+        upright = upright && orientations[i] == 1;
+    }
+    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, out);
 }
 
 }  // extern "C"
@@ -406,7 +432,8 @@ int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *b, const mj_roi *
 namespace {
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, mj_plan **out) {
+    // (orient: NULL, or one checked orientation 1..8 per image, not all of them 1)
     // the output description first: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
     // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
     const int dtype = output ? output->dtype : MJ_DTYPE_U8;
@@ -426,6 +453,25 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     for (int i = 0; slots && i < b->n_images; ++i)
         if (slots[i] < 0 || slots[i] >= n_slots)
             return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, slots[i], n_slots);
+    // oriented plans: all images transposing (orientations 5..8) or none — the two read their source in different ways, so
+    // they are two launches, i.e. two plans (BatchDecoder sorts the files); windows are given in oriented coordinates
+    bool swapped = false;
+    std::vector<mj_roi> stored;
+    if (orient) {
+        if (!b->images) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+        swapped = b->n_images > 0 && (mj::orient_bits(orient[0]) & 4);
+        for (int i = 0; i < b->n_images; ++i)
+            if (((mj::orient_bits(orient[i]) & 4) != 0) != swapped)
+                return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: orientations that exchange width and height (5..8) and others do not share a resized plan; split the batch", fn, i);
+        if (rois) {
+            stored.resize((size_t)b->n_images);
+            for (int i = 0; i < b->n_images; ++i)
+                if (!mj::stored_window(orient[i], b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
+                    return fail(ctx, MJ_ERR_INVALID, "%s: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image", fn,
+                                i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+            rois = stored.data();
+        }
+    }
     mj_plan *p = nullptr;
     // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
     if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
@@ -435,14 +481,26 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     // tap tables: one per distinct source size and axis
     std::map<int, AxisHost> xs, ys;
     std::vector<int32_t> words;
-    auto axis = [&](std::map<int, AxisHost> &m, int in_size, int out_size) -> const AxisHost & {
-        auto it = m.find(in_size);
+    // (back: the table of an axis the orientation reverses — entry j is entry out_size - 1 - j of the plain table read from the
+    // other end of the source, taps in reverse; the sums are integer sums of the same products, and the first source index
+    // still grows with j, which is what the kernels' tile bounds assume.  The kernel stores entry j at out_size - 1 - j.)
+    auto axis = [&](std::map<int, AxisHost> &m, int in_size, int out_size, bool back = false) -> const AxisHost & {
+        const int key = 2 * in_size + (back ? 1 : 0);
+        auto it = m.find(key);
         if (it != m.end()) return it->second;
-        AxisHost &A = m[in_size];
+        AxisHost &A = m[key];
         A.ks = mj::resize_axis_ksize(in_size, out_size);
         A.lo.resize(out_size); A.cnt.resize(out_size);
         std::vector<int32_t> k((size_t)out_size * A.ks);
         mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks);
+        if (back) {
+            std::vector<int32_t> lo(A.lo), cnt(A.cnt), kk(k);
+            for (int j = 0; j < out_size; ++j) {
+                const int s = out_size - 1 - j;
+                A.lo[j] = in_size - lo[s] - cnt[s]; A.cnt[j] = cnt[s];
+                for (int t = 0; t < A.ks; ++t) k[(size_t)j * A.ks + t] = t < cnt[s] ? kk[(size_t)s * A.ks + cnt[s] - 1 - t] : 0;
+            }
+        }
         A.word_off = (int)words.size();
         words.push_back(A.ks);
         words.insert(words.end(), A.lo.begin(), A.lo.end());
@@ -454,13 +512,16 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     std::vector<uint8_t> flags((size_t)n, 0);      // mirror, per image
     int any_mirror = 0;
     for (int i = 0; i < n; ++i) {
-        const int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
+        int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
+        const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+        if (bits & 4) std::swap(w, h);      // (from here on the oriented image's size)
         ri[i].src_off = p->h_images[i].rgb_off;
         ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
         ri[i].w = w; ri[i].h = h;
         if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
-        ri[i].xtab = axis(xs, w, out_width).word_off;
-        ri[i].ytab = axis(ys, h, out_height).word_off;
+        if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
+        ri[i].xtab = axis(xs, w, out_width, bits & 1).word_off;
+        ri[i].ytab = axis(ys, h, out_height, bits & 2).word_off;
         if (words.size() > ((size_t)1 << 28)) return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: the tap tables of this batch are too large", fn);
     }
     // (a pure function of the tile: what it takes in LDS and where the parts lie; nothing is kept until a tile is chosen)
@@ -470,7 +531,8 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     // tile's tap tables, the staging rows, the output table of a 2- or 4-byte element — for every source size of the batch.  Tiles shrink until it does: a row-major plan
     // gives up columns first while a row segment stays 2 KB long (its loads run along the rows), then rows; an x-major plan
     // keeps its rows (its loads run along the columns) and gives up columns.
-    const bool xmajor = (p->layout & 1) == 0;
+    // (how the source is read, which for transposing orientations is the other layout's way: launch_instance)
+    const bool xmajor = ((p->layout & 1) == 0) != swapped;
     mj::ResizeArgs &a = p->rz;
     a = mj::ResizeArgs{};
     int tr = std::min<int>(xmajor ? 32 : 16, out_height), tc = out_width;
@@ -501,7 +563,7 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         if (tc > 1 && cols_first) tc = (tc + 1) / 2;
         else if (tr > 1) tr = (tr + 1) / 2;
         else return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds", fn,
-                         xs.rbegin()->first, ys.rbegin()->first, out_width, out_height);
+                         xs.rbegin()->first / 2, ys.rbegin()->first / 2, out_width, out_height);
     }
     // (a small batch: more, smaller tiles, so that the chip has something to do)
     auto n_tiles = [&](int tr_, int tc_) { return (int64_t)n * ((out_height + tr_ - 1) / tr_) * ((out_width + tc_ - 1) / tc_); };
@@ -517,7 +579,8 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     int rc;
     if ((rc = upload(ctx, &p->d_rz_images, ri.data(), ri.size())) != MJ_OK) return rc;
     if ((rc = upload(ctx, &p->d_rz_tabs, words.data(), words.size())) != MJ_OK) return rc;
-    if (any_mirror) {       // (no flag set: the instances without mirror)
+    a.orient = orient ? (swapped ? 2 : 1) : 0;
+    if (any_mirror || orient) {       // (no flag set: the instances without mirror)
         if ((rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) != MJ_OK) return rc;
         a.mirror = p->d_rz_mirror;
     }
