@@ -272,6 +272,30 @@ int mj_plan_create_oriented(mj_context *ctx, const mj_batch *batch, const mj_roi
 int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
                                     const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
                                     mj_plan **out);
+/* Resample filters: mj_plan_create_resized_oriented (output and orientations may be NULL, as there) whose resize is Pillow's
+ * Image.resize((out_width, out_height), <filter>) for any of its convolution filters — byte for byte, in every layout, with
+ * everything the other arguments do (dtype, normalisation, mirror, orientation, windows, slots) inside the same one launch.
+ *   MJ_FILTER_BILINEAR  support 1    exactly mj_plan_create_resized_oriented: the same plan, the same kernels
+ *   MJ_FILTER_BOX       support 0.5  1 on (-0.5, 0.5]
+ *   MJ_FILTER_HAMMING   support 1    sinc(x) * (0.54 + 0.46 cos(pi x))
+ *   MJ_FILTER_BICUBIC   support 2    Keys' cubic with a = -0.5
+ *   MJ_FILTER_LANCZOS   support 3    sinc(x) * sinc(x / 3) on [-3, 3)
+ * (Pillow's NEAREST is not a convolution — it walks an affine transform — and is not offered.)  The support grows with the scale
+ * when shrinking; weights in doubles, normalised, rounded away from zero to 22 bits (mj_host_resize_table_filtered); per pixel
+ * clip((2^21 + sum taps * in) >> 22, 0, 255) with a signed sum and an arithmetic shift: the taps of BICUBIC and LANCZOS are
+ * negative in their side lobes, and plans of those two run signed instances of the resize kernels (the other three share the
+ * unsigned ones: their taps are >= 0).  Width first, then height, an 8-bit image in between, as ever.
+ * MJ_ERR_INVALID: a filter that is none of these, and whatever mj_plan_create_resized_oriented refuses; MJ_ERR_UNSUPPORTED, in
+ * addition to that function's: a table with a tap of 2^23 or more in magnitude or with 2^21 + 255 * sum |tap| above 2^31 - 1
+ * (the kernels multiply in 24 bits and add in 32; no size up to 129 comes near either bound). */
+#define MJ_FILTER_BILINEAR 0
+#define MJ_FILTER_BOX      1
+#define MJ_FILTER_HAMMING  2
+#define MJ_FILTER_BICUBIC  3
+#define MJ_FILTER_LANCZOS  4
+int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                    int32_t filter, mj_plan **out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -362,6 +386,11 @@ int mj_plan_fill_coef(mj_plan *plan, int byte_value);
 
 /* Test hook: every byte of a resized plan's intermediate buffer (the un-resized pixels) := byte_value (synchronous). */
 int mj_plan_fill_source(mj_plan *plan, int byte_value);
+
+/* Test hook: how a resized plan's launch is cut and which instances it runs — out = { output rows per tile, output columns per
+ * tile, tiles along the width, tiles along the height (per image), bytes of LDS per workgroup, the plan's MJ_FILTER_*, 1 if it
+ * runs the signed instances, the most taps one pixel has along an axis }.  MJ_ERR_INVALID: not a resized plan. */
+int mj_debug_resize_shape(const mj_plan *plan, int32_t out[8]);
 
 /* ---- one-shot conveniences ----------------------------------------------------------------------- */
 /* create + execute + sync + read + destroy; rgb_out/status_out host, coef_out may be NULL. */
@@ -460,6 +489,10 @@ void mj_host_idct_table(double *tt);
  * *ksize = taps a row can hold at most (taps_stride must be at least that).  xmin = count = taps = NULL: only *ksize. */
 int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride,
                          int32_t *ksize);
+/* mj_host_resize_table for any MJ_FILTER_* (filter MJ_FILTER_BILINEAR: the identical table); taps may be negative.
+ * MJ_ERR_INVALID also for a filter that is none of them. */
+int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
+                                  int32_t taps_stride, int32_t *ksize);
 /* The output table of one component of a mj_plan_create_resized_as plan, as the library builds it (host only, no context): out
  * = 256 elements of `dtype` (MJ_DTYPE_F16 / BF16: 2 bytes each, MJ_DTYPE_F32: 4), element v what resized byte v is stored as with
  * this mean and std (mean 0, std 1 = no normalisation).  MJ_ERR_INVALID: MJ_DTYPE_U8 or an unknown dtype, NULL, a mean that is

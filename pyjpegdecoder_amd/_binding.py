@@ -24,6 +24,10 @@ MJ_DTYPE_U8, MJ_DTYPE_F16, MJ_DTYPE_BF16, MJ_DTYPE_F32 = 0, 1, 2, 3
 # the element types of a model-ready output (mj_output_desc.dtype) by the name NumPy and torch share
 DTYPES = {"uint8": MJ_DTYPE_U8, "float16": MJ_DTYPE_F16, "bfloat16": MJ_DTYPE_BF16, "float32": MJ_DTYPE_F32}
 DTYPE_BYTES = {"uint8": 1, "float16": 2, "bfloat16": 2, "float32": 4}
+MJ_FILTER_BILINEAR, MJ_FILTER_BOX, MJ_FILTER_HAMMING, MJ_FILTER_BICUBIC, MJ_FILTER_LANCZOS = 0, 1, 2, 3, 4
+# the resample filters of a decode to a fixed size by name (tools/resize_model.py: FILTERS)
+FILTERS = {"bilinear": MJ_FILTER_BILINEAR, "box": MJ_FILTER_BOX, "hamming": MJ_FILTER_HAMMING, "bicubic": MJ_FILTER_BICUBIC,
+           "lanczos": MJ_FILTER_LANCZOS}
 
 # every symbol include/mijpeg.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -36,6 +40,7 @@ EXPORTS = (
     "mj_plan_create_resized", "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table",
     "mj_plan_create_resized_as", "mj_host_normalize_table",
     "mj_plan_create_oriented", "mj_plan_create_resized_oriented", "mj_host_exif_orientations",
+    "mj_plan_create_resized_filtered", "mj_host_resize_table_filtered", "mj_debug_resize_shape",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -136,6 +141,10 @@ def load_library():
     L.mj_plan_create_oriented.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), vp, ctypes.POINTER(vp)]
     L.mj_plan_create_resized_oriented.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
                                                   ctypes.POINTER(OutputDescC), vp, ctypes.POINTER(vp)]
+    L.mj_plan_create_resized_filtered.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
+                                                  ctypes.POINTER(OutputDescC), vp, i32, ctypes.POINTER(vp)]
+    L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
+    L.mj_debug_resize_shape.argtypes = [vp, ctypes.POINTER(i32)]
     L.mj_host_exif_orientations.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.mj_host_normalize_table.argtypes = [i32, ctypes.c_float, ctypes.c_float, vp]
     L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
@@ -248,17 +257,35 @@ def prog_split_rule(n_images, scans, mode=1, n_bands=68, wave_slots=0, parts=0):
     return out[:n].astype(bool).tolist(), int(po.value)
 
 
-def resize_table(in_size: int, out_size: int):
+def filter_id(filter) -> int:
+    """MJ_FILTER_* from that number or the filter's name (ValueError otherwise); None is bilinear."""
+    if filter is None:
+        return MJ_FILTER_BILINEAR
+    if isinstance(filter, str) and filter in FILTERS:
+        return FILTERS[filter]
+    if isinstance(filter, (int, np.integer)) and not isinstance(filter, bool) and int(filter) in FILTERS.values():
+        return int(filter)
+    raise ValueError(f"filter must be one of {', '.join(FILTERS)} (or its MJ_FILTER_* number), not {filter!r}")
+
+
+def resize_table(in_size: int, out_size: int, filter=None):
     """mj_host_resize_table (host only): (xmin[out_size], count[out_size], taps[out_size, ksize]) int32 — one axis of the
-    resize of ``decode(..., size=...)`` as the library builds it (tools/resize_model.py: axis_table)."""
+    resize of ``decode(..., size=...)`` as the library builds it (tools/resize_model.py: axis_table).  ``filter``: a name of
+    FILTERS or an MJ_FILTER_* — mj_host_resize_table_filtered's table for that filter (None: the bilinear one, through the
+    function that was there before the filters)."""
     L = load_library()
     ks = ctypes.c_int32()
-    if L.mj_host_resize_table(in_size, out_size, None, None, None, 0, ctypes.byref(ks)) != MJ_OK:
-        raise ValueError("mj_host_resize_table: sizes must be 1..65535")
+    if filter is None:
+        fn, call = "mj_host_resize_table", L.mj_host_resize_table
+    else:
+        fid = filter_id(filter)
+        fn, call = "mj_host_resize_table_filtered", lambda *a: L.mj_host_resize_table_filtered(fid, *a)
+    if call(in_size, out_size, None, None, None, 0, ctypes.byref(ks)) != MJ_OK:
+        raise ValueError(f"{fn}: sizes must be 1..65535")
     xmin, count = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
     taps = np.zeros((out_size, ks.value), dtype=np.int32)
-    if L.mj_host_resize_table(in_size, out_size, _ptr(xmin), _ptr(count), _ptr(taps), ks.value, ctypes.byref(ks)) != MJ_OK:
-        raise ValueError("mj_host_resize_table: bad arguments")
+    if call(in_size, out_size, _ptr(xmin), _ptr(count), _ptr(taps), ks.value, ctypes.byref(ks)) != MJ_OK:
+        raise ValueError(f"{fn}: bad arguments")
     return xmin, count, taps
 
 
@@ -396,9 +423,12 @@ class Plan:
     (the resized bytes) or (dtype name, mean or None, std or None, mirror flag per image or None) — a model-ready output
     (mj_plan_create_resized_as): elements of that type, normalised, flagged images mirrored; info.rgb_bytes is then in bytes
     of that type.  orientation: None, or one EXIF orientation 1..8 per image — an oriented plan (mj_plan_create_oriented, with
-    size mj_plan_create_resized_oriented): outputs as the orientation shows the images, rois in oriented coordinates."""
+    size mj_plan_create_resized_oriented): outputs as the orientation shows the images, rois in oriented coordinates.
+    filter: with size, None or "bilinear" (the plans above, through the entry points above) or another name of FILTERS / its
+    MJ_FILTER_*: the resize with that resample filter (mj_plan_create_resized_filtered)."""
 
-    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None):
+    def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
+                 filter=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -410,7 +440,15 @@ class Plan:
             if slots is not None:
                 sl = np.ascontiguousarray(slots[0], dtype=np.int32)
                 n_slots = int(slots[1])
-            if orientation is not None:
+            fid = filter_id(filter)
+            if fid != MJ_FILTER_BILINEAR:
+                turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
+                desc, flags = output_desc(output) if output is not None else (None, None)
+                if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):
+                    raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
+                ctx.check(ctx.lib.mj_plan_create_resized_filtered(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
+                                                                  ctypes.byref(desc) if desc is not None else None, _ptr(turns), fid, ctypes.byref(h)))
+            elif orientation is not None:
                 turns = np.ascontiguousarray(orientation, dtype=np.uint8)
                 desc, flags = output_desc(output) if output is not None else (None, None)
                 if turns.size != batch_c.n_images or (flags is not None and flags.size != batch_c.n_images):
@@ -426,6 +464,8 @@ class Plan:
                     raise ValueError(f"output: {flags.size} mirror flags for {batch_c.n_images} images")
                 ctx.check(ctx.lib.mj_plan_create_resized_as(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl),
                                                             n_slots, ctypes.byref(desc), ctypes.byref(h)))
+        elif filter is not None:
+            raise ValueError("filter needs size: only a resized plan resamples")
         elif output is not None:
             raise ValueError("output needs size: only a resized plan has a dense output")
         elif orientation is not None:
@@ -470,6 +510,15 @@ class Plan:
     def fill_source(self, byte_value: int):
         """Test hook (mj_plan_fill_source): poison a resized plan's intermediate buffer."""
         self.ctx.check(self.ctx.lib.mj_plan_fill_source(self.handle, int(byte_value)))
+
+    def resize_shape(self) -> dict:
+        """mj_debug_resize_shape: how a resized plan's launch is cut (tile_rows, tile_cols, tiles_x, tiles_y per image, lds_bytes),
+        its filter (MJ_FILTER_*), whether it runs the signed instances, and the most taps a pixel has along an axis."""
+        out = (ctypes.c_int32 * 8)()
+        self.ctx.check(self.ctx.lib.mj_debug_resize_shape(self.handle, out))
+        d = dict(zip(("tile_rows", "tile_cols", "tiles_x", "tiles_y", "lds_bytes", "filter", "signed", "max_ksize"), (int(v) for v in out)))
+        d["signed"] = bool(d["signed"])
+        return d
 
     def time_resize(self, iters: int = 10, rgb_device: int = 0):
         """(ms per resize launch, bytes of un-resized pixels it reads) of a resized plan that has been executed."""

@@ -372,6 +372,33 @@ def normalize_size(size) -> Optional[Tuple[int, int]]:
     return int(size[0]), int(size[1])
 
 
+# Pillow's Image.Resampling numbering of the convolution filters (0 is NEAREST)
+_PILLOW_FILTERS = {1: "lanczos", 2: "bilinear", 3: "bicubic", 4: "box", 5: "hamming"}
+
+
+def normalize_resample(resample, size) -> Optional[str]:
+    """The resample filter of a decode to a fixed size, checked: None for the default — ``None``, "bilinear" or Pillow's
+    ``Image.Resampling.BILINEAR`` / 2, which all are a call without the argument — else "box", "hamming", "bicubic" or "lanczos".
+    ``resample``: such a name (in any case), the ``Image.Resampling`` member, or its integer value.  It needs ``size``.
+    ValueError otherwise."""
+    if resample is None:
+        return None
+    if size is None:
+        raise ValueError("resample needs size=(width, height): without it nothing is resized")
+    name = None
+    if isinstance(resample, str):
+        name = resample.lower()
+    elif isinstance(resample, (int, np.integer)) and not isinstance(resample, (bool, np.bool_)):      # (Image.Resampling is an IntEnum)
+        name = "nearest" if int(resample) == 0 else _PILLOW_FILTERS.get(int(resample))
+    if name == "nearest":
+        raise ValueError("resample: Pillow's NEAREST is not a convolution (it walks an affine transform) and is not offered; "
+                         "the filters are bilinear, box, hamming, bicubic and lanczos")
+    if name not in B.FILTERS:
+        raise ValueError(f"resample must be one of {', '.join(B.FILTERS)} (a name, Pillow's Image.Resampling member or its integer "
+                         f"value), not {resample!r}")
+    return None if name == "bilinear" else name
+
+
 def one_component_count(ncomps: Sequence[int]) -> int:
     """The component count the files of a decode to a fixed size share (they fill one array); ValueError naming the first file
     that differs from file 0.  No files at all: 3 — the empty result then has a colour batch's shape, (0, ..., 3)."""
@@ -604,7 +631,8 @@ class _Request:
     (:func:`normalize_size`'s, or None), the model-ready output (or None) and, with ``size``, the array or tensor the plans
     write the images into and every file's slot in it (both None: every plan fills a dense array of its own).  ``index``:
     where every file sits in the list the caller passed, for the messages of errors (None: this is that list).  ``orient``:
-    :func:`normalize_orientation`'s list (None: every file as stored); the windows are then windows of the oriented images."""
+    :func:`normalize_orientation`'s list (None: every file as stored); the windows are then windows of the oriented images.
+    ``resample``: :func:`normalize_resample`'s filter of the resize (None: bilinear, the request of a call without the argument)."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
@@ -613,6 +641,7 @@ class _Request:
     slots: Optional[List[int]] = None
     index: Optional[List[int]] = None
     orient: Optional[List[int]] = None
+    resample: Optional[str] = None
 
     def narrow(self, idxs) -> "_Request":
         """the same request for some of its files: their windows, slots, mirror flags, orientations and positions in the call go
@@ -626,7 +655,7 @@ class _Request:
         if orient is not None and all(o == 1 for o in orient):
             orient = None
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots), pick(index), orient)
+                        self.dest, pick(self.slots), pick(index), orient, self.resample)
 
     def orient_classes(self) -> List[List[int]]:
         """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
@@ -638,12 +667,14 @@ class _Request:
         return list(classes.values())
 
     def plan_kwargs(self) -> dict:
-        """``rois``, ``size``, ``slots``, ``output`` and ``orientation`` of :class:`_binding.Plan` for one plan of all its files, in order"""
+        """``rois``, ``size``, ``slots``, ``output``, ``orientation`` and ``filter`` of :class:`_binding.Plan` for one plan of all its files, in order"""
         kw = {"rois": self.wins, "size": self.size,
               "slots": (self.slots, self.dest.shape[0]) if self.slots is not None else None,
               "output": self.output.plan_output() if self.output else None}
         if self.orient is not None:         # (files as stored: the arguments of a call without orientation)
             kw["orientation"] = self.orient
+        if self.resample is not None:       # (bilinear: the arguments of a call without resample)
+            kw["filter"] = self.resample
         return kw
 
 
@@ -788,7 +819,7 @@ class BatchDecoder:
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs())
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
-               orientation=None):
+               orientation=None, resample=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -798,7 +829,10 @@ class BatchDecoder:
         ``Normalize(mean, std)(to_tensor(img))`` of the resized bytes bit for bit, flagged files flipped along the width.
         ``orientation``: None (the pixels as stored), "exif" (every file turned as its EXIF Orientation tag says: Pillow's
         ``ImageOps.exif_transpose``), an int 1..8 for every file, or one of these per file (:func:`normalize_orientation`).
-        Shapes, ``rois`` and ``size`` then all refer to the turned image; ``mirror`` comes after it."""
+        Shapes, ``rois`` and ``size`` then all refer to the turned image; ``mirror`` comes after it.
+        ``resample``, with ``size``: the filter of the resize — None or "bilinear" (the default), "box", "hamming", "bicubic" or
+        "lanczos", Pillow's ``Image.Resampling`` member or its integer value (:func:`normalize_resample`); one filter for the whole
+        call.  Every image is then Pillow's ``resize(size, <that filter>)`` byte for byte, and everything else composes as ever."""
         if orientation is not None and return_seams:
             raise ValueError("orientation and return_seams do not go together: the seam outputs are in stored order")
         if rois is not None and return_seams:
@@ -807,11 +841,12 @@ class BatchDecoder:
         if size is not None and return_seams:
             raise ValueError("size and return_seams do not go together: the seam outputs are at the files' own sizes")
         normalize_output(dtype, normalize, mirror, size, host=True)       # (what needs no file: before any is parsed)
+        resample = normalize_resample(resample, size)
         gpu_segment = self._gpu_segment_for(files)
         parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
         orient = normalize_orientation(orientation, files)
         req = _Request(files, normalize_rois(rois, _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)), size,
-                       orient=orient)
+                       orient=orient, resample=resample)
         turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
@@ -868,11 +903,11 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None) -> _Request:
+    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order."""
-        req = _Request(files, None, size, orient=normalize_orientation(orientation, files))
+        req = _Request(files, None, size, orient=normalize_orientation(orientation, files), resample=normalize_resample(resample, size))
         if size is not None:
             import torch
             info = [_image_info(f) for f in files]
@@ -896,7 +931,7 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, orientation=None):
+                      mirror=None, orientation=None, resample=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -918,10 +953,13 @@ class BatchDecoder:
         ``orientation`` as in :meth:`decode`: None, "exif", an int 1..8, or one of these per file.  The tags are read on host
         threads; turned files are plans of their own (upright ones decode exactly as without the argument), written turned by
         one more launch per plan — or, with ``size``, by the resize launch itself, whose result is Pillow's resize of the
-        turned image."""
+        turned image.
+        ``resample`` as in :meth:`decode`: the filter of the resize, one for the whole call — every plan of it (second rounds,
+        files of several kinds, parts) resamples with it."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation)
+        normalize_resample(resample, size)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
@@ -1029,7 +1067,7 @@ class BatchDecoder:
                     flight.plan.close()
         return results if req.dest is None else req.dest
 
-    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None):
+    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1045,8 +1083,10 @@ class BatchDecoder:
         ``size=(width, height)``: one tensor per batch, as :meth:`decode_device` returns it with ``size``; ``dtype`` and
         ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file).  ``orientation``: None, "exif" or
-        an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes."""
+        an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes.
+        ``resample`` as in :meth:`decode_device`, for every batch."""
         size = normalize_size(size)
+        normalize_resample(resample, size)                                            # (what needs no file: before any work)
         turns_per_batch = not (orientation is None or isinstance(orientation, (str, int, np.integer)))
         if not turns_per_batch:
             normalize_orientation(orientation, [])                                    # (what needs no file: before any work)
@@ -1072,7 +1112,7 @@ class BatchDecoder:
                         o = next(turns)
                     except StopIteration:
                         raise ValueError("orientation yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m, o)
+                yield self._device_request(files, None, size, dtype, normalize, m, o, resample)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

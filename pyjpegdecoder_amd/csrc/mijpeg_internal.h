@@ -403,10 +403,16 @@ struct ResizeArgs {
     // those of the flipped source; a mirror flag is folded into bit 0).  2: the same, and the images are transposing
     // orientations: the source is read as the other layout's kernel reads it (the stored rows are the oriented columns)
     int32_t orient;
+    // 1: a filter whose taps go below zero (bicubic, Lanczos) — the signed instances; a mirror flag then travels as an
+    // oriented plan's bit 0 does (launch_signed)
+    int32_t sgn;
 };
 constexpr int64_t kResizeGridX = 1 << 20;      // workgroups along x of the resize launch's grid (the rest along y)
-int resize_axis_ksize(int in_size, int out_size);
-void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride);
+// (filter: MJ_FILTER_*, one that resize_filter_known)
+bool resize_filter_known(int filter);
+bool resize_filter_signed(int filter);
+int resize_axis_ksize(int in_size, int out_size, int filter = 0);
+void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0);
 hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp);
 // ---- orient.hip: EXIF orientation at the files' own sizes
 // One image of an oriented plan: its stored-order pixels in the plan's intermediate buffer as rows x len pixels (len along

@@ -1,9 +1,11 @@
 // Decode to a fixed size: the batch's decoded pixels (whole images or windows, as stage 2 packed them) resized to one
 // out_width x out_height, all images in ONE launch, into one dense output.
 //
-// The arithmetic is Pillow's Image.resize(size, BILINEAR) on 8-bit data (tools/resize_model.py restates it): per axis a
-// table of integer taps — triangle-filter weights in doubles, support growing with the scale when shrinking, normalised,
-// rounded to 22 bits: build_resize_axis, host — and per pixel clip8((2^21 + sum taps * in) >> 22).  Two passes with a uint8
+// The arithmetic is Pillow's Image.resize(size, filter) on 8-bit data (tools/resize_model.py restates it) for BILINEAR — the
+// default — BOX, HAMMING, BICUBIC and LANCZOS (mj_plan_create_resized_filtered): per axis a
+// table of integer taps — the filter's weights in doubles, support growing with the scale when shrinking, normalised,
+// rounded to 22 bits: build_resize_axis, host — and per pixel clip8((2^21 + sum taps * in) >> 22), signed and clamped at both
+// ends where the filter's taps go below zero (Tap).  Two passes with a uint8
 // intermediate image: along the width first, then along the height.  The order and the intermediate rounding are part of the
 // result.  (An axis that does not change goes through the same code: its table is one tap of 2^22, which is the identity.)
 //
@@ -36,17 +38,58 @@ namespace mj {
 
 // ---- host: tap tables -----------------------------------------------------------------------------------------------
 // xmin[out], count[out], taps[out][ksize] (zeros behind count); the formulas and their evaluation order are Pillow's
-// (precompute_coeffs + normalize_coeffs_8bpc with the bilinear filter).  Compiled with -ffp-contract=off like everything here.
-int resize_axis_ksize(int in_size, int out_size) {
+// (precompute_coeffs + normalize_coeffs_8bpc with the filter's function and support).  Compiled with -ffp-contract=off like
+// everything here; sin and cos are the host's libm, as they are Pillow's.
+namespace {
+
+const double kPi = 3.14159265358979323846;
+
+double f_bilinear(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+double f_box(double x) { return x > -0.5 && x <= 0.5 ? 1.0 : 0.0; }
+double f_hamming(double x) {
+    if (x < 0.0) x = -x;
+    if (x == 0.0) return 1.0;
+    if (x >= 1.0) return 0.0;
+    x = x * kPi;
+    return sin(x) / x * (0.54f + 0.46f * cos(x));      // (the two constants are float literals in Pillow: part of the result)
+}
+double f_bicubic(double x) {       // a = -0.5, Pillow's Horner form
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * -0.5;
+    return 0.0;
+}
+double f_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * kPi;
+    return sin(x) / x;
+}
+double f_lanczos(double x) { return -3.0 <= x && x < 3.0 ? f_sinc(x) * f_sinc(x / 3) : 0.0; }
+
+struct FilterDef { double support; double (*f)(double); };
+// (indexed by MJ_FILTER_*)
+const FilterDef kFilters[] = {{1.0, f_bilinear}, {0.5, f_box}, {1.0, f_hamming}, {2.0, f_bicubic}, {3.0, f_lanczos}};
+
+}  // namespace
+
+bool resize_filter_known(int filter) { return filter >= 0 && filter < (int)(sizeof(kFilters) / sizeof(kFilters[0])); }
+// taps below zero (side lobes): the kernels' signed instances
+bool resize_filter_signed(int filter) { return filter == MJ_FILTER_BICUBIC || filter == MJ_FILTER_LANCZOS; }
+
+int resize_axis_ksize(int in_size, int out_size, int filter) {
     const double scale = (double)in_size / (double)out_size;
-    const double support = 1.0 * (scale < 1.0 ? 1.0 : scale);
+    const double support = kFilters[filter].support * (scale < 1.0 ? 1.0 : scale);
     return (int)ceil(support) * 2 + 1;
 }
 
-void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride) {
+void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter) {
+    const FilterDef &F = kFilters[filter];
     const double scale = (double)in_size / (double)out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale, ss = 1.0 / filterscale;
+    const double support = F.support * filterscale, ss = 1.0 / filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     std::vector<double> w((size_t)ksize + 2);
     for (int xx = 0; xx < out_size; ++xx) {
@@ -59,9 +102,7 @@ void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count,
         if (n > ksize) n = ksize;
         double ww = 0.0;
         for (int x = 0; x < n; ++x) {
-            double a = ((double)(x + lo) - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            w[x] = a < 1.0 ? 1.0 - a : 0.0;
+            w[x] = F.f(((double)(x + lo) - center + 0.5) * ss);
             ww += w[x];
         }
         xmin[xx] = lo;
@@ -69,7 +110,8 @@ void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count,
         for (int x = 0; x < taps_stride; ++x) {
             double v = x < n ? w[x] : 0.0;
             if (x < n && ww != 0.0) v /= ww;
-            taps[(size_t)xx * taps_stride + x] = x < n ? (int32_t)(v * (double)(1 << 22) + 0.5) : 0;
+            // (rounded away from zero, as normalize_coeffs_8bpc does)
+            taps[(size_t)xx * taps_stride + x] = x >= n ? 0 : v < 0.0 ? (int32_t)(v * (double)(1 << 22) - 0.5) : (int32_t)(v * (double)(1 << 22) + 0.5);
         }
     }
 }
@@ -100,6 +142,23 @@ __device__ __forceinline__ unsigned clip8(unsigned acc) {
     return v > 255u ? 255u : v;
 }
 
+// One output byte's sum.  Tap<false>: every tap is >= 0 (bilinear, box, hamming) — unsigned sums, the unsigned 24-bit multiply,
+// a clamp at the top: the instances that were there before the other filters, the code they were.  Tap<true>: taps with negative
+// side lobes (bicubic, Lanczos) — int sums, the signed 24-bit multiply (plan creation holds every |tap| below 2^23 and every
+// 2^21 + 255 * sum |tap| below 2^31), an arithmetic shift and a clamp at both ends.
+template <bool SGN> struct Tap {
+    typedef unsigned acc_t;
+    static __device__ __forceinline__ unsigned mul(int32_t k, unsigned v) { return __umul24((unsigned)k, v); }
+    static __device__ __forceinline__ unsigned clip(unsigned acc) { return clip8(acc); }
+};
+template <> struct Tap<true> {
+    typedef int acc_t;
+    static __device__ __forceinline__ int mul(int32_t k, unsigned v) { return __mul24(k, (int)v); }
+    // (the lower clamp in front of the shift, which is then a logical one: written as clamp(acc >> 22, 0, 255) the compiler packs
+    // pairs of these with v_ashr_pk_u8_i32, and what came back from the chip was not clamped at 0)
+    static __device__ __forceinline__ unsigned clip(int acc) { return min((unsigned)max(acc, 0) >> 22, 255u); }
+};
+
 // the element a finished byte v of component c is stored as: the byte, or its entry of the workgroup's table
 template <typename OutT>
 __device__ __forceinline__ OutT out_value(const OutT *lut, int c, unsigned v) {
@@ -121,8 +180,9 @@ __device__ __forceinline__ const OutT *stage_lut(const ResizeArgs &a, unsigned c
 
 // Row-major source.  LDS: T [t_rows][t_pitch] | per output column of the tile: first source column (relative), taps, the
 // taps themselves [tc][ksx] | one staging row per wavefront | the output table (2- and 4-byte elements).
-template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false>
+template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false, bool SGN = false>
 __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
+    typedef typename Tap<SGN>::acc_t acc_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tiles = a.tiles_x * a.tiles_y;
     const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
@@ -161,9 +221,9 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
             const unsigned char *s = stage + mis + lx_lo[oxl] + c;
             const int32_t *k = lx_k + oxl * X.ks;
             const int n = lx_cnt[oxl];
-            unsigned acc = 1u << 21;
-            for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * C]);
-            T[r * a.t_pitch + e] = (unsigned char)clip8(acc);
+            acc_t acc = (acc_t)1 << 21;
+            for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * C]);
+            T[r * a.t_pitch + e] = (unsigned char)Tap<SGN>::clip(acc);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -185,19 +245,20 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
         const int n = Y.cnt[oy];
         const int32_t *k = Y.k + (int64_t)oy * Y.ks;
         const unsigned char *s = T + (Y.lo[oy] - ya) * a.t_pitch + oxl * C + c;
-        unsigned acc = 1u << 21;
-        for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * a.t_pitch]);
+        acc_t acc = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * a.t_pitch]);
         const int ox = ox0 + oxl;
-        if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, clip8(acc));
-        else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy, c)] = out_value<OutT>(lut, c, clip8(acc));
+        if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, Tap<SGN>::clip(acc));
+        else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy, c)] = out_value<OutT>(lut, c, Tap<SGN>::clip(acc));
     }
 }
 
 // X-major source.  LDS: T [tc][t_pitch] (one row per output column: the bytes (y, c) of the source rows the tile needs,
 // t_pitch a multiple of 16) | per output row of the tile: first source row (relative), taps, the taps themselves [tr][ksy] |
 // the output table (2- and 4-byte elements).
-template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false>
+template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false, bool SGN = false>
 __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
+    typedef typename Tap<SGN>::acc_t acc_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tiles = a.tiles_x * a.tiles_y;
     const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
@@ -226,20 +287,20 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
         const int ox = ox0 + oxl, n = X.cnt[ox];
         const int32_t *k = X.k + (int64_t)ox * X.ks;
         const unsigned char *p = src + ((int64_t)X.lo[ox] * im.h + ya) * C + 16 * j;
-        unsigned acc[16];
+        acc_t acc[16];
 #pragma unroll
-        for (int b = 0; b < 16; ++b) acc[b] = 1u << 21;
+        for (int b = 0; b < 16; ++b) acc[b] = (acc_t)1 << 21;
         for (int q = 0; q < n; ++q, p += col) {
             u32x4 v;
             __builtin_memcpy(&v, p, 16);
-            const unsigned kq = (unsigned)k[q];
+            const int32_t kq = k[q];
 #pragma unroll
-            for (int b = 0; b < 16; ++b) acc[b] += __umul24(kq, (v[b >> 2] >> (8 * (b & 3))) & 255u);
+            for (int b = 0; b < 16; ++b) acc[b] += Tap<SGN>::mul(kq, (v[b >> 2] >> (8 * (b & 3))) & 255u);
         }
         u32x4 o;
 #pragma unroll
         for (int d = 0; d < 4; ++d)
-            o[d] = clip8(acc[4 * d]) | clip8(acc[4 * d + 1]) << 8 | clip8(acc[4 * d + 2]) << 16 | clip8(acc[4 * d + 3]) << 24;
+            o[d] = Tap<SGN>::clip(acc[4 * d]) | Tap<SGN>::clip(acc[4 * d + 1]) << 8 | Tap<SGN>::clip(acc[4 * d + 2]) << 16 | Tap<SGN>::clip(acc[4 * d + 3]) << 24;
         *reinterpret_cast<u32x4 *>(T + oxl * a.t_pitch + 16 * j) = o;
     }
     __syncthreads();
@@ -257,23 +318,31 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
         const int n = ly_cnt[oyl];
         const int32_t *k = ly_k + oyl * Y.ks;
         const unsigned char *s = T + oxl * a.t_pitch + ly_lo[oyl] + c;
-        unsigned acc = 1u << 21;
-        for (int q = 0; q < n; ++q) acc += __umul24((unsigned)k[q], (unsigned)s[q * C]);
+        acc_t acc = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * C]);
         const int ox = ox0 + oxl;
-        if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - (oy0 + oyl) : oy0 + oyl, c)] = out_value<OutT>(lut, c, clip8(acc));
-        else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy0 + oyl, c)] = out_value<OutT>(lut, c, clip8(acc));
+        if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - (oy0 + oyl) : oy0 + oyl, c)] = out_value<OutT>(lut, c, Tap<SGN>::clip(acc));
+        else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy0 + oyl, c)] = out_value<OutT>(lut, c, Tap<SGN>::clip(acc));
     }
 }
 
 // the instance of one output element and mirror mode: source order and component count picked at run time
-template <typename OutT, bool MIRROR, bool ORIENT = false>
+template <typename OutT, bool MIRROR, bool ORIENT = false, bool SGN = false>
 void launch_instance(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block) {
     // (transposing orientations: the oriented image's rows are the stored columns — the other layout's way of reading)
     const bool xmajor = ((a.layout & 1) == 0) != (ORIENT && a.orient == 2);
-    if (xmajor && ncomp == 3) hipLaunchKernelGGL((k_resize_xmajor<3, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
-    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor<1, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
-    else if (ncomp == 3) hipLaunchKernelGGL((k_resize_rowmajor<3, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
-    else hipLaunchKernelGGL((k_resize_rowmajor<1, OutT, MIRROR, ORIENT>), grid, block, a.lds_bytes, stream, a);
+    if (xmajor && ncomp == 3) hipLaunchKernelGGL((k_resize_xmajor<3, OutT, MIRROR, ORIENT, SGN>), grid, block, a.lds_bytes, stream, a);
+    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor<1, OutT, MIRROR, ORIENT, SGN>), grid, block, a.lds_bytes, stream, a);
+    else if (ncomp == 3) hipLaunchKernelGGL((k_resize_rowmajor<3, OutT, MIRROR, ORIENT, SGN>), grid, block, a.lds_bytes, stream, a);
+    else hipLaunchKernelGGL((k_resize_rowmajor<1, OutT, MIRROR, ORIENT, SGN>), grid, block, a.lds_bytes, stream, a);
+}
+
+// the signed instances of one output element: plain, or — for a mirrored or an oriented plan alike — the oriented instance,
+// whose per-image byte holds a mirror flag in bit 0 as it holds an orientation's (no signed mirror instances: half the count)
+template <typename OutT>
+void launch_signed(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block) {
+    if (a.mirror) launch_instance<OutT, false, true, true>(stream, a, ncomp, grid, block);
+    else launch_instance<OutT, false, false, true>(stream, a, ncomp, grid, block);
 }
 
 }  // namespace
@@ -283,6 +352,12 @@ hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp) {
     // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
     const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
+    if (a.sgn) {        // bicubic and Lanczos plans: the signed instances
+        if (a.esize == 4) launch_signed<uint32_t>(stream, a, ncomp, grid, block);
+        else if (a.esize == 2) launch_signed<uint16_t>(stream, a, ncomp, grid, block);
+        else launch_signed<unsigned char>(stream, a, ncomp, grid, block);
+        return hipGetLastError();
+    }
     if (a.orient) {     // oriented plans: instances of their own (the per-image byte holds both store flips)
         if (a.esize == 4) launch_instance<uint32_t, false, true>(stream, a, ncomp, grid, block);
         else if (a.esize == 2) launch_instance<uint16_t, false, true>(stream, a, ncomp, grid, block);
@@ -376,21 +451,39 @@ const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean
 }
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, mj_plan **out);
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out);
+
+// ... of the oriented images: the orientations checked (NULL, or all of them 1: a plan without them)
+int create_resized_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                            const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int filter,
+                            mj_plan **out) {
+    bool upright = true;
+    for (int i = 0; orientations && b && i < b->n_images; ++i) {
+        if (orientations[i] < 1 || orientations[i] > 8)
+            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
+        upright = upright && orientations[i] == 1;
+    }
+    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, filter, out);
+}
 
 }  // namespace
 
 extern "C" {
 
-int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride,
-                         int32_t *ksize_out) {
-    if (in_size < 1 || out_size < 1 || in_size > 65535 || out_size > 65535) return MJ_ERR_INVALID;
-    const int ks = mj::resize_axis_ksize(in_size, out_size);
+int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
+                                  int32_t taps_stride, int32_t *ksize_out) {
+    if (!mj::resize_filter_known(filter) || in_size < 1 || out_size < 1 || in_size > 65535 || out_size > 65535) return MJ_ERR_INVALID;
+    const int ks = mj::resize_axis_ksize(in_size, out_size, filter);
     if (ksize_out) *ksize_out = ks;
     if (!xmin && !count && !taps) return MJ_OK;
     if (!xmin || !count || !taps || taps_stride < ks) return MJ_ERR_INVALID;
-    mj::build_resize_axis(in_size, out_size, xmin, count, taps, taps_stride);
+    mj::build_resize_axis(in_size, out_size, xmin, count, taps, taps_stride, filter);
     return MJ_OK;
+}
+
+int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride,
+                         int32_t *ksize_out) {
+    return mj_host_resize_table_filtered(MJ_FILTER_BILINEAR, in_size, out_size, xmin, count, taps, taps_stride, ksize_out);
 }
 
 int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
@@ -406,25 +499,35 @@ int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
 
 int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                            const int32_t *slots, int32_t n_slots, mj_plan **out) {
-    return create_resized("mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, nullptr, nullptr, out);
+    return create_resized("mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, nullptr, nullptr, MJ_FILTER_BILINEAR, out);
 }
 
 int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                               const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
-    return create_resized("mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, output, nullptr, out);
+    return create_resized("mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, output, nullptr, MJ_FILTER_BILINEAR, out);
 }
 
 int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                                     const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
                                     mj_plan **out) {
-    const char *fn = "mj_plan_create_resized_oriented";
-    bool upright = true;
-    for (int i = 0; orientations && b && i < b->n_images; ++i) {
-        if (orientations[i] < 1 || orientations[i] > 8)
-            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
-        upright = upright && orientations[i] == 1;
-    }
-    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, out);
+    return create_resized_oriented("mj_plan_create_resized_oriented", ctx, b, rois, out_width, out_height, slots, n_slots, output, orientations,
+                                   MJ_FILTER_BILINEAR, out);
+}
+
+int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                    int32_t filter, mj_plan **out) {
+    const char *fn = "mj_plan_create_resized_filtered";
+    if (!mj::resize_filter_known(filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, filter);
+    return create_resized_oriented(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, orientations, filter, out);
+}
+
+int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
+    if (!p || !out || !p->resized || p->orient_only) return MJ_ERR_INVALID;
+    const mj::ResizeArgs &a = p->rz;
+    const int32_t v[8] = {a.tr, a.tc, a.tiles_x, a.tiles_y, a.lds_bytes, p->rz_filter, a.sgn, p->rz_max_ksize};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return MJ_OK;
 }
 
 }  // extern "C"
@@ -432,8 +535,8 @@ int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *b, const mj
 namespace {
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, mj_plan **out) {
-    // (orient: NULL, or one checked orientation 1..8 per image, not all of them 1)
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out) {
+    // (filter: a known MJ_FILTER_*; orient: NULL, or one checked orientation 1..8 per image, not all of them 1)
     // the output description first: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
     // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
     const int dtype = output ? output->dtype : MJ_DTYPE_U8;
@@ -481,6 +584,11 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     // tap tables: one per distinct source size and axis
     std::map<int, AxisHost> xs, ys;
     std::vector<int32_t> words;
+    // What the kernels' arithmetic holds (resize.hip: Tap): a 24-bit multiply and a 32-bit sum — signed for the filters with side
+    // lobes.  Measured over sizes 1..129 the taps stay far inside (tests/test_resample_host.py); that is no proof for every
+    // size, so every table is checked and one that breaks a bound is refused (range_in / range_out: its sizes).
+    const bool sgn = mj::resize_filter_signed(filter);
+    int range_in = 0, range_out = 0;
     // (back: the table of an axis the orientation reverses — entry j is entry out_size - 1 - j of the plain table read from the
     // other end of the source, taps in reverse; the sums are integer sums of the same products, and the first source index
     // still grows with j, which is what the kernels' tile bounds assume.  The kernel stores entry j at out_size - 1 - j.)
@@ -489,10 +597,19 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         auto it = m.find(key);
         if (it != m.end()) return it->second;
         AxisHost &A = m[key];
-        A.ks = mj::resize_axis_ksize(in_size, out_size);
+        A.ks = mj::resize_axis_ksize(in_size, out_size, filter);
         A.lo.resize(out_size); A.cnt.resize(out_size);
         std::vector<int32_t> k((size_t)out_size * A.ks);
-        mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks);
+        mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks, filter);
+        for (int j = 0; j < out_size && !range_in; ++j) {
+            int64_t sum = 0, big = 0, least = 0;
+            for (int t = 0; t < A.ks; ++t) {
+                const int64_t v = k[(size_t)j * A.ks + t], m = v < 0 ? -v : v;
+                sum += m; big = std::max(big, m); least = std::min(least, v);
+            }
+            const int64_t top = ((int64_t)1 << 21) + 255 * sum;
+            if (sgn ? (big >= (1 << 23) || top > INT32_MAX) : (least < 0 || big >= (1 << 24) || top > (int64_t)UINT32_MAX)) { range_in = in_size; range_out = out_size; }
+        }
         if (back) {
             std::vector<int32_t> lo(A.lo), cnt(A.cnt), kk(k);
             for (int j = 0; j < out_size; ++j) {
@@ -522,6 +639,9 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
         ri[i].xtab = axis(xs, w, out_width, bits & 1).word_off;
         ri[i].ytab = axis(ys, h, out_height, bits & 2).word_off;
+        if (range_in)
+            return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: resizing %d to %d with filter %d gives taps outside what the kernels' 24-bit products and 32-bit sums hold", fn,
+                        range_in, range_out, filter);
         if (words.size() > ((size_t)1 << 28)) return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: the tap tables of this batch are too large", fn);
     }
     // (a pure function of the tile: what it takes in LDS and where the parts lie; nothing is kept until a tile is chosen)
@@ -580,6 +700,10 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     if ((rc = upload(ctx, &p->d_rz_images, ri.data(), ri.size())) != MJ_OK) return rc;
     if ((rc = upload(ctx, &p->d_rz_tabs, words.data(), words.size())) != MJ_OK) return rc;
     a.orient = orient ? (swapped ? 2 : 1) : 0;
+    a.sgn = sgn ? 1 : 0;
+    p->rz_filter = filter;
+    for (auto &kv : xs) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
+    for (auto &kv : ys) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
     if (any_mirror || orient) {       // (no flag set: the instances without mirror)
         if ((rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) != MJ_OK) return rc;
         a.mirror = p->d_rz_mirror;
