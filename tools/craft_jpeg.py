@@ -1,8 +1,10 @@
 """Write baseline JPEG files symbol by symbol, with ANY per-component sampling factors — test inputs for layouts no
 encoder at hand produces (4:1:0, 1x4, luma below the chroma resolution, factors of 3 ...).
 
-The coefficients are random (the decoders under test do not care what the picture shows); the Huffman and quantisation
-tables are the Annex-K ones of tools/std_tables.h.  Input-generation tooling only; nothing here is on the decode path."""
+The coefficients are random (the decoders under test do not care what the picture shows) unless craft_baseline is handed
+the blocks to write (tests/stage2_families.py: coefficients chosen against the fast stage 2's rare paths); the Huffman
+and, by default, the quantisation tables are the Annex-K ones of tools/std_tables.h.  Input-generation tooling only;
+nothing here is on the decode path."""
 from __future__ import annotations
 
 import re
@@ -128,11 +130,16 @@ def wide_ac_table(seed: int = 0):
 
 
 def craft_baseline(width: int, height: int, factors, seed: int = 0, restart_interval: int = 0, density: float = 0.35,
-                   max_size: int = 5, dc_size: int = 5, tables=None, ac_tables=None) -> bytes:
+                   max_size: int = 5, dc_size: int = 5, tables=None, ac_tables=None, blocks=None, qts=None) -> bytes:
     """A baseline file of `width` x `height` with one interleaved scan; `factors` = ((h, v), ...) per component (1 or 3 of them).
     `tables` = per component (dc table, ac table) as indices into the table lists (default: luma tables for the first
     component, chroma tables for the others); `ac_tables` = extra (bits, vals) AC tables behind the two Annex-K ones (index
-    2..): files whose components share or swap tables, up to four tables per class."""
+    2..): files whose components share or swap tables, up to four tables per class.
+    `blocks` = the coefficients to write instead of random ones: int16 [n_blocks, 64], zig-zag, in MCU order (the order of
+    the scan: every MCU its first component's h*v blocks, then the others'), index 0 the ABSOLUTE DC — the DC differences
+    (per component, from 0 again behind every restart marker) are formed here.  `qts` = up to two quantisation tables of 64
+    zig-zag entries 1..255 in place of the Annex-K luma / chroma ones (table 0: first component, table 1: the others).
+    Every value must have a code: the Annex-K tables end at DC size 11 and AC size 10 (wide_ac_table: 15)."""
     factors = [tuple(f) for f in factors]
     ncomp = len(factors)
     assert ncomp in (1, 3)
@@ -141,8 +148,15 @@ def craft_baseline(width: int, height: int, factors, seed: int = 0, restart_inte
     vmax = max(v for _, v in factors) if ncomp > 1 else 1
     mcw, mch = -(-width // (8 * hmax)), -(-height // (8 * vmax))
     out = bytearray(b"\xFF\xD8")
-    out += _seg(0xDB, b"\x00" + _T["STD_QT_LUMA_ZZ"])
-    out += _seg(0xDB, b"\x01" + _T["STD_QT_CHROMA_ZZ"])
+    qt_bytes = [_T["STD_QT_LUMA_ZZ"], _T["STD_QT_CHROMA_ZZ"]]
+    if qts is not None:
+        assert 1 <= len(qts) <= 2
+        for t, q in enumerate(qts):
+            q = [int(v) for v in np.asarray(q).reshape(-1)]
+            assert len(q) == 64 and all(1 <= v <= 255 for v in q), "a quantisation table is 64 zig-zag entries 1..255"
+            qt_bytes[t] = bytes(q)
+    out += _seg(0xDB, b"\x00" + qt_bytes[0])
+    out += _seg(0xDB, b"\x01" + qt_bytes[1])
     sof = bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big") + bytes([ncomp])
     for c, (h, v) in enumerate(factors):
         sof += bytes([c + 1, (h << 4) | v, 0 if c == 0 else 1])
@@ -168,10 +182,28 @@ def craft_baseline(width: int, height: int, factors, seed: int = 0, restart_inte
     w = _Bits()
     n_mcu = mcw * mch
     rst = 0
+    if blocks is not None:
+        blocks = np.asarray(blocks)
+        per_mcu = sum(h * v for h, v in factors) if ncomp > 1 else 1
+        assert blocks.shape == (n_mcu * per_mcu, 64), f"blocks must be [{n_mcu * per_mcu}, 64] for this geometry, not {blocks.shape}"
+    pred = [0] * ncomp                              # (blocks=) the DC predictors
+    nb = 0
     for m in range(n_mcu):
         for c, (h, v) in enumerate(factors):
             rep = h * v if ncomp > 1 else 1
             for _ in range(rep):
+                if blocks is not None:
+                    zz = blocks[nb].astype(np.int64)
+                    nb += 1
+                    dc = int(zz[0])
+                    zz[0] = dc - pred[c]
+                    pred[c] = dc
+                    assert _category(int(zz[0])) in _DC[tables[c][0]], f"block {nb - 1}: no code for a DC difference of {int(zz[0])}"
+                    top = int(np.abs(zz[1:]).max())
+                    assert all(((r << 4) | _category(top)) in ac_codes[tables[c][1]] for r in range(16 if top else 0)), \
+                        f"block {nb - 1}: AC table {tables[c][1]} has no code for a value of {top}"
+                    _encode_block(w, zz, _DC[tables[c][0]], ac_codes[tables[c][1]])
+                    continue
                 # (the Annex-K tables have no symbol for sizes above 10)
                 _encode_block(w, random_block(rng, density, max_size if tables[c][1] >= 2 else min(max_size, 10), dc_size),
                               _DC[tables[c][0]], ac_codes[tables[c][1]])
@@ -179,6 +211,7 @@ def craft_baseline(width: int, height: int, factors, seed: int = 0, restart_inte
             w.flush()
             w.out += bytes([0xFF, 0xD0 + (rst & 7)])
             rst += 1
+            pred = [0] * ncomp
     w.flush()
     out += w.out
     out += b"\xFF\xD9"
