@@ -296,6 +296,35 @@ int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *batch, cons
 int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
                                     const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
                                     int32_t filter, mj_plan **out);
+/* Output colour mode: plans whose outputs have the components the CALLER names instead of the files' — Pillow's img.convert(mode)
+ * (tools/mode_model.py) of the decoded pixels, before everything else: the result is exif_transpose(img.convert(mode)) and, resized,
+ * .resize(size, filter) of that.
+ *   MJ_MODE_NATIVE  the files' own components
+ *   MJ_MODE_L       one component.  A colour image's pixel becomes L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the RGB bytes
+ *                   a plan without the mode gives (not the file's Y plane: the colour conversion's rounding lies in between)
+ *   MJ_MODE_RGB     three components.  A greyscale image's byte goes into all three
+ * MJ_MODE_NATIVE, or the mode that is the batch's own component count (its first image's), returns exactly the plan the function
+ * without the argument returns: the same code makes it.  Any other value: MJ_ERR_INVALID.  A plan that converts:
+ *   mj_plan_info.rgb_bytes, the slots' offsets and mj_plan_image_offsets' rgb_off count OUTPUT components; output->mean / std
+ *   are read for the mode's components (a greyscale file under MJ_MODE_RGB gets three tables applied to its one byte);
+ *   MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT are refused (the seam outputs are in the files' components).
+ *   mj_plan_create_resized_mode   mj_plan_create_resized_filtered plus the mode.  The resize launch converts: colour to L where the
+ *     source is read, in front of the width pass (resize-then-convert is another result), grey to RGB where the output is stored;
+ *     both passes run on one component, and no extra pass over memory is made in either direction.
+ *   mj_plan_create_mode           mj_plan_create_oriented plus the mode (orientations may be NULL): outputs at the files' own sizes,
+ *     packed image after image, every image width * height * <the mode's components> bytes.  The one extra launch of an oriented plan
+ *     (csrc/orient.hip) converts on its way; a plan that converts has that launch for upright images too.
+ *   mj_host_convert_mode          the host twin of the kernels' conversion (no context): n_pixels pixels of src_ncomp (1 or 3)
+ *     interleaved components into out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an
+ *     unknown mode, a src_ncomp that is neither 1 nor 3, NULL with pixels to convert. */
+#define MJ_MODE_NATIVE 0
+#define MJ_MODE_L      1
+#define MJ_MODE_RGB    3
+int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                int32_t filter, int32_t mode, mj_plan **out);
+int mj_plan_create_mode(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, const uint8_t *orientations, int32_t mode, mj_plan **out);
+int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments

@@ -29,6 +29,10 @@ MJ_FILTER_BILINEAR, MJ_FILTER_BOX, MJ_FILTER_HAMMING, MJ_FILTER_BICUBIC, MJ_FILT
 FILTERS = {"bilinear": MJ_FILTER_BILINEAR, "box": MJ_FILTER_BOX, "hamming": MJ_FILTER_HAMMING, "bicubic": MJ_FILTER_BICUBIC,
            "lanczos": MJ_FILTER_LANCZOS}
 
+MJ_MODE_NATIVE, MJ_MODE_L, MJ_MODE_RGB = 0, 1, 3
+# the output colour modes by Pillow's name: MJ_MODE_*, which is the component count of the output
+MODES = {"L": MJ_MODE_L, "RGB": MJ_MODE_RGB}
+
 # every symbol include/mijpeg.h declares (tests check the library exports all of them)
 EXPORTS = (
     "mj_create", "mj_destroy", "mj_last_error", "mj_version", "mj_context_wait_event",
@@ -41,6 +45,7 @@ EXPORTS = (
     "mj_plan_create_resized_as", "mj_host_normalize_table",
     "mj_plan_create_oriented", "mj_plan_create_resized_oriented", "mj_host_exif_orientations",
     "mj_plan_create_resized_filtered", "mj_host_resize_table_filtered", "mj_debug_resize_shape",
+    "mj_plan_create_resized_mode", "mj_plan_create_mode", "mj_host_convert_mode",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -143,6 +148,10 @@ def load_library():
                                                   ctypes.POINTER(OutputDescC), vp, ctypes.POINTER(vp)]
     L.mj_plan_create_resized_filtered.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
                                                   ctypes.POINTER(OutputDescC), vp, i32, ctypes.POINTER(vp)]
+    L.mj_plan_create_resized_mode.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
+                                              ctypes.POINTER(OutputDescC), vp, i32, i32, ctypes.POINTER(vp)]
+    L.mj_plan_create_mode.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), vp, i32, ctypes.POINTER(vp)]
+    L.mj_host_convert_mode.argtypes = [i32, vp, i32, i64, vp]
     L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_debug_resize_shape.argtypes = [vp, ctypes.POINTER(i32)]
     L.mj_host_exif_orientations.argtypes = [vp, vp, vp, vp, i32, i32, vp]
@@ -300,6 +309,31 @@ def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarr
     return out
 
 
+def mode_id(mode) -> int:
+    """MJ_MODE_* from that number or the mode's name (ValueError otherwise); None is MJ_MODE_NATIVE."""
+    if mode is None:
+        return MJ_MODE_NATIVE
+    if isinstance(mode, str) and mode in MODES:
+        return MODES[mode]
+    if isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and int(mode) in (MJ_MODE_NATIVE, MJ_MODE_L, MJ_MODE_RGB):
+        return int(mode)
+    raise ValueError(f"mode must be one of {', '.join(MODES)} (or its MJ_MODE_* number), not {mode!r}")
+
+
+def convert_mode(a: np.ndarray, mode) -> np.ndarray:
+    """mj_host_convert_mode (host only): uint8 pixels ``a`` — (..., 3) colour, or any other shape greyscale — in ``mode`` ("L",
+    "RGB", None or an MJ_MODE_*): the host twin of the kernels' conversion (tools/mode_model.py: convert)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    mid = mode_id(mode)
+    nc = 3 if a.ndim >= 2 and a.shape[-1] == 3 else 1
+    pix = a.shape[:-1] if nc == 3 else a.shape
+    co = mid or nc
+    out = np.empty(tuple(pix) + ((3,) if co == 3 else ()), dtype=np.uint8)
+    if load_library().mj_host_convert_mode(mid, _ptr(a), nc, int(np.prod(pix, dtype=np.int64)), _ptr(out)) != MJ_OK:
+        raise ValueError("mj_host_convert_mode: bad arguments")
+    return out
+
+
 def exif_orientations(files, n_threads: int = 0) -> np.ndarray:
     """mj_host_exif_orientations (host only): the EXIF Orientation tag (1..8) of every file of a list of ``bytes``, uint8 — what
     ``_parse.exif_orientation`` answers for each, read on host threads."""
@@ -425,17 +459,36 @@ class Plan:
     of that type.  orientation: None, or one EXIF orientation 1..8 per image — an oriented plan (mj_plan_create_oriented, with
     size mj_plan_create_resized_oriented): outputs as the orientation shows the images, rois in oriented coordinates.
     filter: with size, None or "bilinear" (the plans above, through the entry points above) or another name of FILTERS / its
-    MJ_FILTER_*: the resize with that resample filter (mj_plan_create_resized_filtered)."""
+    MJ_FILTER_*: the resize with that resample filter (mj_plan_create_resized_filtered).
+    mode: None, or a name of MODES / its MJ_MODE_* — the components of the output (mj_plan_create_mode, with size
+    mj_plan_create_resized_mode, which take all of the above); info.rgb_bytes, slots and image_offsets then count those."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None):
+                 filter=None, mode=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
         arr = None
         if rois is not None:
             arr = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in r)) for r in rois])
-        if size is not None:
+        if mode is not None:
+            turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
+            desc, flags = output_desc(output) if output is not None else (None, None)
+            if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):
+                raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
+            if size is not None:
+                sl, n_slots = None, 0
+                if slots is not None:
+                    sl = np.ascontiguousarray(slots[0], dtype=np.int32)
+                    n_slots = int(slots[1])
+                ctx.check(ctx.lib.mj_plan_create_resized_mode(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
+                                                              ctypes.byref(desc) if desc is not None else None, _ptr(turns), filter_id(filter),
+                                                              mode_id(mode), ctypes.byref(h)))
+            elif filter is not None or output is not None:
+                raise ValueError("filter and output need size: only a resized plan resamples and has a dense output")
+            else:
+                ctx.check(ctx.lib.mj_plan_create_mode(ctx.handle, ctypes.byref(batch_c), arr, _ptr(turns), mode_id(mode), ctypes.byref(h)))
+        elif size is not None:
             sl, n_slots = None, 0
             if slots is not None:
                 sl = np.ascontiguousarray(slots[0], dtype=np.int32)

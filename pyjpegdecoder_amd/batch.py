@@ -399,6 +399,17 @@ def normalize_resample(resample, size) -> Optional[str]:
     return None if name == "bilinear" else name
 
 
+def normalize_mode(mode) -> Optional[str]:
+    """The output colour mode of a call, checked: None (every file in its own components: a call without the argument), "RGB"
+    (three components: a greyscale file's value in all of them, Pillow's ``convert("RGB")``) or "L" (one: a colour file's
+    ``convert("L")``, tools/mode_model.py).  ``mode``: None or one of these two names of Pillow's.  ValueError otherwise."""
+    if mode is None:
+        return None
+    if not isinstance(mode, str) or mode not in B.MODES:
+        raise ValueError(f"mode must be None or one of {', '.join(repr(m) for m in B.MODES)} (Pillow's mode names), not {mode!r}")
+    return mode
+
+
 def one_component_count(ncomps: Sequence[int]) -> int:
     """The component count the files of a decode to a fixed size share (they fill one array); ValueError naming the first file
     that differs from file 0.  No files at all: 3 — the empty result then has a colour batch's shape, (0, ..., 3)."""
@@ -632,7 +643,8 @@ class _Request:
     write the images into and every file's slot in it (both None: every plan fills a dense array of its own).  ``index``:
     where every file sits in the list the caller passed, for the messages of errors (None: this is that list).  ``orient``:
     :func:`normalize_orientation`'s list (None: every file as stored); the windows are then windows of the oriented images.
-    ``resample``: :func:`normalize_resample`'s filter of the resize (None: bilinear, the request of a call without the argument)."""
+    ``resample``: :func:`normalize_resample`'s filter of the resize (None: bilinear, the request of a call without the argument).
+    ``mode``: :func:`normalize_mode`'s output colour mode (None: every file's own components)."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
@@ -642,6 +654,12 @@ class _Request:
     index: Optional[List[int]] = None
     orient: Optional[List[int]] = None
     resample: Optional[str] = None
+    mode: Optional[str] = None
+
+    @property
+    def ncomp(self) -> Optional[int]:
+        """the components of every output under the request's mode (None: the files' own)"""
+        return B.MODES[self.mode] if self.mode is not None else None
 
     def narrow(self, idxs) -> "_Request":
         """the same request for some of its files: their windows, slots, mirror flags, orientations and positions in the call go
@@ -655,7 +673,7 @@ class _Request:
         if orient is not None and all(o == 1 for o in orient):
             orient = None
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots), pick(index), orient, self.resample)
+                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode)
 
     def orient_classes(self) -> List[List[int]]:
         """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
@@ -666,8 +684,9 @@ class _Request:
             classes.setdefault(_orient_class(o, self.size is not None), []).append(i)
         return list(classes.values())
 
-    def plan_kwargs(self) -> dict:
-        """``rois``, ``size``, ``slots``, ``output``, ``orientation`` and ``filter`` of :class:`_binding.Plan` for one plan of all its files, in order"""
+    def plan_kwargs(self, native: Optional[int] = None) -> dict:
+        """``rois``, ``size``, ``slots``, ``output``, ``orientation``, ``filter`` and ``mode`` of :class:`_binding.Plan` for one plan of all
+        its files, in order (``native``: the component count these files have, which decides whether the plan converts)"""
         kw = {"rois": self.wins, "size": self.size,
               "slots": (self.slots, self.dest.shape[0]) if self.slots is not None else None,
               "output": self.output.plan_output() if self.output else None}
@@ -675,6 +694,8 @@ class _Request:
             kw["orientation"] = self.orient
         if self.resample is not None:       # (bilinear: the arguments of a call without resample)
             kw["filter"] = self.resample
+        if self.mode is not None and native != self.ncomp:      # (files of the mode's own count: the arguments of a call without mode)
+            kw["mode"] = self.mode
         return kw
 
 
@@ -794,13 +815,15 @@ class BatchDecoder:
         return (3,) + wh if self.layout >= B.MJ_LAYOUT_PLANAR_XMAJOR else wh + (3,)
 
     @staticmethod
-    def _out_shapes(prep: PreparedBatch, wins=None, orient=None) -> List[Tuple[int, int, int]]:
-        """(width, height, ncomp) of every image's output: the image — as its orientation shows it —, or its window."""
+    def _out_shapes(prep: PreparedBatch, wins=None, orient=None, ncomp: Optional[int] = None) -> List[Tuple[int, int, int]]:
+        """(width, height, ncomp) of every image's output: the image — as its orientation shows it —, or its window; in ``ncomp``
+        components (an output colour mode's), or the files' own."""
+        shapes = prep.shapes if ncomp is None else [(w, h, ncomp) for (w, h, _) in prep.shapes]
         if wins is None:
             if orient is not None:
-                return [(h, w, nc) if o in _TRANSPOSING else (w, h, nc) for (w, h, nc), o in zip(prep.shapes, orient)]
-            return list(prep.shapes)
-        return [(w[2], w[3], nc) for w, (_, _, nc) in zip(wins, prep.shapes)]
+                return [(h, w, nc) if o in _TRANSPOSING else (w, h, nc) for (w, h, nc), o in zip(shapes, orient)]
+            return list(shapes)
+        return [(w[2], w[3], nc) for w, (_, _, nc) in zip(wins, shapes)]
 
     def _views(self, flat, shapes: Sequence[Tuple[int, int, int]], per_pixel: int = 1) -> list:
         """Per-image views of a flat buffer (NumPy array or torch tensor) that holds images of ``shapes`` back to back."""
@@ -811,15 +834,16 @@ class BatchDecoder:
             off += n
         return out
 
-    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None, orient=None) -> List[np.ndarray]:
-        return self._views(flat, self._out_shapes(prep, wins, orient), per_pixel)
+    def split_outputs(self, prep: PreparedBatch, flat: np.ndarray, per_pixel: int = 1, wins=None, orient=None, ncomp=None) -> List[np.ndarray]:
+        return self._views(flat, self._out_shapes(prep, wins, orient, ncomp), per_pixel)
 
     def _plan(self, req: _Request, prep: PreparedBatch, blob_device_ptr: int = 0) -> B.Plan:
         """The plan of a request whose files are ``prep``'s, in order."""
-        return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs())
+        native = prep.shapes[0][2] if prep.shapes else None
+        return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
-               orientation=None, resample=None):
+               orientation=None, resample=None, mode=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -832,7 +856,15 @@ class BatchDecoder:
         Shapes, ``rois`` and ``size`` then all refer to the turned image; ``mirror`` comes after it.
         ``resample``, with ``size``: the filter of the resize — None or "bilinear" (the default), "box", "hamming", "bicubic" or
         "lanczos", Pillow's ``Image.Resampling`` member or its integer value (:func:`normalize_resample`); one filter for the whole
-        call.  Every image is then Pillow's ``resize(size, <that filter>)`` byte for byte, and everything else composes as ever."""
+        call.  Every image is then Pillow's ``resize(size, <that filter>)`` byte for byte, and everything else composes as ever.
+        ``mode``: None (every file in its own components), "RGB" or "L" — Pillow's mode names (:func:`normalize_mode`): every output
+        has three components, a greyscale file's value in all of them, or one, a colour file's ``convert("L")``.  The conversion
+        comes first: the result is ``exif_transpose(img.convert(mode)).resize(size, filter)``, then the output table, then the
+        mirror.  With ``size`` a list may then mix greyscale and colour files, and ``normalize`` is checked against the mode's
+        count; files that already have it decode exactly as without the argument."""
+        mode = normalize_mode(mode)
+        if mode is not None and return_seams:
+            raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
         if orientation is not None and return_seams:
             raise ValueError("orientation and return_seams do not go together: the seam outputs are in stored order")
         if rois is not None and return_seams:
@@ -846,11 +878,11 @@ class BatchDecoder:
         parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
         orient = normalize_orientation(orientation, files)
         req = _Request(files, normalize_rois(rois, _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)), size,
-                       orient=orient, resample=resample)
+                       orient=orient, resample=resample, mode=mode)
         turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
-            nc = one_component_count([len(p.color_components) for p in parsed.values()])
+            nc = req.ncomp or one_component_count([len(p.color_components) for p in parsed.values()])
             req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc, host=True)
             dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         results: List[Optional[np.ndarray]] = [None] * len(files)
@@ -874,7 +906,7 @@ class BatchDecoder:
                 if dense is not None:
                     imgs = out["rgb"].view(dense.dtype).reshape((len(idxs),) + dense.shape[1:])
                 else:
-                    imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins, orient=sub.orient)
+                    imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins, orient=sub.orient, ncomp=sub.ncomp)
                 for k, i in enumerate(idxs):
                     if i in tail or i in unconverged:
                         continue
@@ -903,15 +935,16 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None) -> _Request:
+    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order."""
-        req = _Request(files, None, size, orient=normalize_orientation(orientation, files), resample=normalize_resample(resample, size))
+        req = _Request(files, None, size, orient=normalize_orientation(orientation, files), resample=normalize_resample(resample, size),
+                       mode=normalize_mode(mode))
         if size is not None:
             import torch
             info = [_image_info(f) for f in files]
-            nc = one_component_count([t[2] for t in info])
+            nc = req.ncomp or one_component_count([t[2] for t in info])
             req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
             req.wins = normalize_rois(rois, _oriented_dims([t[:2] for t in info], req.orient))
             req.dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
@@ -931,7 +964,7 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, orientation=None, resample=None):
+                      mirror=None, orientation=None, resample=None, mode=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -955,11 +988,15 @@ class BatchDecoder:
         one more launch per plan — or, with ``size``, by the resize launch itself, whose result is Pillow's resize of the
         turned image.
         ``resample`` as in :meth:`decode`: the filter of the resize, one for the whole call — every plan of it (second rounds,
-        files of several kinds, parts) resamples with it."""
+        files of several kinds, parts) resamples with it.
+        ``mode`` as in :meth:`decode`: None, "RGB" or "L".  Greyscale and colour files are plans of their own as ever; the plans of
+        the files that do not have the mode's components convert inside the launch they end in anyway — the resize launch, or the
+        one extra launch of an own-size plan — and with ``size`` all of them fill their slots of the one tensor."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample)
+        normalize_mode(mode)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
@@ -1058,7 +1095,7 @@ class BatchDecoder:
                         work.append(_Work(unconverged, flags=B.MJ_FLAG_NO_SYNC))
                     if req.dest is not None:                     # (the plan wrote its slots of the one tensor)
                         continue
-                    views = self._views(flight.d_rgb, self._out_shapes(flight.prep, flight.req.wins, flight.req.orient))
+                    views = self._views(flight.d_rgb, self._out_shapes(flight.prep, flight.req.wins, flight.req.orient, flight.req.ncomp))
                     for k, i in enumerate(flight.idxs):
                         if i not in tail and i not in unconverged:
                             results[i] = views[k]
@@ -1067,7 +1104,8 @@ class BatchDecoder:
                     flight.plan.close()
         return results if req.dest is None else req.dest
 
-    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None):
+    def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
+                           mode=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1084,9 +1122,10 @@ class BatchDecoder:
         ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file).  ``orientation``: None, "exif" or
         an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes.
-        ``resample`` as in :meth:`decode_device`, for every batch."""
+        ``resample`` and ``mode`` as in :meth:`decode_device`, for every batch."""
         size = normalize_size(size)
         normalize_resample(resample, size)                                            # (what needs no file: before any work)
+        normalize_mode(mode)
         turns_per_batch = not (orientation is None or isinstance(orientation, (str, int, np.integer)))
         if not turns_per_batch:
             normalize_orientation(orientation, [])                                    # (what needs no file: before any work)
@@ -1112,7 +1151,7 @@ class BatchDecoder:
                         o = next(turns)
                     except StopIteration:
                         raise ValueError("orientation yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m, o, resample)
+                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):
@@ -1132,7 +1171,7 @@ class BatchDecoder:
             try:
                 flight.plan.sync()
                 tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], np.arange(len(req.files)), index=req.index)
-                out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins, req.orient))
+                out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins, req.orient, req.ncomp))
             finally:
                 flight.plan.close()
             again = sorted(tail + unconverged)

@@ -129,7 +129,7 @@ int mj_plan_get_info(const mj_plan *p, mj_plan_info *info) {
 int mj_plan_image_offsets(const mj_plan *p, int32_t image, int64_t *block_off, int64_t *rgb_off) {
     if (!p || image < 0 || image >= p->n_images) return MJ_ERR_INVALID;
     if (block_off) *block_off = p->h_images[image].block_off;
-    if (rgb_off) *rgb_off = p->h_images[image].rgb_off;
+    if (rgb_off) *rgb_off = p->h_out_off.empty() ? p->h_images[image].rgb_off : p->h_out_off[(size_t)image];
     return MJ_OK;
 }
 
@@ -318,12 +318,12 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
     if (p->orient_only) {       // an oriented plan at the files' own sizes: the orient launch in the resize's place
         mj::OrientArgs o = p->oa;
         o.dst = p->last_rgb;
-        MJ_HIP(p->ctx, mj::launch_orient(s, o, p->ncomp));
+        MJ_HIP(p->ctx, mj::launch_orient(s, o, p->ncomp, p->out_ncomp));
         return MJ_OK;
     }
     mj::ResizeArgs a = p->rz;
     a.dst = p->last_rgb;
-    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp));
+    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp, p->out_ncomp));
     return MJ_OK;
 }
 

@@ -413,13 +413,20 @@ bool resize_filter_known(int filter);
 bool resize_filter_signed(int filter);
 int resize_axis_ksize(int in_size, int out_size, int filter = 0);
 void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0);
-hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp);
+// (out_ncomp: 0 or ncomp — the instances there were; else a plan that converts, mj_plan_create_resized_mode)
+hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp = 0);
+// ---- output colour mode (tools/mode_model.py)
+// Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
+__host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }
+// a batch's component count is its first image's (1, else 3; 3 when there is no image to ask)
+inline int batch_ncomp(const mj_batch *b) { return b && b->n_images > 0 && b->images && b->images[0].ncomp == 1 ? 1 : 3; }
 // ---- orient.hip: EXIF orientation at the files' own sizes
 // One image of an oriented plan: its stored-order pixels in the plan's intermediate buffer as rows x len pixels (len along
 // the contiguous axis: row-major plans height x width, x-major plans width x height) and what becomes of them — op bit 0:
 // the destination's rows run backwards, bit 1: its contiguous axis runs backwards, bit 2: rows and columns change places.
 struct DevOrientImage {
-    int64_t src_off, dst_off;     // bytes; an image keeps its place in the packing (orientation keeps the pixel count)
+    int64_t src_off, dst_off;     // bytes; an image keeps its place in the packing (orientation keeps the pixel count; a plan that
+                                  // converts, mj_plan_create_mode, packs the same pixels with the output's components)
     int32_t rows, len;
     int32_t tiles_l;              // tiles along the contiguous axis
     int32_t op;
@@ -432,7 +439,7 @@ struct OrientArgs {
     int64_t total_tiles;
     int32_t n_images, planar;     // planar: the destination holds the components one plane after the other
 };
-hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp);
+hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp, int out_ncomp = 0);      // (out_ncomp as launch_resize's)
 // bits[v] = the bit pattern (in the low esize bytes) of resized byte v as an MJ_DTYPE_F16 / BF16 / F32 element:
 // fl32(fl32(fl32(v) / 255 - mean) / std), then rounded to nearest even into the 16-bit types (tools/normalize_model.py)
 void build_normalize_table(int dtype, float mean, float std, uint32_t *bits);

@@ -13,6 +13,11 @@
 // The LDS row pitch is 64 * C + 4 bytes = 49 dwords (colour) or 17 (grey): odd, so that the lanes of a column read — one
 // row apart each — fall into different banks instead of all into one.  Planar plans read the same interleaved source and
 // store one plane after the other.
+//
+// Output colour mode (mj_plan_create_mode): k_orient<CS, CO> with CS != CO is the same launch converting on its way — the tile
+// lies in LDS in the source's components, the store loop runs over the output's: a grey byte goes into all three components,
+// a colour pixel becomes its L (mode_luma).  Such a plan has the launch for upright images too (op 0: a copy that converts), and
+// an image's place in the output is no longer its place in the source (dst_off: the same pixels, CO components each).
 #include "plan.h"
 
 namespace mj {
@@ -22,7 +27,7 @@ namespace {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 
-template <int C>
+template <int C, int CO = C>
 __global__ __launch_bounds__(256) void k_orient(const OrientArgs a) {
     constexpr int P = kTile * C + 4;
     __shared__ __attribute__((aligned(16))) unsigned char T[kTile * P];
@@ -56,68 +61,81 @@ __global__ __launch_bounds__(256) void k_orient(const OrientArgs a) {
     const int sr0 = swap ? l0 : r0, sl0 = swap ? r0 : l0;
     const int dr0 = back_r ? drows - (sr0 + ndr) : sr0, dl0 = back_l ? dlen - (sl0 + ndl) : sl0;
     unsigned char *dst = a.dst + im.dst_off;
-    const bool planar = a.planar != 0 && C > 1;
-    const int total = ndr * ndl * C;
+    const bool planar = a.planar != 0 && CO > 1;
+    const int total = ndr * ndl * CO;
     for (int i = tid; i < total; i += 256) {
         int dr, dl, c;
         if (planar) { c = i / (ndr * ndl); const int rem = i - c * (ndr * ndl); dr = rem / ndl; dl = rem - dr * ndl; }
-        else { dr = i / (ndl * C); const int e = i - dr * (ndl * C); dl = e / C; c = e - dl * C; }
+        else { dr = i / (ndl * CO); const int e = i - dr * (ndl * CO); dl = e / CO; c = e - dl * CO; }
         const int ar = back_r ? ndr - 1 - dr : dr, al = back_l ? ndl - 1 - dl : dl;
-        const unsigned char v = T[(swap ? al : ar) * P + (swap ? ar : al) * C + c];
+        const unsigned char *s = T + (swap ? al : ar) * P + (swap ? ar : al) * C;
+        unsigned char v;
+        if constexpr (C == CO) v = s[c];
+        else if constexpr (C == 1) v = s[0];                                    // grey into every component
+        else v = (unsigned char)mode_luma(s[0], s[1], s[2]);                    // colour to L
         const int64_t pix = (int64_t)(dr0 + dr) * dlen + dl0 + dl;
         if (planar) dst[(int64_t)c * drows * dlen + pix] = v;
-        else dst[pix * C + c] = v;
+        else dst[pix * CO + c] = v;
     }
 }
 
 }  // namespace
 
-hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp) {
+hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp, int out_ncomp) {
     if (a.n_images <= 0 || a.total_tiles <= 0) return hipSuccess;
     const int64_t gx = std::min<int64_t>(a.total_tiles, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((a.total_tiles + gx - 1) / gx)), block(256);
-    if (ncomp == 3) hipLaunchKernelGGL(k_orient<3>, grid, block, 0, stream, a);
+    if (out_ncomp && out_ncomp != ncomp) {
+        if (ncomp == 3) hipLaunchKernelGGL((k_orient<3, 1>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((k_orient<1, 3>), grid, block, 0, stream, a);
+    } else if (ncomp == 3) hipLaunchKernelGGL(k_orient<3>, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(k_orient<1>, grid, block, 0, stream, a);
     return hipGetLastError();
 }
 
 }  // namespace mj
 
-extern "C" int mj_plan_create_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, mj_plan **out) {
+namespace {
+
+// mode: 0, or the output's component count where it is not the batch's (such a plan has the launch for upright images too)
+int create_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, int mode, mj_plan **out) {
     if (!ctx) return MJ_ERR_INVALID;
-    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: NULL argument");
+    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
     bool upright = true;
     for (int i = 0; orientations && i < b->n_images; ++i) {
         if (orientations[i] < 1 || orientations[i] > 8)
-            return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: image %d: orientation %d (must be 1..8)", i, (int)orientations[i]);
+            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
         upright = upright && orientations[i] == 1;
     }
-    if (upright) return rois ? mj_plan_create_roi(ctx, b, rois, out) : mj_plan_create(ctx, b, out);
+    if (upright && !mode) return rois ? mj_plan_create_roi(ctx, b, rois, out) : mj_plan_create(ctx, b, out);
+    if (upright) orientations = nullptr;
     if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
-        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none");
-    if (!b->images) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: NULL argument");
+        return fail(ctx, MJ_ERR_INVALID, "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
+    if (!b->images) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     std::vector<mj_roi> stored;
     if (rois) {
         stored.resize((size_t)b->n_images);
         for (int i = 0; i < b->n_images; ++i)
-            if (!mj::stored_window(orientations[i], b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
-                return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_oriented: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image",
-                            i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+            if (!mj::stored_window(orientations ? orientations[i] : 1, b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
+                return fail(ctx, MJ_ERR_INVALID, "%s: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image",
+                            fn, i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
     }
     mj_plan *p = nullptr;
     if (int rc = mj::plan_create_common(ctx, b, rois ? stored.data() : nullptr, rois != nullptr, &p)) return rc;
     struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
-    const int n = p->n_images;
+    const int n = p->n_images, C = p->ncomp, CO = mode ? mode : C;
     const bool xmajor = (p->layout & 1) == 0;
     std::vector<mj::DevOrientImage> oi((size_t)n);
     std::vector<int64_t> prefix((size_t)n + 1, 0);
     for (int i = 0; i < n; ++i) {
         const int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
-        const int bits = mj::orient_bits(orientations[i]);
+        const int bits = orientations ? mj::orient_bits(orientations[i]) : 0;
         const int fx = bits & 1, fy = (bits >> 1) & 1;
         mj::DevOrientImage &o = oi[(size_t)i];
-        o.src_off = o.dst_off = p->h_images[i].rgb_off;
+        o.src_off = p->h_images[i].rgb_off;
+        o.dst_off = o.src_off / C * CO;       // (the packing counts pixels: the same ones, CO components each)
+        if (mode) p->h_out_off.push_back(o.dst_off);
         o.rows = xmajor ? w : h; o.len = xmajor ? h : w;
         o.tiles_l = (o.len + mj::kTile - 1) / mj::kTile;
         // rows of a row-major array are the image's rows, rows of an x-major array its columns
@@ -125,7 +143,7 @@ extern "C" int mj_plan_create_oriented(mj_context *ctx, const mj_batch *b, const
         prefix[(size_t)i + 1] = prefix[(size_t)i] + (int64_t)o.tiles_l * ((o.rows + mj::kTile - 1) / mj::kTile);
     }
     if (prefix[(size_t)n] > mj::kResizeGridX * (int64_t)65535)
-        return fail(ctx, MJ_ERR_UNSUPPORTED, "mj_plan_create_oriented: %lld tiles are more than one launch takes; split the batch", (long long)prefix[(size_t)n]);
+        return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: %lld tiles are more than one launch takes; split the batch", fn, (long long)prefix[(size_t)n]);
     int rc;
     if ((rc = upload(ctx, &p->d_or_images, oi.data(), oi.size())) != MJ_OK) return rc;
     if ((rc = upload(ctx, &p->d_or_prefix, prefix.data(), prefix.size())) != MJ_OK) return rc;
@@ -137,9 +155,39 @@ extern "C" int mj_plan_create_oriented(mj_context *ctx, const mj_batch *b, const
     a = mj::OrientArgs{};
     a.src = p->d_src; a.images = p->d_or_images; a.tile_prefix = p->d_or_prefix; a.total_tiles = prefix[(size_t)n];
     a.n_images = n; a.planar = p->layout >= MJ_LAYOUT_PLANAR_XMAJOR ? 1 : 0;
+    if (mode) {       // (the output: the same pixels in the mode's components)
+        p->out_ncomp = CO;
+        p->info.rgb_bytes = p->src_bytes / C * CO;
+    }
     p->resized = true;
     p->orient_only = true;
     guard.p = nullptr;
     *out = p;
     return MJ_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int mj_plan_create_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, mj_plan **out) {
+    return create_oriented("mj_plan_create_oriented", ctx, b, rois, orientations, 0, out);
+}
+
+int mj_plan_create_mode(mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, int32_t mode, mj_plan **out) {
+    const char *fn = "mj_plan_create_mode";
+    if (mode != MJ_MODE_NATIVE && mode != MJ_MODE_L && mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, mode);
+    // (the files' own count: the plan of mj_plan_create_oriented, made by the code that makes it there)
+    return create_oriented(fn, ctx, b, rois, orientations, mode == mj::batch_ncomp(b) ? MJ_MODE_NATIVE : mode, out);
+}
+
+int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out) {
+    if ((mode != MJ_MODE_NATIVE && mode != MJ_MODE_L && mode != MJ_MODE_RGB) || (src_ncomp != 1 && src_ncomp != 3) || n_pixels < 0 || (n_pixels && (!src || !out)))
+        return MJ_ERR_INVALID;
+    if (mode == MJ_MODE_NATIVE || mode == src_ncomp) memcpy(out, src, (size_t)(n_pixels * src_ncomp));
+    else if (mode == MJ_MODE_L) for (int64_t i = 0; i < n_pixels; ++i) out[i] = (uint8_t)mj::mode_luma(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
+    else for (int64_t i = 0; i < n_pixels; ++i) out[3 * i] = out[3 * i + 1] = out[3 * i + 2] = src[i];
+    return MJ_OK;
+}
+
+}  // extern "C"

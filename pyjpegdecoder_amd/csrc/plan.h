@@ -274,6 +274,10 @@ struct mj_plan {
     mj::DevOrientImage *d_or_images = nullptr;
     int64_t *d_or_prefix = nullptr;
     mj::OrientArgs oa{};
+    // plans that convert (mj_plan_create_mode / mj_plan_create_resized_mode): the components of the output where they are not the
+    // files' (0: they are) — the orient / resize launch converts —, and every image's byte offset in the output
+    int out_ncomp = 0;
+    std::vector<int64_t> h_out_off;
 };
 
 // ---- plan_tables.hip: table building (host)

@@ -28,6 +28,14 @@
 // per-image flag (ResizeArgs::mirror) of the mirror instances: the element goes to column out_width - 1 - x.  A lane still stores one element
 // and consecutive lanes consecutive elements of the output's contiguous axis, so a wavefront's store is one run of 64, 128
 // or 256 bytes (descending for a mirrored image of a row-major layout); the plain uint8 instances are the code they were.
+//
+// Output colour mode (mj_plan_create_resized_mode): the k_resize_*_mode instances, whose source has CS components and whose
+// output CO — greyscale files into three components (Pillow's convert("RGB")) and colour files into one (convert("L"),
+// mode_luma of the decoded RGB bytes).  The conversion comes first, as in img.convert(mode).resize(size): colour to L where the
+// source is read, before any tap (the staged row in LDS; 16 pixels = 48 bytes per lane and tap in registers), so both passes and
+// T run on ONE component either way.  Grey to RGB finishes every pixel's sum once into a tile of bytes in LDS and the store
+// loop — one element per lane, consecutive lanes consecutive elements, as above — looks up lut[c][byte] for c = 0..2.  They
+// are instances in the oriented style only (the per-image byte holds the flips and the mirror flag; all zero for a plain plan).
 #include <math.h>
 
 #include <map>
@@ -326,6 +334,190 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
     }
 }
 
+// ---- output colour mode: source components CS != output components CO (T, both passes and the tile geometry: one component)
+// The end of the height pass.  CO == 1: the finished byte is the element.  CO == 3: every pixel's byte goes into the tile O in LDS
+// once; after the barrier a lane stores one element (pixel, c), looked up in component c's table.
+// XM: T is [column][t_pitch] and a tile is walked along its columns (the x-major kernel), else [row][t_pitch] along its rows.
+template <int CO, typename OutT, bool SGN, bool XM>
+__device__ __forceinline__ void mode_height_pass(const ResizeArgs &a, const DevResizeImage &im, int img, const unsigned char *T, unsigned char *O,
+                                                 const OutT *lut, const int32_t *lo, const int32_t *cnt, const int32_t *k_all, int ks, int ya, int ox0,
+                                                 int oy0, int ncols, int orows, int tid) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
+    const unsigned turn = a.mirror[img];      // bit 0 = store at column ow - 1 - x, bit 1 = at row oh - 1 - y
+    const int npix = orows * ncols;
+    for (int i = tid; i < npix; i += 256) {
+        int oyl, oxl;
+        if (XM) { oxl = i / orows; oyl = i - oxl * orows; } else { oyl = i / ncols; oxl = i - oyl * ncols; }
+        // (lo / cnt / k_all: the height axis — the tile's copy in LDS, relative to ya (x-major), or the image's table (row-major))
+        const int n = XM ? cnt[oyl] : cnt[oy0 + oyl];
+        const int32_t *k = XM ? k_all + oyl * ks : k_all + (int64_t)(oy0 + oyl) * ks;
+        const unsigned char *s = XM ? T + oxl * a.t_pitch + lo[oyl] : T + (lo[oy0 + oyl] - ya) * a.t_pitch + oxl;
+        const int step = XM ? 1 : a.t_pitch;
+        acc_t acc = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * step]);
+        const unsigned v = Tap<SGN>::clip(acc);
+        if constexpr (CO == 1) {
+            const int ox = ox0 + oxl, oy = oy0 + oyl;
+            dst[out_index(a, 1, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, 0)] = out_value<OutT>(lut, 0, v);
+        } else O[i] = (unsigned char)v;
+    }
+    if constexpr (CO > 1) {
+        __syncthreads();
+        const bool planar = a.layout >= 2;
+        const int fast = XM ? orows : ncols;      // pixels along the direction the tile is walked in
+        for (int i = tid; i < npix * CO; i += 256) {
+            int pix, c;
+            if (planar) { c = i / npix; pix = i - c * npix; } else { pix = i / CO; c = i - pix * CO; }
+            const int slow = pix / fast, f = pix - slow * fast;
+            const int ox = ox0 + (XM ? slow : f), oy = oy0 + (XM ? f : slow);
+            dst[out_index(a, CO, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, (unsigned)O[pix]);
+        }
+    }
+}
+
+// where the tile O lies: behind the output table
+template <int CO, typename OutT>
+__device__ __forceinline__ unsigned char *mode_tile(const ResizeArgs &a, unsigned char *smem) {
+    return smem + a.lut_off + (sizeof(OutT) > 1 ? 256 * CO * (int)sizeof(OutT) : 0);
+}
+
+// Row-major source.  LDS as k_resize_rowmajor's with T in one component; a colour source's staging row is 3/4 of stage_bytes and
+// the row's L bytes — converted there by the wavefront that staged it — take the last quarter.
+template <int CS, int CO, typename OutT, bool SGN>
+__global__ __launch_bounds__(256) void k_resize_rowmajor_mode(const ResizeArgs a) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int xa = X.lo[ox0], xb = X.lo[ox1 - 1] + X.cnt[ox1 - 1];
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, npx = xb - xa;
+    unsigned char *T = smem;
+    int32_t *lx_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *lx_cnt = lx_lo + a.tc, *lx_k = lx_cnt + a.tc;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    unsigned char *stage = smem + a.stage_off + wave * a.stage_bytes;
+    for (int i = tid; i < ncols; i += 256) { lx_lo[i] = X.lo[ox0 + i] - xa; lx_cnt[i] = X.cnt[ox0 + i]; }
+    for (int i = tid; i < ncols * X.ks; i += 256) lx_k[i] = X.k[(int64_t)ox0 * X.ks + i];
+    const OutT *lut = stage_lut<CO, OutT>(a, smem, tid);
+    __syncthreads();
+    const unsigned char *src = a.src + im.src_off;
+    const int seg = npx * CS;
+    for (int r = wave; r < nrows; r += 4) {
+        const unsigned char *row = src + ((int64_t)(ya + r) * im.w + xa) * CS;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15);
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(row - mis);
+        const int n16 = (mis + seg + 15) >> 4;
+        for (int j = lane; j < n16; j += 64) reinterpret_cast<u32x4 *>(stage)[j] = p[j];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const unsigned char *g = stage + mis;
+        if constexpr (CS == 3) {
+            // the staged row to L, pixel by pixel, before any tap sees it
+            unsigned char *grey = stage + 3 * (a.stage_bytes >> 2);
+            for (int x = lane; x < npx; x += 64) {
+                const unsigned char *s = stage + mis + 3 * x;
+                grey[x] = (unsigned char)mode_luma(s[0], s[1], s[2]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            g = grey;
+        }
+        for (int e = lane; e < ncols; e += 64) {
+            const unsigned char *s = g + lx_lo[e];
+            const int32_t *k = lx_k + e * X.ks;
+            const int n = lx_cnt[e];
+            acc_t acc = (acc_t)1 << 21;
+            for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q]);
+            T[r * a.t_pitch + e] = (unsigned char)Tap<SGN>::clip(acc);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    mode_height_pass<CO, OutT, SGN, false>(a, im, img, T, mode_tile<CO, OutT>(a, smem), lut, Y.lo, Y.cnt, Y.k, Y.ks, ya, ox0, oy0, ncols, oy1 - oy0, tid);
+}
+
+// X-major source.  LDS as k_resize_xmajor's with T in one component.  A colour source: a lane takes 16 PIXELS of a column — 48
+// consecutive bytes, three 16-byte loads — per tap, converts them in registers and accumulates their L.  (The last chunk of a
+// column reads up to 47 bytes behind the rows the tile needs: the next column's, or the buffer's 64 bytes of slack.)
+template <int CS, int CO, typename OutT, bool SGN>
+__global__ __launch_bounds__(256) void k_resize_xmajor_mode(const ResizeArgs a) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, orows = oy1 - oy0;
+    unsigned char *T = smem;
+    int32_t *ly_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *ly_cnt = ly_lo + a.tr, *ly_k = ly_cnt + a.tr;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < orows; i += 256) { ly_lo[i] = Y.lo[oy0 + i] - ya; ly_cnt[i] = Y.cnt[oy0 + i]; }
+    for (int i = tid; i < orows * Y.ks; i += 256) ly_k[i] = Y.k[(int64_t)oy0 * Y.ks + i];
+    const OutT *lut = stage_lut<CO, OutT>(a, smem, tid);
+    const unsigned char *src = a.src + im.src_off;
+    const int nch = (nrows + 15) >> 4;                 // 16 pixels of a column per lane
+    const int64_t col = (int64_t)im.h * CS;
+    for (int i = tid; i < ncols * nch; i += 256) {
+        const int oxl = i / nch, j = i - oxl * nch;
+        const int ox = ox0 + oxl, n = X.cnt[ox];
+        const int32_t *k = X.k + (int64_t)ox * X.ks;
+        const unsigned char *p = src + ((int64_t)X.lo[ox] * im.h + ya + 16 * j) * CS;
+        acc_t acc[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) acc[b] = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q, p += col) {
+            const int32_t kq = k[q];
+            if constexpr (CS == 3) {
+                unsigned w[12];
+                __builtin_memcpy(w, p, 48);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    const unsigned r = (w[(3 * b) >> 2] >> (8 * ((3 * b) & 3))) & 255u, g = (w[(3 * b + 1) >> 2] >> (8 * ((3 * b + 1) & 3))) & 255u,
+                                   bl = (w[(3 * b + 2) >> 2] >> (8 * ((3 * b + 2) & 3))) & 255u;
+                    acc[b] += Tap<SGN>::mul(kq, mode_luma(r, g, bl));
+                }
+            } else {
+                u32x4 v;
+                __builtin_memcpy(&v, p, 16);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) acc[b] += Tap<SGN>::mul(kq, (v[b >> 2] >> (8 * (b & 3))) & 255u);
+            }
+        }
+        u32x4 o;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            o[d] = Tap<SGN>::clip(acc[4 * d]) | Tap<SGN>::clip(acc[4 * d + 1]) << 8 | Tap<SGN>::clip(acc[4 * d + 2]) << 16 | Tap<SGN>::clip(acc[4 * d + 3]) << 24;
+        *reinterpret_cast<u32x4 *>(T + oxl * a.t_pitch + 16 * j) = o;
+    }
+    __syncthreads();
+    mode_height_pass<CO, OutT, SGN, true>(a, im, img, T, mode_tile<CO, OutT>(a, smem), lut, ly_lo, ly_cnt, ly_k, Y.ks, ya, ox0, oy0, ncols, orows, tid);
+}
+
+template <int CS, int CO, typename OutT>
+void launch_mode_instance(hipStream_t stream, const ResizeArgs &a, dim3 grid, dim3 block) {
+    const bool xmajor = ((a.layout & 1) == 0) != (a.orient == 2);      // (as launch_instance: transposing orientations read the other way)
+    if (xmajor && a.sgn) hipLaunchKernelGGL((k_resize_xmajor_mode<CS, CO, OutT, true>), grid, block, a.lds_bytes, stream, a);
+    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor_mode<CS, CO, OutT, false>), grid, block, a.lds_bytes, stream, a);
+    else if (a.sgn) hipLaunchKernelGGL((k_resize_rowmajor_mode<CS, CO, OutT, true>), grid, block, a.lds_bytes, stream, a);
+    else hipLaunchKernelGGL((k_resize_rowmajor_mode<CS, CO, OutT, false>), grid, block, a.lds_bytes, stream, a);
+}
+
 // the instance of one output element and mirror mode: source order and component count picked at run time
 template <typename OutT, bool MIRROR, bool ORIENT = false, bool SGN = false>
 void launch_instance(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block) {
@@ -347,11 +539,23 @@ void launch_signed(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid
 
 }  // namespace
 
-hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp) {
+hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp) {
     if (a.n_images <= 0) return hipSuccess;
     // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
     const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
+    if (out_ncomp && out_ncomp != ncomp) {       // a plan that converts (mj_plan_create_resized_mode): grey to RGB, or colour to L
+        if (ncomp == 1) {
+            if (a.esize == 4) launch_mode_instance<1, 3, uint32_t>(stream, a, grid, block);
+            else if (a.esize == 2) launch_mode_instance<1, 3, uint16_t>(stream, a, grid, block);
+            else launch_mode_instance<1, 3, unsigned char>(stream, a, grid, block);
+        } else {
+            if (a.esize == 4) launch_mode_instance<3, 1, uint32_t>(stream, a, grid, block);
+            else if (a.esize == 2) launch_mode_instance<3, 1, uint16_t>(stream, a, grid, block);
+            else launch_mode_instance<3, 1, unsigned char>(stream, a, grid, block);
+        }
+        return hipGetLastError();
+    }
     if (a.sgn) {        // bicubic and Lanczos plans: the signed instances
         if (a.esize == 4) launch_signed<uint32_t>(stream, a, ncomp, grid, block);
         else if (a.esize == 2) launch_signed<uint16_t>(stream, a, ncomp, grid, block);
@@ -451,19 +655,19 @@ const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean
 }
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out);
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out, int mode = 0);
 
 // ... of the oriented images: the orientations checked (NULL, or all of them 1: a plan without them)
 int create_resized_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                             const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int filter,
-                            mj_plan **out) {
+                            mj_plan **out, int mode = 0) {
     bool upright = true;
     for (int i = 0; orientations && b && i < b->n_images; ++i) {
         if (orientations[i] < 1 || orientations[i] > 8)
             return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
         upright = upright && orientations[i] == 1;
     }
-    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, filter, out);
+    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, filter, out, mode);
 }
 
 }  // namespace
@@ -522,6 +726,17 @@ int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *b, const mj
     return create_resized_oriented(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, orientations, filter, out);
 }
 
+int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                int32_t filter, int32_t mode, mj_plan **out) {
+    const char *fn = "mj_plan_create_resized_mode";
+    if (!mj::resize_filter_known(filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, filter);
+    if (mode != MJ_MODE_NATIVE && mode != MJ_MODE_L && mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, mode);
+    // (the files' own count: the plan of mj_plan_create_resized_filtered, made by the code that makes it there)
+    if (mode == mj::batch_ncomp(b)) mode = MJ_MODE_NATIVE;
+    return create_resized_oriented(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, orientations, filter, out, mode);
+}
+
 int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
     if (!p || !out || !p->resized || p->orient_only) return MJ_ERR_INVALID;
     const mj::ResizeArgs &a = p->rz;
@@ -535,12 +750,13 @@ int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
 namespace {
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out) {
-    // (filter: a known MJ_FILTER_*; orient: NULL, or one checked orientation 1..8 per image, not all of them 1)
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out, int mode) {
+    // (filter: a known MJ_FILTER_*; orient: NULL, or one checked orientation 1..8 per image, not all of them 1; mode: 0, or the
+    // output's component count where it is not the batch's)
     // the output description first: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
     // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
     const int dtype = output ? output->dtype : MJ_DTYPE_U8;
-    const int nc_check = b && b->n_images > 0 && b->images ? (b->images[0].ncomp == 1 ? 1 : 3) : 3;
+    const int nc_check = mode ? mode : mj::batch_ncomp(b);
     if (output)
         if (const char *why = output_fault(dtype, output->normalize != 0, nc_check, output->mean, output->std))
             return fail(ctx, MJ_ERR_INVALID, "%s: output: %s", fn, why);
@@ -579,8 +795,11 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
     if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
     struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
-    const int C = p->ncomp, n = p->n_images;
-    const int64_t out_image = (int64_t)out_width * out_height * C * esize;      // bytes
+    // C: the source's components.  A plan that converts stores CO of them per pixel and runs both passes, and T, on CT = 1:
+    // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
+    const int C = p->ncomp, n = p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
+    if (mode) p->out_ncomp = CO;
+    const int64_t out_image = (int64_t)out_width * out_height * CO * esize;      // bytes
     // tap tables: one per distinct source size and axis
     std::map<int, AxisHost> xs, ys;
     std::vector<int32_t> words;
@@ -634,6 +853,7 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         if (bits & 4) std::swap(w, h);      // (from here on the oriented image's size)
         ri[i].src_off = p->h_images[i].rgb_off;
         ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
+        if (mode) p->h_out_off.push_back(ri[i].dst_off);
         ri[i].w = w; ri[i].h = h;
         if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
         if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
@@ -646,7 +866,7 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     }
     // (a pure function of the tile: what it takes in LDS and where the parts lie; nothing is kept until a tile is chosen)
     struct Lds { bool ok; int t_pitch, tab_off, stage_off, stage_bytes, lut_off, total; };
-    const int lut_bytes = esize > 1 ? 256 * C * esize : 0;
+    const int lut_bytes = esize > 1 ? 256 * CO * esize : 0;
     // The tile: what a workgroup's LDS holds (resize.hip's kernels) must fit 64 KB — the intermediate rows of the tile, the
     // tile's tap tables, the staging rows, the output table of a 2- or 4-byte element — for every source size of the batch.  Tiles shrink until it does: a row-major plan
     // gives up columns first while a row segment stays 2 KB long (its loads run along the rows), then rows; an x-major plan
@@ -663,16 +883,18 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         for (auto &kv : xs) { sx = std::max(sx, kv.second.span(tc_)); ksx = std::max(ksx, kv.second.ks); }
         int64_t t_bytes, tab_bytes, stage = 0;
         if (xmajor) {
-            pitch = round16((int64_t)sy * C);
+            pitch = round16((int64_t)sy * CT);
             t_bytes = (int64_t)tc_ * pitch;
             tab_bytes = ((int64_t)2 * tr_ + (int64_t)tr_ * ksy) * 4;
         } else {
-            pitch = round16((int64_t)tc_ * C);
+            pitch = round16((int64_t)tc_ * CT);
             t_bytes = (int64_t)sy * pitch;
             tab_bytes = ((int64_t)2 * tc_ + (int64_t)tc_ * ksx) * 4;
-            stage = round16((int64_t)sx * C + 32);
+            // (colour to L: three quarters for the staged colour row — 3 * (sx + 16) >= 3 * sx + 32 —, one for its L bytes)
+            stage = mode && C == 3 ? 4 * (int64_t)round16((int64_t)sx + 16) : round16((int64_t)sx * C + 32);
         }
-        const int64_t lut_off = t_bytes + round16(tab_bytes) + 4 * stage, total = lut_off + lut_bytes;
+        // (grey to RGB: the tile of finished bytes behind the output table)
+        const int64_t lut_off = t_bytes + round16(tab_bytes) + 4 * stage, total = lut_off + lut_bytes + (mode && C == 1 ? (int64_t)tr_ * tc_ : 0);
         if (total > budget) return Lds{false, 0, 0, 0, 0, 0, 0};
         return Lds{true, pitch, (int)t_bytes, (int)(t_bytes + round16(tab_bytes)), (int)stage, (int)lut_off, (int)total};
     };
@@ -704,7 +926,7 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     p->rz_filter = filter;
     for (auto &kv : xs) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
     for (auto &kv : ys) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
-    if (any_mirror || orient) {       // (no flag set: the instances without mirror)
+    if (any_mirror || orient || mode) {       // (no flag set: the instances without mirror; a plan that converts: oriented-style instances only)
         if ((rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) != MJ_OK) return rc;
         a.mirror = p->d_rz_mirror;
     }
@@ -712,7 +934,7 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         // the output table, [C][256] elements: the host's arithmetic, which the kernels only look up
         const bool norm = output->normalize != 0;
         std::vector<uint8_t> lut((size_t)lut_bytes);
-        for (int c = 0; c < C; ++c) {
+        for (int c = 0; c < CO; ++c) {
             uint32_t bits[256];
             mj::build_normalize_table(dtype, norm ? output->mean[c] : 0.0f, norm ? output->std[c] : 1.0f, bits);
             for (int v = 0; v < 256; ++v) {
