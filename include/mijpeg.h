@@ -325,6 +325,28 @@ int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *batch, const mj
                                 int32_t filter, int32_t mode, mj_plan **out);
 int mj_plan_create_mode(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, const uint8_t *orientations, int32_t mode, mj_plan **out);
 int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out);
+/* Aspect-preserving sizing: mj_plan_create_resized_mode whose images are not stretched over out_width x out_height — that is now a
+ * CANVAS — but resized each to a size of its own and placed on it (tools/place_model.py): torchvision's Resize(s) + CenterCrop, a
+ * letterbox (Pillow's ImageOps.pad), a crop of the resized image, all in the one resize launch.
+ *   places[k]  width, height: the size image k (oriented, or its window) is resized to, 1..65535 each.  x, y: where its top-left
+ *              lies on the canvas, |x|, |y| <= 65535 — negative: the image is cropped there, positive: padded.
+ *   fill       one byte per OUTPUT component (fill[0] alone for one component); NULL: zeros.
+ * Canvas element (ox, oy, c) of image k is the byte Image.resize((width_k, height_k), filter) has at (ox - x_k, oy - y_k) where
+ * that lies inside the resized image, fill[c] elsewhere; either byte then takes the output's path (the dtype's table, the
+ * normalisation: the fill is a byte that gets normalised, as torchvision's pad before ToTensor yields).  The mode converts first,
+ * the geometry refers to the oriented image or window, and a mirror flag flips the finished canvas, padding included.
+ * Only the canvas's elements are computed.  With windows, only the source rows and columns whose taps reach the canvas are
+ * decoded: every window shrinks to that range (mj_plan_time_resize's source_bytes counts what was decoded); whole images are
+ * decoded whole, which measured faster (option MJ_PLACE_WINDOW, csrc/resize.hip).
+ * places == NULL, or every place {out_width, out_height, 0, 0}: exactly the plan mj_plan_create_resized_mode returns, made by the
+ * same code.  MJ_ERR_INVALID naming the image: a size or offset outside the ranges above, an image that does not meet the canvas. */
+typedef struct {
+    int32_t width, height;
+    int32_t x, y;
+} mj_place;
+int mj_plan_create_resized_placed(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                  const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                  int32_t filter, int32_t mode, const mj_place *places, const uint8_t fill[3], mj_plan **out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -481,6 +503,8 @@ int mj_context_launch_clock(mj_context *ctx, float *shader_mhz, float *launch_ms
  *   MJ_PROG_PARTS     1..8  parts per band of a split scan (4)
  *   MJ_PROG_CHUNKS    0 | 1 | 2  the first AC scans of progressive files in self-synchronising chunks, one per lane, in front of the
  *                     band pipeline: never | from 2 048 images on | always;  MJ_PROG_CHUNK  128..65536 bytes per chunk (512)
+ *   MJ_PLACE_WINDOW   0 | 1  a placed plan decodes only the source range its canvas needs: never | whenever that is less than the
+ *                     images or windows (default: where the caller gave windows; whole images stay whole, see csrc/resize.hip)
  *   MJ_LANES_WAVES    1..16   MJ_LANES_PER_WAVE  1..64 (the 11-bit lane form reads 1 as 2)   MJ_LANES_RING  64 | 128
  *   MJ_STAGE2_CHUNK   1..4096 strips per stage-2 job
  *   MJ_FUSED          0 | 1  (0 = mj_plan_execute always launches the stages separately)

@@ -46,6 +46,7 @@ EXPORTS = (
     "mj_plan_create_oriented", "mj_plan_create_resized_oriented", "mj_host_exif_orientations",
     "mj_plan_create_resized_filtered", "mj_host_resize_table_filtered", "mj_debug_resize_shape",
     "mj_plan_create_resized_mode", "mj_plan_create_mode", "mj_host_convert_mode",
+    "mj_plan_create_resized_placed",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -95,6 +96,11 @@ class HostJobC(ctypes.Structure):
 class RoiC(ctypes.Structure):
     """mj_roi: one image's window (x along image_width, y along image_height)."""
     _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class PlaceC(ctypes.Structure):
+    """mj_place: the size one image is resized to and where its top-left lies on the canvas."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("x", ctypes.c_int32), ("y", ctypes.c_int32)]
 
 
 class OutputDescC(ctypes.Structure):
@@ -150,6 +156,8 @@ def load_library():
                                                   ctypes.POINTER(OutputDescC), vp, i32, ctypes.POINTER(vp)]
     L.mj_plan_create_resized_mode.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
                                               ctypes.POINTER(OutputDescC), vp, i32, i32, ctypes.POINTER(vp)]
+    L.mj_plan_create_resized_placed.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
+                                                ctypes.POINTER(OutputDescC), vp, i32, i32, ctypes.POINTER(PlaceC), vp, ctypes.POINTER(vp)]
     L.mj_plan_create_mode.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), vp, i32, ctypes.POINTER(vp)]
     L.mj_host_convert_mode.argtypes = [i32, vp, i32, i64, vp]
     L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
@@ -461,17 +469,42 @@ class Plan:
     filter: with size, None or "bilinear" (the plans above, through the entry points above) or another name of FILTERS / its
     MJ_FILTER_*: the resize with that resample filter (mj_plan_create_resized_filtered).
     mode: None, or a name of MODES / its MJ_MODE_* — the components of the output (mj_plan_create_mode, with size
-    mj_plan_create_resized_mode, which take all of the above); info.rgb_bytes, slots and image_offsets then count those."""
+    mj_plan_create_resized_mode, which take all of the above); info.rgb_bytes, slots and image_offsets then count those.
+    places: with size — then the canvas —, None or one (width, height, x, y) per image: the size it is resized to and where it lies
+    on the canvas (mj_plan_create_resized_placed, which takes all of the above); fill: with places, None (zeros) or up to three
+    bytes, one per output component."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None, mode=None):
+                 filter=None, mode=None, places=None, fill=None):
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
         arr = None
         if rois is not None:
             arr = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in r)) for r in rois])
-        if mode is not None:
+        if places is not None:
+            if size is None:
+                raise ValueError("places need size: the canvas the images are placed on")
+            if len(places) != batch_c.n_images:
+                raise ValueError(f"places: {len(places)} entries for {batch_c.n_images} images")
+            turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
+            desc, flags = output_desc(output) if output is not None else (None, None)
+            if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):
+                raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
+            sl, n_slots = None, 0
+            if slots is not None:
+                sl = np.ascontiguousarray(slots[0], dtype=np.int32)
+                n_slots = int(slots[1])
+            parr = (PlaceC * max(1, len(places)))(*[PlaceC(*(int(v) for v in pl)) for pl in places])
+            fb = np.zeros(3, dtype=np.uint8)
+            if fill is not None:
+                fb[:len(fill)] = fill
+            ctx.check(ctx.lib.mj_plan_create_resized_placed(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
+                                                            ctypes.byref(desc) if desc is not None else None, _ptr(turns), filter_id(filter),
+                                                            mode_id(mode), parr, _ptr(fb), ctypes.byref(h)))
+        elif fill is not None:
+            raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
+        elif mode is not None:
             turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
             desc, flags = output_desc(output) if output is not None else (None, None)
             if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):

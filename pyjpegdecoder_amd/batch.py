@@ -568,6 +568,115 @@ def normalize_rois(rois, dims: Sequence[Tuple[int, int]]) -> Optional[List[Tuple
     return out
 
 
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_resize_kind(k) -> bool:
+    """one file's ``resize_to``: an int (the shorter side), (width, height) or "contain" """
+    if isinstance(k, str):
+        return k == "contain"
+    if _is_int(k):
+        return 1 <= int(k) <= 65535
+    return isinstance(k, tuple) and len(k) == 2 and all(_is_int(v) and 1 <= int(v) <= 65535 for v in k)
+
+
+def resized_size(kind, w: int, h: int, canvas: Tuple[int, int]) -> Tuple[int, int]:
+    """The (width, height) a w x h image is resized to under one file's ``resize_to`` (tools/place_model.py: resized_size).  An
+    int ``s``: torchvision's ``Resize(s)`` — the shorter side becomes s, the longer ``int(s * long / short)``.  (width, height):
+    that.  "contain": Pillow's ``ImageOps.contain`` into the canvas — ``round(h / w * W)`` or ``round(w / h * H)``, half to even."""
+    if isinstance(kind, str):
+        cw, ch = canvas
+        im_ratio, dest_ratio = w / h, cw / ch
+        if im_ratio == dest_ratio:
+            return cw, ch
+        return (cw, round(h / w * cw)) if im_ratio > dest_ratio else (round(w / h * ch), ch)
+    if isinstance(kind, tuple):
+        return int(kind[0]), int(kind[1])
+    short, long = sorted((w, h))
+    new_long = int(int(kind) * long / short)
+    return (int(kind), new_long) if w <= h else (new_long, int(kind))
+
+
+def centred(kind, resized: Tuple[int, int], canvas: Tuple[int, int]) -> Tuple[int, int]:
+    """Where the resized image's top-left lies on the canvas by the rule of its ``resize_to`` kind (tools/place_model.py:
+    centred): torchvision's ``center_crop`` — crop at ``int(round((r - c) / 2.0))``, pad ``(c - r) // 2`` in front — or, for
+    "contain", ``ImageOps.pad``'s ``round((c - r) * 0.5)``."""
+    if isinstance(kind, str):
+        return tuple(round((c - r) * 0.5) for r, c in zip(resized, canvas))
+    return tuple(-int(round((r - c) / 2.0)) if r >= c else (c - r) // 2 for r, c in zip(resized, canvas))
+
+
+def normalize_fill(fill, resize_to, ncomp: Optional[int] = None) -> Optional[Tuple[int, ...]]:
+    """The fill of a placed decode, checked: None, or one byte 0..255 per output component (``ncomp``; None: not known yet) —
+    from one int for all of them or a sequence of that length.  It needs ``resize_to``.  ValueError otherwise."""
+    if fill is None:
+        return None
+    if resize_to is None:
+        raise ValueError("fill needs resize_to: without it every image covers the whole of size")
+    if _is_int(fill):
+        vals = [int(fill)] * (ncomp or 1)
+    else:
+        ok = isinstance(fill, (tuple, list, np.ndarray)) and 1 <= len(fill) <= 3 and all(_is_int(v) for v in fill)
+        if not ok or (ncomp is not None and len(fill) != ncomp):
+            raise ValueError(f"fill must be one int or one per output component ({ncomp if ncomp is not None else '1 or 3'}), 0..255 each, not {fill!r}")
+        vals = [int(v) for v in fill]
+    if any(v < 0 or v > 255 for v in vals):
+        raise ValueError(f"fill must be one int or one per output component, 0..255 each, not {fill!r}")
+    return tuple(vals)
+
+
+def normalize_places(resize_to, place, size, dims: Optional[Sequence[Tuple[int, int]]] = None, index: Optional[Sequence[int]] = None):
+    """The placement of a decode onto a canvas, checked: None for a call without it, else one (width, height, x, y) per file — the
+    size the file's image (as its orientation shows it; its window, with ``rois``) is resized to, and where its top-left lies on
+    the canvas ``size``; or None where every file is stretched over the whole canvas, which is a call without the arguments.
+
+    ``resize_to``: None, an int (the shorter side: torchvision's ``Resize``), a tuple (width, height), "contain" (Pillow's
+    ``ImageOps.contain``), or a list with one of these per file.  ``place``: None (centred by the rule of the file's kind:
+    :func:`centred`), one (x, y), or a list with (x, y) or None per file.  Both need ``size``; ``place`` needs ``resize_to``.
+    ``dims``: the files' (width, height); None: not known yet — everything but the lengths and the geometry is checked.
+    ValueError naming the file (``index``: its position in the caller's list) otherwise."""
+    if resize_to is None:
+        if place is not None:
+            raise ValueError("place needs resize_to: without it every image covers the whole of size")
+        return None
+    if size is None:
+        raise ValueError("resize_to needs size=(width, height): the canvas the resized images are placed on")
+    per_file = isinstance(resize_to, list)       # ((width, height) is a tuple; a list is one entry per file)
+    for k in (resize_to if per_file else [resize_to]):
+        if not _is_resize_kind(k):
+            raise ValueError(f"resize_to must be None, an int 1..65535 (the shorter side), a tuple (width, height), 'contain' or a list with one of "
+                             f"these per file, not {resize_to!r}")
+
+    def is_xy(v) -> bool:
+        return isinstance(v, (tuple, list, np.ndarray)) and len(v) == 2 and all(_is_int(t) and abs(int(t)) <= 65535 for t in v)
+    one_xy = place is None or is_xy(place)
+    if not one_xy:
+        if not isinstance(place, (list, tuple)) or not all(v is None or is_xy(v) for v in place):
+            raise ValueError(f"place must be None, one (x, y) of integers within +-65535 or a list with (x, y) or None per file, not {place!r}")
+    if dims is None:
+        return None
+    n = len(dims)
+    if per_file and len(resize_to) != n:
+        raise ValueError(f"resize_to has {len(resize_to)} entries for {n} files")
+    if not one_xy and len(place) != n:
+        raise ValueError(f"place has {len(place)} entries for {n} files")
+    out, plain = [], True
+    for i, (w, h) in enumerate(dims):
+        kind = resize_to[i] if per_file else resize_to
+        xy = place if one_xy else place[i]
+        name = i if index is None else index[i]
+        rw, rh = resized_size(kind, int(w), int(h), size)
+        if rw < 1 or rh < 1 or rw > 65535 or rh > 65535:
+            raise ValueError(f"file {name}: resize_to={kind!r} makes the {w}x{h} image {rw}x{rh}; both sides must be 1..65535")
+        x, y = (int(v) for v in xy) if xy is not None else centred(kind, (rw, rh), size)
+        if x >= size[0] or y >= size[1] or x + rw <= 0 or y + rh <= 0:
+            raise ValueError(f"file {name}: the {rw}x{rh} image at ({x}, {y}) does not meet the {size[0]}x{size[1]} canvas")
+        plain = plain and (rw, rh, x, y) == (size[0], size[1], 0, 0)
+        out.append((rw, rh, x, y))
+    return None if plain else out
+
+
 _TRANSPOSING = (5, 6, 7, 8)          # EXIF orientations that exchange width and height (tools/orient_model.py)
 
 
@@ -644,7 +753,9 @@ class _Request:
     where every file sits in the list the caller passed, for the messages of errors (None: this is that list).  ``orient``:
     :func:`normalize_orientation`'s list (None: every file as stored); the windows are then windows of the oriented images.
     ``resample``: :func:`normalize_resample`'s filter of the resize (None: bilinear, the request of a call without the argument).
-    ``mode``: :func:`normalize_mode`'s output colour mode (None: every file's own components)."""
+    ``mode``: :func:`normalize_mode`'s output colour mode (None: every file's own components).
+    ``places``: :func:`normalize_places`' list (None: every image stretched over ``size``, the request of a call without
+    ``resize_to``) and ``fill``: :func:`normalize_fill`'s bytes for the canvas elements no image covers (None: zeros)."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
@@ -655,6 +766,8 @@ class _Request:
     orient: Optional[List[int]] = None
     resample: Optional[str] = None
     mode: Optional[str] = None
+    places: Optional[List[Tuple[int, int, int, int]]] = None
+    fill: Optional[Tuple[int, ...]] = None
 
     @property
     def ncomp(self) -> Optional[int]:
@@ -673,7 +786,7 @@ class _Request:
         if orient is not None and all(o == 1 for o in orient):
             orient = None
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode)
+                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill)
 
     def orient_classes(self) -> List[List[int]]:
         """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
@@ -696,6 +809,9 @@ class _Request:
             kw["filter"] = self.resample
         if self.mode is not None and native != self.ncomp:      # (files of the mode's own count: the arguments of a call without mode)
             kw["mode"] = self.mode
+        if self.places is not None:         # (every image over the whole of size: the arguments of a call without resize_to)
+            kw["places"], kw["fill"] = self.places, self.fill
+            kw.setdefault("mode", self.mode)
         return kw
 
 
@@ -843,7 +959,7 @@ class BatchDecoder:
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
-               orientation=None, resample=None, mode=None):
+               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -861,7 +977,14 @@ class BatchDecoder:
         has three components, a greyscale file's value in all of them, or one, a colour file's ``convert("L")``.  The conversion
         comes first: the result is ``exif_transpose(img.convert(mode)).resize(size, filter)``, then the output table, then the
         mirror.  With ``size`` a list may then mix greyscale and colour files, and ``normalize`` is checked against the mode's
-        count; files that already have it decode exactly as without the argument."""
+        count; files that already have it decode exactly as without the argument.
+        ``resize_to``, with ``size``: aspect-preserving sizing — ``size`` becomes a canvas, every image (oriented; its window) is
+        resized to a size of its own and placed on it, in the same one resize launch (:func:`normalize_places`).  An int ``s``:
+        torchvision's ``Resize(s)`` (the shorter side) then ``CenterCrop(size)``; a tuple (width, height): that size; "contain":
+        Pillow's ``ImageOps.pad(img, size, filter, color=fill)``; or a list with one of these per file.  ``place``: None (centred by
+        the rule of the file's kind), one (x, y) or one per file — the resized image's top-left on the canvas, negative where it is
+        cropped.  ``fill``: the byte (or one per output component) of canvas elements no image covers, 0 by default; it goes
+        through ``dtype`` / ``normalize`` like a pixel, and ``mirror`` flips the finished canvas.  Only the canvas is computed."""
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -874,16 +997,20 @@ class BatchDecoder:
             raise ValueError("size and return_seams do not go together: the seam outputs are at the files' own sizes")
         normalize_output(dtype, normalize, mirror, size, host=True)       # (what needs no file: before any is parsed)
         resample = normalize_resample(resample, size)
+        normalize_places(resize_to, place, size)
+        normalize_fill(fill, resize_to)
         gpu_segment = self._gpu_segment_for(files)
         parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
         orient = normalize_orientation(orientation, files)
-        req = _Request(files, normalize_rois(rois, _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)), size,
-                       orient=orient, resample=resample, mode=mode)
+        odims = _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)
+        req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode)
+        req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
         turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
             nc = req.ncomp or one_component_count([len(p.color_components) for p in parsed.values()])
             req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc, host=True)
+            req.fill = normalize_fill(fill, resize_to, nc)
             dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         results: List[Optional[np.ndarray]] = [None] * len(files)
         seams: List[Optional[dict]] = [None] * len(files)
@@ -935,7 +1062,8 @@ class BatchDecoder:
             self._staging = np.empty(need + need // 4, dtype=np.uint8)
         return self._staging
 
-    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None) -> _Request:
+    def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
+                        resize_to=None, place=None, fill=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order."""
@@ -946,7 +1074,10 @@ class BatchDecoder:
             info = [_image_info(f) for f in files]
             nc = req.ncomp or one_component_count([t[2] for t in info])
             req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
-            req.wins = normalize_rois(rois, _oriented_dims([t[:2] for t in info], req.orient))
+            odims = _oriented_dims([t[:2] for t in info], req.orient)
+            req.wins = normalize_rois(rois, odims)
+            req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
+            req.fill = normalize_fill(fill, resize_to, nc)
             req.dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
             req.slots = list(range(len(files)))
@@ -964,7 +1095,7 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, orientation=None, resample=None, mode=None):
+                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -991,12 +1122,17 @@ class BatchDecoder:
         files of several kinds, parts) resamples with it.
         ``mode`` as in :meth:`decode`: None, "RGB" or "L".  Greyscale and colour files are plans of their own as ever; the plans of
         the files that do not have the mode's components convert inside the launch they end in anyway — the resize launch, or the
-        one extra launch of an own-size plan — and with ``size`` all of them fill their slots of the one tensor."""
+        one extra launch of an own-size plan — and with ``size`` all of them fill their slots of the one tensor.
+        ``resize_to``, ``place`` and ``fill`` as in :meth:`decode`: ``size`` is a canvas, every image is resized to a size of its
+        own and placed on it by the one resize launch of its plan; files of several kinds and orientation classes are still one
+        plan per kind, each writing its slots of the one tensor."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
         normalize_mode(mode)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode)
+        normalize_places(resize_to, place, size)
+        normalize_fill(fill, resize_to)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
@@ -1105,7 +1241,7 @@ class BatchDecoder:
         return results if req.dest is None else req.dest
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
-                           mode=None):
+                           mode=None, resize_to=None, place=None, fill=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1122,10 +1258,13 @@ class BatchDecoder:
         ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file).  ``orientation``: None, "exif" or
         an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes.
-        ``resample`` and ``mode`` as in :meth:`decode_device`, for every batch."""
+        ``resample`` and ``mode`` as in :meth:`decode_device`, for every batch; ``resize_to``, ``place`` and ``fill`` too (a list
+        per file then has to fit every batch)."""
         size = normalize_size(size)
         normalize_resample(resample, size)                                            # (what needs no file: before any work)
         normalize_mode(mode)
+        normalize_places(resize_to, place, size)
+        normalize_fill(fill, resize_to)
         turns_per_batch = not (orientation is None or isinstance(orientation, (str, int, np.integer)))
         if not turns_per_batch:
             normalize_orientation(orientation, [])                                    # (what needs no file: before any work)
@@ -1151,7 +1290,7 @@ class BatchDecoder:
                         o = next(turns)
                     except StopIteration:
                         raise ValueError("orientation yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode)
+                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -323,7 +323,7 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
     }
     mj::ResizeArgs a = p->rz;
     a.dst = p->last_rgb;
-    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp, p->out_ncomp));
+    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp, p->out_ncomp, p->rz_placed, p->rz_fill));
     return MJ_OK;
 }
 

@@ -414,7 +414,9 @@ bool resize_filter_signed(int filter);
 int resize_axis_ksize(int in_size, int out_size, int filter = 0);
 void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0);
 // (out_ncomp: 0 or ncomp — the instances there were; else a plan that converts, mj_plan_create_resized_mode)
-hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp = 0);
+// (placed: a plan of mj_plan_create_resized_placed — its own instances, which store `fill`, byte c in bits 8c..8c+7, where
+// the image does not cover the canvas; a.mirror is then set)
+hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp = 0, int placed = 0, unsigned fill = 0);
 // ---- output colour mode (tools/mode_model.py)
 // Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
 __host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }

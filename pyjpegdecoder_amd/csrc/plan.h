@@ -267,6 +267,8 @@ struct mj_plan {
     uint8_t *d_rz_mirror = nullptr;        // ... with a mirror flag set: one byte per image
     uint8_t *d_rz_lut = nullptr;           // mj_plan_create_resized_as with a float dtype: the output table (info.rgb_bytes: bytes of that type)
     mj::ResizeArgs rz{};
+    int rz_placed = 0;                     // mj_plan_create_resized_placed: the placed instances, which store rz_fill (byte c in bits
+    unsigned rz_fill = 0;                  // 8c..8c+7) where an image does not cover the canvas
     int rz_filter = 0, rz_max_ksize = 0;   // the plan's MJ_FILTER_* and the most taps a pixel of it has per axis (mj_debug_resize_shape)
     // oriented plans at the files' own sizes (mj_plan_create_oriented): `resized` with the orient launch (orient.hip) in the
     // resize launch's place — stage 2 writes stored-order pixels into d_src, the launch writes them oriented into the output

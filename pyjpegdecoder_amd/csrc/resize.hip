@@ -36,6 +36,13 @@
 // T run on ONE component either way.  Grey to RGB finishes every pixel's sum once into a tile of bytes in LDS and the store
 // loop — one element per lane, consecutive lanes consecutive elements, as above — looks up lut[c][byte] for c = 0..2.  They
 // are instances in the oriented style only (the per-image byte holds the flips and the mirror flag; all zero for a plain plan).
+//
+// Aspect-preserving sizing (mj_plan_create_resized_placed): the output is a canvas, every image is resized to a size of its own and
+// placed at an offset on it; elements it does not cover hold a fill byte, which takes the output's path like any other.  The tap
+// tables are built in the canvas's coordinates — an entry outside the image has no taps and keeps the bound of the nearest entry inside
+// as its first index — so the k_resize_*_placed instances compute canvas elements only: a tile the image does not reach stores
+// fill and returns before any staging, a tile it reaches runs the width pass over the covered columns and rows alone.  With windows,
+// plan creation shrinks every window to the source range the canvas needs (create_resized: the rule and its numbers).
 #include <math.h>
 
 #include <map>
@@ -186,6 +193,27 @@ __device__ __forceinline__ const OutT *stage_lut(const ResizeArgs &a, unsigned c
     }
 }
 
+// ---- placed plans (mj_plan_create_resized_placed): `fill` holds the canvas's fill byte of component c in bits 8c..8c+7
+__device__ __forceinline__ unsigned fill_byte(unsigned fill, int c) { return (fill >> (8 * c)) & 255u; }
+
+// A tile no pixel of which the image covers: every element is the fill element, stored in the order the height pass stores
+// (XM: along the columns) — before any staging, so the table entry comes from global memory.
+template <int C, typename OutT, bool XM>
+__device__ __forceinline__ void fill_tile(const ResizeArgs &a, const DevResizeImage &im, int img, unsigned fill, int ox0, int oy0, int ncols, int orows) {
+    OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
+    const OutT *lut = static_cast<const OutT *>(a.lut);
+    const unsigned turn = a.mirror[img];
+    const bool planar = a.layout >= 2 && C > 1;
+    const int npix = orows * ncols, fast = XM ? orows : ncols;
+    for (int i = threadIdx.x; i < npix * C; i += 256) {
+        int pix, c;
+        if (planar) { c = i / npix; pix = i - c * npix; } else { pix = i / C; c = i - pix * C; }
+        const int slow = pix / fast, f = pix - slow * fast;
+        const int ox = ox0 + (XM ? slow : f), oy = oy0 + (XM ? f : slow);
+        dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, fill_byte(fill, c));
+    }
+}
+
 // Row-major source.  LDS: T [t_rows][t_pitch] | per output column of the tile: first source column (relative), taps, the
 // taps themselves [tc][ksx] | one staging row per wavefront | the output table (2- and 4-byte elements).
 template <int C, typename OutT = unsigned char, bool MIRROR = false, bool ORIENT = false, bool SGN = false>
@@ -258,6 +286,83 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor(const ResizeArgs a) {
         const int ox = ox0 + oxl;
         if constexpr (ORIENT) dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, Tap<SGN>::clip(acc));
         else dst[out_index(a, C, flip ? a.ow - 1 - ox : ox, oy, c)] = out_value<OutT>(lut, c, Tap<SGN>::clip(acc));
+    }
+}
+
+// The placed instance: k_resize_rowmajor in the oriented style (the per-image byte holds the flips and the mirror flag, all zero
+// where there are none) over canvas tables — entries outside the image have no taps and keep the bound of the nearest entry
+// inside as their first index, so a tile's span covers only what the image needs and the width pass runs over that alone.
+template <int C, typename OutT, bool SGN>
+__global__ __launch_bounds__(256) void k_resize_rowmajor_placed(const ResizeArgs a, const unsigned fill) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int xa = X.lo[ox0], xb = X.lo[ox1 - 1] + X.cnt[ox1 - 1];       // (both bounds grow with the output index)
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, ne = ncols * C;
+    // (a tile the image does not reach: no source entries along an axis)
+    if (xb == xa || yb == ya) { fill_tile<C, OutT, false>(a, im, img, fill, ox0, oy0, ncols, oy1 - oy0); return; }
+    unsigned char *T = smem;
+    int32_t *lx_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *lx_cnt = lx_lo + a.tc, *lx_k = lx_cnt + a.tc;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    unsigned char *stage = smem + a.stage_off + wave * a.stage_bytes;
+    for (int i = tid; i < ncols; i += 256) { lx_lo[i] = (X.lo[ox0 + i] - xa) * C; lx_cnt[i] = X.cnt[ox0 + i]; }
+    for (int i = tid; i < ncols * X.ks; i += 256) lx_k[i] = X.k[(int64_t)ox0 * X.ks + i];
+    const OutT *lut = stage_lut<C, OutT>(a, smem, tid);
+    __syncthreads();
+    const unsigned char *src = a.src + im.src_off;
+    const int seg = (xb - xa) * C;
+    // width pass: every wavefront takes every fourth source row of the tile
+    for (int r = wave; r < nrows; r += 4) {
+        const unsigned char *row = src + ((int64_t)(ya + r) * im.w + xa) * C;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15);
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(row - mis);
+        const int n16 = (mis + seg + 15) >> 4;
+        for (int j = lane; j < n16; j += 64) reinterpret_cast<u32x4 *>(stage)[j] = p[j];
+        // (the staging row is this wavefront's own: its lanes only have to see each other's LDS writes)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int e = lane; e < ne; e += 64) {
+            const int oxl = e / C, c = e - oxl * C;
+            const unsigned char *s = stage + mis + lx_lo[oxl] + c;
+            const int32_t *k = lx_k + oxl * X.ks;
+            const int n = lx_cnt[oxl];
+            acc_t acc = (acc_t)1 << 21;
+            for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * C]);
+            T[r * a.t_pitch + e] = (unsigned char)Tap<SGN>::clip(acc);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    // height pass: consecutive lanes take consecutive elements of an output row (of a plane's row for planar plans)
+    OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
+    const unsigned turn = a.mirror[img];      // bit 0 = store at column ow - 1 - x, bit 1 = at row oh - 1 - y
+    const int orows = oy1 - oy0, total = orows * ne;
+    const bool planar = a.layout >= 2 && C > 1;
+    for (int i = tid; i < total; i += 256) {
+        int oyl, oxl, c;
+        if (planar) { c = i / (orows * ncols); const int rem = i - c * (orows * ncols); oyl = rem / ncols; oxl = rem - oyl * ncols; }
+        else { oyl = i / ne; const int e = i - oyl * ne; oxl = e / C; c = e - oxl * C; }
+        const int oy = oy0 + oyl;
+        const int n = Y.cnt[oy];
+        const int32_t *k = Y.k + (int64_t)oy * Y.ks;
+        const unsigned char *s = T + (Y.lo[oy] - ya) * a.t_pitch + oxl * C + c;
+        acc_t acc = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * a.t_pitch]);
+        const int ox = ox0 + oxl;
+        // (no taps on either axis: a canvas element the image does not cover)
+        const unsigned v = (n == 0 || lx_cnt[oxl] == 0) ? fill_byte(fill, c) : Tap<SGN>::clip(acc);
+        dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, v);
     }
 }
 
@@ -334,14 +439,88 @@ __global__ __launch_bounds__(256) void k_resize_xmajor(const ResizeArgs a) {
     }
 }
 
+// The placed instance (as k_resize_rowmajor_placed)
+template <int C, typename OutT, bool SGN>
+__global__ __launch_bounds__(256) void k_resize_xmajor_placed(const ResizeArgs a, const unsigned fill) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, orows = oy1 - oy0;
+    // (a tile the image does not reach: no source entries along an axis)
+    if (X.lo[ox1 - 1] + X.cnt[ox1 - 1] == X.lo[ox0] || yb == ya) { fill_tile<C, OutT, true>(a, im, img, fill, ox0, oy0, ncols, orows); return; }
+    unsigned char *T = smem;
+    int32_t *ly_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *ly_cnt = ly_lo + a.tr, *ly_k = ly_cnt + a.tr;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < orows; i += 256) { ly_lo[i] = (Y.lo[oy0 + i] - ya) * C; ly_cnt[i] = Y.cnt[oy0 + i]; }
+    for (int i = tid; i < orows * Y.ks; i += 256) ly_k[i] = Y.k[(int64_t)oy0 * Y.ks + i];
+    const OutT *lut = stage_lut<C, OutT>(a, smem, tid);
+    const unsigned char *src = a.src + im.src_off;
+    // width pass: 16 consecutive bytes of a column per lane, the taps' columns one after the other.  (The last chunk of a
+    // column reads up to 15 bytes behind the rows the tile needs — the next column's, or the buffer's padding — into T's
+    // padding, which nothing reads.)
+    const int nch = (nrows * C + 15) >> 4;
+    const int64_t col = (int64_t)im.h * C;
+    for (int i = tid; i < ncols * nch; i += 256) {
+        const int oxl = i / nch, j = i - oxl * nch;
+        const int ox = ox0 + oxl, n = X.cnt[ox];
+        const int32_t *k = X.k + (int64_t)ox * X.ks;
+        const unsigned char *p = src + ((int64_t)X.lo[ox] * im.h + ya) * C + 16 * j;
+        acc_t acc[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) acc[b] = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q, p += col) {
+            u32x4 v;
+            __builtin_memcpy(&v, p, 16);
+            const int32_t kq = k[q];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) acc[b] += Tap<SGN>::mul(kq, (v[b >> 2] >> (8 * (b & 3))) & 255u);
+        }
+        u32x4 o;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            o[d] = Tap<SGN>::clip(acc[4 * d]) | Tap<SGN>::clip(acc[4 * d + 1]) << 8 | Tap<SGN>::clip(acc[4 * d + 2]) << 16 | Tap<SGN>::clip(acc[4 * d + 3]) << 24;
+        *reinterpret_cast<u32x4 *>(T + oxl * a.t_pitch + 16 * j) = o;
+    }
+    __syncthreads();
+    // height pass: consecutive lanes take consecutive elements of an output column (of a plane's column for planar plans)
+    OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
+    const unsigned turn = a.mirror[img];      // bit 0 = store at column ow - 1 - x, bit 1 = at row oh - 1 - y
+    const int ne = orows * C, total = ncols * ne;
+    const bool planar = a.layout >= 2 && C > 1;
+    for (int i = tid; i < total; i += 256) {
+        int oyl, oxl, c;
+        if (planar) { c = i / (orows * ncols); const int rem = i - c * (orows * ncols); oxl = rem / orows; oyl = rem - oxl * orows; }
+        else { oxl = i / ne; const int e = i - oxl * ne; oyl = e / C; c = e - oyl * C; }
+        const int n = ly_cnt[oyl];
+        const int32_t *k = ly_k + oyl * Y.ks;
+        const unsigned char *s = T + oxl * a.t_pitch + ly_lo[oyl] + c;
+        acc_t acc = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * C]);
+        const int ox = ox0 + oxl;
+        // (no taps on either axis: a canvas element the image does not cover)
+        const unsigned v = (n == 0 || X.cnt[ox] == 0) ? fill_byte(fill, c) : Tap<SGN>::clip(acc);
+        dst[out_index(a, C, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - (oy0 + oyl) : oy0 + oyl, c)] = out_value<OutT>(lut, c, v);
+    }
+}
+
 // ---- output colour mode: source components CS != output components CO (T, both passes and the tile geometry: one component)
 // The end of the height pass.  CO == 1: the finished byte is the element.  CO == 3: every pixel's byte goes into the tile O in LDS
 // once; after the barrier a lane stores one element (pixel, c), looked up in component c's table.
 // XM: T is [column][t_pitch] and a tile is walked along its columns (the x-major kernel), else [row][t_pitch] along its rows.
-template <int CO, typename OutT, bool SGN, bool XM>
+// PLACED: xcnt[oxl] is the tap count of the tile's column oxl — 0 there, or on the height axis, marks an element the image does
+// not cover, stored as the fill byte of its component (`fill`: fill_byte).
+template <int CO, typename OutT, bool SGN, bool XM, bool PLACED = false>
 __device__ __forceinline__ void mode_height_pass(const ResizeArgs &a, const DevResizeImage &im, int img, const unsigned char *T, unsigned char *O,
                                                  const OutT *lut, const int32_t *lo, const int32_t *cnt, const int32_t *k_all, int ks, int ya, int ox0,
-                                                 int oy0, int ncols, int orows, int tid) {
+                                                 int oy0, int ncols, int orows, int tid, const int32_t *xcnt = nullptr, unsigned fill = 0) {
     typedef typename Tap<SGN>::acc_t acc_t;
     OutT *dst = reinterpret_cast<OutT *>(a.dst + im.dst_off);
     const unsigned turn = a.mirror[img];      // bit 0 = store at column ow - 1 - x, bit 1 = at row oh - 1 - y
@@ -356,7 +535,8 @@ __device__ __forceinline__ void mode_height_pass(const ResizeArgs &a, const DevR
         const int step = XM ? 1 : a.t_pitch;
         acc_t acc = (acc_t)1 << 21;
         for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q * step]);
-        const unsigned v = Tap<SGN>::clip(acc);
+        unsigned v = Tap<SGN>::clip(acc);
+        if constexpr (PLACED && CO == 1) { if (n == 0 || xcnt[oxl] == 0) v = fill_byte(fill, 0); }
         if constexpr (CO == 1) {
             const int ox = ox0 + oxl, oy = oy0 + oyl;
             dst[out_index(a, 1, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, 0)] = out_value<OutT>(lut, 0, v);
@@ -371,7 +551,9 @@ __device__ __forceinline__ void mode_height_pass(const ResizeArgs &a, const DevR
             if (planar) { c = i / npix; pix = i - c * npix; } else { pix = i / CO; c = i - pix * CO; }
             const int slow = pix / fast, f = pix - slow * fast;
             const int ox = ox0 + (XM ? slow : f), oy = oy0 + (XM ? f : slow);
-            dst[out_index(a, CO, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, (unsigned)O[pix]);
+            unsigned v = (unsigned)O[pix];
+            if constexpr (PLACED) { if ((XM ? cnt[f] : cnt[oy]) == 0 || xcnt[XM ? slow : f] == 0) v = fill_byte(fill, c); }
+            dst[out_index(a, CO, (turn & 1) ? a.ow - 1 - ox : ox, (turn & 2) ? a.oh - 1 - oy : oy, c)] = out_value<OutT>(lut, c, v);
         }
     }
 }
@@ -447,6 +629,72 @@ __global__ __launch_bounds__(256) void k_resize_rowmajor_mode(const ResizeArgs a
     mode_height_pass<CO, OutT, SGN, false>(a, im, img, T, mode_tile<CO, OutT>(a, smem), lut, Y.lo, Y.cnt, Y.k, Y.ks, ya, ox0, oy0, ncols, oy1 - oy0, tid);
 }
 
+// The placed instance (as k_resize_rowmajor_placed)
+template <int CS, int CO, typename OutT, bool SGN>
+__global__ __launch_bounds__(256) void k_resize_rowmajor_mode_placed(const ResizeArgs a, const unsigned fill) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int xa = X.lo[ox0], xb = X.lo[ox1 - 1] + X.cnt[ox1 - 1];
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, npx = xb - xa;
+    if (xb == xa || yb == ya) { fill_tile<CO, OutT, false>(a, im, img, fill, ox0, oy0, ncols, oy1 - oy0); return; }
+    unsigned char *T = smem;
+    int32_t *lx_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *lx_cnt = lx_lo + a.tc, *lx_k = lx_cnt + a.tc;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    unsigned char *stage = smem + a.stage_off + wave * a.stage_bytes;
+    for (int i = tid; i < ncols; i += 256) { lx_lo[i] = X.lo[ox0 + i] - xa; lx_cnt[i] = X.cnt[ox0 + i]; }
+    for (int i = tid; i < ncols * X.ks; i += 256) lx_k[i] = X.k[(int64_t)ox0 * X.ks + i];
+    const OutT *lut = stage_lut<CO, OutT>(a, smem, tid);
+    __syncthreads();
+    const unsigned char *src = a.src + im.src_off;
+    const int seg = npx * CS;
+    for (int r = wave; r < nrows; r += 4) {
+        const unsigned char *row = src + ((int64_t)(ya + r) * im.w + xa) * CS;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15);
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(row - mis);
+        const int n16 = (mis + seg + 15) >> 4;
+        for (int j = lane; j < n16; j += 64) reinterpret_cast<u32x4 *>(stage)[j] = p[j];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const unsigned char *g = stage + mis;
+        if constexpr (CS == 3) {
+            // the staged row to L, pixel by pixel, before any tap sees it
+            unsigned char *grey = stage + 3 * (a.stage_bytes >> 2);
+            for (int x = lane; x < npx; x += 64) {
+                const unsigned char *s = stage + mis + 3 * x;
+                grey[x] = (unsigned char)mode_luma(s[0], s[1], s[2]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            g = grey;
+        }
+        for (int e = lane; e < ncols; e += 64) {
+            const unsigned char *s = g + lx_lo[e];
+            const int32_t *k = lx_k + e * X.ks;
+            const int n = lx_cnt[e];
+            acc_t acc = (acc_t)1 << 21;
+            for (int q = 0; q < n; ++q) acc += Tap<SGN>::mul(k[q], (unsigned)s[q]);
+            T[r * a.t_pitch + e] = (unsigned char)Tap<SGN>::clip(acc);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    mode_height_pass<CO, OutT, SGN, false, true>(a, im, img, T, mode_tile<CO, OutT>(a, smem), lut, Y.lo, Y.cnt, Y.k, Y.ks, ya, ox0, oy0, ncols, oy1 - oy0, tid,
+                                                   lx_cnt, fill);
+}
+
 // X-major source.  LDS as k_resize_xmajor's with T in one component.  A colour source: a lane takes 16 PIXELS of a column — 48
 // consecutive bytes, three 16-byte loads — per tap, converts them in registers and accumulates their L.  (The last chunk of a
 // column reads up to 47 bytes behind the rows the tile needs: the next column's, or the buffer's 64 bytes of slack.)
@@ -509,9 +757,79 @@ __global__ __launch_bounds__(256) void k_resize_xmajor_mode(const ResizeArgs a) 
     mode_height_pass<CO, OutT, SGN, true>(a, im, img, T, mode_tile<CO, OutT>(a, smem), lut, ly_lo, ly_cnt, ly_k, Y.ks, ya, ox0, oy0, ncols, orows, tid);
 }
 
+// The placed instance (as k_resize_rowmajor_placed)
+template <int CS, int CO, typename OutT, bool SGN>
+__global__ __launch_bounds__(256) void k_resize_xmajor_mode_placed(const ResizeArgs a, const unsigned fill) {
+    typedef typename Tap<SGN>::acc_t acc_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tiles = a.tiles_x * a.tiles_y;
+    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;      // (launch_resize: the grid's tail is idle)
+    if (wg >= (int64_t)a.n_images * tiles) return;
+    const int img = (int)(wg / tiles), t = (int)(wg - (int64_t)img * tiles);
+    const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    const DevResizeImage im = a.images[img];
+    const int ox0 = tx * a.tc, ox1 = min(ox0 + a.tc, a.ow), oy0 = ty * a.tr, oy1 = min(oy0 + a.tr, a.oh);
+    const AxisTab X(a.tabs + im.xtab, a.ow), Y(a.tabs + im.ytab, a.oh);
+    const int ya = Y.lo[oy0], yb = Y.lo[oy1 - 1] + Y.cnt[oy1 - 1];
+    const int nrows = yb - ya, ncols = ox1 - ox0, orows = oy1 - oy0;
+    if (X.lo[ox1 - 1] + X.cnt[ox1 - 1] == X.lo[ox0] || yb == ya) { fill_tile<CO, OutT, true>(a, im, img, fill, ox0, oy0, ncols, orows); return; }
+    unsigned char *T = smem;
+    int32_t *ly_lo = reinterpret_cast<int32_t *>(smem + a.tab_off), *ly_cnt = ly_lo + a.tr, *ly_k = ly_cnt + a.tr;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < orows; i += 256) { ly_lo[i] = Y.lo[oy0 + i] - ya; ly_cnt[i] = Y.cnt[oy0 + i]; }
+    for (int i = tid; i < orows * Y.ks; i += 256) ly_k[i] = Y.k[(int64_t)oy0 * Y.ks + i];
+    const OutT *lut = stage_lut<CO, OutT>(a, smem, tid);
+    const unsigned char *src = a.src + im.src_off;
+    const int nch = (nrows + 15) >> 4;                 // 16 pixels of a column per lane
+    const int64_t col = (int64_t)im.h * CS;
+    for (int i = tid; i < ncols * nch; i += 256) {
+        const int oxl = i / nch, j = i - oxl * nch;
+        const int ox = ox0 + oxl, n = X.cnt[ox];
+        const int32_t *k = X.k + (int64_t)ox * X.ks;
+        const unsigned char *p = src + ((int64_t)X.lo[ox] * im.h + ya + 16 * j) * CS;
+        acc_t acc[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) acc[b] = (acc_t)1 << 21;
+        for (int q = 0; q < n; ++q, p += col) {
+            const int32_t kq = k[q];
+            if constexpr (CS == 3) {
+                unsigned w[12];
+                __builtin_memcpy(w, p, 48);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    const unsigned r = (w[(3 * b) >> 2] >> (8 * ((3 * b) & 3))) & 255u, g = (w[(3 * b + 1) >> 2] >> (8 * ((3 * b + 1) & 3))) & 255u,
+                                   bl = (w[(3 * b + 2) >> 2] >> (8 * ((3 * b + 2) & 3))) & 255u;
+                    acc[b] += Tap<SGN>::mul(kq, mode_luma(r, g, bl));
+                }
+            } else {
+                u32x4 v;
+                __builtin_memcpy(&v, p, 16);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) acc[b] += Tap<SGN>::mul(kq, (v[b >> 2] >> (8 * (b & 3))) & 255u);
+            }
+        }
+        u32x4 o;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            o[d] = Tap<SGN>::clip(acc[4 * d]) | Tap<SGN>::clip(acc[4 * d + 1]) << 8 | Tap<SGN>::clip(acc[4 * d + 2]) << 16 | Tap<SGN>::clip(acc[4 * d + 3]) << 24;
+        *reinterpret_cast<u32x4 *>(T + oxl * a.t_pitch + 16 * j) = o;
+    }
+    __syncthreads();
+    mode_height_pass<CO, OutT, SGN, true, true>(a, im, img, T, mode_tile<CO, OutT>(a, smem), lut, ly_lo, ly_cnt, ly_k, Y.ks, ya, ox0, oy0, ncols, orows, tid,
+                                                  X.cnt + ox0, fill);
+}
+
+
 template <int CS, int CO, typename OutT>
-void launch_mode_instance(hipStream_t stream, const ResizeArgs &a, dim3 grid, dim3 block) {
+void launch_mode_instance(hipStream_t stream, const ResizeArgs &a, dim3 grid, dim3 block, int placed, unsigned fill) {
     const bool xmajor = ((a.layout & 1) == 0) != (a.orient == 2);      // (as launch_instance: transposing orientations read the other way)
+    if (placed) {
+        if (xmajor && a.sgn) hipLaunchKernelGGL((k_resize_xmajor_mode_placed<CS, CO, OutT, true>), grid, block, a.lds_bytes, stream, a, fill);
+        else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor_mode_placed<CS, CO, OutT, false>), grid, block, a.lds_bytes, stream, a, fill);
+        else if (a.sgn) hipLaunchKernelGGL((k_resize_rowmajor_mode_placed<CS, CO, OutT, true>), grid, block, a.lds_bytes, stream, a, fill);
+        else hipLaunchKernelGGL((k_resize_rowmajor_mode_placed<CS, CO, OutT, false>), grid, block, a.lds_bytes, stream, a, fill);
+        return;
+    }
     if (xmajor && a.sgn) hipLaunchKernelGGL((k_resize_xmajor_mode<CS, CO, OutT, true>), grid, block, a.lds_bytes, stream, a);
     else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor_mode<CS, CO, OutT, false>), grid, block, a.lds_bytes, stream, a);
     else if (a.sgn) hipLaunchKernelGGL((k_resize_rowmajor_mode<CS, CO, OutT, true>), grid, block, a.lds_bytes, stream, a);
@@ -537,23 +855,44 @@ void launch_signed(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid
     else launch_instance<OutT, false, false, true>(stream, a, ncomp, grid, block);
 }
 
+// the placed instances of one output element (as launch_instance picks: source order, component count, signed taps)
+template <typename OutT, bool SGN>
+void launch_placed_sgn(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block, unsigned fill) {
+    const bool xmajor = ((a.layout & 1) == 0) != (a.orient == 2);
+    if (xmajor && ncomp == 3) hipLaunchKernelGGL((k_resize_xmajor_placed<3, OutT, SGN>), grid, block, a.lds_bytes, stream, a, fill);
+    else if (xmajor) hipLaunchKernelGGL((k_resize_xmajor_placed<1, OutT, SGN>), grid, block, a.lds_bytes, stream, a, fill);
+    else if (ncomp == 3) hipLaunchKernelGGL((k_resize_rowmajor_placed<3, OutT, SGN>), grid, block, a.lds_bytes, stream, a, fill);
+    else hipLaunchKernelGGL((k_resize_rowmajor_placed<1, OutT, SGN>), grid, block, a.lds_bytes, stream, a, fill);
+}
+template <typename OutT>
+void launch_placed(hipStream_t stream, const ResizeArgs &a, int ncomp, dim3 grid, dim3 block, unsigned fill) {
+    if (a.sgn) launch_placed_sgn<OutT, true>(stream, a, ncomp, grid, block, fill);
+    else launch_placed_sgn<OutT, false>(stream, a, ncomp, grid, block, fill);
+}
+
 }  // namespace
 
-hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp) {
+hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp, int placed, unsigned fill) {
     if (a.n_images <= 0) return hipSuccess;
     // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
     const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
     if (out_ncomp && out_ncomp != ncomp) {       // a plan that converts (mj_plan_create_resized_mode): grey to RGB, or colour to L
         if (ncomp == 1) {
-            if (a.esize == 4) launch_mode_instance<1, 3, uint32_t>(stream, a, grid, block);
-            else if (a.esize == 2) launch_mode_instance<1, 3, uint16_t>(stream, a, grid, block);
-            else launch_mode_instance<1, 3, unsigned char>(stream, a, grid, block);
+            if (a.esize == 4) launch_mode_instance<1, 3, uint32_t>(stream, a, grid, block, placed, fill);
+            else if (a.esize == 2) launch_mode_instance<1, 3, uint16_t>(stream, a, grid, block, placed, fill);
+            else launch_mode_instance<1, 3, unsigned char>(stream, a, grid, block, placed, fill);
         } else {
-            if (a.esize == 4) launch_mode_instance<3, 1, uint32_t>(stream, a, grid, block);
-            else if (a.esize == 2) launch_mode_instance<3, 1, uint16_t>(stream, a, grid, block);
-            else launch_mode_instance<3, 1, unsigned char>(stream, a, grid, block);
+            if (a.esize == 4) launch_mode_instance<3, 1, uint32_t>(stream, a, grid, block, placed, fill);
+            else if (a.esize == 2) launch_mode_instance<3, 1, uint16_t>(stream, a, grid, block, placed, fill);
+            else launch_mode_instance<3, 1, unsigned char>(stream, a, grid, block, placed, fill);
         }
+        return hipGetLastError();
+    }
+    if (placed) {       // placed plans: instances of their own, in the oriented style
+        if (a.esize == 4) launch_placed<uint32_t>(stream, a, ncomp, grid, block, fill);
+        else if (a.esize == 2) launch_placed<uint16_t>(stream, a, ncomp, grid, block, fill);
+        else launch_placed<unsigned char>(stream, a, ncomp, grid, block, fill);
         return hipGetLastError();
     }
     if (a.sgn) {        // bicubic and Lanczos plans: the signed instances
@@ -624,7 +963,7 @@ namespace {
 
 struct AxisHost {
     std::vector<int32_t> lo, cnt;
-    int ks = 0, word_off = 0;
+    int ks = 0, word_off = 0, in_size = 0;
     // the most source entries a tile of `tile` outputs needs
     int span(int tile) const {
         int m = 0;
@@ -655,19 +994,20 @@ const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean
 }
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out, int mode = 0);
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out, int mode = 0,
+                   const mj_place *places = nullptr, const uint8_t *fill = nullptr);
 
 // ... of the oriented images: the orientations checked (NULL, or all of them 1: a plan without them)
 int create_resized_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
                             const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int filter,
-                            mj_plan **out, int mode = 0) {
+                            mj_plan **out, int mode = 0, const mj_place *places = nullptr, const uint8_t *fill = nullptr) {
     bool upright = true;
     for (int i = 0; orientations && b && i < b->n_images; ++i) {
         if (orientations[i] < 1 || orientations[i] > 8)
             return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
         upright = upright && orientations[i] == 1;
     }
-    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, filter, out, mode);
+    return create_resized(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, upright ? nullptr : orientations, filter, out, mode, places, fill);
 }
 
 }  // namespace
@@ -737,6 +1077,21 @@ int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *b, const mj_roi
     return create_resized_oriented(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, orientations, filter, out, mode);
 }
 
+int mj_plan_create_resized_placed(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                  const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                  int32_t filter, int32_t mode, const mj_place *places, const uint8_t fill[3], mj_plan **out) {
+    const char *fn = "mj_plan_create_resized_placed";
+    if (!mj::resize_filter_known(filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, filter);
+    if (mode != MJ_MODE_NATIVE && mode != MJ_MODE_L && mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, mode);
+    if (mode == mj::batch_ncomp(b)) mode = MJ_MODE_NATIVE;
+    // (every image stretched over the whole canvas: the plan of mj_plan_create_resized_mode, made by the code that makes it there)
+    bool plain = true;
+    for (int i = 0; places && b && i < b->n_images && plain; ++i)
+        plain = places[i].width == out_width && places[i].height == out_height && places[i].x == 0 && places[i].y == 0;
+    return create_resized_oriented(fn, ctx, b, rois, out_width, out_height, slots, n_slots, output, orientations, filter, out, mode,
+                                   plain ? nullptr : places, fill);
+}
+
 int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
     if (!p || !out || !p->resized || p->orient_only) return MJ_ERR_INVALID;
     const mj::ResizeArgs &a = p->rz;
@@ -750,9 +1105,10 @@ int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
 namespace {
 
 int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out, int mode) {
+                   const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orient, int filter, mj_plan **out, int mode,
+                   const mj_place *places, const uint8_t *fill) {
     // (filter: a known MJ_FILTER_*; orient: NULL, or one checked orientation 1..8 per image, not all of them 1; mode: 0, or the
-    // output's component count where it is not the batch's)
+    // output's component count where it is not the batch's; places: NULL, or one per image, not all of them the whole canvas)
     // the output description first: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
     // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
     const int dtype = output ? output->dtype : MJ_DTYPE_U8;
@@ -774,6 +1130,71 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
             return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, slots[i], n_slots);
     // oriented plans: all images transposing (orientations 5..8) or none — the two read their source in different ways, so
     // they are two launches, i.e. two plans (BatchDecoder sorts the files); windows are given in oriented coordinates
+    // Placed plans: what every axis of every image needs of its source — the taps of the canvas entries the image covers reach
+    // source entries [first, first + len) of the oriented image or window (need).  Where that is less than the whole, the plan
+    // becomes a window plan of that range (derived), as if the caller had asked for it: restart segments and MCUs outside are
+    // skipped as mj_plan_create_roi skips them, and the tables are rebased to the range.
+    struct Need { int x0, nx, y0, ny, sw, sh; };      // (sw, sh: the oriented image or window the tables are made for)
+    std::vector<Need> need;
+    std::vector<mj_roi> derived;
+    if (places) {
+        if (!b->images && b->n_images > 0) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+        need.resize((size_t)b->n_images);
+        int64_t area_need = 0, area_all = 0;
+        std::map<std::vector<int>, std::pair<int, int>> spans;      // (a batch of one size and one placement: one table per axis)
+        for (int i = 0; i < b->n_images; ++i) {
+            const mj_place &pl = places[i];
+            if (pl.width < 1 || pl.height < 1 || pl.width > 65535 || pl.height > 65535 || pl.x < -65535 || pl.x > 65535 || pl.y < -65535 || pl.y > 65535)
+                return fail(ctx, MJ_ERR_INVALID, "%s: image %d: place (width=%d, height=%d, x=%d, y=%d): the size must be 1..65535, the offsets within +-65535",
+                            fn, i, pl.width, pl.height, pl.x, pl.y);
+            if (pl.x >= out_width || pl.y >= out_height || (int64_t)pl.x + pl.width <= 0 || (int64_t)pl.y + pl.height <= 0)
+                return fail(ctx, MJ_ERR_INVALID, "%s: image %d: a %d x %d image at (%d, %d) does not meet the %d x %d canvas", fn, i, pl.width, pl.height,
+                            pl.x, pl.y, out_width, out_height);
+            const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+            int W = b->images[i].width, H = b->images[i].height;
+            if (bits & 4) std::swap(W, H);
+            mj_roi r = rois ? rois[i] : mj_roi{0, 0, W, H}, tmp;
+            need[(size_t)i] = Need{0, r.width, 0, r.height, r.width, r.height};
+            // (a window the plan will refuse, or a size no table is built for: left as it is, for the code that refuses it)
+            if (W < 1 || H < 1 || W > 65535 || H > 65535 || !mj::stored_window(1, W, H, r, &tmp)) { area_all += 1; area_need += 1; continue; }
+            auto span = [&](int in_size, int resized, int off, int canvas, int *first, int *len) {
+                const std::vector<int> key{in_size, resized, off, canvas};
+                auto it = spans.find(key);
+                if (it != spans.end()) { *first = it->second.first; *len = it->second.second; return; }
+                std::vector<int32_t> lo((size_t)resized), cnt((size_t)resized);
+                const int ks = mj::resize_axis_ksize(in_size, resized, filter);
+                std::vector<int32_t> k((size_t)resized * ks);
+                mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), k.data(), ks, filter);
+                const int j0 = std::max(0, -off), j1 = std::min(resized, canvas - off) - 1;     // the resized entries on the canvas
+                *first = lo[(size_t)j0]; *len = lo[(size_t)j1] + cnt[(size_t)j1] - lo[(size_t)j0];
+                spans[key] = {*first, *len};
+            };
+            Need &nd = need[(size_t)i];
+            span(r.width, pl.width, pl.x, out_width, &nd.x0, &nd.nx);
+            span(r.height, pl.height, pl.y, out_height, &nd.y0, &nd.ny);
+            area_all += (int64_t)r.width * r.height; area_need += (int64_t)nd.nx * nd.ny;
+        }
+        // The rule: a caller's windows make a window plan anyway, and it shrinks to what is needed.  Whole images stay whole: a
+        // window plan does not take the fused launch, and for the evaluation transform of 1024 x 1080p — 44 % of the pixels
+        // needed — decoding the window took 11.1 ms (row-major) / 8.9 ms (x-major) against 6.4 / 6.2 ms for the whole images,
+        // while the placed launch itself cost the same over either (profiles/r13_place_probe.txt).  MJ_PLACE_WINDOW: 0 never,
+        // 1 whenever anything is saved (tests, probes, and crops far smaller than the one measured).
+        bool derive = rois != nullptr;
+        if (const char *e = mj::opt("MJ_PLACE_WINDOW")) derive = atoi(e) != 0;
+        if (derive && area_need < area_all) {
+            derived.resize((size_t)b->n_images);
+            for (int i = 0; i < b->n_images; ++i) {
+                const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+                const mj_roi r = rois ? rois[i] : mj_roi{0, 0, (bits & 4) ? b->images[i].height : b->images[i].width,
+                                                         (bits & 4) ? b->images[i].width : b->images[i].height};
+                const Need &nd = need[(size_t)i];
+                derived[(size_t)i] = mj_roi{r.x + nd.x0, r.y + nd.y0, nd.nx, nd.ny};
+            }
+            rois = derived.data();
+        } else {
+            for (Need &nd : need) nd.x0 = nd.y0 = 0;       // (tables over the whole image or window)
+        }
+    }
     bool swapped = false;
     std::vector<mj_roi> stored;
     if (orient) {
@@ -811,15 +1232,47 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     // (back: the table of an axis the orientation reverses — entry j is entry out_size - 1 - j of the plain table read from the
     // other end of the source, taps in reverse; the sums are integer sums of the same products, and the first source index
     // still grows with j, which is what the kernels' tile bounds assume.  The kernel stores entry j at out_size - 1 - j.)
-    auto axis = [&](std::map<int, AxisHost> &m, int in_size, int out_size, bool back = false) -> const AxisHost & {
-        const int key = 2 * in_size + (back ? 1 : 0);
+    // (placed plans: canvas entry j is entry j - off of the table in_size -> resized, whose first source indices are then
+    // counted from `base`, the first entry of the part of the source that was decoded (`len` entries).  A canvas entry outside
+    // the image has NO taps, and as first index the bound of the nearest entry inside: the bounds still grow with j, so the
+    // kernels' tile spans hold, and a count of 0 on either axis marks a fill element — an entry inside has at least one tap.
+    // The canvas table is built first and reversed after.  Tables are then per (source size, resized size, offset, reversed).)
+    std::map<std::vector<int>, int> placed_ids;
+    auto axis = [&](std::map<int, AxisHost> &m, int in_size, int out_size, bool back = false, int resized = 0, int off = 0, int base = 0,
+                    int len = 0) -> const AxisHost & {
+        int key = 2 * in_size + (back ? 1 : 0);
+        if (places) {
+            const std::vector<int> full{&m == &xs, in_size, resized, off, back, base, len};
+            auto id = placed_ids.find(full);
+            if (id == placed_ids.end()) id = placed_ids.emplace(full, (int)placed_ids.size()).first;
+            key = id->second;
+        }
         auto it = m.find(key);
         if (it != m.end()) return it->second;
         AxisHost &A = m[key];
-        A.ks = mj::resize_axis_ksize(in_size, out_size, filter);
+        A.in_size = in_size;
         A.lo.resize(out_size); A.cnt.resize(out_size);
-        std::vector<int32_t> k((size_t)out_size * A.ks);
-        mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks, filter);
+        std::vector<int32_t> k;
+        if (places) {
+            A.ks = mj::resize_axis_ksize(in_size, resized, filter);
+            std::vector<int32_t> lo((size_t)resized), cnt((size_t)resized), kk((size_t)resized * A.ks);
+            mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), kk.data(), A.ks, filter);
+            k.assign((size_t)out_size * A.ks, 0);
+            const int j0 = std::max(0, off), j1 = std::min(out_size, off + resized);       // the canvas entries inside the image
+            for (int j = 0; j < out_size; ++j) {
+                if (j < j0) { A.lo[j] = lo[(size_t)(j0 - off)] - base; A.cnt[j] = 0; }
+                else if (j >= j1) { A.lo[j] = lo[(size_t)(j1 - 1 - off)] + cnt[(size_t)(j1 - 1 - off)] - base; A.cnt[j] = 0; }
+                else {
+                    A.lo[j] = lo[(size_t)(j - off)] - base; A.cnt[j] = cnt[(size_t)(j - off)];
+                    memcpy(&k[(size_t)j * A.ks], &kk[(size_t)(j - off) * A.ks], (size_t)A.ks * sizeof(int32_t));
+                }
+            }
+            in_size = len;      // (what the reversal below counts from: the decoded part's other end)
+        } else {
+            A.ks = mj::resize_axis_ksize(in_size, out_size, filter);
+            k.resize((size_t)out_size * A.ks);
+            mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks, filter);
+        }
         for (int j = 0; j < out_size && !range_in; ++j) {
             int64_t sum = 0, big = 0, least = 0;
             for (int t = 0; t < A.ks; ++t) {
@@ -827,7 +1280,7 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
                 sum += m; big = std::max(big, m); least = std::min(least, v);
             }
             const int64_t top = ((int64_t)1 << 21) + 255 * sum;
-            if (sgn ? (big >= (1 << 23) || top > INT32_MAX) : (least < 0 || big >= (1 << 24) || top > (int64_t)UINT32_MAX)) { range_in = in_size; range_out = out_size; }
+            if (sgn ? (big >= (1 << 23) || top > INT32_MAX) : (least < 0 || big >= (1 << 24) || top > (int64_t)UINT32_MAX)) { range_in = A.in_size; range_out = places ? resized : out_size; }
         }
         if (back) {
             std::vector<int32_t> lo(A.lo), cnt(A.cnt), kk(k);
@@ -857,8 +1310,15 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         ri[i].w = w; ri[i].h = h;
         if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
         if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
-        ri[i].xtab = axis(xs, w, out_width, bits & 1).word_off;
-        ri[i].ytab = axis(ys, h, out_height, bits & 2).word_off;
+        if (places) {
+            // (w, h: what was decoded of the oriented image — the whole, the caller's window, or the derived range of either)
+            const Need &nd = need[(size_t)i];
+            ri[i].xtab = axis(xs, nd.sw, out_width, bits & 1, places[i].width, places[i].x, nd.x0, w).word_off;
+            ri[i].ytab = axis(ys, nd.sh, out_height, bits & 2, places[i].height, places[i].y, nd.y0, h).word_off;
+        } else {
+            ri[i].xtab = axis(xs, w, out_width, bits & 1).word_off;
+            ri[i].ytab = axis(ys, h, out_height, bits & 2).word_off;
+        }
         if (range_in)
             return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: resizing %d to %d with filter %d gives taps outside what the kernels' 24-bit products and 32-bit sums hold", fn,
                         range_in, range_out, filter);
@@ -904,8 +1364,13 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
         const bool cols_first = xmajor ? (tc >= 32 || tr == 1) : (seg_bytes(tc) >= 2048 || tr == 1);
         if (tc > 1 && cols_first) tc = (tc + 1) / 2;
         else if (tr > 1) tr = (tr + 1) / 2;
-        else return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds", fn,
-                         xs.rbegin()->first / 2, ys.rbegin()->first / 2, out_width, out_height);
+        else {
+            int big_w = 0, big_h = 0;
+            for (auto &kv : xs) big_w = std::max(big_w, kv.second.in_size);
+            for (auto &kv : ys) big_h = std::max(big_h, kv.second.in_size);
+            return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds", fn,
+                        big_w, big_h, out_width, out_height);
+        }
     }
     // (a small batch: more, smaller tiles, so that the chip has something to do)
     auto n_tiles = [&](int tr_, int tc_) { return (int64_t)n * ((out_height + tr_ - 1) / tr_) * ((out_width + tc_ - 1) / tc_); };
@@ -926,7 +1391,12 @@ int create_resized(const char *fn, mj_context *ctx, const mj_batch *b, const mj_
     p->rz_filter = filter;
     for (auto &kv : xs) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
     for (auto &kv : ys) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
-    if (any_mirror || orient || mode) {       // (no flag set: the instances without mirror; a plan that converts: oriented-style instances only)
+    if (places) {
+        p->rz_placed = 1;
+        const int nfill = CO;       // (one byte per output component; fill NULL: zeros)
+        for (int c = 0; c < nfill && fill; ++c) p->rz_fill |= (unsigned)fill[c] << (8 * c);
+    }
+    if (any_mirror || orient || mode || places) {       // (no flag set: the instances without mirror; a plan that converts: oriented-style instances only)
         if ((rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) != MJ_OK) return rc;
         a.mirror = p->d_rz_mirror;
     }
