@@ -76,6 +76,25 @@ __device__ __forceinline__ float group_sum8(float a) {
     return a;
 }
 
+// lane 8g's value in all eight lanes of group g, without a trip through LDS: lane 0 of each quad to its quad, then the upper
+// quad of every group (bank mask 0xA: lanes 4..7 and 12..15 of a row) takes the lower one's by the half-row mirror
+__device__ __forceinline__ int group_lane0(int v) {
+    const int q = __builtin_amdgcn_update_dpp(0, v, 0x00, 0xF, 0xF, true);
+    return __builtin_amdgcn_update_dpp(q, q, 0x141, 0xF, 0xA, false);
+}
+// m's bit of this lane ? a : b, as the VOP3 select on a lane mask held in a scalar register pair (profiles/r02_issue_rate_probe.txt:
+// 2.8 SIMD cycles at four waves per SIMD; the VOP2 form on VCC the compiler prefers takes 12-19 when several follow one another)
+__device__ __forceinline__ uint32_t select_on(uint64_t m, uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+    return r;
+}
+__device__ __forceinline__ int lane_bit(uint64_t m) {      // m's bit of this lane, 0 or 1
+    int r;
+    asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(m));
+    return r;
+}
+
 __device__ __forceinline__ int lo16(uint32_t w) { return (int)(int16_t)(w & 0xFFFFu); }
 __device__ __forceinline__ int hi16(uint32_t w) { return (int)w >> 16; }
 // int16 half of a packed pair -> float in one instruction (the sub-dword select and the sign extension ride on the convert)
@@ -586,21 +605,32 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
             ow.y = __builtin_amdgcn_perm(rb[3], rb[2], 0x05040100u);
             ow.z = __builtin_amdgcn_perm(rb[5], rb[4], 0x05040100u);
             ow.w = __builtin_amdgcn_perm(rb[7], rb[6], 0x05040100u);
-            bool flagged = real && err >= (0.5f - kTie0) - kTieA * asum;
-            if (acb != ~0ull) {                            // some group's block has no AC coefficient at all (wave-uniform test)
+            // the lanes whose row failed level 1, as a lane mask in scalar registers (what a ballot is)
+            uint64_t flagged = __ballot(real && err >= (0.5f - kTie0) - kTieA * asum);
+            // Some group's block has no AC coefficient at all: a zero BYTE in the ballot ((x - 0x01..01) & ~x & 0x80..80 is non-zero
+            // exactly when x has one).  Wave-uniform and scalar: a round without such a block pays four scalar instructions and a
+            // branch.  (`acb != ~0`, the test that stood here, is true whenever ANY row of any block is empty — nearly always —, so
+            // every round went through the DC-only code, a cross-lane read with its wait and four selects included.)
+            if (((acb - 0x0101010101010101ull) & ~acb & 0x8080808080808080ull) != 0) {
+                asm volatile("" ::: "memory");             // (a real branch: nothing of this is to be hoisted into the round)
                 // DC-only blocks need no sum: every sample is round(DC*q * T[0,0,0,0]) and T[0,0,0,0] is a hair above 1/8, so
                 // the product rounds half AWAY from zero (equal to the reference over the whole int16 range)
-                const bool dconly = ((acb >> (lane & 56)) & 0xFF) == 0;
-                const int dc = __shfl(lo16(p0), lane & 56);
+                // the lanes of the DC-only groups, scalar: one bit per byte that has any (bit 0 of the byte), widened to the byte
+                uint64_t m = acb | (acb >> 4);
+                m |= m >> 2; m |= m >> 1; m &= 0x0101010101010101ull;
+                const uint64_t dcm = ~((m << 8) - m);
+                const int dc = group_lane0(lo16(p0));
                 const int sg = dc >> 31, ad = (dc ^ sg) - sg;
                 const int vdc = ((((ad + 4) >> 3) ^ sg) - sg + shift) & 0xFFFF;
                 const uint32_t vv = (uint32_t)vdc | ((uint32_t)vdc << 16);
-                ow.x = dconly ? vv : ow.x; ow.y = dconly ? vv : ow.y; ow.z = dconly ? vv : ow.z; ow.w = dconly ? vv : ow.w;
-                flagged = flagged && !dconly;
+                // four selects in a row on one mask: as VOP2 on VCC they issue at 12-19 cycles each, on an SGPR pair at 2.8
+                // (profiles/r02_issue_rate_probe.txt)
+                ow.x = select_on(dcm, vv, ow.x); ow.y = select_on(dcm, vv, ow.y); ow.z = select_on(dcm, vv, ow.z); ow.w = select_on(dcm, vv, ow.w);
+                flagged &= ~dcm;
             }
             if (real) store_row(k, b, ow);
             if constexpr (SEAMS) {          // how the levels are used (mj_plan_idct_levels; seam-output kernels only: the tests' path)
-                uint64_t fb = __ballot(flagged);
+                uint64_t fb = flagged;
                 fb |= fb >> 4; fb |= fb >> 2; fb |= fb >> 1; fb &= 0x0101010101010101ull;       // one bit per block with a flagged row
                 const uint64_t rb8 = __ballot(real && j == 0);
                 if (lane == 0) {
@@ -610,11 +640,11 @@ __device__ __forceinline__ void strips_worker(const ReconArgs &a, const int64_t 
                 }
             }
             // ---- level 2 (about one round in eight on noisy images): the groups whose block failed do it again in fp64
-            if (__ballot(flagged) != 0) {
+            if (flagged != 0) {
 #ifdef MJ_DIAGNOSTIC
                 if (a.debug == 5 || (dm & 16)) continue;                // timing only (wrong pixels): what level 2 costs
 #endif
-                int gf = flagged ? 1 : 0;                  // any lane of my group?
+                int gf = lane_bit(flagged);                 // any lane of my group?
                 gf |= __builtin_amdgcn_update_dpp(0, gf, 0xB1, 0xF, 0xF, true);
                 gf |= __builtin_amdgcn_update_dpp(0, gf, 0x4E, 0xF, 0xF, true);
                 gf |= __builtin_amdgcn_update_dpp(0, gf, 0x141, 0xF, 0xF, true);
