@@ -372,7 +372,7 @@ hipError_t launch_planes_from_interleaved(hipStream_t stream, const DevImage *im
 // window plans of MJ_FLAG_GPU_SEGMENT batches: out[i] = full[idx[i]] — the restart segments the windows need, out of the
 // list the marker scan filled, into the list stages 0 and 1 read
 hipError_t launch_gather_segments(hipStream_t stream, const DevSegment *full, const int32_t *idx, int64_t n, DevSegment *out);
-// ---- resize.hip: decode to a fixed size
+// ---- resize.hip: decode to a fixed size (plan creation: resize_plan.hip)
 // One image of a resized plan: where its decoded pixels (the image, or its window) lie in the plan's intermediate buffer,
 // their size, its tap tables and where its out_width x out_height pixels go.
 struct DevResizeImage {
@@ -404,7 +404,7 @@ struct ResizeArgs {
     // orientations: the source is read as the other layout's kernel reads it (the stored rows are the oriented columns)
     int32_t orient;
     // 1: a filter whose taps go below zero (bicubic, Lanczos) — the signed instances; a mirror flag then travels as an
-    // oriented plan's bit 0 does (launch_signed)
+    // oriented plan's bit 0 does (launch_resize)
     int32_t sgn;
 };
 constexpr int64_t kResizeGridX = 1 << 20;      // workgroups along x of the resize launch's grid (the rest along y)
@@ -414,7 +414,7 @@ bool resize_filter_signed(int filter);
 int resize_axis_ksize(int in_size, int out_size, int filter = 0);
 void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0);
 // (out_ncomp: 0 or ncomp — the instances there were; else a plan that converts, mj_plan_create_resized_mode)
-// (placed: a plan of mj_plan_create_resized_placed — its own instances, which store `fill`, byte c in bits 8c..8c+7, where
+// (placed: a plan of mj_plan_create_resized_placed — the placed instances, which store `fill`, byte c in bits 8c..8c+7, where
 // the image does not cover the canvas; a.mirror is then set)
 hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp = 0, int placed = 0, unsigned fill = 0);
 // ---- output colour mode (tools/mode_model.py)

@@ -1,0 +1,512 @@
+// Plan creation for the resized plans (mj_plan_create_resized and its six descendants): host code only.  The tap tables'
+// arithmetic (build_resize_axis), the kernels, launch_resize and build_normalize_table are resize.hip's; this file decides what they
+// are given.  Every entry point fills a ResizeRequest, and create_resized goes through it in named steps:
+//   placed_source_ranges   placed plans: what every image's axes need of their source, and the window plan derived from that
+//   TapTables              one table per distinct axis, range-checked, reversed for orientations, serialised for the kernels
+//   choose_tile            the tile a workgroup takes and where its parts lie in LDS — a pure function of the tables and sizes
+//   output_table           the 256 x C elements a 2- or 4-byte output looks its bytes up in
+#include <math.h>
+#include <map>
+
+#include "plan.h"
+
+namespace {
+
+// What a resized plan is asked for.  filter and mode as the caller gave them (checked here); orient: NULL or one EXIF orientation
+// per image; places: NULL or one per image; fill: NULL (zeros) or one byte per output component.
+struct ResizeRequest {
+    const char *fn;       // (the entry point's name, for the messages)
+    mj_context *ctx; const mj_batch *b; const mj_roi *rois;
+    int32_t out_width, out_height;
+    const int32_t *slots; int32_t n_slots;
+    mj_plan **out;
+    const mj_output_desc *output = nullptr;
+    const uint8_t *orient = nullptr;
+    int filter = MJ_FILTER_BILINEAR, mode = MJ_MODE_NATIVE;
+    const mj_place *places = nullptr; const uint8_t *fill = nullptr;
+};
+
+struct AxisHost {
+    std::vector<int32_t> lo, cnt;
+    int ks = 0, word_off = 0, in_size = 0;
+    // the most source entries a tile of `tile` outputs needs
+    int span(int tile) const {
+        int m = 0, out = (int)lo.size();
+        for (int o0 = 0; o0 < out; o0 += tile) {
+            int hi = 0;
+            for (int o = o0; o < std::min(o0 + tile, out); ++o) hi = std::max(hi, lo[o] + cnt[o]);
+            m = std::max(m, hi - lo[o0]);
+        }
+        return m;
+    }
+};
+
+int round16(int64_t v) { return (int)((v + 15) & ~(int64_t)15); }
+int dtype_size(int dtype) { return dtype == MJ_DTYPE_U8 ? 1 : dtype == MJ_DTYPE_F32 ? 4 : 2; }
+
+// what mj_plan_create_resized_as and mj_host_normalize_table refuse: nullptr when `o` is fine, else the reason
+const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std) {
+    if (dtype != MJ_DTYPE_U8 && dtype != MJ_DTYPE_F16 && dtype != MJ_DTYPE_BF16 && dtype != MJ_DTYPE_F32) return "dtype is none of MJ_DTYPE_U8 / F16 / BF16 / F32";
+    if (!normalize) return nullptr;
+    if (dtype == MJ_DTYPE_U8) return "normalize needs a float dtype (MJ_DTYPE_U8 stores the resized bytes)";
+    for (int c = 0; c < ncomp; ++c) {
+        if (!std::isfinite(mean[c])) return "mean must be finite";
+        if (!std::isfinite(std[c]) || !(std[c] > 0.0f)) return "std must be finite and > 0";
+    }
+    return nullptr;
+}
+
+// ---- placed plans: the source ranges -------------------------------------------------------------------------------------
+// What every axis of every image needs of its source — the taps of the canvas entries the image covers reach source entries
+// [x0, x0 + nx) x [y0, y0 + ny) of the oriented image or window, whose size is sw x sh (what the tables are made for).
+struct Need { int x0, nx, y0, ny, sw, sh; };
+// In: the request, its orientations (NULL: none) and windows (NULL: whole images).  Out: `need`, one per image, and `derived` —
+// where the ranges are less than the whole and the rule below says so, the windows of those ranges, as if the caller had asked
+// for them (the plan becomes a window plan: restart segments and MCUs outside are skipped as mj_plan_create_roi skips them, and
+// the tables are rebased to the range); else empty, and every range starts at 0 (tables over the whole image or window).
+int placed_source_ranges(const ResizeRequest &q, const uint8_t *orient, const mj_roi *rois, std::vector<Need> &need, std::vector<mj_roi> &derived) {
+    const mj_batch *b = q.b;
+    if (!b->images && b->n_images > 0) return fail(q.ctx, MJ_ERR_INVALID, "%s: NULL argument", q.fn);
+    need.resize((size_t)b->n_images);
+    int64_t area_need = 0, area_all = 0;
+    std::map<std::vector<int>, std::pair<int, int>> spans;      // (a batch of one size and one placement: one table per axis)
+    // the source entries [*first, *first + *len) the canvas takes of an axis in_size -> resized at offset off
+    auto span = [&](int in_size, int resized, int off, int canvas, int *first, int *len) {
+        const std::vector<int> key{in_size, resized, off, canvas};
+        auto it = spans.find(key);
+        if (it != spans.end()) { *first = it->second.first; *len = it->second.second; return; }
+        std::vector<int32_t> lo((size_t)resized), cnt((size_t)resized);
+        const int ks = mj::resize_axis_ksize(in_size, resized, q.filter);
+        std::vector<int32_t> k((size_t)resized * ks);
+        mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), k.data(), ks, q.filter);
+        const int j0 = std::max(0, -off), j1 = std::min(resized, canvas - off) - 1;     // the resized entries on the canvas
+        *first = lo[(size_t)j0]; *len = lo[(size_t)j1] + cnt[(size_t)j1] - lo[(size_t)j0];
+        spans[key] = {*first, *len};
+    };
+    // (the oriented image, or the caller's window of it)
+    auto whole = [&](int i) {
+        const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+        int W = b->images[i].width, H = b->images[i].height;
+        if (bits & 4) std::swap(W, H);
+        return mj_roi{0, 0, W, H};
+    };
+    for (int i = 0; i < b->n_images; ++i) {
+        const mj_place &pl = q.places[i];
+        if (pl.width < 1 || pl.height < 1 || pl.width > 65535 || pl.height > 65535 || pl.x < -65535 || pl.x > 65535 || pl.y < -65535 || pl.y > 65535)
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: place (width=%d, height=%d, x=%d, y=%d): the size must be 1..65535, the offsets within +-65535",
+                        q.fn, i, pl.width, pl.height, pl.x, pl.y);
+        if (pl.x >= q.out_width || pl.y >= q.out_height || (int64_t)pl.x + pl.width <= 0 || (int64_t)pl.y + pl.height <= 0)
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: a %d x %d image at (%d, %d) does not meet the %d x %d canvas", q.fn, i, pl.width, pl.height,
+                        pl.x, pl.y, q.out_width, q.out_height);
+        const int W = whole(i).width, H = whole(i).height;
+        mj_roi r = rois ? rois[i] : whole(i), tmp;
+        Need &nd = need[(size_t)i] = Need{0, r.width, 0, r.height, r.width, r.height};
+        // (a window the plan will refuse, or a size no table is built for: left as it is, for the code that refuses it)
+        if (W < 1 || H < 1 || W > 65535 || H > 65535 || !mj::stored_window(1, W, H, r, &tmp)) { area_all += 1; area_need += 1; continue; }
+        span(r.width, pl.width, pl.x, q.out_width, &nd.x0, &nd.nx);
+        span(r.height, pl.height, pl.y, q.out_height, &nd.y0, &nd.ny);
+        area_all += (int64_t)r.width * r.height; area_need += (int64_t)nd.nx * nd.ny;
+    }
+    // The rule: a caller's windows make a window plan anyway, and it shrinks to what is needed.  Whole images stay whole: a
+    // window plan does not take the fused launch, and for the evaluation transform of 1024 x 1080p — 44 % of the pixels
+    // needed — decoding the window took 11.1 ms (row-major) / 8.9 ms (x-major) against 6.4 / 6.2 ms for the whole images,
+    // while the placed launch itself cost the same over either (profiles/r13_place_probe.txt).  MJ_PLACE_WINDOW: 0 never,
+    // 1 whenever anything is saved (tests, probes, and crops far smaller than the one measured).
+    bool derive = rois != nullptr;
+    if (const char *e = mj::opt("MJ_PLACE_WINDOW")) derive = atoi(e) != 0;
+    if (derive && area_need < area_all) {
+        derived.resize((size_t)b->n_images);
+        for (int i = 0; i < b->n_images; ++i) {
+            const mj_roi r = rois ? rois[i] : whole(i);
+            const Need &nd = need[(size_t)i];
+            derived[(size_t)i] = mj_roi{r.x + nd.x0, r.y + nd.y0, nd.nx, nd.ny};
+        }
+    } else {
+        for (Need &nd : need) nd.x0 = nd.y0 = 0;
+    }
+    return MJ_OK;
+}
+
+// ---- tap tables: one per distinct axis --------------------------------------------------------------------------------------
+// Where an axis lies on a placed plan's canvas: resized to `resized` entries at offset `off`; `base` is the first source entry of
+// the part of the source that was decoded, `len` that part's entries.
+struct AxisPlace { int resized, off, base, len; };
+
+// Owns the tables of a plan (xs, ys: the AxisHost records the tile search reads), their serialised form for the kernels (words: per
+// table ksize, first source index [out], tap count [out], taps [out][ksize]), the maps that make equal axes share a table, and the
+// range check.
+struct TapTables {
+    const int filter;
+    const bool placed, sgn;
+    std::map<int, AxisHost> xs, ys;
+    std::vector<int32_t> words;
+    // What the kernels' arithmetic holds (resize.hip: Tap): a 24-bit multiply and a 32-bit sum — signed for the filters with side
+    // lobes.  Measured over sizes 1..129 the taps stay far inside (tests/test_resample_host.py); that is no proof for every
+    // size, so every table is checked and one that breaks a bound is recorded here (its sizes; 0: none) for the caller to refuse.
+    int range_in = 0, range_out = 0;
+
+    TapTables(int filter_, bool placed_) : filter(filter_), placed(placed_), sgn(mj::resize_filter_signed(filter_)) {}
+
+    // The table of one axis in_size -> out_size, built once per distinct key.
+    // back: the table of an axis the orientation reverses — entry j is entry out_size - 1 - j of the plain table read from the
+    // other end of the source, taps in reverse; the sums are integer sums of the same products, and the first source index
+    // still grows with j, which is what the kernels' tile bounds assume.  The kernel stores entry j at out_size - 1 - j.
+    // at (placed plans, else NULL): canvas entry j is entry j - off of the table in_size -> resized, whose first source indices are
+    // then counted from `base`.  A canvas entry outside the image has NO taps, and as first index the bound of the nearest entry
+    // inside: the bounds still grow with j, so the kernels' tile spans hold, and a count of 0 on either axis marks a fill element —
+    // an entry inside has at least one tap.  The canvas table is built first and reversed after.  Tables are then per (source
+    // size, resized size, offset, reversed).
+    const AxisHost &axis(bool is_x, int in_size, int out_size, bool back, const AxisPlace *at) {
+        std::map<int, AxisHost> &m = is_x ? xs : ys;
+        int key = 2 * in_size + (back ? 1 : 0);
+        if (placed) {
+            const std::vector<int> full{is_x, in_size, at->resized, at->off, back, at->base, at->len};
+            auto id = placed_ids.find(full);
+            if (id == placed_ids.end()) id = placed_ids.emplace(full, (int)placed_ids.size()).first;
+            key = id->second;
+        }
+        auto it = m.find(key);
+        if (it != m.end()) return it->second;
+        AxisHost &A = m[key];
+        A.in_size = in_size;
+        A.lo.resize(out_size); A.cnt.resize(out_size);
+        std::vector<int32_t> k;
+        if (placed) {
+            const int resized = at->resized, off = at->off, base = at->base;
+            A.ks = mj::resize_axis_ksize(in_size, resized, filter);
+            std::vector<int32_t> lo((size_t)resized), cnt((size_t)resized), kk((size_t)resized * A.ks);
+            mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), kk.data(), A.ks, filter);
+            k.assign((size_t)out_size * A.ks, 0);
+            const int j0 = std::max(0, off), j1 = std::min(out_size, off + resized);       // the canvas entries inside the image
+            for (int j = 0; j < out_size; ++j) {
+                if (j < j0) { A.lo[j] = lo[(size_t)(j0 - off)] - base; A.cnt[j] = 0; }
+                else if (j >= j1) { A.lo[j] = lo[(size_t)(j1 - 1 - off)] + cnt[(size_t)(j1 - 1 - off)] - base; A.cnt[j] = 0; }
+                else {
+                    A.lo[j] = lo[(size_t)(j - off)] - base; A.cnt[j] = cnt[(size_t)(j - off)];
+                    memcpy(&k[(size_t)j * A.ks], &kk[(size_t)(j - off) * A.ks], (size_t)A.ks * sizeof(int32_t));
+                }
+            }
+            in_size = at->len;      // (what the reversal below counts from: the decoded part's other end)
+        } else {
+            A.ks = mj::resize_axis_ksize(in_size, out_size, filter);
+            k.resize((size_t)out_size * A.ks);
+            mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks, filter);
+        }
+        for (int j = 0; j < out_size && !range_in; ++j) {
+            int64_t sum = 0, big = 0, least = 0;
+            for (int t = 0; t < A.ks; ++t) {
+                const int64_t v = k[(size_t)j * A.ks + t], mag = v < 0 ? -v : v;
+                sum += mag; big = std::max(big, mag); least = std::min(least, v);
+            }
+            const int64_t top = ((int64_t)1 << 21) + 255 * sum;
+            if (sgn ? (big >= (1 << 23) || top > INT32_MAX) : (least < 0 || big >= (1 << 24) || top > (int64_t)UINT32_MAX)) { range_in = A.in_size; range_out = placed ? at->resized : out_size; }
+        }
+        if (back) {
+            std::vector<int32_t> lo(A.lo), cnt(A.cnt), kk(k);
+            for (int j = 0; j < out_size; ++j) {
+                const int s = out_size - 1 - j;
+                A.lo[j] = in_size - lo[s] - cnt[s]; A.cnt[j] = cnt[s];
+                for (int t = 0; t < A.ks; ++t) k[(size_t)j * A.ks + t] = t < cnt[s] ? kk[(size_t)s * A.ks + cnt[s] - 1 - t] : 0;
+            }
+        }
+        A.word_off = (int)words.size();
+        words.push_back(A.ks);
+        words.insert(words.end(), A.lo.begin(), A.lo.end());
+        words.insert(words.end(), A.cnt.begin(), A.cnt.end());
+        words.insert(words.end(), k.begin(), k.end());
+        return A;
+    }
+
+private:
+    std::map<std::vector<int>, int> placed_ids;
+};
+
+// ---- the tile ----------------------------------------------------------------------------------------------------------------
+// A tile of tr rows x tc columns: what it takes in LDS and where the parts lie (ok false: it does not fit)
+struct Lds { bool ok; int tr, tc, t_pitch, tab_off, stage_off, stage_bytes, lut_off, total; };
+// How the plan's kernels use LDS.  xmajor: how the source is read, which for transposing orientations is the other layout's way
+// (launch_resize); C: the source's components; CT: those of both passes and of T; converts: a plan of k_resize_*_mode; lut_bytes:
+// the output table of a 2- or 4-byte element.
+struct TileUse { bool xmajor; int C, CT; bool converts; int lut_bytes; };
+
+// The tile: what a workgroup's LDS holds (resize.hip's kernels) must fit 64 KB — the intermediate rows of the tile, the tile's tap
+// tables, the staging rows, the output table of a 2- or 4-byte element — for every source size of the batch.
+Lds lds_for(const TapTables &tabs, const TileUse &u, int tr, int tc) {
+    const int budget = 64 * 1024;
+    int sy = 0, sx = 0, ksx = 0, ksy = 0, pitch;
+    for (auto &kv : tabs.ys) { sy = std::max(sy, kv.second.span(tr)); ksy = std::max(ksy, kv.second.ks); }
+    for (auto &kv : tabs.xs) { sx = std::max(sx, kv.second.span(tc)); ksx = std::max(ksx, kv.second.ks); }
+    int64_t t_bytes, tab_bytes, stage = 0;
+    if (u.xmajor) {
+        pitch = round16((int64_t)sy * u.CT);
+        t_bytes = (int64_t)tc * pitch;
+        tab_bytes = ((int64_t)2 * tr + (int64_t)tr * ksy) * 4;
+    } else {
+        pitch = round16((int64_t)tc * u.CT);
+        t_bytes = (int64_t)sy * pitch;
+        tab_bytes = ((int64_t)2 * tc + (int64_t)tc * ksx) * 4;
+        // (colour to L: three quarters for the staged colour row — 3 * (sx + 16) >= 3 * sx + 32 —, one for its L bytes)
+        stage = u.converts && u.C == 3 ? 4 * (int64_t)round16((int64_t)sx + 16) : round16((int64_t)sx * u.C + 32);
+    }
+    // (grey to RGB: the tile of finished bytes behind the output table)
+    const int64_t lut_off = t_bytes + round16(tab_bytes) + 4 * stage, total = lut_off + u.lut_bytes + (u.converts && u.C == 1 ? (int64_t)tr * tc : 0);
+    if (total > budget) return Lds{false, tr, tc, 0, 0, 0, 0, 0, 0};
+    return Lds{true, tr, tc, pitch, (int)t_bytes, (int)(t_bytes + round16(tab_bytes)), (int)stage, (int)lut_off, (int)total};
+}
+
+// A pure function of the tables, the use and the sizes (n images of out_width x out_height).  Tiles shrink until they fit: a
+// row-major plan gives up columns first while a row segment stays 2 KB long (its loads run along the rows), then rows; an x-major
+// plan keeps its rows (its loads run along the columns) and gives up columns.  ok false: not even a 1 x 1 tile fits.
+Lds choose_tile(const TapTables &tabs, const TileUse &u, int n, int out_width, int out_height) {
+    int tr = std::min<int>(u.xmajor ? 32 : 16, out_height), tc = out_width;
+    auto fits = [&](int tr_, int tc_) { return lds_for(tabs, u, tr_, tc_).ok; };
+    auto seg_bytes = [&](int tc_) { int sx = 0; for (auto &kv : tabs.xs) sx = std::max(sx, kv.second.span(tc_)); return sx * u.C; };
+    while (!fits(tr, tc)) {
+        const bool cols_first = u.xmajor ? (tc >= 32 || tr == 1) : (seg_bytes(tc) >= 2048 || tr == 1);
+        if (tc > 1 && cols_first) tc = (tc + 1) / 2;
+        else if (tr > 1) tr = (tr + 1) / 2;
+        else return lds_for(tabs, u, 1, 1);
+    }
+    // (a small batch: more, smaller tiles, so that the chip has something to do)
+    auto n_tiles = [&](int tr_, int tc_) { return (int64_t)n * ((out_height + tr_ - 1) / tr_) * ((out_width + tc_ - 1) / tc_); };
+    while (n_tiles(tr, tc) < 1024 && tr > 4 && fits((tr + 1) / 2, tc)) tr = (tr + 1) / 2;
+    return lds_for(tabs, u, tr, tc);
+}
+
+// ---- the output table, [CO][256] elements of esize bytes: the host's arithmetic, which the kernels only look up ----------------
+std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize) {
+    const bool norm = o.normalize != 0;
+    std::vector<uint8_t> lut((size_t)256 * CO * esize);
+    for (int c = 0; c < CO; ++c) {
+        uint32_t bits[256];
+        mj::build_normalize_table(o.dtype, norm ? o.mean[c] : 0.0f, norm ? o.std[c] : 1.0f, bits);
+        for (int v = 0; v < 256; ++v) {
+            if (esize == 4) memcpy(&lut[((size_t)c * 256 + v) * 4], &bits[v], 4);
+            else { const uint16_t h = (uint16_t)bits[v]; memcpy(&lut[((size_t)c * 256 + v) * 2], &h, 2); }
+        }
+    }
+    return lut;
+}
+
+// ---- the plan: every entry point's name and arguments in a request (what one does not take keeps the request's default) ----------
+int create_resized(const ResizeRequest &q) {
+    auto [fn, ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter, asked_mode, asked_places, fill] = q;
+    if (!mj::resize_filter_known(filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, filter);
+    if (asked_mode != MJ_MODE_NATIVE && asked_mode != MJ_MODE_L && asked_mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, asked_mode);
+    // (the files' own count: the plan of mj_plan_create_resized_filtered, made by the code that makes it there.  mode: 0, or CO)
+    const int mode = asked_mode == mj::batch_ncomp(b) ? MJ_MODE_NATIVE : asked_mode;
+    // (every image stretched over the whole canvas: the plan of mj_plan_create_resized_mode, likewise.  places: NULL, or not all so)
+    bool stretched = true;
+    for (int i = 0; asked_places && b && i < b->n_images && stretched; ++i)
+        stretched = asked_places[i].width == out_width && asked_places[i].height == out_height && asked_places[i].x == 0 && asked_places[i].y == 0;
+    const mj_place *places = stretched ? nullptr : asked_places;
+    // the orientations checked (NULL, or all of them 1: a plan without them.  orient: NULL, or 1..8 per image, not all of them 1)
+    bool upright = true;
+    for (int i = 0; orientations && b && i < b->n_images; ++i) {
+        if (orientations[i] < 1 || orientations[i] > 8) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
+        upright = upright && orientations[i] == 1;
+    }
+    const uint8_t *orient = upright ? nullptr : orientations;
+    // the output description: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
+    // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
+    const int dtype = output ? output->dtype : MJ_DTYPE_U8;
+    if (output)
+        if (const char *why = output_fault(dtype, output->normalize != 0, mode ? mode : mj::batch_ncomp(b), output->mean, output->std))
+            return fail(ctx, MJ_ERR_INVALID, "%s: output: %s", fn, why);
+    if (!ctx) return MJ_ERR_INVALID;
+    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+    *out = nullptr;
+    const int esize = dtype_size(dtype);
+    if (out_width < 1 || out_height < 1 || out_width > 65535 || out_height > 65535)
+        return fail(ctx, MJ_ERR_INVALID, "%s: output size %d x %d (both must be 1..65535)", fn, out_width, out_height);
+    if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
+        return fail(ctx, MJ_ERR_INVALID, "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none", fn);
+    if (!slots) n_slots = b->n_images;
+    for (int i = 0; slots && i < b->n_images; ++i)
+        if (slots[i] < 0 || slots[i] >= n_slots)
+            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, slots[i], n_slots);
+    std::vector<Need> need;
+    std::vector<mj_roi> derived;
+    if (places) {
+        if (int rc = placed_source_ranges(q, orient, rois, need, derived)) return rc;
+        if (!derived.empty()) rois = derived.data();
+    }
+    // oriented plans: all images transposing (orientations 5..8) or none — the two read their source in different ways, so
+    // they are two launches, i.e. two plans (BatchDecoder sorts the files); windows are given in oriented coordinates
+    bool swapped = false;
+    std::vector<mj_roi> stored;
+    if (orient) {
+        if (!b->images) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+        swapped = b->n_images > 0 && (mj::orient_bits(orient[0]) & 4);
+        for (int i = 0; i < b->n_images; ++i)
+            if (((mj::orient_bits(orient[i]) & 4) != 0) != swapped)
+                return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: orientations that exchange width and height (5..8) and others do not share a resized plan; split the batch", fn, i);
+        if (rois) {
+            stored.resize((size_t)b->n_images);
+            for (int i = 0; i < b->n_images; ++i)
+                if (!mj::stored_window(orient[i], b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
+                    return fail(ctx, MJ_ERR_INVALID, "%s: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image", fn,
+                                i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+            rois = stored.data();
+        }
+    }
+    mj_plan *p = nullptr;
+    // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
+    if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
+    struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
+    // C: the source's components.  A plan that converts stores CO of them per pixel and runs both passes, and T, on CT = 1:
+    // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
+    const int C = p->ncomp, n = p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
+    if (mode) p->out_ncomp = CO;
+    const int64_t out_image = (int64_t)out_width * out_height * CO * esize;      // bytes
+    TapTables tabs(filter, places != nullptr);
+    std::vector<mj::DevResizeImage> ri((size_t)n);
+    std::vector<uint8_t> flags((size_t)n, 0);      // mirror, per image
+    int any_mirror = 0;
+    for (int i = 0; i < n; ++i) {
+        int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
+        const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+        if (bits & 4) std::swap(w, h);      // (from here on the oriented image's size)
+        ri[i].src_off = p->h_images[i].rgb_off;
+        ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
+        if (mode) p->h_out_off.push_back(ri[i].dst_off);
+        ri[i].w = w; ri[i].h = h;
+        if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
+        if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
+        if (places) {
+            // (w, h: what was decoded of the oriented image — the whole, the caller's window, or the derived range of either)
+            const Need &nd = need[(size_t)i];
+            const AxisPlace px{places[i].width, places[i].x, nd.x0, w}, py{places[i].height, places[i].y, nd.y0, h};
+            ri[i].xtab = tabs.axis(true, nd.sw, out_width, bits & 1, &px).word_off;
+            ri[i].ytab = tabs.axis(false, nd.sh, out_height, bits & 2, &py).word_off;
+        } else {
+            ri[i].xtab = tabs.axis(true, w, out_width, bits & 1, nullptr).word_off;
+            ri[i].ytab = tabs.axis(false, h, out_height, bits & 2, nullptr).word_off;
+        }
+        if (tabs.range_in)
+            return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: resizing %d to %d with filter %d gives taps outside what the kernels' 24-bit products and 32-bit sums hold", fn,
+                        tabs.range_in, tabs.range_out, filter);
+        if (tabs.words.size() > ((size_t)1 << 28)) return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: the tap tables of this batch are too large", fn);
+    }
+    const int lut_bytes = esize > 1 ? 256 * CO * esize : 0;
+    const TileUse use{((p->layout & 1) == 0) != swapped, C, CT, mode != 0, lut_bytes};
+    const Lds lds = choose_tile(tabs, use, n, out_width, out_height);
+    if (!lds.ok) {
+        int big_w = 0, big_h = 0;
+        for (auto &kv : tabs.xs) big_w = std::max(big_w, kv.second.in_size);
+        for (auto &kv : tabs.ys) big_h = std::max(big_h, kv.second.in_size);
+        return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: shrinking %d x %d sources to %d x %d takes more taps per pixel than a workgroup's LDS holds", fn,
+                    big_w, big_h, out_width, out_height);
+    }
+    mj::ResizeArgs &a = p->rz = mj::ResizeArgs{};
+    a.tr = lds.tr; a.tc = lds.tc;
+    a.t_pitch = lds.t_pitch; a.tab_off = lds.tab_off; a.stage_off = lds.stage_off; a.stage_bytes = lds.stage_bytes; a.lds_bytes = lds.total;
+    a.esize = esize; a.lut_off = lds.lut_off;
+    a.tiles_x = (out_width + a.tc - 1) / a.tc; a.tiles_y = (out_height + a.tr - 1) / a.tr;
+    const int64_t n_tiles = (int64_t)n * a.tiles_y * a.tiles_x;
+    if (n_tiles > mj::kResizeGridX * (int64_t)65535)
+        return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: %lld tiles are more than one launch takes; split the batch", fn, (long long)n_tiles);
+    a.n_images = n; a.ow = out_width; a.oh = out_height; a.layout = p->layout;
+    if (int rc = upload(ctx, &p->d_rz_images, ri.data(), ri.size())) return rc;
+    if (int rc = upload(ctx, &p->d_rz_tabs, tabs.words.data(), tabs.words.size())) return rc;
+    a.orient = orient ? (swapped ? 2 : 1) : 0;
+    a.sgn = tabs.sgn ? 1 : 0;
+    p->rz_filter = filter;
+    for (auto &kv : tabs.xs) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
+    for (auto &kv : tabs.ys) p->rz_max_ksize = std::max(p->rz_max_ksize, kv.second.ks);
+    if (places) {
+        p->rz_placed = 1;
+        for (int c = 0; c < CO && fill; ++c) p->rz_fill |= (unsigned)fill[c] << (8 * c);       // (one byte per output component; fill NULL: zeros)
+    }
+    if (any_mirror || orient || mode || places) {       // (no flag set: the instances without mirror; a plan that converts: oriented-style instances only)
+        if (int rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) return rc;
+        a.mirror = p->d_rz_mirror;
+    }
+    if (esize > 1) {
+        const std::vector<uint8_t> lut = output_table(*output, CO, esize);
+        if (int rc = upload(ctx, &p->d_rz_lut, lut.data(), lut.size())) return rc;
+        a.lut = p->d_rz_lut;
+    }
+    // the un-resized pixels: a plan-owned buffer from the context's cache (64 bytes of slack: the kernels' 16-byte loads may
+    // start before and end behind the bytes they use)
+    p->src_bytes = p->info.rgb_bytes;
+    MJ_HIP(ctx, ctx->cache.get((void **)&p->d_src, (size_t)p->src_bytes + 64));
+    a.images = p->d_rz_images; a.tabs = p->d_rz_tabs; a.src = p->d_src;
+    p->info.rgb_bytes = (int64_t)n_slots * out_image;
+    p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
+    p->resized = true;
+    guard.p = nullptr;
+    *out = p;
+    return MJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
+                                  int32_t taps_stride, int32_t *ksize_out) {
+    if (!mj::resize_filter_known(filter) || in_size < 1 || out_size < 1 || in_size > 65535 || out_size > 65535) return MJ_ERR_INVALID;
+    const int ks = mj::resize_axis_ksize(in_size, out_size, filter);
+    if (ksize_out) *ksize_out = ks;
+    if (!xmin && !count && !taps) return MJ_OK;
+    if (!xmin || !count || !taps || taps_stride < ks) return MJ_ERR_INVALID;
+    mj::build_resize_axis(in_size, out_size, xmin, count, taps, taps_stride, filter);
+    return MJ_OK;
+}
+
+int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps, int32_t taps_stride, int32_t *ksize_out) {
+    return mj_host_resize_table_filtered(MJ_FILTER_BILINEAR, in_size, out_size, xmin, count, taps, taps_stride, ksize_out);
+}
+
+int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
+    if (!out || dtype == MJ_DTYPE_U8 || output_fault(dtype, true, 1, &mean, &std)) return MJ_ERR_INVALID;
+    uint32_t bits[256];
+    mj::build_normalize_table(dtype, mean, std, bits);
+    for (int v = 0; v < 256; ++v) {
+        if (dtype == MJ_DTYPE_F32) static_cast<uint32_t *>(out)[v] = bits[v];
+        else static_cast<uint16_t *>(out)[v] = (uint16_t)bits[v];
+    }
+    return MJ_OK;
+}
+
+int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                           const int32_t *slots, int32_t n_slots, mj_plan **out) {
+    return create_resized({"mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, out});
+}
+
+int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                              const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
+    return create_resized({"mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, out, output});
+}
+
+int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, mj_plan **out) {
+    return create_resized({"mj_plan_create_resized_oriented", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations});
+}
+
+int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int32_t filter, mj_plan **out) {
+    return create_resized({"mj_plan_create_resized_filtered", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter});
+}
+
+int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int32_t filter, int32_t mode, mj_plan **out) {
+    return create_resized({"mj_plan_create_resized_mode", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter, mode});
+}
+
+int mj_plan_create_resized_placed(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
+                                  const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
+                                  int32_t filter, int32_t mode, const mj_place *places, const uint8_t fill[3], mj_plan **out) {
+    return create_resized({"mj_plan_create_resized_placed", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter, mode, places, fill});
+}
+
+int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
+    if (!p || !out || !p->resized || p->orient_only) return MJ_ERR_INVALID;
+    const mj::ResizeArgs &a = p->rz;
+    const int32_t v[8] = {a.tr, a.tc, a.tiles_x, a.tiles_y, a.lds_bytes, p->rz_filter, a.sgn, p->rz_max_ksize};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return MJ_OK;
+}
+
+}  // extern "C"

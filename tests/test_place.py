@@ -335,3 +335,65 @@ def test_nothing_moved_and_refusals(fixtures):
             dec.decode(raws, size=size, resize_to=(8, 8), place=[None, (0, -8), None, None])
     finally:
         dec.close()
+
+
+@pytest.fixture(scope="module")
+def squares():
+    """One 64 x 64 grey and one 64 x 64 colour golden file: (raw, oracle pixels)."""
+    raws = [(GOLDEN / "files" / name).read_bytes() for name in ("64x64_grey_pil.jpg", "64x64_420_pil.jpg")]
+    fulls = oracle_rgb_all(raws)
+    assert fulls[0].shape == (64, 64) and fulls[1].shape == (64, 64, 3)
+    return list(zip(("grey", "colour"), raws, fulls))
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("filter", ["bilinear", "bicubic"])
+@pytest.mark.parametrize("dtype", ["uint8", "float16", "float32"])
+@pytest.mark.parametrize("kind", ["native", "mode"])
+def test_every_placed_instance_once(squares, kind, dtype, filter, layout):
+    """Every placed instance of the four resize kernels — {native, converting} x {1-, 2-, 4-byte elements} x {unsigned, signed taps}
+    x {grey, colour source} x both source orders, planar or not — on one small plan each: two copies of a 64 x 64 file resized to
+    28 x 28 at (-3, 5) of a 40 x 24 canvas, the second one mirrored, float outputs normalised.  Asserted from the plan's reported
+    shape: along the height there is a tile that is wholly fill (rows above 5), one that straddles the image's edge, and tiles
+    wholly inside its rows; a tile is as wide as the 40-column canvas, so every tile that meets the image also straddles its right
+    edge (columns 25..39 are fill).  Bit-exact against tools/place_model.py over the oracle's pixels, flipped with the padding for
+    the mirrored copy, then tools/normalize_model.py; the output buffer holds a sentinel first."""
+    import torch
+    from tools import mode_model, normalize_model
+    from pyjpegdecoder_amd import BatchDecoder
+    from pyjpegdecoder_amd import _binding as B
+    from pyjpegdecoder_amd.batch import prepare_batch
+    canvas, pl, flags = (40, 24), (28, 28, -3, 5), [0, 1]
+    dec = BatchDecoder(device=0, layout=layout)
+    try:
+        for name, raw, full in squares:
+            mode = None if kind == "native" else "RGB" if name == "grey" else "L"
+            rm = mode_model.convert(rowmajor_window(full, whole(full)), mode)
+            nc = 3 if rm.ndim == 3 else 1
+            fill = (114, 7, 200) if nc == 3 else (99,)
+            mean, std = (MEAN, STD) if nc == 3 else (MEAN[:1], STD[:1])
+            prep = prepare_batch([raw, raw], dec.layout, 0)
+            plan = B.Plan(dec.ctx, prep.to_c(), {"prep": prep, "n_images": 2}, size=canvas, filter=filter, mode=mode, places=[pl, pl], fill=fill,
+                          output=("uint8", None, None, flags) if dtype == "uint8" else (dtype, mean, std, flags))
+            try:
+                shape = plan.resize_shape()
+                tr = shape["tile_rows"]
+                assert shape["signed"] == (filter == "bicubic") and shape["tiles_y"] > 2, shape
+                assert tr <= pl[3], "the first tile is wholly fill"
+                assert pl[3] % tr != 0, "a tile straddles the image's upper edge"
+                assert (pl[3] + tr - 1) // tr * tr + tr <= canvas[1], "a tile lies wholly inside the image's rows"
+                out = torch.full((int(plan.info.rgb_bytes),), 0xA5, dtype=torch.uint8, device=torch.device("cuda", dec.ctx.device))
+                plan.execute(0, out.data_ptr())
+                plan.sync()
+                assert not plan.read(rgb=False)["status"].any()
+                got = out.cpu().numpy()
+            finally:
+                plan.close()
+            placed = model((name, mode), rm, pl, canvas, fill if nc == 3 else fill[0], filter)
+            for i in range(2):
+                img = placed[:, ::-1] if flags[i] else placed
+                want = as_layout(img if dtype == "uint8" else normalize_model.normalize(img, dtype, mean if nc == 3 else mean[0], std if nc == 3 else std[0]), layout)
+                per = want.size * want.dtype.itemsize
+                assert np.array_equal(got[i * per:(i + 1) * per].view(want.dtype).reshape(want.shape), want), (name, mode, i)
+    finally:
+        dec.close()
