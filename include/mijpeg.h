@@ -443,6 +443,25 @@ int mj_plan_fill_source(mj_plan *plan, int byte_value);
  * runs the signed instances, the most taps one pixel has along an axis }.  MJ_ERR_INVALID: not a resized plan. */
 int mj_debug_resize_shape(const mj_plan *plan, int32_t out[8]);
 
+/* Test hook (host only, reads fields): what plan creation decided, MJ_DEBUG_PLAN_SHAPE_WORDS values in this order —
+ *   0 mj_plan_stage1_form's word, 1 fused launch, 2 table slots per image, 3 restart segments, 4 marker-scan jobs;
+ *   5 chunk bytes of the synchronisation form, 6 its chunks, 7 stage-0 pieces, 8 index bits and 9 bytes per table of the resolved
+ *   counting tables (0: classic rounds), 10 / 11 tables per workgroup of the lane launch's / the counting rounds' lists (0: none),
+ *   12 segment order (0 blob, 1 binned, 2 striped);
+ *   13 / 14 resolved AC / DC tables, 15..18 index bits per LDS slot and 19 bytes of a fused launch's AC tables;
+ *   20 images per workgroup, 21 passes, 22 producers, 23 lanes per producer, 24 consumers, 25 segments dealt out by length,
+ *   26 workgroups of such a launch, 27 restart segments per image of a fused launch;
+ *   28 strips per stage-2 job, 29 jobs per ticket, 30 jobs of image 0, 31 jobs in all (low word);
+ *   32 the plan works on a padded copy of the caller's device blob;
+ *   33 progressive: stage-0 stream read, 34 band pipeline, 35 its launches, 36 segments of split scans, 37 first scans in chunks.
+ * cap: room in out, at least MJ_DEBUG_PLAN_SHAPE_WORDS (MJ_ERR_INVALID otherwise). */
+#define MJ_DEBUG_PLAN_SHAPE_WORDS 38
+int mj_debug_plan_shape(const mj_plan *plan, int32_t *out, int32_t cap);
+
+/* Test hook (host only): the context's device buffer cache — out = { blocks handed out now, their bytes, requests made so far,
+ * a running hash of the requested sizes in order (h = h * 0x100000001b3 + bytes per request) }. */
+int mj_debug_cache_stats(const mj_context *ctx, uint64_t out[4]);
+
 /* ---- one-shot conveniences ----------------------------------------------------------------------- */
 /* create + execute + sync + read + destroy; rgb_out/status_out host, coef_out may be NULL. */
 int mj_decode_baseline_batch(mj_context *ctx, const mj_batch *batch, uint8_t *rgb_out, int16_t *coef_out,

@@ -47,9 +47,11 @@ EXPORTS = (
     "mj_plan_create_resized_filtered", "mj_host_resize_table_filtered", "mj_debug_resize_shape",
     "mj_plan_create_resized_mode", "mj_plan_create_mode", "mj_host_convert_mode",
     "mj_plan_create_resized_placed",
+    "mj_debug_plan_shape", "mj_debug_cache_stats",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
+PLAN_SHAPE_WORDS = 38       # MJ_DEBUG_PLAN_SHAPE_WORDS
 
 
 class HuffSpecC(ctypes.Structure):
@@ -162,6 +164,8 @@ def load_library():
     L.mj_host_convert_mode.argtypes = [i32, vp, i32, i64, vp]
     L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_debug_resize_shape.argtypes = [vp, ctypes.POINTER(i32)]
+    L.mj_debug_plan_shape.argtypes = [vp, ctypes.POINTER(i32), i32]
+    L.mj_debug_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.mj_host_exif_orientations.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.mj_host_normalize_table.argtypes = [i32, ctypes.c_float, ctypes.c_float, vp]
     L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
@@ -431,6 +435,12 @@ class Context:
         ``torch.cuda.Event.cuda_event``) has happened."""
         self.check(self.lib.mj_context_wait_event(self.handle, hip_event))
 
+    def cache_stats(self):
+        """mj_debug_cache_stats: (blocks handed out now, their bytes, requests so far, running hash of the requested sizes)."""
+        out = (ctypes.c_uint64 * 4)()
+        self.check(self.lib.mj_debug_cache_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def copy_rate_gbs(self, nbytes: int = 1 << 31, iters: int = 5) -> float:
         """mj_device_copy_rate: GB/s (read + written) of a plain 16-bytes-per-lane device copy of `nbytes`."""
         ms = ctypes.c_float()
@@ -605,6 +615,12 @@ class Plan:
         d = dict(zip(("tile_rows", "tile_cols", "tiles_x", "tiles_y", "lds_bytes", "filter", "signed", "max_ksize"), (int(v) for v in out)))
         d["signed"] = bool(d["signed"])
         return d
+
+    def shape(self) -> list:
+        """mj_debug_plan_shape: what plan creation decided, in the order include/mijpeg.h documents."""
+        out = (ctypes.c_int32 * PLAN_SHAPE_WORDS)()
+        self.ctx.check(self.ctx.lib.mj_debug_plan_shape(self.handle, out, PLAN_SHAPE_WORDS))
+        return [int(v) for v in out]
 
     def time_resize(self, iters: int = 10, rgb_device: int = 0):
         """(ms per resize launch, bytes of un-resized pixels it reads) of a resized plan that has been executed."""

@@ -27,6 +27,28 @@ void build_idct_tt(double *tt) {
                 }
 }
 
+// `warm` launches, then `iters` of them between two events on stream s: *ms_out = ms per launch.  The events go on every way out.
+template <class F>
+static int time_launches(mj_context *ctx, hipStream_t s, int warm, int iters, F &&launch, float *ms_out) {
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    MJ_HIP(ctx, hipEventCreate(&ev.a));
+    MJ_HIP(ctx, hipEventCreate(&ev.b));
+    int rc = MJ_OK;
+    for (int i = 0; i < warm && rc == MJ_OK; ++i) rc = launch();
+    if (rc != MJ_OK) return rc;
+    MJ_HIP(ctx, hipEventRecord(ev.a, s));
+    for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = launch();
+    MJ_HIP(ctx, hipEventRecord(ev.b, s));
+    MJ_HIP(ctx, hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    MJ_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+    *ms_out = ms / iters;
+    return rc;
+}
+
 extern "C" {
 
 int mj_version(void) { return MJ_VERSION; }
@@ -105,10 +127,7 @@ void mj_plan_destroy(mj_plan *p) {
         else (void)hipHostFree(p->arena.base);
     }
     if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
-    void *ptrs[] = {p->d_blob_owned, p->d_segs, p->d_images, p->d_huff, p->d_lut11, p->d_lut13, p->d_lut12, p->d_by_length, p->d_holder, p->d_xwords, p->d_wg_tabs_lanes, p->d_wg_tabs_count, p->d_stream, p->d_seg_bits, p->d_jobs, p->d_lut11u, p->d_acsegs, p->d_pc_chunks, p->d_pc_tabs, p->d_pc_exit, p->d_pc_outs, p->d_pc_items, p->d_pc_owner, p->d_pc_vsegs, p->d_lutc, p->d_sync_items, p->d_seg_chunk0, p->d_chunks, p->d_stateA, p->d_stateB, p->d_couts, p->d_vsegs, p->d_changed, p->d_pieces, p->d_piece_kept, p->d_pscans, p->d_psegs, p->d_pstates, p->d_psubs, p->d_prog_dsegs, p->d_lut11p, p->d_qt, p->d_mcu_prefix, p->d_job_prefix, p->d_tmp_coef, p->d_coef,
-                    p->d_rgb, p->d_rgb_tmp, p->d_planes, p->d_idct, p->d_status, p->d_win, p->d_win_mcu_prefix, p->d_segs_full, p->d_seg_gather, p->d_src, p->d_rz_images, p->d_rz_tabs, p->d_rz_lut, p->d_rz_mirror, p->d_or_images, p->d_or_prefix};
-    for (void *q : ptrs)
-        if (q) p->ctx->cache.put(q);
+    for (void *q : p->blocks) p->ctx->cache.put(q);
     delete p;
 }
 
@@ -118,6 +137,28 @@ int mj_plan_stage1_form(const mj_plan *p) {
     const int base = p->use_sync ? MJ_FORM_SYNC : (p->use_lanes ? MJ_FORM_LANES : MJ_FORM_WAVE);
     return base | (p->d_wg_tabs_lanes ? MJ_FORM_WG_TABLES : 0) | (p->use_lanes && p->d_lut13 ? MJ_FORM_RESOLVED : 0) | (p->use_fused ? MJ_FORM_FUSED : 0) |
            (p->use_sync && p->d_lutc ? MJ_FORM_COUNT_RESOLVED : 0);
+}
+
+int mj_debug_plan_shape(const mj_plan *p, int32_t *out, int32_t cap) {
+    if (!p || !out || cap < MJ_DEBUG_PLAN_SHAPE_WORDS) return MJ_ERR_INVALID;
+    const mj::FusedShape &f = p->fused;
+    const int32_t v[MJ_DEBUG_PLAN_SHAPE_WORDS] = {          // (one line per line of the list in mijpeg.h)
+        mj_plan_stage1_form(p), p->use_fused, p->lut_slots, (int32_t)p->n_segs, p->n_jobs,
+        p->sync_chunk_bytes, (int32_t)p->n_chunks, (int32_t)p->n_pieces, p->lutc_bits, p->lutc_tab_bytes, p->wg_slots_lanes, p->wg_slots_count, p->seg_order_mode,
+        p->n_ac13, p->n_dc13, p->lutf_bits[0], p->lutf_bits[1], p->lutf_bits[2], p->lutf_bits[3], p->lutf_total,
+        f.ipw, f.n_pass, f.n_prod, f.lpw, f.n_cons, f.xwg, f.n_wg, p->fused_spi,
+        p->chunk_strips, p->jobs_per_ticket, p->jobs_per_image, (int32_t)(uint32_t)p->total_jobs, p->blob_src != nullptr,
+        p->prog_fast, p->prog_banded, p->prog_steps, (int32_t)p->n_split, p->prog_chunks};
+    for (int i = 0; i < MJ_DEBUG_PLAN_SHAPE_WORDS; ++i) out[i] = v[i];
+    return MJ_OK;
+}
+
+int mj_debug_cache_stats(const mj_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return MJ_ERR_INVALID;
+    const DevBufferCache &c = ctx->cache;
+    out[0] = c.live.size(); out[1] = 0; out[2] = c.n_get; out[3] = c.size_hash;
+    for (const auto &b : c.live) out[1] += b.size;
+    return MJ_OK;
 }
 
 int mj_plan_get_info(const mj_plan *p, mj_plan_info *info) {
@@ -157,6 +198,14 @@ static int mark_done(mj_plan *p, hipStream_t s) {
 
 static int stage1_impl(mj_plan *p, void *stream);
 static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device);
+
+// what every launch of the plan's lane family is told, and its resolved-table set (lut: d_lut13, or a fused launch's d_lut12)
+static mj::LaneArgs lane_args(const mj_plan *p, hipStream_t s) {
+    return mj::LaneArgs{s, p->d_stream, p->d_seg_bits, p->d_segs, p->n_segs, p->d_images, p->d_huff, p->d_lut11, p->n_huff, p->d_coef, p->d_status, p->transposed ? 1 : 0};
+}
+static mj::ResolvedTables resolved_tables(const mj_plan *p, const uint32_t *lut) {
+    return mj::ResolvedTables{lut, p->n_ac13, p->n_dc13, p->ac_slot_pk, p->dc_slot_pk, p->dc_tab_pk};
+}
 
 int mj_plan_execute_stage1(mj_plan *p, void *stream) {
     if (!p) return MJ_ERR_INVALID;
@@ -226,10 +275,14 @@ static int stage1_impl(mj_plan *p, void *stream) {
         if (p->d_segs_full) MJ_HIP(ctx, mj::launch_gather_segments(s, p->d_segs_full, p->d_seg_gather, p->n_segs, p->d_segs));
     }
     if (p->use_lanes) {
+        const mj::LaneArgs a = lane_args(p, s);
+        const mj::ResolvedTables t = resolved_tables(p, p->d_lut13);
         if (p->d_pieces)
             MJ_HIP(ctx, mj::launch_destuff_pieces(s, p->d_blob, p->d_segs, p->d_pieces, p->n_pieces, p->d_piece_kept, p->d_stream, p->d_seg_bits));
         else
             MJ_HIP(ctx, mj::launch_destuff(s, p->d_blob, p->d_segs, p->n_segs, p->d_stream, p->d_seg_bits));
+        const mj::DevVSeg *vsegs = nullptr;
+        mj::LaneArgs walk = a;                  // the lane launch: over the restart segments, or — synchronisation form — the virtual ones
         if (p->use_sync) {
             // round 0 guesses, round 1.. start every chunk from its predecessor's exit state until no exit state changes
             // (typically the second true-state round changes nothing), then the pieces are decoded like restart segments
@@ -237,13 +290,12 @@ static int stage1_impl(mj_plan *p, void *stream) {
             uint64_t *in = p->d_stateA, *out = p->d_stateB;
             if (p->d_lutc) {
                 // resolved tables: one walk over every chunk, the list of wrong guesses, their repair — three launches
-                MJ_HIP(ctx, mj::launch_count(s, p->d_stream, p->d_seg_bits, p->d_segs, p->d_images, p->d_lutc, p->lutc_tab_bytes, p->n_huff, p->lutc_bits,
-                                             p->d_chunks, p->n_chunks, cbits, p->sync_warm_bits, p->d_stateA, p->d_couts, p->d_sync_items, p->d_changed, p->sync_rounds,
-                                             reinterpret_cast<int32_t *>(p->d_stateB)));
+                MJ_HIP(ctx, mj::launch_count(a, p->d_lutc, p->lutc_tab_bytes, p->lutc_bits, p->d_chunks, p->n_chunks, cbits, p->sync_warm_bits, p->d_stateA,
+                                             p->d_couts, p->d_sync_items, p->d_changed, p->sync_rounds, reinterpret_cast<int32_t *>(p->d_stateB)));
             } else {
                 MJ_HIP(ctx, mj::launch_fill_words(s, p->d_couts, 0xFFFFFFFFu, p->n_chunks * (int64_t)(sizeof(mj::DevChunkOut) / 4)));
-                MJ_HIP(ctx, mj::launch_sync_count(s, p->d_stream, p->d_seg_bits, p->d_segs, p->d_images, p->d_huff, p->d_lut11u, p->n_huff,
-                                                  p->d_chunks, p->n_chunks, cbits, nullptr, p->d_stateA, p->d_couts, p->d_changed, p->d_wg_tabs_count, p->wg_slots_count, nullptr, p->sync_warm_bits));
+                MJ_HIP(ctx, mj::launch_sync_count(a, p->d_lut11u, p->d_chunks, p->n_chunks, cbits, nullptr, p->d_stateA, p->d_couts, p->d_changed,
+                                                  p->d_wg_tabs_count, p->wg_slots_count, nullptr, p->sync_warm_bits));
                 // repair rounds: a fixed number, queued without looking (a chain of wrongly guessed entry states gets one link
                 // shorter per round; after round 0's run-up nearly every guess is right and the second repair round changes
                 // nothing).  Whether they sufficed is decided on the device: k_build_vsegs marks the images whose chunk states
@@ -251,30 +303,19 @@ static int stage1_impl(mj_plan *p, void *stream) {
                 // round trip: the execute is asynchronous and can be captured into a graph like every other form.
                 MJ_HIP(ctx, mj::launch_fill_words(s, p->d_changed, 0u, p->sync_rounds + 8));
                 for (int round = 1; round <= p->sync_rounds; ++round) {
-                    MJ_HIP(ctx, mj::launch_sync_count(s, p->d_stream, p->d_seg_bits, p->d_segs, p->d_images, p->d_huff, p->d_lut11u,
-                                                      p->n_huff, p->d_chunks, p->n_chunks, cbits, in, out, p->d_couts, p->d_changed + round, p->d_wg_tabs_count, p->wg_slots_count,
-                                                      round >= 2 ? p->d_changed + round - 1 : nullptr, p->sync_warm_bits));
+                    MJ_HIP(ctx, mj::launch_sync_count(a, p->d_lut11u, p->d_chunks, p->n_chunks, cbits, in, out, p->d_couts, p->d_changed + round,
+                                                      p->d_wg_tabs_count, p->wg_slots_count, round >= 2 ? p->d_changed + round - 1 : nullptr, p->sync_warm_bits));
                     std::swap(in, out);
                 }
             }
-            MJ_HIP(ctx, mj::launch_build_vsegs(s, p->d_chunks, p->d_seg_chunk0, p->n_segs, p->d_couts, p->d_segs, p->d_seg_bits, p->d_images, p->d_vsegs,
-                                               in, cbits, p->d_status));
-            if (p->d_lut13)
-                MJ_HIP(ctx, mj::launch_huffman_lanes13(s, p->d_stream, p->d_seg_bits, p->d_segs, p->n_chunks, p->d_images, p->d_huff, p->d_lut11,
-                                                       p->d_lut13, p->n_ac13, p->n_dc13, p->ac_slot_pk, p->dc_slot_pk, p->dc_tab_pk,
-                                                       p->d_coef, p->d_status, p->transposed ? 1 : 0, p->d_vsegs));
-            else
-                MJ_HIP(ctx, mj::launch_huffman_lanes(s, p->d_stream, p->d_seg_bits, p->d_segs, p->n_chunks, p->d_images, p->d_huff, p->d_lut11,
-                                                     p->n_huff, p->d_coef, p->d_status, p->transposed ? 1 : 0, p->d_vsegs, p->d_wg_tabs_lanes, p->wg_slots_lanes));
-            return MJ_OK;
+            MJ_HIP(ctx, mj::launch_build_vsegs(a, p->d_chunks, p->d_seg_chunk0, p->d_couts, p->d_vsegs, in, cbits));
+            vsegs = p->d_vsegs;
+            walk.n_segs = p->n_chunks;
         }
         if (p->d_lut13)
-            MJ_HIP(ctx, mj::launch_huffman_lanes13(s, p->d_stream, p->d_seg_bits, p->d_segs, p->n_segs, p->d_images, p->d_huff, p->d_lut11,
-                                                   p->d_lut13, p->n_ac13, p->n_dc13, p->ac_slot_pk, p->dc_slot_pk, p->dc_tab_pk,
-                                                   p->d_coef, p->d_status, p->transposed ? 1 : 0, nullptr, p->d_by_length, p->seg_order_mode));
+            MJ_HIP(ctx, mj::launch_huffman_lanes13(walk, t, vsegs, vsegs ? nullptr : p->d_by_length, vsegs ? 0 : p->seg_order_mode));
         else
-            MJ_HIP(ctx, mj::launch_huffman_lanes(s, p->d_stream, p->d_seg_bits, p->d_segs, p->n_segs, p->d_images, p->d_huff, p->d_lut11,
-                                                 p->n_huff, p->d_coef, p->d_status, p->transposed ? 1 : 0, nullptr, p->d_wg_tabs_lanes, p->wg_slots_lanes));
+            MJ_HIP(ctx, mj::launch_huffman_lanes(walk, vsegs, p->d_wg_tabs_lanes, p->wg_slots_lanes));
     } else
         MJ_HIP(ctx, mj::launch_huffman(s, p->d_blob, p->d_segs, p->n_segs, p->d_images, p->d_huff, p->d_coef,
                                        p->d_status, p->lut_slots, p->transposed ? 1 : 0));
@@ -285,7 +326,7 @@ static int stage1_impl(mj_plan *p, void *stream) {
 static int recon_args(mj_plan *p, uint8_t *rgb_device, mj::ReconArgs &a) {
     mj_context *ctx = p->ctx;
     if (!rgb_device) {
-        if (!p->d_rgb) MJ_HIP(ctx, ctx->cache.get((void **)&p->d_rgb, (size_t)p->info.rgb_bytes + 16));
+        if (!p->d_rgb) MJ_HIP(ctx, alloc(p, &p->d_rgb, (size_t)p->info.rgb_bytes + 16));
         rgb_device = p->d_rgb;
     }
     p->last_rgb = rgb_device;
@@ -339,7 +380,7 @@ static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
     // (a resized planar plan keeps the interleaved image: the resize launch stores the planes)
     const bool planar = p->layout >= MJ_LAYOUT_PLANAR_XMAJOR && p->ncomp == 3 && !p->resized;
     if (planar) {
-        if (!p->d_rgb_tmp) MJ_HIP(ctx, ctx->cache.get((void **)&p->d_rgb_tmp, (size_t)p->info.rgb_bytes + 16));
+        if (!p->d_rgb_tmp) MJ_HIP(ctx, alloc(p, &p->d_rgb_tmp, (size_t)p->info.rgb_bytes + 16));
         a.rgb = p->d_rgb_tmp;
     }
     if (a.planes || a.idct_out) MJ_HIP(ctx, mj::launch_fill_words(s, a.level_counts, 0u, 6));     // mj_plan_idct_levels
@@ -360,25 +401,33 @@ static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
     return resize_launch(p, s);
 }
 
-// Both stages in one launch (fused.hip), for the plans that can (use_fused): the marker scan and stage 0 as in stage1_impl,
-// then producers and consumers side by side.
+// Both stages in one launch (fused.hip), for the plans that can (use_fused): the marker scan and stage 0 as in stage1_impl
+// (fused_front), then producers and consumers side by side (fused_launch).
+static int fused_front(mj_plan *p, hipStream_t s) {
+    MJ_HIP(p->ctx, mj::launch_fill_words(s, p->d_status, 0u, p->n_images));
+    if (p->n_jobs) MJ_HIP(p->ctx, mj::launch_scan_markers(s, p->d_blob, p->d_jobs, p->n_jobs, p->d_segs, p->d_status));
+    MJ_HIP(p->ctx, mj::launch_destuff(s, p->d_blob, p->d_segs, p->n_segs, p->d_stream, p->d_seg_bits));
+    return MJ_OK;
+}
+static int fused_launch(mj_plan *p, hipStream_t s, const mj::ReconArgs &a) {
+    const mj::DevImage &i0 = p->h_images[0];
+    MJ_HIP(p->ctx, mj::launch_fused(lane_args(p, s), resolved_tables(p, p->d_lut12), p->fused, p->lutf_off, p->lutf_bits, a, p->hmax, p->vmax, p->fused_spi,
+                                    i0.restart_interval, i0.mcu_count_h, i0.mcu_count_v, p->d_job_prefix, p->total_jobs, p->jobs_per_image,
+                                    p->d_by_length, p->d_holder, p->d_xwords));
+    return MJ_OK;
+}
 static int fused_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {
     mj_context *ctx = p->ctx;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (int rc = plan_ready(p, s)) return rc;
     mj::ReconArgs a{};
     if (int rc = recon_args(p, rgb_device, a)) return rc;
-    MJ_HIP(ctx, mj::launch_fill_words(s, p->d_status, 0u, p->n_images));
-    if (p->n_jobs) MJ_HIP(ctx, mj::launch_scan_markers(s, p->d_blob, p->d_jobs, p->n_jobs, p->d_segs, p->d_status));
-    MJ_HIP(ctx, mj::launch_destuff(s, p->d_blob, p->d_segs, p->n_segs, p->d_stream, p->d_seg_bits));
+    if (int rc = fused_front(p, s)) return rc;
 #ifdef MJ_DIAGNOSTIC
     const bool dbg_fused = getenv("MJ_DEBUG_FUSED") != nullptr;
     if (dbg_fused) { (void)hipStreamSynchronize(s); mj::dbg_fused_clear(ctx->d_dump); }
 #endif
-    MJ_HIP(ctx, mj::launch_fused(s, p->fused, p->d_stream, p->d_seg_bits, p->d_segs, p->n_segs, p->d_images, p->d_huff, p->d_lut11, p->d_lut12,
-                                 p->n_ac13, p->n_dc13, p->ac_slot_pk, p->dc_slot_pk, p->dc_tab_pk, p->lutf_off, p->lutf_bits, p->d_coef, p->d_status, a, p->hmax, p->vmax,
-                                 p->transposed, p->fused_spi, p->h_images[0].restart_interval, p->h_images[0].mcu_count_h, p->h_images[0].mcu_count_v, p->d_job_prefix, p->total_jobs, p->jobs_per_image,
-                                 p->d_by_length, p->d_holder, p->d_xwords));
+    if (int rc = fused_launch(p, s, a)) return rc;
 #ifdef MJ_DIAGNOSTIC
     if (dbg_fused) {
         (void)hipStreamSynchronize(s);
@@ -489,7 +538,7 @@ int mj_plan_read(mj_plan *p, uint8_t *rgb_host, int16_t *coef_host, int16_t *pla
         MJ_HIP(ctx, hipMemcpy(rgb_host, p->last_rgb, (size_t)p->info.rgb_bytes, hipMemcpyDeviceToHost));
     }
     if (coef_host) {   // the :869 seam is in zig-zag order; the device keeps blocks in natural order
-        if (!p->d_tmp_coef) MJ_HIP(ctx, ctx->cache.get((void **)&p->d_tmp_coef, (size_t)p->info.total_blocks * 128 + 16));
+        if (!p->d_tmp_coef) MJ_HIP(ctx, alloc(p, &p->d_tmp_coef, (size_t)p->info.total_blocks * 128 + 16));
         MJ_HIP(ctx, mj::launch_permute_blocks(ctx->stream, p->d_coef, p->d_tmp_coef, p->info.total_blocks, 0, p->transposed ? 1 : 0));
         MJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
         MJ_HIP(ctx, hipMemcpy(coef_host, p->d_tmp_coef, (size_t)p->info.total_blocks * 128, hipMemcpyDeviceToHost));
@@ -512,7 +561,7 @@ int mj_plan_write_coef(mj_plan *p, const int16_t *coef, int32_t mem) {
     mj_context *ctx = p->ctx;
     const int16_t *src = coef;
     if (mem != MJ_MEM_DEVICE) {
-        if (!p->d_tmp_coef) MJ_HIP(ctx, ctx->cache.get((void **)&p->d_tmp_coef, (size_t)p->info.total_blocks * 128 + 16));
+        if (!p->d_tmp_coef) MJ_HIP(ctx, alloc(p, &p->d_tmp_coef, (size_t)p->info.total_blocks * 128 + 16));
         MJ_HIP(ctx, hipMemcpy(p->d_tmp_coef, coef, (size_t)p->info.total_blocks * 128, hipMemcpyHostToDevice));
         src = p->d_tmp_coef;
     }
@@ -522,25 +571,20 @@ int mj_plan_write_coef(mj_plan *p, const int16_t *coef, int32_t mem) {
     return MJ_OK;
 }
 
-int mj_plan_fill_coef(mj_plan *p, int byte_value) {
-    if (!p) return MJ_ERR_INVALID;
+// the two poisoning test hooks: every byte of one of an idle plan's buffers := byte_value, synchronously
+static int fill_buffer(mj_plan *p, void *buf, size_t bytes, int byte_value) {
     if (int rc = plan_ready(p)) return rc;
-    mj_context *ctx = p->ctx;
-    if (p->done_valid) MJ_HIP(ctx, hipEventSynchronize(p->done));
-    MJ_HIP(ctx, hipMemset(p->d_coef, byte_value & 0xFF, (size_t)p->info.total_blocks * 128));
-    MJ_HIP(ctx, hipDeviceSynchronize());
+    if (p->done_valid) MJ_HIP(p->ctx, hipEventSynchronize(p->done));
+    MJ_HIP(p->ctx, hipMemset(buf, byte_value & 0xFF, bytes));
+    MJ_HIP(p->ctx, hipDeviceSynchronize());
     return MJ_OK;
 }
+int mj_plan_fill_coef(mj_plan *p, int byte_value) { return !p ? MJ_ERR_INVALID : fill_buffer(p, p->d_coef, (size_t)p->info.total_blocks * 128, byte_value); }
 
 int mj_plan_fill_source(mj_plan *p, int byte_value) {
     if (!p) return MJ_ERR_INVALID;
-    mj_context *ctx = p->ctx;
-    if (!p->resized) return fail(ctx, MJ_ERR_INVALID, "mj_plan_fill_source: not a resized plan");
-    if (int rc = plan_ready(p)) return rc;
-    if (p->done_valid) MJ_HIP(ctx, hipEventSynchronize(p->done));
-    MJ_HIP(ctx, hipMemset(p->d_src, byte_value & 0xFF, (size_t)p->src_bytes + 64));
-    MJ_HIP(ctx, hipDeviceSynchronize());
-    return MJ_OK;
+    if (!p->resized) return fail(p->ctx, MJ_ERR_INVALID, "mj_plan_fill_source: not a resized plan");
+    return fill_buffer(p, p->d_src, (size_t)p->src_bytes + 64, byte_value);
 }
 
 int mj_plan_time_resize(mj_plan *p, int iters, uint8_t *rgb_device, float *ms_out, int64_t *source_bytes) {
@@ -551,20 +595,7 @@ int mj_plan_time_resize(mj_plan *p, int iters, uint8_t *rgb_device, float *ms_ou
     hipStream_t s = ctx->stream;
     if (int rc = plan_ready(p, s)) return rc;
     if (rgb_device) p->last_rgb = rgb_device;
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    MJ_HIP(ctx, hipEventCreate(&ev.a));
-    MJ_HIP(ctx, hipEventCreate(&ev.b));
-    int rc = resize_launch(p, s);       // warm
-    MJ_HIP(ctx, hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = resize_launch(p, s);
-    MJ_HIP(ctx, hipEventRecord(ev.b, s));
-    MJ_HIP(ctx, hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    MJ_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
-    *ms_out = ms / iters;
+    const int rc = time_launches(ctx, s, 1, iters, [&] { return resize_launch(p, s); }, ms_out);
     if (source_bytes) *source_bytes = p->src_bytes;
     return rc != MJ_OK ? rc : mark_done(p, s);
 }
@@ -609,50 +640,16 @@ int mj_plan_time_execute(mj_plan *p, int iters, uint8_t *rgb_device, float *fron
     mj_context *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     if (!p->d_blob) return fail(ctx, MJ_ERR_INVALID, "plan has no entropy-coded data");
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    MJ_HIP(ctx, hipEventCreate(&ev.a));
-    MJ_HIP(ctx, hipEventCreate(&ev.b));
     if (int rc = plan_ready(p, s)) return rc;
     float ms = 0.f;
-    if (front_ms) *front_ms = 0.f;
-    if (main_ms) *main_ms = 0.f;
-    if (!p->use_fused) {                       // the two launches: front = stage 1 (with stage 0), main = stage 2
-        return mj_plan_time_stages(p, iters, rgb_device, front_ms, main_ms);
-    }
+    if (front_ms) *front_ms = 0.f; if (main_ms) *main_ms = 0.f;
+    if (!p->use_fused) return mj_plan_time_stages(p, iters, rgb_device, front_ms, main_ms);      // the two launches: front = stage 1 (with stage 0), main = stage 2
     mj::ReconArgs a{};
     if (int rc = recon_args(p, rgb_device, a)) return rc;
-    auto front = [&]() -> int {
-        MJ_HIP(ctx, mj::launch_fill_words(s, p->d_status, 0u, p->n_images));
-        if (p->n_jobs) MJ_HIP(ctx, mj::launch_scan_markers(s, p->d_blob, p->d_jobs, p->n_jobs, p->d_segs, p->d_status));
-        MJ_HIP(ctx, mj::launch_destuff(s, p->d_blob, p->d_segs, p->n_segs, p->d_stream, p->d_seg_bits));
-        return MJ_OK;
-    };
-    auto fused = [&]() -> int {
-        MJ_HIP(ctx, mj::launch_fused(s, p->fused, p->d_stream, p->d_seg_bits, p->d_segs, p->n_segs, p->d_images, p->d_huff, p->d_lut11, p->d_lut12,
-                                     p->n_ac13, p->n_dc13, p->ac_slot_pk, p->dc_slot_pk, p->dc_tab_pk, p->lutf_off, p->lutf_bits, p->d_coef, p->d_status, a, p->hmax, p->vmax,
-                                     p->transposed, p->fused_spi, p->h_images[0].restart_interval, p->h_images[0].mcu_count_h, p->h_images[0].mcu_count_v, p->d_job_prefix, p->total_jobs, p->jobs_per_image,
-                                 p->d_by_length, p->d_holder, p->d_xwords));
-        return MJ_OK;
-    };
-    int rc = front();
-    if (rc == MJ_OK) rc = fused();
-    if (rc != MJ_OK) return rc;
-    MJ_HIP(ctx, hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = front();
-    MJ_HIP(ctx, hipEventRecord(ev.b, s));
-    MJ_HIP(ctx, hipEventSynchronize(ev.b));
-    MJ_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (front_ms) *front_ms = ms / iters;
-    if (rc != MJ_OK) return rc;
-    MJ_HIP(ctx, hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = fused();
-    MJ_HIP(ctx, hipEventRecord(ev.b, s));
-    MJ_HIP(ctx, hipEventSynchronize(ev.b));
-    MJ_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (main_ms) *main_ms = ms / iters;
+    int rc = fused_front(p, s);                 // warm: both once
+    if (rc == MJ_OK) rc = fused_launch(p, s, a);
+    if (rc == MJ_OK) rc = time_launches(ctx, s, 0, iters, [&] { return fused_front(p, s); }, front_ms ? front_ms : &ms);
+    if (rc == MJ_OK) rc = time_launches(ctx, s, 0, iters, [&] { return fused_launch(p, s, a); }, main_ms ? main_ms : &ms);
     return rc != MJ_OK ? rc : mark_done(p, s);
 }
 
@@ -672,28 +669,20 @@ int mj_device_copy_rate(mj_context *ctx, int64_t bytes, int iters, float *ms_per
     MJ_HIP(ctx, hipSetDevice(ctx->device));
     bytes &= ~(int64_t)15;
     struct Bufs {
-        mj_context *c; void *a = nullptr, *b = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Bufs() { if (a) c->cache.put(a); if (b) c->cache.put(b); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+        mj_context *c; void *a = nullptr, *b = nullptr;
+        ~Bufs() { if (a) c->cache.put(a); if (b) c->cache.put(b); }
     } h{ctx};
     MJ_HIP(ctx, ctx->cache.get(&h.a, (size_t)bytes));
     MJ_HIP(ctx, ctx->cache.get(&h.b, (size_t)bytes));
-    MJ_HIP(ctx, hipEventCreate(&h.e0));
-    MJ_HIP(ctx, hipEventCreate(&h.e1));
     hipStream_t s = ctx->stream;
     MJ_HIP(ctx, mj::launch_fill_words(s, h.a, 0x01020304u, bytes / 4));
     float best = 0.f;
     for (int v = 0; v < mj::copy16_variants(); ++v) {          // every launch shape: the best one is the ceiling (util_kernels.hip)
-        for (int i = 0; i < 3; ++i) MJ_HIP(ctx, mj::launch_copy16(s, h.a, h.b, bytes, v));      // warm
-        MJ_HIP(ctx, hipEventRecord(h.e0, s));
-        for (int i = 0; i < iters; ++i) MJ_HIP(ctx, mj::launch_copy16(s, h.a, h.b, bytes, v));
-        MJ_HIP(ctx, hipEventRecord(h.e1, s));
-        MJ_HIP(ctx, hipEventSynchronize(h.e1));
         float t = 0.f;
-        MJ_HIP(ctx, hipEventElapsedTime(&t, h.e0, h.e1));
+        if (int rc = time_launches(ctx, s, 3, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_copy16(s, h.a, h.b, bytes, v)); return MJ_OK; }, &t)) return rc;
         if (best == 0.f || t < best) best = t;
     }
-    float ms = best;
-    *ms_per_copy = ms / iters;
+    *ms_per_copy = best;
     return MJ_OK;
 }
 
@@ -715,24 +704,7 @@ int mj_plan_tune_placement(mj_plan *p, void *stream, uint8_t *rgb_device, int32_
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     if (int rc = plan_ready(p)) return rc;
     if (p->done_valid) MJ_HIP(ctx, hipEventSynchronize(p->done));
-    struct Events {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    MJ_HIP(ctx, hipEventCreate(&ev.a));
-    MJ_HIP(ctx, hipEventCreate(&ev.b));
-    auto timed = [&](float &ms) -> int {
-        int rc = MJ_OK;
-        for (int i = 0; i < 3 && rc == MJ_OK; ++i) rc = execute_impl(p, s, rgb_device);
-        if (rc != MJ_OK) return rc;
-        MJ_HIP(ctx, hipEventRecord(ev.a, s));
-        for (int i = 0; i < 5 && rc == MJ_OK; ++i) rc = execute_impl(p, s, rgb_device);
-        MJ_HIP(ctx, hipEventRecord(ev.b, s));
-        MJ_HIP(ctx, hipEventSynchronize(ev.b));
-        MJ_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
-        ms /= 5.f;
-        return rc;
-    };
+    auto timed = [&](float &ms) -> int { return time_launches(ctx, s, 3, 5, [&] { return execute_impl(p, s, rgb_device); }, &ms); };
     // Two of the plan's buffers carry the launch's traffic: the coefficient store (written, read back) and the stage-0 stream (read
     // by the walk).  Each is tried in turn against everything else as it stands: the plan's own first, then `candidates - 1` others.
     // Candidates come through the context's buffer cache — a block it holds from an earlier plan is as good a candidate as a fresh
@@ -753,6 +725,7 @@ int mj_plan_tune_placement(mj_plan *p, void *stream, uint8_t *rgb_device, int32_
             const int rc = timed(ms);
             if (ms_out && which == 0) ms_out[c] = ms;
             if (rc == MJ_OK && ms < best_ms * 0.99f) {       // (the classes are 5-9 % apart: one per cent is noise)
+                p->swap_block(best, cand);
                 ctx->cache.drop(best);
                 best = cand; best_ms = ms;
                 if (chosen && which == 0) *chosen = c;
@@ -778,25 +751,11 @@ int mj_plan_time_stages(mj_plan *p, int iters, uint8_t *rgb_device, float *stage
     if (!p || iters <= 0) return MJ_ERR_INVALID;
     mj_context *ctx = p->ctx;
     hipStream_t s = ctx->stream;
-    struct Events {           // destroyed on every way out, the error returns of MJ_HIP included
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    MJ_HIP(ctx, hipEventCreate(&ev.a));
-    MJ_HIP(ctx, hipEventCreate(&ev.b));
-    const hipEvent_t e0 = ev.a, e1 = ev.b;
     int rc = MJ_OK;
-    float ms = 0.f;
     if (stage1_ms) {
         *stage1_ms = 0.f;
         if (p->d_blob) {
-            if ((rc = stage1_impl(p, s)) != MJ_OK) return rc;   // warm
-            MJ_HIP(ctx, hipEventRecord(e0, s));
-            for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = stage1_impl(p, s);
-            MJ_HIP(ctx, hipEventRecord(e1, s));
-            MJ_HIP(ctx, hipEventSynchronize(e1));
-            MJ_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-            *stage1_ms = ms / iters;
+            rc = time_launches(ctx, s, 1, iters, [&] { return stage1_impl(p, s); }, stage1_ms);
 #ifdef MJ_DIAGNOSTIC
             mj::dbg_lanes_report();
             mj::dbg_prog_report();
@@ -806,13 +765,7 @@ int mj_plan_time_stages(mj_plan *p, int iters, uint8_t *rgb_device, float *stage
         }
     }
     if (stage2_ms && rc == MJ_OK) {
-        if ((rc = stage2_impl(p, s, rgb_device)) != MJ_OK) return rc;   // warm
-        MJ_HIP(ctx, hipEventRecord(e0, s));
-        for (int i = 0; i < iters && rc == MJ_OK; ++i) rc = stage2_impl(p, s, rgb_device);
-        MJ_HIP(ctx, hipEventRecord(e1, s));
-        MJ_HIP(ctx, hipEventSynchronize(e1));
-        MJ_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-        *stage2_ms = ms / iters;
+        rc = time_launches(ctx, s, 1, iters, [&] { return stage2_impl(p, s, rgb_device); }, stage2_ms);
 #ifdef MJ_DIAGNOSTIC      // the wait probe of the diagnostic build (MJ_DEBUG_STAGE2=8/9): sums the kernel left in the dump buffer
         if (getenv("MJ_DEBUG_STAGE2") && atoi(getenv("MJ_DEBUG_STAGE2")) >= 8) {
             unsigned long long h[3] = {0, 0, 0};

@@ -528,19 +528,18 @@ extern "C" int mj_debug_fused_shape(int32_t cus, int32_t n_ac, int32_t n_dc, int
 
 namespace mj {
 
-hipError_t launch_fused(hipStream_t stream, const FusedShape &shape, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs,
-                        int64_t n_segs, const DevImage *images, const DevHuff *huff, const uint16_t *lut11, const uint32_t *lut13,
-                        int n_ac, int n_dc, uint64_t ac_slot_pk, uint64_t dc_slot_pk, uint64_t dc_tab_pk, const int ac_off[4], const int ac_bits[4],
-                        int16_t *coef, int32_t *status,
-                        const ReconArgs &a, int hmax, int vmax, bool transposed, int spi, int restart_interval, int mcus_per_row, int mcu_rows,
+hipError_t launch_fused(const LaneArgs &l, const ResolvedTables &t, const FusedShape &shape, const int ac_off[4], const int ac_bits[4],
+                        const ReconArgs &a, int hmax, int vmax, int spi, int restart_interval, int mcus_per_row, int mcu_rows,
                         const int64_t *job_prefix, int64_t total_jobs, int jobs_per_image, const int32_t *by_length, const int32_t *holder,
                         uint32_t *x_words) {
+    hipStream_t stream = l.stream;
+    const bool transposed = l.transposed != 0;
     if (restart_interval < 1 || spi < 1) return hipErrorInvalidValue;
     if (!shape.ok || a.n_images < 1) return hipErrorInvalidValue;
     if (shape.xwg && (!by_length || !holder || !x_words)) return hipErrorInvalidValue;
     FusedArgs F{};
-    F.L = lanes13::Args{dstream, seg_bits, segs, n_segs, images, huff, lut11, lut13, n_ac, n_dc, ac_slot_pk, dc_slot_pk, dc_tab_pk,
-                        coef, status, shape.lpw, transposed ? 1 : 0, nullptr, nullptr, 0, shape.ring, shape.ac_total_bytes, shape.dbits,
+    F.L = lanes13::Args{l.dstream, l.seg_bits, l.segs, l.n_segs, l.images, l.huff, l.lut11, t.lut13, t.n_ac, t.n_dc, t.ac_slot_pk, t.dc_slot_pk, t.dc_tab_pk,
+                        l.coef, l.status, shape.lpw, transposed ? 1 : 0, nullptr, nullptr, 0, shape.ring, shape.ac_total_bytes, shape.dbits,
                         {ac_off[0], ac_off[1], ac_off[2], ac_off[3]}, {ac_bits[0], ac_bits[1], ac_bits[2], ac_bits[3]}, shape.ipw * spi, nullptr};
     F.R = a;
     F.job_prefix = job_prefix; F.total_jobs = total_jobs; F.jobs_per_image = jobs_per_image;

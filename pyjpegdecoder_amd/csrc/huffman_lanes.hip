@@ -435,11 +435,11 @@ int lanes_per_wave(int64_t n_segs, int n_slots) {
     return (int)(want > 64 ? 64 : want);
 }
 
-hipError_t launch_huffman_lanes(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs, int64_t n_segs,
-                                const DevImage *images, const DevHuff *huff, const uint16_t *lut11, int n_huff,
-                                int16_t *coef, int32_t *status, int transposed, const DevVSeg *vsegs, const int32_t *wg_tabs, int wg_slots) {
+hipError_t launch_huffman_lanes(const LaneArgs &a, const DevVSeg *vsegs, const int32_t *wg_tabs, int wg_slots) {
+    const int64_t n_segs = a.n_segs;
+    int transposed = a.transposed;
     if (n_segs == 0) return hipSuccess;
-    const int n_slots = wg_tabs ? wg_slots : n_huff;
+    const int n_slots = wg_tabs ? wg_slots : a.n_huff;
     const int lpw_run = lanes_per_wave(n_segs, n_slots);
 #ifdef MJ_DIAGNOSTIC
     if (const char *e = getenv("MJ_DEBUG_STAGE1")) transposed |= atoi(e) << 8;
@@ -453,11 +453,11 @@ hipError_t launch_huffman_lanes(hipStream_t stream, const uint32_t *dstream, con
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_huffman_lanes<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     });
     if (wg_tabs)
-        hipLaunchKernelGGL(k_huffman_lanes<true>, dim3((unsigned)blocks), dim3(256), lds, stream, dstream, seg_bits, segs, n_segs, images,
-                           huff, lut11, n_slots, coef, status, lpw_run, transposed, vsegs, wg_tabs);
+        hipLaunchKernelGGL(k_huffman_lanes<true>, dim3((unsigned)blocks), dim3(256), lds, a.stream, a.dstream, a.seg_bits, a.segs, n_segs, a.images,
+                           a.huff, a.lut11, n_slots, a.coef, a.status, lpw_run, transposed, vsegs, wg_tabs);
     else
-        hipLaunchKernelGGL(k_huffman_lanes<false>, dim3((unsigned)blocks), dim3(256), lds, stream, dstream, seg_bits, segs, n_segs, images,
-                           huff, lut11, n_slots, coef, status, lpw_run, transposed, vsegs, wg_tabs);
+        hipLaunchKernelGGL(k_huffman_lanes<false>, dim3((unsigned)blocks), dim3(256), lds, a.stream, a.dstream, a.seg_bits, a.segs, n_segs, a.images,
+                           a.huff, a.lut11, n_slots, a.coef, a.status, lpw_run, transposed, vsegs, wg_tabs);
     return hipGetLastError();
 }
 

@@ -76,10 +76,10 @@ static size_t lds13(int n_ac, int n_dc, int nw, int lpw, int kRing = 128) { retu
 
 bool lanes13_fits(int n_ac, int n_dc) { return n_ac >= 1 && n_ac <= 3 && n_dc >= 1 && n_dc <= 4 && lds13(n_ac, n_dc, 4, 8, 64) <= 160 * 1024; }
 
-hipError_t launch_huffman_lanes13(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs, int64_t n_segs,
-                                  const DevImage *images, const DevHuff *huff, const uint16_t *lut11, const uint32_t *lut13,
-                                  int n_ac, int n_dc, uint64_t ac_slot_pk, uint64_t dc_slot_pk, uint64_t dc_tab_pk,
-                                  int16_t *coef, int32_t *status, int transposed, const DevVSeg *vsegs, const int32_t *by_length, int order_mode) {
+hipError_t launch_huffman_lanes13(const LaneArgs &a, const ResolvedTables &t, const DevVSeg *vsegs, const int32_t *by_length, int order_mode) {
+    const int64_t n_segs = a.n_segs;
+    const int n_ac = t.n_ac, n_dc = t.n_dc;
+    hipStream_t stream = a.stream;
     if (n_segs == 0) return hipSuccess;
     const int cus = device_cus();
     // tuning switches (mj_set_option; tools/stage_probe.py): waves per workgroup, lanes per wave
@@ -114,8 +114,8 @@ hipError_t launch_huffman_lanes13(hipStream_t stream, const uint32_t *dstream, c
     attr_once.run([&] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_huffman_lanes13), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
-    lanes13::Args A{dstream, seg_bits, segs, n_segs, images, huff, lut11, lut13, n_ac, n_dc, ac_slot_pk, dc_slot_pk, dc_tab_pk,
-                    coef, status, lpw, transposed, vsegs, by_length, order_mode, ring, n_ac * kLanes13SlotBytes, kLaneLutBits, {0, 0, 0, 0}, {13, 13, 13, 13}, 0, nullptr};
+    lanes13::Args A{a.dstream, a.seg_bits, a.segs, n_segs, a.images, a.huff, a.lut11, t.lut13, n_ac, n_dc, t.ac_slot_pk, t.dc_slot_pk, t.dc_tab_pk,
+                    a.coef, a.status, lpw, a.transposed, vsegs, by_length, order_mode, ring, n_ac * kLanes13SlotBytes, kLaneLutBits, {0, 0, 0, 0}, {13, 13, 13, 13}, 0, nullptr};
     hipLaunchKernelGGL(k_huffman_lanes13, dim3((unsigned)blocks), dim3(64 * nw), lds, stream, A);
 #ifdef MJ_X_STAMP
     if (getenv("MJ_X_REPORT")) {

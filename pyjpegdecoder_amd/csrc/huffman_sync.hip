@@ -555,13 +555,15 @@ __global__ void k_sync_scan(const DevChunk *__restrict__ chunks, int64_t n_chunk
     }
 }
 
-hipError_t launch_count(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs, const DevImage *images,
-                        const uint32_t *lutc, int tab_bytes, int n_tabs, int wbits, const DevChunk *chunks, int64_t n_chunks, int cbits,
+hipError_t launch_count(const LaneArgs &a, const uint32_t *lutc, int tab_bytes, int wbits, const DevChunk *chunks, int64_t n_chunks, int cbits,
                         int warm_bits, uint64_t *exit_state, DevChunkOut *outs, void *items, int32_t *n_items, int max_links, int32_t *owner) {
     if (n_chunks == 0) return hipSuccess;
+    hipStream_t stream = a.stream;
+    const int32_t *seg_bits = a.seg_bits;
+    const int n_tabs = a.n_huff;
     CountArgs A{};
     A.owner = owner;
-    A.stream = dstream; A.seg_bits = seg_bits; A.segs = segs; A.images = images;
+    A.stream = a.dstream; A.seg_bits = seg_bits; A.segs = a.segs; A.images = a.images;
     A.lutc = lutc; A.tab_bytes = tab_bytes; A.n_tabs = n_tabs; A.wbits = wbits;
     // the run-up in front of every chunk: half a chunk.  A wrong guess costs one lane of the repair launch, whose duration is one
     // lone wavefront's walk of one chunk however many lanes there are (up to a wave per SIMD) — unless some old walk had not found
@@ -673,12 +675,11 @@ __global__ __launch_bounds__(256) void k_build_vsegs(const DevChunk *__restrict_
     }
 }
 
-hipError_t launch_sync_count(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs,
-                             const DevImage *images, const DevHuff *huff, const uint16_t *lut11u, int n_huff,
-                             const DevChunk *chunks, int64_t n_chunks, int cbits, const uint64_t *entry, uint64_t *exit_out,
-                             DevChunkOut *outs, int32_t *changed, const int32_t *wg_tabs, int wg_slots, const int32_t *prev_changed, int warm_bits) {
+hipError_t launch_sync_count(const LaneArgs &a, const uint16_t *lut11u, const DevChunk *chunks, int64_t n_chunks, int cbits, const uint64_t *entry,
+                             uint64_t *exit_out, DevChunkOut *outs, int32_t *changed, const int32_t *wg_tabs, int wg_slots, const int32_t *prev_changed,
+                             int warm_bits) {
     if (n_chunks == 0) return hipSuccess;
-    if (wg_tabs) n_huff = wg_slots;                             // table slots in LDS
+    const int n_huff = wg_tabs ? wg_slots : a.n_huff;           // table slots in LDS
     const size_t lds = (size_t)n_huff * kLSize * 2 + 16 + kMaxWgTables * 4 + (size_t)n_huff * kLongInts * 4;
     const dim3 grid((unsigned)((n_chunks + 255) / 256));
     static OncePerDevice attr_once;
@@ -688,20 +689,19 @@ hipError_t launch_sync_count(hipStream_t stream, const uint32_t *dstream, const 
     });
     const int warm = warm_bits >= 0 ? warm_bits : cbits / 2;   // run-up in front of every chunk (swept: half a chunk is best; MJ_SYNC_WARM is read once, when the plan is created)
     if (entry)
-        hipLaunchKernelGGL(k_sync_count<false>, grid, dim3(256), lds, stream, dstream, seg_bits, segs, images, huff, lut11u, n_huff,
+        hipLaunchKernelGGL(k_sync_count<false>, grid, dim3(256), lds, a.stream, a.dstream, a.seg_bits, a.segs, a.images, a.huff, lut11u, n_huff,
                            chunks, n_chunks, cbits, warm, entry, exit_out, outs, changed, wg_tabs, prev_changed);
     else
-        hipLaunchKernelGGL(k_sync_count<true>, grid, dim3(256), lds, stream, dstream, seg_bits, segs, images, huff, lut11u, n_huff,
+        hipLaunchKernelGGL(k_sync_count<true>, grid, dim3(256), lds, a.stream, a.dstream, a.seg_bits, a.segs, a.images, a.huff, lut11u, n_huff,
                            chunks, n_chunks, cbits, warm, entry, exit_out, outs, changed, wg_tabs, nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_build_vsegs(hipStream_t stream, const DevChunk *chunks, const int32_t *seg_chunk0, int64_t n_segs, const DevChunkOut *outs,
-                              const DevSegment *segs, const int32_t *seg_bits, const DevImage *images, DevVSeg *vsegs,
-                              const uint64_t *final_exit, int cbits, int32_t *status) {
-    if (n_segs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_build_vsegs, dim3((unsigned)n_segs), dim3(256), 0, stream, chunks, seg_chunk0, outs, segs, seg_bits, images, vsegs,
-                       final_exit, cbits, status);
+hipError_t launch_build_vsegs(const LaneArgs &a, const DevChunk *chunks, const int32_t *seg_chunk0, const DevChunkOut *outs, DevVSeg *vsegs,
+                              const uint64_t *final_exit, int cbits) {
+    if (a.n_segs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_build_vsegs, dim3((unsigned)a.n_segs), dim3(256), 0, a.stream, chunks, seg_chunk0, outs, a.segs, a.seg_bits, a.images, vsegs,
+                       final_exit, cbits, a.status);
     return hipGetLastError();
 }
 

@@ -205,6 +205,24 @@ constexpr int kLaneLutBits = 11;
 constexpr int kMaxLaneTables = 8;
 // per-workgroup table lists (batches with more tables than that): entries per workgroup; 8 or 16 of them are used
 constexpr int kMaxWgTables = 16;
+// what the launches of the lane family share (api.hip fills one per execute: lane_args)
+struct LaneArgs {
+    hipStream_t stream;
+    const uint32_t *dstream; const int32_t *seg_bits;     // stage 0's output
+    const DevSegment *segs; int64_t n_segs;               // restart segments (the lane launches of the synchronisation form: virtual segments)
+    const DevImage *images;
+    const DevHuff *huff;          // the batch's n_huff tables: code books, and
+    const uint16_t *lut11;        // (len << 8 | symbol) for tables used as DC tables, (len << 11 | run << 4 | size, EOB = run 64) for AC tables
+    int n_huff;
+    int16_t *coef; int32_t *status; int transposed;
+};
+// the resolved AC tables and how the batch's tables map onto LDS slots: byte t of ac_slot_pk / dc_slot_pk = LDS slot of table t in
+// that role, byte s of dc_tab_pk = table of DC slot s
+struct ResolvedTables {
+    const uint32_t *lut13;        // [n_ac][kLanes13SlotBytes / 4]: 8192 finished symbols + second-level tables for codes of 14..16 bits
+    int n_ac, n_dc;
+    uint64_t ac_slot_pk, dc_slot_pk, dc_tab_pk;
+};
 // stage 0 (destuff.hip): per restart segment, the bytes the bit reader keeps, as big-endian dwords at dword
 // (begin >> 2) + segment index of `out_stream`; seg_bits[i] = 8 x kept bytes
 hipError_t launch_destuff(hipStream_t stream, const uint8_t *blob, const DevSegment *segs, int64_t n_segs,
@@ -213,40 +231,27 @@ hipError_t launch_scan_markers(hipStream_t stream, const uint8_t *blob, const De
                                int32_t *status);
 // one counting round: entry == nullptr -> speculative round (every chunk assumes a block starts at its first bit);
 // otherwise chunk c starts from entry[c - 1].  *changed counts the chunks whose exit state differs from prev_exit[c].
-hipError_t launch_sync_count(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs,
-                             const DevImage *images, const DevHuff *huff, const uint16_t *lut11u, int n_huff,
-                             const DevChunk *chunks, int64_t n_chunks, int cbits, const uint64_t *entry, uint64_t *exit_out,
-                             DevChunkOut *outs, int32_t *changed, const int32_t *wg_tabs = nullptr, int wg_slots = 0, const int32_t *prev_changed = nullptr,
-                             int warm_bits = -1);   // wg_tabs: per 256 chunks; warm_bits: run-up in front of every chunk, -1 = half a chunk
-// the same on resolved tables (lutc: n_tabs tables of tab_bytes each, wbits index bits: plan_create.hip's build_count_tables): the first
+hipError_t launch_sync_count(const LaneArgs &a, const uint16_t *lut11u, const DevChunk *chunks, int64_t n_chunks, int cbits, const uint64_t *entry,
+                             uint64_t *exit_out, DevChunkOut *outs, int32_t *changed, const int32_t *wg_tabs = nullptr, int wg_slots = 0,
+                             const int32_t *prev_changed = nullptr, int warm_bits = -1);   // wg_tabs: per 256 chunks; warm_bits: run-up in front of every chunk, -1 = half a chunk
+// the same on resolved tables (lutc: a.n_huff tables of tab_bytes each, wbits index bits: plan_create.hip's build_count_tables): the first
 // walk over every chunk, then — max_links > 0 — the list of chunks whose entry state was guessed wrong (items: 16 bytes per
 // chunk, *n_items) and their repair, each lane walking on for at most max_links chunks (owner: 4 bytes per chunk of scratch).
 // exit_state / outs as above.
-hipError_t launch_count(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs, const DevImage *images,
-                        const uint32_t *lutc, int tab_bytes, int n_tabs, int wbits, const DevChunk *chunks, int64_t n_chunks, int cbits,
+hipError_t launch_count(const LaneArgs &a, const uint32_t *lutc, int tab_bytes, int wbits, const DevChunk *chunks, int64_t n_chunks, int cbits,
                         int warm_bits, uint64_t *exit_state, DevChunkOut *outs, void *items, int32_t *n_items, int max_links, int32_t *owner);
-// seg_chunk0[s] = the first chunk of restart segment s (n_segs + 1 entries)
-hipError_t launch_build_vsegs(hipStream_t stream, const DevChunk *chunks, const int32_t *seg_chunk0, int64_t n_segs, const DevChunkOut *outs,
-                              const DevSegment *segs, const int32_t *seg_bits, const DevImage *images, DevVSeg *vsegs,
-                              const uint64_t *final_exit, int cbits, int32_t *status);
+// seg_chunk0[s] = the first chunk of restart segment s (a.n_segs + 1 entries)
+hipError_t launch_build_vsegs(const LaneArgs &a, const DevChunk *chunks, const int32_t *seg_chunk0, const DevChunkOut *outs, DevVSeg *vsegs,
+                              const uint64_t *final_exit, int cbits);
 hipError_t launch_destuff_pieces(hipStream_t stream, const uint8_t *blob, const DevSegment *segs, const DevPiece *pieces,
                                  int64_t n_pieces, int32_t *kept, uint32_t *out_stream, int32_t *seg_bits);
-// lut11: (len << 8 | symbol) for tables used as DC tables, (len << 11 | run << 4 | size, EOB = run 64) for AC tables
-hipError_t launch_huffman_lanes(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits,
-                                const DevSegment *segs, int64_t n_segs,
-                                const DevImage *images, const DevHuff *huff, const uint16_t *lut11, int n_huff,
-                                int16_t *coef, int32_t *status, int transposed, const DevVSeg *vsegs = nullptr,
-                                const int32_t *wg_tabs = nullptr, int wg_slots = 0);   // wg_tabs: [workgroups][kMaxWgTables]
-// the same with resolved 13-bit AC tables (huffman_lanes13.hip); lut13: [n_ac][kLanes13SlotBytes / 4]: 8192 finished symbols + second-level tables for codes of 14..16 bits, lut11 supplies the DC
-// tables; byte t of ac_slot_pk / dc_slot_pk = LDS slot of table t in that role, byte s of dc_tab_pk = table of DC slot s
+hipError_t launch_huffman_lanes(const LaneArgs &a, const DevVSeg *vsegs = nullptr, const int32_t *wg_tabs = nullptr, int wg_slots = 0);   // wg_tabs: [workgroups][kMaxWgTables]
+// the same with resolved 13-bit AC tables (huffman_lanes13.hip); a.lut11 supplies the DC tables
 constexpr int kLanes13SubTables = 144;                              // second-level tables per AC table (8 entries each)
 constexpr int kLanes13SlotBytes = 8192 * 4 + kLanes13SubTables * 32;  // one AC table in that form
 bool lanes13_fits(int n_ac, int n_dc);
-hipError_t launch_huffman_lanes13(hipStream_t stream, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs, int64_t n_segs,
-                                  const DevImage *images, const DevHuff *huff, const uint16_t *lut11, const uint32_t *lut13,
-                                  int n_ac, int n_dc, uint64_t ac_slot_pk, uint64_t dc_slot_pk, uint64_t dc_tab_pk,
-                                  int16_t *coef, int32_t *status, int transposed, const DevVSeg *vsegs,
-                                  const int32_t *by_length = nullptr, int order_mode = 0);   // by_length: segment numbers, longest first
+hipError_t launch_huffman_lanes13(const LaneArgs &a, const ResolvedTables &t, const DevVSeg *vsegs, const int32_t *by_length = nullptr,
+                                  int order_mode = 0);   // by_length: segment numbers, longest first
 // how that launch groups its units of work: lanes per wavefront (a workgroup = 4 waves = 4 x this many consecutive units)
 int lanes_per_wave(int64_t n_segs, int n_slots);
 
@@ -330,14 +335,11 @@ FusedShape fused_shape_x(int cus, int ac_total_bytes, int n_dc, int hmax, int vm
 FusedShape fused_shape(int cus, int ac_total_bytes, int n_dc, int hmax, int vmax, bool transposed, int n_images, int spi, int want_consumers,
                        int want_producers = 0);
 // spi: restart segments per image; restart_interval: MCUs per segment (any: a job's readiness is worked out per MCU)
-hipError_t launch_fused(hipStream_t stream, const FusedShape &shape, const uint32_t *dstream, const int32_t *seg_bits, const DevSegment *segs,
-                        int64_t n_segs, const DevImage *images, const DevHuff *huff, const uint16_t *lut11, const uint32_t *lut13,
-                        int n_ac, int n_dc, uint64_t ac_slot_pk, uint64_t dc_slot_pk, uint64_t dc_tab_pk, const int ac_off[4], const int ac_bits[4],
-                        int16_t *coef, int32_t *status,
-                        const ReconArgs &a, int hmax, int vmax, bool transposed, int spi, int restart_interval, int mcus_per_row, int mcu_rows,
+hipError_t launch_fused(const LaneArgs &l, const ResolvedTables &t, const FusedShape &shape, const int ac_off[4], const int ac_bits[4],
+                        const ReconArgs &a, int hmax, int vmax, int spi, int restart_interval, int mcus_per_row, int mcu_rows,
                         const int64_t *job_prefix, int64_t total_jobs, int jobs_per_image, const int32_t *by_length = nullptr,
                         const int32_t *holder = nullptr, uint32_t *x_words = nullptr);
-// (lut13 of launch_fused: the plan's fused tables, back to back — ac_off / ac_bits per LDS slot)
+// (t.lut13 of launch_fused: the plan's fused tables, back to back — ac_off / ac_bits per LDS slot)
 // Launch-geometry caches are per device: one process may hold contexts on several GPUs (mijpeg.h: one context per GPU per
 // thread), and a function attribute set on one device says nothing about the next.  Contexts on two threads may make a
 // kernel's FIRST launch at the same moment: the per-device flags are std::once_flag (OncePerDevice), the cached integers atomics.

@@ -145,12 +145,12 @@ int create_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj
     if (prefix[(size_t)n] > mj::kResizeGridX * (int64_t)65535)
         return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: %lld tiles are more than one launch takes; split the batch", fn, (long long)prefix[(size_t)n]);
     int rc;
-    if ((rc = upload(ctx, &p->d_or_images, oi.data(), oi.size())) != MJ_OK) return rc;
-    if ((rc = upload(ctx, &p->d_or_prefix, prefix.data(), prefix.size())) != MJ_OK) return rc;
+    if ((rc = upload(p, &p->d_or_images, oi.data(), oi.size())) != MJ_OK) return rc;
+    if ((rc = upload(p, &p->d_or_prefix, prefix.data(), prefix.size())) != MJ_OK) return rc;
     // the stored-order pixels: a plan-owned buffer from the context's cache (64 bytes of slack: a tile row's last 16-byte load
     // may end behind the bytes it uses)
     p->src_bytes = p->info.rgb_bytes;
-    MJ_HIP(ctx, ctx->cache.get((void **)&p->d_src, (size_t)p->src_bytes + 64));
+    MJ_HIP(ctx, alloc(p, &p->d_src, (size_t)p->src_bytes + 64));
     mj::OrientArgs &a = p->oa;
     a = mj::OrientArgs{};
     a.src = p->d_src; a.images = p->d_or_images; a.tile_prefix = p->d_or_prefix; a.total_tiles = prefix[(size_t)n];

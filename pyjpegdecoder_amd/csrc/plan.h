@@ -26,6 +26,7 @@ struct DevBufferCache {
     size_t cached_bytes = 0, limit_bytes = 0;
     uint64_t clock = 0;
     uint64_t n_hit = 0, n_miss = 0, n_evict = 0;    // MJ_CACHE_STATS=1 prints them when the context goes
+    uint64_t n_get = 0, size_hash = 0;              // requests so far and a running hash of their sizes, in order (mj_debug_cache_stats)
     static size_t bucket(size_t n) {
         if (n <= 4096) return 4096;
         size_t p2 = (size_t)1 << (63 - __builtin_clzll((unsigned long long)n));
@@ -34,6 +35,8 @@ struct DevBufferCache {
     }
     hipError_t get(void **out, size_t bytes) {
         const size_t want = bucket(bytes);
+        ++n_get;
+        size_hash = size_hash * 0x100000001b3ull + bytes;
         int best = -1;
         for (int i = 0; i < (int)free_blocks.size(); ++i)
             if (free_blocks[i].size == want && (best < 0 || free_blocks[i].stamp > free_blocks[best].stamp)) best = i;
@@ -51,26 +54,22 @@ struct DevBufferCache {
         live.push_back({*out, want, 0});
         return hipSuccess;
     }
-    void put(void *ptr) {
+    // takes ptr off the list of blocks handed out; false: not one of ours
+    bool take(void *ptr, Block *b) {
         for (size_t i = 0; i < live.size(); ++i)
-            if (live[i].ptr == ptr) {
-                Block b = live[i];
-                live[i] = live.back();
-                live.pop_back();
-                b.stamp = ++clock;
-                free_blocks.push_back(b);
-                cached_bytes += b.size;
-                trim(limit_bytes);
-                return;
-            }
-        (void)hipFree(ptr);             // not one of ours
+            if (live[i].ptr == ptr) { *b = live[i]; live[i] = live.back(); live.pop_back(); return true; }
+        return false;
+    }
+    void put(void *ptr) {
+        Block b;
+        if (!take(ptr, &b)) { (void)hipFree(ptr); return; }
+        b.stamp = ++clock;
+        free_blocks.push_back(b);
+        cached_bytes += b.size;
+        trim(limit_bytes);
     }
     // hand a live block back to the device instead of keeping it for the next plan (mj_plan_tune_placement's losing candidates)
-    void drop(void *ptr) {
-        for (size_t i = 0; i < live.size(); ++i)
-            if (live[i].ptr == ptr) { live[i] = live.back(); live.pop_back(); break; }
-        (void)hipFree(ptr);
-    }
+    void drop(void *ptr) { Block b; (void)take(ptr, &b); (void)hipFree(ptr); }
     void trim(size_t keep) {
         while (cached_bytes > keep && !free_blocks.empty()) {
             int old = 0;
@@ -115,6 +114,11 @@ extern std::string g_create_err;     // what mj_last_error(NULL) returns (api.hi
 
 struct mj_plan {
     mj_context *ctx = nullptr;
+    // every device block the plan holds from ctx->cache, in the order it took them (alloc / upload below enter them;
+    // mj_plan_destroy returns the list).  The typed d_* fields further down only name them for the kernels' arguments.
+    std::vector<void *> blocks;
+    // `old`'s entry now names `now` (mj_plan_tune_placement: a better-placed block)
+    void swap_block(void *old, void *now) { std::replace(blocks.begin(), blocks.end(), old, now); }
     int32_t n_images = 0;
     int32_t layout = 0;
     uint32_t flags = 0;
@@ -333,10 +337,24 @@ int fail(mj_context *ctx, int code, const char *fmt, ...) {
             return fail((ctx), MJ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// a host array into a device buffer from the context's cache — through the plan's pinned arena on the setup stream where it fits
+// a device buffer of the plan's, from its context's cache
 template <typename T>
-int upload(mj_context *ctx, T **dst, const T *src, size_t n, size_t pad_bytes = 0) {
-    MJ_HIP(ctx, ctx->cache.get((void **)dst, n * sizeof(T) + pad_bytes + 16));
+hipError_t alloc(mj_plan *p, T **dst, size_t bytes) {
+    if (*dst) {         // a field that holds a block already (fused_tables' second try) gives it back first
+        p->ctx->cache.put(*dst);
+        p->blocks.erase(std::find(p->blocks.begin(), p->blocks.end(), (void *)*dst));
+        *dst = nullptr;
+    }
+    const hipError_t e = p->ctx->cache.get((void **)dst, bytes);
+    if (e == hipSuccess) p->blocks.push_back(*dst);
+    return e;
+}
+
+// a host array into such a buffer — through the plan's pinned arena on the setup stream where it fits
+template <typename T>
+int upload(mj_plan *p, T **dst, const T *src, size_t n, size_t pad_bytes = 0) {
+    mj_context *ctx = p->ctx;
+    MJ_HIP(ctx, alloc(p, dst, n * sizeof(T) + pad_bytes + 16));
     if (pad_bytes) MJ_HIP(ctx, hipMemsetAsync((char *)*dst + n * sizeof(T), 0, pad_bytes, ctx->setup_stream));
     const size_t bytes = n * sizeof(T);
     if (!bytes) return MJ_OK;

@@ -218,9 +218,9 @@ int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, Prog
     std::vector<mj::DevProgScan> &pscans = S.pscans;
     std::vector<mj::DevProgSeg> &psegs = S.psegs;
     int rc;
-    if ((rc = upload(ctx, &p->d_pscans, pscans.data(), pscans.size())) != MJ_OK) return rc;
+    if ((rc = upload(p, &p->d_pscans, pscans.data(), pscans.size())) != MJ_OK) return rc;
     p->n_psegs = (int64_t)psegs.size();
-    MJ_HIP(ctx, ctx->cache.get((void **)&p->d_pstates, psegs.size() * sizeof(mj::DevProgState) + 16));
+    MJ_HIP(ctx, alloc(p, &p->d_pstates, psegs.size() * sizeof(mj::DevProgState) + 16));
     // DC/AC first scans and AC refining scans walk the stage-0 stream (progressive_fast.hip)
     // (a plan none of whose scans they take — non-interleaved baseline files, DC refinement only — needs neither the
     // stage-0 stream nor its pass per execute)
@@ -241,14 +241,14 @@ int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, Prog
             for (int off = 0; off == 0 || off < g.len; off += 16384)
                 pcs.push_back(mj::DevPiece{(int32_t)n, first, off, std::min(16384, std::max(0, g.len - off))});
         }
-        if ((rc = upload(ctx, &p->d_prog_dsegs, ds.data(), ds.size())) != MJ_OK) return rc;
+        if ((rc = upload(p, &p->d_prog_dsegs, ds.data(), ds.size())) != MJ_OK) return rc;
         p->n_pieces = (int64_t)pcs.size();
-        if ((rc = upload(ctx, &p->d_pieces, pcs.data(), pcs.size())) != MJ_OK) return rc;
-        MJ_HIP(ctx, ctx->cache.get((void **)&p->d_piece_kept, pcs.size() * sizeof(int32_t) + 16));
+        if ((rc = upload(p, &p->d_pieces, pcs.data(), pcs.size())) != MJ_OK) return rc;
+        MJ_HIP(ctx, alloc(p, &p->d_piece_kept, pcs.size() * sizeof(int32_t) + 16));
         const size_t sbytes = ((size_t)b->blob_len / 4 + psegs.size() + 256) * 4;
-        MJ_HIP(ctx, ctx->cache.get((void **)&p->d_stream, sbytes));
+        MJ_HIP(ctx, alloc(p, &p->d_stream, sbytes));
         MJ_HIP(ctx, hipMemsetAsync(p->d_stream, 0, sbytes, ctx->setup_stream));
-        MJ_HIP(ctx, ctx->cache.get((void **)&p->d_seg_bits, (psegs.size() + 1) * sizeof(int32_t)));
+        MJ_HIP(ctx, alloc(p, &p->d_seg_bits, (psegs.size() + 1) * sizeof(int32_t)));
         const int LS = 1 << mj::kProgLutBits;
         std::vector<uint16_t> lp((size_t)b->n_huff * LS, 0);
         for (int t = 0; t < b->n_huff; ++t) {
@@ -265,7 +265,7 @@ int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, Prog
                 }
             }
         }
-        if ((rc = upload(ctx, &p->d_lut11p, lp.data(), lp.size())) != MJ_OK) return rc;
+        if ((rc = upload(p, &p->d_lut11p, lp.data(), lp.size())) != MJ_OK) return rc;
         if (p->prog_chunks && p->n_psegs_wave < (int64_t)psegs.size()) {
             // the chunked first AC scans (progressive_chunks.hip): their segments, the chunk list — padded to whole wavefronts
             // per segment, so that a wavefront's lanes share a table —, and per table the 9-bit LUT + canonical code book
@@ -307,21 +307,21 @@ int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, Prog
                 for (int i = 0; i < 256; ++i) vals[i] = b->huff[t].vals[i];
             }
             p->n_acsegs = (int)as.size(); p->n_pc_chunks = (int64_t)ck.size();
-            if ((rc = upload(ctx, &p->d_acsegs, as.data(), as.size())) != MJ_OK) return rc;
-            if ((rc = upload(ctx, &p->d_pc_chunks, ck.data(), ck.size())) != MJ_OK) return rc;
-            if ((rc = upload(ctx, &p->d_pc_tabs, tb.data(), tb.size())) != MJ_OK) return rc;
-            MJ_HIP(ctx, ctx->cache.get((void **)&p->d_pc_exit, ck.size() * 8 + 16));
-            MJ_HIP(ctx, ctx->cache.get((void **)&p->d_pc_outs, ck.size() * sizeof(mj::DevChunkOut) + 16));
-            MJ_HIP(ctx, ctx->cache.get((void **)&p->d_pc_items, ck.size() * 16 + 16));
-            MJ_HIP(ctx, ctx->cache.get((void **)&p->d_pc_owner, ck.size() * 8 + 128));     // (+ the work list's counter behind it, + a lock word per chunk behind that)
-            MJ_HIP(ctx, ctx->cache.get((void **)&p->d_pc_vsegs, ck.size() * sizeof(mj::DevVSeg) + 16));
+            if ((rc = upload(p, &p->d_acsegs, as.data(), as.size())) != MJ_OK) return rc;
+            if ((rc = upload(p, &p->d_pc_chunks, ck.data(), ck.size())) != MJ_OK) return rc;
+            if ((rc = upload(p, &p->d_pc_tabs, tb.data(), tb.size())) != MJ_OK) return rc;
+            MJ_HIP(ctx, alloc(p, &p->d_pc_exit, ck.size() * 8 + 16));
+            MJ_HIP(ctx, alloc(p, &p->d_pc_outs, ck.size() * sizeof(mj::DevChunkOut) + 16));
+            MJ_HIP(ctx, alloc(p, &p->d_pc_items, ck.size() * 16 + 16));
+            MJ_HIP(ctx, alloc(p, &p->d_pc_owner, ck.size() * 8 + 128));     // (+ the work list's counter behind it, + a lock word per chunk behind that)
+            MJ_HIP(ctx, alloc(p, &p->d_pc_vsegs, ck.size() * sizeof(mj::DevVSeg) + 16));
         } else {
             p->prog_chunks = false;
         }
     }
-    if ((rc = upload(ctx, &p->d_psegs, psegs.data(), psegs.size())) != MJ_OK) return rc;
+    if ((rc = upload(p, &p->d_psegs, psegs.data(), psegs.size())) != MJ_OK) return rc;
     if (p->n_split)     // by segment (the first n_split of them), two sets: even and odd bands
-        MJ_HIP(ctx, ctx->cache.get((void **)&p->d_psubs, (size_t)p->n_split * 2 * mj::kProgSub * sizeof(mj::DevProgSub)));
+        MJ_HIP(ctx, alloc(p, &p->d_psubs, (size_t)p->n_split * 2 * mj::kProgSub * sizeof(mj::DevProgSub)));
     return MJ_OK;
 }
 

@@ -407,8 +407,8 @@ int create_resized(const ResizeRequest &q) {
     if (n_tiles > mj::kResizeGridX * (int64_t)65535)
         return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: %lld tiles are more than one launch takes; split the batch", fn, (long long)n_tiles);
     a.n_images = n; a.ow = out_width; a.oh = out_height; a.layout = p->layout;
-    if (int rc = upload(ctx, &p->d_rz_images, ri.data(), ri.size())) return rc;
-    if (int rc = upload(ctx, &p->d_rz_tabs, tabs.words.data(), tabs.words.size())) return rc;
+    if (int rc = upload(p, &p->d_rz_images, ri.data(), ri.size())) return rc;
+    if (int rc = upload(p, &p->d_rz_tabs, tabs.words.data(), tabs.words.size())) return rc;
     a.orient = orient ? (swapped ? 2 : 1) : 0;
     a.sgn = tabs.sgn ? 1 : 0;
     p->rz_filter = filter;
@@ -419,18 +419,18 @@ int create_resized(const ResizeRequest &q) {
         for (int c = 0; c < CO && fill; ++c) p->rz_fill |= (unsigned)fill[c] << (8 * c);       // (one byte per output component; fill NULL: zeros)
     }
     if (any_mirror || orient || mode || places) {       // (no flag set: the instances without mirror; a plan that converts: oriented-style instances only)
-        if (int rc = upload(ctx, &p->d_rz_mirror, flags.data(), flags.size())) return rc;
+        if (int rc = upload(p, &p->d_rz_mirror, flags.data(), flags.size())) return rc;
         a.mirror = p->d_rz_mirror;
     }
     if (esize > 1) {
         const std::vector<uint8_t> lut = output_table(*output, CO, esize);
-        if (int rc = upload(ctx, &p->d_rz_lut, lut.data(), lut.size())) return rc;
+        if (int rc = upload(p, &p->d_rz_lut, lut.data(), lut.size())) return rc;
         a.lut = p->d_rz_lut;
     }
     // the un-resized pixels: a plan-owned buffer from the context's cache (64 bytes of slack: the kernels' 16-byte loads may
     // start before and end behind the bytes they use)
     p->src_bytes = p->info.rgb_bytes;
-    MJ_HIP(ctx, ctx->cache.get((void **)&p->d_src, (size_t)p->src_bytes + 64));
+    MJ_HIP(ctx, alloc(p, &p->d_src, (size_t)p->src_bytes + 64));
     a.images = p->d_rz_images; a.tabs = p->d_rz_tabs; a.src = p->d_src;
     p->info.rgb_bytes = (int64_t)n_slots * out_image;
     p->info.total_pixels = (int64_t)n_slots * out_width * out_height;

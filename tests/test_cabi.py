@@ -29,6 +29,36 @@ def test_exports_every_declared_symbol(lib):
     assert lib.mj_version() == 1
 
 
+def test_plan_shape_and_cache_accessors_are_exported_and_declared_as_c(lib, tmp_path):
+    """mj_debug_plan_shape / mj_debug_cache_stats (tests/test_plan_shapes.py reads plans through them on the GPU): exported, their
+    prototypes the ones the binding assumes, and without a plan or a context they refuse instead of reading."""
+    import shutil
+    import subprocess
+    from pyjpegdecoder_amd import _binding as B
+    for name in ("mj_debug_plan_shape", "mj_debug_cache_stats"):
+        assert name in B.EXPORTS and hasattr(lib, name), name
+    header = (ROOT / "include" / "mijpeg.h").read_text()
+    assert int(re.search(r"#define MJ_DEBUG_PLAN_SHAPE_WORDS (\d+)", header).group(1)) == B.PLAN_SHAPE_WORDS
+    out, stats = (ctypes.c_int32 * B.PLAN_SHAPE_WORDS)(), (ctypes.c_uint64 * 4)()
+    assert lib.mj_debug_plan_shape(None, out, B.PLAN_SHAPE_WORDS) == B.MJ_ERR_INVALID
+    assert lib.mj_debug_cache_stats(None, stats) == B.MJ_ERR_INVALID
+    gcc = shutil.which("gcc")
+    if gcc is not None:         # a mismatch with the header's declarations is a compile error
+        src = tmp_path / "proto.c"
+        src.write_text("""
+#include "mijpeg.h"
+int main(void) {
+  int (*a)(const mj_plan *, int32_t *, int32_t) = mj_debug_plan_shape;
+  int (*b)(const mj_context *, uint64_t *) = mj_debug_cache_stats;
+  int words[MJ_DEBUG_PLAN_SHAPE_WORDS >= 38 ? 1 : -1] = {0};
+  (void)a; (void)b; (void)words;
+  return 0;
+}
+""")
+        subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include"), "-c", str(src), "-o", str(tmp_path / "proto.o")],
+                       check=True)
+
+
 def test_library_idct_table_is_the_reference_table(lib):
     tt = np.empty(4096, dtype=np.float64)
     lib.mj_host_idct_table(tt.ctypes.data_as(ctypes.c_void_p))
