@@ -186,60 +186,29 @@ int mj_version(void);
 int mj_context_wait_event(mj_context *ctx, void *hip_event);
 
 /* ---- plan: upload once, execute many times (bench.py times mj_plan_execute only) ------------------ */
-int mj_plan_create(mj_context *ctx, const mj_batch *batch, mj_plan **out);
-/* Region-of-interest decode: a plan whose output for image i is the window rois[i] of the image — x along image_width,
- * y along image_height — and nothing else.  rois: host, batch->n_images entries; NULL = whole images (then the same as
- * mj_plan_create, except that the plan never takes the fused launch).  Window i in the plan's layout:
- *   MJ_LAYOUT_XMAJOR    full[x:x+width, y:y+height]      of the (W, H, C) image
- *   MJ_LAYOUT_ROWMAJOR  full_rm[y:y+height, x:x+width]   of the (H, W, C) image
- *   planar layouts      the same windows, one component after another (greyscale: one component)
- * Outputs are packed window after window: mj_plan_info.total_pixels / rgb_bytes are sums over the windows and
- * mj_plan_image_offsets' rgb_off lies in that packing.  A pixel depends only on the MCU that covers it (the reference
- * upsamples inside the MCU), so a window is bit-exact: the whole image's decode, sliced.
- * Only the restart segments that hold an MCU of the window are decoded (host-segmented baseline batches list only those;
- * MJ_FLAG_GPU_SEGMENT batches gather them after the marker scan).  Files without restart markers, progressive and
- * non-interleaved batches decode every scan whole; stage 2 runs on the windows' MCUs only.
- * Status: status[i] reports what the DECODED segments found — a damaged restart segment outside the window does not fail
- * the image (the marker scan of MJ_FLAG_GPU_SEGMENT still checks every marker of the image).
- * MJ_ERR_INVALID (message naming the image): an empty window or one not inside its image; MJ_FLAG_KEEP_PLANES /
- * MJ_FLAG_KEEP_IDCT (the seam outputs are whole-image). */
+/* What a plan's output is to be, beyond the batch itself: every feature is one field of mj_plan_request, specified where the
+ * field is declared below.  A zeroed request asks for nothing — the plain plan: every image whole, as stored, in the files' own
+ * components, at its own size, packed image after image — and every field whose value is its DEFAULT (named with the field)
+ * gives exactly the plan of the request without it: the library turns such a field into its absence before anything is made,
+ * so the same code makes the plan and the same kernels run it.  All arrays are host memory with batch->n_images entries, read
+ * during the call only.
+ *
+ * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
+ * window -> resize with the filter (to the place's size, onto the canvas) -> mirror -> the output's element type.  In Pillow's
+ * terms the result is exif_transpose(img.convert(mode)).crop(window).resize(size, filter).
+ *
+ * Refusals common to all fields: MJ_ERR_INVALID with a message in mj_last_error — naming the image where there is one — for a
+ * value outside what the field takes; MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT together with ANY field that changes the plan
+ * (the seam outputs are whole images in stored order, in the files' components, at the files' sizes; a window plan refuses
+ * MJ_FLAG_KEEP_COEF too).  Checked in this order, the first fault reported: filter, mode, orientations, output — these before
+ * the context is looked at, so that a bad description is diagnosed without a GPU (the message is then mj_last_error(NULL)'s) —,
+ * ctx / batch / out, the size, the KEEP flags, slots, places, windows, then the batch itself. */
 typedef struct {
     int32_t x, y, width, height;
 } mj_roi;
-int mj_plan_create_roi(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, mj_plan **out);
-/* Decode to a fixed size: a window plan (rois != NULL, as mj_plan_create_roi) or a plan of whole images (rois == NULL, as
- * mj_plan_create) whose output is every image — or window — resized to out_width x out_height: ONE dense array of n_slots images
- * in the plan's layout,
- *   MJ_LAYOUT_XMAJOR (n_slots, out_width, out_height, C)    MJ_LAYOUT_PLANAR_XMAJOR   (n_slots, C, out_width, out_height)
- *   MJ_LAYOUT_ROWMAJOR (n_slots, out_height, out_width, C)  MJ_LAYOUT_PLANAR_ROWMAJOR (n_slots, C, out_height, out_width)
- * (C = the batch's component count), and mj_plan_info.rgb_bytes = n_slots * out_width * out_height * C is that array's size.
- * slots: host, n_images entries, image k goes to slot slots[k] < n_slots — several plans can fill one array this way (files of
- * several kinds are one plan per kind); slots the plan does not name are not touched.  NULL: slot k, and n_slots is ignored.
- * The resize is Pillow's Image.resize((out_width, out_height), Image.BILINEAR) of the row-major window, byte for byte: integer
- * taps from triangle weights whose support grows with the scale when shrinking (antialiased), along the width first, then the
- * height, with an 8-bit image in between (mj_host_resize_table; csrc/resize.hip).  mj_plan_execute runs stage 1, stage 2 — into
- * a buffer of the files' own sizes that the plan owns — and the resize as its last launch; mj_plan_execute_stage2 includes it.
- * MJ_ERR_INVALID: a size outside 1..65535, a slot outside n_slots, MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT, and whatever
- * mj_plan_create_roi refuses; MJ_ERR_UNSUPPORTED: a shrink so strong that one pixel's taps do not fit a workgroup's LDS, or
- * more output tiles than one launch takes (about 6.8e10: split the batch). */
-int mj_plan_create_resized(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                           const int32_t *slots, int32_t n_slots, mj_plan **out);
-/* Model-ready output: mj_plan_create_resized whose dense array holds, instead of the resized bytes, what a model takes —
- * elements of `dtype`, normalised, some images mirrored.  Everything mj_plan_create_resized says holds; in addition:
- *   dtype      MJ_DTYPE_U8: the resized byte itself.  MJ_DTYPE_F32: for a resized byte v of component c, torchvision's
- *              Normalize(mean, std)(to_tensor(img)) in float32, every operation rounded on its own,
- *                  y = fl32( fl32( fl32( float(v) / 255.0f ) - mean[c] ) / std[c] )
- *              (normalize == 0: mean 0, std 1, i.e. v / 255).  MJ_DTYPE_F16 / MJ_DTYPE_BF16: y rounded to nearest even to IEEE
- *              binary16 / bfloat16.  The resized bytes are those of mj_plan_create_resized: the function is applied to the
- *              integer result of the two passes, as the height pass stores it (mj_host_normalize_table is its table).
- *   normalize  0 or 1; with 1, mean[c] and std[c] for the batch's components (the rest ignored), in units of value / 255.
- *   mirror     NULL, or host, n_images flags: image k with mirror[k] != 0 is stored flipped along its width axis — element
- *              (x, y, c) of the un-mirrored result goes to column out_width - 1 - x, in whichever layout.  Any dtype.
- * mj_plan_info.rgb_bytes of such a plan is in BYTES of the chosen type: n_slots * out_width * out_height * C * (1, 2 or 4).  It
- * is what mj_plan_execute's rgb_device buffer must hold and what mj_plan_read's rgb copies; slot offsets scale likewise.
- * output == NULL, or {MJ_DTYPE_U8, 0, .., NULL}: exactly mj_plan_create_resized, the same kernels.
- * MJ_ERR_INVALID (with a message): a dtype that is none of the four, normalize with MJ_DTYPE_U8, a mean that is not finite,
- * a std that is not finite or not > 0 — checked before anything else is done. */
+#define MJ_MODE_NATIVE 0
+#define MJ_MODE_L      1
+#define MJ_MODE_RGB    3
 #define MJ_DTYPE_U8   0
 #define MJ_DTYPE_F16  1
 #define MJ_DTYPE_BF16 2
@@ -250,103 +219,137 @@ typedef struct {
     float mean[3], std[3];
     const uint8_t *mirror;      /* NULL, or one flag per image of the batch */
 } mj_output_desc;
-int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                              const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out);
-/* EXIF orientation: plans whose outputs are the images as their Orientation tag (1..8) says they are to be shown — exactly
- * Pillow's ImageOps.exif_transpose (tools/orient_model.py): 1 as stored, 2 left-right flip, 3 rotated by 180, 4 top-bottom flip,
- * 5 transposed, 6 ROTATE_270, 7 transverse, 8 ROTATE_90; 5..8 exchange width and height.
- * orientations: host, one byte per image.  NULL, or all of them 1: exactly the plan mj_plan_create / mj_plan_create_roi /
- * mj_plan_create_resized(_as) gives for the other arguments.  MJ_ERR_INVALID naming the image for a byte outside 1..8;
- * MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT are refused (the seam outputs are in stored order).
- * rois (may be NULL) are windows of the ORIENTED images; the library maps them to the stored images (orient_model.stored_window)
- * and the plan is a window plan of those: restart segments and MCUs outside them are skipped as ever.
- *   mj_plan_create_oriented           outputs at the files' own sizes, packed image after image as mj_plan_create's are — an image
- *     keeps its offset (mj_plan_image_offsets) and its size in bytes; its shape in the plan's layout is the oriented one.
- *     Stage 2 writes into a plan-owned buffer in stored order and one more launch (csrc/orient.hip) writes every image oriented
- *     into the caller's output; mj_plan_fill_source / mj_plan_time_resize work on that buffer / launch.
- *   mj_plan_create_resized_oriented   mj_plan_create_resized_as (output may be NULL) of the oriented images or windows: element by
- *     element Pillow's resize of the oriented pixels, inside the one resize launch — no extra pass over memory.  output->mirror
- *     applies after the orientation.  All images of such a plan either exchange width and height (5..8) or do not:
- *     MJ_ERR_UNSUPPORTED naming the first image that differs from image 0 otherwise (two plans into one array, with slots). */
-int mj_plan_create_oriented(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, const uint8_t *orientations, mj_plan **out);
-int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
-                                    mj_plan **out);
-/* Resample filters: mj_plan_create_resized_oriented (output and orientations may be NULL, as there) whose resize is Pillow's
- * Image.resize((out_width, out_height), <filter>) for any of its convolution filters — byte for byte, in every layout, with
- * everything the other arguments do (dtype, normalisation, mirror, orientation, windows, slots) inside the same one launch.
- *   MJ_FILTER_BILINEAR  support 1    exactly mj_plan_create_resized_oriented: the same plan, the same kernels
- *   MJ_FILTER_BOX       support 0.5  1 on (-0.5, 0.5]
- *   MJ_FILTER_HAMMING   support 1    sinc(x) * (0.54 + 0.46 cos(pi x))
- *   MJ_FILTER_BICUBIC   support 2    Keys' cubic with a = -0.5
- *   MJ_FILTER_LANCZOS   support 3    sinc(x) * sinc(x / 3) on [-3, 3)
- * (Pillow's NEAREST is not a convolution — it walks an affine transform — and is not offered.)  The support grows with the scale
- * when shrinking; weights in doubles, normalised, rounded away from zero to 22 bits (mj_host_resize_table_filtered); per pixel
- * clip((2^21 + sum taps * in) >> 22, 0, 255) with a signed sum and an arithmetic shift: the taps of BICUBIC and LANCZOS are
- * negative in their side lobes, and plans of those two run signed instances of the resize kernels (the other three share the
- * unsigned ones: their taps are >= 0).  Width first, then height, an 8-bit image in between, as ever.
- * MJ_ERR_INVALID: a filter that is none of these, and whatever mj_plan_create_resized_oriented refuses; MJ_ERR_UNSUPPORTED, in
- * addition to that function's: a table with a tap of 2^23 or more in magnitude or with 2^21 + 255 * sum |tap| above 2^31 - 1
- * (the kernels multiply in 24 bits and add in 32; no size up to 129 comes near either bound). */
 #define MJ_FILTER_BILINEAR 0
 #define MJ_FILTER_BOX      1
 #define MJ_FILTER_HAMMING  2
 #define MJ_FILTER_BICUBIC  3
 #define MJ_FILTER_LANCZOS  4
-int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
-                                    int32_t filter, mj_plan **out);
-/* Output colour mode: plans whose outputs have the components the CALLER names instead of the files' — Pillow's img.convert(mode)
- * (tools/mode_model.py) of the decoded pixels, before everything else: the result is exif_transpose(img.convert(mode)) and, resized,
- * .resize(size, filter) of that.
- *   MJ_MODE_NATIVE  the files' own components
- *   MJ_MODE_L       one component.  A colour image's pixel becomes L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the RGB bytes
- *                   a plan without the mode gives (not the file's Y plane: the colour conversion's rounding lies in between)
- *   MJ_MODE_RGB     three components.  A greyscale image's byte goes into all three
- * MJ_MODE_NATIVE, or the mode that is the batch's own component count (its first image's), returns exactly the plan the function
- * without the argument returns: the same code makes it.  Any other value: MJ_ERR_INVALID.  A plan that converts:
- *   mj_plan_info.rgb_bytes, the slots' offsets and mj_plan_image_offsets' rgb_off count OUTPUT components; output->mean / std
- *   are read for the mode's components (a greyscale file under MJ_MODE_RGB gets three tables applied to its one byte);
- *   MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT are refused (the seam outputs are in the files' components).
- *   mj_plan_create_resized_mode   mj_plan_create_resized_filtered plus the mode.  The resize launch converts: colour to L where the
- *     source is read, in front of the width pass (resize-then-convert is another result), grey to RGB where the output is stored;
- *     both passes run on one component, and no extra pass over memory is made in either direction.
- *   mj_plan_create_mode           mj_plan_create_oriented plus the mode (orientations may be NULL): outputs at the files' own sizes,
- *     packed image after image, every image width * height * <the mode's components> bytes.  The one extra launch of an oriented plan
- *     (csrc/orient.hip) converts on its way; a plan that converts has that launch for upright images too.
- *   mj_host_convert_mode          the host twin of the kernels' conversion (no context): n_pixels pixels of src_ncomp (1 or 3)
- *     interleaved components into out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an
- *     unknown mode, a src_ncomp that is neither 1 nor 3, NULL with pixels to convert. */
-#define MJ_MODE_NATIVE 0
-#define MJ_MODE_L      1
-#define MJ_MODE_RGB    3
-int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
-                                int32_t filter, int32_t mode, mj_plan **out);
-int mj_plan_create_mode(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, const uint8_t *orientations, int32_t mode, mj_plan **out);
-int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out);
-/* Aspect-preserving sizing: mj_plan_create_resized_mode whose images are not stretched over out_width x out_height — that is now a
- * CANVAS — but resized each to a size of its own and placed on it (tools/place_model.py): torchvision's Resize(s) + CenterCrop, a
- * letterbox (Pillow's ImageOps.pad), a crop of the resized image, all in the one resize launch.
- *   places[k]  width, height: the size image k (oriented, or its window) is resized to, 1..65535 each.  x, y: where its top-left
- *              lies on the canvas, |x|, |y| <= 65535 — negative: the image is cropped there, positive: padded.
- *   fill       one byte per OUTPUT component (fill[0] alone for one component); NULL: zeros.
- * Canvas element (ox, oy, c) of image k is the byte Image.resize((width_k, height_k), filter) has at (ox - x_k, oy - y_k) where
- * that lies inside the resized image, fill[c] elsewhere; either byte then takes the output's path (the dtype's table, the
- * normalisation: the fill is a byte that gets normalised, as torchvision's pad before ToTensor yields).  The mode converts first,
- * the geometry refers to the oriented image or window, and a mirror flag flips the finished canvas, padding included.
- * Only the canvas's elements are computed.  With windows, only the source rows and columns whose taps reach the canvas are
- * decoded: every window shrinks to that range (mj_plan_time_resize's source_bytes counts what was decoded); whole images are
- * decoded whole, which measured faster (option MJ_PLACE_WINDOW, csrc/resize.hip).
- * places == NULL, or every place {out_width, out_height, 0, 0}: exactly the plan mj_plan_create_resized_mode returns, made by the
- * same code.  MJ_ERR_INVALID naming the image: a size or offset outside the ranges above, an image that does not meet the canvas. */
 typedef struct {
     int32_t width, height;
     int32_t x, y;
 } mj_place;
-int mj_plan_create_resized_placed(mj_context *ctx, const mj_batch *batch, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                  const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
-                                  int32_t filter, int32_t mode, const mj_place *places, const uint8_t fill[3], mj_plan **out);
+typedef struct {
+    /* Region of interest.  DEFAULT NULL: whole images.  Else the output for image i is the window rois[i] of the image — x along
+     * image_width, y along image_height — and nothing else.  Window i in the plan's layout:
+     *   MJ_LAYOUT_XMAJOR    full[x:x+width, y:y+height]      of the (W, H, C) image
+     *   MJ_LAYOUT_ROWMAJOR  full_rm[y:y+height, x:x+width]   of the (H, W, C) image
+     *   planar layouts      the same windows, one component after another (greyscale: one component)
+     * Outputs are packed window after window: mj_plan_info.total_pixels / rgb_bytes are sums over the windows and
+     * mj_plan_image_offsets' rgb_off lies in that packing.  A pixel depends only on the MCU that covers it (the reference
+     * upsamples inside the MCU), so a window is bit-exact: the whole image's decode, sliced.
+     * Only the restart segments that hold an MCU of the window are decoded (host-segmented baseline batches list only those;
+     * MJ_FLAG_GPU_SEGMENT batches gather them after the marker scan).  Files without restart markers, progressive and
+     * non-interleaved batches decode every scan whole; stage 2 runs on the windows' MCUs only.
+     * Status: status[i] reports what the DECODED segments found — a damaged restart segment outside the window does not fail
+     * the image (the marker scan of MJ_FLAG_GPU_SEGMENT still checks every marker of the image).
+     * A plan with windows — windows that are the whole images included — never takes the fused launch (MJ_FORM_FUSED); a
+     * request without windows makes the plain plan, which may.  With orientations the windows are windows of the ORIENTED
+     * images; the library maps them to the stored images (orient_model.stored_window) and the plan is a window plan of those.
+     * MJ_ERR_INVALID: an empty window or one not inside its (oriented) image. */
+    const mj_roi *rois;
+    /* EXIF orientation, one byte 1..8 per image.  DEFAULT NULL, or all of them 1: as stored.  Else the outputs are the images
+     * as their Orientation tag says they are to be shown — exactly Pillow's ImageOps.exif_transpose (tools/orient_model.py): 1 as
+     * stored, 2 left-right flip, 3 rotated by 180, 4 top-bottom flip, 5 transposed, 6 ROTATE_270, 7 transverse, 8 ROTATE_90;
+     * 5..8 exchange width and height.
+     *   without a size   outputs packed image after image as the plain plan's are — an image keeps its offset
+     *     (mj_plan_image_offsets) and its size in bytes; its shape in the plan's layout is the oriented one.  Stage 2 writes into a
+     *     plan-owned buffer in stored order and one more launch (csrc/orient.hip) writes every image oriented into the caller's
+     *     output; mj_plan_fill_source / mj_plan_time_resize work on that buffer / launch.
+     *   with a size      element by element Pillow's resize of the oriented pixels, inside the one resize launch — no extra pass
+     *     over memory.  output->mirror applies after the orientation.  All images of such a plan either exchange width and height
+     *     (5..8) or do not: MJ_ERR_UNSUPPORTED naming the first image that differs from image 0 otherwise (two plans into one
+     *     array, with slots). */
+    const uint8_t *orientations;
+    /* Output colour mode, MJ_MODE_*.  DEFAULT MJ_MODE_NATIVE (0), or the mode that is the batch's own component count (its first
+     * image's): the files' own components.  Else the outputs have the components the CALLER names — Pillow's img.convert(mode)
+     * (tools/mode_model.py) of the decoded pixels, before everything else.
+     *   MJ_MODE_L       one component.  A colour image's pixel becomes L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the RGB
+     *                   bytes a plan without the mode gives (not the file's Y plane: the colour conversion's rounding lies in between)
+     *   MJ_MODE_RGB     three components.  A greyscale image's byte goes into all three
+     * A plan that converts: mj_plan_info.rgb_bytes, the slots' offsets and mj_plan_image_offsets' rgb_off count OUTPUT components;
+     * output->mean / std are read for the mode's components (a greyscale file under MJ_MODE_RGB gets three tables applied to its
+     * one byte).
+     *   without a size   outputs packed image after image, every image width * height * <the mode's components> bytes.  The one
+     *     extra launch of an oriented plan (csrc/orient.hip) converts on its way; a plan that converts has that launch for upright
+     *     images too.
+     *   with a size      the resize launch converts: colour to L where the source is read, in front of the width pass (resize-then-
+     *     convert is another result), grey to RGB where the output is stored; both passes run on one component, and no extra pass
+     *     over memory is made in either direction.
+     * mj_host_convert_mode is the host twin of the kernels' conversion. */
+    int32_t mode;
+    /* Decode to a fixed size.  DEFAULT both 0: outputs at the files' own sizes.  Else, both 1..65535, the output is every image —
+     * or window — resized to out_width x out_height: ONE dense array of n_slots images in the plan's layout,
+     *   MJ_LAYOUT_XMAJOR (n_slots, out_width, out_height, C)    MJ_LAYOUT_PLANAR_XMAJOR   (n_slots, C, out_width, out_height)
+     *   MJ_LAYOUT_ROWMAJOR (n_slots, out_height, out_width, C)  MJ_LAYOUT_PLANAR_ROWMAJOR (n_slots, C, out_height, out_width)
+     * (C = the output's component count), and mj_plan_info.rgb_bytes = n_slots * out_width * out_height * C is that array's size.
+     * The resize is Pillow's Image.resize((out_width, out_height), filter) of the row-major image, byte for byte: integer taps
+     * from the filter's weights, whose support grows with the scale when shrinking (antialiased), along the width first, then the
+     * height, with an 8-bit image in between (mj_host_resize_table; csrc/resize.hip).  mj_plan_execute runs stage 1, stage 2 — into
+     * a buffer of the files' own sizes that the plan owns — and the resize as its last launch; mj_plan_execute_stage2 includes it.
+     * slots, output, filter, places and fill say more about this array: set without a size they are MJ_ERR_INVALID ("... needs a
+     * size").  MJ_ERR_INVALID also: one of the two 0, or either outside 1..65535.  MJ_ERR_UNSUPPORTED: a shrink so strong that one
+     * pixel's taps do not fit a workgroup's LDS, or more output tiles than one launch takes (about 6.8e10: split the batch). */
+    int32_t out_width, out_height;
+    /* DEFAULT NULL: image k goes to slot k, the array has n_images slots, and n_slots is ignored.  Else image k goes to slot
+     * slots[k] < n_slots — several plans can fill one array this way (files of several kinds are one plan per kind); slots the
+     * plan does not name are not touched.  MJ_ERR_INVALID: a slot outside n_slots. */
+    const int32_t *slots; int32_t n_slots;
+    /* Model-ready output.  DEFAULT NULL, or {MJ_DTYPE_U8, 0, .., NULL}: the resized bytes.  Else the dense array holds what a
+     * model takes — elements of `dtype`, normalised, some images mirrored:
+     *   dtype      MJ_DTYPE_U8: the resized byte itself.  MJ_DTYPE_F32: for a resized byte v of component c, torchvision's
+     *              Normalize(mean, std)(to_tensor(img)) in float32, every operation rounded on its own,
+     *                  y = fl32( fl32( fl32( float(v) / 255.0f ) - mean[c] ) / std[c] )
+     *              (normalize == 0: mean 0, std 1, i.e. v / 255).  MJ_DTYPE_F16 / MJ_DTYPE_BF16: y rounded to nearest even to IEEE
+     *              binary16 / bfloat16.  The function is applied to the integer result of the two passes, as the height pass stores
+     *              it (mj_host_normalize_table is its table).
+     *   normalize  0 or 1; with 1, mean[c] and std[c] for the output's components (the rest ignored), in units of value / 255.
+     *   mirror     NULL, or n_images flags: image k with mirror[k] != 0 is stored flipped along its width axis — element
+     *              (x, y, c) of the un-mirrored result goes to column out_width - 1 - x, in whichever layout.  Any dtype.
+     * mj_plan_info.rgb_bytes of such a plan is in BYTES of the chosen type: n_slots * out_width * out_height * C * (1, 2 or 4).  It
+     * is what mj_plan_execute's rgb_device buffer must hold and what mj_plan_read's rgb copies; slot offsets scale likewise.
+     * MJ_ERR_INVALID: a dtype that is none of the four, normalize with MJ_DTYPE_U8, a mean that is not finite, a std that is not
+     * finite or not > 0. */
+    const mj_output_desc *output;
+    /* Resample filter, MJ_FILTER_*.  DEFAULT MJ_FILTER_BILINEAR (0).  Any of Pillow's convolution filters, byte for byte, in every
+     * layout, with everything the other fields do inside the same one launch:
+     *   MJ_FILTER_BILINEAR  support 1    triangle
+     *   MJ_FILTER_BOX       support 0.5  1 on (-0.5, 0.5]
+     *   MJ_FILTER_HAMMING   support 1    sinc(x) * (0.54 + 0.46 cos(pi x))
+     *   MJ_FILTER_BICUBIC   support 2    Keys' cubic with a = -0.5
+     *   MJ_FILTER_LANCZOS   support 3    sinc(x) * sinc(x / 3) on [-3, 3)
+     * (Pillow's NEAREST is not a convolution — it walks an affine transform — and is not offered.)  Weights in doubles, normalised,
+     * rounded away from zero to 22 bits (mj_host_resize_table_filtered); per pixel clip((2^21 + sum taps * in) >> 22, 0, 255) with a
+     * signed sum and an arithmetic shift: the taps of BICUBIC and LANCZOS are negative in their side lobes, and plans of those two
+     * run signed instances of the resize kernels (the other three share the unsigned ones: their taps are >= 0).
+     * MJ_ERR_UNSUPPORTED: a table with a tap of 2^23 or more in magnitude or with 2^21 + 255 * sum |tap| above 2^31 - 1 (the
+     * kernels multiply in 24 bits and add in 32; no size up to 129 comes near either bound). */
+    int32_t filter;
+    /* Aspect-preserving sizing.  DEFAULT NULL, or every place {out_width, out_height, 0, 0}: every image stretched over the whole
+     * of out_width x out_height.  Else that size is a CANVAS, and every image is resized to a size of its own and placed on it
+     * (tools/place_model.py): torchvision's Resize(s) + CenterCrop, a letterbox (Pillow's ImageOps.pad), a crop of the resized
+     * image, all in the one resize launch.
+     *   places[k]  width, height: the size image k (oriented, or its window) is resized to, 1..65535 each.  x, y: where its top-left
+     *              lies on the canvas, |x|, |y| <= 65535 — negative: the image is cropped there, positive: padded.
+     * Canvas element (ox, oy, c) of image k is the byte Image.resize((width_k, height_k), filter) has at (ox - x_k, oy - y_k) where
+     * that lies inside the resized image, fill[c] elsewhere; either byte then takes the output's path (the dtype's table, the
+     * normalisation: the fill is a byte that gets normalised, as torchvision's pad before ToTensor yields).  The mode converts
+     * first, the geometry refers to the oriented image or window, and a mirror flag flips the finished canvas, padding included.
+     * Only the canvas's elements are computed.  With windows, only the source rows and columns whose taps reach the canvas are
+     * decoded: every window shrinks to that range (mj_plan_time_resize's source_bytes counts what was decoded); whole images are
+     * decoded whole, which measured faster (option MJ_PLACE_WINDOW, csrc/resize.hip).
+     * MJ_ERR_INVALID: a size or offset outside the ranges above, an image that does not meet the canvas. */
+    const mj_place *places;
+    /* With places.  DEFAULT NULL: zeros.  Else one byte per OUTPUT component (fill[0] alone for one component). */
+    const uint8_t *fill;
+} mj_plan_request;
+/* request NULL: a zeroed request. */
+int mj_plan_create_with(mj_context *ctx, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
+/* The plain plan: exactly mj_plan_create_with(ctx, batch, NULL, out). */
+int mj_plan_create(mj_context *ctx, const mj_batch *batch, mj_plan **out);
+/* The host twin of the kernels' mode conversion (no context): n_pixels pixels of src_ncomp (1 or 3) interleaved components into
+ * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
+ * is neither 1 nor 3, NULL with pixels to convert. */
+int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -564,7 +567,7 @@ int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32
  * MJ_ERR_INVALID also for a filter that is none of them. */
 int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
                                   int32_t taps_stride, int32_t *ksize);
-/* The output table of one component of a mj_plan_create_resized_as plan, as the library builds it (host only, no context): out
+/* The output table of one component of a plan with mj_plan_request.output, as the library builds it (host only, no context): out
  * = 256 elements of `dtype` (MJ_DTYPE_F16 / BF16: 2 bytes each, MJ_DTYPE_F32: 4), element v what resized byte v is stored as with
  * this mean and std (mean 0, std 1 = no normalisation).  MJ_ERR_INVALID: MJ_DTYPE_U8 or an unknown dtype, NULL, a mean that is
  * not finite, a std that is not finite or not > 0. */

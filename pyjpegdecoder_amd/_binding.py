@@ -36,17 +36,13 @@ MODES = {"L": MJ_MODE_L, "RGB": MJ_MODE_RGB}
 # every symbol include/mijpeg.h declares (tests check the library exports all of them)
 EXPORTS = (
     "mj_create", "mj_destroy", "mj_last_error", "mj_version", "mj_context_wait_event",
-    "mj_plan_create", "mj_plan_create_roi", "mj_plan_destroy", "mj_plan_get_info", "mj_plan_image_offsets",
+    "mj_plan_create", "mj_plan_create_with", "mj_plan_destroy", "mj_plan_get_info", "mj_plan_image_offsets",
     "mj_plan_execute", "mj_plan_execute_stage1", "mj_plan_execute_stage2", "mj_plan_sync",
     "mj_plan_device_buffers", "mj_plan_read", "mj_plan_write_coef", "mj_plan_fill_coef",
     "mj_decode_baseline_batch", "mj_idct_batch", "mj_plan_time_stages", "mj_plan_time_execute", "mj_plan_idct_levels", "mj_host_idct_table", "mj_host_assemble", "mj_plan_stage1_form", "mj_set_option", "mj_get_option", "mj_debug_stage1_form", "mj_debug_fused_shape", "mj_debug_count_tables",
     "mj_device_copy_rate", "mj_context_launch_clock", "mj_debug_prog_split", "mj_debug_fused_applies", "mj_plan_tune_placement",
-    "mj_plan_create_resized", "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table",
-    "mj_plan_create_resized_as", "mj_host_normalize_table",
-    "mj_plan_create_oriented", "mj_plan_create_resized_oriented", "mj_host_exif_orientations",
-    "mj_plan_create_resized_filtered", "mj_host_resize_table_filtered", "mj_debug_resize_shape",
-    "mj_plan_create_resized_mode", "mj_plan_create_mode", "mj_host_convert_mode",
-    "mj_plan_create_resized_placed",
+    "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table", "mj_host_normalize_table", "mj_host_exif_orientations",
+    "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_debug_plan_shape", "mj_debug_cache_stats",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
@@ -111,6 +107,14 @@ class OutputDescC(ctypes.Structure):
                 ("mirror", ctypes.c_void_p)]
 
 
+class PlanRequestC(ctypes.Structure):
+    """mj_plan_request: what a plan's output is to be; zeroed, the plain plan."""
+    _fields_ = [("rois", ctypes.POINTER(RoiC)), ("orientations", ctypes.c_void_p), ("mode", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int32),
+                ("output", ctypes.POINTER(OutputDescC)), ("filter", ctypes.c_int32), ("places", ctypes.POINTER(PlaceC)),
+                ("fill", ctypes.c_void_p)]
+
+
 class PlanInfoC(ctypes.Structure):
     _fields_ = [("total_blocks", ctypes.c_int64), ("total_mcus", ctypes.c_int64), ("total_pixels", ctypes.c_int64),
                 ("rgb_bytes", ctypes.c_int64), ("entropy_bytes", ctypes.c_int64)]
@@ -147,20 +151,7 @@ def load_library():
     L.mj_last_error.restype = ctypes.c_char_p
     L.mj_context_wait_event.argtypes = [vp, vp]
     L.mj_plan_create.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(vp)]
-    L.mj_plan_create_roi.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), ctypes.POINTER(vp)]
-    L.mj_plan_create_resized.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(vp)]
-    L.mj_plan_create_resized_as.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32, ctypes.POINTER(OutputDescC),
-                                            ctypes.POINTER(vp)]
-    L.mj_plan_create_oriented.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), vp, ctypes.POINTER(vp)]
-    L.mj_plan_create_resized_oriented.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
-                                                  ctypes.POINTER(OutputDescC), vp, ctypes.POINTER(vp)]
-    L.mj_plan_create_resized_filtered.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
-                                                  ctypes.POINTER(OutputDescC), vp, i32, ctypes.POINTER(vp)]
-    L.mj_plan_create_resized_mode.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
-                                              ctypes.POINTER(OutputDescC), vp, i32, i32, ctypes.POINTER(vp)]
-    L.mj_plan_create_resized_placed.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), i32, i32, vp, i32,
-                                                ctypes.POINTER(OutputDescC), vp, i32, i32, ctypes.POINTER(PlaceC), vp, ctypes.POINTER(vp)]
-    L.mj_plan_create_mode.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(RoiC), vp, i32, ctypes.POINTER(vp)]
+    L.mj_plan_create_with.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(PlanRequestC), ctypes.POINTER(vp)]
     L.mj_host_convert_mode.argtypes = [i32, vp, i32, i64, vp]
     L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_debug_resize_shape.argtypes = [vp, ctypes.POINTER(i32)]
@@ -384,6 +375,42 @@ def output_desc(output):
     return d, flags
 
 
+def plan_request(n_images, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None, places=None,
+                 fill=None):
+    """(mj_plan_request, the arrays it points to) for a batch of ``n_images`` from Plan's keywords: every keyword is one field of
+    the request (include/mijpeg.h), None its default.  Pure: no library, no context.  ValueError for what only a sized or placed
+    plan has and for a per-image list that has not one entry for each image."""
+    if size is None and (places is not None or filter is not None or output is not None):
+        raise ValueError("places, filter and output need size: only a resized plan has a canvas, resamples and has a dense output")
+    if fill is not None and places is None:
+        raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
+    r, keep = PlanRequestC(), {}
+    if rois is not None:
+        keep["rois"] = r.rois = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in w)) for w in rois])
+    if orientation is not None:
+        keep["orientations"] = turns = np.ascontiguousarray(orientation, dtype=np.uint8)
+        r.orientations = turns.ctypes.data
+    r.mode, r.filter = mode_id(mode), filter_id(filter)
+    if size is not None:
+        r.out_width, r.out_height = int(size[0]), int(size[1])
+    if slots is not None:
+        keep["slots"] = sl = np.ascontiguousarray(slots[0], dtype=np.int32)
+        r.slots, r.n_slots = sl.ctypes.data, int(slots[1])
+    if output is not None:
+        keep["output"], keep["mirror"] = output_desc(output)
+        r.output = ctypes.pointer(keep["output"])
+    if places is not None:
+        keep["places"] = r.places = (PlaceC * max(1, len(places)))(*[PlaceC(*(int(v) for v in pl)) for pl in places])
+    if fill is not None:
+        keep["fill"] = fb = np.zeros(3, dtype=np.uint8)
+        fb[:len(fill)] = fill
+        r.fill = fb.ctypes.data
+    for name, given in (("places", places), ("orientation", orientation), ("mirror", keep.get("mirror"))):
+        if given is not None and len(given) != n_images:
+            raise ValueError(f"{name}: {len(given)} entries, not one for each of the {n_images} images")
+    return r, keep
+
+
 class UnknownOption(ValueError):
     """mj_set_option / mj_get_option: no such option in this library."""
 
@@ -468,111 +495,25 @@ class Context:
 
 
 class Plan:
-    """mj_plan over a prepared batch (see batch.PreparedBatch).  rois: None, or one (x, y, width, height) per image —
-    a window plan (mj_plan_create_roi) whose output for every image is that window.  size: None, or (width, height) — a
-    resized plan (mj_plan_create_resized) whose output is one dense array of every image (or window) at that size; slots:
-    with size, (slot of every image, slots of the array) when the plan fills part of a larger array.  output: with size, None
-    (the resized bytes) or (dtype name, mean or None, std or None, mirror flag per image or None) — a model-ready output
-    (mj_plan_create_resized_as): elements of that type, normalised, flagged images mirrored; info.rgb_bytes is then in bytes
-    of that type.  orientation: None, or one EXIF orientation 1..8 per image — an oriented plan (mj_plan_create_oriented, with
-    size mj_plan_create_resized_oriented): outputs as the orientation shows the images, rois in oriented coordinates.
-    filter: with size, None or "bilinear" (the plans above, through the entry points above) or another name of FILTERS / its
-    MJ_FILTER_*: the resize with that resample filter (mj_plan_create_resized_filtered).
-    mode: None, or a name of MODES / its MJ_MODE_* — the components of the output (mj_plan_create_mode, with size
-    mj_plan_create_resized_mode, which take all of the above); info.rgb_bytes, slots and image_offsets then count those.
-    places: with size — then the canvas —, None or one (width, height, x, y) per image: the size it is resized to and where it lies
-    on the canvas (mj_plan_create_resized_placed, which takes all of the above); fill: with places, None (zeros) or up to three
+    """mj_plan over a prepared batch (see batch.PreparedBatch).  The keywords are the fields of mj_plan_request (include/mijpeg.h
+    specifies each there), None the field's default.  rois: one (x, y, width, height) per image — a window plan whose output for
+    every image is that window.  size: (width, height) — a resized plan whose output is one dense array of every image (or
+    window) at that size; slots: with size, (slot of every image, slots of the array) when the plan fills part of a larger array.
+    output: with size, (dtype name, mean or None, std or None, mirror flag per image or None) — a model-ready output: elements of
+    that type, normalised, flagged images mirrored; info.rgb_bytes is then in bytes of that type.  orientation: one EXIF
+    orientation 1..8 per image — outputs as the orientation shows the images, rois in oriented coordinates.  filter: with size, a
+    name of FILTERS / its MJ_FILTER_*: the resize with that resample filter.  mode: a name of MODES / its MJ_MODE_* — the
+    components of the output; info.rgb_bytes, slots and image_offsets then count those.  places: with size — then the canvas —,
+    one (width, height, x, y) per image: the size it is resized to and where it lies on the canvas; fill: with places, up to three
     bytes, one per output component."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
                  filter=None, mode=None, places=None, fill=None):
+        request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill)
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
-        arr = None
-        if rois is not None:
-            arr = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in r)) for r in rois])
-        if places is not None:
-            if size is None:
-                raise ValueError("places need size: the canvas the images are placed on")
-            if len(places) != batch_c.n_images:
-                raise ValueError(f"places: {len(places)} entries for {batch_c.n_images} images")
-            turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
-            desc, flags = output_desc(output) if output is not None else (None, None)
-            if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):
-                raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
-            sl, n_slots = None, 0
-            if slots is not None:
-                sl = np.ascontiguousarray(slots[0], dtype=np.int32)
-                n_slots = int(slots[1])
-            parr = (PlaceC * max(1, len(places)))(*[PlaceC(*(int(v) for v in pl)) for pl in places])
-            fb = np.zeros(3, dtype=np.uint8)
-            if fill is not None:
-                fb[:len(fill)] = fill
-            ctx.check(ctx.lib.mj_plan_create_resized_placed(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
-                                                            ctypes.byref(desc) if desc is not None else None, _ptr(turns), filter_id(filter),
-                                                            mode_id(mode), parr, _ptr(fb), ctypes.byref(h)))
-        elif fill is not None:
-            raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
-        elif mode is not None:
-            turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
-            desc, flags = output_desc(output) if output is not None else (None, None)
-            if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):
-                raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
-            if size is not None:
-                sl, n_slots = None, 0
-                if slots is not None:
-                    sl = np.ascontiguousarray(slots[0], dtype=np.int32)
-                    n_slots = int(slots[1])
-                ctx.check(ctx.lib.mj_plan_create_resized_mode(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
-                                                              ctypes.byref(desc) if desc is not None else None, _ptr(turns), filter_id(filter),
-                                                              mode_id(mode), ctypes.byref(h)))
-            elif filter is not None or output is not None:
-                raise ValueError("filter and output need size: only a resized plan resamples and has a dense output")
-            else:
-                ctx.check(ctx.lib.mj_plan_create_mode(ctx.handle, ctypes.byref(batch_c), arr, _ptr(turns), mode_id(mode), ctypes.byref(h)))
-        elif size is not None:
-            sl, n_slots = None, 0
-            if slots is not None:
-                sl = np.ascontiguousarray(slots[0], dtype=np.int32)
-                n_slots = int(slots[1])
-            fid = filter_id(filter)
-            if fid != MJ_FILTER_BILINEAR:
-                turns = np.ascontiguousarray(orientation, dtype=np.uint8) if orientation is not None else None
-                desc, flags = output_desc(output) if output is not None else (None, None)
-                if (turns is not None and turns.size != batch_c.n_images) or (flags is not None and flags.size != batch_c.n_images):
-                    raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
-                ctx.check(ctx.lib.mj_plan_create_resized_filtered(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
-                                                                  ctypes.byref(desc) if desc is not None else None, _ptr(turns), fid, ctypes.byref(h)))
-            elif orientation is not None:
-                turns = np.ascontiguousarray(orientation, dtype=np.uint8)
-                desc, flags = output_desc(output) if output is not None else (None, None)
-                if turns.size != batch_c.n_images or (flags is not None and flags.size != batch_c.n_images):
-                    raise ValueError(f"orientation / mirror: not one entry for each of the {batch_c.n_images} images")
-                ctx.check(ctx.lib.mj_plan_create_resized_oriented(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
-                                                                  ctypes.byref(desc) if desc is not None else None, _ptr(turns), ctypes.byref(h)))
-            elif output is None:
-                ctx.check(ctx.lib.mj_plan_create_resized(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl), n_slots,
-                                                         ctypes.byref(h)))
-            else:
-                desc, flags = output_desc(output)
-                if flags is not None and flags.size != batch_c.n_images:
-                    raise ValueError(f"output: {flags.size} mirror flags for {batch_c.n_images} images")
-                ctx.check(ctx.lib.mj_plan_create_resized_as(ctx.handle, ctypes.byref(batch_c), arr, int(size[0]), int(size[1]), _ptr(sl),
-                                                            n_slots, ctypes.byref(desc), ctypes.byref(h)))
-        elif filter is not None:
-            raise ValueError("filter needs size: only a resized plan resamples")
-        elif output is not None:
-            raise ValueError("output needs size: only a resized plan has a dense output")
-        elif orientation is not None:
-            turns = np.ascontiguousarray(orientation, dtype=np.uint8)
-            if turns.size != batch_c.n_images:
-                raise ValueError(f"orientation: {turns.size} entries for {batch_c.n_images} images")
-            ctx.check(ctx.lib.mj_plan_create_oriented(ctx.handle, ctypes.byref(batch_c), arr, _ptr(turns), ctypes.byref(h)))
-        elif rois is None:
-            ctx.check(ctx.lib.mj_plan_create(ctx.handle, ctypes.byref(batch_c), ctypes.byref(h)))
-        else:
-            ctx.check(ctx.lib.mj_plan_create_roi(ctx.handle, ctypes.byref(batch_c), arr, ctypes.byref(h)))
+        ctx.check(ctx.lib.mj_plan_create_with(ctx.handle, ctypes.byref(batch_c), ctypes.byref(request), ctypes.byref(h)))
         self.handle = h
         info = PlanInfoC()
         ctx.check(ctx.lib.mj_plan_get_info(h, ctypes.byref(info)))

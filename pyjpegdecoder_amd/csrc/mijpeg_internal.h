@@ -53,7 +53,7 @@ struct DevImage {
     int64_t pix_off;                  // pixel offset (for the planes output: *ncomp int16 each)
 };
 
-// One image's window of a window plan (mj_plan_create_roi), in the ORIGINAL image's coordinates (x along the width).  The
+// One image's window of a window plan (mj_plan_request.rois), in the ORIGINAL image's coordinates (x along the width).  The
 // image's output (DevImage::rgb_off, in the packing of the windows) is that window only; stage 2 reconstructs the MCUs of
 // the window's MCU rectangle and nothing else.
 struct DevWindow {
@@ -298,7 +298,7 @@ struct ReconArgs {
     int32_t chunk_strips;
     int32_t jobs_per_ticket;     // >= 1
     unsigned long long *level_counts;   // seam-output launches: blocks seen / sent to level 2 / sent to level 3 (mj_plan_idct_levels), per plan
-    // window plans (mj_plan_create_roi): per image, the window stage 2 writes (null: whole images).  The exact-order and generic
+    // window plans (mj_plan_request.rois): per image, the window stage 2 writes (null: whole images).  The exact-order and generic
     // kernels then number the windows' MCUs only: total_mcus and mcu_prefix count those, uniform_geometry is 0.
     const DevWindow *win;
 };
@@ -392,7 +392,7 @@ struct ResizeArgs {
     int32_t n_images, ow, oh, layout;
     int32_t tr, tc, tiles_x, tiles_y;         // output rows / columns per tile, tiles per image
     int32_t t_pitch, tab_off, stage_off, stage_bytes, lds_bytes;    // the workgroup's LDS (resize.hip)
-    // the output element (mj_plan_create_resized_as): esize 1 stores the resized byte itself; 2 / 4 store lut[c * 256 + byte],
+    // the output element (mj_plan_request.output): esize 1 stores the resized byte itself; 2 / 4 store lut[c * 256 + byte],
     // the byte's float16 / bfloat16 / float32 bit pattern, which every workgroup first copies to lut_off of its LDS
     // mirror: NULL, or one byte per image, != 0: that image is stored flipped along the width axis, column out_width - 1 - x
     // (an array of its own, read by the mirror instances only: the image record keeps its 32 bytes, and with them the plain
@@ -400,7 +400,7 @@ struct ResizeArgs {
     const void *lut;
     const uint8_t *mirror;
     int32_t esize, lut_off;
-    // oriented plans (mj_plan_create_resized_oriented): 0 = none.  1: `mirror` holds, per image, bit 0 = store at column
+    // oriented plans (mj_plan_request.orientations with a size): 0 = none.  1: `mirror` holds, per image, bit 0 = store at column
     // out_width - 1 - x, bit 1 = store at row out_height - 1 - y (the image's tap tables are the reversed ones, so the sums are
     // those of the flipped source; a mirror flag is folded into bit 0).  2: the same, and the images are transposing
     // orientations: the source is read as the other layout's kernel reads it (the stored rows are the oriented columns)
@@ -415,8 +415,8 @@ bool resize_filter_known(int filter);
 bool resize_filter_signed(int filter);
 int resize_axis_ksize(int in_size, int out_size, int filter = 0);
 void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0);
-// (out_ncomp: 0 or ncomp — the instances there were; else a plan that converts, mj_plan_create_resized_mode)
-// (placed: a plan of mj_plan_create_resized_placed — the placed instances, which store `fill`, byte c in bits 8c..8c+7, where
+// (out_ncomp: 0 or ncomp — the instances there were; else a plan that converts, mj_plan_request.mode with a size)
+// (placed: a plan of mj_plan_request.places — the placed instances, which store `fill`, byte c in bits 8c..8c+7, where
 // the image does not cover the canvas; a.mirror is then set)
 hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp = 0, int placed = 0, unsigned fill = 0);
 // ---- output colour mode (tools/mode_model.py)
@@ -430,7 +430,7 @@ inline int batch_ncomp(const mj_batch *b) { return b && b->n_images > 0 && b->im
 // the destination's rows run backwards, bit 1: its contiguous axis runs backwards, bit 2: rows and columns change places.
 struct DevOrientImage {
     int64_t src_off, dst_off;     // bytes; an image keeps its place in the packing (orientation keeps the pixel count; a plan that
-                                  // converts, mj_plan_create_mode, packs the same pixels with the output's components)
+                                  // converts, mj_plan_request.mode, packs the same pixels with the output's components)
     int32_t rows, len;
     int32_t tiles_l;              // tiles along the contiguous axis
     int32_t op;

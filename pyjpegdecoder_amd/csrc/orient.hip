@@ -1,4 +1,4 @@
-// EXIF orientation at the files' own sizes: an oriented plan (mj_plan_create_oriented) decodes into a plan-owned buffer in
+// EXIF orientation at the files' own sizes: an oriented plan (mj_plan_request.orientations, no size) decodes into a plan-owned buffer in
 // stored order, as a resized plan does, and ONE launch over all its images writes every image oriented into its packed place
 // in the output.  tools/orient_model.py is the definition: the eight values are a transpose (5..8) followed by reversed
 // columns and / or rows.
@@ -14,7 +14,7 @@
 // row apart each — fall into different banks instead of all into one.  Planar plans read the same interleaved source and
 // store one plane after the other.
 //
-// Output colour mode (mj_plan_create_mode): k_orient<CS, CO> with CS != CO is the same launch converting on its way — the tile
+// Output colour mode (mj_plan_request.mode, no size): k_orient<CS, CO> with CS != CO is the same launch converting on its way — the tile
 // lies in LDS in the source's components, the store loop runs over the output's: a grey byte goes into all three components,
 // a colour pixel becomes its L (mode_luma).  Such a plan has the launch for upright images too (op 0: a copy that converts), and
 // an image's place in the output is no longer its place in the source (dst_off: the same pixels, CO components each).
@@ -93,37 +93,19 @@ hipError_t launch_orient(hipStream_t stream, const OrientArgs &a, int ncomp, int
     return hipGetLastError();
 }
 
-}  // namespace mj
-
-namespace {
-
-// mode: 0, or the output's component count where it is not the batch's (such a plan has the launch for upright images too)
-int create_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, int mode, mj_plan **out) {
-    if (!ctx) return MJ_ERR_INVALID;
-    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
-    *out = nullptr;
-    bool upright = true;
-    for (int i = 0; orientations && i < b->n_images; ++i) {
-        if (orientations[i] < 1 || orientations[i] > 8)
-            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
-        upright = upright && orientations[i] == 1;
-    }
-    if (upright && !mode) return rois ? mj_plan_create_roi(ctx, b, rois, out) : mj_plan_create(ctx, b, out);
-    if (upright) orientations = nullptr;
-    if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
-        return fail(ctx, MJ_ERR_INVALID, "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
+// The plan of a normalised request without a size that has orientations (not all upright) or a mode (not the batch's own): one
+// that converts has the launch for upright images too.
+int create_oriented(const PlanRequest &q) {
+    const char *fn = kCreateFn;
+    mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
+    const mj_roi *rois = q.r.rois; const uint8_t *orientations = q.r.orientations; const int mode = q.r.mode;
     if (!b->images) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     std::vector<mj_roi> stored;
-    if (rois) {
-        stored.resize((size_t)b->n_images);
-        for (int i = 0; i < b->n_images; ++i)
-            if (!mj::stored_window(orientations ? orientations[i] : 1, b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
-                return fail(ctx, MJ_ERR_INVALID, "%s: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image",
-                            fn, i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
-    }
+    if (rois)
+        if (int rc = stored_windows(q, rois, stored)) return rc;
     mj_plan *p = nullptr;
     if (int rc = mj::plan_create_common(ctx, b, rois ? stored.data() : nullptr, rois != nullptr, &p)) return rc;
-    struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
+    PlanGuard guard{p};
     const int n = p->n_images, C = p->ncomp, CO = mode ? mode : C;
     const bool xmajor = (p->layout & 1) == 0;
     std::vector<mj::DevOrientImage> oi((size_t)n);
@@ -166,20 +148,9 @@ int create_oriented(const char *fn, mj_context *ctx, const mj_batch *b, const mj
     return MJ_OK;
 }
 
-}  // namespace
+}  // namespace mj
 
 extern "C" {
-
-int mj_plan_create_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, mj_plan **out) {
-    return create_oriented("mj_plan_create_oriented", ctx, b, rois, orientations, 0, out);
-}
-
-int mj_plan_create_mode(mj_context *ctx, const mj_batch *b, const mj_roi *rois, const uint8_t *orientations, int32_t mode, mj_plan **out) {
-    const char *fn = "mj_plan_create_mode";
-    if (mode != MJ_MODE_NATIVE && mode != MJ_MODE_L && mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, mode);
-    // (the files' own count: the plan of mj_plan_create_oriented, made by the code that makes it there)
-    return create_oriented(fn, ctx, b, rois, orientations, mode == mj::batch_ncomp(b) ? MJ_MODE_NATIVE : mode, out);
-}
 
 int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out) {
     if ((mode != MJ_MODE_NATIVE && mode != MJ_MODE_L && mode != MJ_MODE_RGB) || (src_ncomp != 1 && src_ncomp != 3) || n_pixels < 0 || (n_pixels && (!src || !out)))

@@ -1,5 +1,5 @@
 // Host-side state of libmijpeg.so shared by its translation units: the device buffer cache, the context and the plan
-// (api.hip: the C ABI and the launches of an execute; plan_create.hip: mj_plan_create; options.hip: the test / tuning switches).
+// (api.hip: the C ABI and the launches of an execute; plan_create.hip: mj_plan_create_with; options.hip: the test / tuning switches).
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -250,7 +250,7 @@ struct mj_plan {
     int16_t *d_idct = nullptr;
     int32_t *d_status = nullptr;
     uint8_t *last_rgb = nullptr;    // where the most recent execute wrote
-    // window plans (mj_plan_create_roi): per image the window stage 2 writes; the exact-order and generic kernels number the
+    // window plans (mj_plan_request.rois): per image the window stage 2 writes; the exact-order and generic kernels number the
     // windows' MCUs (win_mcu_prefix: first window MCU of every image + total)
     bool windowed = false;
     std::vector<mj::DevWindow> h_win;
@@ -261,7 +261,7 @@ struct mj_plan {
     // windows need are gathered (d_seg_gather: their indices) into d_segs, which stages 0 and 1 read
     mj::DevSegment *d_segs_full = nullptr;
     int32_t *d_seg_gather = nullptr;
-    // resized plans (mj_plan_create_resized): stage 2 writes its interleaved pixels into d_src, the resize launch reads them and
+    // resized plans (mj_plan_request.out_width / out_height): stage 2 writes its interleaved pixels into d_src, the resize launch reads them and
     // writes the plan's output (info.rgb_bytes is the OUTPUT's size; src_bytes the intermediate's)
     bool resized = false;
     uint8_t *d_src = nullptr;
@@ -269,18 +269,18 @@ struct mj_plan {
     mj::DevResizeImage *d_rz_images = nullptr;
     int32_t *d_rz_tabs = nullptr;
     uint8_t *d_rz_mirror = nullptr;        // ... with a mirror flag set: one byte per image
-    uint8_t *d_rz_lut = nullptr;           // mj_plan_create_resized_as with a float dtype: the output table (info.rgb_bytes: bytes of that type)
+    uint8_t *d_rz_lut = nullptr;           // mj_plan_request.output with a float dtype: the output table (info.rgb_bytes: bytes of that type)
     mj::ResizeArgs rz{};
-    int rz_placed = 0;                     // mj_plan_create_resized_placed: the placed instances, which store rz_fill (byte c in bits
+    int rz_placed = 0;                     // mj_plan_request.places: the placed instances, which store rz_fill (byte c in bits
     unsigned rz_fill = 0;                  // 8c..8c+7) where an image does not cover the canvas
     int rz_filter = 0, rz_max_ksize = 0;   // the plan's MJ_FILTER_* and the most taps a pixel of it has per axis (mj_debug_resize_shape)
-    // oriented plans at the files' own sizes (mj_plan_create_oriented): `resized` with the orient launch (orient.hip) in the
+    // oriented plans at the files' own sizes (mj_plan_request.orientations without a size): `resized` with the orient launch (orient.hip) in the
     // resize launch's place — stage 2 writes stored-order pixels into d_src, the launch writes them oriented into the output
     bool orient_only = false;
     mj::DevOrientImage *d_or_images = nullptr;
     int64_t *d_or_prefix = nullptr;
     mj::OrientArgs oa{};
-    // plans that convert (mj_plan_create_mode / mj_plan_create_resized_mode): the components of the output where they are not the
+    // plans that convert (mj_plan_request.mode): the components of the output where they are not the
     // files' (0: they are) — the orient / resize launch converts —, and every image's byte offset in the output
     int out_ncomp = 0;
     std::vector<int64_t> h_out_off;
@@ -297,8 +297,21 @@ bool build_count_tables(const mj_batch *b, const std::vector<int> &role, int W, 
 struct ProgScans { std::vector<DevProgScan> pscans; std::vector<DevProgSeg> psegs; };
 int plan_progressive_scans(mj_context *ctx, const mj_batch *b, mj_plan *p, ProgScans &S, int64_t &entropy_bytes);
 int plan_progressive_upload(mj_context *ctx, const mj_batch *b, mj_plan *p, ProgScans &S);
-// ---- plan_create.hip: what mj_plan_create / mj_plan_create_roi do (roi_plan: a window plan)
+// ---- plan_create.hip: the plain plan and the window plan (roi_plan; rois == NULL: every window is the whole image)
 int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, bool roi_plan, mj_plan **out);
+// What mj_plan_create_with is asked for, after plan_create.hip's normalise_request: every field of r is checked, and one that
+// named its default names nothing (orientations all 1, the batch's own mode, every place the whole canvas: NULL / 0); n_slots
+// is the output's.  The two makers take it: create_resized (resize_plan.hip) with a size, create_oriented (orient.hip) without
+// one and with orientations or a mode; a request with neither is plan_create_common's.
+struct PlanRequest { mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; };
+constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the messages)
+int create_resized(const PlanRequest &q);
+const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std);     // (resize_plan.hip)
+int create_oriented(const PlanRequest &q);
+// q.r.rois (oriented coordinates, not NULL) or the windows `rois` given in their place, as windows of the stored images
+int stored_windows(const PlanRequest &q, const mj_roi *rois, std::vector<mj_roi> &stored);
+// destroys a plan under construction unless its maker got to the end (p = nullptr)
+struct PlanGuard { mj_plan *p; ~PlanGuard() { if (p) mj_plan_destroy(p); } };
 // ---- EXIF orientation (tools/orient_model.py): value 1..8 as operations on the row-major image — bit 2: transpose first,
 // then bit 0: reverse the columns, bit 1: reverse the rows
 inline int orient_bits(int o) {

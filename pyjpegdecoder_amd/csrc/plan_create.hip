@@ -1,4 +1,4 @@
-// mj_plan_create: validate a batch description, choose the forms its stages take (form_select.h), build the tables and
+// mj_plan_create_with: check and normalise the request, validate the batch description, choose the forms its stages take (form_select.h), build the tables and
 // descriptors and upload them.  Host-side only.
 #include <math.h>
 
@@ -75,7 +75,7 @@ int check_batch(mj_context *ctx, const mj_batch *b, bool roi_plan, mj_plan **out
         return fail(ctx, MJ_ERR_INVALID, "mj_plan_create: unknown layout %d", b->layout);
     if (b->n_qt <= 0 || !b->qt) return fail(ctx, MJ_ERR_INVALID, "mj_plan_create: no quantisation tables");
     if (roi_plan && (b->flags & (MJ_FLAG_KEEP_COEF | MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
-        return fail(ctx, MJ_ERR_INVALID, "mj_plan_create_roi: the seam outputs (MJ_FLAG_KEEP_*) are whole-image; a window plan has none");
+        return fail(ctx, MJ_ERR_INVALID, "%s: the seam outputs (MJ_FLAG_KEEP_*) are whole-image; a window plan has none", mj::kCreateFn);
     MJ_HIP(ctx, hipSetDevice(ctx->device));
     return MJ_OK;
 }
@@ -667,7 +667,7 @@ struct Create {
 
 }  // namespace
 
-// mj_plan_create and mj_plan_create_roi (roi_plan: a window plan), step by step
+// the plain plan and the window plan (roi_plan), step by step
 int mj::plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, bool roi_plan, mj_plan **out) {
     if (int rc = check_batch(ctx, b, roi_plan, out)) return rc;
     mj_plan *p = new mj_plan();
@@ -710,6 +710,63 @@ int mj::plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *roi
     return MJ_OK;
 }
 
+int mj::stored_windows(const PlanRequest &q, const mj_roi *rois, std::vector<mj_roi> &stored) {
+    const mj_batch *b = q.b;
+    stored.resize((size_t)b->n_images);
+    for (int i = 0; i < b->n_images; ++i)
+        if (!stored_window(q.r.orientations ? q.r.orientations[i] : 1, b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image", kCreateFn,
+                        i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+    return MJ_OK;
+}
+
+namespace {
+
+// What every request goes through before a plan is made of it: each field checked, in this order — where several faults coincide
+// the first is reported —, and each field that names its default turned into its absence, so that "the default is exactly the plan
+// without the field" holds by construction: the makers never see the difference.
+int normalise_request(mj::PlanRequest &q) {
+    const char *fn = mj::kCreateFn;
+    mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
+    const bool sized = r.out_width != 0 || r.out_height != 0;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : nullptr;
+    if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
+    if (r.mode != MJ_MODE_NATIVE && r.mode != MJ_MODE_L && r.mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, r.mode);
+    if (r.mode == mj::batch_ncomp(b)) r.mode = MJ_MODE_NATIVE;      // (the files' own count)
+    bool stretched = true;                                          // (every image over the whole canvas)
+    for (int i = 0; r.places && b && i < b->n_images && stretched; ++i)
+        stretched = r.places[i].width == r.out_width && r.places[i].height == r.out_height && r.places[i].x == 0 && r.places[i].y == 0;
+    if (stretched) r.places = nullptr;
+    bool upright = true;
+    for (int i = 0; r.orientations && b && i < b->n_images; ++i) {
+        if (r.orientations[i] < 1 || r.orientations[i] > 8) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)r.orientations[i]);
+        upright = upright && r.orientations[i] == 1;
+    }
+    if (upright) r.orientations = nullptr;
+    // the output description: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
+    // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
+    if (r.output)
+        if (const char *why = mj::output_fault(r.output->dtype, r.output->normalize != 0, r.mode ? r.mode : mj::batch_ncomp(b), r.output->mean, r.output->std))
+            return fail(ctx, MJ_ERR_INVALID, "%s: output: %s", fn, why);
+    if (!ctx) return MJ_ERR_INVALID;
+    if (!b || !q.out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+    *q.out = nullptr;
+    if (!sized && unsized) return fail(ctx, MJ_ERR_INVALID, "%s: %s needs a size (out_width, out_height)", fn, unsized);
+    if (sized && (r.out_width < 1 || r.out_height < 1 || r.out_width > 65535 || r.out_height > 65535))
+        return fail(ctx, MJ_ERR_INVALID, "%s: output size %d x %d (both must be 1..65535)", fn, r.out_width, r.out_height);
+    // (a window plan's refusal of the KEEP flags is plan_create_common's)
+    if ((sized || r.orientations || r.mode) && (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
+        return fail(ctx, MJ_ERR_INVALID, sized ? "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none"
+                                               : "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
+    if (!r.slots) r.n_slots = b->n_images;
+    for (int i = 0; r.slots && i < b->n_images; ++i)
+        if (r.slots[i] < 0 || r.slots[i] >= r.n_slots)
+            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, r.slots[i], r.n_slots);
+    return MJ_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int mj_debug_fused_applies(int32_t layout, int32_t ncomp, int32_t hmax, int32_t vmax, int32_t mcus_per_row, int32_t mcu_rows,
@@ -745,11 +802,14 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
     return MJ_OK;
 }
 
-int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) { return mj::plan_create_common(ctx, b, nullptr, false, out); }
-
-int mj_plan_create_roi(mj_context *ctx, const mj_batch *b, const mj_roi *rois, mj_plan **out) {
-    return mj::plan_create_common(ctx, b, rois, true, out);
+int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
+    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}};
+    if (int rc = normalise_request(q)) return rc;
+    if (q.r.out_width) return mj::create_resized(q);
+    if (q.r.orientations || q.r.mode) return mj::create_oriented(q);
+    return mj::plan_create_common(ctx, b, q.r.rois, q.r.rois != nullptr, out);
 }
 
-}  // extern "C"
+int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) { return mj_plan_create_with(ctx, b, nullptr, out); }
 
+}  // extern "C"

@@ -357,7 +357,7 @@ __device__ __forceinline__ void fill_weights(float4 *wt, int tid, int nthreads) 
     }
 }
 
-// WIN: a window plan (mj_plan_create_roi).  The jobs are strips down the MCU columns of each image's window (a.win, in the
+// WIN: a window plan (mj_plan_request.rois).  The jobs are strips down the MCU columns of each image's window (a.win, in the
 // kernel's — possibly transposed — geometry), and what lies outside the window, inside the first and last MCU column and row,
 // is not stored: its pieces go to the dump line like the pieces past the right and bottom image edges.  Output columns are
 // the window's (a.win[i].h pixels, or w when transposed), packed window after window.

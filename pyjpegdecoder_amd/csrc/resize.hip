@@ -2,7 +2,7 @@
 // out_width x out_height, all images in ONE launch, into one dense output.
 //
 // The arithmetic is Pillow's Image.resize(size, filter) on 8-bit data (tools/resize_model.py restates it) for BILINEAR — the
-// default — BOX, HAMMING, BICUBIC and LANCZOS (mj_plan_create_resized_filtered): per axis a
+// default — BOX, HAMMING, BICUBIC and LANCZOS (mj_plan_request.filter): per axis a
 // table of integer taps — the filter's weights in doubles, support growing with the scale when shrinking, normalised,
 // rounded to 22 bits: build_resize_axis, host — and per pixel clip8((2^21 + sum taps * in) >> 22), signed and clamped at both
 // ends where the filter's taps go below zero (Tap).  Two passes with a uint8
@@ -20,7 +20,7 @@
 // Planar plans read the same interleaved source (stage 2 writes it; the plane separation of a plain planar plan is skipped)
 // and only store elsewhere.
 //
-// Model-ready output (mj_plan_create_resized_as): the height pass ends in a byte v of component c, and what it stores is a
+// Model-ready output (mj_plan_request.output): the height pass ends in a byte v of component c, and what it stores is a
 // pure function of (c, v) — torchvision's Normalize(mean, std)(to_tensor(img)) in float32, operation by operation, then
 // rounded to nearest even for the 16-bit types (tools/normalize_model.py).  The host evaluates it for the 256 x C pairs
 // (build_normalize_table) and the kernels' 2- and 4-byte instances store lut[c][v] out of LDS: exact by construction, no
@@ -29,7 +29,7 @@
 // and consecutive lanes consecutive elements of the output's contiguous axis, so a wavefront's store is one run of 64, 128
 // or 256 bytes (descending for a mirrored image of a row-major layout); the plain uint8 instances are the code they were.
 //
-// Output colour mode (mj_plan_create_resized_mode): the k_resize_*_mode instances, whose source has CS components and whose
+// Output colour mode (mj_plan_request.mode with a size): the k_resize_*_mode instances, whose source has CS components and whose
 // output CO — greyscale files into three components (Pillow's convert("RGB")) and colour files into one (convert("L"),
 // mode_luma of the decoded RGB bytes).  The conversion comes first, as in img.convert(mode).resize(size): colour to L where the
 // source is read, before any tap (the staged row in LDS; 16 pixels = 48 bytes per lane and tap in registers), so both passes and
@@ -37,14 +37,14 @@
 // loop — one element per lane, consecutive lanes consecutive elements, as above — looks up lut[c][byte] for c = 0..2.  They
 // are instances in the oriented style only (the per-image byte holds the flips and the mirror flag; all zero for a plain plan).
 //
-// Aspect-preserving sizing (mj_plan_create_resized_placed): the output is a canvas, every image is resized to a size of its own and
+// Aspect-preserving sizing (mj_plan_request.places): the output is a canvas, every image is resized to a size of its own and
 // placed at an offset on it; elements it does not cover hold a fill byte, which takes the output's path like any other.  The tap
 // tables are built in the canvas's coordinates — an entry outside the image has no taps and keeps the bound of the nearest entry inside
 // as its first index — so the placed instances of the four kernels (the ones with a trailing fill argument: fill_arg) compute canvas
 // elements only: a tile the image does not reach stores fill and returns before any staging, a tile it reaches runs the width pass
 // over the covered columns and rows alone.  With windows, plan creation shrinks every window to the source range the canvas needs.
 // This file: the tables' and the output table's arithmetic (host), the kernels, and launch_resize, the one place that maps a plan
-// to an instance.  Plan creation (mj_plan_create_resized*: tables, tile, LDS layout, the placed source ranges) is resize_plan.hip.
+// to an instance.  Plan creation (a request with a size: tables, tile, LDS layout, the placed source ranges) is resize_plan.hip.
 #include <math.h>
 
 #include <type_traits>
@@ -195,7 +195,7 @@ __device__ __forceinline__ const OutT *stage_lut(const ResizeArgs &a, unsigned c
     }
 }
 
-// ---- placed plans (mj_plan_create_resized_placed): `fill` holds the canvas's fill byte of component c in bits 8c..8c+7
+// ---- placed plans (mj_plan_request.places): `fill` holds the canvas's fill byte of component c in bits 8c..8c+7
 __device__ __forceinline__ unsigned fill_byte(unsigned fill, int c) { return (fill >> (8 * c)) & 255u; }
 // The placed instances of a kernel are the ones with a trailing kernel argument (`Fill... fill`, one unsigned): the
 // oriented-style instance over canvas tables — entries outside the image have no taps and keep the bound of the nearest entry
@@ -578,12 +578,12 @@ hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int
     // one workgroup per tile, numbered along x then y: a grid dimension times the block's stays far below the runtime's 2^32
     const int64_t total = (int64_t)a.n_images * a.tiles_x * a.tiles_y, gx = std::min<int64_t>(total, kResizeGridX);
     const dim3 grid((unsigned)gx, (unsigned)((total + gx - 1) / gx)), block(256);
-    // a plan that converts (mj_plan_create_resized_mode): grey to RGB, or colour to L
+    // a plan that converts (mj_plan_request.mode with a size): grey to RGB, or colour to L
     const bool converts = out_ncomp && out_ncomp != ncomp;
     // how the source is read (transposing orientations: the oriented image's rows are the stored columns — the other layout's
     // way of reading; a.orient is set on plans of oriented-style instances only)
     const bool xmajor = ((a.layout & 1) == 0) != (a.orient == 2);
-    // The style of a native instance, <MIRROR, ORIENT>: <false, false> for a plan of mj_plan_create_resized (esize 1, no mirror —
+    // The style of a native instance, <MIRROR, ORIENT>: <false, false> for a plan with a size and nothing else (esize 1, no mirror —
     // the instances that were there before the others), <true, false> with mirror flags, <false, true> the oriented style, whose
     // per-image byte holds both store flips.  There are no signed mirror instances (half the count): a signed plan with mirror
     // flags takes the oriented instance, whose byte holds a mirror flag in bit 0 as it holds an orientation's.  Converting and

@@ -1,6 +1,6 @@
-// Plan creation for the resized plans (mj_plan_create_resized and its six descendants): host code only.  The tap tables'
-// arithmetic (build_resize_axis), the kernels, launch_resize and build_normalize_table are resize.hip's; this file decides what they
-// are given.  Every entry point fills a ResizeRequest, and create_resized goes through it in named steps:
+// Plan creation for the resized plans (a mj_plan_request with a size): host code only.  The tap tables' arithmetic
+// (build_resize_axis), the kernels, launch_resize and build_normalize_table are resize.hip's; this file decides what they are
+// given.  create_resized takes the normalised request (plan.h: PlanRequest) and goes through it in named steps:
 //   placed_source_ranges   placed plans: what every image's axes need of their source, and the window plan derived from that
 //   TapTables              one table per distinct axis, range-checked, reversed for orientations, serialised for the kernels
 //   choose_tile            the tile a workgroup takes and where its parts lie in LDS — a pure function of the tables and sizes
@@ -11,20 +11,6 @@
 #include "plan.h"
 
 namespace {
-
-// What a resized plan is asked for.  filter and mode as the caller gave them (checked here); orient: NULL or one EXIF orientation
-// per image; places: NULL or one per image; fill: NULL (zeros) or one byte per output component.
-struct ResizeRequest {
-    const char *fn;       // (the entry point's name, for the messages)
-    mj_context *ctx; const mj_batch *b; const mj_roi *rois;
-    int32_t out_width, out_height;
-    const int32_t *slots; int32_t n_slots;
-    mj_plan **out;
-    const mj_output_desc *output = nullptr;
-    const uint8_t *orient = nullptr;
-    int filter = MJ_FILTER_BILINEAR, mode = MJ_MODE_NATIVE;
-    const mj_place *places = nullptr; const uint8_t *fill = nullptr;
-};
 
 struct AxisHost {
     std::vector<int32_t> lo, cnt;
@@ -44,8 +30,10 @@ struct AxisHost {
 int round16(int64_t v) { return (int)((v + 15) & ~(int64_t)15); }
 int dtype_size(int dtype) { return dtype == MJ_DTYPE_U8 ? 1 : dtype == MJ_DTYPE_F32 ? 4 : 2; }
 
-// what mj_plan_create_resized_as and mj_host_normalize_table refuse: nullptr when `o` is fine, else the reason
-const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std) {
+}  // namespace
+
+// what mj_plan_request.output and mj_host_normalize_table refuse: nullptr when the description is fine, else the reason
+const char *mj::output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std) {
     if (dtype != MJ_DTYPE_U8 && dtype != MJ_DTYPE_F16 && dtype != MJ_DTYPE_BF16 && dtype != MJ_DTYPE_F32) return "dtype is none of MJ_DTYPE_U8 / F16 / BF16 / F32";
     if (!normalize) return nullptr;
     if (dtype == MJ_DTYPE_U8) return "normalize needs a float dtype (MJ_DTYPE_U8 stores the resized bytes)";
@@ -56,17 +44,23 @@ const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean
     return nullptr;
 }
 
+namespace {
+using mj::PlanRequest;
+
 // ---- placed plans: the source ranges -------------------------------------------------------------------------------------
 // What every axis of every image needs of its source — the taps of the canvas entries the image covers reach source entries
 // [x0, x0 + nx) x [y0, y0 + ny) of the oriented image or window, whose size is sw x sh (what the tables are made for).
 struct Need { int x0, nx, y0, ny, sw, sh; };
-// In: the request, its orientations (NULL: none) and windows (NULL: whole images).  Out: `need`, one per image, and `derived` —
+// In: the request, with its orientations (NULL: none) and windows (NULL: whole images).  Out: `need`, one per image, and `derived` —
 // where the ranges are less than the whole and the rule below says so, the windows of those ranges, as if the caller had asked
-// for them (the plan becomes a window plan: restart segments and MCUs outside are skipped as mj_plan_create_roi skips them, and
+// for them (the plan becomes a window plan: restart segments and MCUs outside are skipped as for a caller's windows, and
 // the tables are rebased to the range); else empty, and every range starts at 0 (tables over the whole image or window).
-int placed_source_ranges(const ResizeRequest &q, const uint8_t *orient, const mj_roi *rois, std::vector<Need> &need, std::vector<mj_roi> &derived) {
+int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vector<mj_roi> &derived) {
     const mj_batch *b = q.b;
-    if (!b->images && b->n_images > 0) return fail(q.ctx, MJ_ERR_INVALID, "%s: NULL argument", q.fn);
+    const char *fn = mj::kCreateFn;
+    const mj_roi *rois = q.r.rois; const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
+    const int filter = q.r.filter, out_width = q.r.out_width, out_height = q.r.out_height;
+    if (!b->images && b->n_images > 0) return fail(q.ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     need.resize((size_t)b->n_images);
     int64_t area_need = 0, area_all = 0;
     std::map<std::vector<int>, std::pair<int, int>> spans;      // (a batch of one size and one placement: one table per axis)
@@ -76,9 +70,9 @@ int placed_source_ranges(const ResizeRequest &q, const uint8_t *orient, const mj
         auto it = spans.find(key);
         if (it != spans.end()) { *first = it->second.first; *len = it->second.second; return; }
         std::vector<int32_t> lo((size_t)resized), cnt((size_t)resized);
-        const int ks = mj::resize_axis_ksize(in_size, resized, q.filter);
+        const int ks = mj::resize_axis_ksize(in_size, resized, filter);
         std::vector<int32_t> k((size_t)resized * ks);
-        mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), k.data(), ks, q.filter);
+        mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), k.data(), ks, filter);
         const int j0 = std::max(0, -off), j1 = std::min(resized, canvas - off) - 1;     // the resized entries on the canvas
         *first = lo[(size_t)j0]; *len = lo[(size_t)j1] + cnt[(size_t)j1] - lo[(size_t)j0];
         spans[key] = {*first, *len};
@@ -91,20 +85,20 @@ int placed_source_ranges(const ResizeRequest &q, const uint8_t *orient, const mj
         return mj_roi{0, 0, W, H};
     };
     for (int i = 0; i < b->n_images; ++i) {
-        const mj_place &pl = q.places[i];
+        const mj_place &pl = places[i];
         if (pl.width < 1 || pl.height < 1 || pl.width > 65535 || pl.height > 65535 || pl.x < -65535 || pl.x > 65535 || pl.y < -65535 || pl.y > 65535)
             return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: place (width=%d, height=%d, x=%d, y=%d): the size must be 1..65535, the offsets within +-65535",
-                        q.fn, i, pl.width, pl.height, pl.x, pl.y);
-        if (pl.x >= q.out_width || pl.y >= q.out_height || (int64_t)pl.x + pl.width <= 0 || (int64_t)pl.y + pl.height <= 0)
-            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: a %d x %d image at (%d, %d) does not meet the %d x %d canvas", q.fn, i, pl.width, pl.height,
-                        pl.x, pl.y, q.out_width, q.out_height);
+                        fn, i, pl.width, pl.height, pl.x, pl.y);
+        if (pl.x >= out_width || pl.y >= out_height || (int64_t)pl.x + pl.width <= 0 || (int64_t)pl.y + pl.height <= 0)
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: a %d x %d image at (%d, %d) does not meet the %d x %d canvas", fn, i, pl.width, pl.height,
+                        pl.x, pl.y, out_width, out_height);
         const int W = whole(i).width, H = whole(i).height;
         mj_roi r = rois ? rois[i] : whole(i), tmp;
         Need &nd = need[(size_t)i] = Need{0, r.width, 0, r.height, r.width, r.height};
         // (a window the plan will refuse, or a size no table is built for: left as it is, for the code that refuses it)
         if (W < 1 || H < 1 || W > 65535 || H > 65535 || !mj::stored_window(1, W, H, r, &tmp)) { area_all += 1; area_need += 1; continue; }
-        span(r.width, pl.width, pl.x, q.out_width, &nd.x0, &nd.nx);
-        span(r.height, pl.height, pl.y, q.out_height, &nd.y0, &nd.ny);
+        span(r.width, pl.width, pl.x, out_width, &nd.x0, &nd.nx);
+        span(r.height, pl.height, pl.y, out_height, &nd.y0, &nd.ny);
         area_all += (int64_t)r.width * r.height; area_need += (int64_t)nd.nx * nd.ny;
     }
     // The rule: a caller's windows make a window plan anyway, and it shrinks to what is needed.  Whole images stay whole: a
@@ -288,47 +282,18 @@ std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize) {
     return lut;
 }
 
-// ---- the plan: every entry point's name and arguments in a request (what one does not take keeps the request's default) ----------
-int create_resized(const ResizeRequest &q) {
-    auto [fn, ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter, asked_mode, asked_places, fill] = q;
-    if (!mj::resize_filter_known(filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, filter);
-    if (asked_mode != MJ_MODE_NATIVE && asked_mode != MJ_MODE_L && asked_mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, asked_mode);
-    // (the files' own count: the plan of mj_plan_create_resized_filtered, made by the code that makes it there.  mode: 0, or CO)
-    const int mode = asked_mode == mj::batch_ncomp(b) ? MJ_MODE_NATIVE : asked_mode;
-    // (every image stretched over the whole canvas: the plan of mj_plan_create_resized_mode, likewise.  places: NULL, or not all so)
-    bool stretched = true;
-    for (int i = 0; asked_places && b && i < b->n_images && stretched; ++i)
-        stretched = asked_places[i].width == out_width && asked_places[i].height == out_height && asked_places[i].x == 0 && asked_places[i].y == 0;
-    const mj_place *places = stretched ? nullptr : asked_places;
-    // the orientations checked (NULL, or all of them 1: a plan without them.  orient: NULL, or 1..8 per image, not all of them 1)
-    bool upright = true;
-    for (int i = 0; orientations && b && i < b->n_images; ++i) {
-        if (orientations[i] < 1 || orientations[i] > 8) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: orientation %d (must be 1..8)", fn, i, (int)orientations[i]);
-        upright = upright && orientations[i] == 1;
-    }
-    const uint8_t *orient = upright ? nullptr : orientations;
-    // the output description: it needs nothing else, not even a context (the message is then mj_last_error(NULL)'s).
-    // (A batch's component count is its first image's; all three entries are looked at when there is no image to ask.)
-    const int dtype = output ? output->dtype : MJ_DTYPE_U8;
-    if (output)
-        if (const char *why = output_fault(dtype, output->normalize != 0, mode ? mode : mj::batch_ncomp(b), output->mean, output->std))
-            return fail(ctx, MJ_ERR_INVALID, "%s: output: %s", fn, why);
-    if (!ctx) return MJ_ERR_INVALID;
-    if (!b || !out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
-    *out = nullptr;
-    const int esize = dtype_size(dtype);
-    if (out_width < 1 || out_height < 1 || out_width > 65535 || out_height > 65535)
-        return fail(ctx, MJ_ERR_INVALID, "%s: output size %d x %d (both must be 1..65535)", fn, out_width, out_height);
-    if (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT))
-        return fail(ctx, MJ_ERR_INVALID, "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none", fn);
-    if (!slots) n_slots = b->n_images;
-    for (int i = 0; slots && i < b->n_images; ++i)
-        if (slots[i] < 0 || slots[i] >= n_slots)
-            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, slots[i], n_slots);
+}  // namespace
+
+// ---- the plan, from a normalised request with a size ------------------------------------------------------------------------------
+int mj::create_resized(const PlanRequest &q) {
+    const char *fn = kCreateFn;
+    mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
+    auto [rois, orient, mode, out_width, out_height, slots, n_slots, output, filter, places, fill] = q.r;
+    const int dtype = output ? output->dtype : MJ_DTYPE_U8, esize = dtype_size(dtype);
     std::vector<Need> need;
     std::vector<mj_roi> derived;
     if (places) {
-        if (int rc = placed_source_ranges(q, orient, rois, need, derived)) return rc;
+        if (int rc = placed_source_ranges(q, need, derived)) return rc;
         if (!derived.empty()) rois = derived.data();
     }
     // oriented plans: all images transposing (orientations 5..8) or none — the two read their source in different ways, so
@@ -342,18 +307,14 @@ int create_resized(const ResizeRequest &q) {
             if (((mj::orient_bits(orient[i]) & 4) != 0) != swapped)
                 return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: orientations that exchange width and height (5..8) and others do not share a resized plan; split the batch", fn, i);
         if (rois) {
-            stored.resize((size_t)b->n_images);
-            for (int i = 0; i < b->n_images; ++i)
-                if (!mj::stored_window(orient[i], b->images[i].width, b->images[i].height, rois[i], &stored[(size_t)i]))
-                    return fail(ctx, MJ_ERR_INVALID, "%s: image %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image", fn,
-                                i, rois[i].x, rois[i].y, rois[i].width, rois[i].height);
+            if (int rc = stored_windows(q, rois, stored)) return rc;
             rois = stored.data();
         }
     }
     mj_plan *p = nullptr;
     // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
     if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
-    struct Guard { mj_plan *p; ~Guard() { if (p) mj_plan_destroy(p); } } guard{p};
+    PlanGuard guard{p};
     // C: the source's components.  A plan that converts stores CO of them per pixel and runs both passes, and T, on CT = 1:
     // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
     const int C = p->ncomp, n = p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
@@ -440,8 +401,6 @@ int create_resized(const ResizeRequest &q) {
     return MJ_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
@@ -460,7 +419,7 @@ int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32
 }
 
 int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
-    if (!out || dtype == MJ_DTYPE_U8 || output_fault(dtype, true, 1, &mean, &std)) return MJ_ERR_INVALID;
+    if (!out || dtype == MJ_DTYPE_U8 || mj::output_fault(dtype, true, 1, &mean, &std)) return MJ_ERR_INVALID;
     uint32_t bits[256];
     mj::build_normalize_table(dtype, mean, std, bits);
     for (int v = 0; v < 256; ++v) {
@@ -468,37 +427,6 @@ int mj_host_normalize_table(int32_t dtype, float mean, float std, void *out) {
         else static_cast<uint16_t *>(out)[v] = (uint16_t)bits[v];
     }
     return MJ_OK;
-}
-
-int mj_plan_create_resized(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                           const int32_t *slots, int32_t n_slots, mj_plan **out) {
-    return create_resized({"mj_plan_create_resized", ctx, b, rois, out_width, out_height, slots, n_slots, out});
-}
-
-int mj_plan_create_resized_as(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                              const int32_t *slots, int32_t n_slots, const mj_output_desc *output, mj_plan **out) {
-    return create_resized({"mj_plan_create_resized_as", ctx, b, rois, out_width, out_height, slots, n_slots, out, output});
-}
-
-int mj_plan_create_resized_oriented(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, mj_plan **out) {
-    return create_resized({"mj_plan_create_resized_oriented", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations});
-}
-
-int mj_plan_create_resized_filtered(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                    const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int32_t filter, mj_plan **out) {
-    return create_resized({"mj_plan_create_resized_filtered", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter});
-}
-
-int mj_plan_create_resized_mode(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations, int32_t filter, int32_t mode, mj_plan **out) {
-    return create_resized({"mj_plan_create_resized_mode", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter, mode});
-}
-
-int mj_plan_create_resized_placed(mj_context *ctx, const mj_batch *b, const mj_roi *rois, int32_t out_width, int32_t out_height,
-                                  const int32_t *slots, int32_t n_slots, const mj_output_desc *output, const uint8_t *orientations,
-                                  int32_t filter, int32_t mode, const mj_place *places, const uint8_t fill[3], mj_plan **out) {
-    return create_resized({"mj_plan_create_resized_placed", ctx, b, rois, out_width, out_height, slots, n_slots, out, output, orientations, filter, mode, places, fill});
 }
 
 int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {

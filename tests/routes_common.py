@@ -22,6 +22,18 @@ NORMALIZE = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
 _resized = {}
 
 
+def create_with(lib, ctx, batch_c, h, **fields) -> int:
+    """mj_plan_create_with(ctx, &batch_c, &request, &h) as a C caller makes it: ``fields`` are mj_plan_request's, the rest of the
+    request zeroed — ctypes arrays of RoiC / PlaceC as they are, an OutputDescC by pointer, NumPy arrays by address."""
+    import ctypes
+
+    from pyjpegdecoder_amd import _binding as B
+    r = B.PlanRequestC()
+    for name, v in fields.items():
+        setattr(r, name, v.ctypes.data if isinstance(v, np.ndarray) else ctypes.pointer(v) if isinstance(v, B.OutputDescC) else v)
+    return lib.mj_plan_create_with(ctx, None if batch_c is None else ctypes.byref(batch_c), ctypes.byref(r), ctypes.byref(h))
+
+
 def expected(full: np.ndarray, win=None, size=None, dtype=None, normalize=None, mirror: bool = False, layout: str = "xmajor",
              key=None) -> np.ndarray:
     """One file's output: ``full`` is the oracle's (W, H[, 3]) image.  uint8 pixels, or the bit patterns (uint16 / uint32) of

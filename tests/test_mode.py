@@ -1,4 +1,4 @@
-"""Output colour mode on the MI355X (mj_plan_create_mode / mj_plan_create_resized_mode, BatchDecoder's ``mode=``): every output
+"""Output colour mode on the MI355X (mj_plan_request.mode with and without a size, BatchDecoder's ``mode=``): every output
 is tools/mode_model.py, then orient_model.py, then resize_model.py, then normalize_model.py applied to the ORACLE's pixels —
 never to the library's own output.  tests/test_mode_host.py pins mode_model to Pillow's convert() on the CPU."""
 import numpy as np
@@ -358,8 +358,9 @@ def test_no_conversion_needed_is_a_call_without_the_argument(fixtures, layout):
             assert shapes[0] == shapes[1] == shapes[2] and infos[0] == infos[1] == infos[2]
             # the C ABI's own refusal of a mode that is none of MJ_MODE_*
             h, bc, lib = ctypes.c_void_p(), prep.to_c(), dec.ctx.lib
-            assert lib.mj_plan_create_resized_mode(dec.ctx.handle, ctypes.byref(bc), None, 8, 8, None, 0, None, None, 0, 2, ctypes.byref(h)) == B.MJ_ERR_INVALID
-            assert lib.mj_plan_create_mode(dec.ctx.handle, ctypes.byref(bc), None, None, 2, ctypes.byref(h)) == B.MJ_ERR_INVALID
+            from routes_common import create_with
+            assert create_with(lib, dec.ctx.handle, bc, h, out_width=8, out_height=8, mode=2) == B.MJ_ERR_INVALID
+            assert create_with(lib, dec.ctx.handle, bc, h, mode=2) == B.MJ_ERR_INVALID
             assert not h.value and b"mode 2 is none of MJ_MODE_" in lib.mj_last_error(dec.ctx.handle)
     finally:
         dec.close()

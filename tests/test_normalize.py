@@ -1,4 +1,4 @@
-"""Model-ready output on the MI355X (mj_plan_create_resized_as; decode / decode_device / decode_device_iter with dtype=,
+"""Model-ready output on the MI355X (mj_plan_request.output; decode / decode_device / decode_device_iter with dtype=,
 normalize=, mirror=): every element is, bit for bit, tools/normalize_model.py — which tests/test_normalize_host.py pins to
 torch's CPU chain — applied to tools/resize_model.py's resize of the oracle's pixels, laid out per layout and flipped along the
 width where mirrored.  Comparisons are on the raw bits (uint16 / uint32 views), never a tolerance."""
@@ -391,14 +391,15 @@ def test_arguments_are_checked_through_every_entry_point_and_empty_lists_have_th
         d = B.OutputDescC()
         d.dtype, d.normalize = B.MJ_DTYPE_F16, 1
         d.mean[:], d.std[:] = (0.0, 0.0, 0.0), (1.0, -1.0, 1.0)
-        assert L.mj_plan_create_resized_as(dec.ctx.handle, ctypes.byref(bc), None, 8, 8, None, 0, ctypes.byref(d), ctypes.byref(h)) == B.MJ_ERR_INVALID
+        from routes_common import create_with
+        assert create_with(L, dec.ctx.handle, bc, h, out_width=8, out_height=8, output=d) == B.MJ_ERR_INVALID
         assert b"std" in L.mj_last_error(dec.ctx.handle)
         d.dtype = 9
-        assert L.mj_plan_create_resized_as(dec.ctx.handle, ctypes.byref(bc), None, 8, 8, None, 0, ctypes.byref(d), ctypes.byref(h)) == B.MJ_ERR_INVALID
+        assert create_with(L, dec.ctx.handle, bc, h, out_width=8, out_height=8, output=d) == B.MJ_ERR_INVALID
         assert b"dtype" in L.mj_last_error(dec.ctx.handle)
-        assert L.mj_plan_create_resized_as(dec.ctx.handle, ctypes.byref(bc), None, 0, 8, None, 0, None, ctypes.byref(h)) == B.MJ_ERR_INVALID
+        assert create_with(L, dec.ctx.handle, bc, h, out_width=0, out_height=8, output=None) == B.MJ_ERR_INVALID
         assert b"output size" in L.mj_last_error(dec.ctx.handle)
-        assert L.mj_plan_create_resized_as(dec.ctx.handle, ctypes.byref(bc), None, 8, 8, None, 0, None, ctypes.byref(h)) == B.MJ_OK
+        assert create_with(L, dec.ctx.handle, bc, h, out_width=8, out_height=8, output=None) == B.MJ_OK
         info = B.PlanInfoC()
         L.mj_plan_get_info(h, ctypes.byref(info))
         L.mj_plan_destroy(h)

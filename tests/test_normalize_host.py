@@ -197,10 +197,11 @@ def test_a_narrowed_request_takes_its_files_arguments_along():
 
 
 def test_entry_point_refuses_a_bad_output_without_a_device(lib):
-    """mj_plan_create_resized_as looks at the output description before anything else: MJ_ERR_INVALID with a message (no
+    """mj_plan_create_with looks at the output description before the context: MJ_ERR_INVALID with a message (no
     context: mj_last_error(NULL)'s) for a dtype that is none of the four, normalize with MJ_DTYPE_U8, a std <= 0 or not finite, a
     mean not finite."""
     from pyjpegdecoder_amd import _binding as B
+    from routes_common import create_with
     h = ctypes.c_void_p()
 
     def call(dtype, normalize, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
@@ -208,7 +209,7 @@ def test_entry_point_refuses_a_bad_output_without_a_device(lib):
         d.dtype, d.normalize = dtype, normalize
         d.mean[:] = mean
         d.std[:] = std
-        rc = lib.mj_plan_create_resized_as(None, None, None, 8, 8, None, 0, ctypes.byref(d), ctypes.byref(h))
+        rc = create_with(lib, None, None, h, out_width=8, out_height=8, output=d)
         return rc, lib.mj_last_error(None)
     for dtype in (4, -1, 99):
         rc, msg = call(dtype, 0)
@@ -223,7 +224,7 @@ def test_entry_point_refuses_a_bad_output_without_a_device(lib):
         rc, msg = call(B.MJ_DTYPE_F32, 1, mean=mean)
         assert rc == B.MJ_ERR_INVALID and b"mean" in msg, (mean, msg)
     # (without normalize, mean and std are not looked at)
-    lib.mj_plan_create_resized(None, None, None, 0, 0, None, 0, ctypes.byref(h))
+    create_with(lib, None, None, h)
     rc, msg = call(B.MJ_DTYPE_F32, 0, std=(0.0, 0.0, 0.0))
     assert rc == B.MJ_ERR_INVALID and b"std" not in msg.split(b"output:")[-1]
     # the Python binding refuses an output without a size
@@ -233,7 +234,7 @@ def test_entry_point_refuses_a_bad_output_without_a_device(lib):
 
 def test_output_desc_layout_and_prototypes_match_the_binding(lib, tmp_path):
     from pyjpegdecoder_amd import _binding as B
-    for name in ("mj_plan_create_resized_as", "mj_host_normalize_table"):
+    for name in ("mj_host_normalize_table",):
         assert name in B.EXPORTS and hasattr(lib, name), name
     assert (B.MJ_DTYPE_U8, B.MJ_DTYPE_F16, B.MJ_DTYPE_BF16, B.MJ_DTYPE_F32) == (0, 1, 2, 3)
     gcc = shutil.which("gcc")
@@ -245,10 +246,8 @@ def test_output_desc_layout_and_prototypes_match_the_binding(lib, tmp_path):
     proto.write_text("""
 #include "mijpeg.h"
 int main(void) {
-  int (*a)(mj_context *, const mj_batch *, const mj_roi *, int32_t, int32_t, const int32_t *, int32_t, const mj_output_desc *,
-           mj_plan **) = mj_plan_create_resized_as;
   int (*b)(int32_t, float, float, void *) = mj_host_normalize_table;
-  (void)a; (void)b;
+  (void)b;
   return 0;
 }
 """)

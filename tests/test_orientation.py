@@ -1,4 +1,4 @@
-"""EXIF orientation on the MI355X (mj_plan_create_oriented / mj_plan_create_resized_oriented, BatchDecoder's ``orientation=``):
+"""EXIF orientation on the MI355X (mj_plan_request.orientations with and without a size, BatchDecoder's ``orientation=``):
 every output is tools/orient_model.py — and, with ``size``, tools/resize_model.py on top of it — applied to the oracle's
 pixels, never to the library's own output.  tests/test_orientation_host.py pins both models to Pillow on the CPU."""
 import struct

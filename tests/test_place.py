@@ -1,4 +1,4 @@
-"""Aspect-preserving sizing on the MI355X (mj_plan_create_resized_placed, BatchDecoder.decode / decode_device /
+"""Aspect-preserving sizing on the MI355X (mj_plan_request.places / fill, BatchDecoder.decode / decode_device /
 decode_device_iter(size=..., resize_to=..., place=..., fill=...)): every output is byte for byte tools/place_model.py — which
 tests/test_place_host.py pins to Pillow and to the libraries' rules — applied to the oracle's pixels of the image or window, in
 every layout.  Expected values never come from the library."""
@@ -320,11 +320,13 @@ def test_nothing_moved_and_refusals(fixtures):
             plan = B.Plan(dec.ctx, prep.to_c(), keep, size=size, filter="bicubic", **kw)
             shapes.append(plan.resize_shape())
             plan.close()
-        # places=NULL through the new entry point
+        # places=NULL through the C ABI
         import ctypes
+
+        from routes_common import create_with
         h = ctypes.c_void_p()
-        dec.ctx.check(dec.ctx.lib.mj_plan_create_resized_placed(dec.ctx.handle, ctypes.byref(prep.to_c()), None, size[0], size[1], None, 0, None,
-                                                                 None, B.MJ_FILTER_BICUBIC, B.MJ_MODE_NATIVE, None, None, ctypes.byref(h)))
+        dec.ctx.check(create_with(dec.ctx.lib, dec.ctx.handle, prep.to_c(), h, out_width=size[0], out_height=size[1], filter=B.MJ_FILTER_BICUBIC,
+                                  mode=B.MJ_MODE_NATIVE, places=None, fill=None))
         out = (ctypes.c_int32 * 8)()
         dec.ctx.check(dec.ctx.lib.mj_debug_resize_shape(h, out))
         dec.ctx.lib.mj_plan_destroy(h)

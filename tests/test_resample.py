@@ -1,4 +1,4 @@
-"""Resample filters of a decode to a fixed size on the MI355X (mj_plan_create_resized_filtered, BatchDecoder.decode /
+"""Resample filters of a decode to a fixed size on the MI355X (mj_plan_request.filter, BatchDecoder.decode /
 decode_device / decode_device_iter(size=..., resample=...)): every output is byte for byte tools/resize_model.py with that filter
 — which tests/test_resample_host.py pins to Pillow's resize(size, filter) — applied to the oracle's pixels of the image or
 window, in every layout.  Expected values never come from the library."""

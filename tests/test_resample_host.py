@@ -214,7 +214,7 @@ def test_resample_argument_checks_need_no_gpu():
 
 def test_new_entry_points_are_exported_and_declared_as_c(lib, tmp_path):
     from pyjpegdecoder_amd import _binding as B
-    for name in ("mj_host_resize_table_filtered", "mj_plan_create_resized_filtered", "mj_debug_resize_shape"):
+    for name in ("mj_host_resize_table_filtered", "mj_debug_resize_shape"):
         assert name in B.EXPORTS and hasattr(lib, name), name
     gcc = shutil.which("gcc")
     if gcc is None:
@@ -225,11 +225,9 @@ def test_new_entry_points_are_exported_and_declared_as_c(lib, tmp_path):
 #include "mijpeg.h"
 int main(void) {
   int (*a)(int32_t, int32_t, int32_t, int32_t *, int32_t *, int32_t *, int32_t, int32_t *) = mj_host_resize_table_filtered;
-  int (*b)(mj_context *, const mj_batch *, const mj_roi *, int32_t, int32_t, const int32_t *, int32_t, const mj_output_desc *,
-           const uint8_t *, int32_t, mj_plan **) = mj_plan_create_resized_filtered;
   int (*c)(const mj_plan *, int32_t *) = mj_debug_resize_shape;
   int filters[MJ_FILTER_BILINEAR == 0 && MJ_FILTER_LANCZOS == 4 ? 1 : -1] = {MJ_FILTER_BOX + MJ_FILTER_HAMMING + MJ_FILTER_BICUBIC};
-  (void)a; (void)b; (void)c; (void)filters;
+  (void)a; (void)c; (void)filters;
   return 0;
 }
 """)
@@ -237,6 +235,7 @@ int main(void) {
                    check=True)
     # without a context nothing is created and nothing crashes: an unknown filter and a missing context are both refused
     h = ctypes.c_void_p()
-    assert lib.mj_plan_create_resized_filtered(None, None, None, 8, 8, None, 0, None, None, 7, ctypes.byref(h)) == B.MJ_ERR_INVALID
-    assert lib.mj_plan_create_resized_filtered(None, None, None, 8, 8, None, 0, None, None, B.MJ_FILTER_LANCZOS, ctypes.byref(h)) == B.MJ_ERR_INVALID
+    from routes_common import create_with
+    assert create_with(lib, None, None, h, out_width=8, out_height=8, filter=7) == B.MJ_ERR_INVALID
+    assert create_with(lib, None, None, h, out_width=8, out_height=8, filter=B.MJ_FILTER_LANCZOS) == B.MJ_ERR_INVALID
     assert lib.mj_debug_resize_shape(None, (ctypes.c_int32 * 8)()) == B.MJ_ERR_INVALID

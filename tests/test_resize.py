@@ -1,4 +1,4 @@
-"""Decode to a fixed size on the MI355X (mj_plan_create_resized, BatchDecoder.decode / decode_device(size=...)): every output
+"""Decode to a fixed size on the MI355X (mj_plan_request.out_width / out_height, BatchDecoder.decode / decode_device(size=...)): every output
 is byte for byte tools/resize_model.py — which tests/test_resize_host.py pins to Pillow's resize(size, Image.BILINEAR) —
 applied to the oracle's pixels of the image or window, in every layout, for shrinking, enlarging and unchanged axes."""
 import numpy as np
@@ -272,19 +272,19 @@ def test_resized_plans_refuse_what_they_cannot_do():
         prep = prepare_batch(files)
         bc = prep.to_c()
         h = ctypes.c_void_p()
+        from routes_common import create_with
         for ow, oh in ((0, 5), (5, 0), (-1, 5), (70000, 5)):
-            assert L.mj_plan_create_resized(dec.ctx.handle, ctypes.byref(bc), None, ow, oh, None, 0, ctypes.byref(h)) == B.MJ_ERR_INVALID
+            assert create_with(L, dec.ctx.handle, bc, h, out_width=ow, out_height=oh) == B.MJ_ERR_INVALID
             assert b"output size" in L.mj_last_error(dec.ctx.handle)
         for bad in ([0, 2], [-1, 0]):
             sl = np.asarray(bad, dtype=np.int32)
-            assert L.mj_plan_create_resized(dec.ctx.handle, ctypes.byref(bc), None, 8, 8, sl.ctypes.data_as(ctypes.c_void_p), 2,
-                                            ctypes.byref(h)) == B.MJ_ERR_INVALID
+            assert create_with(L, dec.ctx.handle, bc, h, out_width=8, out_height=8, slots=sl, n_slots=2) == B.MJ_ERR_INVALID
             assert b"slot" in L.mj_last_error(dec.ctx.handle)
         for flag in (B.MJ_FLAG_KEEP_PLANES, B.MJ_FLAG_KEEP_IDCT):
             bc2 = prepare_batch(files, flags=flag).to_c()
-            assert L.mj_plan_create_resized(dec.ctx.handle, ctypes.byref(bc2), None, 8, 8, None, 0, ctypes.byref(h)) == B.MJ_ERR_INVALID
+            assert create_with(L, dec.ctx.handle, bc2, h, out_width=8, out_height=8) == B.MJ_ERR_INVALID
         rois = (B.RoiC * 2)(B.RoiC(0, 0, 5, 5), B.RoiC(190, 0, 11, 5))
-        assert L.mj_plan_create_resized(dec.ctx.handle, ctypes.byref(bc), rois, 8, 8, None, 0, ctypes.byref(h)) == B.MJ_ERR_INVALID
+        assert create_with(L, dec.ctx.handle, bc, h, rois=rois, out_width=8, out_height=8) == B.MJ_ERR_INVALID
         assert b"image 1" in L.mj_last_error(dec.ctx.handle)
         plain = B.Plan(dec.ctx, bc, {"prep": prep, "n_images": 2})
         try:

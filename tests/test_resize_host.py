@@ -115,7 +115,7 @@ def test_decode_size_argument_checks_need_no_gpu():
 
 def test_new_entry_points_are_exported_and_declared_as_c(lib, tmp_path):
     from pyjpegdecoder_amd import _binding as B
-    names = ("mj_plan_create_resized", "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table")
+    names = ("mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table")
     for name in names:
         assert name in B.EXPORTS and hasattr(lib, name), name
     gcc = shutil.which("gcc")
@@ -128,11 +128,10 @@ def test_new_entry_points_are_exported_and_declared_as_c(lib, tmp_path):
 #include <stdio.h>
 #include "mijpeg.h"
 int main(void) {
-  int (*a)(mj_context *, const mj_batch *, const mj_roi *, int32_t, int32_t, const int32_t *, int32_t, mj_plan **) = mj_plan_create_resized;
   int (*b)(mj_plan *, int) = mj_plan_fill_source;
   int (*c)(mj_plan *, int, uint8_t *, float *, int64_t *) = mj_plan_time_resize;
   int (*d)(int32_t, int32_t, int32_t *, int32_t *, int32_t *, int32_t, int32_t *) = mj_host_resize_table;
-  (void)a; (void)b; (void)c; (void)d;
+  (void)b; (void)c; (void)d;
   printf("%zu\\n", sizeof(mj_roi));
   return 0;
 }

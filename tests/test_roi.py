@@ -1,4 +1,4 @@
-"""Region-of-interest decode on the MI355X (mj_plan_create_roi, BatchDecoder.decode / decode_device(rois=...)): every window
+"""Region-of-interest decode on the MI355X (mj_plan_request.rois, BatchDecoder.decode / decode_device(rois=...)): every window
 equals the oracle's whole image, sliced, in every layout; only the restart segments the windows need are decoded; nothing
 outside the windows is read or written."""
 import ctypes
@@ -347,17 +347,18 @@ def test_invalid_windows_and_seam_flags_are_rejected():
         prep = prepare_batch(files)
         bc = prep.to_c()
         h = ctypes.c_void_p()
+        from routes_common import create_with
         for bad in [(0, 0, 0, 5), (190, 0, 11, 5), (0, 115, 5, 6), (-1, 0, 5, 5)]:
             rois = (B.RoiC * 2)(B.RoiC(0, 0, 5, 5), B.RoiC(*bad))
-            assert L.mj_plan_create_roi(dec.ctx.handle, ctypes.byref(bc), rois, ctypes.byref(h)) == B.MJ_ERR_INVALID
+            assert create_with(L, dec.ctx.handle, bc, h, rois=rois) == B.MJ_ERR_INVALID
             assert b"image 1" in L.mj_last_error(dec.ctx.handle)
         rois = (B.RoiC * 2)(B.RoiC(0, 0, 5, 5), B.RoiC(0, 0, 5, 5))
         for flag in (B.MJ_FLAG_KEEP_COEF, B.MJ_FLAG_KEEP_PLANES, B.MJ_FLAG_KEEP_IDCT):
             prep2 = prepare_batch(files, flags=flag)
             bc2 = prep2.to_c()
-            assert L.mj_plan_create_roi(dec.ctx.handle, ctypes.byref(bc2), rois, ctypes.byref(h)) == B.MJ_ERR_INVALID
-        # NULL windows: whole images, a plan like mj_plan_create's
-        assert L.mj_plan_create_roi(dec.ctx.handle, ctypes.byref(bc), None, ctypes.byref(h)) == B.MJ_OK
+            assert create_with(L, dec.ctx.handle, bc2, h, rois=rois) == B.MJ_ERR_INVALID
+        # NULL windows: whole images, mj_plan_create's plan
+        assert create_with(L, dec.ctx.handle, bc, h, rois=None) == B.MJ_OK
         L.mj_plan_destroy(h)
     finally:
         dec.close()

@@ -13,7 +13,7 @@ mj_plan_time_resize(iters=1): one warm launch, then one between two HIP events.
     grey_ms                              (b) greyscale files, mode "L" — native: a third of the colour launch's bytes on both sides
     grey_to_rgb_ms                       (c) greyscale files, mode "RGB": reads what (b) reads, writes what (a) writes
     colour_to_l_ms                       (d) colour files, mode "L": reads what (a) reads, writes what (b) writes
-    own_grey_to_rgb_ms, own_copy_ms      (e) the one extra launch of an own-size plan (mj_plan_create_mode) for the greyscale files
+    own_grey_to_rgb_ms, own_copy_ms      (e) the one extra launch of an own-size plan (mj_plan_request.mode) for the greyscale files
                                              under "RGB", and the library's plain 16-bytes-per-lane copy of the bytes it writes
     shape                                mj_debug_resize_shape of every resized plan
 

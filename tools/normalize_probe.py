@@ -1,4 +1,4 @@
-"""Model-ready output (mj_plan_create_resized_as: float16, normalised, mixed mirror flags out of the resize launch) against the
+"""Model-ready output (mj_plan_request.output: float16, normalised, mixed mirror flags out of the resize launch) against the
 plain uint8 resize launch and against what a caller does without it — the uint8 launch followed by the torch chain
 `.to(float32).div(255).sub(mean).div(std).to(float16)` and a `torch.where(flags, x.flip(width), x)` — on the GPU box.
 
@@ -8,7 +8,7 @@ rounds, every round one sample of every point in turn (interleaved, so that a dr
 the median and the spread (min .. max) over the rounds.  A sample of a resize launch is mj_plan_time_resize(iters=1): one warm
 launch, then one between two HIP events.
 
-    u8_ms          the plain resized plan's launch (mj_plan_create_resized), this build
+    u8_ms          the plain resized plan's launch (mj_plan_request.out_width / out_height), this build
     u8_parent_ms   the same from another build of the library (`--parent-lib path/to/libmijpeg.so`, e.g. the parent commit's),
                    loaded into the same process: the same instances, so the two should agree within their spreads
     u8_twin_ms, u8_parent_twin_ms   a second plan of each build — the same code on other buffers: how far two plans of ONE build

@@ -156,7 +156,7 @@ def batch_c(row, prep, torch):
 
 def shape_of(ctx, row, prepared=None):
     """One row's plan on the library of `ctx`, which is only asked for its device: the plan is made on a fresh context.  Returns
-    {"shape": mj_debug_plan_shape's values or None (creation refused), "rc": mj_plan_create's answer, "requests", "size_hash": the
+    {"shape": mj_debug_plan_shape's values or None (creation refused), "rc": mj_plan_create_with's answer, "requests", "size_hash": the
     cache's counters behind the creation, "all_segs": the files' restart segments, "leak": blocks handed out behind
     mj_plan_destroy minus before the creation}."""
     from pyjpegdecoder_amd import _binding as B
@@ -173,12 +173,8 @@ def shape_of(ctx, row, prepared=None):
         b, keep = batch_c(row, prep, torch)
         before = own.cache_stats()
         h = ctypes.c_void_p()
-        arr = None
-        if row["rois"] is not None:
-            arr = (B.RoiC * len(row["rois"]))(*[B.RoiC(*r) for r in row["rois"]])
-            rc = lib.mj_plan_create_roi(own.handle, ctypes.byref(b), arr, ctypes.byref(h))
-        else:
-            rc = lib.mj_plan_create(own.handle, ctypes.byref(b), ctypes.byref(h))
+        request, _arrays = B.plan_request(b.n_images, rois=row["rois"])
+        rc = lib.mj_plan_create_with(own.handle, ctypes.byref(b), ctypes.byref(request), ctypes.byref(h))
         after = own.cache_stats()
         shape = None
         if rc == B.MJ_OK:

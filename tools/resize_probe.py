@@ -1,4 +1,4 @@
-"""Decode to a fixed size (mj_plan_create_resized) against the decode without it and against resizing afterwards with torch, on
+"""Decode to a fixed size (mj_plan_request.out_width / out_height) against the decode without it and against resizing afterwards with torch, on
 the GPU box.
 
 1024 x 1920x1080 4:2:0 files (tools/synth.synth_batch; `--distinct` distinct seeds tiled, DRI = one MCU row, GPU marker scan).
@@ -6,8 +6,8 @@ Per configuration — whole images to 224 x 224, centred 448 x 448 windows to 22
 one process, one JSON line with HIP-event times per step:
 
     base_ms     (a) the same plan's execute without the resize: mj_plan_create for whole images (the fused launch where the
-                    batch takes it), mj_plan_create_roi for windows
-    resized_ms  (b) mj_plan_create_resized's execute: the same launches plus the resize launch
+                    batch takes it), mj_plan_request.rois for windows
+    resized_ms  (b) the resized plan's execute: the same launches plus the resize launch
     resize_ms   (c) the resize launch alone; resize_tbs = (un-resized bytes read + output bytes written) / resize_ms, beside
                     copy_tbs, the rate of a plain 16-bytes-per-lane device copy (mj_device_copy_rate) in the same process
     torch_ms    (d) what a caller does without it: the list decode_device returns, image by image through

@@ -1,11 +1,11 @@
-"""Region-of-interest decode (mj_plan_create_roi) against whole-image decode, on the GPU box.
+"""Region-of-interest decode (mj_plan_request.rois) against whole-image decode, on the GPU box.
 
 1024 x 1920x1080 4:2:0 files (tools/synth.synth_batch; `--distinct` distinct seeds tiled), once with DRI = one MCU row (120)
 and once without restart markers, each through host segmentation and the GPU marker scan.  Per batch, in one process, one
 JSON line per configuration:
 
     plain     whole images, mj_plan_create (the fused launch where the batch takes it)
-    full      full-frame windows (mj_plan_create_roi: stage 0 + stage 1 + the window stage 2)
+    full      full-frame windows (mj_plan_request.rois: stage 0 + stage 1 + the window stage 2)
     c224      centred 224 x 224 windows
     c1024     centred 1024 x 1024 windows
     random    a random window per image (seeded)
