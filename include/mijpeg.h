@@ -195,14 +195,16 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  *
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
  * window -> resize with the filter (to the place's size, onto the canvas) -> mirror -> the output's element type.  In Pillow's
- * terms the result is exif_transpose(img.convert(mode)).crop(window).resize(size, filter).
+ * terms the result is exif_transpose(img.convert(mode)).crop(window).resize(size, filter) — with reducing_gap, Pillow's argument of
+ * that name to that resize.
  *
  * Refusals common to all fields: MJ_ERR_INVALID with a message in mj_last_error — naming the image where there is one — for a
  * value outside what the field takes; MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT together with ANY field that changes the plan
  * (the seam outputs are whole images in stored order, in the files' components, at the files' sizes; a window plan refuses
  * MJ_FLAG_KEEP_COEF too).  Checked in this order, the first fault reported: filter, mode, orientations, output — these before
  * the context is looked at, so that a bad description is diagnosed without a GPU (the message is then mj_last_error(NULL)'s) —,
- * ctx / batch / out, the size, the KEEP flags, slots, places, windows, then the batch itself. */
+ * ctx / batch / out, the size, the KEEP flags, slots, places, windows, then the batch itself.  (reducing_gap's value is checked with
+ * the first four.) */
 typedef struct {
     int32_t x, y, width, height;
 } mj_roi;
@@ -324,6 +326,31 @@ typedef struct {
      * MJ_ERR_UNSUPPORTED: a table with a tap of 2^23 or more in magnitude or with 2^21 + 255 * sum |tap| above 2^31 - 1 (the
      * kernels multiply in 24 bits and add in 32; no size up to 129 comes near either bound). */
     int32_t filter;
+    /* Two-step resize: Pillow's Image.resize(size, filter, reducing_gap=g) (tools/reduce_model.py).  DEFAULT 0: no first step —
+     * also when no image of the batch gets a factor above 1.  Else a finite number >= 1.0, and every image is first shrunk by
+     * integer factors — Image.reduce((fx, fy)), a box average with one rounding — and the reduced image is then resampled with
+     * the filter over the fractional box (0, 0, w / fx, h / fy):
+     *   fx = (int)(w / target_width / g), at least 1, in doubles, divided in that order; fy likewise.  w x h is the image that is
+     *        resized — oriented, its window, after the mode — and the target the size it is resized to (its place's, with places)
+     *   reduce   the output is ceil(w / fx) x ceil(h / fy); a cell of n pixels becomes ((sum + n / 2) * m(n)) >> 24 per component
+     *        in 32-bit unsigned arithmetic, m(n) = (uint32)(float32(2^32) / float32(256 n)); partial cells at the right and
+     *        bottom edges use their own n (mj_host_reduce)
+     *   resample the tap tables of the reduced size over the box, whose bounds are rounded to 32-bit floats as Pillow's are
+     *        (mj_host_resize_table_boxed)
+     * The result is NOT the single-step result (Pillow calls it indistinguishable from g = 3 on); it is, bit for bit,
+     * exif_transpose(img.convert(mode)).crop(window).resize(target, filter, reducing_gap=g) on the canvas.  One more launch
+     * (csrc/reduce.hip) runs between stage 2 and the resize launch, for ALL images of the plan (a 1 x 1 cell is the identity), into
+     * a second plan-owned buffer the resize launch then reads: it cuts the bytes and the taps of the resize of a strong shrink.
+     * mj_plan_time_resize times both launches; its source_bytes stays what was decoded.  With places and windows the windows are
+     * decoded as given (a shrunk window would move the cells).  Pillow's height-first pass order for images more than 100 times
+     * taller than wide is not reproduced (nor is it without the field).
+     * MJ_ERR_INVALID: a value that is not 0 and not a finite number >= 1.0 (checked with filter / mode / orientations / output,
+     * before the context is looked at); set without a size.  MJ_ERR_UNSUPPORTED, naming the image: a cell of more than 65536 pixels.
+     * The field is a float in the four bytes between filter and places that were padding: the request keeps its size and every other
+     * field its offset, so callers built against the request without it — who zero it — ask for what they asked.  A gap a float does
+     * not hold exactly would give other factors than Pillow's double does, so the Python layer refuses such a gap (1.0, 1.5, 2.0,
+     * 3.0 and every other multiple of 2^-20 up to 16 are exact). */
+    float reducing_gap;
     /* Aspect-preserving sizing.  DEFAULT NULL, or every place {out_width, out_height, 0, 0}: every image stretched over the whole
      * of out_width x out_height.  Else that size is a CANVAS, and every image is resized to a size of its own and placed on it
      * (tools/place_model.py): torchvision's Resize(s) + CenterCrop, a letterbox (Pillow's ImageOps.pad), a crop of the resized
@@ -446,6 +473,17 @@ int mj_plan_fill_source(mj_plan *plan, int byte_value);
  * runs the signed instances, the most taps one pixel has along an axis }.  MJ_ERR_INVALID: not a resized plan. */
 int mj_debug_resize_shape(const mj_plan *plan, int32_t out[8]);
 
+/* Test hook: the first step of a resized plan for one image — out = { fx, fy, phase along the width, phase along the height, reduced
+ * width, reduced height, 1 if the plan reduces at all (else 0, factors 1 and the decoded size) }, all in the STORED image's axes: an
+ * axis the orientation reverses has its cell boundaries at phase + k * f, phase = size mod f, and orientations 5..8 exchange the
+ * factors.  MJ_ERR_INVALID: not a resized plan, no such image. */
+int mj_debug_reduce_shape(const mj_plan *plan, int32_t image, int32_t out[7]);
+
+/* Test hook (host only, no context): *normal = the request as plan creation sees it after its checks — every field that names its
+ * default turned into its absence (pointers are the caller's) — or the code of the first fault that needs no context
+ * (mj_last_error(NULL) has the message).  request NULL: a zeroed one. */
+int mj_debug_normalise_request(const mj_batch *batch, const mj_plan_request *request, mj_plan_request *normal);
+
 /* Test hook (host only, reads fields): what plan creation decided, MJ_DEBUG_PLAN_SHAPE_WORDS values in this order —
  *   0 mj_plan_stage1_form's word, 1 fused launch, 2 table slots per image, 3 restart segments, 4 marker-scan jobs;
  *   5 chunk bytes of the synchronisation form, 6 its chunks, 7 stage-0 pieces, 8 index bits and 9 bytes per table of the resolved
@@ -484,6 +522,9 @@ int mj_plan_time_execute(mj_plan *plan, int iters, uint8_t *rgb_device, float *f
 /* A resized plan's resize launch alone (after an execute: it reads what stage 2 left), `iters` times into rgb_device (NULL: where the
  * latest execute wrote): ms per launch, and the bytes of un-resized pixels it reads (written bytes: mj_plan_info.rgb_bytes). */
 int mj_plan_time_resize(mj_plan *plan, int iters, uint8_t *rgb_device, float *ms, int64_t *source_bytes);
+/* A reducing plan's reduce launch alone (mj_plan_request.reducing_gap; after an execute): ms per launch.  It reads the decoded
+ * pixels (mj_plan_time_resize's source_bytes) and writes the reduced images.  MJ_ERR_INVALID: not a reducing plan. */
+int mj_plan_time_reduce(mj_plan *plan, int iters, float *ms);
 
 /* Placement tuning of a plan that is executed many times into ONE output buffer (a service's output slot, a benchmark's step).
  * Where the plan's coefficient store lies relative to that buffer — physically: nothing the virtual addresses show — puts the
@@ -567,6 +608,21 @@ int mj_host_resize_table(int32_t in_size, int32_t out_size, int32_t *xmin, int32
  * MJ_ERR_INVALID also for a filter that is none of them. */
 int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
                                   int32_t taps_stride, int32_t *ksize);
+/* mj_host_resize_table_filtered over the part [in0, in1) of the in_size entries — Pillow's precompute_coeffs(in_size, in0, in1,
+ * out_size): scale = (in1 - in0) / out_size, centres at in0 + (i + 0.5) * scale, bounds clipped to in_size.  in0 and in1 are
+ * rounded to 32-bit floats by the function, as Pillow carries them (mj_plan_request.reducing_gap).  MJ_ERR_INVALID also for a box
+ * that is empty or not inside [0, in_size]. */
+int mj_host_resize_table_boxed(int32_t filter, int32_t in_size, double in0, double in1, int32_t out_size, int32_t *xmin, int32_t *count,
+                               int32_t *taps, int32_t taps_stride, int32_t *ksize);
+/* mj_plan_request.reducing_gap's factors for a src_w x src_h image resized to dst_w x dst_h (host only).  MJ_ERR_INVALID: a size
+ * outside 1..65535, a gap that is not a finite number >= 1.0, NULL. */
+int mj_host_reduce_factors(int32_t src_w, int32_t src_h, int32_t dst_w, int32_t dst_h, double gap, int32_t *fx, int32_t *fy);
+/* The reduce kernel's arithmetic on a row-major (h, w, ncomp) array (host only): out = the (ceil(h / fy), ceil(w / fx), ncomp) reduced
+ * image.  phase_x / phase_y: 0 — cell boundaries at k * f, the partial cell last, Image.reduce itself — or size mod f: boundaries
+ * at phase + k * f, the partial cell first (what the kernel does along an axis the orientation reverses).  MJ_ERR_INVALID: NULL,
+ * a size outside 1..65535, ncomp neither 1 nor 3, a factor below 1, fx * fy above 65536, any other phase. */
+int mj_host_reduce(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, int32_t fx, int32_t fy, int32_t phase_x, int32_t phase_y,
+                   uint8_t *out);
 /* The output table of one component of a plan with mj_plan_request.output, as the library builds it (host only, no context): out
  * = 256 elements of `dtype` (MJ_DTYPE_F16 / BF16: 2 bytes each, MJ_DTYPE_F32: 4), element v what resized byte v is stored as with
  * this mean and std (mean 0, std 1 = no normalisation).  MJ_ERR_INVALID: MJ_DTYPE_U8 or an unknown dtype, NULL, a mean that is

@@ -43,6 +43,8 @@ EXPORTS = (
     "mj_device_copy_rate", "mj_context_launch_clock", "mj_debug_prog_split", "mj_debug_fused_applies", "mj_plan_tune_placement",
     "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table", "mj_host_normalize_table", "mj_host_exif_orientations",
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
+    "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
+    "mj_plan_time_reduce",
     "mj_debug_plan_shape", "mj_debug_cache_stats",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
@@ -114,6 +116,16 @@ class PlanRequestC(ctypes.Structure):
                 ("output", ctypes.POINTER(OutputDescC)), ("filter", ctypes.c_int32), ("places", ctypes.POINTER(PlaceC)),
                 ("fill", ctypes.c_void_p)]
 
+    # mj_plan_request.reducing_gap: a float in the four bytes between filter and places, which the fields above leave as padding —
+    # the structure keeps its size and its fields their offsets
+    @property
+    def reducing_gap(self) -> float:
+        return ctypes.c_float.from_buffer(self, type(self).filter.offset + 4).value
+
+    @reducing_gap.setter
+    def reducing_gap(self, gap: float):
+        ctypes.c_float.from_buffer(self, type(self).filter.offset + 4).value = gap
+
 
 class PlanInfoC(ctypes.Structure):
     _fields_ = [("total_blocks", ctypes.c_int64), ("total_mcus", ctypes.c_int64), ("total_pixels", ctypes.c_int64),
@@ -155,12 +167,18 @@ def load_library():
     L.mj_host_convert_mode.argtypes = [i32, vp, i32, i64, vp]
     L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_debug_resize_shape.argtypes = [vp, ctypes.POINTER(i32)]
+    L.mj_host_resize_table_boxed.argtypes = [i32, i32, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
+    L.mj_host_reduce_factors.argtypes = [i32, i32, i32, i32, ctypes.c_double, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.mj_host_reduce.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.mj_debug_reduce_shape.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    L.mj_debug_normalise_request.argtypes = [ctypes.POINTER(BatchC), ctypes.POINTER(PlanRequestC), ctypes.POINTER(PlanRequestC)]
     L.mj_debug_plan_shape.argtypes = [vp, ctypes.POINTER(i32), i32]
     L.mj_debug_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.mj_host_exif_orientations.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.mj_host_normalize_table.argtypes = [i32, ctypes.c_float, ctypes.c_float, vp]
     L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
     L.mj_plan_time_resize.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
+    L.mj_plan_time_reduce.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
@@ -301,6 +319,42 @@ def resize_table(in_size: int, out_size: int, filter=None):
     return xmin, count, taps
 
 
+def resize_table_boxed(in_size: int, out_size: int, box, filter=None):
+    """mj_host_resize_table_boxed (host only): :func:`resize_table` over the part ``box`` = (in0, in1) of the axis, which the
+    function rounds to 32-bit floats — the resample behind a reduce (tools/reduce_model.py: axis_table)."""
+    L = load_library()
+    ks = ctypes.c_int32()
+    fid = filter_id(filter)
+    if L.mj_host_resize_table_boxed(fid, in_size, float(box[0]), float(box[1]), out_size, None, None, None, 0, ctypes.byref(ks)) != MJ_OK:
+        raise ValueError("mj_host_resize_table_boxed: sizes must be 1..65535 and the box inside the axis")
+    xmin, count = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
+    taps = np.zeros((out_size, ks.value), dtype=np.int32)
+    if L.mj_host_resize_table_boxed(fid, in_size, float(box[0]), float(box[1]), out_size, _ptr(xmin), _ptr(count), _ptr(taps), ks.value,
+                                    ctypes.byref(ks)) != MJ_OK:
+        raise ValueError("mj_host_resize_table_boxed: bad arguments")
+    return xmin, count, taps
+
+
+def reduce_factors(src_w: int, src_h: int, dst_w: int, dst_h: int, gap: float):
+    """mj_host_reduce_factors (host only): (fx, fy) of a two-step resize (tools/reduce_model.py: reduce_factors)."""
+    fx, fy = ctypes.c_int32(), ctypes.c_int32()
+    if load_library().mj_host_reduce_factors(src_w, src_h, dst_w, dst_h, float(gap), ctypes.byref(fx), ctypes.byref(fy)) != MJ_OK:
+        raise ValueError("mj_host_reduce_factors: sizes must be 1..65535 and the gap a finite number >= 1.0")
+    return fx.value, fy.value
+
+
+def reduce(a: np.ndarray, fx: int, fy: int, phase_x: int = 0, phase_y: int = 0) -> np.ndarray:
+    """mj_host_reduce (host only): the reduce kernel's arithmetic on a row-major uint8 (H, W) or (H, W, 3) array
+    (tools/reduce_model.py: reduce)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    h, w = a.shape[:2]
+    nc = a.shape[2] if a.ndim == 3 else 1
+    out = np.empty((-(-h // fy), -(-w // fx)) + a.shape[2:], dtype=np.uint8)
+    if load_library().mj_host_reduce(_ptr(a), w, h, nc, fx, fy, phase_x, phase_y, _ptr(out)) != MJ_OK:
+        raise ValueError("mj_host_reduce: bad arguments")
+    return out
+
+
 def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarray:
     """mj_host_normalize_table (host only): the 256 bit patterns (uint16 for "float16" / "bfloat16", uint32 for "float32") one
     component's resized bytes 0..255 are stored as with this mean and std (tools/normalize_model.py: table_bits)."""
@@ -376,12 +430,14 @@ def output_desc(output):
 
 
 def plan_request(n_images, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None, places=None,
-                 fill=None):
+                 fill=None, reducing_gap=None):
     """(mj_plan_request, the arrays it points to) for a batch of ``n_images`` from Plan's keywords: every keyword is one field of
     the request (include/mijpeg.h), None its default.  Pure: no library, no context.  ValueError for what only a sized or placed
     plan has and for a per-image list that has not one entry for each image."""
     if size is None and (places is not None or filter is not None or output is not None):
         raise ValueError("places, filter and output need size: only a resized plan has a canvas, resamples and has a dense output")
+    if size is None and reducing_gap is not None:
+        raise ValueError("reducing_gap needs size: only a resized plan resamples, in one step or two")
     if fill is not None and places is None:
         raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
     r, keep = PlanRequestC(), {}
@@ -391,6 +447,8 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
         keep["orientations"] = turns = np.ascontiguousarray(orientation, dtype=np.uint8)
         r.orientations = turns.ctypes.data
     r.mode, r.filter = mode_id(mode), filter_id(filter)
+    if reducing_gap is not None:
+        r.reducing_gap = float(reducing_gap)
     if size is not None:
         r.out_width, r.out_height = int(size[0]), int(size[1])
     if slots is not None:
@@ -505,11 +563,12 @@ class Plan:
     name of FILTERS / its MJ_FILTER_*: the resize with that resample filter.  mode: a name of MODES / its MJ_MODE_* — the
     components of the output; info.rgb_bytes, slots and image_offsets then count those.  places: with size — then the canvas —,
     one (width, height, x, y) per image: the size it is resized to and where it lies on the canvas; fill: with places, up to three
-    bytes, one per output component."""
+    bytes, one per output component.  reducing_gap: with size, a number >= 1.0 — the two-step resize, Pillow's argument of that name."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None, mode=None, places=None, fill=None):
-        request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill)
+                 filter=None, mode=None, places=None, fill=None, reducing_gap=None):
+        request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill,
+                                  reducing_gap)
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -557,6 +616,15 @@ class Plan:
         d["signed"] = bool(d["signed"])
         return d
 
+    def reduce_shape(self, image: int = 0) -> dict:
+        """mj_debug_reduce_shape: the first step of a resized plan for one image, in the stored image's axes — the factors, the
+        phases (size mod f along an axis the orientation reverses), the reduced size, and whether the plan reduces at all."""
+        out = (ctypes.c_int32 * 7)()
+        self.ctx.check(self.ctx.lib.mj_debug_reduce_shape(self.handle, int(image), out))
+        d = dict(zip(("fx", "fy", "phase_x", "phase_y", "width", "height", "reduces"), (int(v) for v in out)))
+        d["reduces"] = bool(d["reduces"])
+        return d
+
     def shape(self) -> list:
         """mj_debug_plan_shape: what plan creation decided, in the order include/mijpeg.h documents."""
         out = (ctypes.c_int32 * PLAN_SHAPE_WORDS)()
@@ -568,6 +636,12 @@ class Plan:
         ms, nb = ctypes.c_float(), ctypes.c_int64()
         self.ctx.check(self.ctx.lib.mj_plan_time_resize(self.handle, iters, rgb_device or None, ctypes.byref(ms), ctypes.byref(nb)))
         return ms.value, nb.value
+
+    def time_reduce(self, iters: int = 10) -> float:
+        """ms per reduce launch of a reducing plan that has been executed (mj_plan_time_reduce)."""
+        ms = ctypes.c_float()
+        self.ctx.check(self.ctx.lib.mj_plan_time_reduce(self.handle, iters, ctypes.byref(ms)))
+        return ms.value
 
     def read(self, rgb=True, coef=False, planes=False, idct=False):
         out = {}

@@ -6,6 +6,7 @@ takes (`include/mijpeg.h`); all pixel work happens in libmijpeg.so's HIP kernels
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -370,6 +371,26 @@ def normalize_size(size) -> Optional[Tuple[int, int]]:
     if not ok or int(size[0]) < 1 or int(size[1]) < 1 or int(size[0]) > 65535 or int(size[1]) > 65535:
         raise ValueError(f"size must be (width, height), two positive integers up to 65535, not {size!r}")
     return int(size[0]), int(size[1])
+
+
+def normalize_reducing_gap(reducing_gap, size) -> Optional[float]:
+    """``reducing_gap`` of a decode to a fixed size, checked: None (no first step), or a float >= 1.0 — Pillow's
+    ``Image.resize(..., reducing_gap=)``.  It needs ``size``.  ValueError otherwise (below 1.0: Pillow's message) — also for a gap
+    that a 32-bit float does not hold exactly: the plan request carries a float, and a rounded gap could give other factors than
+    Pillow computes from the double (1.0, 1.5, 2.0, 3.0 and the like are exact)."""
+    if reducing_gap is None:
+        return None
+    if size is None:
+        raise ValueError("reducing_gap needs size=(width, height): without it nothing is resized")
+    if isinstance(reducing_gap, (bool, np.bool_)) or not isinstance(reducing_gap, (int, float, np.integer, np.floating)):
+        raise ValueError(f"reducing_gap must be None or a number 1.0 or greater, not {reducing_gap!r}")
+    gap = float(reducing_gap)
+    if not (gap >= 1.0 and math.isfinite(gap)):
+        raise ValueError("reducing_gap must be 1.0 or greater")
+    if float(np.float32(gap)) != gap:
+        raise ValueError(f"reducing_gap {reducing_gap!r} is not exact as a 32-bit float, which is what the plan request carries; "
+                         f"the nearest values that are: {float(np.float32(gap))!r}")
+    return gap
 
 
 # Pillow's Image.Resampling numbering of the convolution filters (0 is NEAREST)
@@ -755,7 +776,8 @@ class _Request:
     ``resample``: :func:`normalize_resample`'s filter of the resize (None: bilinear, the request of a call without the argument).
     ``mode``: :func:`normalize_mode`'s output colour mode (None: every file's own components).
     ``places``: :func:`normalize_places`' list (None: every image stretched over ``size``, the request of a call without
-    ``resize_to``) and ``fill``: :func:`normalize_fill`'s bytes for the canvas elements no image covers (None: zeros)."""
+    ``resize_to``) and ``fill``: :func:`normalize_fill`'s bytes for the canvas elements no image covers (None: zeros).
+    ``reducing_gap``: :func:`normalize_reducing_gap`'s gap of the two-step resize (None: one step)."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
@@ -768,6 +790,7 @@ class _Request:
     mode: Optional[str] = None
     places: Optional[List[Tuple[int, int, int, int]]] = None
     fill: Optional[Tuple[int, ...]] = None
+    reducing_gap: Optional[float] = None
 
     @property
     def ncomp(self) -> Optional[int]:
@@ -786,7 +809,7 @@ class _Request:
         if orient is not None and all(o == 1 for o in orient):
             orient = None
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill)
+                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap)
 
     def orient_classes(self) -> List[List[int]]:
         """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
@@ -812,6 +835,8 @@ class _Request:
         if self.places is not None:         # (every image over the whole of size: the arguments of a call without resize_to)
             kw["places"], kw["fill"] = self.places, self.fill
             kw.setdefault("mode", self.mode)
+        if self.reducing_gap is not None:   # (one step: the arguments of a call without reducing_gap)
+            kw["reducing_gap"] = self.reducing_gap
         return kw
 
 
@@ -959,7 +984,7 @@ class BatchDecoder:
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
-               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None):
+               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -984,7 +1009,13 @@ class BatchDecoder:
         Pillow's ``ImageOps.pad(img, size, filter, color=fill)``; or a list with one of these per file.  ``place``: None (centred by
         the rule of the file's kind), one (x, y) or one per file — the resized image's top-left on the canvas, negative where it is
         cropped.  ``fill``: the byte (or one per output component) of canvas elements no image covers, 0 by default; it goes
-        through ``dtype`` / ``normalize`` like a pixel, and ``mirror`` flips the finished canvas.  Only the canvas is computed."""
+        through ``dtype`` / ``normalize`` like a pixel, and ``mirror`` flips the finished canvas.  Only the canvas is computed.
+        ``reducing_gap``, with ``size``: None, or a number >= 1.0 — the two-step resize of Pillow's ``Image.resize(size, filter,
+        reducing_gap=g)`` (``Image.thumbnail`` uses 2.0): every image is first shrunk by the integer factors ``int(w / width / g)``
+        and ``int(h / height / g)`` with ``Image.reduce`` (one more launch, a box average) and the small image is then resampled
+        over the fractional box.  Not the single-step bytes — Pillow calls the difference invisible from 3.0 on — but far fewer
+        taps for a strong shrink.  What lands on the canvas is ``exif_transpose(img.convert(mode)).crop(window).resize(target,
+        filter, reducing_gap=g)`` bit for bit, ``target`` being ``size`` or the place's size under ``resize_to``."""
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -997,13 +1028,14 @@ class BatchDecoder:
             raise ValueError("size and return_seams do not go together: the seam outputs are at the files' own sizes")
         normalize_output(dtype, normalize, mirror, size, host=True)       # (what needs no file: before any is parsed)
         resample = normalize_resample(resample, size)
+        reducing_gap = normalize_reducing_gap(reducing_gap, size)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
         gpu_segment = self._gpu_segment_for(files)
         parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
         orient = normalize_orientation(orientation, files)
         odims = _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)
-        req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode)
+        req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode, reducing_gap=reducing_gap)
         req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
         turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
@@ -1063,12 +1095,12 @@ class BatchDecoder:
         return self._staging
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
-                        resize_to=None, place=None, fill=None) -> _Request:
+                        resize_to=None, place=None, fill=None, reducing_gap=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order."""
         req = _Request(files, None, size, orient=normalize_orientation(orientation, files), resample=normalize_resample(resample, size),
-                       mode=normalize_mode(mode))
+                       mode=normalize_mode(mode), reducing_gap=normalize_reducing_gap(reducing_gap, size))
         if size is not None:
             import torch
             info = [_image_info(f) for f in files]
@@ -1095,7 +1127,7 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None):
+                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1125,14 +1157,17 @@ class BatchDecoder:
         one extra launch of an own-size plan — and with ``size`` all of them fill their slots of the one tensor.
         ``resize_to``, ``place`` and ``fill`` as in :meth:`decode`: ``size`` is a canvas, every image is resized to a size of its
         own and placed on it by the one resize launch of its plan; files of several kinds and orientation classes are still one
-        plan per kind, each writing its slots of the one tensor."""
+        plan per kind, each writing its slots of the one tensor.
+        ``reducing_gap`` as in :meth:`decode`: the two-step resize; every plan of the call (second rounds, files of several kinds,
+        parts) carries it."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
+        normalize_reducing_gap(reducing_gap, size)
         normalize_mode(mode)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
@@ -1241,7 +1276,7 @@ class BatchDecoder:
         return results if req.dest is None else req.dest
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
-                           mode=None, resize_to=None, place=None, fill=None):
+                           mode=None, resize_to=None, place=None, fill=None, reducing_gap=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1258,10 +1293,11 @@ class BatchDecoder:
         ``normalize`` as there, for every batch; ``mirror``: None, one bool for all files, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file).  ``orientation``: None, "exif" or
         an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes.
-        ``resample`` and ``mode`` as in :meth:`decode_device`, for every batch; ``resize_to``, ``place`` and ``fill`` too (a list
-        per file then has to fit every batch)."""
+        ``resample``, ``mode`` and ``reducing_gap`` as in :meth:`decode_device`, for every batch; ``resize_to``, ``place`` and
+        ``fill`` too (a list per file then has to fit every batch)."""
         size = normalize_size(size)
         normalize_resample(resample, size)                                            # (what needs no file: before any work)
+        normalize_reducing_gap(reducing_gap, size)
         normalize_mode(mode)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
@@ -1290,7 +1326,7 @@ class BatchDecoder:
                         o = next(turns)
                     except StopIteration:
                         raise ValueError("orientation yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill)
+                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

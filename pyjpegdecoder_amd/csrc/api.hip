@@ -364,7 +364,9 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
     }
     mj::ResizeArgs a = p->rz;
     a.dst = p->last_rgb;
-    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->ncomp, p->out_ncomp, p->rz_placed, p->rz_fill));
+    // a reducing plan: the reduce launch in front, whose packed reduced images the resize reads (colour to L: converted there)
+    if (p->reduces) MJ_HIP(p->ctx, mj::launch_reduce(s, p->rd, p->ncomp, p->rd_luma));
+    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->rd_luma ? 1 : p->ncomp, p->rd_luma ? 0 : p->out_ncomp, p->rz_placed, p->rz_fill));
     return MJ_OK;
 }
 
@@ -597,6 +599,16 @@ int mj_plan_time_resize(mj_plan *p, int iters, uint8_t *rgb_device, float *ms_ou
     if (rgb_device) p->last_rgb = rgb_device;
     const int rc = time_launches(ctx, s, 1, iters, [&] { return resize_launch(p, s); }, ms_out);
     if (source_bytes) *source_bytes = p->src_bytes;
+    return rc != MJ_OK ? rc : mark_done(p, s);
+}
+
+int mj_plan_time_reduce(mj_plan *p, int iters, float *ms_out) {
+    if (!p || iters <= 0 || !ms_out) return MJ_ERR_INVALID;
+    mj_context *ctx = p->ctx;
+    if (!p->reduces) return fail(ctx, MJ_ERR_INVALID, "mj_plan_time_reduce: not a reducing plan");
+    hipStream_t s = ctx->stream;
+    if (int rc = plan_ready(p, s)) return rc;
+    const int rc = time_launches(ctx, s, 1, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_reduce(s, p->rd, p->ncomp, p->rd_luma)); return MJ_OK; }, ms_out);
     return rc != MJ_OK ? rc : mark_done(p, s);
 }
 

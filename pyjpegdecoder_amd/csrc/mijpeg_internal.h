@@ -413,12 +413,46 @@ constexpr int64_t kResizeGridX = 1 << 20;      // workgroups along x of the resi
 // (filter: MJ_FILTER_*, one that resize_filter_known)
 bool resize_filter_known(int filter);
 bool resize_filter_signed(int filter);
-int resize_axis_ksize(int in_size, int out_size, int filter = 0);
-void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0);
+// (box: NULL — the whole axis, [0, in_size) — or the part {in0, in1} of it the table resamples, as 32-bit floats: Pillow's
+// precompute_coeffs(inSize, in0, in1, outSize), the resample behind a reduce, reduce.hip)
+int resize_axis_ksize(int in_size, int out_size, int filter = 0, const float *box = nullptr);
+void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter = 0, const float *box = nullptr);
 // (out_ncomp: 0 or ncomp — the instances there were; else a plan that converts, mj_plan_request.mode with a size)
 // (placed: a plan of mj_plan_request.places — the placed instances, which store `fill`, byte c in bits 8c..8c+7, where
 // the image does not cover the canvas; a.mirror is then set)
 hipError_t launch_resize(hipStream_t stream, const ResizeArgs &a, int ncomp, int out_ncomp = 0, int placed = 0, unsigned fill = 0);
+// ---- reduce.hip: the first step of a two-step resize (mj_plan_request.reducing_gap; tools/reduce_model.py)
+// One image of a reducing plan, as rows x len pixels (len along the contiguous axis) of the plan's intermediate buffer: every
+// cell of f_slow x f_fast pixels becomes one pixel of the reduced image, ((sum + n / 2) * m(n)) >> 24 with n the cell's own
+// pixel count.  Cell k of an axis is [k * f - off, (k + 1) * f - off) clipped to the axis: off 0 puts the partial cell last,
+// off = f - size mod f first (an axis the orientation reverses).  mul / half: m(n) and n / 2 for the four kinds of cell —
+// bit 0: partial along the contiguous axis, bit 1: partial along the rows — evaluated on the host (reduce_multiplier).
+struct DevReduceImage {
+    int64_t src_off, dst_off;     // bytes: into the intermediate buffer, into the buffer of reduced images
+    int32_t rows, len;
+    int32_t f_slow, f_fast, off_slow, off_fast;
+    uint32_t mul[4], half[4];
+};
+struct ReduceArgs {
+    const uint8_t *src;
+    uint8_t *dst;
+    const DevReduceImage *images;
+    int32_t n_images;
+    int32_t tile_slow, tile_fast;       // reduced rows / reduced pixels of a row per workgroup
+    int32_t tiles_slow, tiles_fast;     // tiles per image: those of the largest reduced image (a smaller one's rest idles)
+};
+constexpr int kReduceStage = 4096;       // bytes of a source row a wavefront stages at a time
+constexpr int kReduceMaxCell = 65536;    // pixels per cell: every sum stays below 2^24 and every product inside 32 bits
+// Image.resize's factors for src -> dst with reducing_gap `gap` (doubles, divided in this order)
+void reduce_factors(int src_w, int src_h, int dst_w, int dst_h, double gap, int *fx, int *fy);
+uint32_t reduce_multiplier(uint32_t n);      // (uint32)(float32(2^32) / float32(256 n))
+// the record of one image but for its offsets (phases: size mod f where the axis is reversed, else 0)
+void reduce_record(int rows, int len, int f_slow, int f_fast, int phase_slow, int phase_fast, DevReduceImage *out);
+// the kernel's arithmetic on the host: ncomp interleaved components; luma: three components in, mode_luma of each pixel summed, one out
+void reduce_host(const uint8_t *src, const DevReduceImage &im, int ncomp, bool luma, uint8_t *out);
+// (luma: the instance that converts colour to L where it reads, mj_plan_request.mode with MJ_MODE_L)
+hipError_t launch_reduce(hipStream_t stream, const ReduceArgs &a, int ncomp, bool luma);
+int reduce_tile_fast(int out_ncomp);     // reduced pixels of a row a workgroup takes
 // ---- output colour mode (tools/mode_model.py)
 // Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
 __host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }

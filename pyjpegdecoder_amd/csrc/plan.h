@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <array>
 #include <string>
 #include <vector>
 
@@ -274,6 +275,13 @@ struct mj_plan {
     int rz_placed = 0;                     // mj_plan_request.places: the placed instances, which store rz_fill (byte c in bits
     unsigned rz_fill = 0;                  // 8c..8c+7) where an image does not cover the canvas
     int rz_filter = 0, rz_max_ksize = 0;   // the plan's MJ_FILTER_* and the most taps a pixel of it has per axis (mj_debug_resize_shape)
+    // reducing plans (mj_plan_request.reducing_gap with a factor above 1 somewhere): the reduce launch (reduce.hip) between stage 2
+    // and the resize launch reads d_src and writes the reduced images, packed, into d_red, which is what rz.src then names
+    bool reduces = false, rd_luma = false;     // rd_luma: colour to L is the reduce launch's; the resize runs the one-component instances
+    uint8_t *d_red = nullptr;
+    mj::DevReduceImage *d_rd_images = nullptr;
+    mj::ReduceArgs rd{};
+    std::vector<std::array<int32_t, 6>> h_rd;  // per image, stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)
     // oriented plans at the files' own sizes (mj_plan_request.orientations without a size): `resized` with the orient launch (orient.hip) in the
     // resize launch's place — stage 2 writes stored-order pixels into d_src, the launch writes them oriented into the output
     bool orient_only = false;
@@ -306,6 +314,9 @@ int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, b
 struct PlanRequest { mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; };
 constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the messages)
 int create_resized(const PlanRequest &q);
+// reducing_gap's default rule (normalise_request): whether any image of the request — oriented, its window, to its place's size —
+// gets a factor above 1; images whose sizes the makers will refuse count as none
+bool reduce_applies(const mj_batch *b, const mj_plan_request &r);
 const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std);     // (resize_plan.hip)
 int create_oriented(const PlanRequest &q);
 // q.r.rois (oriented coordinates, not NULL) or the windows `rois` given in their place, as windows of the stored images

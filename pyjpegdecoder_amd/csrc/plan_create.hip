@@ -725,11 +725,12 @@ namespace {
 // What every request goes through before a plan is made of it: each field checked, in this order — where several faults coincide
 // the first is reported —, and each field that names its default turned into its absence, so that "the default is exactly the plan
 // without the field" holds by construction: the makers never see the difference.
-int normalise_request(mj::PlanRequest &q) {
+// (need_ctx false: mj_debug_normalise_request — everything but the context is looked at)
+int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     const char *fn = mj::kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
     const bool sized = r.out_width != 0 || r.out_height != 0;
-    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : nullptr;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : nullptr;
     if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
     if (r.mode != MJ_MODE_NATIVE && r.mode != MJ_MODE_L && r.mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, r.mode);
     if (r.mode == mj::batch_ncomp(b)) r.mode = MJ_MODE_NATIVE;      // (the files' own count)
@@ -748,7 +749,10 @@ int normalise_request(mj::PlanRequest &q) {
     if (r.output)
         if (const char *why = mj::output_fault(r.output->dtype, r.output->normalize != 0, r.mode ? r.mode : mj::batch_ncomp(b), r.output->mean, r.output->std))
             return fail(ctx, MJ_ERR_INVALID, "%s: output: %s", fn, why);
-    if (!ctx) return MJ_ERR_INVALID;
+    // (0: no first step; else Pillow's rule, and its message)
+    if (r.reducing_gap != 0 && !(std::isfinite(r.reducing_gap) && r.reducing_gap >= 1.0))
+        return fail(ctx, MJ_ERR_INVALID, "%s: reducing_gap must be 1.0 or greater (or 0: none)", fn);
+    if (!ctx && need_ctx) return MJ_ERR_INVALID;
     if (!b || !q.out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     *q.out = nullptr;
     if (!sized && unsized) return fail(ctx, MJ_ERR_INVALID, "%s: %s needs a size (out_width, out_height)", fn, unsized);
@@ -762,6 +766,8 @@ int normalise_request(mj::PlanRequest &q) {
     for (int i = 0; r.slots && i < b->n_images; ++i)
         if (r.slots[i] < 0 || r.slots[i] >= r.n_slots)
             return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, r.slots[i], r.n_slots);
+    // (no image with a factor above 1: there is no first step, and the plan is the plan without the field)
+    if (r.reducing_gap != 0 && !mj::reduce_applies(b, r)) r.reducing_gap = 0;
     return MJ_OK;
 }
 
@@ -800,6 +806,15 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
     out[2] = (int32_t)std::min<int64_t>(c.est_chunks, 0x7fffffff);
     out[3] = mj::spread_lengths(seg_len, n_segs) ? 1 : 0;
     return MJ_OK;
+}
+
+int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request, mj_plan_request *normal) {
+    if (!normal) return MJ_ERR_INVALID;
+    mj_plan *none = nullptr;
+    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}};
+    const int rc = normalise_request(q, false);
+    if (rc == MJ_OK) *normal = q.r;
+    return rc;
 }
 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {

@@ -96,21 +96,27 @@ bool resize_filter_known(int filter) { return filter >= 0 && filter < (int)(size
 // taps below zero (side lobes): the kernels' signed instances
 bool resize_filter_signed(int filter) { return filter == MJ_FILTER_BICUBIC || filter == MJ_FILTER_LANCZOS; }
 
-int resize_axis_ksize(int in_size, int out_size, int filter) {
-    const double scale = (double)in_size / (double)out_size;
+// (the scale of an axis: the part of the source the table resamples — box, two 32-bit floats whose difference is a float's —
+// over the entries it makes of it; NULL: the whole axis)
+static double axis_scale(int in_size, int out_size, const float *box) {
+    return box ? (double)(box[1] - box[0]) / out_size : (double)in_size / (double)out_size;
+}
+
+int resize_axis_ksize(int in_size, int out_size, int filter, const float *box) {
+    const double scale = axis_scale(in_size, out_size, box);
     const double support = kFilters[filter].support * (scale < 1.0 ? 1.0 : scale);
     return (int)ceil(support) * 2 + 1;
 }
 
-void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter) {
+void build_resize_axis(int in_size, int out_size, int32_t *xmin, int32_t *count, int32_t *taps, int taps_stride, int filter, const float *box) {
     const FilterDef &F = kFilters[filter];
-    const double scale = (double)in_size / (double)out_size;
+    const double scale = axis_scale(in_size, out_size, box), in0 = box ? (double)box[0] : 0.0;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
     const double support = F.support * filterscale, ss = 1.0 / filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     std::vector<double> w((size_t)ksize + 2);
     for (int xx = 0; xx < out_size; ++xx) {
-        const double center = (xx + 0.5) * scale;
+        const double center = in0 + (xx + 0.5) * scale;      // (in0 0: the product itself)
         int lo = (int)(center - support + 0.5);
         if (lo < 0) lo = 0;
         int hi = (int)(center + support + 0.5);

@@ -2,6 +2,7 @@
 // (build_resize_axis), the kernels, launch_resize and build_normalize_table are resize.hip's; this file decides what they are
 // given.  create_resized takes the normalised request (plan.h: PlanRequest) and goes through it in named steps:
 //   placed_source_ranges   placed plans: what every image's axes need of their source, and the window plan derived from that
+//   reduce_stage           reducing plans: every image's factors, phases, reduced size and float32 box, and the reduce launch's records
 //   TapTables              one table per distinct axis, range-checked, reversed for orientations, serialised for the kernels
 //   choose_tile            the tile a workgroup takes and where its parts lie in LDS — a pure function of the tables and sizes
 //   output_table           the 256 x C elements a 2- or 4-byte output looks its bytes up in
@@ -97,6 +98,9 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
         Need &nd = need[(size_t)i] = Need{0, r.width, 0, r.height, r.width, r.height};
         // (a window the plan will refuse, or a size no table is built for: left as it is, for the code that refuses it)
         if (W < 1 || H < 1 || W > 65535 || H > 65535 || !mj::stored_window(1, W, H, r, &tmp)) { area_all += 1; area_need += 1; continue; }
+        // (a reducing plan decodes whole images and windows as given — a shrunk window would move the cell grid — and its tables
+        // are made for the reduced sizes: reduce_stage sets `need`)
+        if (q.r.reducing_gap != 0) continue;
         span(r.width, pl.width, pl.x, out_width, &nd.x0, &nd.nx);
         span(r.height, pl.height, pl.y, out_height, &nd.y0, &nd.ny);
         area_all += (int64_t)r.width * r.height; area_need += (int64_t)nd.nx * nd.ny;
@@ -108,6 +112,7 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
     // 1 whenever anything is saved (tests, probes, and crops far smaller than the one measured).
     bool derive = rois != nullptr;
     if (const char *e = mj::opt("MJ_PLACE_WINDOW")) derive = atoi(e) != 0;
+    if (q.r.reducing_gap != 0) derive = false;
     if (derive && area_need < area_all) {
         derived.resize((size_t)b->n_images);
         for (int i = 0; i < b->n_images; ++i) {
@@ -118,6 +123,63 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
     } else {
         for (Need &nd : need) nd.x0 = nd.y0 = 0;
     }
+    return MJ_OK;
+}
+
+// ---- reducing plans: the first step's geometry ------------------------------------------------------------------------------
+// One image, in the oriented image's axes (before its flips): the factors, the reduced size, and the part of the reduced image
+// the resample reads — Pillow's box (0, 0, w / fx, h / fy), which it carries as 32-bit floats: {in0, in1} per axis.
+struct Reduced { int fx, fy, w, h; float bx[2], by[2]; int64_t off; };      // (off: bytes, into the buffer of reduced images)
+// In: the plan (its images' or windows' stored sizes), the request, whether the orientations exchange width and height.  Out:
+// `red`, one per image; the plan's reduce launch (p->rd, its records uploaded) and what mj_debug_reduce_shape reports; *bytes,
+// the packed reduced images' size.  ALL images go through the launch: a 1 x 1 cell is the identity.
+int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std::vector<Reduced> &red, int64_t *bytes) {
+    const char *fn = mj::kCreateFn;
+    const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
+    const int n = p->n_images, CO = luma ? 1 : p->ncomp;
+    // (how the source is read, as launch_resize has it: transposing orientations read the other layout's way, so in the oriented
+    // image's axes an image is rows x len = w x h of an x-major reading and h x w of a row-major one)
+    const bool xmajor = ((p->layout & 1) == 0) != swapped;
+    std::vector<mj::DevReduceImage> recs((size_t)n);
+    red.resize((size_t)n); p->h_rd.resize((size_t)n);
+    mj::ReduceArgs &a = p->rd = mj::ReduceArgs{};
+    a.tile_slow = 8;
+    int max_slow = 1, max_fast = 1;      // the largest reduced image's rows and pixels of a row
+    int64_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
+        const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+        if (bits & 4) std::swap(w, h);
+        Reduced &r = red[(size_t)i];
+        mj::reduce_factors(w, h, places ? places[i].width : q.r.out_width, places ? places[i].height : q.r.out_height, q.r.reducing_gap, &r.fx, &r.fy);
+        if ((int64_t)r.fx * r.fy > mj::kReduceMaxCell)
+            return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: reducing %d x %d by %d x %d takes cells of more than %d pixels", fn, i, w, h, r.fx, r.fy,
+                        mj::kReduceMaxCell);
+        r.w = (w + r.fx - 1) / r.fx; r.h = (h + r.fy - 1) / r.fy;
+        r.bx[0] = r.by[0] = 0.0f;
+        r.bx[1] = (float)((double)w / r.fx); r.by[1] = (float)((double)h / r.fy);
+        // (an axis the orientation reverses: the partial cell comes first)
+        const int phx = (bits & 1) ? w % r.fx : 0, phy = (bits & 2) ? h % r.fy : 0;
+        mj::DevReduceImage &d = recs[(size_t)i];
+        if (xmajor) mj::reduce_record(w, h, r.fx, r.fy, phx, phy, &d);
+        else mj::reduce_record(h, w, r.fy, r.fx, phy, phx, &d);
+        d.src_off = p->h_images[i].rgb_off; d.dst_off = r.off = off;
+        off += (int64_t)r.w * r.h * CO;
+        max_slow = std::max(max_slow, xmajor ? r.w : r.h); max_fast = std::max(max_fast, xmajor ? r.h : r.w);
+        // (mj_debug_reduce_shape: in the stored image's axes)
+        if (bits & 4) p->h_rd[(size_t)i] = {r.fy, r.fx, phy, phx, r.h, r.w};
+        else p->h_rd[(size_t)i] = {r.fx, r.fy, phx, phy, r.w, r.h};
+    }
+    // (rows cut into equal tiles, none longer than a wavefront's row of reduced bytes)
+    const int cap = mj::reduce_tile_fast(CO);
+    a.tiles_fast = (max_fast + cap - 1) / cap; a.tile_fast = (max_fast + a.tiles_fast - 1) / a.tiles_fast;
+    a.tiles_slow = (max_slow + a.tile_slow - 1) / a.tile_slow;
+    if ((int64_t)n * a.tiles_slow * a.tiles_fast > mj::kResizeGridX * (int64_t)65535)
+        return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld reduce tiles are more than one launch takes; split the batch", fn, (long long)n * a.tiles_slow * a.tiles_fast);
+    a.n_images = n;
+    if (int rc = upload(p, &p->d_rd_images, recs.data(), recs.size())) return rc;
+    a.images = p->d_rd_images;
+    *bytes = off;
     return MJ_OK;
 }
 
@@ -150,11 +212,15 @@ struct TapTables {
     // inside: the bounds still grow with j, so the kernels' tile spans hold, and a count of 0 on either axis marks a fill element —
     // an entry inside has at least one tap.  The canvas table is built first and reversed after.  Tables are then per (source
     // size, resized size, offset, reversed).
-    const AxisHost &axis(bool is_x, int in_size, int out_size, bool back, const AxisPlace *at) {
+    // box (reducing plans, every axis of them; else NULL): the part of the in_size entries the table resamples, two 32-bit floats
+    // (build_resize_axis) — tables are then per box as well.
+    const AxisHost &axis(bool is_x, int in_size, int out_size, bool back, const AxisPlace *at, const float *box = nullptr) {
         std::map<int, AxisHost> &m = is_x ? xs : ys;
         int key = 2 * in_size + (back ? 1 : 0);
-        if (placed) {
-            const std::vector<int> full{is_x, in_size, at->resized, at->off, back, at->base, at->len};
+        if (placed || box) {
+            std::vector<int> full{is_x, in_size, back};
+            if (placed) full.insert(full.end(), {at->resized, at->off, at->base, at->len});
+            if (box) { int32_t w[2]; memcpy(w, box, 8); full.insert(full.end(), {w[0], w[1]}); }
             auto id = placed_ids.find(full);
             if (id == placed_ids.end()) id = placed_ids.emplace(full, (int)placed_ids.size()).first;
             key = id->second;
@@ -167,9 +233,9 @@ struct TapTables {
         std::vector<int32_t> k;
         if (placed) {
             const int resized = at->resized, off = at->off, base = at->base;
-            A.ks = mj::resize_axis_ksize(in_size, resized, filter);
+            A.ks = mj::resize_axis_ksize(in_size, resized, filter, box);
             std::vector<int32_t> lo((size_t)resized), cnt((size_t)resized), kk((size_t)resized * A.ks);
-            mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), kk.data(), A.ks, filter);
+            mj::build_resize_axis(in_size, resized, lo.data(), cnt.data(), kk.data(), A.ks, filter, box);
             k.assign((size_t)out_size * A.ks, 0);
             const int j0 = std::max(0, off), j1 = std::min(out_size, off + resized);       // the canvas entries inside the image
             for (int j = 0; j < out_size; ++j) {
@@ -182,9 +248,9 @@ struct TapTables {
             }
             in_size = at->len;      // (what the reversal below counts from: the decoded part's other end)
         } else {
-            A.ks = mj::resize_axis_ksize(in_size, out_size, filter);
+            A.ks = mj::resize_axis_ksize(in_size, out_size, filter, box);
             k.resize((size_t)out_size * A.ks);
-            mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks, filter);
+            mj::build_resize_axis(in_size, out_size, A.lo.data(), A.cnt.data(), k.data(), A.ks, filter, box);
         }
         for (int j = 0; j < out_size && !range_in; ++j) {
             int64_t sum = 0, big = 0, least = 0;
@@ -284,11 +350,26 @@ std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize) {
 
 }  // namespace
 
+bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r) {
+    if (!b || !b->images || r.reducing_gap == 0) return false;
+    for (int i = 0; i < b->n_images; ++i) {
+        int w = b->images[i].width, h = b->images[i].height;
+        if (r.orientations && (mj::orient_bits(r.orientations[i]) & 4)) std::swap(w, h);
+        if (r.rois) { w = r.rois[i].width; h = r.rois[i].height; }
+        const int tw = r.places ? r.places[i].width : r.out_width, th = r.places ? r.places[i].height : r.out_height;
+        if (w < 1 || h < 1 || tw < 1 || th < 1) continue;
+        int fx, fy;
+        mj::reduce_factors(w, h, tw, th, r.reducing_gap, &fx, &fy);
+        if (fx > 1 || fy > 1) return true;
+    }
+    return false;
+}
+
 // ---- the plan, from a normalised request with a size ------------------------------------------------------------------------------
 int mj::create_resized(const PlanRequest &q) {
     const char *fn = kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
-    auto [rois, orient, mode, out_width, out_height, slots, n_slots, output, filter, places, fill] = q.r;
+    auto [rois, orient, mode, out_width, out_height, slots, n_slots, output, filter, reducing_gap, places, fill] = q.r;
     const int dtype = output ? output->dtype : MJ_DTYPE_U8, esize = dtype_size(dtype);
     std::vector<Need> need;
     std::vector<mj_roi> derived;
@@ -317,8 +398,18 @@ int mj::create_resized(const PlanRequest &q) {
     PlanGuard guard{p};
     // C: the source's components.  A plan that converts stores CO of them per pixel and runs both passes, and T, on CT = 1:
     // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
-    const int C = p->ncomp, n = p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
+    int C = p->ncomp;
+    const int n = p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
     if (mode) p->out_ncomp = CO;
+    // a reducing plan (normalise_request: some image of it has a factor above 1): the resize reads the reduced images.  Colour to
+    // L is then the reduce launch's — the conversion comes before the reduce — and the resize is the plain one-component one
+    const bool reducing = reducing_gap != 0, luma = reducing && mode == MJ_MODE_L && C == 3;
+    std::vector<Reduced> red;
+    int64_t red_bytes = 0;
+    if (reducing) {
+        if (int rc = reduce_stage(q, p, swapped, luma, red, &red_bytes)) return rc;
+        if (luma) { mode = 0; C = 1; }
+    }
     const int64_t out_image = (int64_t)out_width * out_height * CO * esize;      // bytes
     TapTables tabs(filter, places != nullptr);
     std::vector<mj::DevResizeImage> ri((size_t)n);
@@ -330,7 +421,14 @@ int mj::create_resized(const PlanRequest &q) {
         if (bits & 4) std::swap(w, h);      // (from here on the oriented image's size)
         ri[i].src_off = p->h_images[i].rgb_off;
         ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
-        if (mode) p->h_out_off.push_back(ri[i].dst_off);
+        if (p->out_ncomp) p->h_out_off.push_back(ri[i].dst_off);
+        const float *bx = nullptr, *by = nullptr;
+        if (reducing) {
+            const Reduced &r = red[(size_t)i];
+            w = r.w; h = r.h; bx = r.bx; by = r.by;
+            ri[i].src_off = r.off;
+            if (places) need[(size_t)i] = Need{0, w, 0, h, w, h};
+        }
         ri[i].w = w; ri[i].h = h;
         if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
         if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
@@ -338,11 +436,11 @@ int mj::create_resized(const PlanRequest &q) {
             // (w, h: what was decoded of the oriented image — the whole, the caller's window, or the derived range of either)
             const Need &nd = need[(size_t)i];
             const AxisPlace px{places[i].width, places[i].x, nd.x0, w}, py{places[i].height, places[i].y, nd.y0, h};
-            ri[i].xtab = tabs.axis(true, nd.sw, out_width, bits & 1, &px).word_off;
-            ri[i].ytab = tabs.axis(false, nd.sh, out_height, bits & 2, &py).word_off;
+            ri[i].xtab = tabs.axis(true, nd.sw, out_width, bits & 1, &px, bx).word_off;
+            ri[i].ytab = tabs.axis(false, nd.sh, out_height, bits & 2, &py, by).word_off;
         } else {
-            ri[i].xtab = tabs.axis(true, w, out_width, bits & 1, nullptr).word_off;
-            ri[i].ytab = tabs.axis(false, h, out_height, bits & 2, nullptr).word_off;
+            ri[i].xtab = tabs.axis(true, w, out_width, bits & 1, nullptr, bx).word_off;
+            ri[i].ytab = tabs.axis(false, h, out_height, bits & 2, nullptr, by).word_off;
         }
         if (tabs.range_in)
             return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: resizing %d to %d with filter %d gives taps outside what the kernels' 24-bit products and 32-bit sums hold", fn,
@@ -393,6 +491,13 @@ int mj::create_resized(const PlanRequest &q) {
     p->src_bytes = p->info.rgb_bytes;
     MJ_HIP(ctx, alloc(p, &p->d_src, (size_t)p->src_bytes + 64));
     a.images = p->d_rz_images; a.tabs = p->d_rz_tabs; a.src = p->d_src;
+    if (reducing) {
+        // the reduced images: a second plan-owned buffer with the same slack, which the resize launch reads as it would d_src
+        MJ_HIP(ctx, alloc(p, &p->d_red, (size_t)red_bytes + 64));
+        p->rd.src = p->d_src; p->rd.dst = p->d_red;
+        a.src = p->d_red;
+        p->reduces = true; p->rd_luma = luma;
+    }
     p->info.rgb_bytes = (int64_t)n_slots * out_image;
     p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
     p->resized = true;
@@ -411,6 +516,19 @@ int mj_host_resize_table_filtered(int32_t filter, int32_t in_size, int32_t out_s
     if (!xmin && !count && !taps) return MJ_OK;
     if (!xmin || !count || !taps || taps_stride < ks) return MJ_ERR_INVALID;
     mj::build_resize_axis(in_size, out_size, xmin, count, taps, taps_stride, filter);
+    return MJ_OK;
+}
+
+int mj_host_resize_table_boxed(int32_t filter, int32_t in_size, double in0, double in1, int32_t out_size, int32_t *xmin, int32_t *count, int32_t *taps,
+                               int32_t taps_stride, int32_t *ksize_out) {
+    if (!mj::resize_filter_known(filter) || in_size < 1 || out_size < 1 || in_size > 65535 || out_size > 65535) return MJ_ERR_INVALID;
+    const float box[2] = {(float)in0, (float)in1};
+    if (!(box[0] >= 0.0f) || !(box[1] <= (float)in_size) || !(box[1] > box[0])) return MJ_ERR_INVALID;
+    const int ks = mj::resize_axis_ksize(in_size, out_size, filter, box);
+    if (ksize_out) *ksize_out = ks;
+    if (!xmin && !count && !taps) return MJ_OK;
+    if (!xmin || !count || !taps || taps_stride < ks) return MJ_ERR_INVALID;
+    mj::build_resize_axis(in_size, out_size, xmin, count, taps, taps_stride, filter, box);
     return MJ_OK;
 }
 
@@ -434,6 +552,19 @@ int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
     const mj::ResizeArgs &a = p->rz;
     const int32_t v[8] = {a.tr, a.tc, a.tiles_x, a.tiles_y, a.lds_bytes, p->rz_filter, a.sgn, p->rz_max_ksize};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return MJ_OK;
+}
+
+int mj_debug_reduce_shape(const mj_plan *p, int32_t image, int32_t out[7]) {
+    if (!p || !out || !p->resized || p->orient_only || image < 0 || image >= p->n_images) return MJ_ERR_INVALID;
+    if (p->reduces) {
+        for (int k = 0; k < 6; ++k) out[k] = p->h_rd[(size_t)image][(size_t)k];
+        out[6] = 1;
+        return MJ_OK;
+    }
+    const int32_t w = p->windowed ? p->h_win[image].w : p->h_images[image].width, h = p->windowed ? p->h_win[image].h : p->h_images[image].height;
+    const int32_t v[7] = {1, 1, 0, 0, w, h, 0};
+    for (int k = 0; k < 7; ++k) out[k] = v[k];
     return MJ_OK;
 }
 
