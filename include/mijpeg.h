@@ -190,8 +190,8 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  * field is declared below.  A zeroed request asks for nothing — the plain plan: every image whole, as stored, in the files' own
  * components, at its own size, packed image after image — and every field whose value is its DEFAULT (named with the field)
  * gives exactly the plan of the request without it: the library turns such a field into its absence before anything is made,
- * so the same code makes the plan and the same kernels run it.  All arrays are host memory with batch->n_images entries, read
- * during the call only.
+ * so the same code makes the plan and the same kernels run it.  All arrays are host memory with batch->n_images entries (in a
+ * request with views, the per-output ones — slots, output->mirror, places — with n_views), read during the call only.
  *
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
  * window -> resize with the filter (to the place's size, onto the canvas) -> mirror -> the output's element type.  In Pillow's
@@ -203,8 +203,8 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  * (the seam outputs are whole images in stored order, in the files' components, at the files' sizes; a window plan refuses
  * MJ_FLAG_KEEP_COEF too).  Checked in this order, the first fault reported: filter, mode, orientations, output — these before
  * the context is looked at, so that a bad description is diagnosed without a GPU (the message is then mj_last_error(NULL)'s) —,
- * ctx / batch / out, the size, the KEEP flags, slots, places, windows, then the batch itself.  (reducing_gap's value is checked with
- * the first four.) */
+ * ctx / batch / out, the size, the KEEP flags, views, slots, places, windows, then the batch itself.  (reducing_gap's value is checked
+ * with the first four.) */
 typedef struct {
     int32_t x, y, width, height;
 } mj_roi;
@@ -230,6 +230,10 @@ typedef struct {
     int32_t width, height;
     int32_t x, y;
 } mj_place;
+typedef struct {
+    int32_t image;              /* index into the batch */
+    mj_roi window;              /* of the oriented image, after the mode; all zero: the whole (oriented) image */
+} mj_view;
 typedef struct {
     /* Region of interest.  DEFAULT NULL: whole images.  Else the output for image i is the window rois[i] of the image — x along
      * image_width, y along image_height — and nothing else.  Window i in the plan's layout:
@@ -296,6 +300,28 @@ typedef struct {
      * slots[k] < n_slots — several plans can fill one array this way (files of several kinds are one plan per kind); slots the
      * plan does not name are not touched.  MJ_ERR_INVALID: a slot outside n_slots. */
     const int32_t *slots; int32_t n_slots;
+    /* Views: several sized outputs per image from one decode (tools/views_model.py).  DEFAULT 0 — also n_views == n_images with
+     * views[k] = {k, whole} for every k: one output per image.  Else, with a size, the request is the `request` member of a
+     * mj_plan_views_request — declared below —, whose `views` holds n_views entries: the plan has n_views outputs and output k is the window
+     * views[k].window of image views[k].image — byte for byte output 0 of the plan of that ONE image with rois = {the window}, the
+     * k-th entry of every per-output field and every other field as given: exif_transpose(img.convert(mode)).crop(window)
+     * .resize(target_k, filter[, reducing_gap]) on the canvas, mirrored if mirror[k], through the output table.  Taps stop at the
+     * window's edge (crop().resize(), not resize(box=)); reducing_gap's factors come from the window's size and view k's target,
+     * and its cell grid starts at the window's origin (an axis the orientation reverses: at the oriented window's end, with
+     * mj_debug_reduce_shape's phase convention).  Views come in any order and several may name one image.
+     *   per output (n_views entries, entry k for view k): slots, output->mirror, places; n_slots defaults to n_views
+     *   per image  (n_images entries): orientations, status[]
+     * An image is decoded ONCE however many views name it: the plan is the plain plan of its images — whole images, the fused launch
+     * wherever the plain plan takes it, every image once in the intermediate buffer (mj_plan_time_resize's source_bytes) — and the
+     * resize launch, and the reduce launch of a reducing plan, run one record per view that reads its window of that buffer.  A
+     * placed plan with views never derives windows.  mj_plan_info.rgb_bytes / total_pixels count n_slots outputs;
+     * mj_debug_reduce_shape's index is the view.
+     * MJ_ERR_INVALID: views without a size ("views needs a size"); views together with rois; n_views < 0 or a NULL `views`; an image
+     * outside the batch; an empty window or one not inside its oriented image (naming the view); an image that no view names.
+     * The field is an int in the four bytes between n_slots and output that were padding, as reducing_gap is behind filter: the
+     * request keeps its size and every other field its offset, so callers built against the request without it — who zero it — ask
+     * for what they asked, and the array's pointer lies behind `fill`, in the structure that encloses the request. */
+    int32_t n_views;
     /* Model-ready output.  DEFAULT NULL, or {MJ_DTYPE_U8, 0, .., NULL}: the resized bytes.  Else the dense array holds what a
      * model takes — elements of `dtype`, normalised, some images mirrored:
      *   dtype      MJ_DTYPE_U8: the resized byte itself.  MJ_DTYPE_F32: for a resized byte v of component c, torchvision's
@@ -369,6 +395,12 @@ typedef struct {
     /* With places.  DEFAULT NULL: zeros.  Else one byte per OUTPUT component (fill[0] alone for one component). */
     const uint8_t *fill;
 } mj_plan_request;
+/* A request with views (request.n_views != 0): mj_plan_create_with and mj_debug_normalise_request are given &r.request and read
+ * r.views[0 .. request.n_views).  Zeroed, it is the zeroed request. */
+typedef struct {
+    mj_plan_request request;
+    const mj_view *views;
+} mj_plan_views_request;
 /* request NULL: a zeroed request. */
 int mj_plan_create_with(mj_context *ctx, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
 /* The plain plan: exactly mj_plan_create_with(ctx, batch, NULL, out). */
@@ -476,7 +508,8 @@ int mj_debug_resize_shape(const mj_plan *plan, int32_t out[8]);
 /* Test hook: the first step of a resized plan for one image — out = { fx, fy, phase along the width, phase along the height, reduced
  * width, reduced height, 1 if the plan reduces at all (else 0, factors 1 and the decoded size) }, all in the STORED image's axes: an
  * axis the orientation reverses has its cell boundaries at phase + k * f, phase = size mod f, and orientations 5..8 exchange the
- * factors.  MJ_ERR_INVALID: not a resized plan, no such image. */
+ * factors.  A plan with views: `image` is the view, and the sizes are its window's.  MJ_ERR_INVALID: not a resized plan, no such
+ * image (view). */
 int mj_debug_reduce_shape(const mj_plan *plan, int32_t image, int32_t out[7]);
 
 /* Test hook (host only, no context): *normal = the request as plan creation sees it after its checks — every field that names its

@@ -109,6 +109,11 @@ class OutputDescC(ctypes.Structure):
                 ("mirror", ctypes.c_void_p)]
 
 
+class ViewC(ctypes.Structure):
+    """mj_view: one output of a plan with views — the image it shows and the window of it (all zero: the whole oriented image)."""
+    _fields_ = [("image", ctypes.c_int32), ("window", RoiC)]
+
+
 class PlanRequestC(ctypes.Structure):
     """mj_plan_request: what a plan's output is to be; zeroed, the plain plan."""
     _fields_ = [("rois", ctypes.POINTER(RoiC)), ("orientations", ctypes.c_void_p), ("mode", ctypes.c_int32),
@@ -125,6 +130,21 @@ class PlanRequestC(ctypes.Structure):
     @reducing_gap.setter
     def reducing_gap(self, gap: float):
         ctypes.c_float.from_buffer(self, type(self).filter.offset + 4).value = gap
+
+    # mj_plan_request.n_views: an int in the four bytes between n_slots and output, padding likewise.  Not 0: the request is the
+    # `request` member of a PlanViewsRequestC, whose `views` holds that many entries
+    @property
+    def n_views(self) -> int:
+        return ctypes.c_int32.from_buffer(self, type(self).n_slots.offset + 4).value
+
+    @n_views.setter
+    def n_views(self, n: int):
+        ctypes.c_int32.from_buffer(self, type(self).n_slots.offset + 4).value = n
+
+
+class PlanViewsRequestC(ctypes.Structure):
+    """mj_plan_views_request: a request with views — the request, and behind it the array its n_views counts."""
+    _fields_ = [("request", PlanRequestC), ("views", ctypes.POINTER(ViewC))]
 
 
 class PlanInfoC(ctypes.Structure):
@@ -430,17 +450,25 @@ def output_desc(output):
 
 
 def plan_request(n_images, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None, places=None,
-                 fill=None, reducing_gap=None):
+                 fill=None, reducing_gap=None, views=None):
     """(mj_plan_request, the arrays it points to) for a batch of ``n_images`` from Plan's keywords: every keyword is one field of
     the request (include/mijpeg.h), None its default.  Pure: no library, no context.  ValueError for what only a sized or placed
-    plan has and for a per-image list that has not one entry for each image."""
+    plan has and for a per-image list that has not one entry for each image (with ``views``: places and the mirror flags have one
+    for each view)."""
+    if size is None and views is not None:
+        raise ValueError("views needs size: only a resized plan has several outputs per image")
     if size is None and (places is not None or filter is not None or output is not None):
         raise ValueError("places, filter and output need size: only a resized plan has a canvas, resamples and has a dense output")
     if size is None and reducing_gap is not None:
         raise ValueError("reducing_gap needs size: only a resized plan resamples, in one step or two")
     if fill is not None and places is None:
         raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
-    r, keep = PlanRequestC(), {}
+    keep = {}
+    if views is not None:       # (the request is then the head of the structure that holds the array's pointer)
+        keep["views_request"] = ext = PlanViewsRequestC()
+        r = ext.request
+    else:
+        r = PlanRequestC()
     if rois is not None:
         keep["rois"] = r.rois = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in w)) for w in rois])
     if orientation is not None:
@@ -463,9 +491,14 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
         keep["fill"] = fb = np.zeros(3, dtype=np.uint8)
         fb[:len(fill)] = fill
         r.fill = fb.ctypes.data
+    if views is not None:
+        keep["views"] = ext.views = (ViewC * max(1, len(views)))(*[ViewC(int(i), RoiC(*(int(v) for v in (w if w is not None else (0, 0, 0, 0)))))
+                                                                     for i, w in views])
+        r.n_views = len(views)
     for name, given in (("places", places), ("orientation", orientation), ("mirror", keep.get("mirror"))):
-        if given is not None and len(given) != n_images:
-            raise ValueError(f"{name}: {len(given)} entries, not one for each of the {n_images} images")
+        per_view = views is not None and name != "orientation"
+        if given is not None and len(given) != (len(views) if per_view else n_images):
+            raise ValueError(f"{name}: {len(given)} entries, not one for each of the {len(views) if per_view else n_images} {'views' if per_view else 'images'}")
     return r, keep
 
 
@@ -563,12 +596,14 @@ class Plan:
     name of FILTERS / its MJ_FILTER_*: the resize with that resample filter.  mode: a name of MODES / its MJ_MODE_* — the
     components of the output; info.rgb_bytes, slots and image_offsets then count those.  places: with size — then the canvas —,
     one (width, height, x, y) per image: the size it is resized to and where it lies on the canvas; fill: with places, up to three
-    bytes, one per output component.  reducing_gap: with size, a number >= 1.0 — the two-step resize, Pillow's argument of that name."""
+    bytes, one per output component.  reducing_gap: with size, a number >= 1.0 — the two-step resize, Pillow's argument of that name.
+    views: with size, one (image, (x, y, width, height) or None) per OUTPUT — several windows of one decoded image; slots, the mirror
+    flags and places then have one entry per view."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None, mode=None, places=None, fill=None, reducing_gap=None):
+                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None):
         request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill,
-                                  reducing_gap)
+                                  reducing_gap, views)
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _binding as B
 from ._parse import ParsedJpeg, ScanInfo, exif_orientation, parse_jpeg
-from .errors import CorruptedJpeg, UnsupportedJpeg
+from .errors import CorruptedJpeg, JpegError, UnsupportedJpeg
 
 _STATUS_TEXT = {
     B.MJ_ST_BAD_CODE: "Failed to decode image (no Huffman code within 16 bits).",
@@ -593,6 +593,91 @@ def _is_int(v) -> bool:
     return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
+def normalize_views(views, dims, size, rois=None, return_seams: bool = False, index: Optional[Sequence[int]] = None):
+    """The views of a call, checked: None for a call without them, else one (file, (x, y, width, height)) per OUTPUT — output k is
+    that window of that file's image (as its orientation shows it, after the mode), resized to ``size``; a file is decoded once
+    however many views name it, and a file no view names is not looked at.  ``views``: None, or a list whose entries are
+    ``(file_index, (x, y, width, height))``, ``(file_index, None)`` — the whole image — or a bare ``file_index`` (the same).
+    ``dims``: one (width, height) per file of the call, or None for a file whose header has not been read (its views' windows are
+    then left as given: a first pass, which finds the files to read).  Views need ``size`` and go neither with ``rois`` nor with
+    ``return_seams``.  ValueError naming the view and its file (``index``: the file's position in the caller's list) otherwise."""
+    if views is None:
+        return None
+    if size is None:
+        raise ValueError("views needs size=(width, height): every view is resized to it (crops at their own sizes would be ragged)")
+    if rois is not None:
+        raise ValueError("views and rois do not go together: a view names its own window")
+    if return_seams:
+        raise ValueError("views and return_seams do not go together: the seam outputs are whole images, one per file")
+    if not isinstance(views, (list, tuple)):
+        raise ValueError(f"views must be None or a list with one entry per output — (file_index, (x, y, width, height)), (file_index, None) "
+                         f"or file_index —, not {views!r}")
+    n = len(dims)
+
+    def is_window(r) -> bool:
+        return isinstance(r, (tuple, list, np.ndarray)) and len(r) == 4 and all(_is_int(v) for v in r)
+
+    out = []
+    for k, v in enumerate(views):
+        if _is_int(v):
+            i, r = int(v), None
+        elif isinstance(v, (tuple, list)) and len(v) == 2 and _is_int(v[0]) and (v[1] is None or is_window(v[1])):
+            i, r = int(v[0]), v[1]
+        else:
+            raise ValueError(f"view {k}: {v!r} is none of (file_index, (x, y, width, height)), (file_index, None) and file_index")
+        if i < 0 or i >= n:
+            raise ValueError(f"view {k}: file {i} is not one of the {n} files of the call")
+        name = i if index is None else index[i]
+        if dims[i] is None:
+            out.append((i, tuple(int(t) for t in r) if r is not None else None))
+            continue
+        w, h = (int(t) for t in dims[i])
+        if r is None:
+            out.append((i, (0, 0, w, h)))
+            continue
+        x, y, ww, wh = (int(t) for t in r)
+        if ww <= 0 or wh <= 0 or x < 0 or y < 0 or x + ww > w or y + wh > h:
+            raise ValueError(f"view {k} (file {name}): window (x={x}, y={y}, width={ww}, height={wh}) is empty or not inside the {w}x{h} image")
+        out.append((i, (x, y, ww, wh)))
+    return out
+
+
+def select_view_files(files: Sequence[bytes], views, size, rois=None, return_seams: bool = False):
+    """Which files a call with ``views`` reads at all: None for a call without views, else (kept, views) — the positions, ascending,
+    of the files some view names, and :func:`normalize_views`' first pass with every view's file numbered among THOSE.  The files
+    left out are neither parsed nor decoded."""
+    entries = normalize_views(views, [None] * len(files), size, rois, return_seams)
+    if entries is None:
+        return None
+    kept = sorted({i for i, _ in entries})
+    pos = {i: k for k, i in enumerate(kept)}
+    return kept, [(pos[i], r) for i, r in entries]
+
+
+def _per_file_of(value, n_files: int, kept: Sequence[int], what: str):
+    """a per-file argument of a call with views — one entry per file of the caller's list — for the files that are read; anything
+    that is not such a list (None, one value for all files) as it is"""
+    if value is None or isinstance(value, (str, int, np.integer, bytes)):
+        return value
+    try:
+        entries = value.tolist() if hasattr(value, "tolist") else list(value)
+    except TypeError:
+        return value
+    if len(entries) != n_files:
+        raise ValueError(f"{what} has {len(entries)} entries for {n_files} files")
+    return [entries[i] for i in kept]
+
+
+def _named(index: Optional[Sequence[int]], i: int, fn, *args, **kwargs):
+    """fn(...) for file i of a call with views: what the parser raises about the file names its position in the caller's list"""
+    if index is None:
+        return fn(*args, **kwargs)
+    try:
+        return fn(*args, **kwargs)
+    except JpegError as e:
+        raise type(e)(f"file {index[i]}: {e}") from None
+
+
 def _is_resize_kind(k) -> bool:
     """one file's ``resize_to``: an int (the shorter side), (width, height) or "contain" """
     if isinstance(k, str):
@@ -777,7 +862,10 @@ class _Request:
     ``mode``: :func:`normalize_mode`'s output colour mode (None: every file's own components).
     ``places``: :func:`normalize_places`' list (None: every image stretched over ``size``, the request of a call without
     ``resize_to``) and ``fill``: :func:`normalize_fill`'s bytes for the canvas elements no image covers (None: zeros).
-    ``reducing_gap``: :func:`normalize_reducing_gap`'s gap of the two-step resize (None: one step)."""
+    ``reducing_gap``: :func:`normalize_reducing_gap`'s gap of the two-step resize (None: one step).
+    ``views``: :func:`normalize_views`' list (None: one output per file) — the OUTPUTS of the request, each a window of one of
+    ``files``; ``slots``, the mirror flags and ``places`` then have one entry per view, ``wins`` is None, and every file is named
+    by a view."""
     files: Sequence[bytes]
     wins: Optional[List[Tuple[int, int, int, int]]] = None
     size: Optional[Tuple[int, int]] = None
@@ -791,6 +879,11 @@ class _Request:
     places: Optional[List[Tuple[int, int, int, int]]] = None
     fill: Optional[Tuple[int, ...]] = None
     reducing_gap: Optional[float] = None
+    views: Optional[List[Tuple[int, Tuple[int, int, int, int]]]] = None
+
+    @property
+    def n_outputs(self) -> int:
+        return len(self.views) if self.views is not None else len(self.files)
 
     @property
     def ncomp(self) -> Optional[int]:
@@ -808,6 +901,16 @@ class _Request:
         orient = pick(self.orient)
         if orient is not None and all(o == 1 for o in orient):
             orient = None
+        if self.views is not None:
+            # a file takes its views with it: they keep their order, and what is per view goes with the view
+            pos = {i: k for k, i in enumerate(idxs)}
+            vk = [k for k, (f, _) in enumerate(self.views) if f in pos]
+
+            def pick_view(per_view):
+                return [per_view[k] for k in vk] if per_view is not None else None
+            return _Request(pick(self.files), None, self.size, self.output.for_files(vk) if self.output else None, self.dest, pick_view(self.slots),
+                            pick(index), orient, self.resample, self.mode, pick_view(self.places), self.fill, self.reducing_gap,
+                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk])
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
                         self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap)
 
@@ -824,8 +927,10 @@ class _Request:
         """``rois``, ``size``, ``slots``, ``output``, ``orientation``, ``filter`` and ``mode`` of :class:`_binding.Plan` for one plan of all
         its files, in order (``native``: the component count these files have, which decides whether the plan converts)"""
         kw = {"rois": self.wins, "size": self.size,
-              "slots": (self.slots, self.dest.shape[0]) if self.slots is not None else None,
+              "slots": (self.slots, self.dest.shape[0]) if self.slots is not None and self.dest is not None else None,
               "output": self.output.plan_output() if self.output else None}
+        if self.views is not None:          # (one output per file: the arguments of a call without views)
+            kw["views"] = self.views
         if self.orient is not None:         # (files as stored: the arguments of a call without orientation)
             kw["orientation"] = self.orient
         if self.resample is not None:       # (bilinear: the arguments of a call without resample)
@@ -863,16 +968,17 @@ class _Flight:
     d_blob: object = None
 
 
-def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], headers_only: bool, turn=None) -> List[List[int]]:
+def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], headers_only: bool, turn=None, index=None) -> List[List[int]]:
     """Files ``idxs`` sorted into one index list per kind — what can share a plan (``turn``: index -> :func:`_orient_class`,
     part of the kind; None: no file is turned).  Those that ``parsed`` (index -> ParsedJpeg)
-    does not hold yet are parsed into it (``headers_only`` as asked); every one goes through :func:`check_supported`."""
+    does not hold yet are parsed into it (``headers_only`` as asked); every one goes through :func:`check_supported`.
+    ``index`` (a call with views): every file's position in the caller's list, which an error about the file then names."""
     groups: Dict[tuple, List[int]] = {}
     for i in idxs:
         p = parsed.get(i)
         if p is None:
-            p = parsed[i] = parse_jpeg(files[i], headers_only=headers_only)
-        check_supported(p)
+            p = parsed[i] = _named(index, i, parse_jpeg, files[i], headers_only=headers_only)
+        _named(index, i, check_supported, p)
         comps = list(p.color_components.values())
         key = (p.scan_mode, len(comps), p.headers_only, is_scan_list(p), p.headers_only and p.restart_interval > 0, turn[i] if turn is not None else 0) + (tuple((c.horizontal_sampling, c.vertical_sampling) for c in comps) if len(comps) > 1 else ())
         groups.setdefault(key, []).append(i)
@@ -984,7 +1090,7 @@ class BatchDecoder:
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
-               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None):
+               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1015,7 +1121,14 @@ class BatchDecoder:
         and ``int(h / height / g)`` with ``Image.reduce`` (one more launch, a box average) and the small image is then resampled
         over the fractional box.  Not the single-step bytes — Pillow calls the difference invisible from 3.0 on — but far fewer
         taps for a strong shrink.  What lands on the canvas is ``exif_transpose(img.convert(mode)).crop(window).resize(target,
-        filter, reducing_gap=g)`` bit for bit, ``target`` being ``size`` or the place's size under ``resize_to``."""
+        filter, reducing_gap=g)`` bit for bit, ``target`` being ``size`` or the place's size under ``resize_to``.
+        ``views``, with ``size``: several outputs per file from one decode (:func:`normalize_views`) — a list with one entry per
+        OUTPUT, ``(file_index, (x, y, width, height))``, ``(file_index, None)`` or a bare ``file_index``: output k is that window of
+        that file's image (oriented, after the mode) resized to ``size``, exactly output 0 of the call on that one file with
+        ``rois=[window]`` and the k-th entry of ``mirror`` and of the list forms of ``resize_to`` and ``place``, which then have one
+        entry per view (``orientation`` stays per file).  The result is one array of ``len(views)`` images in the views' order.  A
+        file is uploaded, entropy-decoded and reconstructed once however many views name it; a file no view names is not looked
+        at.  Not with ``rois`` or ``return_seams``."""
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -1031,23 +1144,34 @@ class BatchDecoder:
         reducing_gap = normalize_reducing_gap(reducing_gap, size)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
+        index = None                            # views: where the files that are read sit in the caller's list
+        selected = select_view_files(files, views, size, rois, return_seams)
+        if selected is not None:
+            index, views = selected
+            orientation = _per_file_of(orientation, len(files), index, "orientation")
+            files = [files[i] for i in index]
         gpu_segment = self._gpu_segment_for(files)
-        parsed = {i: parse_jpeg(f, headers_only=gpu_segment) for i, f in enumerate(files)}
+        parsed = {i: _named(index, i, parse_jpeg, f, headers_only=gpu_segment) for i, f in enumerate(files)}
         orient = normalize_orientation(orientation, files)
         odims = _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)
-        req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode, reducing_gap=reducing_gap)
-        req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
+        req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode, reducing_gap=reducing_gap, index=index,
+                       views=normalize_views(views, odims, size, index=index) if selected is not None else None)
+        if req.views is not None:               # (what is per output is per view; an error names the view's file)
+            req.places = normalize_places(resize_to, place, size, [r[2:] for _, r in req.views], [index[f] for f, _ in req.views])
+            req.slots = list(range(len(req.views)))
+        else:
+            req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
         turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
             nc = req.ncomp or one_component_count([len(p.color_components) for p in parsed.values()])
-            req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc, host=True)
+            req.output = normalize_output(dtype, normalize, mirror, size, req.n_outputs, nc, host=True)
             req.fill = normalize_fill(fill, resize_to, nc)
-            dense = np.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
+            dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         results: List[Optional[np.ndarray]] = [None] * len(files)
         seams: List[Optional[dict]] = [None] * len(files)
         flags = ((B.MJ_FLAG_KEEP_PLANES | B.MJ_FLAG_KEEP_IDCT) if return_seams else 0) | self.base_flags
-        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment, turn)]
+        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment, turn, index)]
         while work:
             item = work.pop(0)
             idxs, sub = item.idxs, req.narrow(item.idxs)
@@ -1057,15 +1181,20 @@ class BatchDecoder:
                 plan.execute()
                 plan.sync()
                 out = plan.read(rgb=True, coef=return_seams, planes=return_seams, idct=return_seams)
-                tail, unconverged = _triage(out["status"], idxs, files, parsed)
+                tail, unconverged = _triage(out["status"], idxs, files, parsed, sub.index)
                 if tail:
                     work.append(_Work(tail, flags=item.flags))
                 if unconverged:
                     work.append(_Work(unconverged, flags=item.flags | B.MJ_FLAG_NO_SYNC))
                 if dense is not None:
-                    imgs = out["rgb"].view(dense.dtype).reshape((len(idxs),) + dense.shape[1:])
+                    imgs = out["rgb"].view(dense.dtype).reshape((sub.n_outputs,) + dense.shape[1:])
                 else:
                     imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins, orient=sub.orient, ncomp=sub.ncomp)
+                if sub.views is not None:       # (the plan's outputs are its views, each to its place in the array)
+                    for k, (f, _) in enumerate(sub.views):
+                        if idxs[f] not in tail and idxs[f] not in unconverged:
+                            dense[sub.slots[k]] = imgs[k]
+                    continue
                 for k, i in enumerate(idxs):
                     if i in tail or i in unconverged:
                         continue
@@ -1095,24 +1224,34 @@ class BatchDecoder:
         return self._staging
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
-                        resize_to=None, place=None, fill=None, reducing_gap=None) -> _Request:
+                        resize_to=None, place=None, fill=None, reducing_gap=None, views=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
-        decoder's GPU, one slot per file in order."""
+        decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
+        index = None
+        selected = select_view_files(files, views, size, rois)
+        if selected is not None:
+            index, views = selected
+            orientation = _per_file_of(orientation, len(files), index, "orientation")
+            files = [files[i] for i in index]
         req = _Request(files, None, size, orient=normalize_orientation(orientation, files), resample=normalize_resample(resample, size),
-                       mode=normalize_mode(mode), reducing_gap=normalize_reducing_gap(reducing_gap, size))
+                       mode=normalize_mode(mode), reducing_gap=normalize_reducing_gap(reducing_gap, size), index=index)
         if size is not None:
             import torch
-            info = [_image_info(f) for f in files]
+            info = [_named(index, i, _image_info, f) for i, f in enumerate(files)]
             nc = req.ncomp or one_component_count([t[2] for t in info])
-            req.output = normalize_output(dtype, normalize, mirror, size, len(files), nc)
             odims = _oriented_dims([t[:2] for t in info], req.orient)
-            req.wins = normalize_rois(rois, odims)
-            req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
+            if selected is not None:            # (what is per output is per view; an error names the view's file)
+                req.views = normalize_views(views, odims, size, index=index)
+                req.places = normalize_places(resize_to, place, size, [r[2:] for _, r in req.views], [index[f] for f, _ in req.views])
+            else:
+                req.wins = normalize_rois(rois, odims)
+                req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
+            req.output = normalize_output(dtype, normalize, mirror, size, req.n_outputs, nc)
             req.fill = normalize_fill(fill, resize_to, nc)
-            req.dest = torch.empty((len(files),) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
+            req.dest = torch.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
-            req.slots = list(range(len(files)))
+            req.slots = list(range(req.n_outputs))
         elif rois is not None:
             req.wins = normalize_rois(rois, _oriented_dims([_image_dims(f) for f in files], req.orient))
         return req
@@ -1127,7 +1266,7 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None):
+                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1159,7 +1298,10 @@ class BatchDecoder:
         own and placed on it by the one resize launch of its plan; files of several kinds and orientation classes are still one
         plan per kind, each writing its slots of the one tensor.
         ``reducing_gap`` as in :meth:`decode`: the two-step resize; every plan of the call (second rounds, files of several kinds,
-        parts) carries it."""
+        parts) carries it.
+        ``views`` as in :meth:`decode`: one tensor of ``len(views)`` images in the views' order, every file decoded once.  Files of
+        several kinds are still one plan per kind, each writing its views' slots of the one tensor, and a large call is split into
+        parts by FILE, every file's views in its part."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -1167,7 +1309,8 @@ class BatchDecoder:
         normalize_mode(mode)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap, views)
+        files = req.files                       # (with views: the files some view names)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
@@ -1215,7 +1358,7 @@ class BatchDecoder:
             todo = rest if work else range(len(files))          # everything, unless the front end kept some of it
             # (first in line: what the front end left over is mostly progressive files, whose decode is a long serial chain
             # the other plans can run beside)
-            work = [_Work(idxs) for idxs in _group_by_kind(files, todo, parsed, gpu_segment)] + work
+            work = [_Work(idxs) for idxs in _group_by_kind(files, todo, parsed, gpu_segment, index=req.index if req.views is not None else None)] + work
         # Several plans (a batch of several kinds of files): all are submitted before the first is collected, on a few
         # streams in turn, so that small plans share the GPU instead of queueing behind each other's host round trips
         # (mj_plan_sync waits for a plan's own work only).  Files handed back by the GPU scan go round again.
@@ -1276,7 +1419,7 @@ class BatchDecoder:
         return results if req.dest is None else req.dest
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
-                           mode=None, resize_to=None, place=None, fill=None, reducing_gap=None):
+                           mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1294,8 +1437,13 @@ class BatchDecoder:
         batch, what :meth:`decode_device` takes for that batch (one bool, or one bool per file).  ``orientation``: None, "exif" or
         an int 1..8 for every file of every batch, or an iterable that yields, batch by batch, what :meth:`decode_device` takes.
         ``resample``, ``mode`` and ``reducing_gap`` as in :meth:`decode_device`, for every batch; ``resize_to``, ``place`` and
-        ``fill`` too (a list per file then has to fit every batch)."""
+        ``fill`` too (a list per file then has to fit every batch).  ``views``: None, or an iterable that yields, batch by batch,
+        what :meth:`decode_device` takes for that batch — a list with one entry per output; ``mirror`` and the list forms of
+        ``resize_to`` and ``place`` then go by view."""
         size = normalize_size(size)
+        if views is not None and size is None:
+            raise ValueError("views needs size=(width, height): every view is resized to it (crops at their own sizes would be ragged)")
+        per_batch_views = iter(views) if views is not None else None
         normalize_resample(resample, size)                                            # (what needs no file: before any work)
         normalize_reducing_gap(reducing_gap, size)
         normalize_mode(mode)
@@ -1326,7 +1474,13 @@ class BatchDecoder:
                         o = next(turns)
                     except StopIteration:
                         raise ValueError("orientation yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap)
+                v = None
+                if per_batch_views is not None:
+                    try:
+                        v = next(per_batch_views)
+                    except StopIteration:
+                        raise ValueError("views yields fewer entries than there are batches") from None
+                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -432,6 +432,8 @@ struct DevReduceImage {
     int32_t rows, len;
     int32_t f_slow, f_fast, off_slow, off_fast;
     uint32_t mul[4], half[4];
+    int32_t pitch;                // pixels from one source row to the next: len, but for a view (mj_plan_request.views), whose rows
+                                  // are rows of the decoded image it is a window of
 };
 struct ReduceArgs {
     const uint8_t *src;
@@ -446,7 +448,7 @@ constexpr int kReduceMaxCell = 65536;    // pixels per cell: every sum stays bel
 // Image.resize's factors for src -> dst with reducing_gap `gap` (doubles, divided in this order)
 void reduce_factors(int src_w, int src_h, int dst_w, int dst_h, double gap, int *fx, int *fy);
 uint32_t reduce_multiplier(uint32_t n);      // (uint32)(float32(2^32) / float32(256 n))
-// the record of one image but for its offsets (phases: size mod f where the axis is reversed, else 0)
+// the record of one image but for its offsets (phases: size mod f where the axis is reversed, else 0); pitch = len
 void reduce_record(int rows, int len, int f_slow, int f_fast, int phase_slow, int phase_fast, DevReduceImage *out);
 // the kernel's arithmetic on the host: ncomp interleaved components; luma: three components in, mode_luma of each pixel summed, one out
 void reduce_host(const uint8_t *src, const DevReduceImage &im, int ncomp, bool luma, uint8_t *out);

@@ -281,7 +281,9 @@ struct mj_plan {
     uint8_t *d_red = nullptr;
     mj::DevReduceImage *d_rd_images = nullptr;
     mj::ReduceArgs rd{};
-    std::vector<std::array<int32_t, 6>> h_rd;  // per image, stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)
+    int32_t n_views = 0;                       // a plan with views (mj_plan_request.views): its resize and reduce records are per view (0: per image)
+    std::vector<std::array<int32_t, 2>> h_view_size;   // ... every view's window, stored axes: width, height (mj_debug_reduce_shape)
+    std::vector<std::array<int32_t, 6>> h_rd;  // per image (view), stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)
     // oriented plans at the files' own sizes (mj_plan_request.orientations without a size): `resized` with the orient launch (orient.hip) in the
     // resize launch's place — stage 2 writes stored-order pixels into d_src, the launch writes them oriented into the output
     bool orient_only = false;
@@ -311,12 +313,13 @@ int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, b
 // named its default names nothing (orientations all 1, the batch's own mode, every place the whole canvas: NULL / 0); n_slots
 // is the output's.  The two makers take it: create_resized (resize_plan.hip) with a size, create_oriented (orient.hip) without
 // one and with orientations or a mode; a request with neither is plan_create_common's.
-struct PlanRequest { mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; };
+// views: r.n_views entries where r.n_views != 0 (the caller's mj_plan_views_request), else NULL
+struct PlanRequest { mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; const mj_view *views = nullptr; };
 constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the messages)
 int create_resized(const PlanRequest &q);
 // reducing_gap's default rule (normalise_request): whether any image of the request — oriented, its window, to its place's size —
 // gets a factor above 1; images whose sizes the makers will refuse count as none
-bool reduce_applies(const mj_batch *b, const mj_plan_request &r);
+bool reduce_applies(const mj_batch *b, const mj_plan_request &r, const mj_view *views);
 const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std);     // (resize_plan.hip)
 int create_oriented(const PlanRequest &q);
 // q.r.rois (oriented coordinates, not NULL) or the windows `rois` given in their place, as windows of the stored images
@@ -338,6 +341,18 @@ inline bool stored_window(int o, int width, int height, const mj_roi &r, mj_roi 
     const int x = (bits & 1) ? (int)(wo - r.x - r.width) : r.x, y = (bits & 2) ? (int)(ho - r.y - r.height) : r.y;
     *out = (bits & 4) ? mj_roi{y, x, r.height, r.width} : mj_roi{x, y, r.width, r.height};
     return true;
+}
+// view v of a request with views: its window of the oriented image (`shown`; a window that is all zero: the whole of it) and
+// the window of the stored image that shows (`stored`); false: the window is empty or not inside the oriented image
+inline bool view_window(const mj_batch *b, const uint8_t *orient, const mj_view &v, mj_roi *shown, mj_roi *stored) {
+    const mj_image_desc &im = b->images[v.image];
+    const int o = orient ? orient[v.image] : 1;
+    *shown = v.window;
+    if (!v.window.x && !v.window.y && !v.window.width && !v.window.height) {
+        const bool t = (orient_bits(o) & 4) != 0;
+        *shown = mj_roi{0, 0, t ? im.height : im.width, t ? im.width : im.height};
+    }
+    return stored_window(o, im.width, im.height, *shown, stored);
 }
 }  // namespace mj
 

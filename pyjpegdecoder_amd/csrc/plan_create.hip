@@ -722,6 +722,38 @@ int mj::stored_windows(const PlanRequest &q, const mj_roi *rois, std::vector<mj_
 
 namespace {
 
+// the array of a request with views: the request is then the head of the caller's mj_plan_views_request (include/mijpeg.h)
+const mj_view *request_views(const mj_plan_request *request) {
+    return request && request->n_views ? reinterpret_cast<const mj_plan_views_request *>(request)->views : nullptr;
+}
+
+// The views of a sized request, checked; views that are one whole image each, in order, become their absence.
+// (orientations have been checked and, where all upright, dropped)
+int normalise_views(mj::PlanRequest &q) {
+    const char *fn = mj::kCreateFn;
+    mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
+    if (r.rois) return fail(ctx, MJ_ERR_INVALID, "%s: views and rois do not go together: a view names its own window", fn);
+    if (r.n_views < 1 || !q.views) return fail(ctx, MJ_ERR_INVALID, "%s: views with n_views = %d (must be at least 1, with the array)", fn, r.n_views);
+    if (!b->images && b->n_images > 0) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+    std::vector<char> named((size_t)std::max(b->n_images, 0), 0);
+    bool identity = r.n_views == b->n_images;
+    for (int k = 0; k < r.n_views; ++k) {
+        const mj_view &v = q.views[k];
+        if (v.image < 0 || v.image >= b->n_images)
+            return fail(ctx, MJ_ERR_INVALID, "%s: view %d: image %d outside the %d images of the batch", fn, k, v.image, b->n_images);
+        mj_roi shown, stored;
+        if (!mj::view_window(b, r.orientations, v, &shown, &stored))
+            return fail(ctx, MJ_ERR_INVALID, "%s: view %d: window (x=%d, y=%d, width=%d, height=%d) is empty or not inside the oriented image", fn, k,
+                        v.window.x, v.window.y, v.window.width, v.window.height);
+        named[(size_t)v.image] = 1;
+        identity = identity && v.image == k && stored.width == b->images[k].width && stored.height == b->images[k].height;
+    }
+    for (int i = 0; i < b->n_images; ++i)
+        if (!named[(size_t)i]) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: no view names it (leave it out of the batch)", fn, i);
+    if (identity) { q.views = nullptr; r.n_views = 0; }
+    return MJ_OK;
+}
+
 // What every request goes through before a plan is made of it: each field checked, in this order — where several faults coincide
 // the first is reported —, and each field that names its default turned into its absence, so that "the default is exactly the plan
 // without the field" holds by construction: the makers never see the difference.
@@ -730,12 +762,14 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     const char *fn = mj::kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
     const bool sized = r.out_width != 0 || r.out_height != 0;
-    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : nullptr;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : nullptr;
+    // (what slots, the mirror flags and places have one entry for: the views of a request with views, else the images)
+    const int n_out = r.n_views > 0 ? r.n_views : (b ? b->n_images : 0);
     if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
     if (r.mode != MJ_MODE_NATIVE && r.mode != MJ_MODE_L && r.mode != MJ_MODE_RGB) return fail(ctx, MJ_ERR_INVALID, "%s: mode %d is none of MJ_MODE_*", fn, r.mode);
     if (r.mode == mj::batch_ncomp(b)) r.mode = MJ_MODE_NATIVE;      // (the files' own count)
     bool stretched = true;                                          // (every image over the whole canvas)
-    for (int i = 0; r.places && b && i < b->n_images && stretched; ++i)
+    for (int i = 0; r.places && b && i < n_out && stretched; ++i)
         stretched = r.places[i].width == r.out_width && r.places[i].height == r.out_height && r.places[i].x == 0 && r.places[i].y == 0;
     if (stretched) r.places = nullptr;
     bool upright = true;
@@ -762,12 +796,15 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     if ((sized || r.orientations || r.mode) && (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
         return fail(ctx, MJ_ERR_INVALID, sized ? "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none"
                                                : "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
-    if (!r.slots) r.n_slots = b->n_images;
-    for (int i = 0; r.slots && i < b->n_images; ++i)
+    if (r.n_views)
+        if (int rc = normalise_views(q)) return rc;
+    const int n_outputs = r.n_views ? r.n_views : b->n_images;
+    if (!r.slots) r.n_slots = n_outputs;
+    for (int i = 0; r.slots && i < n_outputs; ++i)
         if (r.slots[i] < 0 || r.slots[i] >= r.n_slots)
-            return fail(ctx, MJ_ERR_INVALID, "%s: image %d: slot %d outside the %d slots of the output", fn, i, r.slots[i], r.n_slots);
+            return fail(ctx, MJ_ERR_INVALID, "%s: %s %d: slot %d outside the %d slots of the output", fn, r.n_views ? "view" : "image", i, r.slots[i], r.n_slots);
     // (no image with a factor above 1: there is no first step, and the plan is the plan without the field)
-    if (r.reducing_gap != 0 && !mj::reduce_applies(b, r)) r.reducing_gap = 0;
+    if (r.reducing_gap != 0 && !mj::reduce_applies(b, r, q.views)) r.reducing_gap = 0;
     return MJ_OK;
 }
 
@@ -811,14 +848,14 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
 int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request, mj_plan_request *normal) {
     if (!normal) return MJ_ERR_INVALID;
     mj_plan *none = nullptr;
-    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}};
+    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request)};
     const int rc = normalise_request(q, false);
     if (rc == MJ_OK) *normal = q.r;
     return rc;
 }
 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
-    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}};
+    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request)};
     if (int rc = normalise_request(q)) return rc;
     if (q.r.out_width) return mj::create_resized(q);
     if (q.r.orientations || q.r.mode) return mj::create_oriented(q);

@@ -14,7 +14,8 @@
 // image is the stored-order counterpart of Pillow's reduced oriented image and the resize's oriented instances run on it unchanged.
 //
 // A workgroup takes tile_slow reduced rows x tile_fast reduced pixels of one image; each wavefront every fourth reduced row.  Rows
-// start at any byte alignment (the pitch is len * C), so — as the resize's row-major width pass — a wavefront stages a source row
+// start at any byte alignment (the pitch is len * C — for a view of a decoded image, mj_plan_request.views, that image's row:
+// DevReduceImage::pitch), so — as the resize's row-major width pass — a wavefront stages a source row
 // segment in LDS with aligned 16-byte loads (they may begin up to 15 bytes before and end up to 15 behind the bytes used: inside
 // the buffer's slack) and its lanes gather their cells from there, f_slow rows one after the other into 32-bit registers.  A
 // segment longer than the staging row goes in pieces.  The finished bytes of a reduced row go through LDS once more, so that
@@ -38,7 +39,7 @@ uint32_t reduce_multiplier(uint32_t n) {
 }
 
 void reduce_record(int rows, int len, int f_slow, int f_fast, int phase_slow, int phase_fast, DevReduceImage *out) {
-    out->rows = rows; out->len = len;
+    out->rows = rows; out->len = out->pitch = len;
     out->f_slow = f_slow; out->f_fast = f_fast;
     out->off_slow = phase_slow ? f_slow - phase_slow : 0;
     out->off_fast = phase_fast ? f_fast - phase_fast : 0;
@@ -63,7 +64,7 @@ void reduce_host(const uint8_t *src, const DevReduceImage &im, int ncomp, bool l
                 uint32_t acc = 0;
                 for (int y = ys; y < ye; ++y)
                     for (int x = c0; x < c1; ++x) {
-                        const uint8_t *s = src + ((int64_t)y * im.len + x) * ncomp;
+                        const uint8_t *s = src + ((int64_t)y * im.pitch + x) * ncomp;
                         acc += luma ? mode_luma(s[0], s[1], s[2]) : s[c];
                     }
                 out[((int64_t)r * olen + p) * CO + c] = (uint8_t)(((acc + im.half[kind]) * im.mul[kind]) >> 24);
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void k_reduce(const ReduceArgs a) {
         for (int y = ys; y < ye; ++y) {
             for (int px = xs; px < xe; px += kPiece) {
                 const int pe = min(px + kPiece, xe);
-                const unsigned char *row = src + ((int64_t)y * im.len + px) * CS;
+                const unsigned char *row = src + ((int64_t)y * im.pitch + px) * CS;
                 const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15);
                 const u32x4 *p = reinterpret_cast<const u32x4 *>(row - mis);
                 const int n16 = (mis + (pe - px) * CS + 15) >> 4;          // <= kReduceStage / 16

@@ -6,6 +6,9 @@
 //   TapTables              one table per distinct axis, range-checked, reversed for orientations, serialised for the kernels
 //   choose_tile            the tile a workgroup takes and where its parts lie in LDS — a pure function of the tables and sizes
 //   output_table           the 256 x C elements a 2- or 4-byte output looks its bytes up in
+// A request with views (mj_plan_request.views) goes the same way with one record per VIEW in the resize and reduce launches: the
+// plan is the plain plan of the images, a view's record starts at its window's origin inside its decoded image (pixel_offset), keeps
+// that image's row as its pitch, and its tables — and factors — are its window's.
 #include <math.h>
 #include <map>
 
@@ -29,6 +32,10 @@ struct AxisHost {
 };
 
 int round16(int64_t v) { return (int)((v + 15) & ~(int64_t)15); }
+// bytes from the start of a decoded image — stored width x height, C interleaved components, in the plan's layout — to its pixel (x, y)
+int64_t pixel_offset(int layout, int width, int height, int C, int x, int y) {
+    return ((layout & 1) ? (int64_t)y * width + x : (int64_t)x * height + y) * C;
+}
 int dtype_size(int dtype) { return dtype == MJ_DTYPE_U8 ? 1 : dtype == MJ_DTYPE_F32 ? 4 : 2; }
 
 }  // namespace
@@ -52,7 +59,8 @@ using mj::PlanRequest;
 // What every axis of every image needs of its source — the taps of the canvas entries the image covers reach source entries
 // [x0, x0 + nx) x [y0, y0 + ny) of the oriented image or window, whose size is sw x sh (what the tables are made for).
 struct Need { int x0, nx, y0, ny, sw, sh; };
-// In: the request, with its orientations (NULL: none) and windows (NULL: whole images).  Out: `need`, one per image, and `derived` —
+// In: the request, with its orientations (NULL: none) and windows (NULL: whole images) or views.  Out: `need`, one per output (image,
+// or view — whose windows are never derived: its image is decoded whole, once, for all its views), and `derived` —
 // where the ranges are less than the whole and the rule below says so, the windows of those ranges, as if the caller had asked
 // for them (the plan becomes a window plan: restart segments and MCUs outside are skipped as for a caller's windows, and
 // the tables are rebased to the range); else empty, and every range starts at 0 (tables over the whole image or window).
@@ -61,8 +69,11 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
     const char *fn = mj::kCreateFn;
     const mj_roi *rois = q.r.rois; const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
     const int filter = q.r.filter, out_width = q.r.out_width, out_height = q.r.out_height;
+    const mj_view *views = q.views;
+    const int n_out = views ? q.r.n_views : b->n_images;
+    const char *what = views ? "view" : "image";
     if (!b->images && b->n_images > 0) return fail(q.ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
-    need.resize((size_t)b->n_images);
+    need.resize((size_t)n_out);
     int64_t area_need = 0, area_all = 0;
     std::map<std::vector<int>, std::pair<int, int>> spans;      // (a batch of one size and one placement: one table per axis)
     // the source entries [*first, *first + *len) the canvas takes of an axis in_size -> resized at offset off
@@ -85,17 +96,19 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
         if (bits & 4) std::swap(W, H);
         return mj_roi{0, 0, W, H};
     };
-    for (int i = 0; i < b->n_images; ++i) {
-        const mj_place &pl = places[i];
+    for (int k = 0; k < n_out; ++k) {
+        const int i = views ? views[k].image : k;
+        const mj_place &pl = places[k];
         if (pl.width < 1 || pl.height < 1 || pl.width > 65535 || pl.height > 65535 || pl.x < -65535 || pl.x > 65535 || pl.y < -65535 || pl.y > 65535)
-            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: place (width=%d, height=%d, x=%d, y=%d): the size must be 1..65535, the offsets within +-65535",
-                        fn, i, pl.width, pl.height, pl.x, pl.y);
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: %s %d: place (width=%d, height=%d, x=%d, y=%d): the size must be 1..65535, the offsets within +-65535",
+                        fn, what, k, pl.width, pl.height, pl.x, pl.y);
         if (pl.x >= out_width || pl.y >= out_height || (int64_t)pl.x + pl.width <= 0 || (int64_t)pl.y + pl.height <= 0)
-            return fail(q.ctx, MJ_ERR_INVALID, "%s: image %d: a %d x %d image at (%d, %d) does not meet the %d x %d canvas", fn, i, pl.width, pl.height,
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: %s %d: a %d x %d image at (%d, %d) does not meet the %d x %d canvas", fn, what, k, pl.width, pl.height,
                         pl.x, pl.y, out_width, out_height);
         const int W = whole(i).width, H = whole(i).height;
-        mj_roi r = rois ? rois[i] : whole(i), tmp;
-        Need &nd = need[(size_t)i] = Need{0, r.width, 0, r.height, r.width, r.height};
+        mj_roi r = rois ? rois[k] : whole(i), tmp;
+        if (views) mj::view_window(b, orient, views[k], &r, &tmp);      // (checked by the request's normalisation)
+        Need &nd = need[(size_t)k] = Need{0, r.width, 0, r.height, r.width, r.height};
         // (a window the plan will refuse, or a size no table is built for: left as it is, for the code that refuses it)
         if (W < 1 || H < 1 || W > 65535 || H > 65535 || !mj::stored_window(1, W, H, r, &tmp)) { area_all += 1; area_need += 1; continue; }
         // (a reducing plan decodes whole images and windows as given — a shrunk window would move the cell grid — and its tables
@@ -112,7 +125,7 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
     // 1 whenever anything is saved (tests, probes, and crops far smaller than the one measured).
     bool derive = rois != nullptr;
     if (const char *e = mj::opt("MJ_PLACE_WINDOW")) derive = atoi(e) != 0;
-    if (q.r.reducing_gap != 0) derive = false;
+    if (q.r.reducing_gap != 0 || views) derive = false;
     if (derive && area_need < area_all) {
         derived.resize((size_t)b->n_images);
         for (int i = 0; i < b->n_images; ++i) {
@@ -131,12 +144,15 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
 // the resample reads — Pillow's box (0, 0, w / fx, h / fy), which it carries as 32-bit floats: {in0, in1} per axis.
 struct Reduced { int fx, fy, w, h; float bx[2], by[2]; int64_t off; };      // (off: bytes, into the buffer of reduced images)
 // In: the plan (its images' or windows' stored sizes), the request, whether the orientations exchange width and height.  Out:
-// `red`, one per image; the plan's reduce launch (p->rd, its records uploaded) and what mj_debug_reduce_shape reports; *bytes,
+// `red`, one per image — per view, in a request with views: a view has its own factors and phases, from ITS window's size and
+// target, its cell grid starts at its window's origin, and its record reads its window of the decoded image (pitch: that image's
+// row) —; the plan's reduce launch (p->rd, its records uploaded) and what mj_debug_reduce_shape reports; *bytes,
 // the packed reduced images' size.  ALL images go through the launch: a 1 x 1 cell is the identity.
 int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std::vector<Reduced> &red, int64_t *bytes) {
     const char *fn = mj::kCreateFn;
     const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
-    const int n = p->n_images, CO = luma ? 1 : p->ncomp;
+    const mj_view *views = q.views;
+    const int n = views ? q.r.n_views : p->n_images, CO = luma ? 1 : p->ncomp;
     // (how the source is read, as launch_resize has it: transposing orientations read the other layout's way, so in the oriented
     // image's axes an image is rows x len = w x h of an x-major reading and h x w of a row-major one)
     const bool xmajor = ((p->layout & 1) == 0) != swapped;
@@ -146,29 +162,38 @@ int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std:
     a.tile_slow = 8;
     int max_slow = 1, max_fast = 1;      // the largest reduced image's rows and pixels of a row
     int64_t off = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < n; ++k) {
+        const int i = views ? views[k].image : k;
         int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
         const int bits = orient ? mj::orient_bits(orient[i]) : 0;
         if (bits & 4) std::swap(w, h);
-        Reduced &r = red[(size_t)i];
-        mj::reduce_factors(w, h, places ? places[i].width : q.r.out_width, places ? places[i].height : q.r.out_height, q.r.reducing_gap, &r.fx, &r.fy);
+        // (a view: the oriented window is what is reduced; the whole oriented image gives the pitch)
+        const int whole_w = w, whole_h = h;
+        mj_roi shown{}, stored{};
+        if (views) { mj::view_window(q.b, orient, views[k], &shown, &stored); w = shown.width; h = shown.height; }
+        Reduced &r = red[(size_t)k];
+        mj::reduce_factors(w, h, places ? places[k].width : q.r.out_width, places ? places[k].height : q.r.out_height, q.r.reducing_gap, &r.fx, &r.fy);
         if ((int64_t)r.fx * r.fy > mj::kReduceMaxCell)
-            return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: reducing %d x %d by %d x %d takes cells of more than %d pixels", fn, i, w, h, r.fx, r.fy,
-                        mj::kReduceMaxCell);
+            return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %s %d: reducing %d x %d by %d x %d takes cells of more than %d pixels", fn, views ? "view" : "image", k, w, h,
+                        r.fx, r.fy, mj::kReduceMaxCell);
         r.w = (w + r.fx - 1) / r.fx; r.h = (h + r.fy - 1) / r.fy;
         r.bx[0] = r.by[0] = 0.0f;
         r.bx[1] = (float)((double)w / r.fx); r.by[1] = (float)((double)h / r.fy);
         // (an axis the orientation reverses: the partial cell comes first)
         const int phx = (bits & 1) ? w % r.fx : 0, phy = (bits & 2) ? h % r.fy : 0;
-        mj::DevReduceImage &d = recs[(size_t)i];
+        mj::DevReduceImage &d = recs[(size_t)k];
         if (xmajor) mj::reduce_record(w, h, r.fx, r.fy, phx, phy, &d);
         else mj::reduce_record(h, w, r.fy, r.fx, phy, phx, &d);
         d.src_off = p->h_images[i].rgb_off; d.dst_off = r.off = off;
+        if (views) {
+            d.pitch = xmajor ? whole_h : whole_w;
+            d.src_off += pixel_offset(p->layout, p->h_images[i].width, p->h_images[i].height, p->ncomp, stored.x, stored.y);
+        }
         off += (int64_t)r.w * r.h * CO;
         max_slow = std::max(max_slow, xmajor ? r.w : r.h); max_fast = std::max(max_fast, xmajor ? r.h : r.w);
         // (mj_debug_reduce_shape: in the stored image's axes)
-        if (bits & 4) p->h_rd[(size_t)i] = {r.fy, r.fx, phy, phx, r.h, r.w};
-        else p->h_rd[(size_t)i] = {r.fx, r.fy, phx, phy, r.w, r.h};
+        if (bits & 4) p->h_rd[(size_t)k] = {r.fy, r.fx, phy, phx, r.h, r.w};
+        else p->h_rd[(size_t)k] = {r.fx, r.fy, phx, phy, r.w, r.h};
     }
     // (rows cut into equal tiles, none longer than a wavefront's row of reduced bytes)
     const int cap = mj::reduce_tile_fast(CO);
@@ -350,13 +375,17 @@ std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize) {
 
 }  // namespace
 
-bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r) {
+bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r, const mj_view *views) {
     if (!b || !b->images || r.reducing_gap == 0) return false;
-    for (int i = 0; i < b->n_images; ++i) {
+    const int n_out = views ? r.n_views : b->n_images;
+    for (int k = 0; k < n_out; ++k) {
+        const int i = views ? views[k].image : k;
         int w = b->images[i].width, h = b->images[i].height;
         if (r.orientations && (mj::orient_bits(r.orientations[i]) & 4)) std::swap(w, h);
         if (r.rois) { w = r.rois[i].width; h = r.rois[i].height; }
-        const int tw = r.places ? r.places[i].width : r.out_width, th = r.places ? r.places[i].height : r.out_height;
+        mj_roi shown, stored;
+        if (views && mj::view_window(b, r.orientations, views[k], &shown, &stored)) { w = shown.width; h = shown.height; }
+        const int tw = r.places ? r.places[k].width : r.out_width, th = r.places ? r.places[k].height : r.out_height;
         if (w < 1 || h < 1 || tw < 1 || th < 1) continue;
         int fx, fy;
         mj::reduce_factors(w, h, tw, th, r.reducing_gap, &fx, &fy);
@@ -369,7 +398,8 @@ bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r) {
 int mj::create_resized(const PlanRequest &q) {
     const char *fn = kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
-    auto [rois, orient, mode, out_width, out_height, slots, n_slots, output, filter, reducing_gap, places, fill] = q.r;
+    auto [rois, orient, mode, out_width, out_height, slots, n_slots, n_views, output, filter, reducing_gap, places, fill] = q.r;
+    const mj_view *views = q.views;
     const int dtype = output ? output->dtype : MJ_DTYPE_U8, esize = dtype_size(dtype);
     std::vector<Need> need;
     std::vector<mj_roi> derived;
@@ -393,13 +423,16 @@ int mj::create_resized(const PlanRequest &q) {
         }
     }
     mj_plan *p = nullptr;
-    // (whole images: a plain plan, which may take the fused launch; windows: a window plan)
+    // (whole images — also under views, which are windows of the DECODED images —: a plain plan, which may take the fused launch;
+    // windows: a window plan)
     if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
     PlanGuard guard{p};
     // C: the source's components.  A plan that converts stores CO of them per pixel and runs both passes, and T, on CT = 1:
     // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
     int C = p->ncomp;
-    const int n = p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
+    // n: the launches' records — one per image, or one per view
+    const int n = views ? n_views : p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
+    p->n_views = views ? n_views : 0;
     if (mode) p->out_ncomp = CO;
     // a reducing plan (normalise_request: some image of it has a factor above 1): the resize reads the reduced images.  Colour to
     // L is then the reduce launch's — the conversion comes before the reduce — and the resize is the plain one-component one
@@ -416,24 +449,35 @@ int mj::create_resized(const PlanRequest &q) {
     std::vector<uint8_t> flags((size_t)n, 0);      // mirror, per image
     int any_mirror = 0;
     for (int i = 0; i < n; ++i) {
-        int w = p->windowed ? p->h_win[i].w : p->h_images[i].width, h = p->windowed ? p->h_win[i].h : p->h_images[i].height;
-        const int bits = orient ? mj::orient_bits(orient[i]) : 0;
+        const int img = views ? views[i].image : i;
+        int w = p->windowed ? p->h_win[img].w : p->h_images[img].width, h = p->windowed ? p->h_win[img].h : p->h_images[img].height;
+        const int bits = orient ? mj::orient_bits(orient[img]) : 0;
         if (bits & 4) std::swap(w, h);      // (from here on the oriented image's size)
-        ri[i].src_off = p->h_images[i].rgb_off;
+        ri[i].src_off = p->h_images[img].rgb_off;
         ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
-        if (p->out_ncomp) p->h_out_off.push_back(ri[i].dst_off);
+        if (p->out_ncomp && !views) p->h_out_off.push_back(ri[i].dst_off);
+        // the record's size is what the kernels step from row to row by (resize.hip): the decoded image's.  w, h from here on: what
+        // the tables are made for — the same, but for a view, whose record starts at its window's origin and whose tables are its window's
+        ri[i].w = w; ri[i].h = h;
+        if (views) {
+            mj_roi shown, stored;
+            mj::view_window(b, orient, views[i], &shown, &stored);      // (checked by the request's normalisation)
+            ri[i].src_off += pixel_offset(p->layout, p->h_images[img].width, p->h_images[img].height, p->ncomp, stored.x, stored.y);
+            w = shown.width; h = shown.height;
+            p->h_view_size.push_back({stored.width, stored.height});
+        }
         const float *bx = nullptr, *by = nullptr;
         if (reducing) {
             const Reduced &r = red[(size_t)i];
             w = r.w; h = r.h; bx = r.bx; by = r.by;
             ri[i].src_off = r.off;
+            ri[i].w = w; ri[i].h = h;
             if (places) need[(size_t)i] = Need{0, w, 0, h, w, h};
         }
-        ri[i].w = w; ri[i].h = h;
         if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
         if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
         if (places) {
-            // (w, h: what was decoded of the oriented image — the whole, the caller's window, or the derived range of either)
+            // (w, h: what was decoded of the oriented image — the whole, the caller's window, or the derived range of either — or the view)
             const Need &nd = need[(size_t)i];
             const AxisPlace px{places[i].width, places[i].x, nd.x0, w}, py{places[i].height, places[i].y, nd.y0, h};
             ri[i].xtab = tabs.axis(true, nd.sw, out_width, bits & 1, &px, bx).word_off;
@@ -556,13 +600,16 @@ int mj_debug_resize_shape(const mj_plan *p, int32_t out[8]) {
 }
 
 int mj_debug_reduce_shape(const mj_plan *p, int32_t image, int32_t out[7]) {
-    if (!p || !out || !p->resized || p->orient_only || image < 0 || image >= p->n_images) return MJ_ERR_INVALID;
+    if (!p || !out || !p->resized || p->orient_only || image < 0 || image >= (p->n_views ? p->n_views : p->n_images)) return MJ_ERR_INVALID;
     if (p->reduces) {
         for (int k = 0; k < 6; ++k) out[k] = p->h_rd[(size_t)image][(size_t)k];
         out[6] = 1;
         return MJ_OK;
     }
-    const int32_t w = p->windowed ? p->h_win[image].w : p->h_images[image].width, h = p->windowed ? p->h_win[image].h : p->h_images[image].height;
+    int32_t w, h;
+    if (p->n_views) { w = p->h_view_size[(size_t)image][0]; h = p->h_view_size[(size_t)image][1]; }
+    else if (p->windowed) { w = p->h_win[image].w; h = p->h_win[image].h; }
+    else { w = p->h_images[image].width; h = p->h_images[image].height; }
     const int32_t v[7] = {1, 1, 0, 0, w, h, 0};
     for (int k = 0; k < 7; ++k) out[k] = v[k];
     return MJ_OK;
