@@ -194,16 +194,16 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  * request with views, the per-output ones — slots, output->mirror, places — with n_views), read during the call only.
  *
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
- * window -> resize with the filter (to the place's size, onto the canvas) -> mirror -> the output's element type.  In Pillow's
- * terms the result is exif_transpose(img.convert(mode)).crop(window).resize(size, filter) — with reducing_gap, Pillow's argument of
- * that name to that resize.
+ * affine transform -> window -> resize with the filter (to the place's size, onto the canvas) -> mirror -> the output's element
+ * type.  In Pillow's terms the result is exif_transpose(img.convert(mode))[.transform(img.size, AFFINE, a, resample, fillcolor)]
+ * .crop(window).resize(size, filter) — with reducing_gap, Pillow's argument of that name to that resize.
  *
  * Refusals common to all fields: MJ_ERR_INVALID with a message in mj_last_error — naming the image where there is one — for a
  * value outside what the field takes; MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT together with ANY field that changes the plan
  * (the seam outputs are whole images in stored order, in the files' components, at the files' sizes; a window plan refuses
  * MJ_FLAG_KEEP_COEF too).  Checked in this order, the first fault reported: filter, mode, orientations, output — these before
  * the context is looked at, so that a bad description is diagnosed without a GPU (the message is then mj_last_error(NULL)'s) —,
- * ctx / batch / out, the size, the KEEP flags, views, slots, places, windows, then the batch itself.  (reducing_gap's value is checked
+ * ctx / batch / out, the size, the KEEP flags, affine (filter, array, reducing_gap), views, affine's matrices, slots, places, windows, then the batch itself.  (reducing_gap's value is checked
  * with the first four.) */
 typedef struct {
     int32_t x, y, width, height;
@@ -234,6 +234,16 @@ typedef struct {
     int32_t image;              /* index into the batch */
     mj_roi window;              /* of the oriented image, after the mode; all zero: the whole (oriented) image */
 } mj_view;
+/* One output's affine transform (mj_plan_request.affine): the matrix maps OUTPUT pixel centres to source coordinates, as the
+ * `data` of Pillow's Image.transform(size, Image.AFFINE, data) and torchvision's inverse matrix do.  All six 0: no transform. */
+typedef struct {
+    double a[6];
+} mj_affine;
+#define MJ_AFFINE_NEAREST  1
+#define MJ_AFFINE_BILINEAR 2
+#define MJ_AFFINE_BICUBIC  3
+/* mj_plan_request.affine's value: the resample filter MJ_AFFINE_* and the fill byte of output components 0, 1, 2 */
+#define MJ_AFFINE_FIELD(filter, f0, f1, f2) ((uint32_t)(filter) | (uint32_t)(f0) << 8 | (uint32_t)(f1) << 16 | (uint32_t)(f2) << 24)
 typedef struct {
     /* Region of interest.  DEFAULT NULL: whole images.  Else the output for image i is the window rois[i] of the image — x along
      * image_width, y along image_height — and nothing else.  Window i in the plan's layout:
@@ -296,6 +306,38 @@ typedef struct {
      * size").  MJ_ERR_INVALID also: one of the two 0, or either outside 1..65535.  MJ_ERR_UNSUPPORTED: a shrink so strong that one
      * pixel's taps do not fit a workgroup's LDS, or more output tiles than one launch takes (about 6.8e10: split the batch). */
     int32_t out_width, out_height;
+    /* Affine transform — rotate, shear, translate, scale — of the whole oriented image, in front of the window and the resize
+     * (tools/affine_model.py).  DEFAULT 0 — also every matrix all zero: no transform.  Else MJ_AFFINE_FIELD(filter, fill...), with a
+     * size, and the request is the `request` member of a mj_plan_affine_request — declared below —, whose `affine` holds one
+     * mj_affine per OUTPUT (n_views entries in a request with views, else n_images): output k is, bit for bit,
+     *   exif_transpose(img.convert(mode)).transform(img.size, Image.AFFINE, affine[k].a, resample, fillcolor=fill)
+     *       .crop(window_k).resize(target_k, filter)
+     * on the canvas, mirrored if mirror[k], through the output table.  The transformed image has the oriented image's size
+     * (Pillow's expand=False); rois / views' windows, places and the size refer to it.  An output whose matrix is all zero is the
+     * output of the request without the field.  Pillow's rules, restated (w x h: the oriented image; (x, y): a pixel of it):
+     *   MJ_AFFINE_BILINEAR / MJ_AFFINE_BICUBIC   xin = a0 (x + 0.5) + a1 (y + 0.5) + a2, yin = a3 (x + 0.5) + a4 (y + 0.5) + a5 in
+     *       doubles, every operation rounded on its own; fill where xin < 0, xin >= w, yin < 0 or yin >= h; else 2 x 2 / 4 x 4 taps
+     *       around (xin - 0.5, yin - 0.5) with clipped columns, a row outside the image taking the value of the row before it,
+     *       interpolated in doubles along x, then y; bilinear truncates, bicubic clips to 0..255 and truncates
+     *   MJ_AFFINE_NEAREST with a1 == 0 and a3 == 0   the source column of output column x is found by ACCUMULATION: xo = a2 + a0 * 0.5,
+     *       then per column (xo < 0 ? -1 : (int)xo) and xo += a0; rows likewise with a5 + a4 * 0.5 and a4 (host-built tables)
+     *   MJ_AFFINE_NEAREST otherwise   16.16 fixed point: FIX(v) = floor(v * 65536 + 0.5); A2 = FIX(a2 + a0 * 0.5 + a1 * 0.5),
+     *       A5 = FIX(a5 + a3 * 0.5 + a4 * 0.5); xi = (int32)(A2 + x FIX(a0) + y FIX(a1)) >> 16 in wrapping 32-bit arithmetic, yi likewise
+     * A pixel whose source lies outside the image is fill.  mj_host_affine is the host twin.
+     * The plan is the PLAIN plan of its images, as a plan with views is: images decoded whole and once, the fused launch wherever
+     * the plain plan takes it; rois with the field become per-output records, not a window plan (a rotated window needs source
+     * pixels outside itself).  One more launch (csrc/affine.hip) between stage 2 and the resize launch writes, for every output,
+     * ONLY its window of the transformed image — evaluated at the window's absolute coordinates —, densely, in the output's
+     * components, into a second plan-owned buffer the resize launch reads as upright images.  Orientation costs no pass (the
+     * kernel maps oriented to stored coordinates where it fetches); MJ_MODE_L converts every fetched tap before interpolating.
+     * MJ_ERR_INVALID, naming the output: set without a size ("affine needs a size"); a filter that is none of MJ_AFFINE_*; a NULL
+     * array; a matrix entry that is not finite; an image with a side of 32768 or more; a matrix under which a corner pixel of the
+     * output has a source coordinate of magnitude 32768 or more (Pillow leaves its defined arithmetic there), and, under
+     * MJ_AFFINE_NEAREST, the same for the corner values Pillow's check_fixed tests; together with reducing_gap ("not yet": the
+     * reduce would have to read the new buffer).  Left for later as well: expand=True, use without a size, perspective transforms.
+     * The field lies in the four bytes between out_height and slots that were padding, as n_views and reducing_gap do: the
+     * request keeps its size and every other field its offset. */
+    uint32_t affine;
     /* DEFAULT NULL: image k goes to slot k, the array has n_images slots, and n_slots is ignored.  Else image k goes to slot
      * slots[k] < n_slots — several plans can fill one array this way (files of several kinds are one plan per kind); slots the
      * plan does not name are not touched.  MJ_ERR_INVALID: a slot outside n_slots. */
@@ -345,7 +387,8 @@ typedef struct {
      *   MJ_FILTER_HAMMING   support 1    sinc(x) * (0.54 + 0.46 cos(pi x))
      *   MJ_FILTER_BICUBIC   support 2    Keys' cubic with a = -0.5
      *   MJ_FILTER_LANCZOS   support 3    sinc(x) * sinc(x / 3) on [-3, 3)
-     * (Pillow's NEAREST is not a convolution — it walks an affine transform — and is not offered.)  Weights in doubles, normalised,
+     * (Pillow's NEAREST is not a convolution — it walks an affine transform, the walk mj_plan_request.affine offers with
+     * MJ_AFFINE_NEAREST — and is not offered as a resize filter.)  Weights in doubles, normalised,
      * rounded away from zero to 22 bits (mj_host_resize_table_filtered); per pixel clip((2^21 + sum taps * in) >> 22, 0, 255) with a
      * signed sum and an arithmetic shift: the taps of BICUBIC and LANCZOS are negative in their side lobes, and plans of those two
      * run signed instances of the resize kernels (the other three share the unsigned ones: their taps are >= 0).
@@ -401,6 +444,13 @@ typedef struct {
     mj_plan_request request;
     const mj_view *views;
 } mj_plan_views_request;
+/* A request with an affine transform (request.affine != 0): its head is a mj_plan_views_request — `views` is read where
+ * request.n_views != 0 —, and `affine` holds one matrix per output.  Zeroed, it is the zeroed request. */
+typedef struct {
+    mj_plan_request request;
+    const mj_view *views;
+    const mj_affine *affine;
+} mj_plan_affine_request;
 /* request NULL: a zeroed request. */
 int mj_plan_create_with(mj_context *ctx, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
 /* The plain plan: exactly mj_plan_create_with(ctx, batch, NULL, out). */
@@ -409,6 +459,13 @@ int mj_plan_create(mj_context *ctx, const mj_batch *batch, mj_plan **out);
  * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
  * is neither 1 nor 3, NULL with pixels to convert. */
 int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, int64_t n_pixels, uint8_t *out);
+/* The host twin of the affine launch (no context): src is a row-major w x h image of ncomp (1 or 3) interleaved components;
+ * out receives the window (x0, y0, win_w, win_h) of its transform under matrix a[6] with MJ_AFFINE_* `filter` and fill[ncomp] —
+ * row-major, win_w * win_h * ncomp bytes, evaluated at the window's absolute coordinates.  The window may reach beyond w x h:
+ * Image.transform(size, ..) with a size of its own is the window (0, 0, size).  MJ_ERR_INVALID: what mj_plan_request.affine
+ * refuses (its corner tests on the larger of the image and the window's end), an empty window, NULL. */
+int mj_host_affine(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, const double *a, int32_t filter, const uint8_t *fill,
+                   int32_t x0, int32_t y0, int32_t win_w, int32_t win_h, uint8_t *out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -555,6 +612,9 @@ int mj_plan_time_execute(mj_plan *plan, int iters, uint8_t *rgb_device, float *f
 /* A resized plan's resize launch alone (after an execute: it reads what stage 2 left), `iters` times into rgb_device (NULL: where the
  * latest execute wrote): ms per launch, and the bytes of un-resized pixels it reads (written bytes: mj_plan_info.rgb_bytes). */
 int mj_plan_time_resize(mj_plan *plan, int iters, uint8_t *rgb_device, float *ms, int64_t *source_bytes);
+/* A plan's affine launch alone (mj_plan_request.affine; after an execute): ms per launch, and the bytes it writes (it reads, at
+ * most, mj_plan_time_resize's source_bytes).  MJ_ERR_INVALID: not a plan with an affine transform. */
+int mj_plan_time_affine(mj_plan *plan, int iters, float *ms, int64_t *written_bytes);
 /* A reducing plan's reduce launch alone (mj_plan_request.reducing_gap; after an execute): ms per launch.  It reads the decoded
  * pixels (mj_plan_time_resize's source_bytes) and writes the reduced images.  MJ_ERR_INVALID: not a reducing plan. */
 int mj_plan_time_reduce(mj_plan *plan, int iters, float *ms);

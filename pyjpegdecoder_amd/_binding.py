@@ -26,6 +26,8 @@ DTYPES = {"uint8": MJ_DTYPE_U8, "float16": MJ_DTYPE_F16, "bfloat16": MJ_DTYPE_BF
 DTYPE_BYTES = {"uint8": 1, "float16": 2, "bfloat16": 2, "float32": 4}
 MJ_FILTER_BILINEAR, MJ_FILTER_BOX, MJ_FILTER_HAMMING, MJ_FILTER_BICUBIC, MJ_FILTER_LANCZOS = 0, 1, 2, 3, 4
 # the resample filters of a decode to a fixed size by name (tools/resize_model.py: FILTERS)
+MJ_AFFINE_NEAREST, MJ_AFFINE_BILINEAR, MJ_AFFINE_BICUBIC = 1, 2, 3
+AFFINE_FILTERS = {"nearest": MJ_AFFINE_NEAREST, "bilinear": MJ_AFFINE_BILINEAR, "bicubic": MJ_AFFINE_BICUBIC}
 FILTERS = {"bilinear": MJ_FILTER_BILINEAR, "box": MJ_FILTER_BOX, "hamming": MJ_FILTER_HAMMING, "bicubic": MJ_FILTER_BICUBIC,
            "lanczos": MJ_FILTER_LANCZOS}
 
@@ -44,7 +46,7 @@ EXPORTS = (
     "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table", "mj_host_normalize_table", "mj_host_exif_orientations",
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
-    "mj_plan_time_reduce",
+    "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine",
     "mj_debug_plan_shape", "mj_debug_cache_stats",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
@@ -142,9 +144,31 @@ class PlanRequestC(ctypes.Structure):
         ctypes.c_int32.from_buffer(self, type(self).n_slots.offset + 4).value = n
 
 
+    # mj_plan_request.affine: a word in the four bytes between out_height and slots, padding likewise — MJ_AFFINE_* in its low byte,
+    # the fill bytes above it.  Not 0: the request is the `request` member of a PlanAffineRequestC, whose `affine` holds one matrix
+    # per output
+    @property
+    def affine(self) -> int:
+        return ctypes.c_uint32.from_buffer(self, type(self).out_height.offset + 4).value
+
+    @affine.setter
+    def affine(self, word: int):
+        ctypes.c_uint32.from_buffer(self, type(self).out_height.offset + 4).value = word
+
+
 class PlanViewsRequestC(ctypes.Structure):
     """mj_plan_views_request: a request with views — the request, and behind it the array its n_views counts."""
     _fields_ = [("request", PlanRequestC), ("views", ctypes.POINTER(ViewC))]
+
+
+class AffineC(ctypes.Structure):
+    """mj_affine: one output's matrix, output to source (all zero: no transform)."""
+    _fields_ = [("a", ctypes.c_double * 6)]
+
+
+class PlanAffineRequestC(ctypes.Structure):
+    """mj_plan_affine_request: a request with an affine transform — a request with views' layout, and behind it one matrix per output."""
+    _fields_ = [("request", PlanRequestC), ("views", ctypes.POINTER(ViewC)), ("affine", ctypes.POINTER(AffineC))]
 
 
 class PlanInfoC(ctypes.Structure):
@@ -199,6 +223,8 @@ def load_library():
     L.mj_plan_fill_source.argtypes = [vp, ctypes.c_int]
     L.mj_plan_time_resize.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
     L.mj_plan_time_reduce.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+    L.mj_host_affine.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_double), i32, vp, i32, i32, i32, i32, vp]
+    L.mj_plan_time_affine.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
@@ -375,6 +401,23 @@ def reduce(a: np.ndarray, fx: int, fy: int, phase_x: int = 0, phase_y: int = 0) 
     return out
 
 
+def affine(a: np.ndarray, matrix, filter="nearest", fill=0, window=None) -> np.ndarray:
+    """mj_host_affine (host only): the affine launch's arithmetic on a row-major uint8 (H, W) or (H, W, 3) array — the window
+    (x, y, width, height) (None: all) of Image.transform(size, AFFINE, matrix, filter, fillcolor=fill) (tools/affine_model.py)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    h, w = a.shape[:2]
+    nc = a.shape[2] if a.ndim == 3 else 1
+    x0, y0, ww, wh = window if window is not None else (0, 0, w, h)
+    fb = np.zeros(3, dtype=np.uint8)
+    fb[:] = fill
+    out = np.empty((max(wh, 0), max(ww, 0)) + a.shape[2:], dtype=np.uint8)
+    m = (ctypes.c_double * 6)(*[float(v) for v in matrix])
+    fid = AFFINE_FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+    if not isinstance(fid, int) or load_library().mj_host_affine(_ptr(a), w, h, nc, m, fid, _ptr(fb), x0, y0, ww, wh, _ptr(out)) != MJ_OK:
+        raise ValueError("mj_host_affine: bad arguments")
+    return out
+
+
 def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarray:
     """mj_host_normalize_table (host only): the 256 bit patterns (uint16 for "float16" / "bfloat16", uint32 for "float32") one
     component's resized bytes 0..255 are stored as with this mean and std (tools/normalize_model.py: table_bits)."""
@@ -450,13 +493,15 @@ def output_desc(output):
 
 
 def plan_request(n_images, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None, places=None,
-                 fill=None, reducing_gap=None, views=None):
+                 fill=None, reducing_gap=None, views=None, affine=None):
     """(mj_plan_request, the arrays it points to) for a batch of ``n_images`` from Plan's keywords: every keyword is one field of
     the request (include/mijpeg.h), None its default.  Pure: no library, no context.  ValueError for what only a sized or placed
     plan has and for a per-image list that has not one entry for each image (with ``views``: places and the mirror flags have one
     for each view)."""
     if size is None and views is not None:
         raise ValueError("views needs size: only a resized plan has several outputs per image")
+    if size is None and affine is not None:
+        raise ValueError("affine needs size: only a resized plan reads the transformed images")
     if size is None and (places is not None or filter is not None or output is not None):
         raise ValueError("places, filter and output need size: only a resized plan has a canvas, resamples and has a dense output")
     if size is None and reducing_gap is not None:
@@ -464,7 +509,10 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
     if fill is not None and places is None:
         raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
     keep = {}
-    if views is not None:       # (the request is then the head of the structure that holds the array's pointer)
+    if affine is not None:      # (the request is then the head of the structure that holds the arrays' pointers)
+        keep["affine_request"] = ext = PlanAffineRequestC()
+        r = ext.request
+    elif views is not None:
         keep["views_request"] = ext = PlanViewsRequestC()
         r = ext.request
     else:
@@ -495,6 +543,15 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
         keep["views"] = ext.views = (ViewC * max(1, len(views)))(*[ViewC(int(i), RoiC(*(int(v) for v in (w if w is not None else (0, 0, 0, 0)))))
                                                                      for i, w in views])
         r.n_views = len(views)
+    if affine is not None:      # ((matrices: one 6-tuple or None per output, a name of AFFINE_FILTERS or its MJ_AFFINE_*, the fill bytes))
+        matrices, name, fb = affine
+        n_out = len(views) if views is not None else n_images
+        if len(matrices) != n_out:
+            raise ValueError(f"affine: {len(matrices)} entries, not one for each of the {n_out} {'views' if views is not None else 'images'}")
+        keep["affine"] = ext.affine = (AffineC * max(1, len(matrices)))(*[AffineC((ctypes.c_double * 6)(*(m if m is not None else (0.0,) * 6)))
+                                                                          for m in matrices])
+        fb = (tuple(fb) + (0, 0, 0))[:3]
+        r.affine = (AFFINE_FILTERS[name] if isinstance(name, str) else int(name)) | fb[0] << 8 | fb[1] << 16 | fb[2] << 24
     for name, given in (("places", places), ("orientation", orientation), ("mirror", keep.get("mirror"))):
         per_view = views is not None and name != "orientation"
         if given is not None and len(given) != (len(views) if per_view else n_images):
@@ -598,12 +655,13 @@ class Plan:
     one (width, height, x, y) per image: the size it is resized to and where it lies on the canvas; fill: with places, up to three
     bytes, one per output component.  reducing_gap: with size, a number >= 1.0 — the two-step resize, Pillow's argument of that name.
     views: with size, one (image, (x, y, width, height) or None) per OUTPUT — several windows of one decoded image; slots, the mirror
-    flags and places then have one entry per view."""
+    flags and places then have one entry per view.  affine: with size, (matrices, filter, fill) — one 6-tuple or None per output, a
+    name of AFFINE_FILTERS, up to three fill bytes: the affine transform in front of the windows and the resize."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None):
+                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None, affine=None):
         request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill,
-                                  reducing_gap, views)
+                                  reducing_gap, views, affine)
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -670,6 +728,12 @@ class Plan:
         """(ms per resize launch, bytes of un-resized pixels it reads) of a resized plan that has been executed."""
         ms, nb = ctypes.c_float(), ctypes.c_int64()
         self.ctx.check(self.ctx.lib.mj_plan_time_resize(self.handle, iters, rgb_device or None, ctypes.byref(ms), ctypes.byref(nb)))
+        return ms.value, nb.value
+
+    def time_affine(self, iters: int = 10):
+        """(ms per affine launch, bytes it writes) of a plan with an affine transform that has been executed (mj_plan_time_affine)."""
+        ms, nb = ctypes.c_float(), ctypes.c_int64()
+        self.ctx.check(self.ctx.lib.mj_plan_time_affine(self.handle, iters, ctypes.byref(ms), ctypes.byref(nb)))
         return ms.value, nb.value
 
     def time_reduce(self, iters: int = 10) -> float:

@@ -678,6 +678,158 @@ def _named(index: Optional[Sequence[int]], i: int, fn, *args, **kwargs):
         raise type(e)(f"file {index[i]}: {e}") from None
 
 
+# Pillow's Image.Resampling numbering of the filters Image.transform takes
+_PILLOW_AFFINE_FILTERS = {0: "nearest", 2: "bilinear", 3: "bicubic"}
+
+
+def _is_number(v) -> bool:
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_matrix(m) -> bool:
+    return isinstance(m, (tuple, list, np.ndarray)) and len(m) == 6 and all(_is_number(v) for v in m)
+
+
+def affine_fault(a: Sequence[float], resample: str, w: int, h: int) -> Optional[str]:
+    """What is refused of one matrix for a ``w`` x ``h`` image (None: nothing) — csrc/affine.hip's affine_fault, restated: an entry
+    that is not finite, a side of 32768 or more, a corner pixel whose source coordinate has a magnitude of 32768 or more (Pillow
+    leaves its defined arithmetic there) and, under "nearest", the same for the corners Pillow's check_fixed tests and entries that
+    do not fit 16.16 fixed point."""
+    if not all(math.isfinite(v) for v in a):
+        return "a matrix entry is not finite"
+    if w >= 32768 or h >= 32768:
+        return "an image with a side of 32768 or more"
+    corners = [(x, y) for y in (0.5, h - 0.5) for x in (0.5, w - 0.5)]
+    if resample == "nearest":
+        corners += [(float(x), float(y)) for y in (0, h) for x in (0, w)]
+    for x, y in corners:
+        if not (abs(a[0] * x + a[1] * y + a[2]) < 32768.0 and abs(a[3] * x + a[4] * y + a[5]) < 32768.0):
+            return "a corner of the output has a source coordinate of magnitude 32768 or more"
+    if resample == "nearest" and not (a[1] == 0 and a[3] == 0):
+        fixed = (a[0], a[1], a[2] + a[0] * 0.5 + a[1] * 0.5, a[3], a[4], a[5] + a[3] * 0.5 + a[4] * 0.5)
+        if not all(abs(v) < 32767.0 for v in fixed):
+            return "a matrix entry of magnitude 32767 or more does not fit NEAREST's 16.16 fixed point"
+    return None
+
+
+@dataclass
+class AffineSpec:
+    """The affine transform of a call (:func:`normalize_affine`): ``matrices`` one 6-tuple of floats or None per OUTPUT, ``resample``
+    "nearest", "bilinear" or "bicubic", ``fill`` one byte per output component (or the one byte given for all of them, until the
+    component count is known)."""
+    matrices: List[Optional[Tuple[float, ...]]]
+    resample: str
+    fill: Tuple[int, ...]
+
+
+def normalize_affine(affine, affine_resample, affine_fill, size, n_outputs: Optional[int] = None, reducing_gap=None, return_seams: bool = False,
+                     ncomp: Optional[int] = None) -> Optional[AffineSpec]:
+    """``affine``, ``affine_resample`` and ``affine_fill`` of a call, checked: None for a call without a transform — ``affine`` None or
+    a list of Nones, which both make the request of a call without the argument — else an :class:`AffineSpec`.  ``affine``: None, one
+    matrix ``(a0, .., a5)`` of numbers for every output, or a list with one matrix or None per output (per file; per view with
+    ``views``); the matrix maps OUTPUT pixel centres to source coordinates, as the ``data`` of Pillow's ``Image.transform(size,
+    Image.AFFINE, data)`` and torchvision's inverse matrix do.  ``affine_resample``: None or "nearest" (the default, as Pillow's and
+    torchvision's is), "bilinear" or "bicubic" — a name in any case, the ``Image.Resampling`` member or its integer.
+    ``affine_fill``: None (0), one byte, or one per output component (``ncomp``, where known).  The transform needs ``size`` and goes
+    neither with ``return_seams`` nor — yet — with ``reducing_gap``.  ``n_outputs`` None: what needs no file.  ValueError otherwise."""
+    name = "nearest"
+    if affine_resample is not None:
+        name = None
+        if isinstance(affine_resample, str):
+            name = affine_resample.lower()
+        elif isinstance(affine_resample, (int, np.integer)) and not isinstance(affine_resample, (bool, np.bool_)):
+            name = _PILLOW_AFFINE_FILTERS.get(int(affine_resample))
+        if name not in B.AFFINE_FILTERS:
+            raise ValueError(f"affine_resample must be one of {', '.join(B.AFFINE_FILTERS)} (a name, Pillow's Image.Resampling member or its "
+                             f"integer value), not {affine_resample!r}")
+    fill = (0,)
+    if affine_fill is not None:
+        entries = (affine_fill,) if _is_int(affine_fill) else tuple(affine_fill) if isinstance(affine_fill, (tuple, list, np.ndarray)) else None
+        if entries is None or len(entries) not in (1, 3) or not all(_is_int(v) and 0 <= int(v) <= 255 for v in entries):
+            raise ValueError(f"affine_fill must be one byte 0..255 or one per output component, not {affine_fill!r}")
+        fill = tuple(int(v) for v in entries)
+    if ncomp is not None:
+        if len(fill) == 1:
+            fill = fill * ncomp
+        if len(fill) != ncomp:
+            raise ValueError(f"affine_fill has {len(fill)} bytes for outputs of {ncomp} component{'s' if ncomp > 1 else ''}")
+    if affine is None:
+        if affine_resample is not None or affine_fill is not None:
+            raise ValueError("affine_resample and affine_fill need affine: without it nothing is transformed")
+        return None
+    if size is None:
+        raise ValueError("affine needs size=(width, height): the transformed images are resized to it")
+    if return_seams:
+        raise ValueError("affine and return_seams do not go together: the seam outputs are the decoded images")
+    if reducing_gap is not None:
+        raise ValueError("affine and reducing_gap do not go together yet: the reduce step would have to read the transformed images "
+                         "(a later step)")
+    if _is_matrix(affine):
+        matrices = None if n_outputs is None else [tuple(float(v) for v in affine)] * n_outputs
+    elif isinstance(affine, (list, tuple)) and all(m is None or _is_matrix(m) for m in affine):
+        if n_outputs is not None and len(affine) != n_outputs:
+            raise ValueError(f"affine has {len(affine)} entries for {n_outputs} outputs")
+        matrices = [tuple(float(v) for v in m) if m is not None else None for m in affine]
+    else:
+        raise ValueError(f"affine must be None, one matrix (a0, a1, a2, a3, a4, a5) of numbers, or a list with one matrix or None per output, "
+                         f"not {affine!r}")
+    for k, m in enumerate(matrices or []):
+        if m is not None and not all(math.isfinite(v) for v in m):
+            raise ValueError(f"affine: output {k}: a matrix entry is not finite")
+        if m is not None and not any(m):
+            raise ValueError(f"affine: output {k}: a matrix that is all zero maps every pixel to the source's corner (None: no transform)")
+    if matrices is not None and all(m is None for m in matrices):
+        return None
+    return AffineSpec(matrices if matrices is not None else [], name, fill)
+
+
+def rois_as_views(rois, n_files: int):
+    """The windows of a call with an affine transform as views, one per file: such a call decodes whole images — a rotated window
+    needs source pixels outside itself — and cuts the window out of the transformed image.  ``rois`` as :func:`normalize_rois`
+    takes it; the windows are checked as views are (:func:`normalize_views`)."""
+    def is_window(r) -> bool:
+        return isinstance(r, (tuple, list, np.ndarray)) and len(r) == 4 and all(_is_int(v) for v in r)
+    if rois is None:
+        return [(i, None) for i in range(n_files)]
+    if is_window(rois):
+        return [(i, tuple(int(v) for v in rois)) for i in range(n_files)]
+    if not isinstance(rois, (list, tuple)) or len(rois) != n_files or not all(r is None or is_window(r) for r in rois):
+        raise ValueError(f"rois must be None, one (x, y, width, height) or a list with one such window or None per file ({n_files}), not {rois!r}")
+    return [(i, tuple(int(v) for v in r) if r is not None else None) for i, r in enumerate(rois)]
+
+
+def check_affine(spec: Optional[AffineSpec], views, odims, index=None) -> None:
+    """every matrix of ``spec`` against the oriented image of its output's file (:func:`affine_fault`): ValueError naming the output"""
+    if spec is None:
+        return
+    for k, ((f, _), m) in enumerate(zip(views, spec.matrices)):
+        why = affine_fault(m, spec.resample, *odims[f]) if m is not None else None
+        if why:
+            raise ValueError(f"affine: output {k} (file {f if index is None else index[f]}): {why}")
+
+
+def rotation_matrix(angle: float, size: Tuple[int, int], center=None, translate=None) -> Tuple[float, ...]:
+    """The matrix ``Image.rotate(angle, center=center, translate=translate)`` builds for ``expand=False`` on an image of ``size`` =
+    (width, height) — counter-clockwise by ``angle`` degrees around ``center`` (None: the image's centre), then moved by
+    ``translate`` — its ``round(.., 15)`` of the sine and cosine included: ``decode(.., affine=rotation_matrix(a, img.size))`` is
+    ``img.rotate(a, resample, fillcolor=fill)``.  At angles that are multiples of 90 Pillow does not transform in some cases (0: a
+    copy; 180, and 90 / 270 of a square image or with expand, without center and translate: a transpose), so its result there is
+    not this matrix's for every filter."""
+    w, h = size
+    angle = angle % 360.0
+    tx, ty = translate if translate is not None else (0, 0)
+    cx, cy = center if center is not None else (w / 2.0, h / 2.0)
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+
+    def transform(x, y):
+        return m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2], m[5] = transform(-cx - tx, -cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
 def _is_resize_kind(k) -> bool:
     """one file's ``resize_to``: an int (the shorter side), (width, height) or "contain" """
     if isinstance(k, str):
@@ -880,6 +1032,7 @@ class _Request:
     fill: Optional[Tuple[int, ...]] = None
     reducing_gap: Optional[float] = None
     views: Optional[List[Tuple[int, Tuple[int, int, int, int]]]] = None
+    affine: Optional[AffineSpec] = None         # :func:`normalize_affine`'s (None: no transform); always with ``views``
 
     @property
     def n_outputs(self) -> int:
@@ -908,9 +1061,12 @@ class _Request:
 
             def pick_view(per_view):
                 return [per_view[k] for k in vk] if per_view is not None else None
+            affine = AffineSpec(pick_view(self.affine.matrices), self.affine.resample, self.affine.fill) if self.affine is not None else None
+            if affine is not None and all(m is None for m in affine.matrices):
+                affine = None
             return _Request(pick(self.files), None, self.size, self.output.for_files(vk) if self.output else None, self.dest, pick_view(self.slots),
                             pick(index), orient, self.resample, self.mode, pick_view(self.places), self.fill, self.reducing_gap,
-                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk])
+                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine)
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
                         self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap)
 
@@ -942,6 +1098,8 @@ class _Request:
             kw.setdefault("mode", self.mode)
         if self.reducing_gap is not None:   # (one step: the arguments of a call without reducing_gap)
             kw["reducing_gap"] = self.reducing_gap
+        if self.affine is not None:         # (no output transformed: the arguments of a call without affine)
+            kw["affine"] = (self.affine.matrices, self.affine.resample, self.affine.fill)
         return kw
 
 
@@ -1090,7 +1248,8 @@ class BatchDecoder:
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
-               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None):
+               orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
+               affine=None, affine_resample=None, affine_fill=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1128,7 +1287,19 @@ class BatchDecoder:
         ``rois=[window]`` and the k-th entry of ``mirror`` and of the list forms of ``resize_to`` and ``place``, which then have one
         entry per view (``orientation`` stays per file).  The result is one array of ``len(views)`` images in the views' order.  A
         file is uploaded, entropy-decoded and reconstructed once however many views name it; a file no view names is not looked
-        at.  Not with ``rois`` or ``return_seams``."""
+        at.  Not with ``rois`` or ``return_seams``.
+        ``affine``, with ``size``: rotate, shear, translate, scale — Pillow's ``Image.transform(img.size, Image.AFFINE, matrix,
+        affine_resample, fillcolor=affine_fill)`` of the whole oriented image, in front of the window and the resize
+        (:func:`normalize_affine`): None, one matrix ``(a0, .., a5)`` for every output, or a list with one matrix or None per output —
+        per file, per view with ``views``.  The matrix maps output to input, as Pillow's and torchvision's inverse matrix do
+        (:func:`rotation_matrix` builds ``Image.rotate``'s).  ``affine_resample``: "nearest" (the default), "bilinear" or "bicubic", one
+        for the call; ``affine_fill``: the byte, or one per output component, of pixels whose source lies outside the image (0).  The
+        transformed image has the oriented image's size (``expand=False``); ``rois``, ``views``, ``resize_to`` and ``size`` refer to
+        it.  What lands on the canvas is ``exif_transpose(img.convert(mode)).transform(img.size, AFFINE, a, affine_resample,
+        fillcolor=affine_fill).crop(window).resize(target, filter)`` bit for bit, then the mirror and the output's element type; an
+        output whose matrix is None is the output of the call without the argument.  Files are decoded whole (a rotated window
+        needs pixels outside itself); one more launch per plan writes every output's window of its transformed image.  Not with
+        ``return_seams``, and not yet with ``reducing_gap``."""
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -1144,6 +1315,10 @@ class BatchDecoder:
         reducing_gap = normalize_reducing_gap(reducing_gap, size)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
+        spec = normalize_affine(affine, affine_resample, affine_fill, size, len(views) if isinstance(views, (list, tuple)) else len(files),
+                                reducing_gap, return_seams)
+        if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
+            views, rois = rois_as_views(rois, len(files)), None
         index = None                            # views: where the files that are read sit in the caller's list
         selected = select_view_files(files, views, size, rois, return_seams)
         if selected is not None:
@@ -1159,6 +1334,7 @@ class BatchDecoder:
         if req.views is not None:               # (what is per output is per view; an error names the view's file)
             req.places = normalize_places(resize_to, place, size, [r[2:] for _, r in req.views], [index[f] for f, _ in req.views])
             req.slots = list(range(len(req.views)))
+            check_affine(spec, req.views, odims, index)
         else:
             req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
         turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
@@ -1167,6 +1343,8 @@ class BatchDecoder:
             nc = req.ncomp or one_component_count([len(p.color_components) for p in parsed.values()])
             req.output = normalize_output(dtype, normalize, mirror, size, req.n_outputs, nc, host=True)
             req.fill = normalize_fill(fill, resize_to, nc)
+            if spec is not None:
+                req.affine = normalize_affine(spec.matrices, spec.resample, spec.fill, size, req.n_outputs, ncomp=nc)
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         results: List[Optional[np.ndarray]] = [None] * len(files)
         seams: List[Optional[dict]] = [None] * len(files)
@@ -1224,10 +1402,14 @@ class BatchDecoder:
         return self._staging
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
-                        resize_to=None, place=None, fill=None, reducing_gap=None, views=None) -> _Request:
+                        resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
+                        affine_fill=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
+        spec = normalize_affine(affine, affine_resample, affine_fill, size, len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap)
+        if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
+            views, rois = rois_as_views(rois, len(files)), None
         index = None
         selected = select_view_files(files, views, size, rois)
         if selected is not None:
@@ -1244,6 +1426,9 @@ class BatchDecoder:
             if selected is not None:            # (what is per output is per view; an error names the view's file)
                 req.views = normalize_views(views, odims, size, index=index)
                 req.places = normalize_places(resize_to, place, size, [r[2:] for _, r in req.views], [index[f] for f, _ in req.views])
+                check_affine(spec, req.views, odims, index)
+                if spec is not None:
+                    req.affine = normalize_affine(spec.matrices, spec.resample, spec.fill, size, len(req.views), ncomp=nc)
             else:
                 req.wins = normalize_rois(rois, odims)
                 req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
@@ -1266,7 +1451,8 @@ class BatchDecoder:
         self.ctx.wait_event(ev.cuda_event)
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
-                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None):
+                      mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
+                      affine=None, affine_resample=None, affine_fill=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1301,7 +1487,9 @@ class BatchDecoder:
         parts) carries it.
         ``views`` as in :meth:`decode`: one tensor of ``len(views)`` images in the views' order, every file decoded once.  Files of
         several kinds are still one plan per kind, each writing its views' slots of the one tensor, and a large call is split into
-        parts by FILE, every file's views in its part."""
+        parts by FILE, every file's views in its part.
+        ``affine``, ``affine_resample`` and ``affine_fill`` as in :meth:`decode`: every plan of the call (files of several kinds and
+        orientation classes, second rounds, parts) runs its own affine launch between its decode and its resize launch."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -1309,7 +1497,8 @@ class BatchDecoder:
         normalize_mode(mode)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap, views)
+        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap, views,
+                                   affine, affine_resample, affine_fill)
         files = req.files                       # (with views: the files some view names)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
@@ -1419,7 +1608,8 @@ class BatchDecoder:
         return results if req.dest is None else req.dest
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
-                           mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None):
+                           mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
+                           affine_fill=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1439,8 +1629,13 @@ class BatchDecoder:
         ``resample``, ``mode`` and ``reducing_gap`` as in :meth:`decode_device`, for every batch; ``resize_to``, ``place`` and
         ``fill`` too (a list per file then has to fit every batch).  ``views``: None, or an iterable that yields, batch by batch,
         what :meth:`decode_device` takes for that batch — a list with one entry per output; ``mirror`` and the list forms of
-        ``resize_to`` and ``place`` then go by view."""
+        ``resize_to`` and ``place`` then go by view.  ``affine``: None, one matrix for every output of every batch, or an iterable
+        that yields, batch by batch, what :meth:`decode_device` takes for that batch; ``affine_resample`` and ``affine_fill`` as
+        there, for every batch."""
         size = normalize_size(size)
+        # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
+        normalize_affine(affine if affine is None or _is_matrix(affine) else (1, 0, 0, 0, 1, 0), affine_resample, affine_fill, size, None, reducing_gap)
+        per_batch_affine = iter(affine) if affine is not None and not _is_matrix(affine) else None
         if views is not None and size is None:
             raise ValueError("views needs size=(width, height): every view is resized to it (crops at their own sizes would be ragged)")
         per_batch_views = iter(views) if views is not None else None
@@ -1480,7 +1675,17 @@ class BatchDecoder:
                         v = next(per_batch_views)
                     except StopIteration:
                         raise ValueError("views yields fewer entries than there are batches") from None
-                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v)
+                t = affine
+                if per_batch_affine is not None:
+                    try:
+                        t = next(per_batch_affine)
+                    except StopIteration:
+                        raise ValueError("affine yields fewer entries than there are batches") from None
+                if t is None or (isinstance(t, (list, tuple)) and all(e is None for e in t)):         # (a batch without a transform)
+                    yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v)
+                    continue
+                yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
+                                           t, affine_resample, affine_fill)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -455,6 +455,45 @@ void reduce_host(const uint8_t *src, const DevReduceImage &im, int ncomp, bool l
 // (luma: the instance that converts colour to L where it reads, mj_plan_request.mode with MJ_MODE_L)
 hipError_t launch_reduce(hipStream_t stream, const ReduceArgs &a, int ncomp, bool luma);
 int reduce_tile_fast(int out_ncomp);     // reduced pixels of a row a workgroup takes
+// ---- affine.hip: the affine transform in front of the window and the resize (mj_plan_request.affine; tools/affine_model.py)
+// One output of a plan with an affine transform: the stored image it is made of (sw x sh pixels of the plan's intermediate
+// buffer, in the plan's layout), the oriented image's size w x h — what Pillow's rules count in —, the window of the transformed
+// image that is written (densely, win_w x win_h, in the plan's layout, at dst_off of the second buffer), and the rule:
+//   kind 0  no transform: the oriented pixels of the window
+//        1  NEAREST by tables: xtab / ytab (word offsets into AffineArgs::tabs) hold the source column / row of every column / row
+//           of the window, -1: outside
+//        2  NEAREST in 16.16 fixed point: fx[6]
+//        3  BILINEAR, 4 BICUBIC: a[6] in doubles
+struct DevAffineImage {
+    int64_t src_off, dst_off;
+    int32_t sw, sh, w, h;
+    int32_t x0, y0, win_w, win_h;
+    int32_t kind, obits;          // obits: orient_bits of the image's orientation
+    int32_t xtab, ytab;
+    int32_t fx[6];
+    double a[6];
+};
+struct AffineArgs {
+    const uint8_t *src;
+    uint8_t *dst;
+    const DevAffineImage *images;
+    const int32_t *tabs;
+    int32_t n_images, layout;           // layout & 1: row-major
+    int32_t tiles_slow, tiles_fast;     // tiles per output: those of the largest window (a smaller one's rest idles)
+    uint32_t fill;                      // byte c in bits 8c..8c+7, per OUTPUT component
+};
+constexpr int kAffineTileFast = 64, kAffineTileSlow = 16;      // pixels of a tile along the layout's contiguous axis / across it
+// what mj_plan_request.affine and mj_host_affine refuse of one matrix for a w x h image: nullptr, or the reason
+const char *affine_fault(const double *a, int filter, int w, int h);
+// the rule's kind for a matrix (filter: MJ_AFFINE_*), its fixed-point form, and the index table of one axis of the NEAREST scale
+// path: entry j is the source index of output index first + j, accumulated from index 0 as Pillow does (-1: outside [0, size))
+int affine_kind(const double *a, int filter);
+void affine_fixed(const double *a, int32_t fx[6]);
+void affine_scale_table(double scale, double offset, int size, int first, int n, int32_t *out);
+// the kernel's arithmetic on the host, for an upright row-major image (obits 0, layout 1); tabs as AffineArgs::tabs
+void affine_host(const uint8_t *src, const DevAffineImage &im, const int32_t *tabs, int ncomp, int out_ncomp, uint32_t fill, uint8_t *out);
+// (ncomp: the decoded images'; out_ncomp: the written ones' — the same, 1 for colour to L, 3 for grey to RGB)
+hipError_t launch_affine(hipStream_t stream, const AffineArgs &a, int ncomp, int out_ncomp);
 // ---- output colour mode (tools/mode_model.py)
 // Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
 __host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }

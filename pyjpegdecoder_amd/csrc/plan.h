@@ -281,6 +281,16 @@ struct mj_plan {
     uint8_t *d_red = nullptr;
     mj::DevReduceImage *d_rd_images = nullptr;
     mj::ReduceArgs rd{};
+    // plans with an affine transform (mj_plan_request.affine): the affine launch (affine.hip) between stage 2 and the resize launch reads
+    // d_src and writes every output's window of its transformed image, packed, in the output's components (af_ncomp), into d_aff,
+    // which is what rz.src then names; the resize launch runs the plain instances of af_ncomp components on upright records
+    bool affine = false;
+    int af_ncomp = 0;
+    int64_t af_bytes = 0;
+    uint8_t *d_aff = nullptr;
+    mj::DevAffineImage *d_af_images = nullptr;
+    int32_t *d_af_tabs = nullptr;
+    mj::AffineArgs af{};
     int32_t n_views = 0;                       // a plan with views (mj_plan_request.views): its resize and reduce records are per view (0: per image)
     std::vector<std::array<int32_t, 2>> h_view_size;   // ... every view's window, stored axes: width, height (mj_debug_reduce_shape)
     std::vector<std::array<int32_t, 6>> h_rd;  // per image (view), stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)
@@ -314,7 +324,14 @@ int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, b
 // is the output's.  The two makers take it: create_resized (resize_plan.hip) with a size, create_oriented (orient.hip) without
 // one and with orientations or a mode; a request with neither is plan_create_common's.
 // views: r.n_views entries where r.n_views != 0 (the caller's mj_plan_views_request), else NULL
-struct PlanRequest { mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; const mj_view *views = nullptr; };
+// affine: one matrix per output where r.affine != 0 (the caller's mj_plan_affine_request), else NULL.  Such a request ALWAYS has
+// views after normalisation: its windows (r.rois) or whole images become one view per image, held in own_views
+struct PlanRequest {
+    mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; const mj_view *views = nullptr; const mj_affine *affine = nullptr;
+    std::vector<mj_view> own_views{};
+};
+// an output without a transform: all six entries 0
+inline bool affine_none(const mj_affine &m) { return !m.a[0] && !m.a[1] && !m.a[2] && !m.a[3] && !m.a[4] && !m.a[5]; }
 constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the messages)
 int create_resized(const PlanRequest &q);
 // reducing_gap's default rule (normalise_request): whether any image of the request — oriented, its window, to its place's size —

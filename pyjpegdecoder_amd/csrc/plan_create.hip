@@ -727,6 +727,24 @@ const mj_view *request_views(const mj_plan_request *request) {
     return request && request->n_views ? reinterpret_cast<const mj_plan_views_request *>(request)->views : nullptr;
 }
 
+const mj_affine *request_affine(const mj_plan_request *request) {
+    return request && request->affine ? reinterpret_cast<const mj_plan_affine_request *>(request)->affine : nullptr;
+}
+
+// The affine transform of a sized request, checked against every output's oriented image (views are in place: normalise_views)
+int check_affine(mj::PlanRequest &q) {
+    const char *fn = mj::kCreateFn;
+    const mj_batch *b = q.b; const mj_plan_request &r = q.r;
+    for (int k = 0; k < r.n_views; ++k) {
+        if (mj::affine_none(q.affine[k])) continue;
+        const mj_image_desc &im = b->images[q.views[k].image];
+        const bool t = r.orientations && (mj::orient_bits(r.orientations[q.views[k].image]) & 4);
+        if (const char *why = mj::affine_fault(q.affine[k].a, (int)(r.affine & 0xFF), t ? im.height : im.width, t ? im.width : im.height))
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: affine: output %d: %s", fn, k, why);
+    }
+    return MJ_OK;
+}
+
 // The views of a sized request, checked; views that are one whole image each, in order, become their absence.
 // (orientations have been checked and, where all upright, dropped)
 int normalise_views(mj::PlanRequest &q) {
@@ -750,7 +768,7 @@ int normalise_views(mj::PlanRequest &q) {
     }
     for (int i = 0; i < b->n_images; ++i)
         if (!named[(size_t)i]) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: no view names it (leave it out of the batch)", fn, i);
-    if (identity) { q.views = nullptr; r.n_views = 0; }
+    if (identity && !q.affine) { q.views = nullptr; r.n_views = 0; }
     return MJ_OK;
 }
 
@@ -762,7 +780,7 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     const char *fn = mj::kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
     const bool sized = r.out_width != 0 || r.out_height != 0;
-    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : nullptr;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : r.affine ? "affine" : nullptr;
     // (what slots, the mirror flags and places have one entry for: the views of a request with views, else the images)
     const int n_out = r.n_views > 0 ? r.n_views : (b ? b->n_images : 0);
     if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
@@ -796,8 +814,30 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     if ((sized || r.orientations || r.mode) && (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
         return fail(ctx, MJ_ERR_INVALID, sized ? "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none"
                                                : "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
+    if (r.affine) {
+        const int n_out_af = r.n_views > 0 ? r.n_views : b->n_images;
+        const int af_filter = (int)(r.affine & 0xFF);
+        if (af_filter != MJ_AFFINE_NEAREST && af_filter != MJ_AFFINE_BILINEAR && af_filter != MJ_AFFINE_BICUBIC)
+            return fail(ctx, MJ_ERR_INVALID, "%s: affine: filter %d is none of MJ_AFFINE_*", fn, af_filter);
+        if (!q.affine) return fail(ctx, MJ_ERR_INVALID, "%s: affine without its array of matrices", fn);
+        bool none = true;
+        for (int k = 0; k < n_out_af && none; ++k) none = mj::affine_none(q.affine[k]);
+        if (none) { r.affine = 0; q.affine = nullptr; }       // (no output is transformed: the request without the field)
+    }
+    if (r.affine) {
+        if (r.reducing_gap != 0)
+            return fail(ctx, MJ_ERR_INVALID, "%s: affine and reducing_gap do not go together yet: the reduce launch would have to read the transformed images", fn);
+        if (!b->images && b->n_images > 0) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+        if (!r.n_views) {       // (windows, or whole images, as one view per image: the plan decodes whole images)
+            q.own_views.resize((size_t)b->n_images);
+            for (int i = 0; i < b->n_images; ++i) q.own_views[(size_t)i] = mj_view{i, r.rois ? r.rois[i] : mj_roi{0, 0, 0, 0}};
+            if (b->n_images > 0) { q.views = q.own_views.data(); r.n_views = b->n_images; r.rois = nullptr; }
+        }
+    }
     if (r.n_views)
         if (int rc = normalise_views(q)) return rc;
+    if (r.affine && r.n_views)
+        if (int rc = check_affine(q)) return rc;
     const int n_outputs = r.n_views ? r.n_views : b->n_images;
     if (!r.slots) r.n_slots = n_outputs;
     for (int i = 0; r.slots && i < n_outputs; ++i)
@@ -848,14 +888,14 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
 int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request, mj_plan_request *normal) {
     if (!normal) return MJ_ERR_INVALID;
     mj_plan *none = nullptr;
-    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request)};
+    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request), request_affine(request)};
     const int rc = normalise_request(q, false);
     if (rc == MJ_OK) *normal = q.r;
     return rc;
 }
 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
-    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request)};
+    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request), request_affine(request)};
     if (int rc = normalise_request(q)) return rc;
     if (q.r.out_width) return mj::create_resized(q);
     if (q.r.orientations || q.r.mode) return mj::create_oriented(q);

@@ -9,6 +9,10 @@
 // A request with views (mj_plan_request.views) goes the same way with one record per VIEW in the resize and reduce launches: the
 // plan is the plain plan of the images, a view's record starts at its window's origin inside its decoded image (pixel_offset), keeps
 // that image's row as its pitch, and its tables — and factors — are its window's.
+// A request with an affine transform (mj_plan_request.affine; always with views, see plan.h) adds one step,
+//   affine_stage           one record per output for the affine launch (affine.hip), its NEAREST index tables, and where every
+//                          output's window of its transformed image lies in the plan's second buffer
+// and the resize launch's records are then upright images of the output's components in THAT buffer, the window's row their pitch.
 #include <math.h>
 #include <map>
 
@@ -208,6 +212,60 @@ int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std:
     return MJ_OK;
 }
 
+// ---- plans with an affine transform: the launch in front of the resize ----------------------------------------------------------
+// In: the request (views in place, matrices checked), the plan, CO — the components the launch writes.  Out: the plan's affine
+// launch (p->af, records and tables uploaded), `off` — per output, where its window lies in the buffer of transformed windows —
+// and *bytes, that buffer's size.
+int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> &off, int64_t *bytes) {
+    const char *fn = mj::kCreateFn;
+    const uint8_t *orient = q.r.orientations;
+    const int n = q.r.n_views, filter = (int)(q.r.affine & 0xFF);
+    std::vector<mj::DevAffineImage> recs((size_t)n);
+    std::vector<int32_t> tabs;
+    off.resize((size_t)n);
+    mj::AffineArgs &a = p->af = mj::AffineArgs{};
+    const bool rowmajor = (p->layout & 1) != 0;
+    int max_slow = 1, max_fast = 1;
+    int64_t at = 0;
+    for (int k = 0; k < n; ++k) {
+        const int i = q.views[k].image;
+        mj_roi shown, stored;
+        mj::view_window(q.b, orient, q.views[k], &shown, &stored);      // (checked by the request's normalisation)
+        mj::DevAffineImage &d = recs[(size_t)k] = mj::DevAffineImage{};
+        d.src_off = p->h_images[i].rgb_off; d.dst_off = off[(size_t)k] = at;
+        d.sw = p->h_images[i].width; d.sh = p->h_images[i].height;
+        d.obits = orient ? mj::orient_bits(orient[i]) : 0;
+        d.w = (d.obits & 4) ? d.sh : d.sw; d.h = (d.obits & 4) ? d.sw : d.sh;
+        d.x0 = shown.x; d.y0 = shown.y; d.win_w = shown.width; d.win_h = shown.height;
+        const mj_affine &m = q.affine[k];
+        if (!mj::affine_none(m)) {
+            d.kind = mj::affine_kind(m.a, filter);
+            for (int t = 0; t < 6; ++t) d.a[t] = m.a[t];
+            if (d.kind == 2) mj::affine_fixed(m.a, d.fx);
+            if (d.kind == 1) {
+                d.xtab = (int32_t)tabs.size(); d.ytab = d.xtab + d.win_w;
+                tabs.resize(tabs.size() + (size_t)d.win_w + d.win_h);
+                mj::affine_scale_table(m.a[0], m.a[2], d.w, d.x0, d.win_w, tabs.data() + d.xtab);
+                mj::affine_scale_table(m.a[4], m.a[5], d.h, d.y0, d.win_h, tabs.data() + d.ytab);
+                if (tabs.size() > ((size_t)1 << 28)) return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: the index tables of this batch are too large", fn);
+            }
+        }
+        at += (int64_t)d.win_w * d.win_h * CO;
+        max_fast = std::max(max_fast, rowmajor ? d.win_w : d.win_h); max_slow = std::max(max_slow, rowmajor ? d.win_h : d.win_w);
+    }
+    a.tiles_fast = (max_fast + mj::kAffineTileFast - 1) / mj::kAffineTileFast;
+    a.tiles_slow = (max_slow + mj::kAffineTileSlow - 1) / mj::kAffineTileSlow;
+    if ((int64_t)n * a.tiles_slow * a.tiles_fast > mj::kResizeGridX * (int64_t)65535)
+        return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld affine tiles are more than one launch takes; split the batch", fn, (long long)n * a.tiles_slow * a.tiles_fast);
+    a.n_images = n; a.layout = p->layout;
+    for (int c = 0; c < CO; ++c) a.fill |= ((q.r.affine >> (8 + 8 * c)) & 0xFFu) << (8 * c);
+    if (int rc = upload(p, &p->d_af_images, recs.data(), recs.size())) return rc;
+    if (int rc = upload(p, &p->d_af_tabs, tabs.data(), tabs.size())) return rc;
+    a.images = p->d_af_images; a.tabs = p->d_af_tabs;
+    *bytes = at;
+    return MJ_OK;
+}
+
 // ---- tap tables: one per distinct axis --------------------------------------------------------------------------------------
 // Where an axis lies on a placed plan's canvas: resized to `resized` entries at offset `off`; `base` is the first source entry of
 // the part of the source that was decoded, `len` that part's entries.
@@ -398,7 +456,7 @@ bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r, const mj_vi
 int mj::create_resized(const PlanRequest &q) {
     const char *fn = kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
-    auto [rois, orient, mode, out_width, out_height, slots, n_slots, n_views, output, filter, reducing_gap, places, fill] = q.r;
+    auto [rois, orient, mode, out_width, out_height, affine, slots, n_slots, n_views, output, filter, reducing_gap, places, fill] = q.r;
     const mj_view *views = q.views;
     const int dtype = output ? output->dtype : MJ_DTYPE_U8, esize = dtype_size(dtype);
     std::vector<Need> need;
@@ -431,7 +489,8 @@ int mj::create_resized(const PlanRequest &q) {
     // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
     int C = p->ncomp;
     // n: the launches' records — one per image, or one per view
-    const int n = views ? n_views : p->n_images, CO = mode ? mode : C, CT = mode ? 1 : C;
+    const int n = views ? n_views : p->n_images, CO = mode ? mode : C;
+    int CT = mode ? 1 : C;
     p->n_views = views ? n_views : 0;
     if (mode) p->out_ncomp = CO;
     // a reducing plan (normalise_request: some image of it has a factor above 1): the resize reads the reduced images.  Colour to
@@ -442,6 +501,14 @@ int mj::create_resized(const PlanRequest &q) {
     if (reducing) {
         if (int rc = reduce_stage(q, p, swapped, luma, red, &red_bytes)) return rc;
         if (luma) { mode = 0; C = 1; }
+    }
+    // a plan with an affine transform: the resize reads upright windows of the transformed images, in the output's components —
+    // mode and orientation are the affine launch's, and the resize is the plain one of CO components
+    std::vector<int64_t> af_off;
+    int64_t af_bytes = 0;
+    if (affine) {
+        if (int rc = affine_stage(q, p, CO, af_off, &af_bytes)) return rc;
+        mode = 0; C = CT = CO; orient = nullptr; swapped = false;
     }
     const int64_t out_image = (int64_t)out_width * out_height * CO * esize;      // bytes
     TapTables tabs(filter, places != nullptr);
@@ -461,10 +528,12 @@ int mj::create_resized(const PlanRequest &q) {
         ri[i].w = w; ri[i].h = h;
         if (views) {
             mj_roi shown, stored;
-            mj::view_window(b, orient, views[i], &shown, &stored);      // (checked by the request's normalisation)
+            mj::view_window(b, q.r.orientations, views[i], &shown, &stored);      // (checked by the request's normalisation)
             ri[i].src_off += pixel_offset(p->layout, p->h_images[img].width, p->h_images[img].height, p->ncomp, stored.x, stored.y);
             w = shown.width; h = shown.height;
             p->h_view_size.push_back({stored.width, stored.height});
+            // (behind an affine launch: the window itself, upright and dense, in the buffer of transformed windows)
+            if (affine) { ri[i].src_off = af_off[(size_t)i]; ri[i].w = w; ri[i].h = h; }
         }
         const float *bx = nullptr, *by = nullptr;
         if (reducing) {
@@ -541,6 +610,13 @@ int mj::create_resized(const PlanRequest &q) {
         p->rd.src = p->d_src; p->rd.dst = p->d_red;
         a.src = p->d_red;
         p->reduces = true; p->rd_luma = luma;
+    }
+    if (affine) {
+        // the transformed windows: a second plan-owned buffer with the same slack, which the resize launch reads as it would d_src
+        MJ_HIP(ctx, alloc(p, &p->d_aff, (size_t)af_bytes + 64));
+        p->af.src = p->d_src; p->af.dst = p->d_aff;
+        a.src = p->d_aff;
+        p->affine = true; p->af_ncomp = CO; p->af_bytes = af_bytes;
     }
     p->info.rgb_bytes = (int64_t)n_slots * out_image;
     p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
