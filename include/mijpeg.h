@@ -569,6 +569,12 @@ int mj_debug_resize_shape(const mj_plan *plan, int32_t out[8]);
  * image (view). */
 int mj_debug_reduce_shape(const mj_plan *plan, int32_t image, int32_t out[7]);
 
+/* Test hook (host only, reads fields): how a reducing plan's reduce launch is cut — out = { reduced rows per tile, reduced pixels of
+ * a row per tile (along the contiguous axis), tiles along the rows, tiles along the contiguous axis (per image: those of the largest
+ * reduced image), source pixels of a row a wavefront stages at a time in the instance the plan launches }.  MJ_ERR_INVALID: not a
+ * reducing plan. */
+int mj_debug_reduce_launch(const mj_plan *plan, int32_t out[5]);
+
 /* Test hook (host only, no context): *normal = the request as plan creation sees it after its checks — every field that names its
  * default turned into its absence (pointers are the caller's) — or the code of the first fault that needs no context
  * (mj_last_error(NULL) has the message).  request NULL: a zeroed one. */

@@ -46,7 +46,7 @@ EXPORTS = (
     "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table", "mj_host_normalize_table", "mj_host_exif_orientations",
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
-    "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine",
+    "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine", "mj_debug_reduce_launch",
     "mj_debug_plan_shape", "mj_debug_cache_stats",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
@@ -215,6 +215,7 @@ def load_library():
     L.mj_host_reduce_factors.argtypes = [i32, i32, i32, i32, ctypes.c_double, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.mj_host_reduce.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.mj_debug_reduce_shape.argtypes = [vp, i32, ctypes.POINTER(i32)]
+    L.mj_debug_reduce_launch.argtypes = [vp, ctypes.POINTER(i32)]
     L.mj_debug_normalise_request.argtypes = [ctypes.POINTER(BatchC), ctypes.POINTER(PlanRequestC), ctypes.POINTER(PlanRequestC)]
     L.mj_debug_plan_shape.argtypes = [vp, ctypes.POINTER(i32), i32]
     L.mj_debug_cache_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
@@ -717,6 +718,13 @@ class Plan:
         d = dict(zip(("fx", "fy", "phase_x", "phase_y", "width", "height", "reduces"), (int(v) for v in out)))
         d["reduces"] = bool(d["reduces"])
         return d
+
+    def reduce_launch(self) -> dict:
+        """mj_debug_reduce_launch: how a reducing plan's reduce launch is cut — reduced rows and reduced pixels of a row per tile,
+        tiles per image along the rows and along the contiguous axis, and the source pixels of a row a wavefront stages at a time."""
+        out = (ctypes.c_int32 * 5)()
+        self.ctx.check(self.ctx.lib.mj_debug_reduce_launch(self.handle, out))
+        return dict(zip(("tile_slow", "tile_fast", "tiles_slow", "tiles_fast", "piece"), (int(v) for v in out)))
 
     def shape(self) -> list:
         """mj_debug_plan_shape: what plan creation decided, in the order include/mijpeg.h documents."""

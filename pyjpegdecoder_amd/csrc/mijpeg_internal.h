@@ -455,6 +455,7 @@ void reduce_host(const uint8_t *src, const DevReduceImage &im, int ncomp, bool l
 // (luma: the instance that converts colour to L where it reads, mj_plan_request.mode with MJ_MODE_L)
 hipError_t launch_reduce(hipStream_t stream, const ReduceArgs &a, int ncomp, bool luma);
 int reduce_tile_fast(int out_ncomp);     // reduced pixels of a row a workgroup takes
+int reduce_piece(int src_ncomp);         // source pixels of a row a wavefront stages at a time (the instance's kPiece)
 // ---- affine.hip: the affine transform in front of the window and the resize (mj_plan_request.affine; tools/affine_model.py)
 // One output of a plan with an affine transform: the stored image it is made of (sw x sh pixels of the plan's intermediate
 // buffer, in the plan's layout), the oriented image's size w x h — what Pillow's rules count in —, the window of the transformed

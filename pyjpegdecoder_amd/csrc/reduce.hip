@@ -185,6 +185,9 @@ hipError_t launch_reduce(hipStream_t stream, const ReduceArgs &a, int ncomp, boo
 // the tile of a reducing plan's launch (resize_plan.hip: reduce_stage): a row of at most 64 * kReduceLaneElems reduced bytes
 int reduce_tile_fast(int out_ncomp) { return kReduceOutRow / out_ncomp; }
 
+// the source pixels of a row a wavefront stages at a time, k_reduce<CS, ...>'s kPiece (mj_debug_reduce_launch reports it)
+int reduce_piece(int src_ncomp) { return (kReduceStage - 16) / src_ncomp; }
+
 }  // namespace mj
 
 extern "C" {

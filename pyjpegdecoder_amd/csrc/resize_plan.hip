@@ -691,4 +691,13 @@ int mj_debug_reduce_shape(const mj_plan *p, int32_t image, int32_t out[7]) {
     return MJ_OK;
 }
 
+int mj_debug_reduce_launch(const mj_plan *p, int32_t out[5]) {
+    if (!p || !out || !p->resized || !p->reduces) return MJ_ERR_INVALID;
+    const mj::ReduceArgs &a = p->rd;
+    // (launch_reduce: colour to L reads three components, every other plan its own)
+    const int32_t v[5] = {a.tile_slow, a.tile_fast, a.tiles_slow, a.tiles_fast, mj::reduce_piece(p->rd_luma ? 3 : p->ncomp)};
+    for (int k = 0; k < 5; ++k) out[k] = v[k];
+    return MJ_OK;
+}
+
 }  // extern "C"

@@ -66,7 +66,8 @@ def assert_reduces(dec, raw, size, gap, factors, **kw):
 
 # (fixture, size, gap, factors): what each exercises is the issue's table — partial cells on both axes with rows that start at
 # every byte alignment (row pitch 210 bytes); a cell wider than a lane's 16 bytes; one axis untouched; the shift cases 2 x 2 and
-# 4 x 4; remainder 1; remainders 1 and 1; one component
+# 4 x 4; remainder 1; remainders 1 and 1; one component.  (Rows staged in pieces, several tiles under a phase, tile rows of 500 bytes
+# and more, the early return along the contiguous axis, the largest cell: tests/reduce_cases.py, test_reduce_paths_host.py, test_reduce_paths.py.)
 ROWS = (("70x50_420_pil_opt", (8, 7), 2.0, (4, 3)),
         ("128x64_420_dri3", (4, 4), 1.0, (32, 16)),
         ("100x36_420_dri7", (12, 18), 2.0, (4, 1)),
