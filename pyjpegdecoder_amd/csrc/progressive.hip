@@ -351,11 +351,15 @@ __global__ __launch_bounds__(256) void k_progressive_scan(const uint8_t *__restr
                     }
                 }
                 // only this scan's band is written back: other scans of the same dependency level may be updating
-                // other coefficients of the block at the same time
-                if (dirty && lane >= ss && lane <= se) p[nat] = (int16_t)cf;
+                // other coefficients of the block at the same time — and, behind the band, what a run that ends behind Se
+                // placed or corrected there (:1184-1225 stop at 63, not at Se; no conformant stream holds such a run)
+                if (dirty && ((lane >= ss && lane <= se) || (lane > se && cf != cf_cur))) p[nat] = (int16_t)cf;
             }
         }
         save_state(eobrun, 0, 0, 0);
+        // a refining scan's end-of-band run that reaches past the scan's last block: refused, as the reference does (:1259-1276
+        // index past the array; a first scan's `current_mcu += eob_run`, :1249, accepts the same run)
+        if (ac_refining && finish && !err && eobrun > 0 && sg->last) err = MJ_ST_OVERRUN;
     }
 
     if (!err && finish) {

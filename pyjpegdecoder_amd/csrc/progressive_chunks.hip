@@ -418,7 +418,9 @@ __global__ __launch_bounds__(256) void k_pc_place(const uint32_t *__restrict__ s
         if ((int)rd.pos > total_bits) err = MJ_ST_OVERRUN;
         else if (!sg.last && total_bits - (int)rd.pos >= 8) err = MJ_ST_DESYNC;
     }
-    if (!err && left < 0) err = MJ_ST_OVERRUN;               // an end-of-band run that reaches past the stretch: records and stream disagree
+    // an end-of-band run that reaches past the stretch: records and stream disagree — unless the stretch ends its segment: a run
+    // past the segment's last block is what the reference accepts (:1249, `current_mcu += eob_run`) and the other walks with it
+    if (!err && left < 0 && !v.last) err = MJ_ST_OVERRUN;
     if (err) atomicMax(status + sg.image, err);
 }
 

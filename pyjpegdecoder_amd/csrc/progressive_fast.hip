@@ -790,7 +790,13 @@ __device__ __forceinline__ void walk_ac_refine(Walk &k, Stream &st, const uint16
         }
         // only this scan's band is written back: other scans of the same dependency level may be updating other
         // coefficients of the block at the same time
-        if (dirty && in_band) *p = (int16_t)cf;
+        // ... and, behind the band, what a run that ends behind Se corrected or placed there (:1184-1225 stop at 63, not at Se; no
+        // conformant stream holds such a run).  Only the lanes this block changed, as in the general walk: the others may belong
+        // to a scan of the same dependency level.  One wave-uniform test per block and ONE store: a second store behind a test of
+        // its own cost 16 x 1080p 0.5 ms of 45 (profiles/prog_paths_fixes.txt)
+        bool wr = in_band;
+        if (__builtin_expect(kend > se + 1, 0)) wr = in_band || (lane > se && lane < kend && cf != cf0);
+        if (dirty && wr) *p = (int16_t)cf;
 #ifdef MJ_DIAGNOSTIC
         if (dbg_on) {
             if (dbg_eob) ++deob; else { ++dblocks; dplaced += __builtin_popcountll(__ballot(cf != 0 && lane >= ss) & ~nzb); }
@@ -942,6 +948,9 @@ __global__ __launch_bounds__(256) void k_progressive_fast(const uint32_t *__rest
         ps->err = err; ps->mcu_next = b_hi;
     }
     if (!err && finish) err = st.end_status(k.sg->last != 0);      // (a split scan's scout reads every bit the parts read)
+    // a refining scan's end-of-band run that reaches past the scan's last block: refused, as the reference does (:1259-1276 index
+    // past the array; a first scan's `current_mcu += eob_run`, :1249, accepts the same run).  (A split scan's scout carries the run.)
+    if (!err && finish && sc->ah != 0 && k.eobrun > 0 && k.sg->last != 0) err = MJ_ST_OVERRUN;
     if (err && lane == 0) atomicMax(status + sc->image, err);
 }
 

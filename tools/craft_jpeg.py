@@ -408,6 +408,137 @@ def craft_progressive(width: int, height: int, factors, seed: int = 0, script=No
     return bytes(out)
 
 
+Y420 = ((2, 2), (1, 1), (1, 1))
+CRAFTED_PROGRESSIVE = [   # the files of tests/golden/crafted_progressive.npz (tools/make_layout_goldens.py; seed 200 + position)
+    # name, arguments of craft_progressive
+    ("default_420_dri3", dict(width=50, height=37, factors=Y420, restart_interval=3)),
+    ("dc_y_cb_then_cr", dict(width=50, height=37, factors=Y420,            # interleaved DC scan over a SUBSET of the components
+                             script=[((0, 1), 0, 0, 0, 0), ((2,), 0, 0, 0, 0), ((0,), 1, 63, 0, 0), ((1,), 1, 63, 0, 0), ((2,), 1, 63, 0, 0)])),
+    ("dc_y_cr_refined", dict(width=41, height=33, factors=((2, 1), (1, 1), (1, 1)),   # ... refined through the same subsets
+                             script=[((0, 2), 0, 0, 0, 2), ((1,), 0, 0, 0, 1), ((0,), 1, 63, 0, 1), ((0, 2), 0, 0, 2, 1), ((1,), 1, 63, 0, 0),
+                                     ((2,), 1, 20, 0, 0), ((0, 2), 0, 0, 1, 0), ((1,), 0, 0, 1, 0), ((0,), 1, 63, 1, 0), ((2,), 21, 63, 0, 0)])),
+    ("bands_444_two_levels", dict(width=33, height=21, factors=((1, 1), (1, 1), (1, 1)), new_density=0.15,
+                                  script=[((0, 1, 2), 0, 0, 0, 0), ((0,), 1, 9, 0, 2), ((0,), 10, 40, 0, 2), ((0,), 41, 63, 0, 2), ((1,), 1, 63, 0, 2),
+                                          ((2,), 1, 63, 0, 2), ((0,), 1, 63, 2, 1), ((1,), 1, 63, 2, 1), ((2,), 1, 63, 2, 1), ((0,), 1, 30, 1, 0),
+                                          ((0,), 31, 63, 1, 0), ((1,), 1, 63, 1, 0), ((2,), 1, 63, 1, 0)])),
+    ("grey_sparse_long_eob_runs", dict(width=120, height=64, factors=((1, 1),), empty_block=0.9, density=0.05)),
+    ("y4x2", dict(width=70, height=40, factors=((4, 2), (1, 1), (1, 1)))),              # 4:1:0
+    ("y1x1_c2x2", dict(width=40, height=40, factors=((1, 1), (2, 2), (2, 2)))),
+    ("y3x1_dri", dict(width=50, height=20, factors=((3, 1), (1, 1), (1, 1)), restart_interval=2)),
+    ("y2x4", dict(width=30, height=70, factors=((2, 4), (1, 1), (1, 1)))),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Progressive files from an explicit description (tests/prog_cases.py): nothing is drawn, nothing is checked — every scan is
+# the list of stream items its author wants, so symbols no conformant encoder writes (a run that ends behind the band, a
+# size of 10 in a refining scan, a bit pattern without a code) can be written as easily as the usual ones.
+
+def huffman_table(lengths):
+    """(bits, vals) of the canonical table in which symbol s has a code of lengths[s] bits (symbols of one length in the
+    order given).  The lengths may leave codes unused (Kraft sum below one): then some bit patterns match no code."""
+    order = sorted(lengths.items(), key=lambda kv: kv[1])           # (stable: the given order within one length)
+    counts = [0] * 17
+    for _, l in order:
+        assert 1 <= l <= 16
+        counts[l] += 1
+    assert sum(c << (16 - l) for l, c in enumerate(counts) if l) < (1 << 16), "the code lengths leave no pattern unused"
+    return bytes(counts[1:]), bytes(s for s, _ in order)
+
+
+def long_ac_table(variant: int = 0):
+    """An AC table for progressive scans whose code lengths include 11, 12, 15 and 16 bits and whose symbols reach size 15.
+    variant 0: the usual symbols ((run, 1), EOB0, ZRL, small EOBn) short, the large sizes and the long end-of-band runs long —
+      0x31 11 bits, 0x41 / 0x0B / 0x12 12 bits, 0x51 / 0x0C / 0x0D 15 bits, 0x61 / 0x0E / 0x0F / 0xE0 16 bits;
+    variant 1: ZRL, EOB0 and the end-of-band runs behind the 11-bit table (ZRL 12 bits, EOB0 13, EOB1 15, EOB2 16) and
+      (0, 1) at 11 bits exactly;
+    variant 2: ZRL at 16 bits, (0, 1) at 16 bits, EOB0 at 15.
+    Every variant leaves the all-ones pattern (and more) without a code."""
+    if variant == 0:
+        L = {0x00: 3, 0x01: 3, 0x11: 4, 0xF0: 4, 0x02: 5, 0x10: 5, 0x21: 5, 0x0A: 6, 0x20: 6, 0x03: 6, 0x30: 7, 0x71: 7, 0xF1: 7,
+             0x22: 7, 0x40: 8, 0x04: 8, 0x50: 8, 0x91: 8, 0xE1: 8, 0x60: 9, 0x70: 9, 0x05: 9, 0xA1: 9, 0x80: 10, 0x90: 10, 0x06: 10,
+             0x81: 10, 0x31: 11, 0xA0: 11, 0x07: 11, 0x41: 12, 0x0B: 12, 0x12: 12, 0xB0: 12, 0x08: 13, 0xC0: 13, 0x09: 14, 0xD0: 14,
+             0x51: 15, 0x0C: 15, 0x0D: 15, 0x1A: 15, 0x61: 16, 0x0E: 16, 0x0F: 16, 0xE0: 16, 0xF2: 16}
+    elif variant == 1:
+        L = {0x11: 2, 0x21: 3, 0x02: 4, 0x31: 4, 0x41: 5, 0x03: 6, 0x51: 6, 0x61: 7, 0x71: 8, 0x81: 9, 0x91: 10, 0x01: 11, 0xA1: 11,
+             0xF0: 12, 0xB1: 12, 0x00: 13, 0x30: 13, 0x10: 15, 0xC1: 15, 0x20: 16, 0xE0: 16, 0xD1: 16}
+    else:
+        L = {0x11: 2, 0x21: 3, 0x02: 4, 0x10: 4, 0x31: 5, 0x20: 6, 0x41: 7, 0x51: 12, 0x00: 15, 0x01: 16, 0xF0: 16, 0xF1: 16}
+    return huffman_table(L)
+
+
+def long_dc_table():
+    """A DC table holding the sizes 0..16 (the reference takes whatever size a symbol names, :1017) with codes of 2..16 bits:
+    sizes 0..9 inside a 9-bit table, size 10 at 10 bits, 11 at 11, 12 at 12, 13 at 13, 14 at 14, 15 at 15, 16 at 16."""
+    L = {0: 2, 1: 3, 2: 3, 3: 4, 4: 4, 5: 5, 6: 6, 7: 7, 8: 8, 9: 9, 10: 10, 11: 11, 12: 12, 13: 13, 14: 14, 15: 15, 16: 16}
+    return huffman_table(L)
+
+
+def craft_progressive_symbols(width: int, height: int, factors, scans, dc_tables=None, ac_tables=None, restart_interval: int = 0) -> bytes:
+    """A progressive file of `width` x `height`, `factors` = ((h, v), ...) per component (1 or 3), written item by item.
+    `dc_tables` / `ac_tables` = up to four (bits, vals) each (default: the Annex-K luma and chroma ones), sent once in front
+    of the first scan.  `scans` = a list of (components, Ss, Se, Ah, Al, tables, items): `tables` = per scan component the
+    (DC table, AC table) indices; `items` = what the scan's entropy-coded segment holds, in order:
+      ("dc", i, size[, bits])  the code of `size` in the DC table of the scan's i-th component, then the low `size` bits of `bits`
+      ("ac", rs[, bits])       the code of symbol rs = run << 4 | size in the scan's AC table, then the low n bits of `bits`:
+                               n = size, or for size 0 and run < 15 (an end-of-band run of (1 << run) + bits blocks) n = run
+      ("bits", value, n)       n raw bits: correction bits, the bits of a refining DC scan, anything else
+      ("rst",)                 pad to a byte with ones and write the next restart marker
+    The last byte of every scan is padded with ones.  A symbol without a code in its table is an error here."""
+    factors = [tuple(f) for f in factors]
+    ncomp = len(factors)
+    assert ncomp in (1, 3)
+    dc_tables = list(dc_tables or [(_T["STD_DC_LUMA_BITS"], _T["STD_DC_LUMA_VALS"]), (_T["STD_DC_CHROMA_BITS"], _T["STD_DC_CHROMA_VALS"])])
+    ac_tables = list(ac_tables or [(_T["STD_AC_LUMA_BITS"], _T["STD_AC_LUMA_VALS"]), (_T["STD_AC_CHROMA_BITS"], _T["STD_AC_CHROMA_VALS"])])
+    assert len(dc_tables) <= 4 and len(ac_tables) <= 4
+    dc_codes = [_codes(bytes(b), bytes(v)) for b, v in dc_tables]
+    ac_codes = [_codes(bytes(b), bytes(v)) for b, v in ac_tables]
+    out = bytearray(b"\xFF\xD8")
+    out += _seg(0xDB, b"\x00" + _T["STD_QT_LUMA_ZZ"])
+    out += _seg(0xDB, b"\x01" + _T["STD_QT_CHROMA_ZZ"])
+    sof = bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big") + bytes([ncomp])
+    for c, (h, v) in enumerate(factors):
+        sof += bytes([c + 1, (h << 4) | v, 0 if c == 0 else 1])
+    out += _seg(0xC2, sof)
+    for t, (b, v) in enumerate(dc_tables):
+        out += _seg(0xC4, bytes([t]) + bytes(b) + bytes(v))
+    for t, (b, v) in enumerate(ac_tables):
+        out += _seg(0xC4, bytes([0x10 | t]) + bytes(b) + bytes(v))
+    if restart_interval:
+        out += _seg(0xDD, restart_interval.to_bytes(2, "big"))
+    for comps, ss, se, ah, al, tables, items in scans:
+        tables = [tuple(t) for t in tables]
+        assert len(tables) == len(comps)
+        sos = bytes([len(comps)]) + b"".join(bytes([c + 1, (d << 4) | a]) for c, (d, a) in zip(comps, tables))
+        out += _seg(0xDA, sos + bytes([ss, se, (ah << 4) | al]))
+        w = _Bits()
+        rst = 0
+        for it in items:
+            if it[0] == "dc":
+                size = it[2]
+                w.put(*dc_codes[tables[it[1]][0]][size])
+                if size:
+                    w.put(it[3], size)
+            elif it[0] == "ac":
+                rs = it[1]
+                w.put(*ac_codes[tables[0][1]][rs])
+                n = (rs & 15) or (rs >> 4 if rs >> 4 < 15 else 0)
+                if n:
+                    w.put(it[2], n)
+            elif it[0] == "bits":
+                if it[2]:
+                    w.put(it[1], it[2])
+            else:
+                assert it[0] == "rst"
+                w.flush()
+                w.out += bytes([0xFF, 0xD0 + (rst & 7)])
+                rst += 1
+        w.flush()
+        out += w.out
+    out += b"\xFF\xD9"
+    return bytes(out)
+
+
 # ---- random files of both kinds (tests, tools/stress_crafted.py, tools/crosscheck_reference.py --crafted) ----------------
 def random_baseline(rng, seed: int) -> bytes:
     """Any factors 1..4 per component (at most 16 blocks per MCU), 1..119 pixels a side, with and without restart intervals."""
