@@ -526,6 +526,15 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
 int mj_debug_count_tables(const mj_huff_spec *huff, int32_t n_huff, const int32_t *roles, int32_t wbits, uint32_t *out, int64_t cap_words,
                           int32_t *tab_bytes);
 
+/* Test hook, host only: the resolved AC tables of the lane walk (csrc/lanes13_walk.h) as mj_plan_create builds them for a batch with
+ * these n_huff <= 8 tables — roles[t] 2 = AC table, anything else: not built; slot_of_table[t] = the slot (0 .. n_ac - 1) of AC table t;
+ * ab_of_slot[s] = 10..13 index bits of slot s.  fixed_slot_bytes: the stride from one slot to the next (the stage-1 kernel's), or 0: back
+ * to back, each as small as its codes allow (a fused launch's).  slot_off[s] = byte offset of slot s, *total_bytes = bytes in all; out
+ * (may be NULL) receives total_bytes / 4 words.  MJ_ERR_UNSUPPORTED: does not fit (more second-level tables than a slot holds). */
+int mj_debug_resolved_tables(const mj_huff_spec *huff, int32_t n_huff, const int32_t *roles, const int32_t *slot_of_table, int32_t n_ac,
+                             const int32_t ab_of_slot[4], int32_t fixed_slot_bytes, uint32_t *out, int64_t cap_words, int32_t slot_off[4],
+                             int32_t *total_bytes);
+
 /* Test hook, host only: how a fused launch (MJ_FORM_FUSED) would be cut for a batch of n_images images of segments_per_image
  * restart segments on a chip of `cus` CUs — out = { applies (LDS), images per workgroup and pass, producer wavefronts, lanes per
  * producer, consumer wavefronts beside them, bytes of LDS the producers take, passes per workgroup, workgroups }. */

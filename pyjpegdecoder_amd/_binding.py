@@ -47,7 +47,7 @@ EXPORTS = (
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
     "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine", "mj_debug_reduce_launch",
-    "mj_debug_plan_shape", "mj_debug_cache_stats",
+    "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -293,6 +293,40 @@ def count_tables(huff_specs, roles, wbits=12):
     if rc != MJ_OK:
         raise ValueError("mj_debug_count_tables: bad arguments")
     return out, tb.value
+
+
+def resolved_tables(huff_specs, roles, slots, index_bits, fixed_slot_bytes=0):
+    """mj_debug_resolved_tables (host only): (words, slot offsets in bytes) — the lane walk's resolved AC tables for these tables
+    (list of (bits[16], vals) pairs; roles: 2 = AC; slots[t] = the slot of AC table t; index_bits per slot, 10..13), `fixed_slot_bytes`
+    apart or (0) packed back to back — or None where they do not fit."""
+    L = load_library()
+    n = len(huff_specs)
+    arr = (HuffSpecC * n)()
+    for i, (bits, vals) in enumerate(huff_specs):
+        for j in range(16):
+            arr[i].bits[j] = int(bits[j])
+        for j, v in enumerate(vals):
+            arr[i].vals[j] = int(v)
+    n_ac = max(s for s, r in zip(slots, roles) if r == 2) + 1
+    r = (ctypes.c_int32 * n)(*[int(x) for x in roles])
+    sl = (ctypes.c_int32 * n)(*[int(x) for x in slots])
+    ab = (ctypes.c_int32 * 4)(*(list(index_bits) + [13] * 4)[:4])
+    off = (ctypes.c_int32 * 4)()
+    total = ctypes.c_int32(0)
+    L.mj_debug_resolved_tables.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                           ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]
+    rc = L.mj_debug_resolved_tables(ctypes.byref(arr), n, ctypes.byref(r), ctypes.byref(sl), n_ac, ctypes.byref(ab), fixed_slot_bytes, None, 0,
+                                    ctypes.byref(off), ctypes.byref(total))
+    if rc == MJ_ERR_UNSUPPORTED:
+        return None
+    if rc != MJ_OK:
+        raise ValueError("mj_debug_resolved_tables: bad arguments")
+    out = np.zeros(total.value // 4, dtype=np.uint32)
+    rc = L.mj_debug_resolved_tables(ctypes.byref(arr), n, ctypes.byref(r), ctypes.byref(sl), n_ac, ctypes.byref(ab), fixed_slot_bytes, _ptr(out),
+                                    out.size, ctypes.byref(off), ctypes.byref(total))
+    if rc != MJ_OK:
+        raise ValueError("mj_debug_resolved_tables: bad arguments")
+    return out, [int(off[s]) for s in range(n_ac)]
 
 
 def fused_shape_rule(n_images, segments_per_image, hmax=2, vmax=2, transposed=False, cus=256, n_ac=2, n_dc=2, ac_slot_bytes=17024,

@@ -219,4 +219,36 @@ int mj_debug_count_tables(const mj_huff_spec *huff, int32_t n_huff, const int32_
     return MJ_OK;
 }
 
+int mj_debug_resolved_tables(const mj_huff_spec *huff, int32_t n_huff, const int32_t *roles, const int32_t *slot_of_table, int32_t n_ac,
+                             const int32_t ab_of_slot[4], int32_t fixed_slot_bytes, uint32_t *out, int64_t cap_words, int32_t slot_off[4],
+                             int32_t *total_bytes) {
+    if (!huff || !roles || !slot_of_table || !ab_of_slot || !slot_off || !total_bytes || n_huff < 1 || n_huff > 8 || n_ac < 1 || n_ac > 4 ||
+        fixed_slot_bytes < 0 || fixed_slot_bytes % 16)
+        return MJ_ERR_INVALID;
+    uint64_t ac_pk = 0;
+    int ab[4];
+    for (int s = 0; s < 4; ++s) {
+        ab[s] = ab_of_slot[s];
+        if (ab[s] < 10 || ab[s] > 13 || (fixed_slot_bytes && fixed_slot_bytes / 4 < (1 << ab[s]) + (1 << (16 - ab[s])))) return MJ_ERR_INVALID;
+    }
+    for (int t = 0; t < n_huff; ++t) {
+        if (roles[t] != 2) continue;
+        if (slot_of_table[t] < 0 || slot_of_table[t] >= n_ac) return MJ_ERR_INVALID;
+        ac_pk |= (uint64_t)slot_of_table[t] << (8 * t);
+    }
+    mj_batch b{};
+    b.n_huff = n_huff; b.huff = huff;
+    std::vector<int> role(roles, roles + n_huff);
+    std::vector<uint32_t> t;
+    int off[4] = {0, 0, 0, 0}, total = 0;
+    if (!mj::build_resolved_tables(&b, role, ac_pk, n_ac, ab, fixed_slot_bytes, t, off, total)) return MJ_ERR_UNSUPPORTED;
+    *total_bytes = total;
+    for (int s = 0; s < 4; ++s) slot_off[s] = off[s];
+    if (out) {
+        if ((int64_t)t.size() > cap_words) return MJ_ERR_INVALID;
+        memcpy(out, t.data(), t.size() * 4);
+    }
+    return MJ_OK;
+}
+
 }  // extern "C"

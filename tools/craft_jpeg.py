@@ -539,6 +539,94 @@ def craft_progressive_symbols(width: int, height: int, factors, scans, dc_tables
     return bytes(out)
 
 
+def craft_baseline_symbols(width: int, height: int, factors, mcus, dc_tables=None, ac_tables=None, tables=None,
+                           restart_interval: int = 0, qts=None) -> bytes:
+    """The baseline twin of craft_progressive_symbols: a file of `width` x `height` with one interleaved scan, `factors` =
+    ((h, v), ...) per component (1 or 3), written item by item; nothing is drawn and nothing is checked.  `dc_tables` /
+    `ac_tables` = up to four (bits, vals) each (default: the Annex-K luma and chroma ones); `tables` = per component the (DC
+    table, AC table) indices (default: table 0 for the first component, 1 for the others); `qts` as in craft_baseline.
+    `mcus` = what the entropy-coded segment holds, in order — the caller writes every MCU and every restart marker:
+      [block, ...]             one MCU: a list of blocks in the scan's order (the component of a block follows from its place),
+                               each block a list of
+          ("dc", size[, bits])       the code of `size` in the block's DC table, then the low `size` bits of `bits`
+          ("ac", run, size[, bits])  the code of run << 4 | size in its AC table, then the low `size` bits of `bits`;
+                                     bits = None: the value bits are NOT written (what follows a run past index 63)
+          ("bits", value, n)         n raw bits
+      ("rst",) / ("rst", extra)  pad to a byte with ones, write `extra` (spare bytes, default none) and the next restart marker
+      ("bytes", b)               pad to a byte with ones and write the bytes b as they are
+      ("cut", n)                 pad to a byte with ones and drop the last n bytes written (a truncated segment)
+    The last byte is padded with ones.  A symbol without a code in its table is an error here."""
+    factors = [tuple(f) for f in factors]
+    ncomp = len(factors)
+    assert ncomp in (1, 3)
+    dc_tables = list(dc_tables or [(_T["STD_DC_LUMA_BITS"], _T["STD_DC_LUMA_VALS"]), (_T["STD_DC_CHROMA_BITS"], _T["STD_DC_CHROMA_VALS"])])
+    ac_tables = list(ac_tables or [(_T["STD_AC_LUMA_BITS"], _T["STD_AC_LUMA_VALS"]), (_T["STD_AC_CHROMA_BITS"], _T["STD_AC_CHROMA_VALS"])])
+    assert len(dc_tables) <= 4 and len(ac_tables) <= 4
+    if tables is None:
+        tables = [(0, 0) if c == 0 else (1, 1) for c in range(ncomp)]
+    tables = [tuple(t) for t in tables]
+    dc_codes = [_codes(bytes(b), bytes(v)) for b, v in dc_tables]
+    ac_codes = [_codes(bytes(b), bytes(v)) for b, v in ac_tables]
+    out = bytearray(b"\xFF\xD8")
+    qt_bytes = [_T["STD_QT_LUMA_ZZ"], _T["STD_QT_CHROMA_ZZ"]]
+    for t, q in enumerate(qts or []):
+        q = [int(v) for v in np.asarray(q).reshape(-1)]
+        assert t < 2 and len(q) == 64 and all(1 <= v <= 255 for v in q), "a quantisation table is 64 zig-zag entries 1..255"
+        qt_bytes[t] = bytes(q)
+    out += _seg(0xDB, b"\x00" + qt_bytes[0])
+    out += _seg(0xDB, b"\x01" + qt_bytes[1])
+    sof = bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big") + bytes([ncomp])
+    for c, (h, v) in enumerate(factors):
+        sof += bytes([c + 1, (h << 4) | v, 0 if c == 0 else 1])
+    out += _seg(0xC0, sof)
+    for t in range(4):                                             # (the order craft_baseline writes them in)
+        if t in {d for d, _ in tables}:
+            out += _seg(0xC4, bytes([t]) + bytes(dc_tables[t][0]) + bytes(dc_tables[t][1]))
+        if t in {a for _, a in tables}:
+            out += _seg(0xC4, bytes([0x10 | t]) + bytes(ac_tables[t][0]) + bytes(ac_tables[t][1]))
+    if restart_interval:
+        out += _seg(0xDD, restart_interval.to_bytes(2, "big"))
+    sos = bytes([ncomp])
+    for c in range(ncomp):
+        sos += bytes([c + 1, (tables[c][0] << 4) | tables[c][1]])
+    out += _seg(0xDA, sos + bytes([0, 63, 0]))
+    comp_of_block = [c for c, (h, v) in enumerate(factors) for _ in range(h * v if ncomp > 1 else 1)]
+    w = _Bits()
+    rst = 0
+    for unit in mcus:
+        if isinstance(unit, tuple):
+            w.flush()
+            if unit[0] == "rst":
+                w.out += bytes(unit[1]) if len(unit) > 1 else b""
+                w.out += bytes([0xFF, 0xD0 + (rst & 7)])
+                rst += 1
+            elif unit[0] == "bytes":
+                w.out += bytes(unit[1])
+            else:
+                assert unit[0] == "cut"
+                del w.out[len(w.out) - unit[1]:]
+            continue
+        assert len(unit) == len(comp_of_block), f"an MCU of this layout has {len(comp_of_block)} blocks, not {len(unit)}"
+        for c, block in zip(comp_of_block, unit):
+            for it in block:
+                if it[0] == "dc":
+                    w.put(*dc_codes[tables[c][0]][it[1]])
+                    if it[1]:
+                        w.put(it[2], it[1])
+                elif it[0] == "ac":
+                    w.put(*ac_codes[tables[c][1]][(it[1] << 4) | it[2]])
+                    if it[2] and (len(it) < 4 or it[3] is not None):
+                        w.put(it[3] if len(it) > 3 else 0, it[2])
+                else:
+                    assert it[0] == "bits"
+                    if it[2]:
+                        w.put(it[1], it[2])
+    w.flush()
+    out += w.out
+    out += b"\xFF\xD9"
+    return bytes(out)
+
+
 # ---- random files of both kinds (tests, tools/stress_crafted.py, tools/crosscheck_reference.py --crafted) ----------------
 def random_baseline(rng, seed: int) -> bytes:
     """Any factors 1..4 per component (at most 16 blocks per MCU), 1..119 pixels a side, with and without restart intervals."""
