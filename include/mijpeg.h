@@ -194,9 +194,10 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  * request with views, the per-output ones — slots, output->mirror, places — with n_views), read during the call only.
  *
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
- * affine transform -> window -> resize with the filter (to the place's size, onto the canvas) -> mirror -> the output's element
- * type.  In Pillow's terms the result is exif_transpose(img.convert(mode))[.transform(img.size, AFFINE, a, resample, fillcolor)]
- * .crop(window).resize(size, filter) — with reducing_gap, Pillow's argument of that name to that resize.
+ * affine transform -> window -> resize with the filter (to the place's size, onto the canvas) -> colour operations
+ * (MJ_MODE_COLOUR_OPS, below the request) -> mirror -> the output's element type.  In Pillow's terms the result is
+ * exif_transpose(img.convert(mode))[.transform(img.size, AFFINE, a, resample, fillcolor)].crop(window).resize(size, filter) —
+ * with reducing_gap, Pillow's argument of that name to that resize.
  *
  * Refusals common to all fields: MJ_ERR_INVALID with a message in mj_last_error — naming the image where there is one — for a
  * value outside what the field takes; MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT together with ANY field that changes the plan
@@ -451,6 +452,76 @@ typedef struct {
     const mj_view *views;
     const mj_affine *affine;
 } mj_plan_affine_request;
+/* Colour operations on the finished canvas (mj_plan_request.mode with MJ_MODE_COLOUR_OPS or-ed in; tools/colour_model.py): what
+ * one call of Pillow's ImageEnhance.* / ImageOps.* does to the bytes, bit for bit — the colour half of ColorJitter, RandAugment,
+ * AutoAugment and TrivialAugment.  The flag is one more bit of `mode` (the mode itself is the low byte; a caller who never sets the
+ * bit is unaffected), it needs a size, and the request is then the `head.request` of a mj_plan_colour_request — declared below —
+ * whose `colour` holds one chain per OUTPUT (n_views entries in a request with views, else n_images).  The order of operations
+ * becomes decode -> mode -> orientation -> affine -> window -> resize / place / fill -> COLOUR OPS -> mirror -> element type:
+ *   let C_k be the uint8 canvas of output k that the same request gives without the flag, without output->mirror and with
+ *   MJ_DTYPE_U8, fill pixels included.  Output k is chain k applied to C_k as a Pillow image of the output's components ("RGB" or
+ *   "L"), op after op, then mirrored if mirror[k] and passed through the output table — in all four layouts.
+ * An output whose chain is empty (n == 0) is the output of the request without the flag; a request whose chains are ALL empty is
+ * that request (mj_debug_normalise_request clears the flag), with no extra launch and no extra buffer.  The rules, restated
+ * (v: a byte of the canvas; every float32 / double operation rounded on its own):
+ *   blend(d, v, f)         Image.blend: alpha = (float)f, t = (float)d + alpha * (float)(v - d) with v - d an int; for 0 <= alpha <= 1
+ *                          the byte (uint8)t, else 0 where t <= 0, 255 where t >= 255, else (uint8)t
+ *   MJ_COLOUR_BRIGHTNESS   blend(0, v, value)
+ *   MJ_COLOUR_COLOR        blend(L, v, value) in all three components, L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the pixel;
+ *                          the identity on a one-component output
+ *   MJ_COLOUR_CONTRAST     blend(m, v, value) in every component, m = (int)(sum of i * hist_L[i] / n + 0.5) in doubles, hist_L the
+ *                          histogram of the canvas's L (of the canvas itself for one component), n its pixels
+ *   MJ_COLOUR_SHARPNESS    blend(s, v, value), s = ImageFilter.SMOOTH per component: k = (float)(e / 13.0) for e in (1,1,1, 1,5,1,
+ *                          1,1,1); ss = 0.5f, then ss += row(y + 1), row(y), row(y - 1) with row(r) = (p[x-1] k0 + p[x] k1) + p[x+1] k2
+ *                          of that row's kernel entries; s = 0 where ss <= 0, 255 where ss >= 255, else (uint8)ss; pixels of the
+ *                          first and last row and column are copied (a canvas with a side below 3 is unchanged)
+ *   MJ_COLOUR_POSTERIZE    v & ~(2^(8 - value) - 1), value 1..8
+ *   MJ_COLOUR_SOLARIZE     v where v < t, else 255 - v; t = min(max(ceil(value), 0), 256)
+ *   MJ_COLOUR_INVERT       255 - v
+ *   MJ_COLOUR_AUTOCONTRAST per component (cutoff 0, no mask): lo, hi the first and last non-empty bins; hi <= lo: the identity; else
+ *                          scale = 255.0 / (hi - lo), offset = -lo * scale, v -> clip((int)(v * scale + offset), 0, 255) in doubles
+ *   MJ_COLOUR_EQUALIZE     per component with histogram h (no mask): one non-empty bin, or step = (pixels - the last non-empty bin's
+ *                          count) / 255 == 0: the identity; else n = step / 2 and for i = 0..255: i -> min(255, n / step), n += h[i]
+ * The launches (csrc/colour.hip): the plan's resize launch runs exactly as that of the MJ_DTYPE_U8, unmirrored, identity-slot
+ * request would, into a plan-owned canvas buffer in the plan's layout.  Then, for every step s of the longest chain: a histogram
+ * launch over the outputs whose op s is contrast, autocontrast or equalize (32-bit bins: LDS atomics, merged into a zeroed
+ * per-output array); a launch of one wavefront per output that builds the 3 x 256 byte table of every table-shaped op, from the
+ * statistics where it has some — they never leave the device, nothing synchronises —; and one launch that applies step s to
+ * every output (a table look-up, color, sharpness, or a copy where the chain has ended) from one canvas into a second, the last
+ * step into the caller's array at the output's slot, mirrored if flagged, through the output table.  mj_plan_time_resize times
+ * these launches too.  mj_host_colour_ops is the host twin.
+ * MJ_ERR_INVALID, naming the output: the flag without a size ("colour_ops needs a size"), a NULL array, n outside 0..4, a kind that
+ * is none of MJ_COLOUR_*, a value that is not finite, posterize bits that are not one of 1..8.  Not offered yet: hue (Pillow's HSV
+ * round trip), autocontrast's cutoffs and masks, more than MJ_COLOUR_MAX_OPS ops. */
+#define MJ_MODE_COLOUR_OPS 0x100
+#define MJ_COLOUR_MAX_OPS 4
+#define MJ_COLOUR_BRIGHTNESS   1
+#define MJ_COLOUR_COLOR        2
+#define MJ_COLOUR_CONTRAST     3
+#define MJ_COLOUR_SHARPNESS    4
+#define MJ_COLOUR_POSTERIZE    5
+#define MJ_COLOUR_SOLARIZE     6
+#define MJ_COLOUR_AUTOCONTRAST 7
+#define MJ_COLOUR_EQUALIZE     8
+#define MJ_COLOUR_INVERT       9
+typedef struct {
+    int32_t kind;               /* MJ_COLOUR_* */
+    float value;                /* the factor, bits or threshold; ignored by autocontrast, equalize and invert */
+} mj_colour_op;
+typedef struct {
+    int32_t n;                  /* 0..MJ_COLOUR_MAX_OPS ops, applied in order */
+    mj_colour_op op[MJ_COLOUR_MAX_OPS];
+} mj_colour_chain;
+/* A request with colour operations (request.mode & MJ_MODE_COLOUR_OPS): its head is a mj_plan_affine_request — `views` and
+ * `affine` are read where their fields say so —, and `colour` holds one chain per output.  Zeroed, it is the zeroed request. */
+typedef struct {
+    mj_plan_affine_request head;
+    const mj_colour_chain *colour;
+} mj_plan_colour_request;
+/* The host twin of the colour launches (no context): src is a row-major w x h image of ncomp (1 or 3) interleaved components, out
+ * receives the chain applied to it (w * h * ncomp bytes; out may be src).  MJ_ERR_INVALID: what the flag refuses of a chain, a size
+ * below 1, ncomp neither 1 nor 3, NULL. */
+int mj_host_colour_ops(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, const mj_colour_chain *chain, uint8_t *out);
 /* request NULL: a zeroed request. */
 int mj_plan_create_with(mj_context *ctx, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
 /* The plain plan: exactly mj_plan_create_with(ctx, batch, NULL, out). */
@@ -630,6 +701,11 @@ int mj_plan_time_resize(mj_plan *plan, int iters, uint8_t *rgb_device, float *ms
 /* A plan's affine launch alone (mj_plan_request.affine; after an execute): ms per launch, and the bytes it writes (it reads, at
  * most, mj_plan_time_resize's source_bytes).  MJ_ERR_INVALID: not a plan with an affine transform. */
 int mj_plan_time_affine(mj_plan *plan, int iters, float *ms, int64_t *written_bytes);
+/* The colour launches of a plan with colour operations alone (MJ_MODE_COLOUR_OPS; after an execute: they read the canvases the
+ * resize launch left), `iters` times into where the latest execute wrote: ms per run of all of them — the histogram, table and
+ * apply launches of every step —, and the bytes of one set of canvases (outputs x out_width x out_height x components).
+ * MJ_ERR_INVALID: not a plan with colour operations, nothing executed yet. */
+int mj_plan_time_colour(mj_plan *plan, int iters, float *ms, int64_t *canvas_bytes);
 /* A reducing plan's reduce launch alone (mj_plan_request.reducing_gap; after an execute): ms per launch.  It reads the decoded
  * pixels (mj_plan_time_resize's source_bytes) and writes the reduced images.  MJ_ERR_INVALID: not a reducing plan. */
 int mj_plan_time_reduce(mj_plan *plan, int iters, float *ms);

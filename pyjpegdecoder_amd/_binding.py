@@ -32,6 +32,12 @@ FILTERS = {"bilinear": MJ_FILTER_BILINEAR, "box": MJ_FILTER_BOX, "hamming": MJ_F
            "lanczos": MJ_FILTER_LANCZOS}
 
 MJ_MODE_NATIVE, MJ_MODE_L, MJ_MODE_RGB = 0, 1, 3
+# colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): the ops by name (tools/colour_model.py: OPS), MJ_COLOUR_*
+MJ_MODE_COLOUR_OPS = 0x100
+MJ_COLOUR_MAX_OPS = 4
+COLOUR_OPS = {"brightness": 1, "color": 2, "contrast": 3, "sharpness": 4, "posterize": 5, "solarize": 6, "autocontrast": 7,
+              "equalize": 8, "invert": 9}
+COLOUR_VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize")        # the ops that take a value
 # the output colour modes by Pillow's name: MJ_MODE_*, which is the component count of the output
 MODES = {"L": MJ_MODE_L, "RGB": MJ_MODE_RGB}
 
@@ -46,7 +52,7 @@ EXPORTS = (
     "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table", "mj_host_normalize_table", "mj_host_exif_orientations",
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
-    "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine", "mj_debug_reduce_launch",
+    "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine", "mj_debug_reduce_launch", "mj_host_colour_ops", "mj_plan_time_colour",
     "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
@@ -171,6 +177,36 @@ class PlanAffineRequestC(ctypes.Structure):
     _fields_ = [("request", PlanRequestC), ("views", ctypes.POINTER(ViewC)), ("affine", ctypes.POINTER(AffineC))]
 
 
+class ColourOpC(ctypes.Structure):
+    """mj_colour_op: one colour operation — MJ_COLOUR_* and its factor, bits or threshold."""
+    _fields_ = [("kind", ctypes.c_int32), ("value", ctypes.c_float)]
+
+
+class ColourChainC(ctypes.Structure):
+    """mj_colour_chain: one output's ops, applied in order (n == 0: none)."""
+    _fields_ = [("n", ctypes.c_int32), ("op", ColourOpC * MJ_COLOUR_MAX_OPS)]
+
+
+class PlanColourRequestC(ctypes.Structure):
+    """mj_plan_colour_request: a request with colour operations — a request with an affine transform's layout, and behind it one
+    chain per output."""
+    _fields_ = [("head", PlanAffineRequestC), ("colour", ctypes.POINTER(ColourChainC))]
+
+
+def colour_chain(chain) -> ColourChainC:
+    """mj_colour_chain from None or a sequence of at most MJ_COLOUR_MAX_OPS ops ``(name,)`` / ``(name, value)`` (an MJ_COLOUR_* number
+    passes for the name)."""
+    c = ColourChainC()
+    ops = list(chain) if chain is not None else []
+    if len(ops) > MJ_COLOUR_MAX_OPS:
+        raise ValueError(f"a chain has at most {MJ_COLOUR_MAX_OPS} ops, not {len(ops)}")
+    c.n = len(ops)
+    for s, op in enumerate(ops):
+        c.op[s].kind = COLOUR_OPS[op[0]] if isinstance(op[0], str) else int(op[0])
+        c.op[s].value = float(op[1]) if len(op) > 1 else 0.0
+    return c
+
+
 class PlanInfoC(ctypes.Structure):
     _fields_ = [("total_blocks", ctypes.c_int64), ("total_mcus", ctypes.c_int64), ("total_pixels", ctypes.c_int64),
                 ("rgb_bytes", ctypes.c_int64), ("entropy_bytes", ctypes.c_int64)]
@@ -225,6 +261,8 @@ def load_library():
     L.mj_plan_time_resize.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i64)]
     L.mj_plan_time_reduce.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
     L.mj_host_affine.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_double), i32, vp, i32, i32, i32, i32, vp]
+    L.mj_plan_time_colour.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
+    L.mj_host_colour_ops.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ColourChainC), vp]
     L.mj_plan_time_affine.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
@@ -453,6 +491,19 @@ def affine(a: np.ndarray, matrix, filter="nearest", fill=0, window=None) -> np.n
     return out
 
 
+def colour_ops(a: np.ndarray, chain) -> np.ndarray:
+    """mj_host_colour_ops (host only): the colour launches' arithmetic on a row-major uint8 (H, W) or (H, W, 3) array — ``chain``
+    applied to it as to a Pillow "L" / "RGB" image (tools/colour_model.py: apply_chain)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    h, w = a.shape[:2]
+    nc = a.shape[2] if a.ndim == 3 else 1
+    out = np.empty_like(a)
+    c = colour_chain(chain)
+    if load_library().mj_host_colour_ops(_ptr(a), w, h, nc, ctypes.byref(c), _ptr(out)) != MJ_OK:
+        raise ValueError("mj_host_colour_ops: bad arguments")
+    return out
+
+
 def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarray:
     """mj_host_normalize_table (host only): the 256 bit patterns (uint16 for "float16" / "bfloat16", uint32 for "float32") one
     component's resized bytes 0..255 are stored as with this mean and std (tools/normalize_model.py: table_bits)."""
@@ -528,7 +579,7 @@ def output_desc(output):
 
 
 def plan_request(n_images, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None, places=None,
-                 fill=None, reducing_gap=None, views=None, affine=None):
+                 fill=None, reducing_gap=None, views=None, affine=None, colour=None):
     """(mj_plan_request, the arrays it points to) for a batch of ``n_images`` from Plan's keywords: every keyword is one field of
     the request (include/mijpeg.h), None its default.  Pure: no library, no context.  ValueError for what only a sized or placed
     plan has and for a per-image list that has not one entry for each image (with ``views``: places and the mirror flags have one
@@ -537,6 +588,8 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
         raise ValueError("views needs size: only a resized plan has several outputs per image")
     if size is None and affine is not None:
         raise ValueError("affine needs size: only a resized plan reads the transformed images")
+    if size is None and colour is not None:
+        raise ValueError("colour needs size: only a resized plan has a canvas the operations work on")
     if size is None and (places is not None or filter is not None or output is not None):
         raise ValueError("places, filter and output need size: only a resized plan has a canvas, resamples and has a dense output")
     if size is None and reducing_gap is not None:
@@ -544,7 +597,11 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
     if fill is not None and places is None:
         raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
     keep = {}
-    if affine is not None:      # (the request is then the head of the structure that holds the arrays' pointers)
+    if colour is not None:      # (the request is then the head of the structure that holds the arrays' pointers)
+        keep["colour_request"] = whole = PlanColourRequestC()
+        ext = whole.head
+        r = ext.request
+    elif affine is not None:
         keep["affine_request"] = ext = PlanAffineRequestC()
         r = ext.request
     elif views is not None:
@@ -587,6 +644,12 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
                                                                           for m in matrices])
         fb = (tuple(fb) + (0, 0, 0))[:3]
         r.affine = (AFFINE_FILTERS[name] if isinstance(name, str) else int(name)) | fb[0] << 8 | fb[1] << 16 | fb[2] << 24
+    if colour is not None:      # (one chain — None or a sequence of ops — per output)
+        n_out = len(views) if views is not None else n_images
+        if len(colour) != n_out:
+            raise ValueError(f"colour: {len(colour)} entries, not one for each of the {n_out} {'views' if views is not None else 'images'}")
+        keep["colour"] = whole.colour = (ColourChainC * max(1, len(colour)))(*[colour_chain(c) for c in colour])
+        r.mode |= MJ_MODE_COLOUR_OPS
     for name, given in (("places", places), ("orientation", orientation), ("mirror", keep.get("mirror"))):
         per_view = views is not None and name != "orientation"
         if given is not None and len(given) != (len(views) if per_view else n_images):
@@ -691,12 +754,13 @@ class Plan:
     bytes, one per output component.  reducing_gap: with size, a number >= 1.0 — the two-step resize, Pillow's argument of that name.
     views: with size, one (image, (x, y, width, height) or None) per OUTPUT — several windows of one decoded image; slots, the mirror
     flags and places then have one entry per view.  affine: with size, (matrices, filter, fill) — one 6-tuple or None per output, a
-    name of AFFINE_FILTERS, up to three fill bytes: the affine transform in front of the windows and the resize."""
+    name of AFFINE_FILTERS, up to three fill bytes: the affine transform in front of the windows and the resize.  colour: with size,
+    one chain (None or a sequence of ops, :func:`colour_chain`) per output: the colour operations on the finished canvas."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None, affine=None):
+                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None, affine=None, colour=None):
         request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill,
-                                  reducing_gap, views, affine)
+                                  reducing_gap, views, affine, colour)
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -776,6 +840,13 @@ class Plan:
         """(ms per affine launch, bytes it writes) of a plan with an affine transform that has been executed (mj_plan_time_affine)."""
         ms, nb = ctypes.c_float(), ctypes.c_int64()
         self.ctx.check(self.ctx.lib.mj_plan_time_affine(self.handle, iters, ctypes.byref(ms), ctypes.byref(nb)))
+        return ms.value, nb.value
+
+    def time_colour(self, iters: int = 10):
+        """(ms per run of the colour launches, bytes of one set of canvases) of a plan with colour operations that has been executed
+        (mj_plan_time_colour)."""
+        ms, nb = ctypes.c_float(), ctypes.c_int64()
+        self.ctx.check(self.ctx.lib.mj_plan_time_colour(self.handle, iters, ctypes.byref(ms), ctypes.byref(nb)))
         return ms.value, nb.value
 
     def time_reduce(self, iters: int = 10) -> float:

@@ -808,6 +808,74 @@ def check_affine(spec: Optional[AffineSpec], views, odims, index=None) -> None:
             raise ValueError(f"affine: output {k} (file {f if index is None else index[f]}): {why}")
 
 
+def _is_colour_op(op) -> bool:
+    """an op is always a tuple whose first element is a string: that tells one chain from a list of chains"""
+    return isinstance(op, tuple) and len(op) >= 1 and isinstance(op[0], str)
+
+
+def _is_chain(c) -> bool:
+    return isinstance(c, (list, tuple)) and all(_is_colour_op(op) for op in c)
+
+
+def _colour_chain(chain, where: str) -> Optional[Tuple[tuple, ...]]:
+    """one chain, checked: a tuple of ``(name,)`` / ``(name, value)`` with the value the C ABI takes, or None for an empty one"""
+    if len(chain) > B.MJ_COLOUR_MAX_OPS:
+        raise ValueError(f"color_ops: {where}{len(chain)} ops in one chain; at most {B.MJ_COLOUR_MAX_OPS} are offered yet")
+    ops = []
+    for op in chain:
+        name = op[0]
+        if name not in B.COLOUR_OPS:
+            raise ValueError(f"color_ops: {where}unknown op {name!r} (one of {', '.join(B.COLOUR_OPS)}; hue is not offered yet)")
+        if name not in B.COLOUR_VALUED:
+            if len(op) != 1:
+                raise ValueError(f"color_ops: {where}{name!r} takes no value (cutoffs and masks are not offered yet), not {op!r}")
+            ops.append((name,))
+            continue
+        if len(op) != 2 or not _is_number(op[1]):
+            raise ValueError(f"color_ops: {where}{name!r} takes one number, not {op!r}")
+        v = float(op[1])
+        if not math.isfinite(v):
+            raise ValueError(f"color_ops: {where}{name!r}: {op[1]!r} is not finite")
+        if name == "posterize":
+            if v != int(v) or not 1 <= int(v) <= 8:
+                raise ValueError(f"color_ops: {where}posterize takes 1..8 bits, not {op[1]!r}")
+        elif name == "solarize":            # (v stays where v < t: for a byte, where v < ceil(t))
+            v = float(min(max(math.ceil(v), 0), 256))
+        ops.append((name, v))
+    return tuple(ops) or None
+
+
+def normalize_color_ops(color_ops, size, n_outputs: Optional[int] = None, return_seams: bool = False):
+    """``color_ops`` of a call, checked: None for a call without colour operations — ``color_ops`` None, or chains that are all None or
+    empty, which make the request of a call without the argument — else a list with one chain (a tuple of ops) or None per OUTPUT.
+    ``color_ops``: None, one chain for every output, or a list with one chain or None per output (per file; per view with
+    ``views``).  A chain is a sequence of at most four ops, applied in order to the finished canvas as to a Pillow image of the
+    output's mode, each op the one Pillow call that defines its bytes (tools/colour_model.py): ``("brightness", f)``, ``("color", f)``,
+    ``("contrast", f)``, ``("sharpness", f)`` — ``ImageEnhance.<Name>(im).enhance(f)`` —, ``("posterize", bits)`` with 1..8 bits,
+    ``("solarize", t)``, ``("autocontrast",)``, ``("equalize",)``, ``("invert",)`` — ``ImageOps.<name>(im[, value])``.  An op is always
+    a tuple whose first element is a string; that is how one chain is told from a list of chains.  The operations need ``size`` and
+    do not go with ``return_seams``.  ``n_outputs`` None: what needs no file.  ValueError otherwise."""
+    if color_ops is None:
+        return None
+    if size is None:
+        raise ValueError("color_ops needs size=(width, height): the operations work on the finished canvas")
+    if return_seams:
+        raise ValueError("color_ops and return_seams do not go together: the seam outputs are the decoded images")
+    if _is_chain(color_ops):
+        one = _colour_chain(color_ops, "")
+        chains = None if n_outputs is None else [one] * n_outputs
+    elif isinstance(color_ops, (list, tuple)) and all(c is None or _is_chain(c) for c in color_ops):
+        if n_outputs is not None and len(color_ops) != n_outputs:
+            raise ValueError(f"color_ops has {len(color_ops)} entries for {n_outputs} outputs")
+        chains = [_colour_chain(c, f"output {k}: ") if c is not None else None for k, c in enumerate(color_ops)]
+    else:
+        raise ValueError(f"color_ops must be None, one chain — a sequence of ops such as ('brightness', 1.2) or ('equalize',), each a tuple "
+                         f"that starts with the op's name — or a list with one chain or None per output, not {color_ops!r}")
+    if chains is None or all(c is None for c in chains):
+        return None
+    return chains
+
+
 def rotation_matrix(angle: float, size: Tuple[int, int], center=None, translate=None) -> Tuple[float, ...]:
     """The matrix ``Image.rotate(angle, center=center, translate=translate)`` builds for ``expand=False`` on an image of ``size`` =
     (width, height) — counter-clockwise by ``angle`` degrees around ``center`` (None: the image's centre), then moved by
@@ -1033,6 +1101,7 @@ class _Request:
     reducing_gap: Optional[float] = None
     views: Optional[List[Tuple[int, Tuple[int, int, int, int]]]] = None
     affine: Optional[AffineSpec] = None         # :func:`normalize_affine`'s (None: no transform); always with ``views``
+    colour: Optional[List[Optional[tuple]]] = None      # :func:`normalize_color_ops`' chains, one or None per OUTPUT (None: no operations)
 
     @property
     def n_outputs(self) -> int:
@@ -1054,6 +1123,9 @@ class _Request:
         orient = pick(self.orient)
         if orient is not None and all(o == 1 for o in orient):
             orient = None
+
+        def chains(picked):                 # (outputs without operations: the request of a call without color_ops)
+            return picked if picked is not None and any(c is not None for c in picked) else None
         if self.views is not None:
             # a file takes its views with it: they keep their order, and what is per view goes with the view
             pos = {i: k for k, i in enumerate(idxs)}
@@ -1066,9 +1138,10 @@ class _Request:
                 affine = None
             return _Request(pick(self.files), None, self.size, self.output.for_files(vk) if self.output else None, self.dest, pick_view(self.slots),
                             pick(index), orient, self.resample, self.mode, pick_view(self.places), self.fill, self.reducing_gap,
-                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine)
+                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine, chains(pick_view(self.colour)))
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
-                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap)
+                        self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap,
+                        colour=chains(pick(self.colour)))
 
     def orient_classes(self) -> List[List[int]]:
         """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
@@ -1100,6 +1173,8 @@ class _Request:
             kw["reducing_gap"] = self.reducing_gap
         if self.affine is not None:         # (no output transformed: the arguments of a call without affine)
             kw["affine"] = (self.affine.matrices, self.affine.resample, self.affine.fill)
+        if self.colour is not None:         # (no output with operations: the arguments of a call without color_ops)
+            kw["colour"] = self.colour
         return kw
 
 
@@ -1249,7 +1324,7 @@ class BatchDecoder:
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1299,7 +1374,18 @@ class BatchDecoder:
         fillcolor=affine_fill).crop(window).resize(target, filter)`` bit for bit, then the mirror and the output's element type; an
         output whose matrix is None is the output of the call without the argument.  Files are decoded whole (a rotated window
         needs pixels outside itself); one more launch per plan writes every output's window of its transformed image.  Not with
-        ``return_seams``, and not yet with ``reducing_gap``."""
+        ``return_seams``, and not yet with ``reducing_gap``.
+        ``color_ops``, with ``size``: the colour half of ColorJitter, RandAugment, AutoAugment and TrivialAugment, on the finished
+        canvas (:func:`normalize_color_ops`): None, one chain for every output, or a list with one chain or None per output — per
+        file, per view with ``views``.  A chain is a sequence of at most four ops — ``("brightness", f)``, ``("color", f)``,
+        ``("contrast", f)``, ``("sharpness", f)``, ``("posterize", bits)``, ``("solarize", t)``, ``("autocontrast",)``,
+        ``("equalize",)``, ``("invert",)`` —, each what the one call of Pillow's ``ImageEnhance`` / ``ImageOps`` of that name does.
+        The order is decode, mode, orientation, affine, window, resize / place / fill, colour ops, mirror, element type
+        (torchvision's: crop, flip, jitter, ToTensor, Normalize — every op commutes with the flip): output k is its chain applied to
+        the uint8 canvas the call gives without the argument, without ``mirror`` and with ``dtype="uint8"`` — fill pixels
+        included —, as a Pillow image of the output's mode, bit for bit; then the mirror and the element type.  An output whose
+        chain is None or empty is the output of the call without the argument.  Not with ``return_seams``; hue, autocontrast's
+        cutoffs and masks, and more than four ops are not offered yet."""
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -1317,6 +1403,7 @@ class BatchDecoder:
         normalize_fill(fill, resize_to)
         spec = normalize_affine(affine, affine_resample, affine_fill, size, len(views) if isinstance(views, (list, tuple)) else len(files),
                                 reducing_gap, return_seams)
+        colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files), return_seams)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None                            # views: where the files that are read sit in the caller's list
@@ -1330,7 +1417,7 @@ class BatchDecoder:
         orient = normalize_orientation(orientation, files)
         odims = _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)
         req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode, reducing_gap=reducing_gap, index=index,
-                       views=normalize_views(views, odims, size, index=index) if selected is not None else None)
+                       views=normalize_views(views, odims, size, index=index) if selected is not None else None, colour=colour)
         if req.views is not None:               # (what is per output is per view; an error names the view's file)
             req.places = normalize_places(resize_to, place, size, [r[2:] for _, r in req.views], [index[f] for f, _ in req.views])
             req.slots = list(range(len(req.views)))
@@ -1403,11 +1490,12 @@ class BatchDecoder:
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
                         resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                        affine_fill=None) -> _Request:
+                        affine_fill=None, color_ops=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
         spec = normalize_affine(affine, affine_resample, affine_fill, size, len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap)
+        colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files))
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None
@@ -1417,7 +1505,7 @@ class BatchDecoder:
             orientation = _per_file_of(orientation, len(files), index, "orientation")
             files = [files[i] for i in index]
         req = _Request(files, None, size, orient=normalize_orientation(orientation, files), resample=normalize_resample(resample, size),
-                       mode=normalize_mode(mode), reducing_gap=normalize_reducing_gap(reducing_gap, size), index=index)
+                       mode=normalize_mode(mode), reducing_gap=normalize_reducing_gap(reducing_gap, size), index=index, colour=colour)
         if size is not None:
             import torch
             info = [_named(index, i, _image_info, f) for i, f in enumerate(files)]
@@ -1452,7 +1540,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1489,7 +1577,10 @@ class BatchDecoder:
         several kinds are still one plan per kind, each writing its views' slots of the one tensor, and a large call is split into
         parts by FILE, every file's views in its part.
         ``affine``, ``affine_resample`` and ``affine_fill`` as in :meth:`decode`: every plan of the call (files of several kinds and
-        orientation classes, second rounds, parts) runs its own affine launch between its decode and its resize launch."""
+        orientation classes, second rounds, parts) runs its own affine launch between its decode and its resize launch.
+        ``color_ops`` as in :meth:`decode`: every plan of the call whose outputs have operations writes its canvases into a buffer of
+        its own and runs the colour launches behind its resize launch — histograms, tables and the operations themselves, all on the
+        GPU —, which store into the one tensor; plans whose outputs have none are the plans of a call without the argument."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -1498,7 +1589,7 @@ class BatchDecoder:
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
         req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap, views,
-                                   affine, affine_resample, affine_fill)
+                                   affine, affine_resample, affine_fill, color_ops)
         files = req.files                       # (with views: the files some view names)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
@@ -1609,7 +1700,7 @@ class BatchDecoder:
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None):
+                           affine_fill=None, color_ops=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1631,8 +1722,11 @@ class BatchDecoder:
         what :meth:`decode_device` takes for that batch — a list with one entry per output; ``mirror`` and the list forms of
         ``resize_to`` and ``place`` then go by view.  ``affine``: None, one matrix for every output of every batch, or an iterable
         that yields, batch by batch, what :meth:`decode_device` takes for that batch; ``affine_resample`` and ``affine_fill`` as
-        there, for every batch."""
+        there, for every batch.  ``color_ops``: None, one chain for every output of every batch, or an iterable that yields, batch by
+        batch, what :meth:`decode_device` takes for that batch."""
         size = normalize_size(size)
+        normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
+        per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
         normalize_affine(affine if affine is None or _is_matrix(affine) else (1, 0, 0, 0, 1, 0), affine_resample, affine_fill, size, None, reducing_gap)
         per_batch_affine = iter(affine) if affine is not None and not _is_matrix(affine) else None
@@ -1681,11 +1775,18 @@ class BatchDecoder:
                         t = next(per_batch_affine)
                     except StopIteration:
                         raise ValueError("affine yields fewer entries than there are batches") from None
+                c = color_ops
+                if per_batch_colour is not None:
+                    try:
+                        c = next(per_batch_colour)
+                    except StopIteration:
+                        raise ValueError("color_ops yields fewer entries than there are batches") from None
                 if t is None or (isinstance(t, (list, tuple)) and all(e is None for e in t)):         # (a batch without a transform)
-                    yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v)
+                    yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
+                                               color_ops=c)
                     continue
                 yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                           t, affine_resample, affine_fill)
+                                           t, affine_resample, affine_fill, c)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -363,16 +363,22 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
         return MJ_OK;
     }
     mj::ResizeArgs a = p->rz;
-    a.dst = p->last_rgb;
+    // (a plan with colour operations: the resize writes the plan's canvases, and the colour launches behind it the output)
+    a.dst = p->colour ? p->co.canvas[0] : p->last_rgb;
     // a reducing plan: the reduce launch in front, whose packed reduced images the resize reads (colour to L: converted there)
     if (p->reduces) MJ_HIP(p->ctx, mj::launch_reduce(s, p->rd, p->ncomp, p->rd_luma));
     // a plan with an affine transform: the affine launch in front, whose upright windows — in the output's components — the resize reads
     if (p->affine) {
         MJ_HIP(p->ctx, mj::launch_affine(s, p->af, p->ncomp, p->af_ncomp));
         MJ_HIP(p->ctx, mj::launch_resize(s, a, p->af_ncomp, 0, p->rz_placed, p->rz_fill));
-        return MJ_OK;
+    } else {
+        MJ_HIP(p->ctx, mj::launch_resize(s, a, p->rd_luma ? 1 : p->ncomp, p->rd_luma ? 0 : p->out_ncomp, p->rz_placed, p->rz_fill));
     }
-    MJ_HIP(p->ctx, mj::launch_resize(s, a, p->rd_luma ? 1 : p->ncomp, p->rd_luma ? 0 : p->out_ncomp, p->rz_placed, p->rz_fill));
+    if (p->colour) {
+        mj::ColourArgs c = p->co;
+        c.dst = p->last_rgb;
+        MJ_HIP(p->ctx, mj::launch_colour(s, c));
+    }
     return MJ_OK;
 }
 
@@ -626,6 +632,20 @@ int mj_plan_time_affine(mj_plan *p, int iters, float *ms_out, int64_t *written_b
     if (int rc = plan_ready(p, s)) return rc;
     const int rc = time_launches(ctx, s, 1, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_affine(s, p->af, p->ncomp, p->af_ncomp)); return MJ_OK; }, ms_out);
     if (written_bytes) *written_bytes = p->af_bytes;
+    return rc != MJ_OK ? rc : mark_done(p, s);
+}
+
+int mj_plan_time_colour(mj_plan *p, int iters, float *ms_out, int64_t *canvas_bytes) {
+    if (!p || iters <= 0 || !ms_out) return MJ_ERR_INVALID;
+    mj_context *ctx = p->ctx;
+    if (!p->colour) return fail(ctx, MJ_ERR_INVALID, "mj_plan_time_colour: not a plan with colour operations");
+    if (!p->last_rgb) return fail(ctx, MJ_ERR_INVALID, "mj_plan_time_colour: nothing executed yet");
+    hipStream_t s = ctx->stream;
+    if (int rc = plan_ready(p, s)) return rc;
+    mj::ColourArgs c = p->co;
+    c.dst = p->last_rgb;
+    const int rc = time_launches(ctx, s, 1, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_colour(s, c)); return MJ_OK; }, ms_out);
+    if (canvas_bytes) *canvas_bytes = (int64_t)c.n_outputs * c.ow * c.oh * c.C;
     return rc != MJ_OK ? rc : mark_done(p, s);
 }
 

@@ -495,6 +495,84 @@ void affine_scale_table(double scale, double offset, int size, int first, int n,
 void affine_host(const uint8_t *src, const DevAffineImage &im, const int32_t *tabs, int ncomp, int out_ncomp, uint32_t fill, uint8_t *out);
 // (ncomp: the decoded images'; out_ncomp: the written ones' — the same, 1 for colour to L, 3 for grey to RGB)
 hipError_t launch_affine(hipStream_t stream, const AffineArgs &a, int ncomp, int out_ncomp);
+// ---- colour.hip: colour operations on the finished canvas (mj_plan_request.mode with MJ_MODE_COLOUR_OPS; tools/colour_model.py)
+// One output of a plan with colour operations: its chain (n ops; value: the factor of brightness, color, contrast and sharpness;
+// ivalue: posterize's MASK and solarize's clamped threshold, as integers — colour_ivalue), where its elements go in the caller's
+// array (dst_off, in ELEMENTS) and whether it is mirrored.
+struct DevColourOutput {
+    int64_t dst_off;
+    int32_t n, mirror;
+    int32_t kind[4];
+    float value[4];
+    int32_t ivalue[4];
+};
+// The canvases are n_outputs images of ow x oh pixels of C components in the plan's layout, output after output.  A pixel's
+// place is p = y * ow + x (row-major layouts) or x * oh + y (x-major); component c of it is byte p * C + c (interleaved) or
+// c * ow * oh + p (planar) of its image.  hist: uint32[n_outputs][4][256] — components 0..2 and L —, tables: uint8[n_outputs][3][256].
+// hist_list[hist_first[s] .. hist_first[s + 1]): the outputs whose op s takes a histogram; tables_at bit s: some output's op s is a table
+struct ColourArgs {
+    uint8_t *canvas[2];
+    uint32_t *hist;
+    uint8_t *tables;
+    const DevColourOutput *outputs;
+    const int32_t *hist_list;
+    const void *lut;                    // the output table (ResizeArgs::lut's), NULL for bytes
+    void *dst;
+    int32_t hist_first[5];
+    int32_t n_outputs, ow, oh, C, layout, esize, steps, tables_at;
+};
+constexpr int kColourHistPixels = 4096;       // pixels of a canvas one workgroup of the histogram launch counts
+// Image.blend of one byte (tools/colour_model.py: blend); every operation rounds on its own (-ffp-contract=off, host and device)
+__host__ __device__ inline unsigned colour_blend(int d, int v, float alpha) {
+    const float t = (float)d + alpha * (float)(v - d);
+    if (alpha >= 0.0f && alpha <= 1.0f) return (unsigned)t;
+    return t <= 0.0f ? 0u : t >= 255.0f ? 255u : (unsigned)t;
+}
+// ImageFilter.SMOOTH of one interior pixel from its 3 x 3 neighbourhood p[row][column], row 0 above
+__host__ __device__ inline unsigned colour_smooth(const float p[3][3]) {
+    const float k1 = (float)(1 / 13.0), k5 = (float)(5 / 13.0);
+    float ss = 0.5f;
+    ss += (p[2][0] * k1 + p[2][1] * k1) + p[2][2] * k1;
+    ss += (p[1][0] * k1 + p[1][1] * k5) + p[1][2] * k1;
+    ss += (p[0][0] * k1 + p[0][1] * k1) + p[0][2] * k1;
+    return ss <= 0.0f ? 0u : ss >= 255.0f ? 255u : (unsigned)ss;
+}
+// whether an op is a look-up table per component / takes a histogram
+__host__ __device__ inline bool colour_is_table(int kind) { return kind != MJ_COLOUR_COLOR && kind != MJ_COLOUR_SHARPNESS && kind != 0; }
+__host__ __device__ inline bool colour_needs_hist(int kind) { return kind == MJ_COLOUR_CONTRAST || kind == MJ_COLOUR_AUTOCONTRAST || kind == MJ_COLOUR_EQUALIZE; }
+// Entry i of a table-shaped op's table for one component.  st: that component's histogram, scanned (ops that take one) — lo, hi
+// its first and last non-empty bins, nz how many are non-empty, last the last one's count, total the sum of all —, with mean
+// contrast's grey level, which comes from the L histogram; prefix: the sum of the component's bins below i (equalize)
+struct ColourStats { int lo, hi, nz, mean; unsigned long long last, total; };
+__host__ __device__ inline unsigned colour_table_entry(int kind, float value, int ivalue, int i, const ColourStats &st, unsigned long long prefix) {
+    switch (kind) {
+    case MJ_COLOUR_BRIGHTNESS: return colour_blend(0, i, value);
+    case MJ_COLOUR_CONTRAST: return colour_blend(st.mean, i, value);
+    case MJ_COLOUR_POSTERIZE: return (unsigned)i & (unsigned)ivalue;
+    case MJ_COLOUR_SOLARIZE: return i < ivalue ? (unsigned)i : 255u - (unsigned)i;
+    case MJ_COLOUR_INVERT: return 255u - (unsigned)i;
+    case MJ_COLOUR_AUTOCONTRAST: {
+        if (st.hi <= st.lo) return (unsigned)i;
+        const double scale = 255.0 / (double)(st.hi - st.lo), offset = (double)(-st.lo) * scale;
+        const double t = (double)i * scale + offset;
+        return t <= 0.0 ? 0u : t >= 255.0 ? 255u : (unsigned)(int)t;
+    }
+    case MJ_COLOUR_EQUALIZE: {
+        if (st.nz <= 1) return (unsigned)i;
+        const unsigned long long step = (st.total - st.last) / 255u;
+        if (!step) return (unsigned)i;
+        const unsigned long long q = (step / 2 + prefix) / step;
+        return q > 255u ? 255u : (unsigned)q;
+    }
+    }
+    return (unsigned)i;
+}
+// what the flag and mj_host_colour_ops refuse of one chain: nullptr, or the reason
+const char *colour_fault(const mj_colour_chain &c);
+// the integer form of an op's value (posterize: the mask, solarize: the clamped threshold; else 0)
+int colour_ivalue(const mj_colour_op &op);
+// the launches of one execute: the canvas in a.canvas[0] -> a.dst
+hipError_t launch_colour(hipStream_t stream, const ColourArgs &a);
 // ---- output colour mode (tools/mode_model.py)
 // Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
 __host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }

@@ -291,6 +291,16 @@ struct mj_plan {
     mj::DevAffineImage *d_af_images = nullptr;
     int32_t *d_af_tabs = nullptr;
     mj::AffineArgs af{};
+    // plans with colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): the resize launch writes uint8 canvases, unmirrored,
+    // output after output, into the first half of d_canvas; the colour launches (colour.hip) take them through their chains, from one
+    // half to the other, and store the last step into the caller's array — slots, mirror flags and the output table are theirs
+    bool colour = false;
+    uint8_t *d_canvas = nullptr;
+    uint32_t *d_co_hist = nullptr;
+    uint8_t *d_co_tables = nullptr;
+    mj::DevColourOutput *d_co_outputs = nullptr;
+    int32_t *d_co_list = nullptr;
+    mj::ColourArgs co{};
     int32_t n_views = 0;                       // a plan with views (mj_plan_request.views): its resize and reduce records are per view (0: per image)
     std::vector<std::array<int32_t, 2>> h_view_size;   // ... every view's window, stored axes: width, height (mj_debug_reduce_shape)
     std::vector<std::array<int32_t, 6>> h_rd;  // per image (view), stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)
@@ -326,8 +336,11 @@ int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, b
 // views: r.n_views entries where r.n_views != 0 (the caller's mj_plan_views_request), else NULL
 // affine: one matrix per output where r.affine != 0 (the caller's mj_plan_affine_request), else NULL.  Such a request ALWAYS has
 // views after normalisation: its windows (r.rois) or whole images become one view per image, held in own_views
+// colour: one chain per output where the caller's r.mode had MJ_MODE_COLOUR_OPS (its mj_plan_colour_request) and some chain is not
+// empty, else NULL; r.mode itself holds the mode alone after normalisation
 struct PlanRequest {
     mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; const mj_view *views = nullptr; const mj_affine *affine = nullptr;
+    const mj_colour_chain *colour = nullptr;
     std::vector<mj_view> own_views{};
 };
 // an output without a transform: all six entries 0

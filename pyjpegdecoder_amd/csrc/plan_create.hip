@@ -731,6 +731,10 @@ const mj_affine *request_affine(const mj_plan_request *request) {
     return request && request->affine ? reinterpret_cast<const mj_plan_affine_request *>(request)->affine : nullptr;
 }
 
+const mj_colour_chain *request_colour(const mj_plan_request *request) {
+    return request && (request->mode & MJ_MODE_COLOUR_OPS) ? reinterpret_cast<const mj_plan_colour_request *>(request)->colour : nullptr;
+}
+
 // The affine transform of a sized request, checked against every output's oriented image (views are in place: normalise_views)
 int check_affine(mj::PlanRequest &q) {
     const char *fn = mj::kCreateFn;
@@ -780,7 +784,10 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     const char *fn = mj::kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
     const bool sized = r.out_width != 0 || r.out_height != 0;
-    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : r.affine ? "affine" : nullptr;
+    // (the colour flag is a bit of `mode`; from here on r.mode is the mode alone, and q.colour says whether the flag was set)
+    const bool colour_flag = (r.mode & MJ_MODE_COLOUR_OPS) != 0;
+    r.mode &= ~MJ_MODE_COLOUR_OPS;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : r.affine ? "affine" : colour_flag ? "colour_ops" : nullptr;
     // (what slots, the mirror flags and places have one entry for: the views of a request with views, else the images)
     const int n_out = r.n_views > 0 ? r.n_views : (b ? b->n_images : 0);
     if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
@@ -814,6 +821,17 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     if ((sized || r.orientations || r.mode) && (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
         return fail(ctx, MJ_ERR_INVALID, sized ? "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none"
                                                : "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
+    if (colour_flag) {      // (every chain checked; all of them empty: the request without the flag)
+        if (!q.colour) return fail(ctx, MJ_ERR_INVALID, "%s: colour_ops without its array of chains", fn);
+        bool none = true;
+        for (int k = 0; k < n_out; ++k) {
+            if (const char *why = mj::colour_fault(q.colour[k])) return fail(ctx, MJ_ERR_INVALID, "%s: colour_ops: output %d: %s", fn, k, why);
+            none = none && q.colour[k].n == 0;
+        }
+        if (none) q.colour = nullptr;
+    } else {
+        q.colour = nullptr;
+    }
     if (r.affine) {
         const int n_out_af = r.n_views > 0 ? r.n_views : b->n_images;
         const int af_filter = (int)(r.affine & 0xFF);
@@ -888,14 +906,15 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
 int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request, mj_plan_request *normal) {
     if (!normal) return MJ_ERR_INVALID;
     mj_plan *none = nullptr;
-    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request), request_affine(request)};
+    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request)};
     const int rc = normalise_request(q, false);
     if (rc == MJ_OK) *normal = q.r;
+    if (rc == MJ_OK && q.colour) normal->mode |= MJ_MODE_COLOUR_OPS;
     return rc;
 }
 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
-    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request), request_affine(request)};
+    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request)};
     if (int rc = normalise_request(q)) return rc;
     if (q.r.out_width) return mj::create_resized(q);
     if (q.r.orientations || q.r.mode) return mj::create_oriented(q);

@@ -13,6 +13,9 @@
 //   affine_stage           one record per output for the affine launch (affine.hip), its NEAREST index tables, and where every
 //                          output's window of its transformed image lies in the plan's second buffer
 // and the resize launch's records are then upright images of the output's components in THAT buffer, the window's row their pitch.
+// A request with colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS) adds one step behind everything else,
+//   colour_stage           the resize launch is made for uint8 canvases of the plan's own, unmirrored, canvas k for output k; the
+//                          colour launches (colour.hip) get the chains, the slots, the mirror flags and the output table
 #include <math.h>
 #include <map>
 
@@ -266,6 +269,56 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
     return MJ_OK;
 }
 
+// ---- plans with colour operations: the launches behind the resize ---------------------------------------------------------------
+// In: the request (chains checked, some not empty), the plan — its resize launch made for uint8 canvases, output k at canvas k —,
+// CO — the output's components — and the output's element size.  Out: the plan's colour launches (p->co): one record per output
+// with its chain, its slot's offset in elements and its mirror flag; per step, the outputs that take a histogram; the two
+// canvases, the histograms, the tables and the output table, all plan-owned.
+std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize);
+int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
+    const mj_plan_request &r = q.r;
+    const int n = r.n_views ? r.n_views : p->n_images;
+    const int64_t npix = (int64_t)r.out_width * r.out_height, canvas = (int64_t)n * npix * CO;
+    mj::ColourArgs &a = p->co = mj::ColourArgs{};
+    std::vector<mj::DevColourOutput> recs((size_t)n);
+    std::vector<int32_t> list;
+    for (int k = 0; k < n; ++k) {
+        const mj_colour_chain &c = q.colour[k];
+        mj::DevColourOutput &d = recs[(size_t)k] = mj::DevColourOutput{};
+        d.dst_off = (int64_t)(r.slots ? r.slots[k] : k) * npix * CO;
+        d.n = c.n; d.mirror = r.output && r.output->mirror && r.output->mirror[k] ? 1 : 0;
+        for (int s = 0; s < c.n; ++s) {
+            d.kind[s] = c.op[s].kind; d.value[s] = c.op[s].value; d.ivalue[s] = mj::colour_ivalue(c.op[s]);
+            if (mj::colour_is_table(d.kind[s])) a.tables_at |= 1 << s;
+        }
+        a.steps = std::max(a.steps, c.n);
+    }
+    for (int s = 0; s < MJ_COLOUR_MAX_OPS; ++s) {
+        a.hist_first[s] = (int32_t)list.size();
+        for (int k = 0; k < n; ++k)
+            if (s < recs[(size_t)k].n && mj::colour_needs_hist(recs[(size_t)k].kind[s])) list.push_back(k);
+    }
+    a.hist_first[MJ_COLOUR_MAX_OPS] = (int32_t)list.size();
+    const int64_t per_output = std::max<int64_t>((npix + mj::kColourHistPixels - 1) / mj::kColourHistPixels, (npix + 255) / 256);
+    if ((int64_t)n * per_output > mj::kResizeGridX * (int64_t)65535)
+        return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld colour workgroups are more than one launch takes; split the batch", mj::kCreateFn, (long long)n * per_output);
+    if (int rc = upload(p, &p->d_co_outputs, recs.data(), recs.size())) return rc;
+    if (int rc = upload(p, &p->d_co_list, list.data(), list.size())) return rc;
+    MJ_HIP(q.ctx, alloc(p, &p->d_canvas, (size_t)(2 * canvas) + 64));
+    MJ_HIP(q.ctx, alloc(p, &p->d_co_hist, (size_t)n * 1024 * sizeof(uint32_t)));
+    MJ_HIP(q.ctx, alloc(p, &p->d_co_tables, (size_t)n * 768));
+    if (out_esize > 1) {
+        const std::vector<uint8_t> lut = output_table(*r.output, CO, out_esize);
+        if (int rc = upload(p, &p->d_rz_lut, lut.data(), lut.size())) return rc;
+        a.lut = p->d_rz_lut;
+    }
+    a.canvas[0] = p->d_canvas; a.canvas[1] = p->d_canvas + canvas;
+    a.hist = p->d_co_hist; a.tables = p->d_co_tables; a.outputs = p->d_co_outputs; a.hist_list = p->d_co_list;
+    a.n_outputs = n; a.ow = r.out_width; a.oh = r.out_height; a.C = CO; a.layout = p->layout; a.esize = out_esize;
+    p->colour = true;
+    return MJ_OK;
+}
+
 // ---- tap tables: one per distinct axis --------------------------------------------------------------------------------------
 // Where an axis lies on a placed plan's canvas: resized to `resized` entries at offset `off`; `base` is the first source entry of
 // the part of the source that was decoded, `len` that part's entries.
@@ -458,7 +511,10 @@ int mj::create_resized(const PlanRequest &q) {
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
     auto [rois, orient, mode, out_width, out_height, affine, slots, n_slots, n_views, output, filter, reducing_gap, places, fill] = q.r;
     const mj_view *views = q.views;
-    const int dtype = output ? output->dtype : MJ_DTYPE_U8, esize = dtype_size(dtype);
+    // a plan with colour operations: the resize launch is that of the uint8, unmirrored, identity-slot request — it writes the
+    // canvases —, and the element type, the slots and the mirror flags are the colour launches' (colour_stage)
+    const bool colour = q.colour != nullptr;
+    const int dtype = output ? output->dtype : MJ_DTYPE_U8, out_esize = dtype_size(dtype), esize = colour ? 1 : out_esize;
     std::vector<Need> need;
     std::vector<mj_roi> derived;
     if (places) {
@@ -521,8 +577,9 @@ int mj::create_resized(const PlanRequest &q) {
         const int bits = orient ? mj::orient_bits(orient[img]) : 0;
         if (bits & 4) std::swap(w, h);      // (from here on the oriented image's size)
         ri[i].src_off = p->h_images[img].rgb_off;
-        ri[i].dst_off = (int64_t)(slots ? slots[i] : i) * out_image;
-        if (p->out_ncomp && !views) p->h_out_off.push_back(ri[i].dst_off);
+        const int64_t slot_off = (int64_t)(slots ? slots[i] : i) * out_image;
+        ri[i].dst_off = colour ? (int64_t)i * out_image : slot_off;      // (canvas i of the plan's own buffer)
+        if (p->out_ncomp && !views) p->h_out_off.push_back(colour ? slot_off * out_esize : slot_off);
         // the record's size is what the kernels step from row to row by (resize.hip): the decoded image's.  w, h from here on: what
         // the tables are made for — the same, but for a view, whose record starts at its window's origin and whose tables are its window's
         ri[i].w = w; ri[i].h = h;
@@ -543,7 +600,7 @@ int mj::create_resized(const PlanRequest &q) {
             ri[i].w = w; ri[i].h = h;
             if (places) need[(size_t)i] = Need{0, w, 0, h, w, h};
         }
-        if (output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
+        if (!colour && output && output->mirror) any_mirror |= (flags[i] = output->mirror[i] ? 1 : 0);
         if (orient) flags[i] = (uint8_t)((flags[i] ^ (bits & 1)) | (bits & 2));      // (the mirror comes after the orientation)
         if (places) {
             // (w, h: what was decoded of the oriented image — the whole, the caller's window, or the derived range of either — or the view)
@@ -618,7 +675,9 @@ int mj::create_resized(const PlanRequest &q) {
         a.src = p->d_aff;
         p->affine = true; p->af_ncomp = CO; p->af_bytes = af_bytes;
     }
-    p->info.rgb_bytes = (int64_t)n_slots * out_image;
+    if (colour)
+        if (int rc = colour_stage(q, p, CO, out_esize)) return rc;
+    p->info.rgb_bytes = (int64_t)n_slots * out_image * (colour ? out_esize : 1);
     p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
     p->resized = true;
     guard.p = nullptr;

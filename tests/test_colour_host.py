@@ -1,0 +1,375 @@
+"""Colour operations on the host (no GPU): tools/colour_model.py — the statement of Pillow's ImageEnhance.* / ImageOps.* — against
+Pillow itself, the library's host twin mj_host_colour_ops against the model, and the request: batch.normalize_color_ops, the
+binding's structures against the header, and the checks and the default rule through mj_debug_normalise_request."""
+import ctypes
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+SIDES = (1, 2, 3, 4, 17, 40)
+FACTORS = (0, 0.05, 0.3, 1, 1.4, 2.5)
+OPS = ([(name, f) for name in ("brightness", "color", "contrast", "sharpness") for f in FACTORS] +
+       [("posterize", bits) for bits in range(1, 9)] + [("solarize", t) for t in (0, 100, 229.5, 256)] +
+       [("autocontrast",), ("equalize",), ("invert",)])
+CHAINS = ([("contrast", 1.4), ("brightness", 0.77)], [("brightness", 0.77), ("contrast", 1.4)],
+          [("brightness", 1.3), ("contrast", 0.7), ("color", 1.6)], [("color", 0.2), ("contrast", 1.9), ("brightness", 0.9)],
+          [("autocontrast",), ("equalize",)], [("sharpness", 1.9), ("contrast", 0.6), ("posterize", 5), ("solarize", 130)],
+          [("invert",), ("sharpness", 0.3), ("equalize",)])
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    from pyjpegdecoder_amd import _binding as B
+    if not B.LIB_PATH.exists():
+        g.build()
+    return B.load_library()
+
+
+def images():
+    """(name, uint8 array) — RGB and L, every pair of SIDES' neighbours, random, narrow-range, flat, one image with two grey levels,
+    and for equalize: 40 x 40 random images (step about 6, so n starts at step // 2 > 0 and the quotients are real divisions),
+    20 x 15 random ones (step 1, and n // step passes 255 at values the image HAS: the clip shows in the bytes) and one of four
+    levels whose quotient reaches exactly 255"""
+    rng = np.random.default_rng(20)
+    out = []
+    for k, w in enumerate(SIDES):
+        h = SIDES[(k + 2) % len(SIDES)]
+        for C in (3, 1):
+            shape = (h, w, 3) if C == 3 else (h, w)
+            out.append((f"random {w}x{h}x{C}", rng.integers(0, 256, shape, dtype=np.uint8)))
+            out.append((f"narrow {w}x{h}x{C}", rng.integers(100, 131, shape, dtype=np.uint8)))
+    for C in (3, 1):
+        shape = (9, 11, 3) if C == 3 else (9, 11)
+        out.append((f"flat x{C}", np.full(shape, 77, dtype=np.uint8)))        # one non-empty bin: autocontrast and equalize are the identity
+        two = np.full(shape, 10, dtype=np.uint8)
+        two[:4] = 200
+        out.append((f"two levels x{C}", two))
+        out.append((f"zero step x{C}", np.arange(99, dtype=np.uint8).reshape(9, 11)[..., None].repeat(C, -1).reshape(shape)))     # step == 0
+    for C in (3, 1):
+        out.append((f"equalize steps x{C}", rng.integers(0, 256, (40, 40, 3) if C == 3 else (40, 40), dtype=np.uint8)))
+        out.append((f"equalize passes 255 x{C}", rng.integers(0, 256, (15, 20, 3) if C == 3 else (15, 20), dtype=np.uint8)))
+    # 16 x 16 pixels of 4 levels, the last holding one pixel: step = 255 // 255 = 1, and n // step reaches 255 and beyond
+    small = np.repeat(np.array([0, 50, 100], dtype=np.uint8), 85).tolist() + [200]
+    out.append(("equalize clips", np.array(small, dtype=np.uint8).reshape(16, 16)))
+    out.append(("equalize clips rgb", np.stack([np.array(small, dtype=np.uint8).reshape(16, 16)] * 3, axis=-1)))
+    return out
+
+
+def pillow(im, op):
+    from PIL import ImageEnhance, ImageOps
+    from tools import colour_model as M
+    name = op[0]
+    if name in ("brightness", "color", "contrast", "sharpness"):
+        return getattr(ImageEnhance, name.capitalize())(im).enhance(op[1])
+    if name == "posterize":
+        return ImageOps.posterize(im, op[1])
+    if name == "solarize":
+        return ImageOps.solarize(im, M.solarize_threshold(op[1]))
+    return getattr(ImageOps, name)(im)
+
+
+# ---- the model is Pillow; the host twin is the model ---------------------------------------------------------------------------------
+def test_model_is_pillows_enhance_and_imageops():
+    from PIL import Image
+    from tools import colour_model as M
+    for name, a in images():
+        im = Image.fromarray(a)
+        for op in OPS:
+            assert np.array_equal(M.apply_op(a, op), np.asarray(pillow(im, op))), (name, op)
+        for chain in CHAINS:
+            want = im
+            for op in chain:
+                want = pillow(want, op)
+            assert np.array_equal(M.apply_chain(a, chain), np.asarray(want)), (name, chain)
+
+
+def test_the_models_rare_branches_are_reached():
+    """what the cases above are there for: the identity branches, a zero step, and a quotient above 255"""
+    from tools import colour_model as M
+    named = dict(images())
+    flat, two, clips = named["flat x1"], named["two levels x1"], named["equalize clips"]
+    assert np.array_equal(M.autocontrast_table(np.bincount(flat.ravel(), minlength=256)), np.arange(256))
+    assert np.array_equal(M.equalize_table(np.bincount(flat.ravel(), minlength=256)), np.arange(256))
+    assert np.array_equal(M.equalize_table(np.bincount(named["zero step x1"].ravel(), minlength=256)), np.arange(256))
+    assert set(np.unique(M.apply_op(two, ("autocontrast",)))) == {0, 255}
+    h = np.bincount(clips.ravel(), minlength=256)
+    step = (int(h.sum()) - 1) // 255
+    assert step == 1 and (step // 2 + int(h[:200].sum())) // step == 255 and (step // 2 + int(h.sum())) // step > 255
+    assert M.equalize_table(h)[255] == 255
+
+    def quotients(a):           # (step, the UNCLIPPED n // step at every value the band has)
+        h = np.bincount(a.ravel(), minlength=256)
+        nz = [int(v) for v in h if v]
+        step = (sum(nz) - nz[-1]) // 255
+        return step, [(step // 2 + int(h[:v].sum())) // step for v in np.flatnonzero(h)]
+    for c in range(3):
+        step, q = quotients(named["equalize steps x3"][..., c])
+        assert step > 1 and step // 2 > 0 and len(set(q)) > 100
+        step, q = quotients(named["equalize passes 255 x3"][..., c])
+        assert step == 1 and max(q) > 255 and sum(v > 255 for v in q) >= 5         # values the image has, whose quotient is clipped
+    step, q = quotients(named["equalize steps x1"])
+    assert step > 1 and step // 2 > 0
+    step, q = quotients(named["equalize passes 255 x1"])
+    assert step == 1 and max(q) > 255
+    # ... so a table that started at n = 0, or wrapped instead of clipping, gives other bytes than Pillow's on these images
+    for name in ("equalize steps x1", "equalize passes 255 x1"):
+        a = named[name]
+        h = np.bincount(a.ravel(), minlength=256)
+        nz = [int(v) for v in h if v]
+        step = (sum(nz) - nz[-1]) // 255
+        from_zero = np.array([min(255, int(h[:v].sum()) // step) for v in range(256)], dtype=np.uint8)
+        wrapped = np.array([((step // 2 + int(h[:v].sum())) // step) & 255 for v in range(256)], dtype=np.uint8)
+        good = M.equalize_table(h)[a]
+        assert not np.array_equal(from_zero[a], good) or name.startswith("equalize passes"), name
+        assert not np.array_equal(wrapped[a], good) or name.startswith("equalize steps"), name
+    assert M.contrast_mean(flat) == 77 and M.solarize_threshold(229.5) == 230 and M.solarize_threshold(-4) == 0 and M.solarize_threshold(1e9) == 256
+
+
+def test_host_twin_is_the_model(lib):
+    from pyjpegdecoder_amd import _binding as B
+    from tools import colour_model as M
+    for name, a in images():
+        for op in OPS + [("brightness", -0.5), ("sharpness", -1.0), ("solarize", -3), ("solarize", 400)]:
+            assert np.array_equal(B.colour_ops(a, [op]), M.apply_op(a, op)), (name, op)
+        for chain in CHAINS:
+            assert np.array_equal(B.colour_ops(a, chain), M.apply_chain(a, chain)), (name, chain)
+        assert np.array_equal(B.colour_ops(a, None), a) and np.array_equal(B.colour_ops(a, []), a)
+
+
+def test_host_twin_refuses_what_the_request_refuses(lib):
+    from pyjpegdecoder_amd import _binding as B
+    a = np.zeros((4, 5, 3), dtype=np.uint8)
+    out = np.empty_like(a)
+
+    def rc(chain, w=5, h=4, nc=3):
+        return lib.mj_host_colour_ops(a.ctypes.data, w, h, nc, ctypes.byref(chain), out.ctypes.data)
+    assert rc(B.colour_chain([("invert",)])) == B.MJ_OK
+    for bad in ([("brightness", float("nan"))], [("contrast", float("inf"))], [("posterize", 0)], [("posterize", 9)], [("posterize", 2.5)],
+                [(0,)], [(10,)]):
+        assert rc(B.colour_chain(bad)) == B.MJ_ERR_INVALID, bad
+    c = B.colour_chain([("invert",)])
+    c.n = 5
+    assert rc(c) == B.MJ_ERR_INVALID
+    c.n = -1
+    assert rc(c) == B.MJ_ERR_INVALID
+    ok = B.colour_chain([("invert",)])
+    assert rc(ok, w=0) == rc(ok, h=0) == rc(ok, nc=2) == B.MJ_ERR_INVALID
+    assert lib.mj_host_colour_ops(None, 5, 4, 3, ctypes.byref(ok), out.ctypes.data) == B.MJ_ERR_INVALID
+    assert lib.mj_host_colour_ops(a.ctypes.data, 5, 4, 3, None, out.ctypes.data) == B.MJ_ERR_INVALID
+    with pytest.raises(ValueError, match="at most 4 ops"):
+        B.colour_chain([("invert",)] * 5)
+
+
+# ---- the Python layer ---------------------------------------------------------------------------------------------------------------
+def test_normalize_color_ops_forms():
+    from pyjpegdecoder_amd.batch import normalize_color_ops
+    size = (24, 16)
+    assert normalize_color_ops(None, None) is None and normalize_color_ops(None, size, 3) is None
+    one = [("brightness", 1.2), ("equalize",)]
+    want = (("brightness", 1.2), ("equalize",))
+    # one chain for every output — a list or a tuple of op tuples —, or one chain or None per output
+    assert normalize_color_ops(one, size, 3) == [want] * 3 and normalize_color_ops(tuple(one), size, 2) == [want] * 2
+    assert normalize_color_ops([one, None, [("invert",)]], size, 3) == [want, None, (("invert",),)]
+    assert normalize_color_ops([one, one], size, 2) == [want, want]
+    # None and empty chains are no operations; all of them: the call without the argument
+    assert normalize_color_ops([None, []], size, 2) is None and normalize_color_ops([], size, 2) is None and normalize_color_ops([None] * 2, size, 2) is None
+    assert normalize_color_ops([[], one], size, 2) == [None, want]
+    # solarize: the layer passes min(max(ceil(t), 0), 256); integers may come as numpy scalars
+    assert normalize_color_ops([("solarize", 229.5)], size, 1) == [(("solarize", 230.0),)]
+    assert normalize_color_ops([("solarize", -7)], size, 1) == [(("solarize", 0.0),)] and normalize_color_ops([("solarize", 1e9)], size, 1) == [(("solarize", 256.0),)]
+    assert normalize_color_ops([("posterize", np.int64(3)), ("contrast", np.float32(0.5))], size, 1) == [(("posterize", 3.0), ("contrast", 0.5))]
+    # what needs no file
+    assert normalize_color_ops(one, size) is None
+
+
+def test_normalize_color_ops_refusals():
+    from pyjpegdecoder_amd.batch import normalize_color_ops
+    size = (24, 16)
+    one = [("invert",)]
+    with pytest.raises(ValueError, match="color_ops needs size"):
+        normalize_color_ops(one, None, 1)
+    with pytest.raises(ValueError, match="color_ops and return_seams do not go together"):
+        normalize_color_ops(one, size, 1, return_seams=True)
+    with pytest.raises(ValueError, match="unknown op 'hue'"):
+        normalize_color_ops([("hue", 0.1)], size, 1)
+    with pytest.raises(ValueError, match="output 1: unknown op 'Brightness'"):
+        normalize_color_ops([None, [("Brightness", 1.0)]], size, 2)
+    with pytest.raises(ValueError, match="5 ops in one chain; at most 4"):
+        normalize_color_ops([("invert",)] * 5, size, 1)
+    for bad in (float("nan"), float("inf"), -float("inf")):
+        with pytest.raises(ValueError, match="is not finite"):
+            normalize_color_ops([("contrast", bad)], size, 1)
+        with pytest.raises(ValueError, match="is not finite"):
+            normalize_color_ops([("solarize", bad)], size, 1)
+    for bits in (0, 9, 2.5, -1):
+        with pytest.raises(ValueError, match="posterize takes 1..8 bits"):
+            normalize_color_ops([("posterize", bits)], size, 1)
+    with pytest.raises(ValueError, match="takes one number"):
+        normalize_color_ops([("brightness",)], size, 1)
+    with pytest.raises(ValueError, match="takes one number"):
+        normalize_color_ops([("brightness", "1.0")], size, 1)
+    with pytest.raises(ValueError, match="takes one number"):
+        normalize_color_ops([("brightness", True)], size, 1)
+    with pytest.raises(ValueError, match="takes no value"):
+        normalize_color_ops([("autocontrast", 5)], size, 1)
+    with pytest.raises(ValueError, match="color_ops has 2 entries for 3 outputs"):
+        normalize_color_ops([one, one], size, 3)
+    # an op that is not wrapped in a chain, ops that are lists, anything else
+    for bad in (("invert",), [["invert"]], "invert", 1.5, [one, "invert"], [[("invert",)], 3]):
+        with pytest.raises(ValueError, match="color_ops must be None, one chain"):
+            normalize_color_ops(bad, size, 2)
+
+
+def test_narrow_takes_the_chains_with_the_outputs():
+    from pyjpegdecoder_amd.batch import _Request, normalize_color_ops
+    a, b = (("invert",),), (("contrast", 0.5),)
+    req = _Request([b"x", b"y", b"z"], None, (24, 16), colour=normalize_color_ops([list(a), None, list(b)], (24, 16), 3))
+    assert req.narrow([2, 0]).colour == [b, a] and req.narrow([1]).colour is None and req.narrow([1, 2]).colour == [None, b]
+    assert req.narrow([1]).plan_kwargs(3) == _Request([b"y"], None, (24, 16)).plan_kwargs(3)
+    views = [(0, None), (2, (1, 1, 4, 4)), (0, (0, 0, 2, 2)), (1, None)]
+    req = _Request([b"x", b"y", b"z"], None, (24, 16), views=views, slots=[0, 1, 2, 3], colour=[a, b, None, None])
+    sub = req.narrow([0])
+    assert sub.colour == [a, None] and sub.slots == [0, 2]
+    assert req.narrow([2]).colour == [b] and req.narrow([1]).colour is None
+    assert req.plan_kwargs(3)["colour"] == [a, b, None, None]
+
+
+# ---- the request: structures and mj_debug_normalise_request -----------------------------------------------------------------------------
+def _batch(sizes):
+    from pyjpegdecoder_amd import _binding as B
+    images = (B.ImageDescC * len(sizes))()
+    for d, (w, h) in zip(images, sizes):
+        d.width, d.height, d.ncomp = w, h, 3
+    b = B.BatchC()
+    b.n_images = len(sizes)
+    b.images = ctypes.cast(images, ctypes.POINTER(B.ImageDescC))
+    return b, images
+
+
+def _normal(lib, batch, **kw):
+    from pyjpegdecoder_amd import _binding as B
+    size = kw.pop("size", (24, 16))
+    r, keep = B.plan_request(batch.n_images, size=(24, 16), **kw)
+    if size is None:
+        r.out_width = r.out_height = 0
+    out = B.PlanRequestC()
+    rc = lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out))
+    return rc, out, lib.mj_last_error(None).decode()
+
+
+def test_the_request_with_colour_operations_is_laid_out_as_the_binding_assumes(lib, tmp_path):
+    from pyjpegdecoder_amd import _binding as B
+    gcc = shutil.which("gcc")
+    assert gcc is not None, "the header is held to a C compiler"
+    flags = ["-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include")]
+    rfields = [f for f, _ in B.PlanRequestC._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(
+        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_colour_request zeroed = {{{0}, 0, 0}, 0};',
+         '  printf("%zu %zu %zu", sizeof(mj_plan_request), sizeof(mj_plan_affine_request), sizeof(mj_plan_colour_request));'] +
+        [f'  printf(" %zu", offsetof(mj_plan_request, {f}));' for f in rfields] +
+        ['  printf(" %zu %zu", offsetof(mj_plan_colour_request, head), offsetof(mj_plan_colour_request, colour));',
+         '  printf(" %zu %zu %zu", sizeof(mj_colour_chain), sizeof(mj_colour_op), offsetof(mj_colour_chain, op));',
+         '  printf(" %d %d", MJ_MODE_COLOUR_OPS, MJ_COLOUR_MAX_OPS);',
+         '  printf(" %d %d %d %d %d %d %d %d %d", MJ_COLOUR_BRIGHTNESS, MJ_COLOUR_COLOR, MJ_COLOUR_CONTRAST, MJ_COLOUR_SHARPNESS, MJ_COLOUR_POSTERIZE,',
+         '         MJ_COLOUR_SOLARIZE, MJ_COLOUR_AUTOCONTRAST, MJ_COLOUR_EQUALIZE, MJ_COLOUR_INVERT);',
+         '  printf(" %d\\n", zeroed.colour == 0 && zeroed.head.affine == 0 && zeroed.head.request.mode == 0);', '  return 0;', '}']))
+    exe = tmp_path / "layout"
+    subprocess.run([gcc] + flags + [str(src), "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    R, A, E = B.PlanRequestC, B.PlanAffineRequestC, B.PlanColourRequestC
+    want = ([ctypes.sizeof(R), ctypes.sizeof(A), ctypes.sizeof(E)] + [getattr(R, f).offset for f in rfields] + [E.head.offset, E.colour.offset] +
+            [ctypes.sizeof(B.ColourChainC), ctypes.sizeof(B.ColourOpC), B.ColourChainC.op.offset, B.MJ_MODE_COLOUR_OPS, B.MJ_COLOUR_MAX_OPS] +
+            [B.COLOUR_OPS[n] for n in ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "autocontrast", "equalize", "invert")] + [1])
+    assert got == want
+    # the request's size and every field's offset are what they were (the flag is a bit of `mode`); the chains' pointer lies behind `affine`
+    assert ctypes.sizeof(R) == 80 and ctypes.sizeof(A) == 96 and E.head.offset == 0 and E.colour.offset == ctypes.sizeof(A) == A.affine.offset + 8
+    assert ctypes.sizeof(B.ColourChainC) == 36 and ctypes.sizeof(B.ColourOpC) == 8 and B.MJ_MODE_COLOUR_OPS == 0x100
+    # plan_request: the flag, one chain per output (None: empty), views and matrices where a request with them has them
+    one = (("brightness", 1.25), ("equalize",))
+    r, keep = B.plan_request(2, size=(24, 16), colour=[one, None], mode="L")
+    ext = keep["colour_request"]
+    assert ctypes.addressof(r) == ctypes.addressof(ext) and r.mode == (B.MJ_MODE_L | B.MJ_MODE_COLOUR_OPS) and r.n_views == 0 and not ext.head.views
+    assert ext.colour[0].n == 2 and ext.colour[1].n == 0 and ext.colour[0].op[0].kind == 1 and ext.colour[0].op[0].value == 1.25 and ext.colour[0].op[1].kind == 8
+    m = (0.5, 0.25, 3.0, -0.25, 0.5, 1.5)
+    r, keep = B.plan_request(2, size=(24, 16), views=[(1, None), (0, (1, 1, 4, 4)), (1, None)], affine=([m, None, m], "nearest", (5,)),
+                             colour=[None, one, one])
+    ext = keep["colour_request"]
+    assert r.n_views == 3 and r.affine == (1 | 5 << 8) and ext.head.views[1].window.width == 4 and tuple(ext.head.affine[2].a) == m and ext.colour[2].n == 2
+    with pytest.raises(ValueError, match="colour: 1 entries, not one for each of the 2 images"):
+        B.plan_request(2, size=(24, 16), colour=[one])
+    with pytest.raises(ValueError, match="colour: 2 entries, not one for each of the 3 views"):
+        B.plan_request(2, size=(24, 16), views=[(0, None), (1, None), (0, None)], colour=[one, one])
+    with pytest.raises(ValueError, match="colour needs size"):
+        B.plan_request(2, colour=[one, one])
+    header = (ROOT / "include" / "mijpeg.h").read_text()
+    assert "const mj_colour_chain *colour;" in header and "mj_plan_affine_request head;" in header
+
+
+def test_no_operations_is_the_zeroed_request(lib):
+    """None and lists of None or empty chains make the byte-identical request of a call without the argument — in Python — and
+    chains that are all empty normalise to the flag's absence in the library"""
+    from pyjpegdecoder_amd import _binding as B
+    from pyjpegdecoder_amd.batch import _Request, normalize_color_ops
+    plain = _Request([b"a", b"b"], None, (24, 16))
+    for ops in (None, [None, None], [[], None], []):
+        req = _Request([b"a", b"b"], None, (24, 16), colour=normalize_color_ops(ops, (24, 16), 2))
+        a, _ = B.plan_request(2, **req.plan_kwargs(3))
+        b, _ = B.plan_request(2, **plain.plan_kwargs(3))
+        assert bytes(a) == bytes(b) and req.plan_kwargs(3) == plain.plan_kwargs(3)
+    batch, keep = _batch([(128, 64), (50, 70)])
+    rc, plain_out, _ = _normal(lib, batch)
+    rc, out, msg = _normal(lib, batch, colour=[None, ()])
+    assert rc == B.MJ_OK and out.mode == 0 and bytes(out) == bytes(plain_out), msg
+    rc, out, msg = _normal(lib, batch, colour=[None, ()], mode="L")
+    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_L, msg
+    # a request with operations keeps the flag, and the mode beside it is normalised as ever (RGB is these files' own)
+    rc, out, msg = _normal(lib, batch, colour=[None, (("invert",),)])
+    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_COLOUR_OPS and out.n_slots == 2, msg
+    rc, out, msg = _normal(lib, batch, colour=[None, (("invert",),)], mode="RGB")
+    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_COLOUR_OPS, msg
+    rc, out, msg = _normal(lib, batch, colour=[(("equalize",),), None], mode="L")
+    assert rc == B.MJ_OK and out.mode == (B.MJ_MODE_L | B.MJ_MODE_COLOUR_OPS), msg
+    rc, out, msg = _normal(lib, batch, colour=[None, (("invert",),), None], views=[(1, None), (0, (1, 1, 4, 4)), (1, None)])
+    assert rc == B.MJ_OK and out.n_views == 3 and out.mode == B.MJ_MODE_COLOUR_OPS, msg
+    # a zeroed request with a mode that was never given the bit is what it was
+    r = B.PlanRequestC()
+    out = B.PlanRequestC()
+    assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_OK and bytes(out)[:16] == bytes(16)
+
+
+def test_request_refusals(lib):
+    from pyjpegdecoder_amd import _binding as B
+    batch, keep = _batch([(128, 64), (50, 70)])
+    ok = [(("invert",),), (("contrast", 0.5),)]
+    rc, _, msg = _normal(lib, batch, colour=ok, size=None)
+    assert rc == B.MJ_ERR_INVALID and "colour_ops needs a size" in msg
+    for bad, why in (((("brightness", float("nan")),), "an op's value is not finite"), ((("solarize", float("inf")),), "an op's value is not finite"),
+                     (((12, 1.0),), "an op's kind is none of MJ_COLOUR_*"), (((0,),), "an op's kind is none of MJ_COLOUR_*"),
+                     ((("posterize", 0),), "posterize takes 1..8 bits"), ((("posterize", 9),), "posterize takes 1..8 bits")):
+        rc, _, msg = _normal(lib, batch, colour=[None, bad])
+        assert rc == B.MJ_ERR_INVALID and "colour_ops: output 1: " + why in msg, (bad, msg)
+    r, keep_r = B.plan_request(2, size=(24, 16), colour=ok)
+    keep_r["colour"][0].n = 5                                   # (more than four ops)
+    out = B.PlanRequestC()
+    assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
+    assert "colour_ops: output 0: a chain has 0..MJ_COLOUR_MAX_OPS ops" in lib.mj_last_error(None).decode()
+    r, keep_r = B.plan_request(2, size=(24, 16), colour=ok)
+    keep_r["colour_request"].colour = None                      # (the flag without the array)
+    assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
+    assert "colour_ops without its array" in lib.mj_last_error(None).decode()
+    # a mode that is none of MJ_MODE_* stays refused beside the flag
+    r, keep_r = B.plan_request(2, size=(24, 16), colour=ok)
+    r.mode = 2 | B.MJ_MODE_COLOUR_OPS
+    assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
+    assert "mode 2 is none of MJ_MODE_*" in lib.mj_last_error(None).decode()
+
+
+def test_the_library_exports_the_host_twin(lib):
+    from pyjpegdecoder_amd import _binding as B
+    assert "mj_host_colour_ops" in B.EXPORTS and hasattr(lib, "mj_host_colour_ops")
