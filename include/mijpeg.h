@@ -482,16 +482,33 @@ typedef struct {
  *                          scale = 255.0 / (hi - lo), offset = -lo * scale, v -> clip((int)(v * scale + offset), 0, 255) in doubles
  *   MJ_COLOUR_EQUALIZE     per component with histogram h (no mask): one non-empty bin, or step = (pixels - the last non-empty bin's
  *                          count) / 255 == 0: the identity; else n = step / 2 and for i = 0..255: i -> min(255, n / step), n += h[i]
+ *   pass(fr) along an axis of length n, per component (Pillow's BoxBlur.c; fr a float32 box radius): r = (int)fr, ww = (uint32)((float)
+ *                          (1 << 24) / (fr * 2 + 1)), fw = ((1 << 24) - (2 r + 1) ww) / 2, and out[x] = (ww * sum of in[clamp(x + d)],
+ *                          d = -r..r, + fw * (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + (1 << 23)) >> 24 with clamp to 0 .. n - 1,
+ *                          in 32-bit unsigned arithmetic.  Every pass stores bytes, and the next pass reads those bytes.  Width and
+ *                          height are the image's axes in every layout; the width passes come first
+ *   MJ_COLOUR_BOX_BLUR     im.filter(ImageFilter.BoxBlur(value)): pass((float)value) along the width, then along the height
+ *   MJ_COLOUR_GAUSSIAN_BLUR  im.filter(ImageFilter.GaussianBlur(value)): three passes along the width, then three along the height,
+ *                          all with fr = l + a, in float32 but for the double square root and floor: sigma2 = value * value / 3,
+ *                          L = (float)sqrt(12.0 * sigma2 + 1.0), l = (float)floor((L - 1.0) / 2.0), a = (2 l + 1) * (l (l + 1) - 3 sigma2),
+ *                          a = a / (6 * (sigma2 - (l + 1) (l + 1)))
+ *                          Both take one radius 0 <= value <= 1024 (0: the identity; Pillow's per-axis radii are not offered); the
+ *                          fill pixels take part as in every op, and the blur commutes with the mirror
  * The launches (csrc/colour.hip): the plan's resize launch runs exactly as that of the MJ_DTYPE_U8, unmirrored, identity-slot
  * request would, into a plan-owned canvas buffer in the plan's layout.  Then, for every step s of the longest chain: a histogram
  * launch over the outputs whose op s is contrast, autocontrast or equalize (32-bit bins: LDS atomics, merged into a zeroed
  * per-output array); a launch of one wavefront per output that builds the 3 x 256 byte table of every table-shaped op, from the
  * statistics where it has some — they never leave the device, nothing synchronises —; and one launch that applies step s to
  * every output (a table look-up, color, sharpness, or a copy where the chain has ended) from one canvas into a second, the last
- * step into the caller's array at the output's slot, mirrored if flagged, through the output table.  mj_plan_time_resize times
+ * step into the caller's array at the output's slot, mirrored if flagged, through the output table.  The outputs whose op s is a
+ * blur are left out by that launch (which is not made where every output's op s is a blur) and taken by one more: a workgroup holds one component plane of one output in LDS, runs all
+ * the passes there and stores the last one as above; a plan whose canvas is too large for that (two planes of ow rounded up to
+ * four, times oh, bytes: more than 160 KB) runs one launch per pass through a third plan-owned canvas instead (option MJ_BLUR
+ * forces that route).  r, ww and fw are computed on the host, once per op.  mj_plan_time_resize times
  * these launches too.  mj_host_colour_ops is the host twin.
  * MJ_ERR_INVALID, naming the output: the flag without a size ("colour_ops needs a size"), a NULL array, n outside 0..4, a kind that
- * is none of MJ_COLOUR_*, a value that is not finite, posterize bits that are not one of 1..8.  Not offered yet: hue (Pillow's HSV
+ * is none of MJ_COLOUR_*, a value that is not finite, posterize bits that are not one of 1..8, a blur radius outside 0..1024
+ * (Pillow takes a negative Gaussian radius; this library refuses it).  Not offered yet: hue (Pillow's HSV
  * round trip), autocontrast's cutoffs and masks, more than MJ_COLOUR_MAX_OPS ops. */
 #define MJ_MODE_COLOUR_OPS 0x100
 #define MJ_COLOUR_MAX_OPS 4
@@ -504,9 +521,11 @@ typedef struct {
 #define MJ_COLOUR_AUTOCONTRAST 7
 #define MJ_COLOUR_EQUALIZE     8
 #define MJ_COLOUR_INVERT       9
+#define MJ_COLOUR_GAUSSIAN_BLUR 10
+#define MJ_COLOUR_BOX_BLUR     11
 typedef struct {
     int32_t kind;               /* MJ_COLOUR_* */
-    float value;                /* the factor, bits or threshold; ignored by autocontrast, equalize and invert */
+    float value;                /* the factor, bits, threshold or radius; ignored by autocontrast, equalize and invert */
 } mj_colour_op;
 typedef struct {
     int32_t n;                  /* 0..MJ_COLOUR_MAX_OPS ops, applied in order */
@@ -752,6 +771,8 @@ int mj_context_launch_clock(mj_context *ctx, float *shader_mhz, float *launch_ms
  *                     band pipeline: never | from 2 048 images on | always;  MJ_PROG_CHUNK  128..65536 bytes per chunk (512)
  *   MJ_PLACE_WINDOW   0 | 1  a placed plan decodes only the source range its canvas needs: never | whenever that is less than the
  *                     images or windows (default: where the caller gave windows; whole images stay whole, see csrc/resize.hip)
+ *   MJ_BLUR           passes  the blur ops of a plan with colour operations run one launch per pass through a third canvas, whatever
+ *                     the canvas's size (default: only where two planes of the canvas do not fit in LDS, see MJ_COLOUR_GAUSSIAN_BLUR)
  *   MJ_LANES_WAVES    1..16   MJ_LANES_PER_WAVE  1..64 (the 11-bit lane form reads 1 as 2)   MJ_LANES_RING  64 | 128
  *   MJ_STAGE2_CHUNK   1..4096 strips per stage-2 job
  *   MJ_FUSED          0 | 1  (0 = mj_plan_execute always launches the stages separately)

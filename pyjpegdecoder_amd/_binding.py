@@ -36,8 +36,10 @@ MJ_MODE_NATIVE, MJ_MODE_L, MJ_MODE_RGB = 0, 1, 3
 MJ_MODE_COLOUR_OPS = 0x100
 MJ_COLOUR_MAX_OPS = 4
 COLOUR_OPS = {"brightness": 1, "color": 2, "contrast": 3, "sharpness": 4, "posterize": 5, "solarize": 6, "autocontrast": 7,
-              "equalize": 8, "invert": 9}
-COLOUR_VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize")        # the ops that take a value
+              "equalize": 8, "invert": 9, "gaussian_blur": 10, "box_blur": 11}
+COLOUR_VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "gaussian_blur", "box_blur")        # the ops that take a value
+COLOUR_BLURS = ("gaussian_blur", "box_blur")           # ... whose value is a radius, 0 .. MJ_COLOUR_MAX_RADIUS
+MJ_COLOUR_MAX_RADIUS = 1024
 # the output colour modes by Pillow's name: MJ_MODE_*, which is the component count of the output
 MODES = {"L": MJ_MODE_L, "RGB": MJ_MODE_RGB}
 
@@ -195,7 +197,7 @@ class PlanColourRequestC(ctypes.Structure):
 
 def colour_chain(chain) -> ColourChainC:
     """mj_colour_chain from None or a sequence of at most MJ_COLOUR_MAX_OPS ops ``(name,)`` / ``(name, value)`` (an MJ_COLOUR_* number
-    passes for the name)."""
+    passes for the name).  A blur that comes without its radius gets NaN, which the library refuses: no radius is not radius 0."""
     c = ColourChainC()
     ops = list(chain) if chain is not None else []
     if len(ops) > MJ_COLOUR_MAX_OPS:
@@ -203,7 +205,8 @@ def colour_chain(chain) -> ColourChainC:
     c.n = len(ops)
     for s, op in enumerate(ops):
         c.op[s].kind = COLOUR_OPS[op[0]] if isinstance(op[0], str) else int(op[0])
-        c.op[s].value = float(op[1]) if len(op) > 1 else 0.0
+        blur = c.op[s].kind in (COLOUR_OPS["gaussian_blur"], COLOUR_OPS["box_blur"])
+        c.op[s].value = float(op[1]) if len(op) > 1 else float("nan") if blur else 0.0
     return c
 
 

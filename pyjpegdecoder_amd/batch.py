@@ -841,6 +841,8 @@ def _colour_chain(chain, where: str) -> Optional[Tuple[tuple, ...]]:
                 raise ValueError(f"color_ops: {where}posterize takes 1..8 bits, not {op[1]!r}")
         elif name == "solarize":            # (v stays where v < t: for a byte, where v < ceil(t))
             v = float(min(max(math.ceil(v), 0), 256))
+        elif name in B.COLOUR_BLURS and not 0 <= v <= B.MJ_COLOUR_MAX_RADIUS:
+            raise ValueError(f"color_ops: {where}{name} takes a radius of 0..{B.MJ_COLOUR_MAX_RADIUS}, not {op[1]!r}")
         ops.append((name, v))
     return tuple(ops) or None
 
@@ -852,7 +854,9 @@ def normalize_color_ops(color_ops, size, n_outputs: Optional[int] = None, return
     ``views``).  A chain is a sequence of at most four ops, applied in order to the finished canvas as to a Pillow image of the
     output's mode, each op the one Pillow call that defines its bytes (tools/colour_model.py): ``("brightness", f)``, ``("color", f)``,
     ``("contrast", f)``, ``("sharpness", f)`` — ``ImageEnhance.<Name>(im).enhance(f)`` —, ``("posterize", bits)`` with 1..8 bits,
-    ``("solarize", t)``, ``("autocontrast",)``, ``("equalize",)``, ``("invert",)`` — ``ImageOps.<name>(im[, value])``.  An op is always
+    ``("solarize", t)``, ``("autocontrast",)``, ``("equalize",)``, ``("invert",)`` — ``ImageOps.<name>(im[, value])`` —,
+    ``("gaussian_blur", radius)``, ``("box_blur", radius)`` with one radius of 0..1024 — ``im.filter(ImageFilter.GaussianBlur(radius))``
+    / ``BoxBlur(radius)``.  An op is always
     a tuple whose first element is a string; that is how one chain is told from a list of chains.  The operations need ``size`` and
     do not go with ``return_seams``.  ``n_outputs`` None: what needs no file.  ValueError otherwise."""
     if color_ops is None:
@@ -1379,7 +1383,9 @@ class BatchDecoder:
         canvas (:func:`normalize_color_ops`): None, one chain for every output, or a list with one chain or None per output — per
         file, per view with ``views``.  A chain is a sequence of at most four ops — ``("brightness", f)``, ``("color", f)``,
         ``("contrast", f)``, ``("sharpness", f)``, ``("posterize", bits)``, ``("solarize", t)``, ``("autocontrast",)``,
-        ``("equalize",)``, ``("invert",)`` —, each what the one call of Pillow's ``ImageEnhance`` / ``ImageOps`` of that name does.
+        ``("equalize",)``, ``("invert",)`` —, each what the one call of Pillow's ``ImageEnhance`` / ``ImageOps`` of that name does,
+        ``("gaussian_blur", radius)`` or ``("box_blur", radius)`` with one radius of 0..1024 — ``im.filter(ImageFilter.GaussianBlur(radius))``
+        / ``BoxBlur(radius)``, the random blur of the SimCLR / MoCo / BYOL / DINO recipes.
         The order is decode, mode, orientation, affine, window, resize / place / fill, colour ops, mirror, element type
         (torchvision's: crop, flip, jitter, ToTensor, Normalize — every op commutes with the flip): output k is its chain applied to
         the uint8 canvas the call gives without the argument, without ``mirror`` and with ``dtype="uint8"`` — fill pixels

@@ -5,9 +5,9 @@
 //
 // The arithmetic is Pillow's (tools/colour_model.py restates it; include/mijpeg.h has the rules), and it is written once, in
 // mijpeg_internal.h, for the kernels and for the host twin (mj_host_colour_ops): colour_blend, colour_smooth,
-// colour_table_entry.  float32 and double operations round one by one (the library is compiled with -ffp-contract=off).
+// colour_table_entry, blur_pixel.  float32 and double operations round one by one (the library is compiled with -ffp-contract=off).
 //
-// Per step s of the plan's longest chain, up to three launches:
+// Per step s of the plan's longest chain, up to three launches, and one more (or one per pass) where a chain blurs:
 //   k_colour_hist    only where some output's op s is contrast, autocontrast or equalize, over those outputs: a workgroup counts
 //                    kColourHistPixels pixels of one canvas into 4 x 256 32-bit bins in LDS (components 0..2 and L) with LDS
 //                    atomics — a lane takes consecutive pixels and adds once per run of one value — and adds the bins that are
@@ -18,6 +18,9 @@
 //                    the source canvas, edges copied), or a copy where the chain has ended.  Steps go from one canvas to the
 //                    other (sharpness cannot run in place); the last step stores at the output's slot, column ow - 1 - x where the
 //                    output is mirrored, through the output table in the plan's element type
+//   k_colour_blur    only where some output's op s is gaussian_blur or box_blur, over those outputs, which k_colour_apply leaves out:
+//                    a workgroup holds one component plane of one output in LDS and runs all the passes there; on plans whose canvas
+//                    LDS does not hold, k_colour_blur_pass instead, one launch per pass through a third canvas (further down)
 // Everything addresses a canvas through a pixel's place p and two strides (DevColourOutput's comment), so that one kernel serves
 // the four layouts.  The statistics never leave the device and nothing waits for the host.
 #include <math.h>
@@ -125,6 +128,30 @@ __global__ __launch_bounds__(64) void k_colour_tables(const ColourArgs a, const 
     }
 }
 
+// Components c0 .. c0 + N - 1 of the pixel at place p = (x, y) of output k after step `step`, values r[0 .. N - 1]: into the other
+// canvas, or — the chain's last step — to the output's slot, mirrored where flagged, through the output table.  Every launch that
+// ends a step stores here.
+template <int C, int N>
+__device__ inline void colour_store(const ColourArgs &a, const DevColourOutput &o, int step, int64_t k, int64_t p, int x, int y, int c0, const unsigned *r) {
+    const int64_t npix = (int64_t)a.ow * a.oh;
+    const int64_t ps = a.layout >= 2 ? 1 : C, cs = a.layout >= 2 ? npix : 1;
+    if (step + 1 < a.steps) {
+        unsigned char *dst = a.canvas[(step + 1) & 1] + k * npix * C;
+        for (int c = 0; c < N; ++c) dst[p * ps + (c0 + c) * cs] = (unsigned char)r[c];
+        return;
+    }
+    // the last step: to the output's slot, mirrored where flagged, through the output table
+    const bool rowmajor = (a.layout & 1) != 0;
+    const int xm = o.mirror ? a.ow - 1 - x : x;
+    const int64_t pm = rowmajor ? (int64_t)y * a.ow + xm : (int64_t)xm * a.oh + y;
+    for (int c = 0; c < N; ++c) {
+        const int64_t e = o.dst_off + pm * ps + (c0 + c) * cs;
+        if (a.esize == 1) static_cast<unsigned char *>(a.dst)[e] = (unsigned char)r[c];
+        else if (a.esize == 2) static_cast<uint16_t *>(a.dst)[e] = static_cast<const uint16_t *>(a.lut)[(c0 + c) * 256 + r[c]];
+        else static_cast<uint32_t *>(a.dst)[e] = static_cast<const uint32_t *>(a.lut)[(c0 + c) * 256 + r[c]];
+    }
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void k_colour_apply(const ColourArgs a, const int step) {
     const int64_t npix = (int64_t)a.ow * a.oh, per_output = (npix + 255) / 256;
@@ -155,20 +182,111 @@ __global__ __launch_bounds__(256) void k_colour_apply(const ColourArgs a, const 
             r[c] = colour_blend((int)colour_smooth(nb), (int)v[c], o.value[step]);
         }
     }
-    if (step + 1 < a.steps) {
-        unsigned char *dst = a.canvas[(step + 1) & 1] + k * npix * C;
-        for (int c = 0; c < C; ++c) dst[p * ps + c * cs] = (unsigned char)r[c];
+    // (an output whose op is a blur is the blur launch's.  Asked here, behind the loads and the op, and not on top: the code of
+    // every other output stays close to what it was; the price is that a blur output's pixel is read for nothing — launch_colour_t
+    // does not launch this kernel for a step whose outputs are all blurs)
+    if (colour_is_blur(kind)) return;
+    colour_store<C, C>(a, o, step, k, p, x, y, 0, r);
+}
+
+// ---- the blurs (MJ_COLOUR_GAUSSIAN_BLUR, MJ_COLOUR_BOX_BLUR): passes of blur_pixel along the width, then along the height ----------
+// The plane-resident launch: workgroup wg takes component wg % C of the wg / C-th output of the step's blur list.  It loads the
+// plane into LDS as oh rows of `pitch` dwords (ow bytes rounded up), runs every pass from one LDS plane to the other — a lane takes
+// one dword, four neighbouring pixels of a row, in both directions: along the width it slides the window over its four pixels, along
+// the height it sums the same dword of the rows y - r .. y + r, byte by byte —, and stores the last plane through colour_store.
+// The bytes of a row's last dword beyond ow (padding) are computed like pixels and never stored to the canvas.  A pixel's taps are
+// clamped to 0 .. ow - 1, so no pixel reads padding; only the lanes' work on the padding bytes themselves may read padding — of
+// the first plane: bytes nobody wrote — inside the same dword, and what they make of it is padding again.
+__device__ inline uint32_t blur_dword_along(const uint8_t *row, int n, int x0, int r, uint32_t ww, uint32_t fw) {
+    uint32_t s = blur_window(row, 1, n, x0, r), out = 0;
+    for (int j = 0; j < 4; ++j) {
+        const int x = x0 + j;
+        if (j) s += (uint32_t)row[min(x + r, n - 1)] - (uint32_t)row[max(x - 1 - r, 0)];
+        out |= blur_byte(ww, fw, s, (uint32_t)row[max(x - r - 1, 0)] + row[min(x + r + 1, n - 1)]) << (8 * j);
+    }
+    return out;
+}
+__device__ inline uint32_t blur_dword_across(const uint32_t *col, int pitch, int n, int y, int r, uint32_t ww, uint32_t fw) {
+    const int lo = max(y - r, 0), hi = min(y + r, n - 1);
+    const uint32_t cl = (uint32_t)(lo - (y - r)), cr = (uint32_t)(y + r - hi), top = col[0], bot = col[(n - 1) * pitch];
+    uint32_t s[4];
+    for (int j = 0; j < 4; ++j) s[j] = cl * (top >> (8 * j) & 0xFFu) + cr * (bot >> (8 * j) & 0xFFu);
+    for (int i = lo; i <= hi; ++i) {
+        const uint32_t w = col[i * pitch];
+        for (int j = 0; j < 4; ++j) s[j] += w >> (8 * j) & 0xFFu;
+    }
+    const uint32_t fa = col[max(y - r - 1, 0) * pitch], fb = col[min(y + r + 1, n - 1) * pitch];
+    uint32_t out = 0;
+    for (int j = 0; j < 4; ++j) out |= blur_byte(ww, fw, s[j], (fa >> (8 * j) & 0xFFu) + (fb >> (8 * j) & 0xFFu)) << (8 * j);
+    return out;
+}
+
+template <int C>
+__global__ __launch_bounds__(1024) void k_colour_blur(const ColourArgs a, const ColourBlurArgs b, const int step) {
+    extern __shared__ uint32_t blur_planes[];
+    const int64_t wg = workgroup_index();
+    const int first = b.first[step], n_list = b.first[step + 1] - first;
+    if (wg >= (int64_t)n_list * C) return;
+    const int64_t k = b.list[first + (int)(wg / C)];
+    const int c = (int)(wg % C), t = threadIdx.x, nt = blockDim.x;
+    const DevColourOutput &o = a.outputs[k];
+    const int r = o.ivalue[step], passes = colour_blur_passes(o.kind[step]);
+    const uint32_t ww = b.weights[(k * 4 + step) * 2], fw = b.weights[(k * 4 + step) * 2 + 1];
+    const int ow = a.ow, oh = a.oh, pitch = (ow + 3) >> 2, dwords = pitch * oh, npix = ow * oh;       // (npix <= kBlurLdsMax / 2)
+    const bool rowmajor = (a.layout & 1) != 0;
+    const int64_t ps = a.layout >= 2 ? 1 : C, cs = a.layout >= 2 ? npix : 1;
+    uint32_t *cur = blur_planes, *next = blur_planes + dwords;
+    const unsigned char *src = a.canvas[step & 1] + k * npix * C + c * cs;
+    for (int p = t; p < npix; p += nt) {
+        const int x = rowmajor ? p % ow : p / oh, y = rowmajor ? p / ow : p % oh;
+        reinterpret_cast<uint8_t *>(cur)[y * pitch * 4 + x] = src[p * ps];
+    }
+    __syncthreads();
+    for (int pass = 0; pass < 2 * passes; ++pass) {
+        for (int i = t; i < dwords; i += nt) {
+            const int y = i / pitch, xd = i - y * pitch;
+            next[i] = pass < passes ? blur_dword_along(reinterpret_cast<const uint8_t *>(cur + y * pitch), ow, xd * 4, r, ww, fw)
+                                    : blur_dword_across(cur + xd, pitch, oh, y, r, ww, fw);
+        }
+        __syncthreads();
+        uint32_t *swap = cur; cur = next; next = swap;
+    }
+    for (int p = t; p < npix; p += nt) {
+        const int x = rowmajor ? p % ow : p / oh, y = rowmajor ? p / ow : p % oh;
+        const unsigned v = reinterpret_cast<const uint8_t *>(cur)[y * pitch * 4 + x];
+        colour_store<C, 1>(a, o, step, k, p, x, y, c, &v);
+    }
+}
+
+// The pass launch, for canvases whose two planes LDS does not hold: one thread per pixel of the step's blur outputs, pass `pass` of
+// the output's 2 or 6 — canvas A = canvas[step & 1] -> scratch T -> A -> ... -> T -> colour_store (every chain of passes is even, so
+// its last pass reads T).  A's part of a blur output is free within the step: no other launch of the step reads it.
+template <int C>
+__global__ __launch_bounds__(256) void k_colour_blur_pass(const ColourArgs a, const ColourBlurArgs b, const int step, const int pass) {
+    const int64_t npix = (int64_t)a.ow * a.oh, per_output = (npix + 255) / 256;
+    const int64_t wg = workgroup_index();
+    const int first = b.first[step], n_list = b.first[step + 1] - first;
+    if (wg >= n_list * per_output) return;
+    const int64_t k = b.list[first + (int)(wg / per_output)], p = (wg % per_output) * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const DevColourOutput &o = a.outputs[k];
+    const int passes = colour_blur_passes(o.kind[step]);
+    if (pass >= 2 * passes) return;
+    const bool rowmajor = (a.layout & 1) != 0;
+    const int x = rowmajor ? (int)(p % a.ow) : (int)(p / a.oh), y = rowmajor ? (int)(p / a.ow) : (int)(p % a.oh);
+    const int64_t ps = a.layout >= 2 ? 1 : C, cs = a.layout >= 2 ? npix : 1;
+    const int64_t sx = rowmajor ? 1 : a.oh, sy = rowmajor ? a.ow : 1;
+    const bool along = pass < passes;
+    const unsigned char *line = (pass & 1 ? b.scratch : a.canvas[step & 1]) + k * npix * C + (along ? p - x * sx : p - y * sy) * ps;
+    unsigned v[C];
+    for (int c = 0; c < C; ++c)
+        v[c] = blur_pixel(line + c * cs, (along ? sx : sy) * ps, along ? a.ow : a.oh, along ? x : y, o.ivalue[step], b.weights[(k * 4 + step) * 2], b.weights[(k * 4 + step) * 2 + 1]);
+    if (pass + 1 < 2 * passes) {
+        unsigned char *dst = (pass & 1 ? a.canvas[step & 1] : b.scratch) + k * npix * C;
+        for (int c = 0; c < C; ++c) dst[p * ps + c * cs] = (unsigned char)v[c];
         return;
     }
-    // the last step: to the output's slot, mirrored where flagged, through the output table
-    const int xm = o.mirror ? a.ow - 1 - x : x;
-    const int64_t pm = rowmajor ? (int64_t)y * a.ow + xm : (int64_t)xm * a.oh + y;
-    for (int c = 0; c < C; ++c) {
-        const int64_t e = o.dst_off + pm * ps + c * cs;
-        if (a.esize == 1) static_cast<unsigned char *>(a.dst)[e] = (unsigned char)r[c];
-        else if (a.esize == 2) static_cast<uint16_t *>(a.dst)[e] = static_cast<const uint16_t *>(a.lut)[c * 256 + r[c]];
-        else static_cast<uint32_t *>(a.dst)[e] = static_cast<const uint32_t *>(a.lut)[c * 256 + r[c]];
-    }
+    colour_store<C, C>(a, o, step, k, p, x, y, 0, v);
 }
 
 dim3 grid_for(int64_t total) {
@@ -177,8 +295,12 @@ dim3 grid_for(int64_t total) {
 }
 
 template <int C>
-hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a) {
+hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b) {
     const int64_t npix = (int64_t)a.ow * a.oh;
+    static OncePerDevice attr_once;
+    attr_once.run([&] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_colour_blur<C>), hipFuncAttributeMaxDynamicSharedMemorySize, kBlurLdsMax);
+    });
     for (int s = 0; s < a.steps; ++s) {
         const int n_list = a.hist_first[s + 1] - a.hist_first[s];
         if (n_list > 0) {
@@ -187,7 +309,16 @@ hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a) {
             hipLaunchKernelGGL((k_colour_hist<C>), grid_for(n_list * chunks), dim3(256), 0, stream, a, s);
         }
         if (a.tables_at >> s & 1) hipLaunchKernelGGL((k_colour_tables<C>), grid_for(a.n_outputs), dim3(64), 0, stream, a, s);
-        hipLaunchKernelGGL((k_colour_apply<C>), grid_for(a.n_outputs * ((npix + 255) / 256)), dim3(256), 0, stream, a, s);
+        const int n_blur = b.first[s + 1] - b.first[s];
+        // (k_colour_apply reads a blur output's pixel before it returns: a step whose outputs are ALL blurs goes without the launch)
+        if (n_blur < a.n_outputs) hipLaunchKernelGGL((k_colour_apply<C>), grid_for(a.n_outputs * ((npix + 255) / 256)), dim3(256), 0, stream, a, s);
+        if (n_blur > 0 && b.lds) {
+            const int dwords = b.lds / 8;
+            hipLaunchKernelGGL((k_colour_blur<C>), grid_for((int64_t)n_blur * C), dim3((unsigned)std::min(1024, (dwords + 63) & ~63)), (size_t)b.lds, stream, a, b, s);
+        } else if (n_blur > 0) {
+            for (int pass = 0; pass < b.passes[s]; ++pass)
+                hipLaunchKernelGGL((k_colour_blur_pass<C>), grid_for(n_blur * ((npix + 255) / 256)), dim3(256), 0, stream, a, b, s, pass);
+        }
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -198,6 +329,21 @@ template <int C>
 void colour_host_op(const uint8_t *src, int w, int h, const mj_colour_op &op, uint8_t *out) {
     const int64_t npix = (int64_t)w * h;
     const int kind = op.kind, iv = colour_ivalue(op);
+    if (colour_is_blur(kind)) {
+        const BlurPass b = colour_blur_pass(op);
+        const int passes = colour_blur_passes(kind);
+        std::vector<uint8_t> cur(src, src + npix * C), next((size_t)npix * C);
+        for (int pass = 0; pass < 2 * passes; ++pass) {
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x)
+                    for (int c = 0; c < C; ++c)
+                        next[(size_t)(((int64_t)y * w + x) * C + c)] = (uint8_t)(pass < passes ? blur_pixel(cur.data() + (int64_t)y * w * C + c, C, w, x, b.r, b.ww, b.fw)
+                                                                                             : blur_pixel(cur.data() + (int64_t)x * C + c, (int64_t)w * C, h, y, b.r, b.ww, b.fw));
+            cur.swap(next);
+        }
+        memcpy(out, cur.data(), (size_t)npix * C);
+        return;
+    }
     if (colour_is_table(kind)) {
         std::vector<uint32_t> hist(4 * 256, 0);
         std::vector<unsigned long long> prefix(4 * 256, 0);
@@ -245,9 +391,10 @@ const char *colour_fault(const mj_colour_chain &c) {
     if (c.n < 0 || c.n > MJ_COLOUR_MAX_OPS) return "a chain has 0..MJ_COLOUR_MAX_OPS ops";
     for (int s = 0; s < c.n; ++s) {
         const mj_colour_op &op = c.op[s];
-        if (op.kind < MJ_COLOUR_BRIGHTNESS || op.kind > MJ_COLOUR_INVERT) return "an op's kind is none of MJ_COLOUR_*";
-        const bool valued = op.kind <= MJ_COLOUR_SOLARIZE;
+        if (op.kind < MJ_COLOUR_BRIGHTNESS || op.kind > MJ_COLOUR_BOX_BLUR) return "an op's kind is none of MJ_COLOUR_*";
+        const bool valued = op.kind <= MJ_COLOUR_SOLARIZE || colour_is_blur(op.kind);
         if (valued && !std::isfinite(op.value)) return "an op's value is not finite";
+        if (colour_is_blur(op.kind) && !(op.value >= 0.0f && op.value <= kBlurMaxRadius)) return "a blur takes a radius of 0..1024";
         if (op.kind == MJ_COLOUR_POSTERIZE && !(op.value >= 1.0f && op.value <= 8.0f && op.value == floorf(op.value))) return "posterize takes 1..8 bits";
     }
     return nullptr;
@@ -256,12 +403,32 @@ const char *colour_fault(const mj_colour_chain &c) {
 int colour_ivalue(const mj_colour_op &op) {
     if (op.kind == MJ_COLOUR_POSTERIZE) return ~((1 << (8 - (int)op.value)) - 1) & 0xFF;
     if (op.kind == MJ_COLOUR_SOLARIZE) return (int)std::min(std::max(ceilf(op.value), 0.0f), 256.0f);
+    if (colour_is_blur(op.kind)) return colour_blur_pass(op).r;
     return 0;
 }
 
-hipError_t launch_colour(hipStream_t stream, const ColourArgs &a) {
+// Pillow's BoxBlur.c: the box radius of a Gaussian's three passes (_gaussian_blur_radius: float32, the square root and the floor
+// in double) and the weights of a pass (ImagingLineBoxBlur8), every operation rounded on its own
+BlurPass colour_blur_pass(const mj_colour_op &op) {
+    float fr = op.value;
+    if (op.kind == MJ_COLOUR_GAUSSIAN_BLUR) {
+        const float sigma2 = op.value * op.value / 3;
+        const float L = (float)sqrt(12.0 * sigma2 + 1.0);
+        const float l = (float)floor((L - 1.0) / 2.0);
+        float a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2);
+        a /= 6 * (sigma2 - (l + 1) * (l + 1));
+        fr = l + a;
+    }
+    BlurPass b;
+    b.r = (int)fr;
+    b.ww = (uint32_t)((float)(1 << 24) / (fr * 2 + 1));
+    b.fw = ((1u << 24) - (uint32_t)(b.r * 2 + 1) * b.ww) / 2;
+    return b;
+}
+
+hipError_t launch_colour(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b) {
     if (a.n_outputs <= 0 || a.steps <= 0) return hipSuccess;
-    return a.C == 3 ? launch_colour_t<3>(stream, a) : launch_colour_t<1>(stream, a);
+    return a.C == 3 ? launch_colour_t<3>(stream, a, b) : launch_colour_t<1>(stream, a, b);
 }
 
 }  // namespace mj

@@ -497,8 +497,8 @@ void affine_host(const uint8_t *src, const DevAffineImage &im, const int32_t *ta
 hipError_t launch_affine(hipStream_t stream, const AffineArgs &a, int ncomp, int out_ncomp);
 // ---- colour.hip: colour operations on the finished canvas (mj_plan_request.mode with MJ_MODE_COLOUR_OPS; tools/colour_model.py)
 // One output of a plan with colour operations: its chain (n ops; value: the factor of brightness, color, contrast and sharpness;
-// ivalue: posterize's MASK and solarize's clamped threshold, as integers — colour_ivalue), where its elements go in the caller's
-// array (dst_off, in ELEMENTS) and whether it is mirrored.
+// ivalue: posterize's MASK and solarize's clamped threshold, as integers — colour_ivalue; a blur's r, with ww and fw beside it —
+// colour_blur_pass), where its elements go in the caller's array (dst_off, in ELEMENTS) and whether it is mirrored.
 struct DevColourOutput {
     int64_t dst_off;
     int32_t n, mirror;
@@ -521,7 +521,23 @@ struct ColourArgs {
     int32_t hist_first[5];
     int32_t n_outputs, ow, oh, C, layout, esize, steps, tables_at;
 };
+// What the blur launches take beside ColourArgs (which the other launches take as it was).  list[first[s] .. first[s + 1]): the
+// outputs whose op s is a blur (the plan's list array, behind the histogram lists); passes[s]: the passes of step s's longest
+// blur (6: some Gaussian, 2: boxes only, 0: no blur).  lds: the bytes of LDS a workgroup of the plane-resident launch takes — two
+// planes of oh rows of ow bytes rounded up to whole dwords —, or 0 on a plan that blurs pass by pass through `scratch`, a third
+// canvas (kBlurLdsMax; option MJ_BLUR)
+struct ColourBlurArgs {
+    const int32_t *list;
+    const uint32_t *weights;            // [n_outputs][4 steps][2]: ww and fw of output k's op s where that is a blur (the record keeps its size)
+    uint8_t *scratch;
+    int32_t first[5];
+    int32_t passes[4];
+    int32_t lds;
+};
 constexpr int kColourHistPixels = 4096;       // pixels of a canvas one workgroup of the histogram launch counts
+constexpr int kBlurLdsMax = 160 * 1024;       // the LDS of a gfx950 workgroup: what two planes of a canvas must fit in
+constexpr float kBlurMaxRadius = 1024.0f;
+inline int64_t blur_lds_bytes(int ow, int oh) { return 2 * (int64_t)((ow + 3) & ~3) * oh; }
 // Image.blend of one byte (tools/colour_model.py: blend); every operation rounds on its own (-ffp-contract=off, host and device)
 __host__ __device__ inline unsigned colour_blend(int d, int v, float alpha) {
     const float t = (float)d + alpha * (float)(v - d);
@@ -537,8 +553,25 @@ __host__ __device__ inline unsigned colour_smooth(const float p[3][3]) {
     ss += (p[0][0] * k1 + p[0][1] * k1) + p[0][2] * k1;
     return ss <= 0.0f ? 0u : ss >= 255.0f ? 255u : (unsigned)ss;
 }
+// One pass of Pillow's box blur (BoxBlur.c; tools/colour_model.py: box_pass) at place x of a line of n bytes `stride` apart, in
+// 32-bit unsigned arithmetic: blur_window is the sum of in[clamp(x + d)], d = -r .. r, as count_left * in[0] + the part inside
+// the line + count_right * in[n - 1] — at most n terms, whatever r —, blur_byte the weighted sum's byte
+__host__ __device__ inline uint32_t blur_byte(uint32_t ww, uint32_t fw, uint32_t sum, uint32_t far) { return ((ww * sum + fw * far + (1u << 23)) >> 24) & 0xFFu; }
+__host__ __device__ inline uint32_t blur_window(const uint8_t *line, int64_t stride, int n, int x, int r) {
+    const int lo = x - r > 0 ? x - r : 0, hi = x + r < n - 1 ? x + r : n - 1;
+    uint32_t s = (uint32_t)(lo - (x - r)) * line[0] + (uint32_t)(x + r - hi) * line[(int64_t)(n - 1) * stride];
+    for (int i = lo; i <= hi; ++i) s += line[(int64_t)i * stride];
+    return s;
+}
+__host__ __device__ inline uint32_t blur_pixel(const uint8_t *line, int64_t stride, int n, int x, int r, uint32_t ww, uint32_t fw) {
+    const int a = x - r - 1 > 0 ? x - r - 1 : 0, b = x + r + 1 < n - 1 ? x + r + 1 : n - 1;
+    return blur_byte(ww, fw, blur_window(line, stride, n, x, r), (uint32_t)line[(int64_t)a * stride] + line[(int64_t)b * stride]);
+}
+__host__ __device__ inline bool colour_is_blur(int kind) { return kind == MJ_COLOUR_GAUSSIAN_BLUR || kind == MJ_COLOUR_BOX_BLUR; }
+// passes along each axis
+__host__ __device__ inline int colour_blur_passes(int kind) { return kind == MJ_COLOUR_GAUSSIAN_BLUR ? 3 : 1; }
 // whether an op is a look-up table per component / takes a histogram
-__host__ __device__ inline bool colour_is_table(int kind) { return kind != MJ_COLOUR_COLOR && kind != MJ_COLOUR_SHARPNESS && kind != 0; }
+__host__ __device__ inline bool colour_is_table(int kind) { return kind != MJ_COLOUR_COLOR && kind != MJ_COLOUR_SHARPNESS && kind != 0 && !colour_is_blur(kind); }
 __host__ __device__ inline bool colour_needs_hist(int kind) { return kind == MJ_COLOUR_CONTRAST || kind == MJ_COLOUR_AUTOCONTRAST || kind == MJ_COLOUR_EQUALIZE; }
 // Entry i of a table-shaped op's table for one component.  st: that component's histogram, scanned (ops that take one) — lo, hi
 // its first and last non-empty bins, nz how many are non-empty, last the last one's count, total the sum of all —, with mean
@@ -569,10 +602,13 @@ __host__ __device__ inline unsigned colour_table_entry(int kind, float value, in
 }
 // what the flag and mj_host_colour_ops refuse of one chain: nullptr, or the reason
 const char *colour_fault(const mj_colour_chain &c);
-// the integer form of an op's value (posterize: the mask, solarize: the clamped threshold; else 0)
+// the integer form of an op's value (posterize: the mask, solarize: the clamped threshold, a blur: r; else 0)
 int colour_ivalue(const mj_colour_op &op);
+// a blur's pass: r, ww and fw of its box radius (gaussian_blur: the radius of the box whose three passes stand for it)
+struct BlurPass { int32_t r; uint32_t ww, fw; };
+BlurPass colour_blur_pass(const mj_colour_op &op);
 // the launches of one execute: the canvas in a.canvas[0] -> a.dst
-hipError_t launch_colour(hipStream_t stream, const ColourArgs &a);
+hipError_t launch_colour(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b);
 // ---- output colour mode (tools/mode_model.py)
 // Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
 __host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }

@@ -23,7 +23,7 @@ const OptionRule kOptionRules[] = {
     {"MJ_FUSED_ACBITS", nullptr, 10, 13, 1}, {"MJ_FUSED_PRODUCERS", nullptr, 1, 8, 1},
     {"MJ_FUSED_PIECE", nullptr, 1, 4096, 1},
     {"MJ_PROG_CHUNKS", nullptr, 0, 2, 1},    {"MJ_PROG_CHUNK", nullptr, 128, 65536, 4},
-    {"MJ_PLACE_WINDOW", nullptr, 0, 1, 1},
+    {"MJ_PLACE_WINDOW", nullptr, 0, 1, 1},   {"MJ_BLUR", "passes", 0, 0, 1},
 };
 constexpr int kNumOptions = (int)(sizeof(kOptionRules) / sizeof(kOptionRules[0]));
 struct OptionTable {

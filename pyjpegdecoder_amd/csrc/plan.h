@@ -293,14 +293,18 @@ struct mj_plan {
     mj::AffineArgs af{};
     // plans with colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): the resize launch writes uint8 canvases, unmirrored,
     // output after output, into the first half of d_canvas; the colour launches (colour.hip) take them through their chains, from one
-    // half to the other, and store the last step into the caller's array — slots, mirror flags and the output table are theirs
+    // half to the other, and store the last step into the caller's array — slots, mirror flags and the output table are theirs.
+    // d_blur_scratch: a third canvas, only on plans that blur pass by pass (co_blur.lds == 0 with a blur in some chain)
     bool colour = false;
     uint8_t *d_canvas = nullptr;
+    uint8_t *d_blur_scratch = nullptr;
+    uint32_t *d_blur_weights = nullptr;         // ww and fw of every blur op (ColourBlurArgs::weights), only on plans with a blur
     uint32_t *d_co_hist = nullptr;
     uint8_t *d_co_tables = nullptr;
     mj::DevColourOutput *d_co_outputs = nullptr;
     int32_t *d_co_list = nullptr;
     mj::ColourArgs co{};
+    mj::ColourBlurArgs co_blur{};
     int32_t n_views = 0;                       // a plan with views (mj_plan_request.views): its resize and reduce records are per view (0: per image)
     std::vector<std::array<int32_t, 2>> h_view_size;   // ... every view's window, stored axes: width, height (mj_debug_reduce_shape)
     std::vector<std::array<int32_t, 6>> h_rd;  // per image (view), stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)

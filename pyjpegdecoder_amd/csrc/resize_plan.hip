@@ -272,16 +272,19 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
 // ---- plans with colour operations: the launches behind the resize ---------------------------------------------------------------
 // In: the request (chains checked, some not empty), the plan — its resize launch made for uint8 canvases, output k at canvas k —,
 // CO — the output's components — and the output's element size.  Out: the plan's colour launches (p->co): one record per output
-// with its chain, its slot's offset in elements and its mirror flag; per step, the outputs that take a histogram; the two
-// canvases, the histograms, the tables and the output table, all plan-owned.
+// with its chain, its slot's offset in elements and its mirror flag; per step, the outputs that take a histogram and, behind them
+// in the same array, the outputs that are blurred; the two canvases, the histograms, the tables and the output table, all
+// plan-owned.  A plan with a blur whose canvas LDS does not hold (or under option MJ_BLUR=passes) owns a third canvas.
 std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize);
 int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     const mj_plan_request &r = q.r;
     const int n = r.n_views ? r.n_views : p->n_images;
     const int64_t npix = (int64_t)r.out_width * r.out_height, canvas = (int64_t)n * npix * CO;
     mj::ColourArgs &a = p->co = mj::ColourArgs{};
+    mj::ColourBlurArgs &b = p->co_blur = mj::ColourBlurArgs{};
     std::vector<mj::DevColourOutput> recs((size_t)n);
     std::vector<int32_t> list;
+    std::vector<uint32_t> weights((size_t)n * 8, 0);
     for (int k = 0; k < n; ++k) {
         const mj_colour_chain &c = q.colour[k];
         mj::DevColourOutput &d = recs[(size_t)k] = mj::DevColourOutput{};
@@ -290,6 +293,11 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
         for (int s = 0; s < c.n; ++s) {
             d.kind[s] = c.op[s].kind; d.value[s] = c.op[s].value; d.ivalue[s] = mj::colour_ivalue(c.op[s]);
             if (mj::colour_is_table(d.kind[s])) a.tables_at |= 1 << s;
+            if (mj::colour_is_blur(d.kind[s])) {
+                const mj::BlurPass pass = mj::colour_blur_pass(c.op[s]);
+                weights[((size_t)k * 4 + s) * 2] = pass.ww; weights[((size_t)k * 4 + s) * 2 + 1] = pass.fw;
+                b.passes[s] = std::max(b.passes[s], 2 * mj::colour_blur_passes(d.kind[s]));
+            }
         }
         a.steps = std::max(a.steps, c.n);
     }
@@ -299,7 +307,17 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
             if (s < recs[(size_t)k].n && mj::colour_needs_hist(recs[(size_t)k].kind[s])) list.push_back(k);
     }
     a.hist_first[MJ_COLOUR_MAX_OPS] = (int32_t)list.size();
-    const int64_t per_output = std::max<int64_t>((npix + mj::kColourHistPixels - 1) / mj::kColourHistPixels, (npix + 255) / 256);
+    for (int s = 0; s < MJ_COLOUR_MAX_OPS; ++s) {
+        b.first[s] = (int32_t)list.size();
+        for (int k = 0; k < n; ++k)
+            if (s < recs[(size_t)k].n && mj::colour_is_blur(recs[(size_t)k].kind[s])) list.push_back(k);
+    }
+    b.first[MJ_COLOUR_MAX_OPS] = (int32_t)list.size();
+    const bool blurs = b.first[MJ_COLOUR_MAX_OPS] > b.first[0];
+    const char *route = mj::opt("MJ_BLUR");
+    if (blurs && !(route && !strcmp(route, "passes")) && mj::blur_lds_bytes(r.out_width, r.out_height) <= mj::kBlurLdsMax)
+        b.lds = (int32_t)mj::blur_lds_bytes(r.out_width, r.out_height);
+    const int64_t per_output = std::max<int64_t>({(npix + mj::kColourHistPixels - 1) / mj::kColourHistPixels, (npix + 255) / 256, (int64_t)CO});
     if ((int64_t)n * per_output > mj::kResizeGridX * (int64_t)65535)
         return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld colour workgroups are more than one launch takes; split the batch", mj::kCreateFn, (long long)n * per_output);
     if (int rc = upload(p, &p->d_co_outputs, recs.data(), recs.size())) return rc;
@@ -307,6 +325,9 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     MJ_HIP(q.ctx, alloc(p, &p->d_canvas, (size_t)(2 * canvas) + 64));
     MJ_HIP(q.ctx, alloc(p, &p->d_co_hist, (size_t)n * 1024 * sizeof(uint32_t)));
     MJ_HIP(q.ctx, alloc(p, &p->d_co_tables, (size_t)n * 768));
+    if (blurs)
+        if (int rc = upload(p, &p->d_blur_weights, weights.data(), weights.size())) return rc;
+    if (blurs && !b.lds) MJ_HIP(q.ctx, alloc(p, &p->d_blur_scratch, (size_t)canvas + 64));
     if (out_esize > 1) {
         const std::vector<uint8_t> lut = output_table(*r.output, CO, out_esize);
         if (int rc = upload(p, &p->d_rz_lut, lut.data(), lut.size())) return rc;
@@ -314,6 +335,7 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     }
     a.canvas[0] = p->d_canvas; a.canvas[1] = p->d_canvas + canvas;
     a.hist = p->d_co_hist; a.tables = p->d_co_tables; a.outputs = p->d_co_outputs; a.hist_list = p->d_co_list;
+    b.list = p->d_co_list; b.weights = p->d_blur_weights; b.scratch = p->d_blur_scratch;
     a.n_outputs = n; a.ow = r.out_width; a.oh = r.out_height; a.C = CO; a.layout = p->layout; a.esize = out_esize;
     p->colour = true;
     return MJ_OK;

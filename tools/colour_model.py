@@ -7,11 +7,16 @@ element type (tools/normalize_model.py).  An op is a tuple whose first element i
 
     ("brightness", f)  ("color", f)  ("contrast", f)  ("sharpness", f)      ImageEnhance.<Name>(im).enhance(f)
     ("posterize", bits)  ("solarize", t)  ("autocontrast",)  ("equalize",)  ("invert",)      ImageOps.<name>(im[, value])
+    ("gaussian_blur", radius)  ("box_blur", radius)      im.filter(ImageFilter.GaussianBlur(radius) / BoxBlur(radius)), 0 <= radius <= 1024
 
 Images are row-major: (H, W, 3) for "RGB", (H, W) for "L".
 
 The four enhancers are ``Image.blend(degenerate, image, f)`` with their own degenerate image (blend).  Everything else is a
 look-up table per band; three of them — contrast's mean, autocontrast and equalize — are made from the image's histogram.
+
+The two blurs are Pillow's BoxBlur.c: passes of one box filter with a fractional radius along the width, then along the height
+(box_pass) — one pass each for box_blur, three each for gaussian_blur with the box radius gaussian_box_radius gives.  Every pass
+stores bytes, and the next pass reads those bytes.
 """
 import math
 
@@ -20,8 +25,9 @@ import numpy as np
 from tools import mode_model
 
 MAX_OPS = 4
-OPS = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "autocontrast", "equalize", "invert")
-VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize")       # ops that take a value
+OPS = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "autocontrast", "equalize", "invert", "gaussian_blur", "box_blur")
+VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "gaussian_blur", "box_blur")       # ops that take a value
+MAX_RADIUS = 1024
 
 
 def blend(d: np.ndarray, v: np.ndarray, f: float) -> np.ndarray:
@@ -102,6 +108,53 @@ def solarize_threshold(t: float) -> int:
     return min(max(math.ceil(t), 0), 256)
 
 
+def gaussian_box_radius(radius: float) -> np.float32:
+    """the radius of the box filter whose three passes stand for a Gaussian of this radius (BoxBlur.c: _gaussian_blur_radius with
+    passes = 3): float32 throughout, except that the square root and the floor are taken in double"""
+    f = np.float32
+    sigma2 = f(f(radius) * f(radius)) / f(3)
+    L = f(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f(math.floor((float(L) - 1.0) / 2.0))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * sigma2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = a / (f(6) * (sigma2 - (l + f(1)) * (l + f(1))))
+    return f(l + a)
+
+
+def box_weights(fr) -> tuple:
+    """(r, ww, fw) of one pass with box radius ``fr``: its whole part, the 8.24 weight of a pixel inside it and that of the two
+    pixels just outside — ww = (uint32)(fl32(1 << 24) / fl32(fr * 2 + 1)), fw = ((1 << 24) - (2 r + 1) ww) / 2 in 32-bit unsigned"""
+    fr = np.float32(fr)
+    r = int(fr)
+    ww = int(np.float32(1 << 24) / (fr * np.float32(2) + np.float32(1))) & 0xFFFFFFFF
+    fw = (((1 << 24) - (2 * r + 1) * ww) & 0xFFFFFFFF) // 2
+    return r, ww, fw
+
+
+def box_pass(a: np.ndarray, fr, axis: int) -> np.ndarray:
+    """one pass along ``axis`` (of length n) of a uint8 array: out[x] = (ww * sum(in[clamp(x + d)], d = -r .. r) + fw * (in[clamp(x - r
+    - 1)] + in[clamp(x + r + 1)]) + (1 << 23)) >> 24, clamp to 0 .. n - 1, in 32-bit unsigned arithmetic.  (Pillow keeps a running
+    sum; the sums are exact integers, so this direct form gives its bytes.)"""
+    r, ww, fw = box_weights(fr)
+    v = np.moveaxis(a, axis, 0).astype(np.uint64)
+    n = v.shape[0]
+    idx = np.clip(np.arange(-r - 1, n + r + 1), 0, n - 1)
+    p = v[idx]                                          # (entry j is in[clamp(j - r - 1)])
+    cs = np.concatenate([np.zeros((1,) + p.shape[1:], dtype=np.uint64), np.cumsum(p, axis=0, dtype=np.uint64)])
+    inner = cs[2 * r + 2:2 * r + 2 + n] - cs[1:1 + n]                # sum of p[x + 1 .. x + 2 r + 1]
+    far = p[:n] + p[2 * r + 2:2 * r + 2 + n]
+    out = (((np.uint64(ww) * inner + np.uint64(fw) * far + np.uint64(1 << 23)) & np.uint64(0xFFFFFFFF)) >> np.uint64(24)) & np.uint64(0xFF)
+    return np.ascontiguousarray(np.moveaxis(out.astype(np.uint8), 0, axis))
+
+
+def blur(a: np.ndarray, fr, passes: int) -> np.ndarray:
+    """``passes`` passes along the width, then as many along the height (axes 1 and 0 of (H, W[, 3])), all with box radius ``fr``"""
+    for axis in (1, 0):
+        for _ in range(passes):
+            a = box_pass(a, fr, axis)
+    return a
+
+
 def _per_band(a: np.ndarray, table_of) -> np.ndarray:
     if a.ndim == 2:
         return table_of(np.bincount(a.ravel(), minlength=256))[a]
@@ -131,6 +184,10 @@ def apply_op(a: np.ndarray, op) -> np.ndarray:
         return np.where(a < solarize_threshold(op[1]), a, 255 - a).astype(np.uint8)
     if name == "invert":
         return (255 - a).astype(np.uint8)
+    if name in ("gaussian_blur", "box_blur"):
+        if not 0 <= op[1] <= MAX_RADIUS:
+            raise ValueError(f"{name} takes a radius of 0..{MAX_RADIUS}, not {op[1]!r}")
+        return blur(a, gaussian_box_radius(op[1]), 3) if name == "gaussian_blur" else blur(a, np.float32(op[1]), 1)
     return _per_band(a, autocontrast_table if name == "autocontrast" else equalize_table)
 
 

@@ -14,12 +14,19 @@ per plan the median and the spread (min .. max).
               the plan minus the colour launches, and of the plan without color_ops).  `_padded`: the same on a letterbox — every
               image resized to 112 x 63 in the middle of the canvas, the rest one fill colour —, the histogram launch's worst case:
               most lanes of a workgroup add to the same LDS bin
+              `blur` and `simclr`: ("gaussian_blur", r) alone and behind (brightness, contrast, color), r drawn per output from
+              U(0.1, 2.0) as the self-supervised recipes do — the plane-resident blur launch (a component plane in LDS, all six
+              passes there) —, and `_passes`: the same plans made under option MJ_BLUR=passes, one launch per pass through a third
+              canvas (five more reads and writes of the canvas)
     call      decode_device(size=(224, 224), color_ops=jitter, dtype=float16, normalize=...) end to end, wall clock around a
               synchronised call, against the same call without color_ops= (the feature's cost) and against what a user does today:
               the uint8 call, then brightness, contrast and saturation in torch on the GPU, then the normalisation.  That route
               rounds differently — it does NOT give Pillow's bytes; it is compared for time only.
-    untouched the plain bilinear and bicubic resize launches, the reducing_gap=2.0 reduce launch and the affine launch, this build
-              against the parent's, with a second parent plan beside the first: what two plans of ONE build differ by
+    call_blur the same for color_ops=[("gaussian_blur", r_k)] per output: against the call without it, and against the uint8 call,
+              then a separable Gaussian (sigma = r_k, 13 taps, edges reflected) as two grouped convolutions in torch and the
+              normalisation — other bytes than Pillow's again, compared for time only
+    untouched the plain bilinear and bicubic resize launches, the reducing_gap=2.0 reduce launch, the affine launch and the colour
+              launches of the ColorJitter chain, this build against the parent's, with a second parent plan beside the first: what two plans of ONE build differ by
 
     python tools/colour_probe.py --parent-lib PATH [--n 1024] [--distinct 64] [--reps 12] [--layouts rowmajor,xmajor]
 """
@@ -44,7 +51,8 @@ MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 JITTER = (("brightness", 1.2), ("contrast", 0.8), ("color", 1.3))
 CHAINS = {"jitter": JITTER, "autocontrast_equalize": (("autocontrast",), ("equalize",))}
 # canvases moved: per step one read and one write (the last write is float16: two), one more read per step with a histogram
-MOVED = {"jitter": 3 + 2 + 2 + 1, "autocontrast_equalize": 2 + 1 + 2 + 2}
+MOVED = {"jitter": 3 + 2 + 2 + 1, "autocontrast_equalize": 2 + 1 + 2 + 2, "blur": 1 + 2, "simclr": 4 + 3 + 2 + 1,
+         "blur_passes": 6 + 5 + 2, "simclr_passes": 3 + 3 + 1 + 6 + 5 + 2}
 
 
 def main() -> int:
@@ -59,6 +67,7 @@ def main() -> int:
     ap.add_argument("--parent-first", action="store_true", help="call: the parent build's route first in every round (the order's share of a difference)")
     args = ap.parse_args()
 
+    import numpy as np
     import torch
     from pyjpegdecoder_amd import BatchDecoder, rotation_matrix
     from pyjpegdecoder_amd import _binding as B
@@ -91,6 +100,13 @@ def main() -> int:
 
         # ---- the colour launches alone
         plans = {name: B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=[chain] * n) for name, chain in CHAINS.items()}
+        radii = [float(v) for v in np.random.default_rng(args.seed).uniform(0.1, 2.0, n)]
+        blurs = {"blur": [(("gaussian_blur", r),) for r in radii], "simclr": [JITTER + (("gaussian_blur", r),) for r in radii]}
+        for route in (None, "passes"):
+            B.set_option("MJ_BLUR", route)          # (read when a plan is created)
+            for name, chains in blurs.items():
+                plans[name + ("_passes" if route else "")] = B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=chains)
+        B.set_option("MJ_BLUR", None)
         for name, chain in CHAINS.items():
             plans[name + "_padded"] = B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=[chain] * n,
                                              places=[(112, 63, 56, 80)] * n, fill=(124, 116, 104))
@@ -157,10 +173,37 @@ def main() -> int:
         emit(layout=lname, point="call", e2e_decode_device_ms={name: summary(xs) for name, xs in times.items()},
              color_ops_cost_ms=round(statistics.median(times["color_ops"]) - statistics.median(times["without"]), 3))
 
+        # ---- the whole call with a blur per output
+        taps = torch.arange(-6, 7, device=dev, dtype=torch.float32)
+        kern = torch.exp(-0.5 * (taps[None, :] / torch.tensor(radii, device=dev)[:, None]) ** 2)
+        kern = (kern / kern.sum(dim=1, keepdim=True)).repeat_interleave(3, dim=0)                  # (one row per output and component)
+
+        def torch_blur_route():             # (interleaved layouts: the two image axes are 1 and 2, whichever is the width)
+            x = pdec.decode_device(files, size=(224, 224)).float().movedim(3, 1).reshape(1, n * 3, 224, 224)
+            x = torch.nn.functional.conv2d(torch.nn.functional.pad(x, (6, 6, 0, 0), mode="reflect"), kern.view(n * 3, 1, 1, 13), groups=n * 3)
+            x = torch.nn.functional.conv2d(torch.nn.functional.pad(x, (0, 0, 6, 6), mode="reflect"), kern.view(n * 3, 1, 13, 1), groups=n * 3)
+            x = x.reshape(n, 3, 224, 224).movedim(1, 3)
+            return ((x / 255.0 - mean_t) / std_t).half()
+
+        routes = {"blur": lambda: dec.decode_device(files, color_ops=blurs["blur"], **kw),
+                  "without": lambda: dec.decode_device(files, **kw),
+                  "parent_uint8_then_torch_blur": torch_blur_route}
+        times = {name: [] for name in routes}
+        for r in range(args.e2e_reps + 1):
+            for name, fn in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if r:
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+        emit(layout=lname, point="call_blur", e2e_decode_device_ms={name: summary(xs) for name, xs in times.items()},
+             blur_cost_ms=round(statistics.median(times["blur"]) - statistics.median(times["without"]), 3))
+
         # ---- the launches this change did not mean to touch: this build against the parent's, a second parent plan beside the first
         matrix = rotation_matrix(15.0, (W, H))
         for label, pk in (("bilinear", {}), ("bicubic", {"filter": "bicubic"}), ("gap2_bicubic", {"filter": "bicubic", "reducing_gap": 2.0}),
-                          ("affine_bilinear", {"affine": ([matrix] * n, "bilinear", (0, 0, 0))})):
+                          ("affine_bilinear", {"affine": ([matrix] * n, "bilinear", (0, 0, 0))}), ("colour_jitter", {"colour": [JITTER] * n})):
             plans = {"parent": B.Plan(pctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), **pk),
                      "parent_twin": B.Plan(pctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), **pk),
                      "this": B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), **pk)}
@@ -178,11 +221,13 @@ def main() -> int:
                             rd[name].append(plan.time_reduce(1))
                         if "affine" in pk:
                             rd[name].append(plan.time_affine(1)[0])
+                        if "colour" in pk:
+                            rd[name].append(plan.time_colour(1)[0])
                 line = {"layout": lname, "point": "untouched_" + label, "this_equals_parent": bool(torch.equal(out["this"], out["parent"]))}
                 for name in plans:
                     line[name + "_resize_ms"] = summary(rs[name])
                     if rd[name]:
-                        line[name + ("_reduce_ms" if "reducing_gap" in pk else "_affine_ms")] = summary(rd[name])
+                        line[name + ("_reduce_ms" if "reducing_gap" in pk else "_affine_ms" if "affine" in pk else "_colour_ms")] = summary(rd[name])
                 which = rd if rd["this"] else rs
                 lo, hi = min(which["parent"] + which["parent_twin"]), max(which["parent"] + which["parent_twin"])
                 line["this_median_inside_parents_spread"] = bool(lo <= statistics.median(which["this"]) <= hi)
