@@ -196,7 +196,7 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
  * affine transform -> window -> resize with the filter (to the place's size, onto the canvas) -> colour operations
  * (MJ_MODE_COLOUR_OPS, below the request) -> mirror -> the output's element type.  In Pillow's terms the result is
- * exif_transpose(img.convert(mode))[.transform(img.size, AFFINE, a, resample, fillcolor)].crop(window).resize(size, filter) —
+ * exif_transpose(img.convert(mode))[.transform(img.size, AFFINE or PERSPECTIVE, a, resample, fillcolor)].crop(window).resize(size, filter) —
  * with reducing_gap, Pillow's argument of that name to that resize.
  *
  * Refusals common to all fields: MJ_ERR_INVALID with a message in mj_last_error — naming the image where there is one — for a
@@ -245,6 +245,14 @@ typedef struct {
 #define MJ_AFFINE_BICUBIC  3
 /* mj_plan_request.affine's value: the resample filter MJ_AFFINE_* and the fill byte of output components 0, 1, 2 */
 #define MJ_AFFINE_FIELD(filter, f0, f1, f2) ((uint32_t)(filter) | (uint32_t)(f0) << 8 | (uint32_t)(f1) << 16 | (uint32_t)(f2) << 24)
+/* One output's perspective transform (mj_plan_request.affine with MJ_AFFINE_PERSPECTIVE): the eight coefficients map OUTPUT pixel
+ * centres to source coordinates, as the `data` of Pillow's Image.transform(size, Image.PERSPECTIVE, data) and torchvision's
+ * _get_perspective_coeffs do.  All eight 0: no transform. */
+typedef struct {
+    double a[8];
+} mj_perspective;
+/* or-ed into the filter of MJ_AFFINE_FIELD: the transform is a perspective one (mj_plan_perspective_request, below) */
+#define MJ_AFFINE_PERSPECTIVE 0x10
 typedef struct {
     /* Region of interest.  DEFAULT NULL: whole images.  Else the output for image i is the window rois[i] of the image — x along
      * image_width, y along image_height — and nothing else.  Window i in the plan's layout:
@@ -335,7 +343,9 @@ typedef struct {
      * array; a matrix entry that is not finite; an image with a side of 32768 or more; a matrix under which a corner pixel of the
      * output has a source coordinate of magnitude 32768 or more (Pillow leaves its defined arithmetic there), and, under
      * MJ_AFFINE_NEAREST, the same for the corner values Pillow's check_fixed tests; together with reducing_gap ("not yet": the
-     * reduce would have to read the new buffer).  Left for later as well: expand=True, use without a size, perspective transforms.
+     * reduce would have to read the new buffer).  Left for later as well: expand=True, use without a size.
+     * With MJ_AFFINE_PERSPECTIVE or-ed into the filter the transform is a perspective one, with coefficients and rules of its own:
+     * see mj_plan_perspective_request below.
      * The field lies in the four bytes between out_height and slots that were padding, as n_views and reducing_gap do: the
      * request keeps its size and every other field its offset. */
     uint32_t affine;
@@ -537,6 +547,37 @@ typedef struct {
     mj_plan_affine_request head;
     const mj_colour_chain *colour;
 } mj_plan_colour_request;
+/* A request with a perspective transform (request.affine with MJ_AFFINE_PERSPECTIVE in its filter byte, e.g.
+ * MJ_AFFINE_FIELD(MJ_AFFINE_BILINEAR | MJ_AFFINE_PERSPECTIVE, fill...)): its head is a mj_plan_colour_request — `views` and `colour`
+ * are read where their fields say so, `head.head.affine` is NOT read —, and `perspective` holds one entry per OUTPUT (n_views
+ * entries in a request with views, else n_images).  Everything mj_plan_request.affine says of its place in the order of
+ * operations, of the plan (the PLAIN plan of its images; rois become per-output records), of the one more launch (csrc/affine.hip:
+ * k_perspective, the affine launch's geometry), of the second plan-owned buffer, of orientation and MJ_MODE_L holds here: output k
+ * is, bit for bit,
+ *   exif_transpose(img.convert(mode)).transform(img.size, Image.PERSPECTIVE, perspective[k].a, resample, fillcolor=fill)
+ *       .crop(window_k).resize(target_k, filter)
+ * and an output whose coefficients are all zero is the output of the request without the field; where ALL are, the request is that
+ * request (mj_debug_normalise_request clears the field).  Pillow's rules (Geometry.c: perspective_transform,
+ * ImagingGenericTransform), restated in tools/perspective_model.py — (X, Y): a pixel of the transformed image in ABSOLUTE
+ * coordinates (a window is the transform evaluated at the window's coordinates); w x h: the oriented image; every double
+ * operation rounded on its own, in this order:
+ *   xc = X + 0.5, yc = Y + 0.5;  d = a6 xc + a7 yc + 1;  xin = (a0 xc + a1 yc + a2) / d;  yin = (a3 xc + a4 yc + a5) / d
+ *   the divisions are IEEE double divisions.  The pixel is INSIDE iff xin >= 0 && xin < w && yin >= 0 && yin < h — NaN and +-inf
+ *   are outside —, and an outside pixel is fill
+ *   MJ_AFFINE_NEAREST    source pixel ((int)xin, (int)yin): no 0.5 shift, no fixed point, no tables
+ *   MJ_AFFINE_BILINEAR / MJ_AFFINE_BICUBIC   the 2 x 2 / 4 x 4 taps around (xin - 0.5, yin - 0.5) exactly as under mj_plan_request.affine
+ * The pole — the line d = 0 — may cross the frame: coordinates near it are huge or infinite, hence outside, hence fill, and beyond
+ * it the source is sampled where the formula says.  0 / 0 gives NaN, which Pillow's C converts to an int (undefined); here that
+ * pixel is fill.  No double is converted to an int before it is known to be inside, so NO coefficient magnitude is refused.
+ * MJ_ERR_INVALID, naming the output: set without a size ("perspective needs a size"); a filter byte that is none of MJ_AFFINE_*
+ * with or without MJ_AFFINE_PERSPECTIVE; a NULL array; a coefficient that is not finite; an image with a side of 32768 or more;
+ * together with reducing_gap ("not yet").  An affine and a perspective transform in one request are not offered (the field
+ * names one array).  Left for later as well: expand=True, use without a size.
+ * No struct that existed changed: the new request wraps the one before it, as every one so far did. */
+typedef struct {
+    mj_plan_colour_request head;
+    const mj_perspective *perspective;
+} mj_plan_perspective_request;
 /* The host twin of the colour launches (no context): src is a row-major w x h image of ncomp (1 or 3) interleaved components, out
  * receives the chain applied to it (w * h * ncomp bytes; out may be src).  MJ_ERR_INVALID: what the flag refuses of a chain, a size
  * below 1, ncomp neither 1 nor 3, NULL. */
@@ -556,6 +597,12 @@ int mj_host_convert_mode(int32_t mode, const uint8_t *src, int32_t src_ncomp, in
  * refuses (its corner tests on the larger of the image and the window's end), an empty window, NULL. */
 int mj_host_affine(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, const double *a, int32_t filter, const uint8_t *fill,
                    int32_t x0, int32_t y0, int32_t win_w, int32_t win_h, uint8_t *out);
+/* The host twin of the perspective launch (no context), shaped like mj_host_affine: the window (x0, y0, win_w, win_h) of the
+ * transform of the row-major w x h image under coefficients a[8] with MJ_AFFINE_NEAREST / BILINEAR / BICUBIC `filter` and
+ * fill[ncomp] (NULL: zeros).  The window may reach beyond w x h.  MJ_ERR_INVALID: a filter that is none of the three, a
+ * coefficient that is not finite, a side of 32768 or more, an empty window or one that ends at 32768 or beyond, NULL. */
+int mj_host_perspective(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, const double *a, int32_t filter, const uint8_t *fill,
+                        int32_t x0, int32_t y0, int32_t win_w, int32_t win_h, uint8_t *out);
 void mj_plan_destroy(mj_plan *plan);
 int mj_plan_get_info(const mj_plan *plan, mj_plan_info *info);
 /* Which form of stage 1 the plan chose: one restart segment per wavefront, one per lane, long segments
@@ -717,7 +764,7 @@ int mj_plan_time_execute(mj_plan *plan, int iters, uint8_t *rgb_device, float *f
 /* A resized plan's resize launch alone (after an execute: it reads what stage 2 left), `iters` times into rgb_device (NULL: where the
  * latest execute wrote): ms per launch, and the bytes of un-resized pixels it reads (written bytes: mj_plan_info.rgb_bytes). */
 int mj_plan_time_resize(mj_plan *plan, int iters, uint8_t *rgb_device, float *ms, int64_t *source_bytes);
-/* A plan's affine launch alone (mj_plan_request.affine; after an execute): ms per launch, and the bytes it writes (it reads, at
+/* A plan's affine — or perspective — launch alone (mj_plan_request.affine; after an execute): ms per launch, and the bytes it writes (it reads, at
  * most, mj_plan_time_resize's source_bytes).  MJ_ERR_INVALID: not a plan with an affine transform. */
 int mj_plan_time_affine(mj_plan *plan, int iters, float *ms, int64_t *written_bytes);
 /* The colour launches of a plan with colour operations alone (MJ_MODE_COLOUR_OPS; after an execute: they read the canvases the

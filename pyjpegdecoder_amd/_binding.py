@@ -28,6 +28,7 @@ MJ_FILTER_BILINEAR, MJ_FILTER_BOX, MJ_FILTER_HAMMING, MJ_FILTER_BICUBIC, MJ_FILT
 # the resample filters of a decode to a fixed size by name (tools/resize_model.py: FILTERS)
 MJ_AFFINE_NEAREST, MJ_AFFINE_BILINEAR, MJ_AFFINE_BICUBIC = 1, 2, 3
 AFFINE_FILTERS = {"nearest": MJ_AFFINE_NEAREST, "bilinear": MJ_AFFINE_BILINEAR, "bicubic": MJ_AFFINE_BICUBIC}
+MJ_AFFINE_PERSPECTIVE = 0x10        # or-ed into the filter byte of mj_plan_request.affine: a perspective transform
 FILTERS = {"bilinear": MJ_FILTER_BILINEAR, "box": MJ_FILTER_BOX, "hamming": MJ_FILTER_HAMMING, "bicubic": MJ_FILTER_BICUBIC,
            "lanczos": MJ_FILTER_LANCZOS}
 
@@ -54,7 +55,7 @@ EXPORTS = (
     "mj_plan_fill_source", "mj_plan_time_resize", "mj_host_resize_table", "mj_host_normalize_table", "mj_host_exif_orientations",
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
-    "mj_plan_time_reduce", "mj_host_affine", "mj_plan_time_affine", "mj_debug_reduce_launch", "mj_host_colour_ops", "mj_plan_time_colour",
+    "mj_plan_time_reduce", "mj_host_affine", "mj_host_perspective", "mj_plan_time_affine", "mj_debug_reduce_launch", "mj_host_colour_ops", "mj_plan_time_colour",
     "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
@@ -195,6 +196,17 @@ class PlanColourRequestC(ctypes.Structure):
     _fields_ = [("head", PlanAffineRequestC), ("colour", ctypes.POINTER(ColourChainC))]
 
 
+class PerspectiveC(ctypes.Structure):
+    """mj_perspective: one output's eight coefficients, output to source (all zero: no transform)."""
+    _fields_ = [("a", ctypes.c_double * 8)]
+
+
+class PlanPerspectiveRequestC(ctypes.Structure):
+    """mj_plan_perspective_request: a request with a perspective transform — a request with colour operations' layout, and behind
+    it one set of coefficients per output."""
+    _fields_ = [("head", PlanColourRequestC), ("perspective", ctypes.POINTER(PerspectiveC))]
+
+
 def colour_chain(chain) -> ColourChainC:
     """mj_colour_chain from None or a sequence of at most MJ_COLOUR_MAX_OPS ops ``(name,)`` / ``(name, value)`` (an MJ_COLOUR_* number
     passes for the name).  A blur that comes without its radius gets NaN, which the library refuses: no radius is not radius 0."""
@@ -266,6 +278,7 @@ def load_library():
     L.mj_host_affine.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_double), i32, vp, i32, i32, i32, i32, vp]
     L.mj_plan_time_colour.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
     L.mj_host_colour_ops.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ColourChainC), vp]
+    L.mj_host_perspective.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_double), i32, vp, i32, i32, i32, i32, vp]
     L.mj_plan_time_affine.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
@@ -494,6 +507,24 @@ def affine(a: np.ndarray, matrix, filter="nearest", fill=0, window=None) -> np.n
     return out
 
 
+def perspective(a: np.ndarray, coeffs, filter="nearest", fill=0, window=None) -> np.ndarray:
+    """mj_host_perspective (host only): the perspective launch's arithmetic on a row-major uint8 (H, W) or (H, W, 3) array — the
+    window (x, y, width, height) (None: all) of Image.transform(size, PERSPECTIVE, coeffs, filter, fillcolor=fill)
+    (tools/perspective_model.py)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    h, w = a.shape[:2]
+    nc = a.shape[2] if a.ndim == 3 else 1
+    x0, y0, ww, wh = window if window is not None else (0, 0, w, h)
+    fb = np.zeros(3, dtype=np.uint8)
+    fb[:] = fill
+    out = np.empty((max(wh, 0), max(ww, 0)) + a.shape[2:], dtype=np.uint8)
+    c = (ctypes.c_double * 8)(*[float(v) for v in coeffs])
+    fid = AFFINE_FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+    if not isinstance(fid, int) or load_library().mj_host_perspective(_ptr(a), w, h, nc, c, fid, _ptr(fb), x0, y0, ww, wh, _ptr(out)) != MJ_OK:
+        raise ValueError("mj_host_perspective: bad arguments")
+    return out
+
+
 def colour_ops(a: np.ndarray, chain) -> np.ndarray:
     """mj_host_colour_ops (host only): the colour launches' arithmetic on a row-major uint8 (H, W) or (H, W, 3) array — ``chain``
     applied to it as to a Pillow "L" / "RGB" image (tools/colour_model.py: apply_chain)."""
@@ -582,7 +613,7 @@ def output_desc(output):
 
 
 def plan_request(n_images, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None, places=None,
-                 fill=None, reducing_gap=None, views=None, affine=None, colour=None):
+                 fill=None, reducing_gap=None, views=None, affine=None, colour=None, perspective=None):
     """(mj_plan_request, the arrays it points to) for a batch of ``n_images`` from Plan's keywords: every keyword is one field of
     the request (include/mijpeg.h), None its default.  Pure: no library, no context.  ValueError for what only a sized or placed
     plan has and for a per-image list that has not one entry for each image (with ``views``: places and the mirror flags have one
@@ -591,6 +622,10 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
         raise ValueError("views needs size: only a resized plan has several outputs per image")
     if size is None and affine is not None:
         raise ValueError("affine needs size: only a resized plan reads the transformed images")
+    if size is None and perspective is not None:
+        raise ValueError("perspective needs size: only a resized plan reads the transformed images")
+    if affine is not None and perspective is not None:
+        raise ValueError("affine and perspective do not go together: the request's one field names one of them")
     if size is None and colour is not None:
         raise ValueError("colour needs size: only a resized plan has a canvas the operations work on")
     if size is None and (places is not None or filter is not None or output is not None):
@@ -600,7 +635,12 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
     if fill is not None and places is None:
         raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
     keep = {}
-    if colour is not None:      # (the request is then the head of the structure that holds the arrays' pointers)
+    if perspective is not None:     # (the request is then the head of the structure that holds the arrays' pointers)
+        keep["perspective_request"] = top = PlanPerspectiveRequestC()
+        whole = top.head
+        ext = whole.head
+        r = ext.request
+    elif colour is not None:
         keep["colour_request"] = whole = PlanColourRequestC()
         ext = whole.head
         r = ext.request
@@ -647,6 +687,15 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
                                                                           for m in matrices])
         fb = (tuple(fb) + (0, 0, 0))[:3]
         r.affine = (AFFINE_FILTERS[name] if isinstance(name, str) else int(name)) | fb[0] << 8 | fb[1] << 16 | fb[2] << 24
+    if perspective is not None:     # ((coefficients: one 8-tuple or None per output, the filter and the fill bytes as affine's))
+        coeffs, name, fb = perspective
+        n_out = len(views) if views is not None else n_images
+        if len(coeffs) != n_out:
+            raise ValueError(f"perspective: {len(coeffs)} entries, not one for each of the {n_out} {'views' if views is not None else 'images'}")
+        keep["perspective"] = top.perspective = (PerspectiveC * max(1, len(coeffs)))(*[PerspectiveC((ctypes.c_double * 8)(*(c if c is not None else (0.0,) * 8)))
+                                                                                       for c in coeffs])
+        fb = (tuple(fb) + (0, 0, 0))[:3]
+        r.affine = (AFFINE_FILTERS[name] if isinstance(name, str) else int(name)) | MJ_AFFINE_PERSPECTIVE | fb[0] << 8 | fb[1] << 16 | fb[2] << 24
     if colour is not None:      # (one chain — None or a sequence of ops — per output)
         n_out = len(views) if views is not None else n_images
         if len(colour) != n_out:
@@ -757,13 +806,14 @@ class Plan:
     bytes, one per output component.  reducing_gap: with size, a number >= 1.0 — the two-step resize, Pillow's argument of that name.
     views: with size, one (image, (x, y, width, height) or None) per OUTPUT — several windows of one decoded image; slots, the mirror
     flags and places then have one entry per view.  affine: with size, (matrices, filter, fill) — one 6-tuple or None per output, a
-    name of AFFINE_FILTERS, up to three fill bytes: the affine transform in front of the windows and the resize.  colour: with size,
+    name of AFFINE_FILTERS, up to three fill bytes: the affine transform in front of the windows and the resize.  perspective: the
+    same with 8-tuples of coefficients, in affine's stead.  colour: with size,
     one chain (None or a sequence of ops, :func:`colour_chain`) per output: the colour operations on the finished canvas."""
 
     def __init__(self, ctx: Context, batch_c: BatchC, keepalive, rois=None, size=None, slots=None, output=None, orientation=None,
-                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None, affine=None, colour=None):
+                 filter=None, mode=None, places=None, fill=None, reducing_gap=None, views=None, affine=None, colour=None, perspective=None):
         request, _ = plan_request(getattr(batch_c, "n_images", 0), rois, size, slots, output, orientation, filter, mode, places, fill,
-                                  reducing_gap, views, affine, colour)
+                                  reducing_gap, views, affine, colour, perspective)
         self.ctx = ctx
         self._keep = keepalive
         h = ctypes.c_void_p()
@@ -840,7 +890,8 @@ class Plan:
         return ms.value, nb.value
 
     def time_affine(self, iters: int = 10):
-        """(ms per affine launch, bytes it writes) of a plan with an affine transform that has been executed (mj_plan_time_affine)."""
+        """(ms per affine — or perspective — launch, bytes it writes) of a plan with such a transform that has been executed
+        (mj_plan_time_affine)."""
         ms, nb = ctypes.c_float(), ctypes.c_int64()
         self.ctx.check(self.ctx.lib.mj_plan_time_affine(self.handle, iters, ctypes.byref(ms), ctypes.byref(nb)))
         return ms.value, nb.value

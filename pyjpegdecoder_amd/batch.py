@@ -716,10 +716,12 @@ def affine_fault(a: Sequence[float], resample: str, w: int, h: int) -> Optional[
 class AffineSpec:
     """The affine transform of a call (:func:`normalize_affine`): ``matrices`` one 6-tuple of floats or None per OUTPUT, ``resample``
     "nearest", "bilinear" or "bicubic", ``fill`` one byte per output component (or the one byte given for all of them, until the
-    component count is known)."""
+    component count is known).  ``perspective``: the transform is a perspective one (:func:`normalize_perspective`) and ``matrices``
+    holds 8-tuples of coefficients."""
     matrices: List[Optional[Tuple[float, ...]]]
     resample: str
     fill: Tuple[int, ...]
+    perspective: bool = False
 
 
 def normalize_affine(affine, affine_resample, affine_fill, size, n_outputs: Optional[int] = None, reducing_gap=None, return_seams: bool = False,
@@ -732,30 +734,10 @@ def normalize_affine(affine, affine_resample, affine_fill, size, n_outputs: Opti
     torchvision's is), "bilinear" or "bicubic" — a name in any case, the ``Image.Resampling`` member or its integer.
     ``affine_fill``: None (0), one byte, or one per output component (``ncomp``, where known).  The transform needs ``size`` and goes
     neither with ``return_seams`` nor — yet — with ``reducing_gap``.  ``n_outputs`` None: what needs no file.  ValueError otherwise."""
-    name = "nearest"
-    if affine_resample is not None:
-        name = None
-        if isinstance(affine_resample, str):
-            name = affine_resample.lower()
-        elif isinstance(affine_resample, (int, np.integer)) and not isinstance(affine_resample, (bool, np.bool_)):
-            name = _PILLOW_AFFINE_FILTERS.get(int(affine_resample))
-        if name not in B.AFFINE_FILTERS:
-            raise ValueError(f"affine_resample must be one of {', '.join(B.AFFINE_FILTERS)} (a name, Pillow's Image.Resampling member or its "
-                             f"integer value), not {affine_resample!r}")
-    fill = (0,)
-    if affine_fill is not None:
-        entries = (affine_fill,) if _is_int(affine_fill) else tuple(affine_fill) if isinstance(affine_fill, (tuple, list, np.ndarray)) else None
-        if entries is None or len(entries) not in (1, 3) or not all(_is_int(v) and 0 <= int(v) <= 255 for v in entries):
-            raise ValueError(f"affine_fill must be one byte 0..255 or one per output component, not {affine_fill!r}")
-        fill = tuple(int(v) for v in entries)
-    if ncomp is not None:
-        if len(fill) == 1:
-            fill = fill * ncomp
-        if len(fill) != ncomp:
-            raise ValueError(f"affine_fill has {len(fill)} bytes for outputs of {ncomp} component{'s' if ncomp > 1 else ''}")
+    name, fill = _transform_resample_fill(affine_resample, affine_fill, ncomp)
     if affine is None:
         if affine_resample is not None or affine_fill is not None:
-            raise ValueError("affine_resample and affine_fill need affine: without it nothing is transformed")
+            raise ValueError("affine_resample and affine_fill need affine or perspective: without one nothing is transformed")
         return None
     if size is None:
         raise ValueError("affine needs size=(width, height): the transformed images are resized to it")
@@ -783,6 +765,133 @@ def normalize_affine(affine, affine_resample, affine_fill, size, n_outputs: Opti
     return AffineSpec(matrices if matrices is not None else [], name, fill)
 
 
+def _transform_resample_fill(affine_resample, affine_fill, ncomp: Optional[int] = None):
+    """(name, fill) of ``affine_resample`` and ``affine_fill``, which serve ``affine`` and ``perspective`` alike"""
+    name = "nearest"
+    if affine_resample is not None:
+        name = None
+        if isinstance(affine_resample, str):
+            name = affine_resample.lower()
+        elif isinstance(affine_resample, (int, np.integer)) and not isinstance(affine_resample, (bool, np.bool_)):
+            name = _PILLOW_AFFINE_FILTERS.get(int(affine_resample))
+        if name not in B.AFFINE_FILTERS:
+            raise ValueError(f"affine_resample must be one of {', '.join(B.AFFINE_FILTERS)} (a name, Pillow's Image.Resampling member or its "
+                             f"integer value), not {affine_resample!r}")
+    fill = (0,)
+    if affine_fill is not None:
+        entries = (affine_fill,) if _is_int(affine_fill) else tuple(affine_fill) if isinstance(affine_fill, (tuple, list, np.ndarray)) else None
+        if entries is None or len(entries) not in (1, 3) or not all(_is_int(v) and 0 <= int(v) <= 255 for v in entries):
+            raise ValueError(f"affine_fill must be one byte 0..255 or one per output component, not {affine_fill!r}")
+        fill = tuple(int(v) for v in entries)
+    if ncomp is not None:
+        if len(fill) == 1:
+            fill = fill * ncomp
+        if len(fill) != ncomp:
+            raise ValueError(f"affine_fill has {len(fill)} bytes for outputs of {ncomp} component{'s' if ncomp > 1 else ''}")
+    return name, fill
+
+
+def _is_coeffs(c) -> bool:
+    return isinstance(c, (tuple, list, np.ndarray)) and len(c) == 8 and all(_is_number(v) for v in c)
+
+
+def perspective_fault(c: Sequence[float], w: int, h: int) -> Optional[str]:
+    """What is refused of one set of coefficients for a ``w`` x ``h`` image (None: nothing) — csrc/affine.hip's perspective_fault,
+    restated.  No magnitude is: a source coordinate of any size, NaN included, is tested before it is used."""
+    if not all(math.isfinite(v) for v in c):
+        return "a coefficient is not finite"
+    if w >= 32768 or h >= 32768:
+        return "an image with a side of 32768 or more"
+    return None
+
+
+def normalize_perspective(perspective, affine_resample, affine_fill, size, n_outputs: Optional[int] = None, reducing_gap=None,
+                          return_seams: bool = False, ncomp: Optional[int] = None) -> Optional[AffineSpec]:
+    """``perspective`` of a call, with the ``affine_resample`` and ``affine_fill`` it shares with ``affine``, checked as
+    :func:`normalize_affine` checks a matrix: None for a call without a transform, else an :class:`AffineSpec` with ``perspective``
+    set.  ``perspective``: None, one sequence ``(c0, .., c7)`` of eight numbers for every output, or a list with one such sequence
+    or None per output (per file; per view with ``views``).  The coefficients map OUTPUT pixel centres to source coordinates —
+    ``x_in = (c0 x + c1 y + c2) / (c6 x + c7 y + 1)``, ``y_in = (c3 x + c4 y + c5) / (c6 x + c7 y + 1)`` — as the ``data`` of Pillow's
+    ``Image.transform(size, Image.PERSPECTIVE, data)`` and torchvision's ``_get_perspective_coeffs`` do
+    (:func:`perspective_coeffs` solves for them).  ValueError otherwise; what depends on the output's file — a coefficient that is
+    not finite is reported with it — is :func:`check_affine`'s."""
+    name, fill = _transform_resample_fill(affine_resample, affine_fill, ncomp)
+    if perspective is None:
+        if affine_resample is not None or affine_fill is not None:
+            raise ValueError("affine_resample and affine_fill need affine or perspective: without one nothing is transformed")
+        return None
+    if size is None:
+        raise ValueError("perspective needs size=(width, height): the transformed images are resized to it")
+    if return_seams:
+        raise ValueError("perspective and return_seams do not go together: the seam outputs are the decoded images")
+    if reducing_gap is not None:
+        raise ValueError("perspective and reducing_gap do not go together yet: the reduce step would have to read the transformed images "
+                         "(a later step)")
+    if _is_coeffs(perspective):
+        coeffs = None if n_outputs is None else [tuple(float(v) for v in perspective)] * n_outputs
+    elif isinstance(perspective, (list, tuple)) and all(c is None or _is_coeffs(c) for c in perspective):
+        if n_outputs is not None and len(perspective) != n_outputs:
+            raise ValueError(f"perspective has {len(perspective)} entries for {n_outputs} outputs")
+        coeffs = [tuple(float(v) for v in c) if c is not None else None for c in perspective]
+    else:
+        raise ValueError(f"perspective must be None, one sequence (c0, .., c7) of eight numbers, or a list with one such sequence or None per "
+                         f"output, not {perspective!r}")
+    for k, c in enumerate(coeffs or []):            # (a coefficient that is not finite: check_affine's, which can name the file)
+        if c is not None and not any(c):
+            raise ValueError(f"perspective: output {k}: coefficients that are all zero map every pixel to the source's corner (None: no transform)")
+    if coeffs is not None and all(c is None for c in coeffs):
+        return None
+    return AffineSpec(coeffs if coeffs is not None else [], name, fill, True)
+
+
+def normalize_transform(affine, perspective, affine_resample, affine_fill, size, n_outputs: Optional[int] = None, reducing_gap=None,
+                        return_seams: bool = False, ncomp: Optional[int] = None) -> Optional[AffineSpec]:
+    """the one geometric transform of a call: :func:`normalize_affine` or :func:`normalize_perspective` — not both"""
+    if affine is not None and perspective is not None:
+        raise ValueError("affine and perspective do not go together: a call has one transform in front of the window "
+                         "(a perspective transform with c6 = c7 = 0 is an affine one)")
+    if perspective is not None:
+        return normalize_perspective(perspective, affine_resample, affine_fill, size, n_outputs, reducing_gap, return_seams, ncomp)
+    return normalize_affine(affine, affine_resample, affine_fill, size, n_outputs, reducing_gap, return_seams, ncomp)
+
+
+def _spec_for_outputs(spec: AffineSpec, size, n_outputs: int, ncomp: int) -> Optional[AffineSpec]:
+    """a checked spec again, now that the outputs' count and components are known (the fill then has one byte per component)"""
+    return (normalize_perspective if spec.perspective else normalize_affine)(spec.matrices, spec.resample, spec.fill, size, n_outputs, ncomp=ncomp)
+
+
+def perspective_coeffs(startpoints, endpoints) -> Tuple[float, ...]:
+    """The eight coefficients of the perspective transform that takes the four corners ``startpoints`` of the source to
+    ``endpoints`` in the output — each four ``(x, y)`` pairs, torchvision's order: top-left, top-right, bottom-right, bottom-left —,
+    as ``perspective=`` takes them: the solution torchvision's ``_get_perspective_coeffs(startpoints, endpoints)`` solves for, i.e.
+    what ``F.perspective(img, startpoints, endpoints)`` hands Pillow.  The 8 x 8 system in float64 — per pair the rows
+    ``[ex, ey, 1, 0, 0, 0, -sx ex, -sx ey]`` and ``[0, 0, 0, ex, ey, 1, -sy ex, -sy ey]``, right-hand side the start points —
+    solved with NumPy.  NOT pinned to torchvision's bits: torchvision solves the same system with ``torch.linalg.lstsq`` in
+    float64 and rounds to float32 on the way, so its coefficients agree with these to rounding, not bit for bit; the pixels are
+    Pillow's for whichever coefficients are given.  ValueError for anything but four pairs of finite numbers each, or corners
+    that determine no transform (three on a line)."""
+    def pairs(pts, what):
+        ok = isinstance(pts, (list, tuple, np.ndarray)) and len(pts) == 4 and all(
+            isinstance(q, (list, tuple, np.ndarray)) and len(q) == 2 and all(_is_number(v) and math.isfinite(v) for v in q) for q in pts)
+        if not ok:
+            raise ValueError(f"{what} must be four (x, y) pairs of finite numbers, not {pts!r}")
+        return [(float(q[0]), float(q[1])) for q in pts]
+    start, end = pairs(startpoints, "startpoints"), pairs(endpoints, "endpoints")
+    a = np.zeros((8, 8), dtype=np.float64)
+    b = np.zeros(8, dtype=np.float64)
+    for i, ((sx, sy), (ex, ey)) in enumerate(zip(start, end)):
+        a[2 * i] = [ex, ey, 1, 0, 0, 0, -sx * ex, -sx * ey]
+        a[2 * i + 1] = [0, 0, 0, ex, ey, 1, -sy * ex, -sy * ey]
+        b[2 * i], b[2 * i + 1] = sx, sy
+    try:
+        c = np.linalg.solve(a, b)
+    except np.linalg.LinAlgError:
+        raise ValueError(f"startpoints {startpoints!r} and endpoints {endpoints!r} determine no perspective transform") from None
+    if not np.all(np.isfinite(c)):
+        raise ValueError(f"startpoints {startpoints!r} and endpoints {endpoints!r} determine no perspective transform")
+    return tuple(float(v) for v in c)
+
+
 def rois_as_views(rois, n_files: int):
     """The windows of a call with an affine transform as views, one per file: such a call decodes whole images — a rotated window
     needs source pixels outside itself — and cuts the window out of the transformed image.  ``rois`` as :func:`normalize_rois`
@@ -803,9 +912,9 @@ def check_affine(spec: Optional[AffineSpec], views, odims, index=None) -> None:
     if spec is None:
         return
     for k, ((f, _), m) in enumerate(zip(views, spec.matrices)):
-        why = affine_fault(m, spec.resample, *odims[f]) if m is not None else None
+        why = None if m is None else perspective_fault(m, *odims[f]) if spec.perspective else affine_fault(m, spec.resample, *odims[f])
         if why:
-            raise ValueError(f"affine: output {k} (file {f if index is None else index[f]}): {why}")
+            raise ValueError(f"{'perspective' if spec.perspective else 'affine'}: output {k} (file {f if index is None else index[f]}): {why}")
 
 
 def _is_colour_op(op) -> bool:
@@ -1104,7 +1213,7 @@ class _Request:
     fill: Optional[Tuple[int, ...]] = None
     reducing_gap: Optional[float] = None
     views: Optional[List[Tuple[int, Tuple[int, int, int, int]]]] = None
-    affine: Optional[AffineSpec] = None         # :func:`normalize_affine`'s (None: no transform); always with ``views``
+    affine: Optional[AffineSpec] = None         # :func:`normalize_transform`'s, affine or perspective (None: no transform); always with ``views``
     colour: Optional[List[Optional[tuple]]] = None      # :func:`normalize_color_ops`' chains, one or None per OUTPUT (None: no operations)
 
     @property
@@ -1137,7 +1246,8 @@ class _Request:
 
             def pick_view(per_view):
                 return [per_view[k] for k in vk] if per_view is not None else None
-            affine = AffineSpec(pick_view(self.affine.matrices), self.affine.resample, self.affine.fill) if self.affine is not None else None
+            affine = (AffineSpec(pick_view(self.affine.matrices), self.affine.resample, self.affine.fill, self.affine.perspective)
+                      if self.affine is not None else None)
             if affine is not None and all(m is None for m in affine.matrices):
                 affine = None
             return _Request(pick(self.files), None, self.size, self.output.for_files(vk) if self.output else None, self.dest, pick_view(self.slots),
@@ -1176,7 +1286,7 @@ class _Request:
         if self.reducing_gap is not None:   # (one step: the arguments of a call without reducing_gap)
             kw["reducing_gap"] = self.reducing_gap
         if self.affine is not None:         # (no output transformed: the arguments of a call without affine)
-            kw["affine"] = (self.affine.matrices, self.affine.resample, self.affine.fill)
+            kw["perspective" if self.affine.perspective else "affine"] = (self.affine.matrices, self.affine.resample, self.affine.fill)
         if self.colour is not None:         # (no output with operations: the arguments of a call without color_ops)
             kw["colour"] = self.colour
         return kw
@@ -1328,7 +1438,7 @@ class BatchDecoder:
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None, color_ops=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1379,6 +1489,14 @@ class BatchDecoder:
         output whose matrix is None is the output of the call without the argument.  Files are decoded whole (a rotated window
         needs pixels outside itself); one more launch per plan writes every output's window of its transformed image.  Not with
         ``return_seams``, and not yet with ``reducing_gap``.
+        ``perspective``, with ``size``: torchvision's ``RandomPerspective`` / ``F.perspective`` on PIL images — Pillow's
+        ``Image.transform(img.size, Image.PERSPECTIVE, coeffs, affine_resample, fillcolor=affine_fill)`` in ``affine``'s place and in
+        its stead (:func:`normalize_perspective`): None, one sequence ``(c0, .., c7)`` for every output, or a list with one or None
+        per output.  The coefficients map output to input, as Pillow's do; :func:`perspective_coeffs` solves for them from four
+        corners.  ``affine_resample`` and ``affine_fill`` serve it as they serve ``affine``, and all that is said of ``affine`` above
+        holds, bit for bit in the same way.  The coordinates are two double divisions per pixel; where the denominator is zero or
+        the coordinates lie outside the image — beyond a pole line that crosses the frame, say — the pixel is ``affine_fill``, as
+        Pillow's is.  No coefficient magnitude is refused.  Not together with ``affine``.
         ``color_ops``, with ``size``: the colour half of ColorJitter, RandAugment, AutoAugment and TrivialAugment, on the finished
         canvas (:func:`normalize_color_ops`): None, one chain for every output, or a list with one chain or None per output — per
         file, per view with ``views``.  A chain is a sequence of at most four ops — ``("brightness", f)``, ``("color", f)``,
@@ -1407,8 +1525,8 @@ class BatchDecoder:
         reducing_gap = normalize_reducing_gap(reducing_gap, size)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
-        spec = normalize_affine(affine, affine_resample, affine_fill, size, len(views) if isinstance(views, (list, tuple)) else len(files),
-                                reducing_gap, return_seams)
+        spec = normalize_transform(affine, perspective, affine_resample, affine_fill, size,
+                                   len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap, return_seams)
         colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files), return_seams)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
@@ -1437,7 +1555,7 @@ class BatchDecoder:
             req.output = normalize_output(dtype, normalize, mirror, size, req.n_outputs, nc, host=True)
             req.fill = normalize_fill(fill, resize_to, nc)
             if spec is not None:
-                req.affine = normalize_affine(spec.matrices, spec.resample, spec.fill, size, req.n_outputs, ncomp=nc)
+                req.affine = _spec_for_outputs(spec, size, req.n_outputs, nc)
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         results: List[Optional[np.ndarray]] = [None] * len(files)
         seams: List[Optional[dict]] = [None] * len(files)
@@ -1496,11 +1614,12 @@ class BatchDecoder:
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
                         resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                        affine_fill=None, color_ops=None) -> _Request:
+                        affine_fill=None, color_ops=None, perspective=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
-        spec = normalize_affine(affine, affine_resample, affine_fill, size, len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap)
+        spec = normalize_transform(affine, perspective, affine_resample, affine_fill, size,
+                                   len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap)
         colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files))
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
@@ -1522,7 +1641,7 @@ class BatchDecoder:
                 req.places = normalize_places(resize_to, place, size, [r[2:] for _, r in req.views], [index[f] for f, _ in req.views])
                 check_affine(spec, req.views, odims, index)
                 if spec is not None:
-                    req.affine = normalize_affine(spec.matrices, spec.resample, spec.fill, size, len(req.views), ncomp=nc)
+                    req.affine = _spec_for_outputs(spec, size, len(req.views), nc)
             else:
                 req.wins = normalize_rois(rois, odims)
                 req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
@@ -1546,7 +1665,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None, color_ops=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1584,6 +1703,7 @@ class BatchDecoder:
         parts by FILE, every file's views in its part.
         ``affine``, ``affine_resample`` and ``affine_fill`` as in :meth:`decode`: every plan of the call (files of several kinds and
         orientation classes, second rounds, parts) runs its own affine launch between its decode and its resize launch.
+        ``perspective`` as in :meth:`decode`, in ``affine``'s place: every such plan runs the perspective launch there instead.
         ``color_ops`` as in :meth:`decode`: every plan of the call whose outputs have operations writes its canvases into a buffer of
         its own and runs the colour launches behind its resize launch — histograms, tables and the operations themselves, all on the
         GPU —, which store into the one tensor; plans whose outputs have none are the plans of a call without the argument."""
@@ -1595,7 +1715,7 @@ class BatchDecoder:
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
         req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap, views,
-                                   affine, affine_resample, affine_fill, color_ops)
+                                   affine, affine_resample, affine_fill, color_ops, perspective)
         files = req.files                       # (with views: the files some view names)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
@@ -1706,7 +1826,7 @@ class BatchDecoder:
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None, color_ops=None):
+                           affine_fill=None, color_ops=None, perspective=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1728,14 +1848,18 @@ class BatchDecoder:
         what :meth:`decode_device` takes for that batch — a list with one entry per output; ``mirror`` and the list forms of
         ``resize_to`` and ``place`` then go by view.  ``affine``: None, one matrix for every output of every batch, or an iterable
         that yields, batch by batch, what :meth:`decode_device` takes for that batch; ``affine_resample`` and ``affine_fill`` as
-        there, for every batch.  ``color_ops``: None, one chain for every output of every batch, or an iterable that yields, batch by
+        there, for every batch.  ``perspective``: None, one sequence of eight coefficients for every output of every batch, or an
+        iterable that yields one value per batch, as ``affine`` does; not together with ``affine``.  ``color_ops``: None, one chain for every output of every batch, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch."""
         size = normalize_size(size)
         normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
         per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
-        normalize_affine(affine if affine is None or _is_matrix(affine) else (1, 0, 0, 0, 1, 0), affine_resample, affine_fill, size, None, reducing_gap)
+        normalize_transform(affine if affine is None or _is_matrix(affine) else (1, 0, 0, 0, 1, 0),
+                            perspective if perspective is None or _is_coeffs(perspective) else (1, 0, 0, 0, 1, 0, 0, 0), affine_resample, affine_fill, size, None,
+                            reducing_gap)
         per_batch_affine = iter(affine) if affine is not None and not _is_matrix(affine) else None
+        per_batch_perspective = iter(perspective) if perspective is not None and not _is_coeffs(perspective) else None
         if views is not None and size is None:
             raise ValueError("views needs size=(width, height): every view is resized to it (crops at their own sizes would be ragged)")
         per_batch_views = iter(views) if views is not None else None
@@ -1781,18 +1905,26 @@ class BatchDecoder:
                         t = next(per_batch_affine)
                     except StopIteration:
                         raise ValueError("affine yields fewer entries than there are batches") from None
+                ps = perspective
+                if per_batch_perspective is not None:
+                    try:
+                        ps = next(per_batch_perspective)
+                    except StopIteration:
+                        raise ValueError("perspective yields fewer entries than there are batches") from None
                 c = color_ops
                 if per_batch_colour is not None:
                     try:
                         c = next(per_batch_colour)
                     except StopIteration:
                         raise ValueError("color_ops yields fewer entries than there are batches") from None
-                if t is None or (isinstance(t, (list, tuple)) and all(e is None for e in t)):         # (a batch without a transform)
+                def none(g):
+                    return g is None or (isinstance(g, (list, tuple)) and all(e is None for e in g))
+                if none(t) and none(ps):                # (a batch without a transform)
                     yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
                                                color_ops=c)
                     continue
                 yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                           t, affine_resample, affine_fill, c)
+                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -369,7 +369,8 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
     if (p->reduces) MJ_HIP(p->ctx, mj::launch_reduce(s, p->rd, p->ncomp, p->rd_luma));
     // a plan with an affine transform: the affine launch in front, whose upright windows — in the output's components — the resize reads
     if (p->affine) {
-        MJ_HIP(p->ctx, mj::launch_affine(s, p->af, p->ncomp, p->af_ncomp));
+        if (p->perspective) MJ_HIP(p->ctx, mj::launch_perspective(s, p->pf, p->ncomp, p->af_ncomp));
+        else MJ_HIP(p->ctx, mj::launch_affine(s, p->af, p->ncomp, p->af_ncomp));
         MJ_HIP(p->ctx, mj::launch_resize(s, a, p->af_ncomp, 0, p->rz_placed, p->rz_fill));
     } else {
         MJ_HIP(p->ctx, mj::launch_resize(s, a, p->rd_luma ? 1 : p->ncomp, p->rd_luma ? 0 : p->out_ncomp, p->rz_placed, p->rz_fill));
@@ -630,7 +631,11 @@ int mj_plan_time_affine(mj_plan *p, int iters, float *ms_out, int64_t *written_b
     if (!p->affine) return fail(ctx, MJ_ERR_INVALID, "mj_plan_time_affine: not a plan with an affine transform");
     hipStream_t s = ctx->stream;
     if (int rc = plan_ready(p, s)) return rc;
-    const int rc = time_launches(ctx, s, 1, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_affine(s, p->af, p->ncomp, p->af_ncomp)); return MJ_OK; }, ms_out);
+    const int rc = time_launches(ctx, s, 1, iters, [&]() -> int {
+        if (p->perspective) MJ_HIP(ctx, mj::launch_perspective(s, p->pf, p->ncomp, p->af_ncomp));
+        else MJ_HIP(ctx, mj::launch_affine(s, p->af, p->ncomp, p->af_ncomp));
+        return MJ_OK;
+    }, ms_out);
     if (written_bytes) *written_bytes = p->af_bytes;
     return rc != MJ_OK ? rc : mark_done(p, s);
 }

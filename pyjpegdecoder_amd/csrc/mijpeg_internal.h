@@ -495,6 +495,33 @@ void affine_scale_table(double scale, double offset, int size, int first, int n,
 void affine_host(const uint8_t *src, const DevAffineImage &im, const int32_t *tabs, int ncomp, int out_ncomp, uint32_t fill, uint8_t *out);
 // (ncomp: the decoded images'; out_ncomp: the written ones' — the same, 1 for colour to L, 3 for grey to RGB)
 hipError_t launch_affine(hipStream_t stream, const AffineArgs &a, int ncomp, int out_ncomp);
+// ---- affine.hip: the perspective transform in the same place (MJ_AFFINE_PERSPECTIVE in mj_plan_request.affine's filter byte;
+// tools/perspective_model.py).  One output of such a plan: DevAffineImage's image, window and orientation, and the rule:
+//   kind 0  no transform: the oriented pixels of the window
+//        1  NEAREST: the truncated coordinates, in doubles
+//        3  BILINEAR, 4 BICUBIC (DevAffineImage's numbers: the taps are the same code)
+// with c[8] for all three: no tables, no fixed point.  The launch's geometry is the affine launch's (kAffineTile*).
+struct DevPerspectiveImage {
+    int64_t src_off, dst_off;
+    int32_t sw, sh, w, h;
+    int32_t x0, y0, win_w, win_h;
+    int32_t kind, obits;
+    double c[8];
+};
+struct PerspectiveArgs {
+    const uint8_t *src;
+    uint8_t *dst;
+    const DevPerspectiveImage *images;
+    int32_t n_images, layout;
+    int32_t tiles_slow, tiles_fast;
+    uint32_t fill;
+};
+// what the field and mj_host_perspective refuse of one set of coefficients for a w x h image (no magnitude is refused: the rule
+// has no fixed point, and a coordinate of any size, NaN included, is tested before it is used): nullptr, or the reason
+const char *perspective_fault(const double *c, int filter, int w, int h);
+int perspective_kind(int filter);
+void perspective_host(const uint8_t *src, const DevPerspectiveImage &im, int ncomp, int out_ncomp, uint32_t fill, uint8_t *out);
+hipError_t launch_perspective(hipStream_t stream, const PerspectiveArgs &a, int ncomp, int out_ncomp);
 // ---- colour.hip: colour operations on the finished canvas (mj_plan_request.mode with MJ_MODE_COLOUR_OPS; tools/colour_model.py)
 // One output of a plan with colour operations: its chain (n ops; value: the factor of brightness, color, contrast and sharpness;
 // ivalue: posterize's MASK and solarize's clamped threshold, as integers — colour_ivalue; a blur's r, with ww and fw beside it —

@@ -291,6 +291,11 @@ struct mj_plan {
     mj::DevAffineImage *d_af_images = nullptr;
     int32_t *d_af_tabs = nullptr;
     mj::AffineArgs af{};
+    // ... or a perspective transform (MJ_AFFINE_PERSPECTIVE): `affine` is set, the buffer and af_* are as above, and the launch is
+    // the perspective one with records of its own
+    bool perspective = false;
+    mj::DevPerspectiveImage *d_pf_images = nullptr;
+    mj::PerspectiveArgs pf{};
     // plans with colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): the resize launch writes uint8 canvases, unmirrored,
     // output after output, into the first half of d_canvas; the colour launches (colour.hip) take them through their chains, from one
     // half to the other, and store the last step into the caller's array — slots, mirror flags and the output table are theirs.
@@ -342,13 +347,21 @@ int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, b
 // views after normalisation: its windows (r.rois) or whole images become one view per image, held in own_views
 // colour: one chain per output where the caller's r.mode had MJ_MODE_COLOUR_OPS (its mj_plan_colour_request) and some chain is not
 // empty, else NULL; r.mode itself holds the mode alone after normalisation
+// perspective: one entry per output where r.affine's filter byte has MJ_AFFINE_PERSPECTIVE (the caller's
+// mj_plan_perspective_request), else NULL; `affine` is then NULL, and what is said of views above holds
 struct PlanRequest {
     mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; const mj_view *views = nullptr; const mj_affine *affine = nullptr;
     const mj_colour_chain *colour = nullptr;
+    const mj_perspective *perspective = nullptr;
     std::vector<mj_view> own_views{};
 };
 // an output without a transform: all six entries 0
 inline bool affine_none(const mj_affine &m) { return !m.a[0] && !m.a[1] && !m.a[2] && !m.a[3] && !m.a[4] && !m.a[5]; }
+inline bool perspective_none(const mj_perspective &m) {
+    for (double v : m.a)
+        if (v) return false;
+    return true;
+}
 constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the messages)
 int create_resized(const PlanRequest &q);
 // reducing_gap's default rule (normalise_request): whether any image of the request — oriented, its window, to its place's size —

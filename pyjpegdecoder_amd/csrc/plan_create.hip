@@ -727,24 +727,32 @@ const mj_view *request_views(const mj_plan_request *request) {
     return request && request->n_views ? reinterpret_cast<const mj_plan_views_request *>(request)->views : nullptr;
 }
 
+// (a perspective request's matrices are not read: mj_plan_perspective_request)
 const mj_affine *request_affine(const mj_plan_request *request) {
-    return request && request->affine ? reinterpret_cast<const mj_plan_affine_request *>(request)->affine : nullptr;
+    return request && request->affine && !(request->affine & MJ_AFFINE_PERSPECTIVE) ? reinterpret_cast<const mj_plan_affine_request *>(request)->affine : nullptr;
+}
+
+const mj_perspective *request_perspective(const mj_plan_request *request) {
+    return request && (request->affine & MJ_AFFINE_PERSPECTIVE) ? reinterpret_cast<const mj_plan_perspective_request *>(request)->perspective : nullptr;
 }
 
 const mj_colour_chain *request_colour(const mj_plan_request *request) {
     return request && (request->mode & MJ_MODE_COLOUR_OPS) ? reinterpret_cast<const mj_plan_colour_request *>(request)->colour : nullptr;
 }
 
-// The affine transform of a sized request, checked against every output's oriented image (views are in place: normalise_views)
+// The affine or perspective transform of a sized request, checked against every output's oriented image (views are in place:
+// normalise_views)
 int check_affine(mj::PlanRequest &q) {
     const char *fn = mj::kCreateFn;
     const mj_batch *b = q.b; const mj_plan_request &r = q.r;
+    const int filter = (int)(r.affine & 0xFF & ~MJ_AFFINE_PERSPECTIVE);
     for (int k = 0; k < r.n_views; ++k) {
-        if (mj::affine_none(q.affine[k])) continue;
+        if (q.perspective ? mj::perspective_none(q.perspective[k]) : mj::affine_none(q.affine[k])) continue;
         const mj_image_desc &im = b->images[q.views[k].image];
         const bool t = r.orientations && (mj::orient_bits(r.orientations[q.views[k].image]) & 4);
-        if (const char *why = mj::affine_fault(q.affine[k].a, (int)(r.affine & 0xFF), t ? im.height : im.width, t ? im.width : im.height))
-            return fail(q.ctx, MJ_ERR_INVALID, "%s: affine: output %d: %s", fn, k, why);
+        const int w = t ? im.height : im.width, h = t ? im.width : im.height;
+        if (const char *why = q.perspective ? mj::perspective_fault(q.perspective[k].a, filter, w, h) : mj::affine_fault(q.affine[k].a, filter, w, h))
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: %s: output %d: %s", fn, q.perspective ? "perspective" : "affine", k, why);
     }
     return MJ_OK;
 }
@@ -772,7 +780,7 @@ int normalise_views(mj::PlanRequest &q) {
     }
     for (int i = 0; i < b->n_images; ++i)
         if (!named[(size_t)i]) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: no view names it (leave it out of the batch)", fn, i);
-    if (identity && !q.affine) { q.views = nullptr; r.n_views = 0; }
+    if (identity && !q.affine && !q.perspective) { q.views = nullptr; r.n_views = 0; }
     return MJ_OK;
 }
 
@@ -787,7 +795,7 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     // (the colour flag is a bit of `mode`; from here on r.mode is the mode alone, and q.colour says whether the flag was set)
     const bool colour_flag = (r.mode & MJ_MODE_COLOUR_OPS) != 0;
     r.mode &= ~MJ_MODE_COLOUR_OPS;
-    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : r.affine ? "affine" : colour_flag ? "colour_ops" : nullptr;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : r.affine ? ((r.affine & MJ_AFFINE_PERSPECTIVE) ? "perspective" : "affine") : colour_flag ? "colour_ops" : nullptr;
     // (what slots, the mirror flags and places have one entry for: the views of a request with views, else the images)
     const int n_out = r.n_views > 0 ? r.n_views : (b ? b->n_images : 0);
     if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
@@ -834,17 +842,21 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     }
     if (r.affine) {
         const int n_out_af = r.n_views > 0 ? r.n_views : b->n_images;
-        const int af_filter = (int)(r.affine & 0xFF);
-        if (af_filter != MJ_AFFINE_NEAREST && af_filter != MJ_AFFINE_BILINEAR && af_filter != MJ_AFFINE_BICUBIC)
+        // (the filter byte: MJ_AFFINE_*, with MJ_AFFINE_PERSPECTIVE or-ed in for a perspective transform)
+        const int af_filter = (int)(r.affine & 0xFF), af_base = af_filter & ~MJ_AFFINE_PERSPECTIVE;
+        const bool persp = (af_filter & MJ_AFFINE_PERSPECTIVE) != 0;
+        if (af_base != MJ_AFFINE_NEAREST && af_base != MJ_AFFINE_BILINEAR && af_base != MJ_AFFINE_BICUBIC)
             return fail(ctx, MJ_ERR_INVALID, "%s: affine: filter %d is none of MJ_AFFINE_*", fn, af_filter);
-        if (!q.affine) return fail(ctx, MJ_ERR_INVALID, "%s: affine without its array of matrices", fn);
+        if (persp && !q.perspective) return fail(ctx, MJ_ERR_INVALID, "%s: perspective without its array of coefficients", fn);
+        if (!persp && !q.affine) return fail(ctx, MJ_ERR_INVALID, "%s: affine without its array of matrices", fn);
         bool none = true;
-        for (int k = 0; k < n_out_af && none; ++k) none = mj::affine_none(q.affine[k]);
-        if (none) { r.affine = 0; q.affine = nullptr; }       // (no output is transformed: the request without the field)
+        for (int k = 0; k < n_out_af && none; ++k) none = persp ? mj::perspective_none(q.perspective[k]) : mj::affine_none(q.affine[k]);
+        if (none) { r.affine = 0; q.affine = nullptr; q.perspective = nullptr; }       // (no output is transformed: the request without the field)
     }
     if (r.affine) {
         if (r.reducing_gap != 0)
-            return fail(ctx, MJ_ERR_INVALID, "%s: affine and reducing_gap do not go together yet: the reduce launch would have to read the transformed images", fn);
+            return fail(ctx, MJ_ERR_INVALID, "%s: %s and reducing_gap do not go together yet: the reduce launch would have to read the transformed images", fn,
+                        q.perspective ? "perspective" : "affine");
         if (!b->images && b->n_images > 0) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
         if (!r.n_views) {       // (windows, or whole images, as one view per image: the plan decodes whole images)
             q.own_views.resize((size_t)b->n_images);
@@ -906,7 +918,7 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
 int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request, mj_plan_request *normal) {
     if (!normal) return MJ_ERR_INVALID;
     mj_plan *none = nullptr;
-    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request)};
+    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request), request_perspective(request)};
     const int rc = normalise_request(q, false);
     if (rc == MJ_OK) *normal = q.r;
     if (rc == MJ_OK && q.colour) normal->mode |= MJ_MODE_COLOUR_OPS;
@@ -914,7 +926,7 @@ int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request
 }
 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
-    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request)};
+    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request), request_perspective(request)};
     if (int rc = normalise_request(q)) return rc;
     if (q.r.out_width) return mj::create_resized(q);
     if (q.r.orientations || q.r.mode) return mj::create_oriented(q);

@@ -219,27 +219,44 @@ int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std:
 // In: the request (views in place, matrices checked), the plan, CO — the components the launch writes.  Out: the plan's affine
 // launch (p->af, records and tables uploaded), `off` — per output, where its window lies in the buffer of transformed windows —
 // and *bytes, that buffer's size.
+// (a perspective transform — q.perspective — has records of its own and no tables: p->pf, and p->perspective says so)
 int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> &off, int64_t *bytes) {
     const char *fn = mj::kCreateFn;
     const uint8_t *orient = q.r.orientations;
-    const int n = q.r.n_views, filter = (int)(q.r.affine & 0xFF);
-    std::vector<mj::DevAffineImage> recs((size_t)n);
+    const int n = q.r.n_views, filter = (int)(q.r.affine & 0xFF & ~MJ_AFFINE_PERSPECTIVE);
+    std::vector<mj::DevAffineImage> recs(q.perspective ? 0 : (size_t)n);
+    std::vector<mj::DevPerspectiveImage> precs(q.perspective ? (size_t)n : 0);
     std::vector<int32_t> tabs;
     off.resize((size_t)n);
-    mj::AffineArgs &a = p->af = mj::AffineArgs{};
     const bool rowmajor = (p->layout & 1) != 0;
     int max_slow = 1, max_fast = 1;
     int64_t at = 0;
-    for (int k = 0; k < n; ++k) {
+    // what both kinds of record say of output k: its image, orientation and window, and where its window goes
+    auto place = [&](int k, auto &d) {
         const int i = q.views[k].image;
         mj_roi shown, stored;
         mj::view_window(q.b, orient, q.views[k], &shown, &stored);      // (checked by the request's normalisation)
-        mj::DevAffineImage &d = recs[(size_t)k] = mj::DevAffineImage{};
         d.src_off = p->h_images[i].rgb_off; d.dst_off = off[(size_t)k] = at;
         d.sw = p->h_images[i].width; d.sh = p->h_images[i].height;
         d.obits = orient ? mj::orient_bits(orient[i]) : 0;
         d.w = (d.obits & 4) ? d.sh : d.sw; d.h = (d.obits & 4) ? d.sw : d.sh;
         d.x0 = shown.x; d.y0 = shown.y; d.win_w = shown.width; d.win_h = shown.height;
+        at += (int64_t)d.win_w * d.win_h * CO;
+        max_fast = std::max(max_fast, rowmajor ? d.win_w : d.win_h); max_slow = std::max(max_slow, rowmajor ? d.win_h : d.win_w);
+    };
+    for (int k = 0; k < n; ++k) {
+        if (q.perspective) {
+            mj::DevPerspectiveImage &d = precs[(size_t)k] = mj::DevPerspectiveImage{};
+            place(k, d);
+            const mj_perspective &m = q.perspective[k];
+            if (!mj::perspective_none(m)) {
+                d.kind = mj::perspective_kind(filter);
+                for (int t = 0; t < 8; ++t) d.c[t] = m.a[t];
+            }
+            continue;
+        }
+        mj::DevAffineImage &d = recs[(size_t)k] = mj::DevAffineImage{};
+        place(k, d);
         const mj_affine &m = q.affine[k];
         if (!mj::affine_none(m)) {
             d.kind = mj::affine_kind(m.a, filter);
@@ -253,19 +270,26 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
                 if (tabs.size() > ((size_t)1 << 28)) return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: the index tables of this batch are too large", fn);
             }
         }
-        at += (int64_t)d.win_w * d.win_h * CO;
-        max_fast = std::max(max_fast, rowmajor ? d.win_w : d.win_h); max_slow = std::max(max_slow, rowmajor ? d.win_h : d.win_w);
     }
-    a.tiles_fast = (max_fast + mj::kAffineTileFast - 1) / mj::kAffineTileFast;
-    a.tiles_slow = (max_slow + mj::kAffineTileSlow - 1) / mj::kAffineTileSlow;
-    if ((int64_t)n * a.tiles_slow * a.tiles_fast > mj::kResizeGridX * (int64_t)65535)
-        return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld affine tiles are more than one launch takes; split the batch", fn, (long long)n * a.tiles_slow * a.tiles_fast);
-    a.n_images = n; a.layout = p->layout;
-    for (int c = 0; c < CO; ++c) a.fill |= ((q.r.affine >> (8 + 8 * c)) & 0xFFu) << (8 * c);
+    const int tiles_fast = (max_fast + mj::kAffineTileFast - 1) / mj::kAffineTileFast, tiles_slow = (max_slow + mj::kAffineTileSlow - 1) / mj::kAffineTileSlow;
+    if ((int64_t)n * tiles_slow * tiles_fast > mj::kResizeGridX * (int64_t)65535)
+        return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld affine tiles are more than one launch takes; split the batch", fn, (long long)n * tiles_slow * tiles_fast);
+    uint32_t fill = 0;
+    for (int c = 0; c < CO; ++c) fill |= ((q.r.affine >> (8 + 8 * c)) & 0xFFu) << (8 * c);
+    *bytes = at;
+    if (q.perspective) {
+        mj::PerspectiveArgs &a = p->pf = mj::PerspectiveArgs{};
+        a.tiles_fast = tiles_fast; a.tiles_slow = tiles_slow; a.n_images = n; a.layout = p->layout; a.fill = fill;
+        if (int rc = upload(p, &p->d_pf_images, precs.data(), precs.size())) return rc;
+        a.images = p->d_pf_images;
+        p->perspective = true;
+        return MJ_OK;
+    }
+    mj::AffineArgs &a = p->af = mj::AffineArgs{};
+    a.tiles_fast = tiles_fast; a.tiles_slow = tiles_slow; a.n_images = n; a.layout = p->layout; a.fill = fill;
     if (int rc = upload(p, &p->d_af_images, recs.data(), recs.size())) return rc;
     if (int rc = upload(p, &p->d_af_tabs, tabs.data(), tabs.size())) return rc;
     a.images = p->d_af_images; a.tabs = p->d_af_tabs;
-    *bytes = at;
     return MJ_OK;
 }
 
@@ -693,7 +717,7 @@ int mj::create_resized(const PlanRequest &q) {
     if (affine) {
         // the transformed windows: a second plan-owned buffer with the same slack, which the resize launch reads as it would d_src
         MJ_HIP(ctx, alloc(p, &p->d_aff, (size_t)af_bytes + 64));
-        p->af.src = p->d_src; p->af.dst = p->d_aff;
+        p->af.src = p->pf.src = p->d_src; p->af.dst = p->pf.dst = p->d_aff;
         a.src = p->d_aff;
         p->affine = true; p->af_ncomp = CO; p->af_bytes = af_bytes;
     }

@@ -80,7 +80,15 @@ def transform(img: np.ndarray, a, resample: str = "nearest", fill=0, window=None
     xin = a[0] * xc + a[1] * yc + a[2]
     yin = a[3] * xc + a[4] * yc + a[5]
     ok = ~((xin < 0.0) | (xin >= w) | (yin < 0.0) | (yin >= h))
-    xin, yin = xin[ok] - 0.5, yin[ok] - 0.5
+    out[ok] = taps(src, xin[ok], yin[ok], resample)
+    return out.reshape((wh, ww) + img.shape[2:])
+
+
+def taps(src: np.ndarray, xin: np.ndarray, yin: np.ndarray, resample: str) -> np.ndarray:
+    """The bilinear / bicubic bytes (n, C) of source coordinates (xin, yin) — n doubles each, all INSIDE the image src (h, w, C) —:
+    the 2 x 2 / 4 x 4 taps around (xin - 0.5, yin - 0.5) as the module's head describes them.  tools/perspective_model.py shares it."""
+    h, w = src.shape[:2]
+    xin, yin = xin - 0.5, yin - 0.5
     ix, iy = np.floor(xin).astype(np.int64), np.floor(yin).astype(np.int64)
     dx, dy = (xin - ix)[:, None], (yin - iy)[:, None]
     s = src.astype(np.float64)
@@ -95,8 +103,8 @@ def transform(img: np.ndarray, a, resample: str = "nearest", fill=0, window=None
         v1 = row(cy(iy))
         inside = ((iy + 1 >= 0) & (iy + 1 < h))[:, None]
         v2 = np.where(inside, row(cy(iy + 1)), v1)
-        out[ok] = (v1 + (v2 - v1) * dy).astype(np.int64).astype(np.uint8)
-    elif resample == "bicubic":
+        return (v1 + (v2 - v1) * dy).astype(np.int64).astype(np.uint8)
+    if resample == "bicubic":
         c = [cx(ix - 1), cx(ix), cx(ix + 1), cx(ix + 2)]
 
         def row(r):
@@ -106,10 +114,8 @@ def transform(img: np.ndarray, a, resample: str = "nearest", fill=0, window=None
             inside = ((iy + k >= 0) & (iy + k < h))[:, None]
             v.append(np.where(inside, row(cy(iy + k)), v[-1]))
         t = _cubic(v[0], v[1], v[2], v[3], dy)
-        out[ok] = np.where(t <= 0.0, 0, np.where(t >= 255.0, 255, np.trunc(np.clip(t, 0.0, 255.0)))).astype(np.uint8)
-    else:
-        raise ValueError(f"resample must be one of {FILTERS}, not {resample!r}")
-    return out.reshape((wh, ww) + img.shape[2:])
+        return np.where(t <= 0.0, 0, np.where(t >= 255.0, 255, np.trunc(np.clip(t, 0.0, 255.0)))).astype(np.uint8)
+    raise ValueError(f"resample must be one of {FILTERS}, not {resample!r}")
 
 
 def rotation_matrix(angle: float, size, center=None, translate=None):
