@@ -2,9 +2,10 @@
 tests/view_routes_common.py — the thirteen files of tests/routes_common.py (ordinary, declined, MJ_ST_TAIL, MJ_ST_UNCONVERGED) as
 some thirty interleaved views behind a leading entry that is no JPEG — through decode, decode_device (one call, three parts) and
 decode_device_iter, as views alone, with mode and a bicubic resize, with places, fill, float16 normalisation and mirror flags, with
-a NEAREST affine transform (index tables among the matrices) and with a bicubic one on turned files.  Every view is held to
+a NEAREST affine transform (index tables among the matrices) and with a bicubic one on turned files, with a colour chain per view
+behind a float16 output, with a bicubic perspective transform on turned files and with a NEAREST one in front of chains in mode "L".  Every view is held to
 view_routes_common.expect (the models on the oracle's pixels; floats as bit patterns); a recording `_binding.Plan` proves that the
-second rounds ran and that every plan got exactly its own views' slots, windows, matrices, places and flags.  A damaged file is
+second rounds ran and that every plan got exactly its own views' slots, windows, matrices, coefficients, chains, places and flags.  A damaged file is
 named by its position in the caller's list.  tests/test_view_routes_host.py holds, on the CPU, that these expectations tell a
 decoder that mixes views up from a right one."""
 import numpy as np
@@ -18,7 +19,9 @@ pytestmark = pytest.mark.gpu
 
 # two layouts per combination, all four for one
 LAYOUTS_OF = {"views": ("xmajor", "planar_rowmajor"), "L_bicubic": ("rowmajor", "planar"), "places_f16": ("xmajor", "planar_rowmajor"),
-              "affine_nearest": ("rowmajor", "planar_rowmajor"), "affine_bicubic_orient": ("xmajor", "rowmajor", "planar", "planar_rowmajor")}
+              "affine_nearest": ("rowmajor", "planar_rowmajor"), "affine_bicubic_orient": ("xmajor", "rowmajor", "planar", "planar_rowmajor"),
+              "colour_f16": ("xmajor", "rowmajor", "planar", "planar_rowmajor"), "perspective_bicubic_orient": ("rowmajor", "planar"),
+              "perspective_nearest_colour_L": ("xmajor", "planar_rowmajor")}
 CASES = [(c, lay) for c, lays in LAYOUTS_OF.items() for lay in lays]
 
 
@@ -62,9 +65,7 @@ def _check_plans(plans, call, cname, on_device, what, **kw):
     kw.setdefault("one_plan_each", True)
     kw["one_plan_each"] = kw["one_plan_each"] and not VC.COMBOS[cname].get("orientation")
     assert_second_rounds([r.rec for r in records], call.entries, False, what, **kw)
-    bare = VC.assert_plans_hold_their_views(records, call, cname, on_device, what)
-    if VC.COMBOS[cname].get("affine") and VC.UNTRANSFORMED in call.gis:
-        assert bare >= 1, (what, "no plan without a transformed view")
+    VC.assert_bare_plans(VC.assert_plans_hold_their_views(records, call, cname, on_device, what), call, cname, what)
 
 
 @pytest.mark.parametrize("cname,layout", CASES)
@@ -91,18 +92,14 @@ def test_every_view_through_second_rounds(call, unsettled, plans, cname, layout)
 
 @pytest.mark.parametrize("cname,layout", [(c, lay) for c, lay in CASES if not VC.COMBOS[c].get("places")])
 def test_every_view_through_collects_redo(call, unsettled, plans, cname, layout):  # noqa: F811
-    """decode_device_iter: views, flags, matrices and orientations come batch by batch (the list forms of resize_to and place would
+    """decode_device_iter: views, flags, matrices, coefficients, chains and orientations come batch by batch (the list forms of resize_to and place would
     have to fit every batch, so the iterator is not given them); the third batch is one pipelined plan whose collect() sends its tail
     file and its unconverged files round again through a narrowed request"""
     from pyjpegdecoder_amd import BatchDecoder
     entries = call.entries
     raws = [e.raw for e in entries]
     calls = [VC.make_call([entries[i] for i in b], list(b)) for b in ITER_BATCHES]
-    kws = [VC.call_kwargs(c, cname) for c in calls]
-    kw = {k: v for k, v in kws[0].items() if k not in ("views", "mirror", "affine", "orientation")}
-    for name in ("views", "mirror", "affine", "orientation"):
-        if name in kws[0]:
-            kw[name] = iter([k[name] for k in kws])
+    kw = VC.iter_kwargs(calls, cname)
     dec = BatchDecoder(device=0, layout=layout, segment="gpu", gpu_segment_min_files=1)
     try:
         assert_the_rounds_do_not_settle(dec, entries, plans)
@@ -137,11 +134,11 @@ def test_errors_name_the_position_in_the_callers_list(plans, what):
     named = at + 1
     dec = BatchDecoder(device=0, segment="gpu", gpu_segment_min_files=1)
     try:
-        for cname in ("views", "affine_bicubic_orient"):
+        for cname in ("views", "affine_bicubic_orient", "perspective_bicubic_orient", "colour_f16"):
             kw = VC.call_kwargs(call, cname)
-            per_batch = {k: (iter([v]) if k in ("views", "mirror", "affine", "orientation") else v) for k, v in kw.items()}
             for name, route in (("decode", lambda: dec.decode(call.files, **kw)), ("decode_device", lambda: dec.decode_device(call.files, **kw)),
-                                ("decode_device_iter", lambda: list(dec.decode_device_iter([call.files], **per_batch)))):
+                                ("decode_device_iter", lambda: list(dec.decode_device_iter(
+                                    [call.files], **{k: (iter([v]) if k in VC.PER_BATCH else v) for k, v in kw.items()})))):
                 with pytest.raises(CorruptedJpeg, match=rf"^image {named}: Failed to decode image") as err:
                     route()
                 holders = [h for h in (files_of(r.rec, call.files) for r in plans.take()) if named in h]
@@ -168,6 +165,30 @@ def test_an_affine_refusal_names_the_output_and_the_file_in_the_callers_numberin
             kw["affine"][v.k] = (1.0, 0.0, 40000.0, 0.0, 1.0, 0.0)
             for route in (dec.decode, dec.decode_device):
                 with pytest.raises(ValueError, match=rf"^affine: output {v.k} \(file {v.file}\): a corner of the output has a source coordinate"):
+                    route(call.files, **kw)
+        assert not plans.take(), "a plan was made for a call that is refused"
+    finally:
+        dec.close()
+
+
+def test_a_perspective_refusal_and_a_bad_chain_name_the_output_in_the_callers_numbering(call, plans):
+    from pyjpegdecoder_amd import BatchDecoder
+    tail = positions(call.entries, "tail")[1]
+    v = [v for v in call.views if v.file == tail + 1][1]
+    cases = [("perspective_bicubic_orient", "perspective", (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, float("inf"), 0.0),
+              rf"^perspective: output {v.k} \(file {v.file}\): a coefficient is not finite"),
+             ("perspective_nearest_colour_L", "perspective", (1.0, 0.0, float("nan"), 0.0, 1.0, 0.0, 0.0, 0.0),
+              rf"^perspective: output {v.k} \(file {v.file}\): a coefficient is not finite"),
+             ("colour_f16", "color_ops", (("posterize", 9),), rf"^color_ops: output {v.k}: posterize takes 1\.\.8 bits"),
+             ("perspective_nearest_colour_L", "color_ops", (("invert",), ("posterize", 9)), rf"^color_ops: output {v.k}: posterize takes 1\.\.8 bits")]
+    dec = BatchDecoder(device=0, segment="gpu", gpu_segment_min_files=1)
+    try:
+        for cname, name, bad, text in cases:
+            kw = VC.call_kwargs(call, cname)
+            kw[name] = list(kw[name])
+            kw[name][v.k] = bad
+            for route in (dec.decode, dec.decode_device):
+                with pytest.raises(ValueError, match=text):
                     route(call.files, **kw)
         assert not plans.take(), "a plan was made for a call that is refused"
     finally:

@@ -2,11 +2,12 @@
 tests/view_routes_common.py through BatchDecoder.decode, decode_device (one call, three parts) and decode_device_iter with stand-ins
 for `_binding.Context`, `_binding.Plan` and torch, as tests/test_request_routes_host.py does for calls without views.  The stand-in
 plan takes every keyword `_Request.plan_kwargs` can produce and computes output k of the plan from what THAT plan was given, per
-view of that plan — views, orientation, mode, filter, places / fill, affine, output, slots — with tools/affine_model.expected on
-the oracle's pixels and tools/normalize_model; it reads nothing of batch._Request, and it refuses a window that does not lie inside
+view of that plan — views, orientation, mode, filter, places / fill, affine or perspective, colour, output, slots — with
+tools/affine_model.expected or tools/perspective_model.expected on the oracle's pixels, tools/colour_model.apply_chain and
+tools/normalize_model; it reads nothing of batch._Request, and it refuses a window that does not lie inside
 its oriented image, as the library does.  Statuses are scripted as in test_request_routes_host.py.  So what is held here is the
-host's part alone: which file, window, flag, matrix, place and slot every view of every plan gets — through `_Request.narrow` at
-every level —, and which position an error names."""
+host's part alone: which file, window, flag, matrix, coefficient set, chain, place and slot every view of every plan gets —
+through `_Request.narrow` at every level —, and which position an error names."""
 import sys
 from types import SimpleNamespace
 
@@ -32,13 +33,15 @@ class _ViewBackend(_Backend):
 
         class Plan:
             def __init__(self, ctx, batch_c, keepalive, rois=None, size=None, slots=None, output=None, orientation=None, filter=None, mode=None,
-                         places=None, fill=None, reducing_gap=None, views=None, affine=None):
+                         places=None, fill=None, reducing_gap=None, views=None, affine=None, colour=None, perspective=None):
                 prep = keepalive["prep"]
                 n = int(batch_c.n_images)
                 assert n == keepalive["n_images"] == len(prep.parsed) and reducing_gap is None
-                assert size is not None or (slots is None and output is None and views is None and places is None and affine is None)
+                assert size is not None or (slots is None and output is None and views is None and places is None and affine is None
+                                            and colour is None and perspective is None)
+                assert affine is None or perspective is None
                 self.kw = dict(rois=rois, size=size, slots=slots, output=output, orientation=orientation, filter=filter, mode=mode, places=places,
-                               fill=fill, views=views, affine=affine)
+                               fill=fill, views=views, affine=affine, colour=colour, perspective=perspective)
                 turns = list(orientation) if orientation is not None else [1] * n
                 assert len(turns) == n
                 dims = [(h, w) if o >= 5 else (w, h) for (w, h, _), o in zip(prep.shapes, turns)]
@@ -47,7 +50,8 @@ class _ViewBackend(_Backend):
                 self.views = [(int(f), tuple(int(t) for t in w) if w is not None else (0, 0) + dims[int(f)]) for f, w in views]
                 n_out = len(self.views)
                 for name, per_output in (("slots", slots[0] if slots is not None else None), ("mirror", output[3] if output is not None else None),
-                                         ("places", places), ("affine", affine[0] if affine is not None else None)):
+                                         ("places", places), ("affine", affine[0] if affine is not None else None), ("colour", colour),
+                                         ("perspective", perspective[0] if perspective is not None else None)):
                     assert per_output is None or len(per_output) == n_out, f"{name}: {len(per_output)} entries for a plan of {n_out} outputs"
                 for k, (f, (x, y, ww, wh)) in enumerate(self.views):          # as mj_plan_create_with does
                     assert 0 <= f < n
@@ -70,21 +74,26 @@ class _ViewBackend(_Backend):
                 self.info = SimpleNamespace(rgb_bytes=self.per * (int(slots[1]) if slots is not None else n_out))
 
             def _image(self, k: int) -> np.ndarray:
-                from tools import affine_model, normalize_model
+                from tools import affine_model, colour_model, normalize_model, perspective_model
                 f, win = self.views[k]
                 kw = self.kw
                 dtype, mean, std, mirror = self.output if self.output is not None else (None, None, None, None)
                 a, resample, afill = (kw["affine"][0][k], kw["affine"][1], tuple(kw["affine"][2])) if kw["affine"] is not None else (None, "nearest", (0,))
+                if kw["perspective"] is not None:
+                    a, resample, afill = kw["perspective"][0][k], kw["perspective"][1], tuple(kw["perspective"][2])
+                model = perspective_model if kw["perspective"] is not None else affine_model
+                chain = kw["colour"][k] if kw["colour"] is not None else None
                 place = tuple(kw["places"][k]) if kw["places"] is not None else tuple(self.size) + (0, 0)
                 fill = tuple(kw["fill"]) if kw["fill"] is not None else (0,)
                 flip = bool(mirror[k]) if mirror is not None else False
-                key = (self.raws[f], a, win, tuple(self.size), resample, afill, kw["filter"], self.turns[f], kw["mode"], place, fill, dtype,
+                key = (self.raws[f], a, win, tuple(self.size), resample, afill, kw["filter"], self.turns[f], kw["mode"], place, fill, dtype, chain,
                        None if mean is None else (tuple(np.ravel(mean)), tuple(np.ravel(std))))
                 if key not in _images:
                     px = np.ascontiguousarray(be.full(self.raws[f]).swapaxes(0, 1))
                     one = lambda t: (t if len(t) == self.ncomp else t * self.ncomp) if self.ncomp == 3 else t[0]          # noqa: E731
-                    rm = affine_model.expected(px, a, win, self.size, resample=resample, affine_fill=one(afill), filter=kw["filter"] or "bilinear",
+                    rm = model.expected(px, a, win, self.size, resample=resample, affine_fill=one(afill), filter=kw["filter"] or "bilinear",
                                                orientation=self.turns[f], mode=kw["mode"], resized=place[:2], xy=place[2:], fill=one(fill))
+                    rm = colour_model.apply_chain(rm, chain)
                     if dtype not in (None, "uint8"):
                         rm = normalize_model.normalize(rm, dtype, mean, std)
                     _images[key] = rm
@@ -147,7 +156,7 @@ def call():
 
 def test_the_expectations_tell_the_views_of_the_call_apart(call):
     VC.assert_expectations_tell_views_apart(call, list(VC.COMBOS), ("xmajor",))
-    VC.assert_expectations_tell_views_apart(call, ("places_f16", "affine_bicubic_orient"), ("planar_rowmajor",))
+    VC.assert_expectations_tell_views_apart(call, ("places_f16", "affine_bicubic_orient", "colour_f16", "perspective_nearest_colour_L"), ("planar_rowmajor",))
 
 
 def _decoder(layout, **kw):
@@ -160,9 +169,7 @@ def _check_plans(be, call, cname, on_device, what, one_plan_each=True):
     assert_second_rounds([r.rec for r in records], call.entries, False, what,
                          one_plan_each=one_plan_each and not VC.COMBOS[cname].get("orientation"))
     # (files_of by the call's own list: the plan's files are positions in the CALLER's list, the leading non-JPEG counted)
-    bare = VC.assert_plans_hold_their_views(records, call, cname, on_device, what)
-    if VC.COMBOS[cname].get("affine") and VC.UNTRANSFORMED in call.gis:
-        assert bare >= 1, (what, "no plan without a transformed view: the check that it carries no affine ran on nothing")
+    VC.assert_bare_plans(VC.assert_plans_hold_their_views(records, call, cname, on_device, what), call, cname, what)
     assert all(p.closed for p in be.plans), what
 
 
@@ -204,11 +211,7 @@ def test_decode_device_iter_every_view_through_collects_redo(monkeypatch, call, 
     calls = [VC.make_call([entries[i] for i in b], list(b)) for b in ITER_BATCHES]
     be = _ViewBackend(_script(entries), known=[e.raw for e in entries]).install(monkeypatch)
     monkeypatch.setitem(sys.modules, "torch", _torch_stand_in(be))
-    kws = [VC.call_kwargs(c, cname) for c in calls]
-    kw = {k: v for k, v in kws[0].items() if k not in ("views", "mirror", "affine", "orientation")}
-    for name in ("views", "mirror", "affine", "orientation"):
-        if name in kws[0]:
-            kw[name] = iter([k[name] for k in kws])
+    kw = VC.iter_kwargs(calls, cname)
     dec = _decoder(layout)
     try:
         outs = list(dec.decode_device_iter([c.files for c in calls], depth=2, **kw))
@@ -251,7 +254,7 @@ def _finish_damaged(entries, at):
     return entries
 
 
-@pytest.mark.parametrize("cname", ["views", "affine_bicubic_orient"])
+@pytest.mark.parametrize("cname", ["views", "affine_bicubic_orient", "perspective_bicubic_orient", "colour_f16"])
 @pytest.mark.parametrize("what", ["first_round", "second_round", "in_parts", "collects_redo"])
 def test_errors_name_the_position_in_the_callers_list(monkeypatch, what, cname):
     """a views call whose damaged file is found in a first round, in a second round, in the third part of a call and in collect()'s
@@ -277,7 +280,7 @@ def test_errors_name_the_position_in_the_callers_list(monkeypatch, what, cname):
                 elif route == "parts":
                     dec.decode_device(call.files, parts=3, **kw)
                 else:
-                    list(dec.decode_device_iter([call.files], **{k: (iter([v]) if k in ("views", "mirror", "affine", "orientation") else v) for k, v in kw.items()}))
+                    list(dec.decode_device_iter([call.files], **{k: (iter([v]) if k in VC.PER_BATCH else v) for k, v in kw.items()}))
             records = be.take_records()
             holders = [files_of(r.rec, call.files) for r in records if named in files_of(r.rec, call.files)]
             assert holders, (route, "no plan held the damaged file")
@@ -306,6 +309,33 @@ def test_an_affine_refusal_names_the_output_and_the_file_in_the_callers_numberin
         try:
             for route in (dec.decode, dec.decode_device):
                 with pytest.raises(ValueError, match=rf"^affine: output {v.k} \(file {v.file}\): a corner of the output has a source coordinate"):
+                    route(call.files, **kw)
+            assert not be.plans, "a plan was made for a call that is refused"
+        finally:
+            dec.close()
+
+
+def test_a_perspective_refusal_and_a_bad_chain_name_the_output_in_the_callers_numbering(monkeypatch, call):
+    """a coefficient that is not finite for ONE view of a second-round file: `output k (file i)` as an affine refusal names them; a
+    chain that cannot be for that view: `output k`; no plan is made for either call"""
+    tail = positions(call.entries, "tail")[1]
+    v = [v for v in call.views if v.file == tail + 1][1]
+    cases = [("perspective_bicubic_orient", "perspective", (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, float("inf"), 0.0),
+              rf"^perspective: output {v.k} \(file {v.file}\): a coefficient is not finite"),
+             ("perspective_nearest_colour_L", "perspective", (1.0, 0.0, float("nan"), 0.0, 1.0, 0.0, 0.0, 0.0),
+              rf"^perspective: output {v.k} \(file {v.file}\): a coefficient is not finite"),
+             ("colour_f16", "color_ops", (("posterize", 9),), rf"^color_ops: output {v.k}: posterize takes 1\.\.8 bits"),
+             ("perspective_nearest_colour_L", "color_ops", (("invert",), ("posterize", 9)), rf"^color_ops: output {v.k}: posterize takes 1\.\.8 bits")]
+    for cname, name, bad, text in cases:
+        kw = VC.call_kwargs(call, cname)
+        kw[name] = list(kw[name])
+        kw[name][v.k] = bad
+        be = _ViewBackend(_script(call.entries), known=call.files[1:]).install(monkeypatch)
+        monkeypatch.setitem(sys.modules, "torch", _torch_stand_in(be))
+        dec = _decoder("xmajor")
+        try:
+            for route in (dec.decode, dec.decode_device):
+                with pytest.raises(ValueError, match=text):
                     route(call.files, **kw)
             assert not be.plans, "a plan was made for a call that is refused"
         finally:

@@ -1,13 +1,14 @@
 """What the view-route tests share (tests/test_view_routes.py on the MI355X, tests/test_view_routes_host.py with a stand-in back
 end): the call of tests/routes_common.py — files of every kind, some of which go round again — asked for as VIEWS, two or three per
-file and interleaved, behind a leading entry that is no JPEG and that no view names; what is per view (window, mirror flag, matrix,
-place) and per file (orientation) under each combination of arguments; ONE expectation per view; and the reading of the plans a
+file and interleaved, behind a leading entry that is no JPEG and that no view names; what is per view (window, mirror flag, matrix or
+perspective coefficients, colour chain, place) and per file (orientation) under each combination of arguments; ONE expectation per view; and the reading of the plans a
 call made against the call's views.  Not a test file: nothing here is collected.
 
 The expectation of a view (`expect`) is the models' pipeline evaluated on the view's window only — tools/mode_model.convert,
-orient_model.orient, affine_model.transform(window=), place_model.place, the mirror, normalize_model.normalize — on the oracle's
-pixels; the stand-in plan of the host file computes the same view with tools/affine_model.expected, which transforms the whole
-image and cuts the window out, so that the two agree is itself held."""
+orient_model.orient, affine_model.transform(window=) or perspective_model.transform(window=), place_model.place,
+colour_model.apply_chain, the mirror, normalize_model.normalize — on the oracle's pixels; the stand-in plan of the host file
+computes the same view with tools/affine_model.expected or tools/perspective_model.expected, which transform the whole image and
+cut the window out, so that the two agree is itself held."""
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -32,7 +33,11 @@ COMBOS = {
     "places_f16": dict(places=True, dtype="float16", mirror=True),
     "affine_nearest": dict(affine="nearest"),
     "affine_bicubic_orient": dict(affine="bicubic", orientation=True, mirror=True),
+    "colour_f16": dict(colour=True, dtype="float16", mirror=True),
+    "perspective_bicubic_orient": dict(perspective="bicubic", orientation=True, mirror=True),
+    "perspective_nearest_colour_L": dict(perspective="nearest", colour=True, mode="L"),
 }
+HIST_OPS, BLUR_OPS = ("contrast", "autocontrast", "equalize"), ("gaussian_blur", "box_blur")
 
 
 @dataclass
@@ -100,6 +105,53 @@ def matrix_of(call: ViewCall, v: View, combo: dict):
     return rotate_shear((W, H), -20.0 + 4.0 * t, 0.1, (t % 3, -(t % 4)))
 
 
+def chain_of(v: View):
+    """the view's own colour chain (a tuple of ops, as the request holds it) under the colour combinations: some None, the others
+    pairwise different — every factor, threshold and radius is made from t —, one to four ops long, every kind of op among them;
+    ("equalize",) stands first in some chains and second in others"""
+    if v.gi == UNTRANSFORMED:
+        return None
+    t = 3 * v.gi + v.j
+    m = t % 8
+    if m == 0:
+        return (("contrast", 0.6 + 0.03 * t), ("gaussian_blur", 0.9 + 0.05 * t))
+    if m == 1:
+        return (("equalize",), ("brightness", 0.7 + 0.02 * t))
+    if m == 2:
+        return (("box_blur", 0.25 + 0.1 * t), ("solarize", float(100 + t)), ("invert",))
+    if m == 3:
+        return None
+    if m == 4:
+        return (("sharpness", 0.5 + 0.05 * t), ("color", 0.3 + 0.04 * t), ("posterize", float(2 + t % 6)), ("autocontrast",))
+    if m == 5:
+        return (("brightness", 0.7 + 0.02 * t), ("equalize",))
+    if m == 6:
+        return (("gaussian_blur", 0.8 + 0.04 * t),)
+    return (("autocontrast",), ("contrast", 1.9 - 0.03 * t), ("box_blur", 0.5 + 0.07 * t))
+
+
+def coeffs_of(call: ViewCall, v: View, combo: dict):
+    """the view's own perspective coefficients under the perspective combinations (some None): the corners of its file's oriented
+    image drawn inwards by two to seven per cent of the side, every corner by its own amount, every view by its own"""
+    if not combo.get("perspective") or v.gi == UNTRANSFORMED:
+        return None
+    from tools import perspective_model
+    W, H = oriented_dims(call, v, combo)
+    t = 3 * v.gi + v.j
+    if t % (4 if combo["perspective"] == "nearest" else 5) == 0:
+        return None
+    ends = []
+    for i, (x, y) in enumerate(perspective_model.corners(W, H)):
+        fx, fy = 0.02 + 0.01 * ((t + 2 * i) % 5) + 0.0007 * t, 0.02 + 0.01 * ((3 * t + i) % 5) + 0.0005 * t
+        ends.append((x + fx * W if x == 0 else x - fx * W, y + fy * H if y == 0 else y - fy * H))
+    return perspective_model.coeffs(perspective_model.corners(W, H), ends)
+
+
+def transform_fill(combo: dict):
+    """affine_fill as the call passes it: one byte per output component"""
+    return AFFINE_FILL[0] if combo.get("mode") == "L" else AFFINE_FILL
+
+
 def place_of(v: View):
     """(width, height, x, y): the view's own resize_to and place on the canvas SIZE"""
     t = 3 * v.gi + v.j
@@ -121,8 +173,25 @@ def call_kwargs(call: ViewCall, cname: str, entry_point: str = "decode_device") 
         kw.update(resize_to=[place_of(v)[:2] for v in call.views], place=[place_of(v)[2:] for v in call.views], fill=FILL)
     if combo.get("affine"):
         kw.update(affine=[matrix_of(call, v, combo) for v in call.views], affine_resample=combo["affine"], affine_fill=AFFINE_FILL)
+    if combo.get("perspective"):
+        kw.update(perspective=[coeffs_of(call, v, combo) for v in call.views], affine_resample=combo["perspective"], affine_fill=transform_fill(combo))
+    if combo.get("colour"):
+        kw["color_ops"] = [chain_of(v) for v in call.views]
     if combo.get("orientation"):
         kw["orientation"] = [1] + [ORIENT[g] for g in call.gis]
+    return kw
+
+
+PER_BATCH = ("views", "mirror", "affine", "orientation", "color_ops", "perspective")         # what decode_device_iter takes batch by batch
+
+
+def iter_kwargs(calls: List[ViewCall], cname: str) -> dict:
+    """the keyword arguments of decode_device_iter for these batches: what is per view or per file as one iterator over the batches"""
+    kws = [call_kwargs(c, cname) for c in calls]
+    kw = {k: v for k, v in kws[0].items() if k not in PER_BATCH}
+    for name in PER_BATCH:
+        if name in kws[0]:
+            kw[name] = iter([k[name] for k in kws])
     return kw
 
 
@@ -138,26 +207,32 @@ def pixels_rm(e: CallFile) -> np.ndarray:
 _expect = {}
 
 
-def expect(call: ViewCall, v: View, cname: str, layout: str, window="own", matrix="own", place="own", mirror="own") -> np.ndarray:
-    """One view's output under a combination: uint8 pixels or the bit patterns of float16.  window / matrix / place / mirror: the
-    view's own, or another's — what a decoder that mixes views up would compute."""
-    from tools import affine_model, mode_model, normalize_model, orient_model, place_model
+def expect(call: ViewCall, v: View, cname: str, layout: str, window="own", matrix="own", place="own", mirror="own", chain="own",
+           coeffs="own") -> np.ndarray:
+    """One view's output under a combination: uint8 pixels or the bit patterns of float16.  window / matrix / place / mirror / chain /
+    coeffs: the view's own, or another's — what a decoder that mixes views up would compute."""
+    from tools import affine_model, colour_model, mode_model, normalize_model, orient_model, perspective_model, place_model
     combo = COMBOS[cname]
     e = call.entries[v.file - 1]
     win = window_of(call, v, combo) if window == "own" else window
     a = matrix_of(call, v, combo) if matrix == "own" else matrix
     pl = (place_of(v) if place == "own" else place) if combo.get("places") else SIZE + (0, 0)
     flip = (mirror_of(v) if mirror == "own" else mirror) if combo.get("mirror") else False
-    key = (e.name, cname, win, a, pl)
+    c = coeffs_of(call, v, combo) if coeffs == "own" else coeffs
+    ch = (chain_of(v) if chain == "own" else chain) if combo.get("colour") else None
+    key = (e.name, cname, win, a, pl, c, ch)
     if key not in _expect:
         img = orient_model.orient(mode_model.convert(pixels_rm(e), combo.get("mode")), ORIENT[v.gi] if combo.get("orientation") else 1)
         x, y, w, h = win
-        if a is not None:
-            fill = AFFINE_FILL if img.ndim == 3 else AFFINE_FILL[0]
+        fill = AFFINE_FILL if img.ndim == 3 else AFFINE_FILL[0]
+        if c is not None:
+            part = perspective_model.transform(img, c, combo["perspective"], fill, win)
+        elif a is not None:
             part = affine_model.transform(img, a, combo["affine"], fill, win)
         else:
             part = np.ascontiguousarray(img[y:y + h, x:x + w])
         out = place_model.place(part, pl[:2], pl[2:], SIZE, FILL if combo.get("places") else 0, combo.get("resample") or "bilinear")
+        out = colour_model.apply_chain(out, ch)
         if combo.get("dtype"):
             out = normalize_model.normalize(out, combo["dtype"], *NORMALIZE)
         _expect[key] = out
@@ -179,9 +254,9 @@ def others_of(call: ViewCall, v: View) -> List[View]:
 
 def assert_expectations_tell_views_apart(call: ViewCall, cnames, layouts):
     """Without this the view-by-view comparison could pass for a decoder that mixes views up: the expectations of all views are
-    pairwise different; each changes with its own flag; each changes when given the window, the matrix or the place of the view
-    before it, of the view after it and of a view of another file, where that window lies inside its image (elsewhere the plan is
-    refused: no image comes of it)."""
+    pairwise different; each changes with its own flag; each changes when given the window, the matrix, the coefficients, the
+    chain or the place of the view before it, of the view after it and of a view of another file — wherever that value is not its
+    own, and where that window lies inside its image (elsewhere the plan is refused: no image comes of it)."""
     for cname in cnames:
         combo = COMBOS[cname]
         for layout in layouts:
@@ -200,6 +275,10 @@ def assert_expectations_tell_views_apart(call: ViewCall, cnames, layouts):
                         assert differ(want[v.k], expect(call, v, cname, layout, matrix=matrix_of(call, o, combo))), (cname, layout, v.k, "matrix of", o.k)
                     if combo.get("places"):
                         assert differ(want[v.k], expect(call, v, cname, layout, place=place_of(o))), (cname, layout, v.k, "place of", o.k)
+                    if combo.get("colour") and chain_of(o) != chain_of(v):
+                        assert differ(want[v.k], expect(call, v, cname, layout, chain=chain_of(o))), (cname, layout, v.k, "chain of", o.k)
+                    if combo.get("perspective") and coeffs_of(call, o, combo) != coeffs_of(call, v, combo):
+                        assert differ(want[v.k], expect(call, v, cname, layout, coeffs=coeffs_of(call, o, combo))), (cname, layout, v.k, "coefficients of", o.k)
 
 
 def assert_the_call_is_interleaved(call: ViewCall):
@@ -219,6 +298,25 @@ def assert_the_call_is_interleaved(call: ViewCall):
             assert all(m is None for m, v in zip(mats, call.views) if v.gi == UNTRANSFORMED)
         if combo.get("affine") == "nearest":
             assert sum(m is not None and m[1] == 0 and m[3] == 0 for m in mats) >= 5
+        cs = [coeffs_of(call, v, combo) for v in call.views]
+        if combo.get("perspective"):
+            assert sum(c is None for c in cs) > sum(v.gi == UNTRANSFORMED for v in call.views), "no view of a transformed file without coefficients"
+            assert len({c for c in cs if c is not None}) == sum(c is not None for c in cs) >= 20
+            assert all(c is None for c, v in zip(cs, call.views) if v.gi == UNTRANSFORMED)
+            assert all(mats[k] is None for k in range(len(mats)))
+        else:
+            assert all(c is None for c in cs)
+    from tools import colour_model
+    chains = [chain_of(v) for v in call.views]
+    real = [c for c in chains if c is not None]
+    assert all(c is None for c, v in zip(chains, call.views) if v.gi == UNTRANSFORMED)
+    assert len(chains) - len(real) > sum(v.gi == UNTRANSFORMED for v in call.views), "no view of another file without a chain"
+    assert len(set(real)) == len(real) >= 20 and {len(c) for c in real} == {1, 2, 3, 4}
+    assert {op[0] for c in real for op in c} == set(colour_model.OPS), "an op kind that no chain of the call has"
+    assert sum(any(op[0] in HIST_OPS for op in c) for c in real) >= 5
+    radii = [op[1] for c in real for op in c if op[0] in BLUR_OPS]
+    assert sum(any(op[0] in BLUR_OPS for op in c) for c in real) >= 5 and len(set(radii)) == len(radii)
+    assert {c.index(("equalize",)) for c in real if ("equalize",) in c} == {0, 1}, "no op stands at two positions"
     flags = [mirror_of(v) for v in call.views]
     assert 10 <= sum(flags) <= len(flags) - 10
     assert len({place_of(v) for v in call.views}) == len(call.views)
@@ -242,12 +340,29 @@ class ViewPlanRecord:
     plan: object = None
 
 
+@dataclass
+class Bare:
+    affine: int = 0
+    perspective: int = 0
+    colour: int = 0
+
+
+def assert_bare_plans(bare: Bare, call: ViewCall, cname: str, what):
+    """the call's file without a transformed view and without a chain made a plan: the checks that such a plan carries no affine, no
+    perspective and no colour ran on something"""
+    if UNTRANSFORMED in call.gis:
+        for name in ("affine", "perspective", "colour"):
+            assert getattr(bare, name) >= 1 or not COMBOS[cname].get(name), (what, f"no plan without {name}")
+
+
 def assert_plans_hold_their_views(records: List[ViewPlanRecord], call: ViewCall, cname: str, on_device: bool, what):
     """every plan against the call: its slots are exactly the call positions of the views of its files, in view order; its views
-    name plan-local files and those views' own windows; its matrices, places and mirror flags are those views' own; a plan whose
-    views are all untransformed carries no affine.  Returns how many plans carried none though the call had matrices."""
+    name plan-local files and those views' own windows; its matrices or coefficients, chains, places and mirror flags are those
+    views' own; a plan whose views are all untransformed carries neither affine nor perspective, one whose views all have no chain
+    no colour.  Returns Bare: how many plans carried no affine though the call had matrices, no perspective though it had
+    coefficients, no colour though it had chains."""
     combo = COMBOS[cname]
-    bare = 0
+    bare = Bare()
     for r in records:
         held = files_of(r.rec, call.files)                      # positions in the caller's list, in the plan's order
         assert 0 not in held
@@ -274,7 +389,21 @@ def assert_plans_hold_their_views(records: List[ViewPlanRecord], call: ViewCall,
         mats = [matrix_of(call, v, combo) for v in mine]
         if all(m is None for m in mats):
             assert kw.get("affine") is None, (what, "a plan without a transformed view carries affine")
-            bare += bool(combo.get("affine"))
+            bare.affine += bool(combo.get("affine"))
         else:
             assert list(kw["affine"][0]) == mats and kw["affine"][1] == combo["affine"] and tuple(kw["affine"][2]) == AFFINE_FILL, what
+        cs = [coeffs_of(call, v, combo) for v in mine]
+        if all(c is None for c in cs):
+            assert kw.get("perspective") is None, (what, "a plan without a transformed view carries perspective")
+            bare.perspective += bool(combo.get("perspective"))
+        else:
+            fill = AFFINE_FILL[:1] if combo.get("mode") == "L" else AFFINE_FILL
+            assert kw.get("affine") is None, (what, "a plan of a perspective call carries affine")
+            assert list(kw["perspective"][0]) == cs and kw["perspective"][1] == combo["perspective"] and tuple(kw["perspective"][2]) == fill, what
+        chains = [chain_of(v) if combo.get("colour") else None for v in mine]
+        if all(c is None for c in chains):
+            assert kw.get("colour") is None, (what, "a plan whose views all have no chain carries colour")
+            bare.colour += bool(combo.get("colour"))
+        else:
+            assert [tuple(c) if c is not None else None for c in kw["colour"]] == chains, (what, kw["colour"], chains)
     return bare
