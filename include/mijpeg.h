@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MJ_VERSION 1
+#define MJ_VERSION 2
 
 /* API results */
 #define MJ_OK               0
@@ -191,11 +191,11 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  * components, at its own size, packed image after image — and every field whose value is its DEFAULT (named with the field)
  * gives exactly the plan of the request without it: the library turns such a field into its absence before anything is made,
  * so the same code makes the plan and the same kernels run it.  All arrays are host memory with batch->n_images entries (in a
- * request with views, the per-output ones — slots, output->mirror, places — with n_views), read during the call only.
+ * request with views, the per-output ones — slots, output->mirror, places, affine, perspective, colour — with n_views), read during the call only.
  *
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
  * affine transform -> window -> resize with the filter (to the place's size, onto the canvas) -> colour operations
- * (MJ_MODE_COLOUR_OPS, below the request) -> mirror -> the output's element type.  In Pillow's terms the result is
+ * (the `colour` field) -> mirror -> the output's element type.  In Pillow's terms the result is
  * exif_transpose(img.convert(mode))[.transform(img.size, AFFINE or PERSPECTIVE, a, resample, fillcolor)].crop(window).resize(size, filter) —
  * with reducing_gap, Pillow's argument of that name to that resize.
  *
@@ -243,16 +243,33 @@ typedef struct {
 #define MJ_AFFINE_NEAREST  1
 #define MJ_AFFINE_BILINEAR 2
 #define MJ_AFFINE_BICUBIC  3
-/* mj_plan_request.affine's value: the resample filter MJ_AFFINE_* and the fill byte of output components 0, 1, 2 */
-#define MJ_AFFINE_FIELD(filter, f0, f1, f2) ((uint32_t)(filter) | (uint32_t)(f0) << 8 | (uint32_t)(f1) << 16 | (uint32_t)(f2) << 24)
-/* One output's perspective transform (mj_plan_request.affine with MJ_AFFINE_PERSPECTIVE): the eight coefficients map OUTPUT pixel
+/* One output's perspective transform (mj_plan_request.perspective): the eight coefficients map OUTPUT pixel
  * centres to source coordinates, as the `data` of Pillow's Image.transform(size, Image.PERSPECTIVE, data) and torchvision's
  * _get_perspective_coeffs do.  All eight 0: no transform. */
 typedef struct {
     double a[8];
 } mj_perspective;
-/* or-ed into the filter of MJ_AFFINE_FIELD: the transform is a perspective one (mj_plan_perspective_request, below) */
-#define MJ_AFFINE_PERSPECTIVE 0x10
+/* One output's colour operations (mj_plan_request.colour) */
+#define MJ_COLOUR_MAX_OPS 4
+#define MJ_COLOUR_BRIGHTNESS   1
+#define MJ_COLOUR_COLOR        2
+#define MJ_COLOUR_CONTRAST     3
+#define MJ_COLOUR_SHARPNESS    4
+#define MJ_COLOUR_POSTERIZE    5
+#define MJ_COLOUR_SOLARIZE     6
+#define MJ_COLOUR_AUTOCONTRAST 7
+#define MJ_COLOUR_EQUALIZE     8
+#define MJ_COLOUR_INVERT       9
+#define MJ_COLOUR_GAUSSIAN_BLUR 10
+#define MJ_COLOUR_BOX_BLUR     11
+typedef struct {
+    int32_t kind;               /* MJ_COLOUR_* */
+    float value;                /* the factor, bits, threshold or radius; ignored by autocontrast, equalize and invert */
+} mj_colour_op;
+typedef struct {
+    int32_t n;                  /* 0..MJ_COLOUR_MAX_OPS ops, applied in order */
+    mj_colour_op op[MJ_COLOUR_MAX_OPS];
+} mj_colour_chain;
 typedef struct {
     /* Region of interest.  DEFAULT NULL: whole images.  Else the output for image i is the window rois[i] of the image — x along
      * image_width, y along image_height — and nothing else.  Window i in the plan's layout:
@@ -316,9 +333,9 @@ typedef struct {
      * pixel's taps do not fit a workgroup's LDS, or more output tiles than one launch takes (about 6.8e10: split the batch). */
     int32_t out_width, out_height;
     /* Affine transform — rotate, shear, translate, scale — of the whole oriented image, in front of the window and the resize
-     * (tools/affine_model.py).  DEFAULT 0 — also every matrix all zero: no transform.  Else MJ_AFFINE_FIELD(filter, fill...), with a
-     * size, and the request is the `request` member of a mj_plan_affine_request — declared below —, whose `affine` holds one
-     * mj_affine per OUTPUT (n_views entries in a request with views, else n_images): output k is, bit for bit,
+     * (tools/affine_model.py).  DEFAULT NULL — also every matrix all zero: no transform.  Else, with a size, `affine` holds one
+     * mj_affine per OUTPUT (n_views entries in a request with views, else n_images), transform_filter is the resample filter
+     * MJ_AFFINE_* and transform_fill (the request's last member) the fill byte of output components 0, 1, 2: output k is, bit for bit,
      *   exif_transpose(img.convert(mode)).transform(img.size, Image.AFFINE, affine[k].a, resample, fillcolor=fill)
      *       .crop(window_k).resize(target_k, filter)
      * on the canvas, mirrored if mirror[k], through the output table.  The transformed image has the oriented image's size
@@ -339,23 +356,48 @@ typedef struct {
      * ONLY its window of the transformed image — evaluated at the window's absolute coordinates —, densely, in the output's
      * components, into a second plan-owned buffer the resize launch reads as upright images.  Orientation costs no pass (the
      * kernel maps oriented to stored coordinates where it fetches); MJ_MODE_L converts every fetched tap before interpolating.
-     * MJ_ERR_INVALID, naming the output: set without a size ("affine needs a size"); a filter that is none of MJ_AFFINE_*; a NULL
-     * array; a matrix entry that is not finite; an image with a side of 32768 or more; a matrix under which a corner pixel of the
+     * MJ_ERR_INVALID, naming the output: set without a size ("affine needs a size"); a transform_filter that is none of
+     * MJ_AFFINE_*; a matrix entry that is not finite; an image with a side of 32768 or more; a matrix under which a corner pixel of the
      * output has a source coordinate of magnitude 32768 or more (Pillow leaves its defined arithmetic there), and, under
      * MJ_AFFINE_NEAREST, the same for the corner values Pillow's check_fixed tests; together with reducing_gap ("not yet": the
      * reduce would have to read the new buffer).  Left for later as well: expand=True, use without a size.
-     * With MJ_AFFINE_PERSPECTIVE or-ed into the filter the transform is a perspective one, with coefficients and rules of its own:
-     * see mj_plan_perspective_request below.
-     * The field lies in the four bytes between out_height and slots that were padding, as n_views and reducing_gap do: the
-     * request keeps its size and every other field its offset. */
-    uint32_t affine;
+     * transform_filter and transform_fill serve whichever of `affine` and `perspective` is set: either of them set while both
+     * arrays are NULL is MJ_ERR_INVALID, and so are both arrays in one request ("affine and perspective do not go together").
+     * A perspective transform has coefficients and rules of its own: see `perspective` below. */
+    int32_t transform_filter;
+    const mj_affine *affine;
+    /* Perspective transform.  DEFAULT NULL — also every entry all zero: no transform.  Else, with a size, `perspective` holds one
+     * entry per OUTPUT (n_views entries in a request with views, else n_images), with transform_filter and transform_fill as under
+     * `affine`.  Everything mj_plan_request.affine says of its place in the order of
+     * operations, of the plan (the PLAIN plan of its images; rois become per-output records), of the one more launch (csrc/affine.hip:
+     * k_perspective, the affine launch's geometry), of the second plan-owned buffer, of orientation and MJ_MODE_L holds here: output k
+     * is, bit for bit,
+     *   exif_transpose(img.convert(mode)).transform(img.size, Image.PERSPECTIVE, perspective[k].a, resample, fillcolor=fill)
+     *       .crop(window_k).resize(target_k, filter)
+     * and an output whose coefficients are all zero is the output of the request without the field; where ALL are, the request is that
+     * request (mj_debug_normalise_request clears the field).  Pillow's rules (Geometry.c: perspective_transform,
+     * ImagingGenericTransform), restated in tools/perspective_model.py — (X, Y): a pixel of the transformed image in ABSOLUTE
+     * coordinates (a window is the transform evaluated at the window's coordinates); w x h: the oriented image; every double
+     * operation rounded on its own, in this order:
+     *   xc = X + 0.5, yc = Y + 0.5;  d = a6 xc + a7 yc + 1;  xin = (a0 xc + a1 yc + a2) / d;  yin = (a3 xc + a4 yc + a5) / d
+     *   the divisions are IEEE double divisions.  The pixel is INSIDE iff xin >= 0 && xin < w && yin >= 0 && yin < h — NaN and +-inf
+     *   are outside —, and an outside pixel is fill
+     *   MJ_AFFINE_NEAREST    source pixel ((int)xin, (int)yin): no 0.5 shift, no fixed point, no tables
+     *   MJ_AFFINE_BILINEAR / MJ_AFFINE_BICUBIC   the 2 x 2 / 4 x 4 taps around (xin - 0.5, yin - 0.5) exactly as under mj_plan_request.affine
+     * The pole — the line d = 0 — may cross the frame: coordinates near it are huge or infinite, hence outside, hence fill, and beyond
+     * it the source is sampled where the formula says.  0 / 0 gives NaN, which Pillow's C converts to an int (undefined); here that
+     * pixel is fill.  No double is converted to an int before it is known to be inside, so NO coefficient magnitude is refused.
+     * MJ_ERR_INVALID, naming the output: set without a size ("perspective needs a size"); a transform_filter that is none of
+     * MJ_AFFINE_*; a coefficient that is not finite; an image with a side of 32768 or more; together with reducing_gap ("not yet").
+     * An affine and a perspective transform in one request are not offered.  Left for later as well: expand=True, use without a
+     * size. */
+    const mj_perspective *perspective;
     /* DEFAULT NULL: image k goes to slot k, the array has n_images slots, and n_slots is ignored.  Else image k goes to slot
      * slots[k] < n_slots — several plans can fill one array this way (files of several kinds are one plan per kind); slots the
      * plan does not name are not touched.  MJ_ERR_INVALID: a slot outside n_slots. */
     const int32_t *slots; int32_t n_slots;
     /* Views: several sized outputs per image from one decode (tools/views_model.py).  DEFAULT 0 — also n_views == n_images with
-     * views[k] = {k, whole} for every k: one output per image.  Else, with a size, the request is the `request` member of a
-     * mj_plan_views_request — declared below —, whose `views` holds n_views entries: the plan has n_views outputs and output k is the window
+     * views[k] = {k, whole} for every k: one output per image.  Else, with a size, `views` holds n_views entries: the plan has n_views outputs and output k is the window
      * views[k].window of image views[k].image — byte for byte output 0 of the plan of that ONE image with rois = {the window}, the
      * k-th entry of every per-output field and every other field as given: exif_transpose(img.convert(mode)).crop(window)
      * .resize(target_k, filter[, reducing_gap]) on the canvas, mirrored if mirror[k], through the output table.  Taps stop at the
@@ -370,11 +412,8 @@ typedef struct {
      * placed plan with views never derives windows.  mj_plan_info.rgb_bytes / total_pixels count n_slots outputs;
      * mj_debug_reduce_shape's index is the view.
      * MJ_ERR_INVALID: views without a size ("views needs a size"); views together with rois; n_views < 0 or a NULL `views`; an image
-     * outside the batch; an empty window or one not inside its oriented image (naming the view); an image that no view names.
-     * The field is an int in the four bytes between n_slots and output that were padding, as reducing_gap is behind filter: the
-     * request keeps its size and every other field its offset, so callers built against the request without it — who zero it — ask
-     * for what they asked, and the array's pointer lies behind `fill`, in the structure that encloses the request. */
-    int32_t n_views;
+     * outside the batch; an empty window or one not inside its oriented image (naming the view); an image that no view names. */
+    int32_t n_views; const mj_view *views;
     /* Model-ready output.  DEFAULT NULL, or {MJ_DTYPE_U8, 0, .., NULL}: the resized bytes.  Else the dense array holds what a
      * model takes — elements of `dtype`, normalised, some images mirrored:
      *   dtype      MJ_DTYPE_U8: the resized byte itself.  MJ_DTYPE_F32: for a resized byte v of component c, torchvision's
@@ -426,8 +465,7 @@ typedef struct {
      * taller than wide is not reproduced (nor is it without the field).
      * MJ_ERR_INVALID: a value that is not 0 and not a finite number >= 1.0 (checked with filter / mode / orientations / output,
      * before the context is looked at); set without a size.  MJ_ERR_UNSUPPORTED, naming the image: a cell of more than 65536 pixels.
-     * The field is a float in the four bytes between filter and places that were padding: the request keeps its size and every other
-     * field its offset, so callers built against the request without it — who zero it — ask for what they asked.  A gap a float does
+     * The field is a float.  A gap a float does
      * not hold exactly would give other factors than Pillow's double does, so the Python layer refuses such a gap (1.0, 1.5, 2.0,
      * 3.0 and every other multiple of 2^-20 up to 16 are exact). */
     float reducing_gap;
@@ -448,138 +486,70 @@ typedef struct {
     const mj_place *places;
     /* With places.  DEFAULT NULL: zeros.  Else one byte per OUTPUT component (fill[0] alone for one component). */
     const uint8_t *fill;
-} mj_plan_request;
-/* A request with views (request.n_views != 0): mj_plan_create_with and mj_debug_normalise_request are given &r.request and read
- * r.views[0 .. request.n_views).  Zeroed, it is the zeroed request. */
-typedef struct {
-    mj_plan_request request;
-    const mj_view *views;
-} mj_plan_views_request;
-/* A request with an affine transform (request.affine != 0): its head is a mj_plan_views_request — `views` is read where
- * request.n_views != 0 —, and `affine` holds one matrix per output.  Zeroed, it is the zeroed request. */
-typedef struct {
-    mj_plan_request request;
-    const mj_view *views;
-    const mj_affine *affine;
-} mj_plan_affine_request;
-/* Colour operations on the finished canvas (mj_plan_request.mode with MJ_MODE_COLOUR_OPS or-ed in; tools/colour_model.py): what
- * one call of Pillow's ImageEnhance.* / ImageOps.* does to the bytes, bit for bit — the colour half of ColorJitter, RandAugment,
- * AutoAugment and TrivialAugment.  The flag is one more bit of `mode` (the mode itself is the low byte; a caller who never sets the
- * bit is unaffected), it needs a size, and the request is then the `head.request` of a mj_plan_colour_request — declared below —
- * whose `colour` holds one chain per OUTPUT (n_views entries in a request with views, else n_images).  The order of operations
- * becomes decode -> mode -> orientation -> affine -> window -> resize / place / fill -> COLOUR OPS -> mirror -> element type:
- *   let C_k be the uint8 canvas of output k that the same request gives without the flag, without output->mirror and with
- *   MJ_DTYPE_U8, fill pixels included.  Output k is chain k applied to C_k as a Pillow image of the output's components ("RGB" or
- *   "L"), op after op, then mirrored if mirror[k] and passed through the output table — in all four layouts.
- * An output whose chain is empty (n == 0) is the output of the request without the flag; a request whose chains are ALL empty is
- * that request (mj_debug_normalise_request clears the flag), with no extra launch and no extra buffer.  The rules, restated
- * (v: a byte of the canvas; every float32 / double operation rounded on its own):
- *   blend(d, v, f)         Image.blend: alpha = (float)f, t = (float)d + alpha * (float)(v - d) with v - d an int; for 0 <= alpha <= 1
- *                          the byte (uint8)t, else 0 where t <= 0, 255 where t >= 255, else (uint8)t
- *   MJ_COLOUR_BRIGHTNESS   blend(0, v, value)
- *   MJ_COLOUR_COLOR        blend(L, v, value) in all three components, L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the pixel;
- *                          the identity on a one-component output
- *   MJ_COLOUR_CONTRAST     blend(m, v, value) in every component, m = (int)(sum of i * hist_L[i] / n + 0.5) in doubles, hist_L the
- *                          histogram of the canvas's L (of the canvas itself for one component), n its pixels
- *   MJ_COLOUR_SHARPNESS    blend(s, v, value), s = ImageFilter.SMOOTH per component: k = (float)(e / 13.0) for e in (1,1,1, 1,5,1,
- *                          1,1,1); ss = 0.5f, then ss += row(y + 1), row(y), row(y - 1) with row(r) = (p[x-1] k0 + p[x] k1) + p[x+1] k2
- *                          of that row's kernel entries; s = 0 where ss <= 0, 255 where ss >= 255, else (uint8)ss; pixels of the
- *                          first and last row and column are copied (a canvas with a side below 3 is unchanged)
- *   MJ_COLOUR_POSTERIZE    v & ~(2^(8 - value) - 1), value 1..8
- *   MJ_COLOUR_SOLARIZE     v where v < t, else 255 - v; t = min(max(ceil(value), 0), 256)
- *   MJ_COLOUR_INVERT       255 - v
- *   MJ_COLOUR_AUTOCONTRAST per component (cutoff 0, no mask): lo, hi the first and last non-empty bins; hi <= lo: the identity; else
- *                          scale = 255.0 / (hi - lo), offset = -lo * scale, v -> clip((int)(v * scale + offset), 0, 255) in doubles
- *   MJ_COLOUR_EQUALIZE     per component with histogram h (no mask): one non-empty bin, or step = (pixels - the last non-empty bin's
- *                          count) / 255 == 0: the identity; else n = step / 2 and for i = 0..255: i -> min(255, n / step), n += h[i]
- *   pass(fr) along an axis of length n, per component (Pillow's BoxBlur.c; fr a float32 box radius): r = (int)fr, ww = (uint32)((float)
- *                          (1 << 24) / (fr * 2 + 1)), fw = ((1 << 24) - (2 r + 1) ww) / 2, and out[x] = (ww * sum of in[clamp(x + d)],
- *                          d = -r..r, + fw * (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + (1 << 23)) >> 24 with clamp to 0 .. n - 1,
- *                          in 32-bit unsigned arithmetic.  Every pass stores bytes, and the next pass reads those bytes.  Width and
- *                          height are the image's axes in every layout; the width passes come first
- *   MJ_COLOUR_BOX_BLUR     im.filter(ImageFilter.BoxBlur(value)): pass((float)value) along the width, then along the height
- *   MJ_COLOUR_GAUSSIAN_BLUR  im.filter(ImageFilter.GaussianBlur(value)): three passes along the width, then three along the height,
- *                          all with fr = l + a, in float32 but for the double square root and floor: sigma2 = value * value / 3,
- *                          L = (float)sqrt(12.0 * sigma2 + 1.0), l = (float)floor((L - 1.0) / 2.0), a = (2 l + 1) * (l (l + 1) - 3 sigma2),
- *                          a = a / (6 * (sigma2 - (l + 1) (l + 1)))
- *                          Both take one radius 0 <= value <= 1024 (0: the identity; Pillow's per-axis radii are not offered); the
- *                          fill pixels take part as in every op, and the blur commutes with the mirror
- * The launches (csrc/colour.hip): the plan's resize launch runs exactly as that of the MJ_DTYPE_U8, unmirrored, identity-slot
- * request would, into a plan-owned canvas buffer in the plan's layout.  Then, for every step s of the longest chain: a histogram
- * launch over the outputs whose op s is contrast, autocontrast or equalize (32-bit bins: LDS atomics, merged into a zeroed
- * per-output array); a launch of one wavefront per output that builds the 3 x 256 byte table of every table-shaped op, from the
- * statistics where it has some — they never leave the device, nothing synchronises —; and one launch that applies step s to
- * every output (a table look-up, color, sharpness, or a copy where the chain has ended) from one canvas into a second, the last
- * step into the caller's array at the output's slot, mirrored if flagged, through the output table.  The outputs whose op s is a
- * blur are left out by that launch (which is not made where every output's op s is a blur) and taken by one more: a workgroup holds one component plane of one output in LDS, runs all
- * the passes there and stores the last one as above; a plan whose canvas is too large for that (two planes of ow rounded up to
- * four, times oh, bytes: more than 160 KB) runs one launch per pass through a third plan-owned canvas instead (option MJ_BLUR
- * forces that route).  r, ww and fw are computed on the host, once per op.  mj_plan_time_resize times
- * these launches too.  mj_host_colour_ops is the host twin.
- * MJ_ERR_INVALID, naming the output: the flag without a size ("colour_ops needs a size"), a NULL array, n outside 0..4, a kind that
- * is none of MJ_COLOUR_*, a value that is not finite, posterize bits that are not one of 1..8, a blur radius outside 0..1024
- * (Pillow takes a negative Gaussian radius; this library refuses it).  Not offered yet: hue (Pillow's HSV
- * round trip), autocontrast's cutoffs and masks, more than MJ_COLOUR_MAX_OPS ops. */
-#define MJ_MODE_COLOUR_OPS 0x100
-#define MJ_COLOUR_MAX_OPS 4
-#define MJ_COLOUR_BRIGHTNESS   1
-#define MJ_COLOUR_COLOR        2
-#define MJ_COLOUR_CONTRAST     3
-#define MJ_COLOUR_SHARPNESS    4
-#define MJ_COLOUR_POSTERIZE    5
-#define MJ_COLOUR_SOLARIZE     6
-#define MJ_COLOUR_AUTOCONTRAST 7
-#define MJ_COLOUR_EQUALIZE     8
-#define MJ_COLOUR_INVERT       9
-#define MJ_COLOUR_GAUSSIAN_BLUR 10
-#define MJ_COLOUR_BOX_BLUR     11
-typedef struct {
-    int32_t kind;               /* MJ_COLOUR_* */
-    float value;                /* the factor, bits, threshold or radius; ignored by autocontrast, equalize and invert */
-} mj_colour_op;
-typedef struct {
-    int32_t n;                  /* 0..MJ_COLOUR_MAX_OPS ops, applied in order */
-    mj_colour_op op[MJ_COLOUR_MAX_OPS];
-} mj_colour_chain;
-/* A request with colour operations (request.mode & MJ_MODE_COLOUR_OPS): its head is a mj_plan_affine_request — `views` and
- * `affine` are read where their fields say so —, and `colour` holds one chain per output.  Zeroed, it is the zeroed request. */
-typedef struct {
-    mj_plan_affine_request head;
+    /* Colour operations on the finished canvas (tools/colour_model.py): what
+     * one call of Pillow's ImageEnhance.* / ImageOps.* does to the bytes, bit for bit — the colour half of ColorJitter, RandAugment,
+     * AutoAugment and TrivialAugment.  DEFAULT NULL — also every chain empty: none.  Else, with a size, `colour` holds one chain
+     * per OUTPUT (n_views entries in a request with views, else n_images).  The order of operations
+     * becomes decode -> mode -> orientation -> affine -> window -> resize / place / fill -> COLOUR OPS -> mirror -> element type:
+     *   let C_k be the uint8 canvas of output k that the same request gives without the field, without output->mirror and with
+     *   MJ_DTYPE_U8, fill pixels included.  Output k is chain k applied to C_k as a Pillow image of the output's components ("RGB" or
+     *   "L"), op after op, then mirrored if mirror[k] and passed through the output table — in all four layouts.
+     * An output whose chain is empty (n == 0) is the output of the request without the field; a request whose chains are ALL empty is
+     * that request (mj_debug_normalise_request clears the field), with no extra launch and no extra buffer.  The rules, restated
+     * (v: a byte of the canvas; every float32 / double operation rounded on its own):
+     *   blend(d, v, f)         Image.blend: alpha = (float)f, t = (float)d + alpha * (float)(v - d) with v - d an int; for 0 <= alpha <= 1
+     *                          the byte (uint8)t, else 0 where t <= 0, 255 where t >= 255, else (uint8)t
+     *   MJ_COLOUR_BRIGHTNESS   blend(0, v, value)
+     *   MJ_COLOUR_COLOR        blend(L, v, value) in all three components, L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of the pixel;
+     *                          the identity on a one-component output
+     *   MJ_COLOUR_CONTRAST     blend(m, v, value) in every component, m = (int)(sum of i * hist_L[i] / n + 0.5) in doubles, hist_L the
+     *                          histogram of the canvas's L (of the canvas itself for one component), n its pixels
+     *   MJ_COLOUR_SHARPNESS    blend(s, v, value), s = ImageFilter.SMOOTH per component: k = (float)(e / 13.0) for e in (1,1,1, 1,5,1,
+     *                          1,1,1); ss = 0.5f, then ss += row(y + 1), row(y), row(y - 1) with row(r) = (p[x-1] k0 + p[x] k1) + p[x+1] k2
+     *                          of that row's kernel entries; s = 0 where ss <= 0, 255 where ss >= 255, else (uint8)ss; pixels of the
+     *                          first and last row and column are copied (a canvas with a side below 3 is unchanged)
+     *   MJ_COLOUR_POSTERIZE    v & ~(2^(8 - value) - 1), value 1..8
+     *   MJ_COLOUR_SOLARIZE     v where v < t, else 255 - v; t = min(max(ceil(value), 0), 256)
+     *   MJ_COLOUR_INVERT       255 - v
+     *   MJ_COLOUR_AUTOCONTRAST per component (cutoff 0, no mask): lo, hi the first and last non-empty bins; hi <= lo: the identity; else
+     *                          scale = 255.0 / (hi - lo), offset = -lo * scale, v -> clip((int)(v * scale + offset), 0, 255) in doubles
+     *   MJ_COLOUR_EQUALIZE     per component with histogram h (no mask): one non-empty bin, or step = (pixels - the last non-empty bin's
+     *                          count) / 255 == 0: the identity; else n = step / 2 and for i = 0..255: i -> min(255, n / step), n += h[i]
+     *   pass(fr) along an axis of length n, per component (Pillow's BoxBlur.c; fr a float32 box radius): r = (int)fr, ww = (uint32)((float)
+     *                          (1 << 24) / (fr * 2 + 1)), fw = ((1 << 24) - (2 r + 1) ww) / 2, and out[x] = (ww * sum of in[clamp(x + d)],
+     *                          d = -r..r, + fw * (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + (1 << 23)) >> 24 with clamp to 0 .. n - 1,
+     *                          in 32-bit unsigned arithmetic.  Every pass stores bytes, and the next pass reads those bytes.  Width and
+     *                          height are the image's axes in every layout; the width passes come first
+     *   MJ_COLOUR_BOX_BLUR     im.filter(ImageFilter.BoxBlur(value)): pass((float)value) along the width, then along the height
+     *   MJ_COLOUR_GAUSSIAN_BLUR  im.filter(ImageFilter.GaussianBlur(value)): three passes along the width, then three along the height,
+     *                          all with fr = l + a, in float32 but for the double square root and floor: sigma2 = value * value / 3,
+     *                          L = (float)sqrt(12.0 * sigma2 + 1.0), l = (float)floor((L - 1.0) / 2.0), a = (2 l + 1) * (l (l + 1) - 3 sigma2),
+     *                          a = a / (6 * (sigma2 - (l + 1) (l + 1)))
+     *                          Both take one radius 0 <= value <= 1024 (0: the identity; Pillow's per-axis radii are not offered); the
+     *                          fill pixels take part as in every op, and the blur commutes with the mirror
+     * The launches (csrc/colour.hip): the plan's resize launch runs exactly as that of the MJ_DTYPE_U8, unmirrored, identity-slot
+     * request would, into a plan-owned canvas buffer in the plan's layout.  Then, for every step s of the longest chain: a histogram
+     * launch over the outputs whose op s is contrast, autocontrast or equalize (32-bit bins: LDS atomics, merged into a zeroed
+     * per-output array); a launch of one wavefront per output that builds the 3 x 256 byte table of every table-shaped op, from the
+     * statistics where it has some — they never leave the device, nothing synchronises —; and one launch that applies step s to
+     * every output (a table look-up, color, sharpness, or a copy where the chain has ended) from one canvas into a second, the last
+     * step into the caller's array at the output's slot, mirrored if flagged, through the output table.  The outputs whose op s is a
+     * blur are left out by that launch (which is not made where every output's op s is a blur) and taken by one more: a workgroup holds one component plane of one output in LDS, runs all
+     * the passes there and stores the last one as above; a plan whose canvas is too large for that (two planes of ow rounded up to
+     * four, times oh, bytes: more than 160 KB) runs one launch per pass through a third plan-owned canvas instead (option MJ_BLUR
+     * forces that route).  r, ww and fw are computed on the host, once per op.  mj_plan_time_resize times
+     * these launches too.  mj_host_colour_ops is the host twin.
+     * MJ_ERR_INVALID, naming the output: the field without a size ("colour_ops needs a size"), n outside 0..4, a kind that
+     * is none of MJ_COLOUR_*, a value that is not finite, posterize bits that are not one of 1..8, a blur radius outside 0..1024
+     * (Pillow takes a negative Gaussian radius; this library refuses it).  Not offered yet: hue (Pillow's HSV
+     * round trip), autocontrast's cutoffs and masks, more than MJ_COLOUR_MAX_OPS ops. */
     const mj_colour_chain *colour;
-} mj_plan_colour_request;
-/* A request with a perspective transform (request.affine with MJ_AFFINE_PERSPECTIVE in its filter byte, e.g.
- * MJ_AFFINE_FIELD(MJ_AFFINE_BILINEAR | MJ_AFFINE_PERSPECTIVE, fill...)): its head is a mj_plan_colour_request — `views` and `colour`
- * are read where their fields say so, `head.head.affine` is NOT read —, and `perspective` holds one entry per OUTPUT (n_views
- * entries in a request with views, else n_images).  Everything mj_plan_request.affine says of its place in the order of
- * operations, of the plan (the PLAIN plan of its images; rois become per-output records), of the one more launch (csrc/affine.hip:
- * k_perspective, the affine launch's geometry), of the second plan-owned buffer, of orientation and MJ_MODE_L holds here: output k
- * is, bit for bit,
- *   exif_transpose(img.convert(mode)).transform(img.size, Image.PERSPECTIVE, perspective[k].a, resample, fillcolor=fill)
- *       .crop(window_k).resize(target_k, filter)
- * and an output whose coefficients are all zero is the output of the request without the field; where ALL are, the request is that
- * request (mj_debug_normalise_request clears the field).  Pillow's rules (Geometry.c: perspective_transform,
- * ImagingGenericTransform), restated in tools/perspective_model.py — (X, Y): a pixel of the transformed image in ABSOLUTE
- * coordinates (a window is the transform evaluated at the window's coordinates); w x h: the oriented image; every double
- * operation rounded on its own, in this order:
- *   xc = X + 0.5, yc = Y + 0.5;  d = a6 xc + a7 yc + 1;  xin = (a0 xc + a1 yc + a2) / d;  yin = (a3 xc + a4 yc + a5) / d
- *   the divisions are IEEE double divisions.  The pixel is INSIDE iff xin >= 0 && xin < w && yin >= 0 && yin < h — NaN and +-inf
- *   are outside —, and an outside pixel is fill
- *   MJ_AFFINE_NEAREST    source pixel ((int)xin, (int)yin): no 0.5 shift, no fixed point, no tables
- *   MJ_AFFINE_BILINEAR / MJ_AFFINE_BICUBIC   the 2 x 2 / 4 x 4 taps around (xin - 0.5, yin - 0.5) exactly as under mj_plan_request.affine
- * The pole — the line d = 0 — may cross the frame: coordinates near it are huge or infinite, hence outside, hence fill, and beyond
- * it the source is sampled where the formula says.  0 / 0 gives NaN, which Pillow's C converts to an int (undefined); here that
- * pixel is fill.  No double is converted to an int before it is known to be inside, so NO coefficient magnitude is refused.
- * MJ_ERR_INVALID, naming the output: set without a size ("perspective needs a size"); a filter byte that is none of MJ_AFFINE_*
- * with or without MJ_AFFINE_PERSPECTIVE; a NULL array; a coefficient that is not finite; an image with a side of 32768 or more;
- * together with reducing_gap ("not yet").  An affine and a perspective transform in one request are not offered (the field
- * names one array).  Left for later as well: expand=True, use without a size.
- * No struct that existed changed: the new request wraps the one before it, as every one so far did. */
-typedef struct {
-    mj_plan_colour_request head;
-    const mj_perspective *perspective;
-} mj_plan_perspective_request;
+    /* The fill bytes of `affine` / `perspective`, beside transform_filter (specified with `affine`; the member lies here, last, so that
+     * the request has no hole).  DEFAULT zeros.  One byte per OUTPUT component; set without either array: MJ_ERR_INVALID. */
+    uint8_t transform_fill[3];
+} mj_plan_request;
 /* The host twin of the colour launches (no context): src is a row-major w x h image of ncomp (1 or 3) interleaved components, out
- * receives the chain applied to it (w * h * ncomp bytes; out may be src).  MJ_ERR_INVALID: what the flag refuses of a chain, a size
+ * receives the chain applied to it (w * h * ncomp bytes; out may be src).  MJ_ERR_INVALID: what mj_plan_request.colour refuses of a chain, a size
  * below 1, ncomp neither 1 nor 3, NULL. */
 int mj_host_colour_ops(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, const mj_colour_chain *chain, uint8_t *out);
 /* request NULL: a zeroed request. */
@@ -722,7 +692,8 @@ int mj_debug_reduce_shape(const mj_plan *plan, int32_t image, int32_t out[7]);
 int mj_debug_reduce_launch(const mj_plan *plan, int32_t out[5]);
 
 /* Test hook (host only, no context): *normal = the request as plan creation sees it after its checks — every field that names its
- * default turned into its absence (pointers are the caller's) — or the code of the first fault that needs no context
+ * default turned into its absence (pointers are the caller's; where the library derived the views of a request with a transform
+ * itself, n_views is their count and views is NULL) — or the code of the first fault that needs no context
  * (mj_last_error(NULL) has the message).  request NULL: a zeroed one. */
 int mj_debug_normalise_request(const mj_batch *batch, const mj_plan_request *request, mj_plan_request *normal);
 
@@ -767,7 +738,7 @@ int mj_plan_time_resize(mj_plan *plan, int iters, uint8_t *rgb_device, float *ms
 /* A plan's affine — or perspective — launch alone (mj_plan_request.affine; after an execute): ms per launch, and the bytes it writes (it reads, at
  * most, mj_plan_time_resize's source_bytes).  MJ_ERR_INVALID: not a plan with an affine transform. */
 int mj_plan_time_affine(mj_plan *plan, int iters, float *ms, int64_t *written_bytes);
-/* The colour launches of a plan with colour operations alone (MJ_MODE_COLOUR_OPS; after an execute: they read the canvases the
+/* The colour launches of a plan with colour operations alone (mj_plan_request.colour; after an execute: they read the canvases the
  * resize launch left), `iters` times into where the latest execute wrote: ms per run of all of them — the histogram, table and
  * apply launches of every step —, and the bytes of one set of canvases (outputs x out_width x out_height x components).
  * MJ_ERR_INVALID: not a plan with colour operations, nothing executed yet. */

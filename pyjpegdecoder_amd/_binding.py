@@ -12,6 +12,7 @@ from .errors import BackendError
 
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libmijpeg.so"
+MJ_VERSION = 2      # include/mijpeg.h's: the layout of the structures below; load_library refuses a library of another version
 
 MJ_OK, MJ_ERR_INVALID, MJ_ERR_HIP, MJ_ERR_UNSUPPORTED = 0, -1, -2, -3
 MJ_ST_OK, MJ_ST_BAD_CODE, MJ_ST_OVERRUN, MJ_ST_DESYNC, MJ_ST_TAIL, MJ_ST_UNCONVERGED, MJ_ST_INTERNAL = 0, 1, 2, 3, 4, 5, 6
@@ -28,13 +29,11 @@ MJ_FILTER_BILINEAR, MJ_FILTER_BOX, MJ_FILTER_HAMMING, MJ_FILTER_BICUBIC, MJ_FILT
 # the resample filters of a decode to a fixed size by name (tools/resize_model.py: FILTERS)
 MJ_AFFINE_NEAREST, MJ_AFFINE_BILINEAR, MJ_AFFINE_BICUBIC = 1, 2, 3
 AFFINE_FILTERS = {"nearest": MJ_AFFINE_NEAREST, "bilinear": MJ_AFFINE_BILINEAR, "bicubic": MJ_AFFINE_BICUBIC}
-MJ_AFFINE_PERSPECTIVE = 0x10        # or-ed into the filter byte of mj_plan_request.affine: a perspective transform
 FILTERS = {"bilinear": MJ_FILTER_BILINEAR, "box": MJ_FILTER_BOX, "hamming": MJ_FILTER_HAMMING, "bicubic": MJ_FILTER_BICUBIC,
            "lanczos": MJ_FILTER_LANCZOS}
 
 MJ_MODE_NATIVE, MJ_MODE_L, MJ_MODE_RGB = 0, 1, 3
-# colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): the ops by name (tools/colour_model.py: OPS), MJ_COLOUR_*
-MJ_MODE_COLOUR_OPS = 0x100
+# colour operations (mj_plan_request.colour): the ops by name (tools/colour_model.py: OPS), MJ_COLOUR_*
 MJ_COLOUR_MAX_OPS = 4
 COLOUR_OPS = {"brightness": 1, "color": 2, "contrast": 3, "sharpness": 4, "posterize": 5, "solarize": 6, "autocontrast": 7,
               "equalize": 8, "invert": 9, "gaussian_blur": 10, "box_blur": 11}
@@ -125,59 +124,14 @@ class ViewC(ctypes.Structure):
     _fields_ = [("image", ctypes.c_int32), ("window", RoiC)]
 
 
-class PlanRequestC(ctypes.Structure):
-    """mj_plan_request: what a plan's output is to be; zeroed, the plain plan."""
-    _fields_ = [("rois", ctypes.POINTER(RoiC)), ("orientations", ctypes.c_void_p), ("mode", ctypes.c_int32),
-                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int32),
-                ("output", ctypes.POINTER(OutputDescC)), ("filter", ctypes.c_int32), ("places", ctypes.POINTER(PlaceC)),
-                ("fill", ctypes.c_void_p)]
-
-    # mj_plan_request.reducing_gap: a float in the four bytes between filter and places, which the fields above leave as padding —
-    # the structure keeps its size and its fields their offsets
-    @property
-    def reducing_gap(self) -> float:
-        return ctypes.c_float.from_buffer(self, type(self).filter.offset + 4).value
-
-    @reducing_gap.setter
-    def reducing_gap(self, gap: float):
-        ctypes.c_float.from_buffer(self, type(self).filter.offset + 4).value = gap
-
-    # mj_plan_request.n_views: an int in the four bytes between n_slots and output, padding likewise.  Not 0: the request is the
-    # `request` member of a PlanViewsRequestC, whose `views` holds that many entries
-    @property
-    def n_views(self) -> int:
-        return ctypes.c_int32.from_buffer(self, type(self).n_slots.offset + 4).value
-
-    @n_views.setter
-    def n_views(self, n: int):
-        ctypes.c_int32.from_buffer(self, type(self).n_slots.offset + 4).value = n
-
-
-    # mj_plan_request.affine: a word in the four bytes between out_height and slots, padding likewise — MJ_AFFINE_* in its low byte,
-    # the fill bytes above it.  Not 0: the request is the `request` member of a PlanAffineRequestC, whose `affine` holds one matrix
-    # per output
-    @property
-    def affine(self) -> int:
-        return ctypes.c_uint32.from_buffer(self, type(self).out_height.offset + 4).value
-
-    @affine.setter
-    def affine(self, word: int):
-        ctypes.c_uint32.from_buffer(self, type(self).out_height.offset + 4).value = word
-
-
-class PlanViewsRequestC(ctypes.Structure):
-    """mj_plan_views_request: a request with views — the request, and behind it the array its n_views counts."""
-    _fields_ = [("request", PlanRequestC), ("views", ctypes.POINTER(ViewC))]
-
-
 class AffineC(ctypes.Structure):
     """mj_affine: one output's matrix, output to source (all zero: no transform)."""
     _fields_ = [("a", ctypes.c_double * 6)]
 
 
-class PlanAffineRequestC(ctypes.Structure):
-    """mj_plan_affine_request: a request with an affine transform — a request with views' layout, and behind it one matrix per output."""
-    _fields_ = [("request", PlanRequestC), ("views", ctypes.POINTER(ViewC)), ("affine", ctypes.POINTER(AffineC))]
+class PerspectiveC(ctypes.Structure):
+    """mj_perspective: one output's eight coefficients, output to source (all zero: no transform)."""
+    _fields_ = [("a", ctypes.c_double * 8)]
 
 
 class ColourOpC(ctypes.Structure):
@@ -190,21 +144,15 @@ class ColourChainC(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int32), ("op", ColourOpC * MJ_COLOUR_MAX_OPS)]
 
 
-class PlanColourRequestC(ctypes.Structure):
-    """mj_plan_colour_request: a request with colour operations — a request with an affine transform's layout, and behind it one
-    chain per output."""
-    _fields_ = [("head", PlanAffineRequestC), ("colour", ctypes.POINTER(ColourChainC))]
-
-
-class PerspectiveC(ctypes.Structure):
-    """mj_perspective: one output's eight coefficients, output to source (all zero: no transform)."""
-    _fields_ = [("a", ctypes.c_double * 8)]
-
-
-class PlanPerspectiveRequestC(ctypes.Structure):
-    """mj_plan_perspective_request: a request with a perspective transform — a request with colour operations' layout, and behind
-    it one set of coefficients per output."""
-    _fields_ = [("head", PlanColourRequestC), ("perspective", ctypes.POINTER(PerspectiveC))]
+class PlanRequestC(ctypes.Structure):
+    """mj_plan_request: what a plan's output is to be; zeroed, the plain plan.  Every field of the header's struct, in its order."""
+    _fields_ = [("rois", ctypes.POINTER(RoiC)), ("orientations", ctypes.c_void_p), ("mode", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("transform_filter", ctypes.c_int32), ("affine", ctypes.POINTER(AffineC)), ("perspective", ctypes.POINTER(PerspectiveC)),
+                ("slots", ctypes.c_void_p), ("n_slots", ctypes.c_int32), ("n_views", ctypes.c_int32), ("views", ctypes.POINTER(ViewC)),
+                ("output", ctypes.POINTER(OutputDescC)), ("filter", ctypes.c_int32), ("reducing_gap", ctypes.c_float),
+                ("places", ctypes.POINTER(PlaceC)), ("fill", ctypes.c_void_p), ("colour", ctypes.POINTER(ColourChainC)),
+                ("transform_fill", ctypes.c_uint8 * 3)]
 
 
 def colour_chain(chain) -> ColourChainC:
@@ -250,6 +198,9 @@ def load_library():
         L = ctypes.CDLL(str(LIB_PATH))
     except OSError as exc:
         raise BackendError(f"cannot load {LIB_PATH}: {exc}") from exc
+    if L.mj_version() != MJ_VERSION:      # (a library of another version lays mj_plan_request out differently)
+        raise BackendError(f"{LIB_PATH} is version {L.mj_version()} of the C ABI and this binding version {MJ_VERSION}: rebuild the "
+                           f"library (`make -C pyjpegdecoder_amd/csrc`)")
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
     L.mj_create.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
     L.mj_destroy.argtypes = [vp]
@@ -635,23 +586,7 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
     if fill is not None and places is None:
         raise ValueError("fill needs places: only a placed plan has canvas elements no image covers")
     keep = {}
-    if perspective is not None:     # (the request is then the head of the structure that holds the arrays' pointers)
-        keep["perspective_request"] = top = PlanPerspectiveRequestC()
-        whole = top.head
-        ext = whole.head
-        r = ext.request
-    elif colour is not None:
-        keep["colour_request"] = whole = PlanColourRequestC()
-        ext = whole.head
-        r = ext.request
-    elif affine is not None:
-        keep["affine_request"] = ext = PlanAffineRequestC()
-        r = ext.request
-    elif views is not None:
-        keep["views_request"] = ext = PlanViewsRequestC()
-        r = ext.request
-    else:
-        r = PlanRequestC()
+    r = PlanRequestC()
     if rois is not None:
         keep["rois"] = r.rois = (RoiC * max(1, len(rois)))(*[RoiC(*(int(v) for v in w)) for w in rois])
     if orientation is not None:
@@ -675,34 +610,23 @@ def plan_request(n_images, rois=None, size=None, slots=None, output=None, orient
         fb[:len(fill)] = fill
         r.fill = fb.ctypes.data
     if views is not None:
-        keep["views"] = ext.views = (ViewC * max(1, len(views)))(*[ViewC(int(i), RoiC(*(int(v) for v in (w if w is not None else (0, 0, 0, 0)))))
-                                                                     for i, w in views])
+        keep["views"] = r.views = (ViewC * max(1, len(views)))(*[ViewC(int(i), RoiC(*(int(v) for v in (w if w is not None else (0, 0, 0, 0)))))
+                                                                 for i, w in views])
         r.n_views = len(views)
-    if affine is not None:      # ((matrices: one 6-tuple or None per output, a name of AFFINE_FILTERS or its MJ_AFFINE_*, the fill bytes))
-        matrices, name, fb = affine
-        n_out = len(views) if views is not None else n_images
-        if len(matrices) != n_out:
-            raise ValueError(f"affine: {len(matrices)} entries, not one for each of the {n_out} {'views' if views is not None else 'images'}")
-        keep["affine"] = ext.affine = (AffineC * max(1, len(matrices)))(*[AffineC((ctypes.c_double * 6)(*(m if m is not None else (0.0,) * 6)))
-                                                                          for m in matrices])
-        fb = (tuple(fb) + (0, 0, 0))[:3]
-        r.affine = (AFFINE_FILTERS[name] if isinstance(name, str) else int(name)) | fb[0] << 8 | fb[1] << 16 | fb[2] << 24
-    if perspective is not None:     # ((coefficients: one 8-tuple or None per output, the filter and the fill bytes as affine's))
-        coeffs, name, fb = perspective
-        n_out = len(views) if views is not None else n_images
-        if len(coeffs) != n_out:
-            raise ValueError(f"perspective: {len(coeffs)} entries, not one for each of the {n_out} {'views' if views is not None else 'images'}")
-        keep["perspective"] = top.perspective = (PerspectiveC * max(1, len(coeffs)))(*[PerspectiveC((ctypes.c_double * 8)(*(c if c is not None else (0.0,) * 8)))
-                                                                                       for c in coeffs])
-        fb = (tuple(fb) + (0, 0, 0))[:3]
-        r.affine = (AFFINE_FILTERS[name] if isinstance(name, str) else int(name)) | MJ_AFFINE_PERSPECTIVE | fb[0] << 8 | fb[1] << 16 | fb[2] << 24
+    # affine: (matrices: one 6-tuple or None per output, a name of AFFINE_FILTERS or its MJ_AFFINE_*, the fill bytes);
+    # perspective: (coefficients: one 8-tuple or None per output, the filter and the fill bytes as affine's)
+    for name, given, entry, width in (("affine", affine, AffineC, 6), ("perspective", perspective, PerspectiveC, 8)):
+        if given is not None:
+            entries, filter_name, fb = given
+            keep[name] = (entry * max(1, len(entries)))(*[entry((ctypes.c_double * width)(*(e if e is not None else (0.0,) * width))) for e in entries])
+            setattr(r, name, keep[name])
+            r.transform_filter = AFFINE_FILTERS[filter_name] if isinstance(filter_name, str) else int(filter_name)
+            r.transform_fill[:] = (tuple(int(v) for v in fb) + (0, 0, 0))[:3]
     if colour is not None:      # (one chain — None or a sequence of ops — per output)
-        n_out = len(views) if views is not None else n_images
-        if len(colour) != n_out:
-            raise ValueError(f"colour: {len(colour)} entries, not one for each of the {n_out} {'views' if views is not None else 'images'}")
-        keep["colour"] = whole.colour = (ColourChainC * max(1, len(colour)))(*[colour_chain(c) for c in colour])
-        r.mode |= MJ_MODE_COLOUR_OPS
-    for name, given in (("places", places), ("orientation", orientation), ("mirror", keep.get("mirror"))):
+        keep["colour"] = r.colour = (ColourChainC * max(1, len(colour)))(*[colour_chain(c) for c in colour])
+    for name, given in (("affine", affine[0] if affine is not None else None),
+                        ("perspective", perspective[0] if perspective is not None else None), ("colour", colour),
+                        ("places", places), ("orientation", orientation), ("mirror", keep.get("mirror"))):
         per_view = views is not None and name != "orientation"
         if given is not None and len(given) != (len(views) if per_view else n_images):
             raise ValueError(f"{name}: {len(given)} entries, not one for each of the {len(views) if per_view else n_images} {'views' if per_view else 'images'}")

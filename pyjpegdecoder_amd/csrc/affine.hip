@@ -20,7 +20,7 @@
 // rotated tile's footprint is a rotated rectangle); the finished bytes of a row go through LDS so that consecutive lanes store
 // consecutive runs of 4 bytes (at any alignment) and never a byte outside the row.
 //
-// Perspective transform (MJ_AFFINE_PERSPECTIVE in the field's filter byte): Pillow's Image.transform(img.size, Image.PERSPECTIVE, c,
+// Perspective transform (mj_plan_request.perspective): Pillow's Image.transform(img.size, Image.PERSPECTIVE, c,
 // resample, fillcolor=fill) in the same place, with the same launch geometry, fetch and 2 x 2 / 4 x 4 taps (k_perspective; records
 // of its own, DevPerspectiveImage).  The coordinates are two IEEE double divisions per pixel (tools/perspective_model.py), NEAREST
 // truncates them — no fixed point, no tables —, and a pixel whose coordinates are not inside the image, NaN and +-inf included, is

@@ -1,4 +1,4 @@
-// Colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): what one call of Pillow's ImageEnhance.* / ImageOps.* does to
+// Colour operations (mj_plan_request.colour): what one call of Pillow's ImageEnhance.* / ImageOps.* does to
 // the bytes of the finished canvas, between the resize launch and the mirror and element type of the output.  The resize launch
 // of such a plan writes uint8 canvases, unmirrored, output after output, into a plan-owned buffer; the launches here take every
 // output through its chain, step by step, and store the last step into the caller's array (resize_plan.hip: colour_stage).

@@ -495,7 +495,7 @@ void affine_scale_table(double scale, double offset, int size, int first, int n,
 void affine_host(const uint8_t *src, const DevAffineImage &im, const int32_t *tabs, int ncomp, int out_ncomp, uint32_t fill, uint8_t *out);
 // (ncomp: the decoded images'; out_ncomp: the written ones' — the same, 1 for colour to L, 3 for grey to RGB)
 hipError_t launch_affine(hipStream_t stream, const AffineArgs &a, int ncomp, int out_ncomp);
-// ---- affine.hip: the perspective transform in the same place (MJ_AFFINE_PERSPECTIVE in mj_plan_request.affine's filter byte;
+// ---- affine.hip: the perspective transform in the same place (mj_plan_request.perspective;
 // tools/perspective_model.py).  One output of such a plan: DevAffineImage's image, window and orientation, and the rule:
 //   kind 0  no transform: the oriented pixels of the window
 //        1  NEAREST: the truncated coordinates, in doubles
@@ -522,7 +522,7 @@ const char *perspective_fault(const double *c, int filter, int w, int h);
 int perspective_kind(int filter);
 void perspective_host(const uint8_t *src, const DevPerspectiveImage &im, int ncomp, int out_ncomp, uint32_t fill, uint8_t *out);
 hipError_t launch_perspective(hipStream_t stream, const PerspectiveArgs &a, int ncomp, int out_ncomp);
-// ---- colour.hip: colour operations on the finished canvas (mj_plan_request.mode with MJ_MODE_COLOUR_OPS; tools/colour_model.py)
+// ---- colour.hip: colour operations on the finished canvas (mj_plan_request.colour; tools/colour_model.py)
 // One output of a plan with colour operations: its chain (n ops; value: the factor of brightness, color, contrast and sharpness;
 // ivalue: posterize's MASK and solarize's clamped threshold, as integers — colour_ivalue; a blur's r, with ww and fw beside it —
 // colour_blur_pass), where its elements go in the caller's array (dst_off, in ELEMENTS) and whether it is mirrored.
@@ -627,7 +627,7 @@ __host__ __device__ inline unsigned colour_table_entry(int kind, float value, in
     }
     return (unsigned)i;
 }
-// what the flag and mj_host_colour_ops refuse of one chain: nullptr, or the reason
+// what mj_plan_request.colour and mj_host_colour_ops refuse of one chain: nullptr, or the reason
 const char *colour_fault(const mj_colour_chain &c);
 // the integer form of an op's value (posterize: the mask, solarize: the clamped threshold, a blur: r; else 0)
 int colour_ivalue(const mj_colour_op &op);

@@ -291,12 +291,12 @@ struct mj_plan {
     mj::DevAffineImage *d_af_images = nullptr;
     int32_t *d_af_tabs = nullptr;
     mj::AffineArgs af{};
-    // ... or a perspective transform (MJ_AFFINE_PERSPECTIVE): `affine` is set, the buffer and af_* are as above, and the launch is
+    // ... or a perspective transform (mj_plan_request.perspective): `affine` is set, the buffer and af_* are as above, and the launch is
     // the perspective one with records of its own
     bool perspective = false;
     mj::DevPerspectiveImage *d_pf_images = nullptr;
     mj::PerspectiveArgs pf{};
-    // plans with colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS): the resize launch writes uint8 canvases, unmirrored,
+    // plans with colour operations (mj_plan_request.colour): the resize launch writes uint8 canvases, unmirrored,
     // output after output, into the first half of d_canvas; the colour launches (colour.hip) take them through their chains, from one
     // half to the other, and store the last step into the caller's array — slots, mirror flags and the output table are theirs.
     // d_blur_scratch: a third canvas, only on plans that blur pass by pass (co_blur.lds == 0 with a blur in some chain)
@@ -342,17 +342,13 @@ int plan_create_common(mj_context *ctx, const mj_batch *b, const mj_roi *rois, b
 // named its default names nothing (orientations all 1, the batch's own mode, every place the whole canvas: NULL / 0); n_slots
 // is the output's.  The two makers take it: create_resized (resize_plan.hip) with a size, create_oriented (orient.hip) without
 // one and with orientations or a mode; a request with neither is plan_create_common's.
-// views: r.n_views entries where r.n_views != 0 (the caller's mj_plan_views_request), else NULL
-// affine: one matrix per output where r.affine != 0 (the caller's mj_plan_affine_request), else NULL.  Such a request ALWAYS has
-// views after normalisation: its windows (r.rois) or whole images become one view per image, held in own_views
-// colour: one chain per output where the caller's r.mode had MJ_MODE_COLOUR_OPS (its mj_plan_colour_request) and some chain is not
-// empty, else NULL; r.mode itself holds the mode alone after normalisation
-// perspective: one entry per output where r.affine's filter byte has MJ_AFFINE_PERSPECTIVE (the caller's
-// mj_plan_perspective_request), else NULL; `affine` is then NULL, and what is said of views above holds
+// r.views: r.n_views entries where r.n_views != 0, else NULL
+// r.affine / r.perspective: one entry per output where some output is transformed, else NULL — at most one of the two, and
+// without either r.transform_filter and r.transform_fill are 0.  Such a request ALWAYS has views after normalisation: its
+// windows (r.rois) or whole images become one view per image, held in own_views, which r.views then names
+// r.colour: one chain per output where some chain is not empty, else NULL
 struct PlanRequest {
-    mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r; const mj_view *views = nullptr; const mj_affine *affine = nullptr;
-    const mj_colour_chain *colour = nullptr;
-    const mj_perspective *perspective = nullptr;
+    mj_context *ctx; const mj_batch *b; mj_plan **out; mj_plan_request r;
     std::vector<mj_view> own_views{};
 };
 // an output without a transform: all six entries 0
@@ -366,7 +362,7 @@ constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the message
 int create_resized(const PlanRequest &q);
 // reducing_gap's default rule (normalise_request): whether any image of the request — oriented, its window, to its place's size —
 // gets a factor above 1; images whose sizes the makers will refuse count as none
-bool reduce_applies(const mj_batch *b, const mj_plan_request &r, const mj_view *views);
+bool reduce_applies(const mj_batch *b, const mj_plan_request &r);
 const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std);     // (resize_plan.hip)
 int create_oriented(const PlanRequest &q);
 // q.r.rois (oriented coordinates, not NULL) or the windows `rois` given in their place, as windows of the stored images

@@ -722,37 +722,19 @@ int mj::stored_windows(const PlanRequest &q, const mj_roi *rois, std::vector<mj_
 
 namespace {
 
-// the array of a request with views: the request is then the head of the caller's mj_plan_views_request (include/mijpeg.h)
-const mj_view *request_views(const mj_plan_request *request) {
-    return request && request->n_views ? reinterpret_cast<const mj_plan_views_request *>(request)->views : nullptr;
-}
-
-// (a perspective request's matrices are not read: mj_plan_perspective_request)
-const mj_affine *request_affine(const mj_plan_request *request) {
-    return request && request->affine && !(request->affine & MJ_AFFINE_PERSPECTIVE) ? reinterpret_cast<const mj_plan_affine_request *>(request)->affine : nullptr;
-}
-
-const mj_perspective *request_perspective(const mj_plan_request *request) {
-    return request && (request->affine & MJ_AFFINE_PERSPECTIVE) ? reinterpret_cast<const mj_plan_perspective_request *>(request)->perspective : nullptr;
-}
-
-const mj_colour_chain *request_colour(const mj_plan_request *request) {
-    return request && (request->mode & MJ_MODE_COLOUR_OPS) ? reinterpret_cast<const mj_plan_colour_request *>(request)->colour : nullptr;
-}
-
 // The affine or perspective transform of a sized request, checked against every output's oriented image (views are in place:
 // normalise_views)
 int check_affine(mj::PlanRequest &q) {
     const char *fn = mj::kCreateFn;
     const mj_batch *b = q.b; const mj_plan_request &r = q.r;
-    const int filter = (int)(r.affine & 0xFF & ~MJ_AFFINE_PERSPECTIVE);
+    const int filter = r.transform_filter;
     for (int k = 0; k < r.n_views; ++k) {
-        if (q.perspective ? mj::perspective_none(q.perspective[k]) : mj::affine_none(q.affine[k])) continue;
-        const mj_image_desc &im = b->images[q.views[k].image];
-        const bool t = r.orientations && (mj::orient_bits(r.orientations[q.views[k].image]) & 4);
+        if (r.perspective ? mj::perspective_none(r.perspective[k]) : mj::affine_none(r.affine[k])) continue;
+        const mj_image_desc &im = b->images[r.views[k].image];
+        const bool t = r.orientations && (mj::orient_bits(r.orientations[r.views[k].image]) & 4);
         const int w = t ? im.height : im.width, h = t ? im.width : im.height;
-        if (const char *why = q.perspective ? mj::perspective_fault(q.perspective[k].a, filter, w, h) : mj::affine_fault(q.affine[k].a, filter, w, h))
-            return fail(q.ctx, MJ_ERR_INVALID, "%s: %s: output %d: %s", fn, q.perspective ? "perspective" : "affine", k, why);
+        if (const char *why = r.perspective ? mj::perspective_fault(r.perspective[k].a, filter, w, h) : mj::affine_fault(r.affine[k].a, filter, w, h))
+            return fail(q.ctx, MJ_ERR_INVALID, "%s: %s: output %d: %s", fn, r.perspective ? "perspective" : "affine", k, why);
     }
     return MJ_OK;
 }
@@ -763,12 +745,12 @@ int normalise_views(mj::PlanRequest &q) {
     const char *fn = mj::kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
     if (r.rois) return fail(ctx, MJ_ERR_INVALID, "%s: views and rois do not go together: a view names its own window", fn);
-    if (r.n_views < 1 || !q.views) return fail(ctx, MJ_ERR_INVALID, "%s: views with n_views = %d (must be at least 1, with the array)", fn, r.n_views);
+    if (r.n_views < 1 || !r.views) return fail(ctx, MJ_ERR_INVALID, "%s: views with n_views = %d (must be at least 1, with the array)", fn, r.n_views);
     if (!b->images && b->n_images > 0) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
     std::vector<char> named((size_t)std::max(b->n_images, 0), 0);
     bool identity = r.n_views == b->n_images;
     for (int k = 0; k < r.n_views; ++k) {
-        const mj_view &v = q.views[k];
+        const mj_view &v = r.views[k];
         if (v.image < 0 || v.image >= b->n_images)
             return fail(ctx, MJ_ERR_INVALID, "%s: view %d: image %d outside the %d images of the batch", fn, k, v.image, b->n_images);
         mj_roi shown, stored;
@@ -780,7 +762,7 @@ int normalise_views(mj::PlanRequest &q) {
     }
     for (int i = 0; i < b->n_images; ++i)
         if (!named[(size_t)i]) return fail(ctx, MJ_ERR_INVALID, "%s: image %d: no view names it (leave it out of the batch)", fn, i);
-    if (identity && !q.affine && !q.perspective) { q.views = nullptr; r.n_views = 0; }
+    if (identity && !r.affine && !r.perspective) { r.views = nullptr; r.n_views = 0; }
     return MJ_OK;
 }
 
@@ -792,10 +774,17 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     const char *fn = mj::kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan_request &r = q.r;
     const bool sized = r.out_width != 0 || r.out_height != 0;
-    // (the colour flag is a bit of `mode`; from here on r.mode is the mode alone, and q.colour says whether the flag was set)
-    const bool colour_flag = (r.mode & MJ_MODE_COLOUR_OPS) != 0;
-    r.mode &= ~MJ_MODE_COLOUR_OPS;
-    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill" : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : r.affine ? ((r.affine & MJ_AFFINE_PERSPECTIVE) ? "perspective" : "affine") : colour_flag ? "colour_ops" : nullptr;
+    // (transform_filter and transform_fill belong to whichever of the two arrays is set; set alone, they are refused below)
+    const bool transform_word = r.transform_filter || r.transform_fill[0] || r.transform_fill[1] || r.transform_fill[2];
+    // (n_views switches views on: an array that comes with a count of 0 is not looked at, and the makers, who test the pointer,
+    // never see it)
+    if (!r.n_views) r.views = nullptr;
+    // the first field, in this order, that only a sized request has.  The transform is named by its array; the filter or a fill
+    // byte alone, and both arrays at once — either is refused further down, where there is a size —, say "affine"
+    const char *transform_name = r.perspective && !r.affine ? "perspective" : (r.affine || r.perspective || transform_word) ? "affine" : nullptr;
+    const char *unsized = r.slots ? "slots" : r.output ? "output" : r.filter ? "filter" : r.places ? "places" : r.fill ? "fill"
+                        : r.reducing_gap != 0 ? "reducing_gap" : r.n_views ? "views" : transform_name ? transform_name
+                        : r.colour ? "colour_ops" : nullptr;
     // (what slots, the mirror flags and places have one entry for: the views of a request with views, else the images)
     const int n_out = r.n_views > 0 ? r.n_views : (b ? b->n_images : 0);
     if (!mj::resize_filter_known(r.filter)) return fail(ctx, MJ_ERR_INVALID, "%s: filter %d is none of MJ_FILTER_*", fn, r.filter);
@@ -829,44 +818,43 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
     if ((sized || r.orientations || r.mode) && (b->flags & (MJ_FLAG_KEEP_PLANES | MJ_FLAG_KEEP_IDCT)))
         return fail(ctx, MJ_ERR_INVALID, sized ? "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are at the files' own sizes; a resized plan has none"
                                                : "%s: the seam outputs (MJ_FLAG_KEEP_PLANES / MJ_FLAG_KEEP_IDCT) are in stored order; an oriented plan has none", fn);
-    if (colour_flag) {      // (every chain checked; all of them empty: the request without the flag)
-        if (!q.colour) return fail(ctx, MJ_ERR_INVALID, "%s: colour_ops without its array of chains", fn);
+    if (r.colour) {      // (every chain checked; all of them empty: the request without the field)
         bool none = true;
         for (int k = 0; k < n_out; ++k) {
-            if (const char *why = mj::colour_fault(q.colour[k])) return fail(ctx, MJ_ERR_INVALID, "%s: colour_ops: output %d: %s", fn, k, why);
-            none = none && q.colour[k].n == 0;
+            if (const char *why = mj::colour_fault(r.colour[k])) return fail(ctx, MJ_ERR_INVALID, "%s: colour_ops: output %d: %s", fn, k, why);
+            none = none && r.colour[k].n == 0;
         }
-        if (none) q.colour = nullptr;
-    } else {
-        q.colour = nullptr;
+        if (none) r.colour = nullptr;
     }
-    if (r.affine) {
+    if (r.affine && r.perspective) return fail(ctx, MJ_ERR_INVALID, "%s: affine and perspective do not go together", fn);
+    if (r.affine || r.perspective) {
         const int n_out_af = r.n_views > 0 ? r.n_views : b->n_images;
-        // (the filter byte: MJ_AFFINE_*, with MJ_AFFINE_PERSPECTIVE or-ed in for a perspective transform)
-        const int af_filter = (int)(r.affine & 0xFF), af_base = af_filter & ~MJ_AFFINE_PERSPECTIVE;
-        const bool persp = (af_filter & MJ_AFFINE_PERSPECTIVE) != 0;
-        if (af_base != MJ_AFFINE_NEAREST && af_base != MJ_AFFINE_BILINEAR && af_base != MJ_AFFINE_BICUBIC)
-            return fail(ctx, MJ_ERR_INVALID, "%s: affine: filter %d is none of MJ_AFFINE_*", fn, af_filter);
-        if (persp && !q.perspective) return fail(ctx, MJ_ERR_INVALID, "%s: perspective without its array of coefficients", fn);
-        if (!persp && !q.affine) return fail(ctx, MJ_ERR_INVALID, "%s: affine without its array of matrices", fn);
+        if (r.transform_filter != MJ_AFFINE_NEAREST && r.transform_filter != MJ_AFFINE_BILINEAR && r.transform_filter != MJ_AFFINE_BICUBIC)
+            return fail(ctx, MJ_ERR_INVALID, "%s: affine: filter %d is none of MJ_AFFINE_*", fn, r.transform_filter);
         bool none = true;
-        for (int k = 0; k < n_out_af && none; ++k) none = persp ? mj::perspective_none(q.perspective[k]) : mj::affine_none(q.affine[k]);
-        if (none) { r.affine = 0; q.affine = nullptr; q.perspective = nullptr; }       // (no output is transformed: the request without the field)
+        for (int k = 0; k < n_out_af && none; ++k) none = r.perspective ? mj::perspective_none(r.perspective[k]) : mj::affine_none(r.affine[k]);
+        if (none) {       // (no output is transformed: the request without the field)
+            r.affine = nullptr; r.perspective = nullptr; r.transform_filter = 0;
+            r.transform_fill[0] = r.transform_fill[1] = r.transform_fill[2] = 0;
+        }
+    } else if (transform_word) {
+        return fail(ctx, MJ_ERR_INVALID, "%s: transform_filter / transform_fill without an array (affine or perspective)", fn);
     }
-    if (r.affine) {
+    const bool transform = r.affine || r.perspective;
+    if (transform) {
         if (r.reducing_gap != 0)
             return fail(ctx, MJ_ERR_INVALID, "%s: %s and reducing_gap do not go together yet: the reduce launch would have to read the transformed images", fn,
-                        q.perspective ? "perspective" : "affine");
+                        r.perspective ? "perspective" : "affine");
         if (!b->images && b->n_images > 0) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
         if (!r.n_views) {       // (windows, or whole images, as one view per image: the plan decodes whole images)
             q.own_views.resize((size_t)b->n_images);
             for (int i = 0; i < b->n_images; ++i) q.own_views[(size_t)i] = mj_view{i, r.rois ? r.rois[i] : mj_roi{0, 0, 0, 0}};
-            if (b->n_images > 0) { q.views = q.own_views.data(); r.n_views = b->n_images; r.rois = nullptr; }
+            if (b->n_images > 0) { r.views = q.own_views.data(); r.n_views = b->n_images; r.rois = nullptr; }
         }
     }
     if (r.n_views)
         if (int rc = normalise_views(q)) return rc;
-    if (r.affine && r.n_views)
+    if (transform && r.n_views)
         if (int rc = check_affine(q)) return rc;
     const int n_outputs = r.n_views ? r.n_views : b->n_images;
     if (!r.slots) r.n_slots = n_outputs;
@@ -874,7 +862,7 @@ int normalise_request(mj::PlanRequest &q, bool need_ctx = true) {
         if (r.slots[i] < 0 || r.slots[i] >= r.n_slots)
             return fail(ctx, MJ_ERR_INVALID, "%s: %s %d: slot %d outside the %d slots of the output", fn, r.n_views ? "view" : "image", i, r.slots[i], r.n_slots);
     // (no image with a factor above 1: there is no first step, and the plan is the plan without the field)
-    if (r.reducing_gap != 0 && !mj::reduce_applies(b, r, q.views)) r.reducing_gap = 0;
+    if (r.reducing_gap != 0 && !mj::reduce_applies(b, r)) r.reducing_gap = 0;
     return MJ_OK;
 }
 
@@ -918,15 +906,15 @@ int mj_debug_stage1_form(const int32_t *seg_len, int64_t n_segs, uint64_t blob_l
 int mj_debug_normalise_request(const mj_batch *b, const mj_plan_request *request, mj_plan_request *normal) {
     if (!normal) return MJ_ERR_INVALID;
     mj_plan *none = nullptr;
-    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request), request_perspective(request)};
+    mj::PlanRequest q{nullptr, b, &none, request ? *request : mj_plan_request{}};
     const int rc = normalise_request(q, false);
     if (rc == MJ_OK) *normal = q.r;
-    if (rc == MJ_OK && q.colour) normal->mode |= MJ_MODE_COLOUR_OPS;
+    if (rc == MJ_OK && !q.own_views.empty()) normal->views = nullptr;      // (the library's own views end with q: the count alone goes out)
     return rc;
 }
 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
-    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}, request_views(request), request_affine(request), request_colour(request), request_perspective(request)};
+    mj::PlanRequest q{ctx, b, out, request ? *request : mj_plan_request{}};
     if (int rc = normalise_request(q)) return rc;
     if (q.r.out_width) return mj::create_resized(q);
     if (q.r.orientations || q.r.mode) return mj::create_oriented(q);

@@ -13,7 +13,7 @@
 //   affine_stage           one record per output for the affine launch (affine.hip), its NEAREST index tables, and where every
 //                          output's window of its transformed image lies in the plan's second buffer
 // and the resize launch's records are then upright images of the output's components in THAT buffer, the window's row their pitch.
-// A request with colour operations (mj_plan_request.mode with MJ_MODE_COLOUR_OPS) adds one step behind everything else,
+// A request with colour operations (mj_plan_request.colour) adds one step behind everything else,
 //   colour_stage           the resize launch is made for uint8 canvases of the plan's own, unmirrored, canvas k for output k; the
 //                          colour launches (colour.hip) get the chains, the slots, the mirror flags and the output table
 #include <math.h>
@@ -76,7 +76,7 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
     const char *fn = mj::kCreateFn;
     const mj_roi *rois = q.r.rois; const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
     const int filter = q.r.filter, out_width = q.r.out_width, out_height = q.r.out_height;
-    const mj_view *views = q.views;
+    const mj_view *views = q.r.views;
     const int n_out = views ? q.r.n_views : b->n_images;
     const char *what = views ? "view" : "image";
     if (!b->images && b->n_images > 0) return fail(q.ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
@@ -158,7 +158,7 @@ struct Reduced { int fx, fy, w, h; float bx[2], by[2]; int64_t off; };      // (
 int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std::vector<Reduced> &red, int64_t *bytes) {
     const char *fn = mj::kCreateFn;
     const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
-    const mj_view *views = q.views;
+    const mj_view *views = q.r.views;
     const int n = views ? q.r.n_views : p->n_images, CO = luma ? 1 : p->ncomp;
     // (how the source is read, as launch_resize has it: transposing orientations read the other layout's way, so in the oriented
     // image's axes an image is rows x len = w x h of an x-major reading and h x w of a row-major one)
@@ -219,13 +219,13 @@ int reduce_stage(const PlanRequest &q, mj_plan *p, bool swapped, bool luma, std:
 // In: the request (views in place, matrices checked), the plan, CO — the components the launch writes.  Out: the plan's affine
 // launch (p->af, records and tables uploaded), `off` — per output, where its window lies in the buffer of transformed windows —
 // and *bytes, that buffer's size.
-// (a perspective transform — q.perspective — has records of its own and no tables: p->pf, and p->perspective says so)
+// (a perspective transform — q.r.perspective — has records of its own and no tables: p->pf, and p->perspective says so)
 int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> &off, int64_t *bytes) {
     const char *fn = mj::kCreateFn;
     const uint8_t *orient = q.r.orientations;
-    const int n = q.r.n_views, filter = (int)(q.r.affine & 0xFF & ~MJ_AFFINE_PERSPECTIVE);
-    std::vector<mj::DevAffineImage> recs(q.perspective ? 0 : (size_t)n);
-    std::vector<mj::DevPerspectiveImage> precs(q.perspective ? (size_t)n : 0);
+    const int n = q.r.n_views, filter = q.r.transform_filter;
+    std::vector<mj::DevAffineImage> recs(q.r.perspective ? 0 : (size_t)n);
+    std::vector<mj::DevPerspectiveImage> precs(q.r.perspective ? (size_t)n : 0);
     std::vector<int32_t> tabs;
     off.resize((size_t)n);
     const bool rowmajor = (p->layout & 1) != 0;
@@ -233,9 +233,9 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
     int64_t at = 0;
     // what both kinds of record say of output k: its image, orientation and window, and where its window goes
     auto place = [&](int k, auto &d) {
-        const int i = q.views[k].image;
+        const int i = q.r.views[k].image;
         mj_roi shown, stored;
-        mj::view_window(q.b, orient, q.views[k], &shown, &stored);      // (checked by the request's normalisation)
+        mj::view_window(q.b, orient, q.r.views[k], &shown, &stored);      // (checked by the request's normalisation)
         d.src_off = p->h_images[i].rgb_off; d.dst_off = off[(size_t)k] = at;
         d.sw = p->h_images[i].width; d.sh = p->h_images[i].height;
         d.obits = orient ? mj::orient_bits(orient[i]) : 0;
@@ -245,10 +245,10 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
         max_fast = std::max(max_fast, rowmajor ? d.win_w : d.win_h); max_slow = std::max(max_slow, rowmajor ? d.win_h : d.win_w);
     };
     for (int k = 0; k < n; ++k) {
-        if (q.perspective) {
+        if (q.r.perspective) {
             mj::DevPerspectiveImage &d = precs[(size_t)k] = mj::DevPerspectiveImage{};
             place(k, d);
-            const mj_perspective &m = q.perspective[k];
+            const mj_perspective &m = q.r.perspective[k];
             if (!mj::perspective_none(m)) {
                 d.kind = mj::perspective_kind(filter);
                 for (int t = 0; t < 8; ++t) d.c[t] = m.a[t];
@@ -257,7 +257,7 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
         }
         mj::DevAffineImage &d = recs[(size_t)k] = mj::DevAffineImage{};
         place(k, d);
-        const mj_affine &m = q.affine[k];
+        const mj_affine &m = q.r.affine[k];
         if (!mj::affine_none(m)) {
             d.kind = mj::affine_kind(m.a, filter);
             for (int t = 0; t < 6; ++t) d.a[t] = m.a[t];
@@ -275,9 +275,9 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
     if ((int64_t)n * tiles_slow * tiles_fast > mj::kResizeGridX * (int64_t)65535)
         return fail(q.ctx, MJ_ERR_UNSUPPORTED, "%s: %lld affine tiles are more than one launch takes; split the batch", fn, (long long)n * tiles_slow * tiles_fast);
     uint32_t fill = 0;
-    for (int c = 0; c < CO; ++c) fill |= ((q.r.affine >> (8 + 8 * c)) & 0xFFu) << (8 * c);
+    for (int c = 0; c < CO; ++c) fill |= (uint32_t)q.r.transform_fill[c] << (8 * c);
     *bytes = at;
-    if (q.perspective) {
+    if (q.r.perspective) {
         mj::PerspectiveArgs &a = p->pf = mj::PerspectiveArgs{};
         a.tiles_fast = tiles_fast; a.tiles_slow = tiles_slow; a.n_images = n; a.layout = p->layout; a.fill = fill;
         if (int rc = upload(p, &p->d_pf_images, precs.data(), precs.size())) return rc;
@@ -310,7 +310,7 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     std::vector<int32_t> list;
     std::vector<uint32_t> weights((size_t)n * 8, 0);
     for (int k = 0; k < n; ++k) {
-        const mj_colour_chain &c = q.colour[k];
+        const mj_colour_chain &c = q.r.colour[k];
         mj::DevColourOutput &d = recs[(size_t)k] = mj::DevColourOutput{};
         d.dst_off = (int64_t)(r.slots ? r.slots[k] : k) * npix * CO;
         d.n = c.n; d.mirror = r.output && r.output->mirror && r.output->mirror[k] ? 1 : 0;
@@ -532,8 +532,9 @@ std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize) {
 
 }  // namespace
 
-bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r, const mj_view *views) {
+bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r) {
     if (!b || !b->images || r.reducing_gap == 0) return false;
+    const mj_view *views = r.views;
     const int n_out = views ? r.n_views : b->n_images;
     for (int k = 0; k < n_out; ++k) {
         const int i = views ? views[k].image : k;
@@ -555,11 +556,12 @@ bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r, const mj_vi
 int mj::create_resized(const PlanRequest &q) {
     const char *fn = kCreateFn;
     mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
-    auto [rois, orient, mode, out_width, out_height, affine, slots, n_slots, n_views, output, filter, reducing_gap, places, fill] = q.r;
-    const mj_view *views = q.views;
+    auto [rois, orient, mode, out_width, out_height, transform_filter, matrices, perspective, slots, n_slots, n_views, views, output, filter,
+          reducing_gap, places, fill, chains, transform_fill] = q.r;
+    const bool affine = matrices || perspective;      // (either transform: the launch in front of the resize)
     // a plan with colour operations: the resize launch is that of the uint8, unmirrored, identity-slot request — it writes the
     // canvases —, and the element type, the slots and the mirror flags are the colour launches' (colour_stage)
-    const bool colour = q.colour != nullptr;
+    const bool colour = chains != nullptr;
     const int dtype = output ? output->dtype : MJ_DTYPE_U8, out_esize = dtype_size(dtype), esize = colour ? 1 : out_esize;
     std::vector<Need> need;
     std::vector<mj_roi> derived;

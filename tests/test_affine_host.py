@@ -251,40 +251,25 @@ def test_the_request_with_an_affine_transform_is_laid_out_as_the_binding_assumes
     gcc = shutil.which("gcc")
     assert gcc is not None, "the header is held to a C compiler"
     flags = ["-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include")]
-    efields = [f for f, _ in B.PlanAffineRequestC._fields_]
-    assert efields == ["request", "views", "affine"]
     src = tmp_path / "layout.c"
     src.write_text("\n".join(
-        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_affine_request zeroed = {{0}, 0, 0};',
-         '  printf("%zu %zu %zu %zu", sizeof(mj_plan_request), offsetof(mj_plan_request, out_height), offsetof(mj_plan_request, affine), offsetof(mj_plan_request, slots));',
-         '  printf(" %zu %zu", sizeof(mj_plan_affine_request), sizeof(mj_affine));'] +
-        [f'  printf(" %zu", offsetof(mj_plan_affine_request, {f}));' for f in efields] +
-        ['  printf(" %zu %u", offsetof(mj_plan_views_request, views), (unsigned)MJ_AFFINE_FIELD(MJ_AFFINE_BICUBIC, 7, 99, 200));',
+        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_request zeroed = {0};',
+         '  printf("%zu", sizeof(mj_affine));',
          '  printf(" %d %d %d", MJ_AFFINE_NEAREST, MJ_AFFINE_BILINEAR, MJ_AFFINE_BICUBIC);',
-         '  printf(" %d\\n", zeroed.affine == 0 && zeroed.request.affine == 0);', '  return 0;', '}']))
+         '  printf(" %d\\n", zeroed.affine == 0 && zeroed.transform_filter == 0 && zeroed.transform_fill[2] == 0);', '  return 0;', '}']))
     exe = tmp_path / "layout"
     subprocess.run([gcc] + flags + [str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    R, E = B.PlanRequestC, B.PlanAffineRequestC
-    want = ([ctypes.sizeof(R), R.out_height.offset, R.out_height.offset + 4, R.slots.offset, ctypes.sizeof(E), ctypes.sizeof(B.AffineC)] +
-            [getattr(E, f).offset for f in efields] + [B.PlanViewsRequestC.views.offset, 3 | 7 << 8 | 99 << 16 | 200 << 24] +
-            [B.MJ_AFFINE_NEAREST, B.MJ_AFFINE_BILINEAR, B.MJ_AFFINE_BICUBIC, 1])
-    assert got == want
-    # the word lies in what was padding — the request keeps its size and every other field its offset —, the views pointer where a
-    # request with views has it, and the matrices' pointer behind it
-    assert R.slots.offset - R.out_height.offset == 8 and E.views.offset == B.PlanViewsRequestC.views.offset == ctypes.sizeof(R)
-    assert E.affine.offset == ctypes.sizeof(R) + 8 and ctypes.sizeof(B.AffineC) == 48
-    r = B.PlanRequestC()
-    r.affine = 0xC8630703
-    assert r.affine == 0xC8630703 and r.out_height == 0 and not r.slots and r.n_slots == 0
-    # plan_request: the word, the matrices (None: all zero), one per output
+    assert got == [ctypes.sizeof(B.AffineC), B.MJ_AFFINE_NEAREST, B.MJ_AFFINE_BILINEAR, B.MJ_AFFINE_BICUBIC, 1]
+    assert ctypes.sizeof(B.AffineC) == 48
+    # (the request's own layout, these fields included: test_plan_request_host)
+    # plan_request: the filter, the fill bytes, the matrices (None: all zero), one per output
     m = (0.5, 0.25, 3.0, -0.25, 0.5, 1.5)
     r, keep = B.plan_request(2, size=(24, 16), affine=([m, None], "bicubic", (7, 99, 200)))
-    ext = keep["affine_request"]
-    assert ctypes.addressof(r) == ctypes.addressof(ext) and r.affine == (3 | 7 << 8 | 99 << 16 | 200 << 24) and r.n_views == 0 and not ext.views
-    assert tuple(ext.affine[0].a) == m and tuple(ext.affine[1].a) == (0.0,) * 6
+    assert r.transform_filter == B.MJ_AFFINE_BICUBIC and tuple(r.transform_fill) == (7, 99, 200) and r.n_views == 0 and not r.views and not r.perspective
+    assert tuple(r.affine[0].a) == m and tuple(r.affine[1].a) == (0.0,) * 6
     r, keep = B.plan_request(2, size=(24, 16), views=[(1, None), (0, (1, 1, 4, 4)), (1, None)], affine=([m, None, m], "nearest", (5,)))
-    assert r.n_views == 3 and r.affine == (1 | 5 << 8) and keep["affine_request"].views[1].window.width == 4
+    assert r.n_views == 3 and r.transform_filter == B.MJ_AFFINE_NEAREST and tuple(r.transform_fill) == (5, 0, 0) and r.views[1].window.width == 4
     with pytest.raises(ValueError, match="affine: 1 entries, not one for each of the 2 images"):
         B.plan_request(2, size=(24, 16), affine=([m], "nearest", (0,)))
     with pytest.raises(ValueError, match="affine: 2 entries, not one for each of the 3 views"):
@@ -292,7 +277,7 @@ def test_the_request_with_an_affine_transform_is_laid_out_as_the_binding_assumes
     with pytest.raises(ValueError, match="affine needs size"):
         B.plan_request(2, affine=([m, m], "nearest", (0,)))
     header = (ROOT / "include" / "mijpeg.h").read_text()
-    assert "uint32_t affine;" in header and "const mj_affine *affine;" in header
+    assert "int32_t transform_filter;" in header and "uint8_t transform_fill[3];" in header and "const mj_affine *affine;" in header
 
 
 def test_no_transform_is_the_zeroed_request(lib):
@@ -308,13 +293,15 @@ def test_no_transform_is_the_zeroed_request(lib):
         assert bytes(a) == bytes(b) and req.plan_kwargs(3) == plain.plan_kwargs(3)
     batch, keep = _batch([(128, 64), (50, 70)])
     rc, out, msg = _normal(lib, batch, affine=([None, None], "bilinear", (1, 2, 3)))
-    assert rc == B.MJ_OK and out.affine == 0 and out.n_views == 0 and out.n_slots == 2, msg
+    assert rc == B.MJ_OK and not out.affine and not out.perspective and out.transform_filter == 0 and bytes(out.transform_fill) == bytes(3), msg
+    assert out.n_views == 0 and out.n_slots == 2
     rc, plain_out, _ = _normal(lib, batch)
     assert bytes(out) == bytes(plain_out)
     # a request with a transform: its windows, or whole images, become one view per image
     m = (0.9, 0.3, -2.0, -0.3, 0.9, 4.0)
     rc, out, msg = _normal(lib, batch, affine=([m, None], "bilinear", (1, 2, 3)))
-    assert rc == B.MJ_OK and out.affine == (2 | 1 << 8 | 2 << 16 | 3 << 24) and out.n_views == 2 and out.n_slots == 2 and not out.rois, msg
+    assert rc == B.MJ_OK and bool(out.affine) and out.transform_filter == 2 and tuple(out.transform_fill) == (1, 2, 3), msg
+    assert out.n_views == 2 and out.n_slots == 2 and not out.rois and not out.views, "the library's own views do not leave it"
     rc, out, msg = _normal(lib, batch, affine=([m, m], "nearest", (0,)), rois=[(1, 1, 4, 4), (0, 0, 50, 70)])
     assert rc == B.MJ_OK and out.n_views == 2 and not out.rois, msg
     rc, out, msg = _normal(lib, batch, affine=([m, None, m], "bicubic", (0,)), views=[(1, None), (0, (1, 1, 4, 4)), (1, None)])
@@ -345,8 +332,15 @@ def test_request_refusals(lib):
     assert rc == B.MJ_ERR_INVALID and "affine: output 1: an image with a side of 32768 or more" in msg
     rc, _, msg = _normal(lib, big, affine=ok, orientation=[1, 6])
     assert rc == B.MJ_ERR_INVALID and "affine: output 1: an image with a side of 32768 or more" in msg
+    for fill in ((0, 0, 0), (0, 0, 1)):                       # (the filter, or a fill byte, without an array)
+        r, keep_r = B.plan_request(2, size=(24, 16), affine=(ok[0], "bilinear" if not any(fill) else 0, fill))
+        r.affine = None
+        out = B.PlanRequestC()
+        assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
+        assert "transform_filter / transform_fill without an array" in lib.mj_last_error(None).decode()
+    # both arrays in one request
     r, keep_r = B.plan_request(2, size=(24, 16), affine=ok)
-    keep_r["affine_request"].affine = None                   # (the word without the array)
+    keep_p = r.perspective = (B.PerspectiveC * 2)()
     out = B.PlanRequestC()
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
-    assert "affine without its array" in lib.mj_last_error(None).decode()
+    assert "affine and perspective do not go together" in lib.mj_last_error(None).decode()

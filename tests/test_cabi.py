@@ -26,7 +26,7 @@ def test_exports_every_declared_symbol(lib):
     assert declared == set(B.EXPORTS), declared ^ set(B.EXPORTS)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.mj_version() == 1
+    assert lib.mj_version() == 2
 
 
 def test_plan_shape_and_cache_accessors_are_exported_and_declared_as_c(lib, tmp_path):

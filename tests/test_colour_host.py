@@ -267,40 +267,32 @@ def test_the_request_with_colour_operations_is_laid_out_as_the_binding_assumes(l
     gcc = shutil.which("gcc")
     assert gcc is not None, "the header is held to a C compiler"
     flags = ["-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include")]
-    rfields = [f for f, _ in B.PlanRequestC._fields_]
     src = tmp_path / "layout.c"
     src.write_text("\n".join(
-        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_colour_request zeroed = {{{0}, 0, 0}, 0};',
-         '  printf("%zu %zu %zu", sizeof(mj_plan_request), sizeof(mj_plan_affine_request), sizeof(mj_plan_colour_request));'] +
-        [f'  printf(" %zu", offsetof(mj_plan_request, {f}));' for f in rfields] +
-        ['  printf(" %zu %zu", offsetof(mj_plan_colour_request, head), offsetof(mj_plan_colour_request, colour));',
-         '  printf(" %zu %zu %zu", sizeof(mj_colour_chain), sizeof(mj_colour_op), offsetof(mj_colour_chain, op));',
-         '  printf(" %d %d", MJ_MODE_COLOUR_OPS, MJ_COLOUR_MAX_OPS);',
+        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_request zeroed = {0};',
+         '  printf("%zu %zu %zu", sizeof(mj_colour_chain), sizeof(mj_colour_op), offsetof(mj_colour_chain, op));',
+         '  printf(" %d", MJ_COLOUR_MAX_OPS);',
          '  printf(" %d %d %d %d %d %d %d %d %d", MJ_COLOUR_BRIGHTNESS, MJ_COLOUR_COLOR, MJ_COLOUR_CONTRAST, MJ_COLOUR_SHARPNESS, MJ_COLOUR_POSTERIZE,',
          '         MJ_COLOUR_SOLARIZE, MJ_COLOUR_AUTOCONTRAST, MJ_COLOUR_EQUALIZE, MJ_COLOUR_INVERT);',
-         '  printf(" %d\\n", zeroed.colour == 0 && zeroed.head.affine == 0 && zeroed.head.request.mode == 0);', '  return 0;', '}']))
+         '  printf(" %d\\n", zeroed.colour == 0 && zeroed.affine == 0 && zeroed.mode == 0);', '  return 0;', '}']))
     exe = tmp_path / "layout"
     subprocess.run([gcc] + flags + [str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    R, A, E = B.PlanRequestC, B.PlanAffineRequestC, B.PlanColourRequestC
-    want = ([ctypes.sizeof(R), ctypes.sizeof(A), ctypes.sizeof(E)] + [getattr(R, f).offset for f in rfields] + [E.head.offset, E.colour.offset] +
-            [ctypes.sizeof(B.ColourChainC), ctypes.sizeof(B.ColourOpC), B.ColourChainC.op.offset, B.MJ_MODE_COLOUR_OPS, B.MJ_COLOUR_MAX_OPS] +
+    want = ([ctypes.sizeof(B.ColourChainC), ctypes.sizeof(B.ColourOpC), B.ColourChainC.op.offset, B.MJ_COLOUR_MAX_OPS] +
             [B.COLOUR_OPS[n] for n in ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "autocontrast", "equalize", "invert")] + [1])
     assert got == want
-    # the request's size and every field's offset are what they were (the flag is a bit of `mode`); the chains' pointer lies behind `affine`
-    assert ctypes.sizeof(R) == 80 and ctypes.sizeof(A) == 96 and E.head.offset == 0 and E.colour.offset == ctypes.sizeof(A) == A.affine.offset + 8
-    assert ctypes.sizeof(B.ColourChainC) == 36 and ctypes.sizeof(B.ColourOpC) == 8 and B.MJ_MODE_COLOUR_OPS == 0x100
-    # plan_request: the flag, one chain per output (None: empty), views and matrices where a request with them has them
+    assert ctypes.sizeof(B.ColourChainC) == 36 and ctypes.sizeof(B.ColourOpC) == 8
+    # (the request's own layout, `colour` included: test_plan_request_host)
+    # plan_request: one chain per output (None: empty), the mode untouched, views and matrices beside them
     one = (("brightness", 1.25), ("equalize",))
     r, keep = B.plan_request(2, size=(24, 16), colour=[one, None], mode="L")
-    ext = keep["colour_request"]
-    assert ctypes.addressof(r) == ctypes.addressof(ext) and r.mode == (B.MJ_MODE_L | B.MJ_MODE_COLOUR_OPS) and r.n_views == 0 and not ext.head.views
-    assert ext.colour[0].n == 2 and ext.colour[1].n == 0 and ext.colour[0].op[0].kind == 1 and ext.colour[0].op[0].value == 1.25 and ext.colour[0].op[1].kind == 8
+    assert r.mode == B.MJ_MODE_L and r.n_views == 0 and not r.views and not r.affine
+    assert r.colour[0].n == 2 and r.colour[1].n == 0 and r.colour[0].op[0].kind == 1 and r.colour[0].op[0].value == 1.25 and r.colour[0].op[1].kind == 8
     m = (0.5, 0.25, 3.0, -0.25, 0.5, 1.5)
     r, keep = B.plan_request(2, size=(24, 16), views=[(1, None), (0, (1, 1, 4, 4)), (1, None)], affine=([m, None, m], "nearest", (5,)),
                              colour=[None, one, one])
-    ext = keep["colour_request"]
-    assert r.n_views == 3 and r.affine == (1 | 5 << 8) and ext.head.views[1].window.width == 4 and tuple(ext.head.affine[2].a) == m and ext.colour[2].n == 2
+    assert r.n_views == 3 and r.transform_filter == 1 and tuple(r.transform_fill) == (5, 0, 0)
+    assert r.views[1].window.width == 4 and tuple(r.affine[2].a) == m and r.colour[2].n == 2
     with pytest.raises(ValueError, match="colour: 1 entries, not one for each of the 2 images"):
         B.plan_request(2, size=(24, 16), colour=[one])
     with pytest.raises(ValueError, match="colour: 2 entries, not one for each of the 3 views"):
@@ -308,12 +300,12 @@ def test_the_request_with_colour_operations_is_laid_out_as_the_binding_assumes(l
     with pytest.raises(ValueError, match="colour needs size"):
         B.plan_request(2, colour=[one, one])
     header = (ROOT / "include" / "mijpeg.h").read_text()
-    assert "const mj_colour_chain *colour;" in header and "mj_plan_affine_request head;" in header
+    assert "const mj_colour_chain *colour;" in header
 
 
 def test_no_operations_is_the_zeroed_request(lib):
     """None and lists of None or empty chains make the byte-identical request of a call without the argument — in Python — and
-    chains that are all empty normalise to the flag's absence in the library"""
+    chains that are all empty normalise to the field's absence in the library"""
     from pyjpegdecoder_amd import _binding as B
     from pyjpegdecoder_amd.batch import _Request, normalize_color_ops
     plain = _Request([b"a", b"b"], None, (24, 16))
@@ -325,19 +317,19 @@ def test_no_operations_is_the_zeroed_request(lib):
     batch, keep = _batch([(128, 64), (50, 70)])
     rc, plain_out, _ = _normal(lib, batch)
     rc, out, msg = _normal(lib, batch, colour=[None, ()])
-    assert rc == B.MJ_OK and out.mode == 0 and bytes(out) == bytes(plain_out), msg
+    assert rc == B.MJ_OK and out.mode == 0 and not out.colour and bytes(out) == bytes(plain_out), msg
     rc, out, msg = _normal(lib, batch, colour=[None, ()], mode="L")
-    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_L, msg
-    # a request with operations keeps the flag, and the mode beside it is normalised as ever (RGB is these files' own)
+    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_L and not out.colour, msg
+    # a request with operations keeps its chains, and the mode beside it is normalised as ever (RGB is these files' own)
     rc, out, msg = _normal(lib, batch, colour=[None, (("invert",),)])
-    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_COLOUR_OPS and out.n_slots == 2, msg
+    assert rc == B.MJ_OK and out.mode == 0 and bool(out.colour) and out.n_slots == 2, msg
     rc, out, msg = _normal(lib, batch, colour=[None, (("invert",),)], mode="RGB")
-    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_COLOUR_OPS, msg
+    assert rc == B.MJ_OK and out.mode == 0 and bool(out.colour), msg
     rc, out, msg = _normal(lib, batch, colour=[(("equalize",),), None], mode="L")
-    assert rc == B.MJ_OK and out.mode == (B.MJ_MODE_L | B.MJ_MODE_COLOUR_OPS), msg
+    assert rc == B.MJ_OK and out.mode == B.MJ_MODE_L and bool(out.colour), msg
     rc, out, msg = _normal(lib, batch, colour=[None, (("invert",),), None], views=[(1, None), (0, (1, 1, 4, 4)), (1, None)])
-    assert rc == B.MJ_OK and out.n_views == 3 and out.mode == B.MJ_MODE_COLOUR_OPS, msg
-    # a zeroed request with a mode that was never given the bit is what it was
+    assert rc == B.MJ_OK and out.n_views == 3 and out.mode == 0 and bool(out.colour), msg
+    # a zeroed request is what it was
     r = B.PlanRequestC()
     out = B.PlanRequestC()
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_OK and bytes(out)[:16] == bytes(16)
@@ -359,13 +351,9 @@ def test_request_refusals(lib):
     out = B.PlanRequestC()
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
     assert "colour_ops: output 0: a chain has 0..MJ_COLOUR_MAX_OPS ops" in lib.mj_last_error(None).decode()
+    # a mode that is none of MJ_MODE_* stays refused beside the chains
     r, keep_r = B.plan_request(2, size=(24, 16), colour=ok)
-    keep_r["colour_request"].colour = None                      # (the flag without the array)
-    assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
-    assert "colour_ops without its array" in lib.mj_last_error(None).decode()
-    # a mode that is none of MJ_MODE_* stays refused beside the flag
-    r, keep_r = B.plan_request(2, size=(24, 16), colour=ok)
-    r.mode = 2 | B.MJ_MODE_COLOUR_OPS
+    r.mode = 2
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
     assert "mode 2 is none of MJ_MODE_*" in lib.mj_last_error(None).decode()
 

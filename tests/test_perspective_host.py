@@ -355,35 +355,23 @@ def test_the_request_with_a_perspective_transform_is_laid_out_as_the_binding_ass
     flags = ["-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include")]
     src = tmp_path / "layout.c"
     src.write_text("\n".join(
-        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_perspective_request zeroed = {{{{0}, 0, 0}, 0}, 0};',
-         '  printf("%zu %zu %zu %zu", sizeof(mj_perspective), sizeof(mj_plan_perspective_request), offsetof(mj_plan_perspective_request, perspective),',
-         '         offsetof(mj_plan_perspective_request, head));',
-         '  printf(" %zu %zu %zu %zu", sizeof(mj_plan_request), sizeof(mj_plan_views_request), sizeof(mj_plan_affine_request), sizeof(mj_plan_colour_request));',
-         '  printf(" %zu %zu %zu", offsetof(mj_plan_request, affine), offsetof(mj_plan_affine_request, affine), offsetof(mj_plan_colour_request, colour));',
-         '  printf(" %d %u", MJ_AFFINE_PERSPECTIVE, (unsigned)MJ_AFFINE_FIELD(MJ_AFFINE_BICUBIC | MJ_AFFINE_PERSPECTIVE, 7, 99, 200));',
-         '  printf(" %d\\n", zeroed.perspective == 0 && zeroed.head.head.request.affine == 0);', '  return 0;', '}']))
+        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_request zeroed = {0};',
+         '  printf("%zu", sizeof(mj_perspective));',
+         '  printf(" %d\\n", zeroed.perspective == 0 && zeroed.affine == 0 && zeroed.transform_filter == 0);', '  return 0;', '}']))
     exe = tmp_path / "layout"
     subprocess.run([gcc] + flags + [str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    R, V, A, C, P = B.PlanRequestC, B.PlanViewsRequestC, B.PlanAffineRequestC, B.PlanColourRequestC, B.PlanPerspectiveRequestC
-    want = [ctypes.sizeof(B.PerspectiveC), ctypes.sizeof(P), P.perspective.offset, P.head.offset,
-            ctypes.sizeof(R), ctypes.sizeof(V), ctypes.sizeof(A), ctypes.sizeof(C), R.out_height.offset + 4, A.affine.offset, C.colour.offset,
-            B.MJ_AFFINE_PERSPECTIVE, 0x13 | 7 << 8 | 99 << 16 | 200 << 24, 1]
-    assert got == want
-    # the new request wraps the one before it: no structure that existed changed its size, and the new pointer lies behind them all
-    assert got[0] == 64 and got[3] == 0 and got[2] == ctypes.sizeof(C) and got[1] == ctypes.sizeof(C) + 8 and B.MJ_AFFINE_PERSPECTIVE == 0x10
-    assert (ctypes.sizeof(V), ctypes.sizeof(A), ctypes.sizeof(C)) == (ctypes.sizeof(R) + 8, ctypes.sizeof(R) + 16, ctypes.sizeof(R) + 24)
-    # plan_request: the word with the flag, the coefficients (None: all zero), one per output; the matrices' pointer stays NULL
+    assert got == [ctypes.sizeof(B.PerspectiveC), 1] and got[0] == 64
+    # (the request's own layout, `perspective` included: test_plan_request_host)
+    # plan_request: the filter, the fill bytes, the coefficients (None: all zero), one per output; the matrices' pointer stays NULL
     c = (0.5, 0.25, 3.0, -0.25, 0.5, 1.5, 0.001, -0.002)
     r, keep = B.plan_request(2, size=(24, 16), perspective=([c, None], "bicubic", (7, 99, 200)))
-    top = keep["perspective_request"]
-    assert ctypes.addressof(r) == ctypes.addressof(top) and r.affine == (0x13 | 7 << 8 | 99 << 16 | 200 << 24) and r.n_views == 0
-    assert tuple(top.perspective[0].a) == c and tuple(top.perspective[1].a) == (0.0,) * 8 and not top.head.head.affine and not top.head.colour
+    assert r.transform_filter == B.MJ_AFFINE_BICUBIC and tuple(r.transform_fill) == (7, 99, 200) and r.n_views == 0
+    assert tuple(r.perspective[0].a) == c and tuple(r.perspective[1].a) == (0.0,) * 8 and not r.affine and not r.colour
     r, keep = B.plan_request(2, size=(24, 16), views=[(1, None), (0, (1, 1, 4, 4)), (1, None)], perspective=([c, None, c], "nearest", (5,)),
                              colour=[None, [("invert",)], None])
-    top = keep["perspective_request"]
-    assert r.n_views == 3 and r.affine == (0x11 | 5 << 8) and top.head.head.views[1].window.width == 4 and top.head.colour[1].n == 1
-    assert r.mode & B.MJ_MODE_COLOUR_OPS
+    assert r.n_views == 3 and r.transform_filter == B.MJ_AFFINE_NEAREST and tuple(r.transform_fill) == (5, 0, 0)
+    assert r.views[1].window.width == 4 and r.colour[1].n == 1 and r.mode == 0
     with pytest.raises(ValueError, match="perspective: 1 entries, not one for each of the 2 images"):
         B.plan_request(2, size=(24, 16), perspective=([c], "nearest", (0,)))
     with pytest.raises(ValueError, match="perspective: 2 entries, not one for each of the 3 views"):
@@ -393,7 +381,7 @@ def test_the_request_with_a_perspective_transform_is_laid_out_as_the_binding_ass
     with pytest.raises(ValueError, match="affine and perspective do not go together"):
         B.plan_request(2, size=(24, 16), perspective=([c, c], "nearest", (0,)), affine=([None, None], "nearest", (0,)))
     header = (ROOT / "include" / "mijpeg.h").read_text()
-    assert "const mj_perspective *perspective;" in header and "#define MJ_AFFINE_PERSPECTIVE 0x10" in header
+    assert "const mj_perspective *perspective;" in header
     assert "mj_host_perspective" in B.EXPORTS and hasattr(lib, "mj_host_perspective")
 
 
@@ -410,13 +398,15 @@ def test_no_transform_is_the_zeroed_request(lib):
         assert bytes(a) == bytes(b) and req.plan_kwargs(3) == plain.plan_kwargs(3)
     batch, keep = _batch([(128, 64), (50, 70)])
     rc, out, msg = _normal(lib, batch, perspective=([None, None], "bilinear", (1, 2, 3)))
-    assert rc == B.MJ_OK and out.affine == 0 and out.n_views == 0 and out.n_slots == 2, msg
+    assert rc == B.MJ_OK and not out.affine and not out.perspective and out.transform_filter == 0 and bytes(out.transform_fill) == bytes(3), msg
+    assert out.n_views == 0 and out.n_slots == 2
     rc, plain_out, _ = _normal(lib, batch)
     assert bytes(out) == bytes(plain_out)
-    # a request with a transform: its windows, or whole images, become one view per image; the word keeps its flag
+    # a request with a transform: its windows, or whole images, become one view per image; the array stays the caller's
     c = (0.9, 0.3, -2.0, -0.3, 0.9, 4.0, 0.001, 0.0)
     rc, out, msg = _normal(lib, batch, perspective=([c, None], "bilinear", (1, 2, 3)))
-    assert rc == B.MJ_OK and out.affine == (0x12 | 1 << 8 | 2 << 16 | 3 << 24) and out.n_views == 2 and out.n_slots == 2 and not out.rois, msg
+    assert rc == B.MJ_OK and bool(out.perspective) and not out.affine and out.transform_filter == 2 and tuple(out.transform_fill) == (1, 2, 3), msg
+    assert out.n_views == 2 and out.n_slots == 2 and not out.rois and not out.views
     rc, out, msg = _normal(lib, batch, perspective=([c, c], "nearest", (0,)), rois=[(1, 1, 4, 4), (0, 0, 50, 70)])
     assert rc == B.MJ_OK and out.n_views == 2 and not out.rois, msg
     rc, out, msg = _normal(lib, batch, perspective=([c, None, c], "bicubic", (0,)), views=[(1, None), (0, (1, 1, 4, 4)), (1, None)])
@@ -435,9 +425,9 @@ def test_request_refusals(lib):
     assert rc == B.MJ_ERR_INVALID and "perspective needs a size" in msg
     rc, _, msg = _normal(lib, batch, perspective=ok, reducing_gap=2.0)
     assert rc == B.MJ_ERR_INVALID and "perspective and reducing_gap do not go together yet" in msg
-    for bad_filter in (9, 4, 0):                # (with the flag or-ed in by plan_request: 0x19, 0x14, 0x10)
+    for bad_filter in (9, 4, 0):
         rc, _, msg = _normal(lib, batch, perspective=([c, c], bad_filter, (0,)))
-        assert rc == B.MJ_ERR_INVALID and f"affine: filter {bad_filter | 0x10} is none of MJ_AFFINE_*" in msg
+        assert rc == B.MJ_ERR_INVALID and f"affine: filter {bad_filter} is none of MJ_AFFINE_*" in msg
     for good in (1, 2, 3):
         assert _normal(lib, batch, perspective=([c, c], good, (0,)))[0] == B.MJ_OK
     rc, _, msg = _normal(lib, batch, perspective=ok, rois=[(1, 1, 4, 4), (0, 0, 51, 70)])
@@ -454,10 +444,15 @@ def test_request_refusals(lib):
     rc, _, msg = _normal(lib, big, perspective=ok, orientation=[1, 6])
     assert rc == B.MJ_ERR_INVALID and "perspective: output 1: an image with a side of 32768 or more" in msg
     r, keep_r = B.plan_request(2, size=(24, 16), perspective=ok)
-    keep_r["perspective_request"].perspective = None            # (the word without the array)
+    r.perspective = None                                        # (the filter without an array)
     out = B.PlanRequestC()
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
-    assert "perspective without its array" in lib.mj_last_error(None).decode()
+    assert "transform_filter / transform_fill without an array" in lib.mj_last_error(None).decode()
+    # both arrays in one request
+    r, keep_r = B.plan_request(2, size=(24, 16), perspective=ok)
+    keep_a = r.affine = (B.AffineC * 2)()
+    assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
+    assert "affine and perspective do not go together" in lib.mj_last_error(None).decode()
     # the affine refusals, with their messages as they were
     m = (0.9, 0.3, -2.0, -0.3, 0.9, 4.0)
     rc, _, msg = _normal(lib, batch, affine=([m, m], "bilinear", (0,)), size=None)

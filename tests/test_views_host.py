@@ -73,8 +73,7 @@ def test_per_view_lists_have_one_entry_per_view():
     # the binding: places and the mirror flags per view, orientations per image
     from pyjpegdecoder_amd import _binding as B
     r, keep = B.plan_request(2, size=(24, 16), views=views, places=places, orientation=[1, 6], output=("uint8", None, None, [1, 0, 1]))
-    ext = keep["views_request"]
-    assert r.n_views == 3 and ctypes.addressof(r) == ctypes.addressof(ext) and (ext.views[1].image, ext.views[1].window.x, ext.views[1].window.width) == (0, 3, 61)
+    assert r.n_views == 3 and (r.views[1].image, r.views[1].window.x, r.views[1].window.width) == (0, 3, 61)
     with pytest.raises(ValueError, match="places: 2 entries, not one for each of the 3 views"):
         B.plan_request(2, size=(24, 16), views=views, places=places[:2])
     with pytest.raises(ValueError, match="mirror: 2 entries, not one for each of the 3 views"):
@@ -165,7 +164,17 @@ def test_request_identity_views_come_back_absent(lib):
         rc, out, msg = _normal(lib, batch, views=views)
         assert rc == B.MJ_OK and out.n_views == 0 and out.n_slots == 2, msg
     rc, out, _ = _normal(lib, batch, views=[(0, None), (1, (0, 0, 70, 50))], orientation=[1, 6])     # whole, as the orientation shows it
-    assert rc == B.MJ_OK and out.n_views == 0
+    assert rc == B.MJ_OK and out.n_views == 0 and not out.views
+    # the count switches views on: an array that comes with n_views == 0 is not looked at — the request is the plain one —,
+    # from C and from plan_request(views=[])
+    rc, plain_out, _ = _normal(lib, batch)
+    r, keep_r = B.plan_request(2, size=(24, 16), views=[(1, None), (0, (1, 1, 4, 4))])
+    r.n_views = 0
+    for req in (r, B.plan_request(2, size=(24, 16), views=[])[0]):
+        assert bool(req.views) and req.n_views == 0
+        out = B.PlanRequestC()
+        assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(req), ctypes.byref(out)) == B.MJ_OK
+        assert not out.views and out.n_views == 0 and out.n_slots == 2 and bytes(out) == bytes(plain_out)
     # anything else stays: another order, a window, a file twice — and n_slots defaults to the views
     for views in ([(1, None), (0, None)], [(0, None), (1, (0, 0, 50, 69))], [(0, None), (1, None), (0, None)]):
         rc, out, msg = _normal(lib, batch, views=views)
@@ -206,7 +215,7 @@ def test_request_refusals(lib):
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
     assert "n_views = -1" in lib.mj_last_error(None).decode()
     r.n_views = 2
-    keep_r["views_request"].views = None                     # (the count without the array)
+    r.views = None                                           # (the count without the array)
     assert lib.mj_debug_normalise_request(ctypes.byref(batch), ctypes.byref(r), ctypes.byref(out)) == B.MJ_ERR_INVALID
     assert "n_views = 2" in lib.mj_last_error(None).decode()
 
@@ -217,30 +226,23 @@ def test_mj_view_and_the_request_with_views_are_laid_out_as_the_binding_assumes(
     gcc = shutil.which("gcc")
     assert gcc is not None, "the header is held to a C compiler"
     flags = ["-std=c99", "-Wall", "-Werror", "-pedantic", "-I", str(ROOT / "include")]
-    efields, vfields = [f for f, _ in B.PlanViewsRequestC._fields_], [f for f, _ in B.ViewC._fields_]
-    assert efields == ["request", "views"] and vfields == ["image", "window"]
+    vfields = [f for f, _ in B.ViewC._fields_]
+    assert vfields == ["image", "window"]
     src = tmp_path / "layout.c"
     src.write_text("\n".join(
-        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_views_request zeroed = {{0}, 0};',
-         '  printf("%zu %zu %zu %zu", sizeof(mj_plan_request), offsetof(mj_plan_request, n_slots), offsetof(mj_plan_request, n_views), offsetof(mj_plan_request, output));',
-         '  printf(" %zu", sizeof(mj_plan_views_request));'] +
-        [f'  printf(" %zu", offsetof(mj_plan_views_request, {f}));' for f in efields] + ['  printf(" %zu", sizeof(mj_view));'] +
+        ['#include <stdio.h>', '#include <stddef.h>', '#include "mijpeg.h"', 'int main(void) {', '  mj_plan_request zeroed = {0};',
+         '  printf("%zu", sizeof(mj_view));'] +
         [f'  printf(" %zu", offsetof(mj_view, {f}));' for f in vfields] +
-        ['  printf(" %d\\n", zeroed.views == 0 && zeroed.request.n_views == 0);', '  return 0;', '}']))
+        ['  printf(" %d\\n", zeroed.views == 0 && zeroed.n_views == 0);', '  return 0;', '}']))
     exe = tmp_path / "layout"
     subprocess.run([gcc] + flags + [str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    R = B.PlanRequestC
-    want = ([ctypes.sizeof(R), R.n_slots.offset, R.n_slots.offset + 4, R.output.offset, ctypes.sizeof(B.PlanViewsRequestC)] +
-            [getattr(B.PlanViewsRequestC, f).offset for f in efields] + [ctypes.sizeof(B.ViewC)] + [getattr(B.ViewC, f).offset for f in vfields] + [1])
-    assert got == want
-    # n_views lies in what was padding — the request keeps its size and every other field its offset — and the array's pointer
-    # behind the request's last field
-    assert R.output.offset - R.n_slots.offset == 8 and B.PlanViewsRequestC.views.offset == ctypes.sizeof(R) == R.fill.offset + 8
+    assert got == [ctypes.sizeof(B.ViewC)] + [getattr(B.ViewC, f).offset for f in vfields] + [1]
     assert ctypes.sizeof(B.ViewC) == 20
+    # (the request's own layout, views and n_views included: test_plan_request_host)
     r = B.PlanRequestC()
     r.n_views = 7
-    assert r.n_views == 7 and r.n_slots == 0 and not r.output and not r.slots
+    assert r.n_views == 7 and r.n_slots == 0 and not r.output and not r.slots and not r.views
     header = (ROOT / "include" / "mijpeg.h").read_text()
     assert "int32_t n_views;" in header and "const mj_view *views;" in header
 
