@@ -262,6 +262,7 @@ typedef struct {
 #define MJ_COLOUR_INVERT       9
 #define MJ_COLOUR_GAUSSIAN_BLUR 10
 #define MJ_COLOUR_BOX_BLUR     11
+#define MJ_COLOUR_ADJUST_HUE   13      /* (12 is no kind) */
 typedef struct {
     int32_t kind;               /* MJ_COLOUR_* */
     float value;                /* the factor, bits, threshold or radius; ignored by autocontrast, equalize and invert */
@@ -527,6 +528,18 @@ typedef struct {
      *                          a = a / (6 * (sigma2 - (l + 1) (l + 1)))
      *                          Both take one radius 0 <= value <= 1024 (0: the identity; Pillow's per-axis radii are not offered); the
      *                          fill pixels take part as in every op, and the blur commutes with the mirror
+     *   MJ_COLOUR_ADJUST_HUE   torchvision's F.adjust_hue(im, value) on a PIL image, -0.5 <= value <= 0.5: im.convert("HSV"), H = (H + shift)
+     *                          mod 256 with shift = (int)((double)value * 255) & 255 (truncated toward zero, then wrapped: 0.1 -> 25,
+     *                          -0.1 -> 231, +-0.5 -> 127 / 129), and convert("RGB") — Pillow's Convert.c both ways.  To HSV: V = max; max ==
+     *                          min: H = S = 0; else, in float32, cr = max - min, s = cr / max, rc = (max - r) / cr (gc, bc alike), h =
+     *                          bc - gc where r is the max, else 2.0 + rc - bc where g is, else 4.0 + gc - rc, in double and rounded to
+     *                          float32; h = (float)fmod(h / 6.0 + 1.0, 1.0), H = (int)(h * 255.0), S = (int)(s * 255.0) in double, clipped
+     *                          to a byte.  To RGB: S == 0: V thrice; else hf = (float)H * 6.0 / 255.0 in double, i = floor(hf), f = (float)
+     *                          (hf - i), fs = (float)(S / 255.0), p = round(V * (1.0 - fs)), q = round(V * (1.0 - fs * f)) with fs * f a
+     *                          float32 product, t = round(V * (1.0 - fs * (1.0 - f))), else in double, round half away from zero; i % 6
+     *                          picks (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q).  value 0 is NOT the identity: the round trip through
+     *                          HSV bytes moves most colours by a few units, and torchvision takes it whenever the op is called.  On a
+     *                          one-component output the op is the identity (it still takes up a step)
      * The launches (csrc/colour.hip): the plan's resize launch runs exactly as that of the MJ_DTYPE_U8, unmirrored, identity-slot
      * request would, into a plan-owned canvas buffer in the plan's layout.  Then, for every step s of the longest chain: a histogram
      * launch over the outputs whose op s is contrast, autocontrast or equalize (32-bit bins: LDS atomics, merged into a zeroed
@@ -537,12 +550,14 @@ typedef struct {
      * blur are left out by that launch (which is not made where every output's op s is a blur) and taken by one more: a workgroup holds one component plane of one output in LDS, runs all
      * the passes there and stores the last one as above; a plan whose canvas is too large for that (two planes of ow rounded up to
      * four, times oh, bytes: more than 160 KB) runs one launch per pass through a third plan-owned canvas instead (option MJ_BLUR
-     * forces that route).  r, ww and fw are computed on the host, once per op.  mj_plan_time_resize times
+     * forces that route).  r, ww and fw are computed on the host, once per op.  The three-component outputs whose op s is adjust_hue
+     * are left out in the same way and taken by a launch of their own, four neighbouring pixels per lane, with the second
+     * conversion's per-byte terms (i % 6, f, fs) tabled on the host and held in LDS; the launches see the shift only.  mj_plan_time_resize times
      * these launches too.  mj_host_colour_ops is the host twin.
      * MJ_ERR_INVALID, naming the output: the field without a size ("colour_ops needs a size"), n outside 0..4, a kind that
      * is none of MJ_COLOUR_*, a value that is not finite, posterize bits that are not one of 1..8, a blur radius outside 0..1024
-     * (Pillow takes a negative Gaussian radius; this library refuses it).  Not offered yet: hue (Pillow's HSV
-     * round trip), autocontrast's cutoffs and masks, more than MJ_COLOUR_MAX_OPS ops. */
+     * (Pillow takes a negative Gaussian radius; this library refuses it), an adjust_hue factor outside -0.5..0.5 (torchvision raises
+     * there too).  Not offered yet: autocontrast's cutoffs and masks, more than MJ_COLOUR_MAX_OPS ops. */
     const mj_colour_chain *colour;
     /* The fill bytes of `affine` / `perspective`, beside transform_filter (specified with `affine`; the member lies here, last, so that
      * the request has no hole).  DEFAULT zeros.  One byte per OUTPUT component; set without either array: MJ_ERR_INVALID. */

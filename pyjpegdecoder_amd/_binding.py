@@ -36,8 +36,8 @@ MJ_MODE_NATIVE, MJ_MODE_L, MJ_MODE_RGB = 0, 1, 3
 # colour operations (mj_plan_request.colour): the ops by name (tools/colour_model.py: OPS), MJ_COLOUR_*
 MJ_COLOUR_MAX_OPS = 4
 COLOUR_OPS = {"brightness": 1, "color": 2, "contrast": 3, "sharpness": 4, "posterize": 5, "solarize": 6, "autocontrast": 7,
-              "equalize": 8, "invert": 9, "gaussian_blur": 10, "box_blur": 11}
-COLOUR_VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "gaussian_blur", "box_blur")        # the ops that take a value
+              "equalize": 8, "invert": 9, "gaussian_blur": 10, "box_blur": 11, "adjust_hue": 13}          # (12 is no kind)
+COLOUR_VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "gaussian_blur", "box_blur", "adjust_hue")        # the ops that take a value
 COLOUR_BLURS = ("gaussian_blur", "box_blur")           # ... whose value is a radius, 0 .. MJ_COLOUR_MAX_RADIUS
 MJ_COLOUR_MAX_RADIUS = 1024
 # the output colour modes by Pillow's name: MJ_MODE_*, which is the component count of the output

@@ -934,7 +934,7 @@ def _colour_chain(chain, where: str) -> Optional[Tuple[tuple, ...]]:
     for op in chain:
         name = op[0]
         if name not in B.COLOUR_OPS:
-            raise ValueError(f"color_ops: {where}unknown op {name!r} (one of {', '.join(B.COLOUR_OPS)}; hue is not offered yet)")
+            raise ValueError(f"color_ops: {where}unknown op {name!r} (one of {', '.join(B.COLOUR_OPS)}; hue is ('adjust_hue', f))")
         if name not in B.COLOUR_VALUED:
             if len(op) != 1:
                 raise ValueError(f"color_ops: {where}{name!r} takes no value (cutoffs and masks are not offered yet), not {op!r}")
@@ -952,6 +952,8 @@ def _colour_chain(chain, where: str) -> Optional[Tuple[tuple, ...]]:
             v = float(min(max(math.ceil(v), 0), 256))
         elif name in B.COLOUR_BLURS and not 0 <= v <= B.MJ_COLOUR_MAX_RADIUS:
             raise ValueError(f"color_ops: {where}{name} takes a radius of 0..{B.MJ_COLOUR_MAX_RADIUS}, not {op[1]!r}")
+        elif name == "adjust_hue" and not -0.5 <= v <= 0.5:          # (torchvision raises there too)
+            raise ValueError(f"color_ops: {where}adjust_hue takes a factor of -0.5..0.5, not {op[1]!r}")
         ops.append((name, v))
     return tuple(ops) or None
 
@@ -965,7 +967,8 @@ def normalize_color_ops(color_ops, size, n_outputs: Optional[int] = None, return
     ``("contrast", f)``, ``("sharpness", f)`` — ``ImageEnhance.<Name>(im).enhance(f)`` —, ``("posterize", bits)`` with 1..8 bits,
     ``("solarize", t)``, ``("autocontrast",)``, ``("equalize",)``, ``("invert",)`` — ``ImageOps.<name>(im[, value])`` —,
     ``("gaussian_blur", radius)``, ``("box_blur", radius)`` with one radius of 0..1024 — ``im.filter(ImageFilter.GaussianBlur(radius))``
-    / ``BoxBlur(radius)``.  An op is always
+    / ``BoxBlur(radius)`` —, ``("adjust_hue", f)`` with -0.5 <= f <= 0.5 — torchvision's ``F.adjust_hue(im, f)`` on a PIL image: Pillow's
+    HSV round trip with ``int(f * 255) & 255`` added to H, the identity on an "L" output and NOT the identity for f = 0.  An op is always
     a tuple whose first element is a string; that is how one chain is told from a list of chains.  The operations need ``size`` and
     do not go with ``return_seams``.  ``n_outputs`` None: what needs no file.  ValueError otherwise."""
     if color_ops is None:
@@ -1503,12 +1506,14 @@ class BatchDecoder:
         ``("contrast", f)``, ``("sharpness", f)``, ``("posterize", bits)``, ``("solarize", t)``, ``("autocontrast",)``,
         ``("equalize",)``, ``("invert",)`` —, each what the one call of Pillow's ``ImageEnhance`` / ``ImageOps`` of that name does,
         ``("gaussian_blur", radius)`` or ``("box_blur", radius)`` with one radius of 0..1024 — ``im.filter(ImageFilter.GaussianBlur(radius))``
-        / ``BoxBlur(radius)``, the random blur of the SimCLR / MoCo / BYOL / DINO recipes.
+        / ``BoxBlur(radius)``, the random blur of the SimCLR / MoCo / BYOL / DINO recipes —, or ``("adjust_hue", f)`` with
+        -0.5 <= f <= 0.5: torchvision's ``F.adjust_hue`` on a PIL image, the fourth knob of ``ColorJitter`` (Pillow's HSV round trip
+        with ``int(f * 255) & 255`` added to H; f = 0 is that round trip, not the identity; the identity on an "L" output).
         The order is decode, mode, orientation, affine, window, resize / place / fill, colour ops, mirror, element type
         (torchvision's: crop, flip, jitter, ToTensor, Normalize — every op commutes with the flip): output k is its chain applied to
         the uint8 canvas the call gives without the argument, without ``mirror`` and with ``dtype="uint8"`` — fill pixels
         included —, as a Pillow image of the output's mode, bit for bit; then the mirror and the element type.  An output whose
-        chain is None or empty is the output of the call without the argument.  Not with ``return_seams``; hue, autocontrast's
+        chain is None or empty is the output of the call without the argument.  Not with ``return_seams``; autocontrast's
         cutoffs and masks, and more than four ops are not offered yet."""
         mode = normalize_mode(mode)
         if mode is not None and return_seams:

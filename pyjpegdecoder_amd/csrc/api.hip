@@ -378,7 +378,7 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
     if (p->colour) {
         mj::ColourArgs c = p->co;
         c.dst = p->last_rgb;
-        MJ_HIP(p->ctx, mj::launch_colour(s, c, p->co_blur));
+        MJ_HIP(p->ctx, mj::launch_colour(s, c, p->co_blur, p->co_hue));
     }
     return MJ_OK;
 }
@@ -649,7 +649,7 @@ int mj_plan_time_colour(mj_plan *p, int iters, float *ms_out, int64_t *canvas_by
     if (int rc = plan_ready(p, s)) return rc;
     mj::ColourArgs c = p->co;
     c.dst = p->last_rgb;
-    const int rc = time_launches(ctx, s, 1, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_colour(s, c, p->co_blur)); return MJ_OK; }, ms_out);
+    const int rc = time_launches(ctx, s, 1, iters, [&]() -> int { MJ_HIP(ctx, mj::launch_colour(s, c, p->co_blur, p->co_hue)); return MJ_OK; }, ms_out);
     if (canvas_bytes) *canvas_bytes = (int64_t)c.n_outputs * c.ow * c.oh * c.C;
     return rc != MJ_OK ? rc : mark_done(p, s);
 }

@@ -5,7 +5,7 @@
 //
 // The arithmetic is Pillow's (tools/colour_model.py restates it; include/mijpeg.h has the rules), and it is written once, in
 // mijpeg_internal.h, for the kernels and for the host twin (mj_host_colour_ops): colour_blend, colour_smooth,
-// colour_table_entry, blur_pixel.  float32 and double operations round one by one (the library is compiled with -ffp-contract=off).
+// colour_table_entry, blur_pixel, colour_hue.  float32 and double operations round one by one (the library is compiled with -ffp-contract=off).
 //
 // Per step s of the plan's longest chain, up to three launches, and one more (or one per pass) where a chain blurs:
 //   k_colour_hist    only where some output's op s is contrast, autocontrast or equalize, over those outputs: a workgroup counts
@@ -21,6 +21,8 @@
 //   k_colour_blur    only where some output's op s is gaussian_blur or box_blur, over those outputs, which k_colour_apply leaves out:
 //                    a workgroup holds one component plane of one output in LDS and runs all the passes there; on plans whose canvas
 //                    LDS does not hold, k_colour_blur_pass instead, one launch per pass through a third canvas (further down)
+//   k_colour_hue     only where some output of three components has adjust_hue as its op s, over those outputs, which k_colour_apply
+//                    leaves out as it does blur outputs: four neighbouring pixels per lane through colour_hue (further down)
 // Everything addresses a canvas through a pixel's place p and two strides (DevColourOutput's comment), so that one kernel serves
 // the four layouts.  The statistics never leave the device and nothing waits for the host.
 #include <math.h>
@@ -182,11 +184,65 @@ __global__ __launch_bounds__(256) void k_colour_apply(const ColourArgs a, const 
             r[c] = colour_blend((int)colour_smooth(nb), (int)v[c], o.value[step]);
         }
     }
-    // (an output whose op is a blur is the blur launch's.  Asked here, behind the loads and the op, and not on top: the code of
-    // every other output stays close to what it was; the price is that a blur output's pixel is read for nothing — launch_colour_t
-    // does not launch this kernel for a step whose outputs are all blurs)
-    if (colour_is_blur(kind)) return;
+    // (an output whose op is a blur is the blur launch's, one of three components whose op is adjust_hue the hue launch's.  Asked
+    // here, behind the loads and the op, and not on top: the code of every other output stays close to what it was; the price is
+    // that such an output's pixel is read for nothing — launch_colour_t does not launch this kernel for a step whose outputs are
+    // all another launch's)
+    if (colour_is_elsewhere(kind, C)) return;
     colour_store<C, C>(a, o, step, k, p, x, y, 0, r);
+}
+
+// ---- adjust_hue (MJ_COLOUR_ADJUST_HUE) on three components: colour_hue of every pixel of the step's hue outputs ----------------------
+// Not a branch of k_colour_apply: the op carries fp64 and three float divisions, and its registers would be charged to every output
+// of every chain.  A lane takes four neighbouring pixels, places p0 .. p0 + 3 — twelve consecutive bytes of an interleaved canvas,
+// four of each plane of a planar one: three dwords either way, loaded as such (an image starts at a byte offset of k * npix * 3,
+// so the dwords are not aligned in general; global loads need not be) —, and stores pixel by pixel through colour_store.  The last
+// lane of a canvas whose pixels are no multiple of four loads its one to three pixels byte by byte: nothing is read beyond the
+// canvas.  The tables come from the plan's copy into LDS once per workgroup.
+__global__ __launch_bounds__(256) void k_colour_hue(const ColourArgs a, const ColourHueArgs h, const int step) {
+    __shared__ float tf[256], tfs[256];
+    __shared__ uint8_t tsext[256];
+    const int64_t npix = (int64_t)a.ow * a.oh, quads = (npix + 3) >> 2, per_output = (quads + 255) / 256;
+    const int64_t wg = workgroup_index();
+    const int first = h.first[step], n_list = h.first[step + 1] - first;
+    if (wg >= n_list * per_output) return;
+    const int t = threadIdx.x;
+    tf[t] = h.tables->f[t]; tfs[t] = h.tables->fs[t]; tsext[t] = h.tables->sextant[t];
+    __syncthreads();
+    const int64_t k = h.list[first + (int)(wg / per_output)], p0 = ((wg % per_output) * 256 + t) * 4;
+    if (p0 >= npix) return;
+    const DevColourOutput &o = a.outputs[k];
+    const int shift = o.ivalue[step];
+    const bool rowmajor = (a.layout & 1) != 0, planar = a.layout >= 2;
+    const unsigned char *src = a.canvas[step & 1] + k * npix * 3;
+    const int n = npix - p0 < 4 ? (int)(npix - p0) : 4;
+    unsigned v[4][3];
+    if (n == 4) {
+        uint32_t d[3];
+        if (planar) for (int c = 0; c < 3; ++c) __builtin_memcpy(&d[c], src + c * npix + p0, 4);
+        else __builtin_memcpy(d, src + p0 * 3, 12);
+        for (int j = 0; j < 4; ++j)
+            for (int c = 0; c < 3; ++c) {         // (byte j of dword c, or byte 3 j + c of the twelve: both with constant indices)
+                const int byte = j * 3 + c;
+                v[j][c] = (planar ? d[c] >> (8 * j) : d[byte >> 2] >> (8 * (byte & 3))) & 0xFFu;
+            }
+    } else {
+        for (int j = 0; j < 3; ++j)
+            for (int c = 0; c < 3; ++c) v[j][c] = j < n ? src[planar ? c * npix + p0 + j : (p0 + j) * 3 + c] : 0u;
+        v[3][0] = v[3][1] = v[3][2] = 0;
+    }
+    // (x, y) of the first pixel by division, of the next ones by stepping along the stored axis
+    const int len = rowmajor ? a.ow : a.oh;
+    int major = (int)(p0 / len), minor = (int)(p0 % len);
+    // (unrolled: the four pixels stay in registers — a rolled loop indexes v[] by a variable, which puts the array into LDS)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j >= n) break;
+        unsigned r[3];
+        colour_hue(v[j][0], v[j][1], v[j][2], shift, tf, tfs, tsext, r);
+        colour_store<3, 3>(a, o, step, k, p0 + j, rowmajor ? minor : major, rowmajor ? major : minor, 0, r);
+        if (++minor == len) { minor = 0; ++major; }
+    }
 }
 
 // ---- the blurs (MJ_COLOUR_GAUSSIAN_BLUR, MJ_COLOUR_BOX_BLUR): passes of blur_pixel along the width, then along the height ----------
@@ -295,7 +351,7 @@ dim3 grid_for(int64_t total) {
 }
 
 template <int C>
-hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b) {
+hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b, const ColourHueArgs &h) {
     const int64_t npix = (int64_t)a.ow * a.oh;
     static OncePerDevice attr_once;
     attr_once.run([&] {
@@ -309,9 +365,9 @@ hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a, const Colour
             hipLaunchKernelGGL((k_colour_hist<C>), grid_for(n_list * chunks), dim3(256), 0, stream, a, s);
         }
         if (a.tables_at >> s & 1) hipLaunchKernelGGL((k_colour_tables<C>), grid_for(a.n_outputs), dim3(64), 0, stream, a, s);
-        const int n_blur = b.first[s + 1] - b.first[s];
-        // (k_colour_apply reads a blur output's pixel before it returns: a step whose outputs are ALL blurs goes without the launch)
-        if (n_blur < a.n_outputs) hipLaunchKernelGGL((k_colour_apply<C>), grid_for(a.n_outputs * ((npix + 255) / 256)), dim3(256), 0, stream, a, s);
+        const int n_blur = b.first[s + 1] - b.first[s], n_hue = h.first[s + 1] - h.first[s];
+        // (k_colour_apply reads a blur or hue output's pixel before it returns: a step whose outputs are ALL such goes without the launch)
+        if (n_blur + n_hue < a.n_outputs) hipLaunchKernelGGL((k_colour_apply<C>), grid_for(a.n_outputs * ((npix + 255) / 256)), dim3(256), 0, stream, a, s);
         if (n_blur > 0 && b.lds) {
             const int dwords = b.lds / 8;
             hipLaunchKernelGGL((k_colour_blur<C>), grid_for((int64_t)n_blur * C), dim3((unsigned)std::min(1024, (dwords + 63) & ~63)), (size_t)b.lds, stream, a, b, s);
@@ -319,6 +375,8 @@ hipError_t launch_colour_t(hipStream_t stream, const ColourArgs &a, const Colour
             for (int pass = 0; pass < b.passes[s]; ++pass)
                 hipLaunchKernelGGL((k_colour_blur_pass<C>), grid_for(n_blur * ((npix + 255) / 256)), dim3(256), 0, stream, a, b, s, pass);
         }
+        if constexpr (C == 3)
+            if (n_hue > 0) hipLaunchKernelGGL(k_colour_hue, grid_for(n_hue * (((npix + 3) / 4 + 255) / 256)), dim3(256), 0, stream, a, h, s);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -342,6 +400,15 @@ void colour_host_op(const uint8_t *src, int w, int h, const mj_colour_op &op, ui
             cur.swap(next);
         }
         memcpy(out, cur.data(), (size_t)npix * C);
+        return;
+    }
+    if (kind == MJ_COLOUR_ADJUST_HUE && C == 3) {
+        static const HueTables tables = colour_hue_tables();
+        for (int64_t p = 0; p < npix; ++p) {
+            unsigned r[3];
+            colour_hue(src[p * 3], src[p * 3 + 1], src[p * 3 + 2], iv, tables.f, tables.fs, tables.sextant, r);
+            for (int c = 0; c < 3; ++c) out[p * 3 + c] = (uint8_t)r[c];
+        }
         return;
     }
     if (colour_is_table(kind)) {
@@ -391,10 +458,11 @@ const char *colour_fault(const mj_colour_chain &c) {
     if (c.n < 0 || c.n > MJ_COLOUR_MAX_OPS) return "a chain has 0..MJ_COLOUR_MAX_OPS ops";
     for (int s = 0; s < c.n; ++s) {
         const mj_colour_op &op = c.op[s];
-        if (op.kind < MJ_COLOUR_BRIGHTNESS || op.kind > MJ_COLOUR_BOX_BLUR) return "an op's kind is none of MJ_COLOUR_*";
-        const bool valued = op.kind <= MJ_COLOUR_SOLARIZE || colour_is_blur(op.kind);
+        if (op.kind < MJ_COLOUR_BRIGHTNESS || (op.kind > MJ_COLOUR_BOX_BLUR && op.kind != MJ_COLOUR_ADJUST_HUE)) return "an op's kind is none of MJ_COLOUR_*";
+        const bool valued = op.kind <= MJ_COLOUR_SOLARIZE || colour_is_blur(op.kind) || op.kind == MJ_COLOUR_ADJUST_HUE;
         if (valued && !std::isfinite(op.value)) return "an op's value is not finite";
         if (colour_is_blur(op.kind) && !(op.value >= 0.0f && op.value <= kBlurMaxRadius)) return "a blur takes a radius of 0..1024";
+        if (op.kind == MJ_COLOUR_ADJUST_HUE && !(op.value >= -0.5f && op.value <= 0.5f)) return "adjust_hue takes a factor of -0.5..0.5";
         if (op.kind == MJ_COLOUR_POSTERIZE && !(op.value >= 1.0f && op.value <= 8.0f && op.value == floorf(op.value))) return "posterize takes 1..8 bits";
     }
     return nullptr;
@@ -404,6 +472,8 @@ int colour_ivalue(const mj_colour_op &op) {
     if (op.kind == MJ_COLOUR_POSTERIZE) return ~((1 << (8 - (int)op.value)) - 1) & 0xFF;
     if (op.kind == MJ_COLOUR_SOLARIZE) return (int)std::min(std::max(ceilf(op.value), 0.0f), 256.0f);
     if (colour_is_blur(op.kind)) return colour_blur_pass(op).r;
+    // torchvision's np.array(f * 255).astype(np.uint8): the double product truncated toward zero, then wrapped
+    if (op.kind == MJ_COLOUR_ADJUST_HUE) return (int)((double)op.value * 255) & 255;
     return 0;
 }
 
@@ -426,9 +496,9 @@ BlurPass colour_blur_pass(const mj_colour_op &op) {
     return b;
 }
 
-hipError_t launch_colour(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b) {
+hipError_t launch_colour(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b, const ColourHueArgs &h) {
     if (a.n_outputs <= 0 || a.steps <= 0) return hipSuccess;
-    return a.C == 3 ? launch_colour_t<3>(stream, a, b) : launch_colour_t<1>(stream, a, b);
+    return a.C == 3 ? launch_colour_t<3>(stream, a, b, h) : launch_colour_t<1>(stream, a, b, h);
 }
 
 }  // namespace mj

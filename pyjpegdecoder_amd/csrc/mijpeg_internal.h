@@ -525,7 +525,7 @@ hipError_t launch_perspective(hipStream_t stream, const PerspectiveArgs &a, int 
 // ---- colour.hip: colour operations on the finished canvas (mj_plan_request.colour; tools/colour_model.py)
 // One output of a plan with colour operations: its chain (n ops; value: the factor of brightness, color, contrast and sharpness;
 // ivalue: posterize's MASK and solarize's clamped threshold, as integers — colour_ivalue; a blur's r, with ww and fw beside it —
-// colour_blur_pass), where its elements go in the caller's array (dst_off, in ELEMENTS) and whether it is mirrored.
+// colour_blur_pass; adjust_hue's shift, the only thing the launches see of its factor), where its elements go in the caller's array (dst_off, in ELEMENTS) and whether it is mirrored.
 struct DevColourOutput {
     int64_t dst_off;
     int32_t n, mirror;
@@ -560,6 +560,14 @@ struct ColourBlurArgs {
     int32_t first[5];
     int32_t passes[4];
     int32_t lds;
+};
+// What the hue launch takes beside ColourArgs.  list[first[s] .. first[s + 1]): the outputs of three components whose op s is
+// adjust_hue (the plan's list array, behind the blur lists); tables: the plan's copy of colour_hue_tables()
+struct HueTables;
+struct ColourHueArgs {
+    const int32_t *list;
+    const HueTables *tables;
+    int32_t first[5];
 };
 constexpr int kColourHistPixels = 4096;       // pixels of a canvas one workgroup of the histogram launch counts
 constexpr int kBlurLdsMax = 160 * 1024;       // the LDS of a gfx950 workgroup: what two planes of a canvas must fit in
@@ -597,8 +605,13 @@ __host__ __device__ inline uint32_t blur_pixel(const uint8_t *line, int64_t stri
 __host__ __device__ inline bool colour_is_blur(int kind) { return kind == MJ_COLOUR_GAUSSIAN_BLUR || kind == MJ_COLOUR_BOX_BLUR; }
 // passes along each axis
 __host__ __device__ inline int colour_blur_passes(int kind) { return kind == MJ_COLOUR_GAUSSIAN_BLUR ? 3 : 1; }
+// whether an output of C components whose op is `kind` is another launch's than k_colour_apply's: a blur, or adjust_hue on three
+// components (on one component adjust_hue is the identity: k_colour_apply's copy)
+__host__ __device__ inline bool colour_is_elsewhere(int kind, int C) { return colour_is_blur(kind) || (kind == MJ_COLOUR_ADJUST_HUE && C == 3); }
 // whether an op is a look-up table per component / takes a histogram
-__host__ __device__ inline bool colour_is_table(int kind) { return kind != MJ_COLOUR_COLOR && kind != MJ_COLOUR_SHARPNESS && kind != 0 && !colour_is_blur(kind); }
+__host__ __device__ inline bool colour_is_table(int kind) {
+    return kind != MJ_COLOUR_COLOR && kind != MJ_COLOUR_SHARPNESS && kind != 0 && !colour_is_blur(kind) && kind != MJ_COLOUR_ADJUST_HUE;
+}
 __host__ __device__ inline bool colour_needs_hist(int kind) { return kind == MJ_COLOUR_CONTRAST || kind == MJ_COLOUR_AUTOCONTRAST || kind == MJ_COLOUR_EQUALIZE; }
 // Entry i of a table-shaped op's table for one component.  st: that component's histogram, scanned (ops that take one) — lo, hi
 // its first and last non-empty bins, nz how many are non-empty, last the last one's count, total the sum of all —, with mean
@@ -627,15 +640,74 @@ __host__ __device__ inline unsigned colour_table_entry(int kind, float value, in
     }
     return (unsigned)i;
 }
+// adjust_hue (MJ_COLOUR_ADJUST_HUE; tools/colour_model.py: rgb_to_hsv, hsv_to_rgb): Pillow's Convert.c both ways around H + shift.
+// What the second conversion makes of one byte alone is tabled — by the H byte: hf = (float)H * 6.0 / 255.0 in double, its floor's
+// i % 6 (sextant) and f = (float)(hf - i); by the S byte: fs = (float)(S / 255.0) —, which takes every division out of it
+struct HueTables { float f[256]; float fs[256]; uint8_t sextant[256]; };
+inline HueTables colour_hue_tables() {
+    HueTables t;
+    for (int b = 0; b < 256; ++b) {
+        const double hf = (double)(float)b * 6.0 / 255.0, i = floor(hf);
+        t.f[b] = (float)(hf - i); t.sextant[b] = (uint8_t)((int)i % 6);
+        t.fs[b] = (float)((double)b / 255.0);
+    }
+    return t;
+}
+// rgb2hsv_row of one pixel.  Of rc, gc, bc = (float)(max - component) / cr only the two the branch takes are divided: h = base + a - b
+// in double with base 0 (r is the max: bc - gc, which a float subtraction rounds alike), 2 (g: rc - bc) or 4 (gc - rc).  h / 6 + 1
+// lies in [5 / 6, 11 / 6], where fmod(., 1.0) is the subtraction of 1 from what is not below it, and exact
+__host__ __device__ inline void colour_rgb_to_hsv(unsigned r, unsigned g, unsigned b, unsigned &H, unsigned &S, unsigned &V) {
+    const unsigned maxc = r > g ? (r > b ? r : b) : (g > b ? g : b), minc = r < g ? (r < b ? r : b) : (g < b ? g : b);
+    V = maxc; H = S = 0;
+    if (maxc == minc) return;
+    const float cr = (float)(int)(maxc - minc), s = cr / (float)(int)maxc;
+    const unsigned na = r == maxc ? maxc - b : g == maxc ? maxc - r : maxc - g, nb = r == maxc ? maxc - g : g == maxc ? maxc - b : maxc - r;
+    const double base = r == maxc ? 0.0 : g == maxc ? 2.0 : 4.0;
+    const float fa = (float)(int)na / cr, fb = (float)(int)nb / cr;
+    const float h = (float)((base + (double)fa) - (double)fb);
+    double w = (double)h / 6.0 + 1.0;
+    if (w >= 1.0) w -= 1.0;
+    const int ih = (int)((double)(float)w * 255.0), is = (int)((double)s * 255.0);
+    H = (unsigned)(ih > 255 ? 255 : ih); S = (unsigned)(is > 255 ? 255 : is);
+}
+// C's round of a double in 0 .. 255 (x - trunc(x) is exact)
+__host__ __device__ inline unsigned colour_hue_round(double x) {
+    const double t = trunc(x);
+    return (unsigned)(int)(x - t >= 0.5 ? t + 1.0 : t);
+}
+// hsv2rgb of one pixel, the tables' three entries given.  p = round(V * (1.0 - fs)); an odd sextant takes q = round(V * (1.0 - fs * f))
+// — a float product —, an even one t = round(V * (1.0 - fs * (1.0 - f))) — in double —: u is the one of them this sextant has
+__host__ __device__ inline void colour_hsv_to_rgb(unsigned S, unsigned V, int sextant, float f, float fs, unsigned *rgb) {
+    rgb[0] = rgb[1] = rgb[2] = V;
+    if (S == 0) return;
+    const double v = (double)(int)V, dfs = (double)fs;
+    const unsigned p = colour_hue_round(v * (1.0 - dfs));
+    const unsigned u = colour_hue_round(v * (1.0 - (sextant & 1 ? (double)(fs * f) : dfs * (1.0 - (double)f))));
+    switch (sextant) {
+    case 0: rgb[1] = u; rgb[2] = p; break;
+    case 1: rgb[0] = u; rgb[2] = p; break;
+    case 2: rgb[0] = p; rgb[2] = u; break;
+    case 3: rgb[0] = p; rgb[1] = u; break;
+    case 4: rgb[0] = u; rgb[1] = p; break;
+    default: rgb[1] = p; rgb[2] = u; break;
+    }
+}
+// adjust_hue of one pixel: to HSV, H + shift mod 256, and back (tf, tfs, tsext: HueTables' arrays, wherever they lie)
+__host__ __device__ inline void colour_hue(unsigned r, unsigned g, unsigned b, int shift, const float *tf, const float *tfs, const uint8_t *tsext, unsigned *rgb) {
+    unsigned H, S, V;
+    colour_rgb_to_hsv(r, g, b, H, S, V);
+    H = (H + (unsigned)shift) & 255u;
+    colour_hsv_to_rgb(S, V, tsext[H], tf[H], tfs[S], rgb);
+}
 // what mj_plan_request.colour and mj_host_colour_ops refuse of one chain: nullptr, or the reason
 const char *colour_fault(const mj_colour_chain &c);
-// the integer form of an op's value (posterize: the mask, solarize: the clamped threshold, a blur: r; else 0)
+// the integer form of an op's value (posterize: the mask, solarize: the clamped threshold, a blur: r, adjust_hue: the shift; else 0)
 int colour_ivalue(const mj_colour_op &op);
 // a blur's pass: r, ww and fw of its box radius (gaussian_blur: the radius of the box whose three passes stand for it)
 struct BlurPass { int32_t r; uint32_t ww, fw; };
 BlurPass colour_blur_pass(const mj_colour_op &op);
 // the launches of one execute: the canvas in a.canvas[0] -> a.dst
-hipError_t launch_colour(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b);
+hipError_t launch_colour(hipStream_t stream, const ColourArgs &a, const ColourBlurArgs &b, const ColourHueArgs &h);
 // ---- output colour mode (tools/mode_model.py)
 // Pillow's convert("L") of one RGB pixel: (19595 R + 38470 G + 7471 B + 32768) >> 16 — at most 65536 * 255 + 32768, far inside 32 bits
 __host__ __device__ inline unsigned mode_luma(unsigned r, unsigned g, unsigned b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }

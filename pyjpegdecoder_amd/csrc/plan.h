@@ -308,8 +308,10 @@ struct mj_plan {
     uint8_t *d_co_tables = nullptr;
     mj::DevColourOutput *d_co_outputs = nullptr;
     int32_t *d_co_list = nullptr;
+    mj::HueTables *d_hue_tables = nullptr;      // colour_hue_tables() (ColourHueArgs::tables), only on plans with a hue launch
     mj::ColourArgs co{};
     mj::ColourBlurArgs co_blur{};
+    mj::ColourHueArgs co_hue{};
     int32_t n_views = 0;                       // a plan with views (mj_plan_request.views): its resize and reduce records are per view (0: per image)
     std::vector<std::array<int32_t, 2>> h_view_size;   // ... every view's window, stored axes: width, height (mj_debug_reduce_shape)
     std::vector<std::array<int32_t, 6>> h_rd;  // per image (view), stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)

@@ -297,7 +297,7 @@ int affine_stage(const PlanRequest &q, mj_plan *p, int CO, std::vector<int64_t> 
 // In: the request (chains checked, some not empty), the plan — its resize launch made for uint8 canvases, output k at canvas k —,
 // CO — the output's components — and the output's element size.  Out: the plan's colour launches (p->co): one record per output
 // with its chain, its slot's offset in elements and its mirror flag; per step, the outputs that take a histogram and, behind them
-// in the same array, the outputs that are blurred; the two canvases, the histograms, the tables and the output table, all
+// in the same array, the outputs that are blurred and then those of the hue launch; the two canvases, the histograms, the tables and the output table, all
 // plan-owned.  A plan with a blur whose canvas LDS does not hold (or under option MJ_BLUR=passes) owns a third canvas.
 std::vector<uint8_t> output_table(const mj_output_desc &o, int CO, int esize);
 int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
@@ -306,6 +306,7 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     const int64_t npix = (int64_t)r.out_width * r.out_height, canvas = (int64_t)n * npix * CO;
     mj::ColourArgs &a = p->co = mj::ColourArgs{};
     mj::ColourBlurArgs &b = p->co_blur = mj::ColourBlurArgs{};
+    mj::ColourHueArgs &h = p->co_hue = mj::ColourHueArgs{};
     std::vector<mj::DevColourOutput> recs((size_t)n);
     std::vector<int32_t> list;
     std::vector<uint32_t> weights((size_t)n * 8, 0);
@@ -338,6 +339,13 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     }
     b.first[MJ_COLOUR_MAX_OPS] = (int32_t)list.size();
     const bool blurs = b.first[MJ_COLOUR_MAX_OPS] > b.first[0];
+    for (int s = 0; s < MJ_COLOUR_MAX_OPS; ++s) {
+        h.first[s] = (int32_t)list.size();
+        for (int k = 0; k < n; ++k)
+            if (CO == 3 && s < recs[(size_t)k].n && recs[(size_t)k].kind[s] == MJ_COLOUR_ADJUST_HUE) list.push_back(k);
+    }
+    h.first[MJ_COLOUR_MAX_OPS] = (int32_t)list.size();
+    const bool hues = h.first[MJ_COLOUR_MAX_OPS] > h.first[0];
     const char *route = mj::opt("MJ_BLUR");
     if (blurs && !(route && !strcmp(route, "passes")) && mj::blur_lds_bytes(r.out_width, r.out_height) <= mj::kBlurLdsMax)
         b.lds = (int32_t)mj::blur_lds_bytes(r.out_width, r.out_height);
@@ -352,6 +360,10 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     if (blurs)
         if (int rc = upload(p, &p->d_blur_weights, weights.data(), weights.size())) return rc;
     if (blurs && !b.lds) MJ_HIP(q.ctx, alloc(p, &p->d_blur_scratch, (size_t)canvas + 64));
+    if (hues) {
+        const mj::HueTables tables = mj::colour_hue_tables();
+        if (int rc = upload(p, &p->d_hue_tables, &tables, 1)) return rc;
+    }
     if (out_esize > 1) {
         const std::vector<uint8_t> lut = output_table(*r.output, CO, out_esize);
         if (int rc = upload(p, &p->d_rz_lut, lut.data(), lut.size())) return rc;
@@ -360,6 +372,7 @@ int colour_stage(const PlanRequest &q, mj_plan *p, int CO, int out_esize) {
     a.canvas[0] = p->d_canvas; a.canvas[1] = p->d_canvas + canvas;
     a.hist = p->d_co_hist; a.tables = p->d_co_tables; a.outputs = p->d_co_outputs; a.hist_list = p->d_co_list;
     b.list = p->d_co_list; b.weights = p->d_blur_weights; b.scratch = p->d_blur_scratch;
+    h.list = p->d_co_list; h.tables = p->d_hue_tables;
     a.n_outputs = n; a.ow = r.out_width; a.oh = r.out_height; a.C = CO; a.layout = p->layout; a.esize = out_esize;
     p->colour = true;
     return MJ_OK;

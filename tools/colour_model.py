@@ -8,6 +8,7 @@ element type (tools/normalize_model.py).  An op is a tuple whose first element i
     ("brightness", f)  ("color", f)  ("contrast", f)  ("sharpness", f)      ImageEnhance.<Name>(im).enhance(f)
     ("posterize", bits)  ("solarize", t)  ("autocontrast",)  ("equalize",)  ("invert",)      ImageOps.<name>(im[, value])
     ("gaussian_blur", radius)  ("box_blur", radius)      im.filter(ImageFilter.GaussianBlur(radius) / BoxBlur(radius)), 0 <= radius <= 1024
+    ("adjust_hue", f)      torchvision's F.adjust_hue(im, f), -0.5 <= f <= 0.5: the H of im.convert("HSV") plus hue_shift(f), and back
 
 Images are row-major: (H, W, 3) for "RGB", (H, W) for "L".
 
@@ -17,6 +18,9 @@ look-up table per band; three of them — contrast's mean, autocontrast and equa
 The two blurs are Pillow's BoxBlur.c: passes of one box filter with a fractional radius along the width, then along the height
 (box_pass) — one pass each for box_blur, three each for gaussian_blur with the box radius gaussian_box_radius gives.  Every pass
 stores bytes, and the next pass reads those bytes.
+
+adjust_hue is Pillow's Convert.c both ways (rgb_to_hsv, hsv_to_rgb) around a byte addition that wraps.  The round trip alone — factor
+0 — changes most colours: torchvision takes it whenever the op is called, and so does this model.  An "L" image is returned as it is.
 """
 import math
 
@@ -27,6 +31,7 @@ from tools import mode_model
 MAX_OPS = 4
 OPS = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "autocontrast", "equalize", "invert", "gaussian_blur", "box_blur")
 VALUED = ("brightness", "color", "contrast", "sharpness", "posterize", "solarize", "gaussian_blur", "box_blur")       # ops that take a value
+TORCHVISION_OPS = ("adjust_hue",)       # the op that is torchvision's and not Pillow's (OPS stays Pillow's own; it takes a value too)
 MAX_RADIUS = 1024
 
 
@@ -155,6 +160,70 @@ def blur(a: np.ndarray, fr, passes: int) -> np.ndarray:
     return a
 
 
+def rgb_to_hsv(a: np.ndarray) -> np.ndarray:
+    """im.convert("HSV") of uint8 (..., 3) (Convert.c: rgb2hsv_row).  V = max; max == min: H = S = 0.  Else, in float32 unless said
+    otherwise, cr = max - min, s = cr / max, rc = (max - r) / cr (gc, bc alike); h = bc - gc where r is the max, else 2.0 + rc - bc
+    where g is, else 4.0 + gc - rc — evaluated in double and rounded to float32 —; h = fl32(fmod(h / 6.0 + 1.0, 1.0)) in double;
+    H = (int)(h * 255.0), S = (int)(s * 255.0) in double, clipped to a byte."""
+    f, d = np.float32, np.float64
+    a = np.asarray(a, dtype=np.uint8)
+    r, g, b = (a[..., c].astype(np.int32) for c in range(3))
+    maxc, minc = np.maximum(np.maximum(r, g), b), np.minimum(np.minimum(r, g), b)
+    flat = maxc == minc
+    cr = np.where(flat, 1, maxc - minc).astype(f)
+    s = cr / np.where(flat, 1, maxc).astype(f)
+    rc, gc, bc = ((maxc - v).astype(f) / cr for v in (r, g, b))
+    rc, gc, bc = rc.astype(d), gc.astype(d), bc.astype(d)
+    h = np.where(r == maxc, bc - gc, np.where(g == maxc, 2.0 + rc - bc, 4.0 + gc - rc)).astype(f)
+    h = np.fmod(h.astype(d) / 6.0 + 1.0, 1.0).astype(f)
+    H = np.clip((h.astype(d) * 255.0).astype(np.int32), 0, 255)
+    S = np.clip((s.astype(d) * 255.0).astype(np.int32), 0, 255)
+    return np.stack([np.where(flat, 0, H), np.where(flat, 0, S), maxc], axis=-1).astype(np.uint8)
+
+
+def hsv_to_rgb(a: np.ndarray) -> np.ndarray:
+    """Image.merge("HSV", ...).convert("RGB") of uint8 (..., 3) (Convert.c: hsv2rgb).  S == 0: R = G = B = V.  Else hf = fl32(H) * 6.0
+    / 255.0 in double, i = floor(hf), f = fl32(hf - i), fs = fl32(S / 255.0); p = round(V * (1.0 - fs)), q = round(V * (1.0 - fs * f))
+    — the product fs * f a float32 one —, t = round(V * (1.0 - fs * (1.0 - f))), otherwise in double, round half away from zero, clipped
+    to a byte; i % 6 picks (V, t, p), (q, V, p), (p, V, t), (p, q, V), (t, p, V), (V, p, q)."""
+    f32, d = np.float32, np.float64
+    a = np.asarray(a, dtype=np.uint8)
+    H, S, V = a[..., 0], a[..., 1], a[..., 2]
+    hf = H.astype(f32).astype(d) * 6.0 / 255.0
+    i = np.floor(hf)
+    f = (hf - i).astype(f32)
+    fs = (S.astype(d) / 255.0).astype(f32)
+    v = V.astype(d)
+
+    def rnd(x):         # (C's round on values that are not negative: x - trunc(x) is exact)
+        t = np.trunc(x)
+        return np.clip(np.where(x - t >= 0.5, t + 1, t), 0, 255).astype(np.uint8)
+    p = rnd(v * (1.0 - fs.astype(d)))
+    q = rnd(v * (1.0 - (fs * f).astype(d)))
+    t = rnd(v * (1.0 - fs.astype(d) * (1.0 - f.astype(d))))
+    k = i.astype(np.int32) % 6
+    pick = lambda c0, c1, c2, c3, c4, c5: np.choose(k, [c0, c1, c2, c3, c4, c5])       # noqa: E731
+    out = np.stack([pick(V, q, p, p, t, V), pick(t, V, V, q, p, p), pick(p, p, t, V, V, q)], axis=-1)
+    return np.where((S == 0)[..., None], V[..., None], out).astype(np.uint8)
+
+
+def hue_shift(f: float) -> int:
+    """what adjust_hue adds to the H byte: int(f * 255) & 255 — the product a double's, truncated toward zero, then wrapped (what
+    torchvision's np.array(f * 255).astype(np.uint8) gives on x86-64)"""
+    return int(float(f) * 255) & 255
+
+
+def adjust_hue(a: np.ndarray, f: float) -> np.ndarray:
+    """torchvision's F.adjust_hue on a PIL image: "L" as it is; "RGB" to HSV, H + hue_shift(f) mod 256, and back — also for f = 0"""
+    if not -0.5 <= f <= 0.5:
+        raise ValueError(f"adjust_hue takes a factor of -0.5..0.5, not {f!r}")
+    if a.ndim == 2:
+        return a
+    hsv = rgb_to_hsv(a)
+    hsv[..., 0] = (hsv[..., 0].astype(np.int32) + hue_shift(f)) & 255
+    return hsv_to_rgb(hsv)
+
+
 def _per_band(a: np.ndarray, table_of) -> np.ndarray:
     if a.ndim == 2:
         return table_of(np.bincount(a.ravel(), minlength=256))[a]
@@ -165,7 +234,7 @@ def apply_op(a: np.ndarray, op) -> np.ndarray:
     """one op on a uint8 (H, W, 3) or (H, W) image"""
     a = np.ascontiguousarray(a, dtype=np.uint8)
     name = op[0]
-    if name not in OPS or len(op) != (2 if name in VALUED else 1):
+    if name not in OPS + TORCHVISION_OPS or len(op) != (2 if name in VALUED + TORCHVISION_OPS else 1):
         raise ValueError(f"no colour op {op!r}")
     if name == "brightness":
         return blend(np.zeros_like(a), a, op[1])
@@ -188,6 +257,8 @@ def apply_op(a: np.ndarray, op) -> np.ndarray:
         if not 0 <= op[1] <= MAX_RADIUS:
             raise ValueError(f"{name} takes a radius of 0..{MAX_RADIUS}, not {op[1]!r}")
         return blur(a, gaussian_box_radius(op[1]), 3) if name == "gaussian_blur" else blur(a, np.float32(op[1]), 1)
+    if name == "adjust_hue":
+        return adjust_hue(a, op[1])
     return _per_band(a, autocontrast_table if name == "autocontrast" else equalize_table)
 
 

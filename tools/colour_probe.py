@@ -25,10 +25,18 @@ per plan the median and the spread (min .. max).
     call_blur the same for color_ops=[("gaussian_blur", r_k)] per output: against the call without it, and against the uint8 call,
               then a separable Gaussian (sigma = r_k, 13 taps, edges reflected) as two grouped convolutions in torch and the
               normalisation — other bytes than Pillow's again, compared for time only
+    launches_hue / launches_color / launches_jitter_hue   (`--hue`) the colour launches alone for ("adjust_hue", f_k) with f_k drawn per
+              output from U(-0.1, 0.1) as ColorJitter(hue=0.1) does — the hue launch k_colour_hue, four pixels per lane —, for ("color", 1.3)
+              alone — the per-pixel three-component op most like it, one k_colour_apply launch —, and for the whole four-op ColorJitter
+              chain (jitter + that hue); the three-op chain is launches_jitter as ever
+    call_hue  (`--hue`) decode_device end to end with color_ops=[("adjust_hue", f_k)] per output and with the four-op chain, against the
+              call without color_ops and against the uint8 call, then the HSV round trip with h + f_k in float32 and the normalisation
+              in torch on the GPU (torchvision's tensor branch, restated) — that route does NOT give the PIL branch's bytes, which
+              are what a Pillow pipeline trains on; it is compared for time only
     untouched the plain bilinear and bicubic resize launches, the reducing_gap=2.0 reduce launch, the affine launch and the colour
-              launches of the ColorJitter chain, this build against the parent's, with a second parent plan beside the first: what two plans of ONE build differ by
+              launches of the ColorJitter chain (and, with `--hue`, of a blur-only chain), this build against the parent's, with a second parent plan beside the first: what two plans of ONE build differ by
 
-    python tools/colour_probe.py --parent-lib PATH [--n 1024] [--distinct 64] [--reps 12] [--layouts rowmajor,xmajor]
+    python tools/colour_probe.py --parent-lib PATH [--n 1024] [--distinct 64] [--reps 12] [--layouts rowmajor,xmajor] [--hue]
 """
 from __future__ import annotations
 
@@ -52,7 +60,7 @@ JITTER = (("brightness", 1.2), ("contrast", 0.8), ("color", 1.3))
 CHAINS = {"jitter": JITTER, "autocontrast_equalize": (("autocontrast",), ("equalize",))}
 # canvases moved: per step one read and one write (the last write is float16: two), one more read per step with a histogram
 MOVED = {"jitter": 3 + 2 + 2 + 1, "autocontrast_equalize": 2 + 1 + 2 + 2, "blur": 1 + 2, "simclr": 4 + 3 + 2 + 1,
-         "blur_passes": 6 + 5 + 2, "simclr_passes": 3 + 3 + 1 + 6 + 5 + 2}
+         "blur_passes": 6 + 5 + 2, "simclr_passes": 3 + 3 + 1 + 6 + 5 + 2, "hue": 1 + 2, "color": 1 + 2, "jitter_hue": 3 + 2 + 2 + 1 + 2}
 
 
 def main() -> int:
@@ -64,6 +72,7 @@ def main() -> int:
     ap.add_argument("--seed", type=int, default=4242)
     ap.add_argument("--layouts", default="rowmajor,xmajor")
     ap.add_argument("--parent-lib", required=True)
+    ap.add_argument("--hue", action="store_true", help="the adjust_hue points, in the place of the `_padded` and `_passes` ones (the parent build runs none of them and need not have the op)")
     ap.add_argument("--parent-first", action="store_true", help="call: the parent build's route first in every round (the order's share of a difference)")
     args = ap.parse_args()
 
@@ -102,12 +111,17 @@ def main() -> int:
         plans = {name: B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=[chain] * n) for name, chain in CHAINS.items()}
         radii = [float(v) for v in np.random.default_rng(args.seed).uniform(0.1, 2.0, n)]
         blurs = {"blur": [(("gaussian_blur", r),) for r in radii], "simclr": [JITTER + (("gaussian_blur", r),) for r in radii]}
-        for route in (None, "passes"):
+        for route in ((None,) if args.hue else (None, "passes")):
             B.set_option("MJ_BLUR", route)          # (read when a plan is created)
             for name, chains in blurs.items():
                 plans[name + ("_passes" if route else "")] = B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=chains)
         B.set_option("MJ_BLUR", None)
-        for name, chain in CHAINS.items():
+        factors = [float(v) for v in np.random.default_rng(args.seed + 1).uniform(-0.1, 0.1, n)]
+        hues = {"hue": [(("adjust_hue", f),) for f in factors], "color": [(("color", 1.3),)] * n, "jitter_hue": [JITTER + (("adjust_hue", f),) for f in factors]}
+        if args.hue:
+            for name, chains in hues.items():
+                plans[name] = B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=chains)
+        for name, chain in ({} if args.hue else CHAINS).items():
             plans[name + "_padded"] = B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output, colour=[chain] * n,
                                              places=[(112, 63, 56, 80)] * n, fill=(124, 116, 104))
         plans["without"] = B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), output=output)
@@ -200,10 +214,55 @@ def main() -> int:
         emit(layout=lname, point="call_blur", e2e_decode_device_ms={name: summary(xs) for name, xs in times.items()},
              blur_cost_ms=round(statistics.median(times["blur"]) - statistics.median(times["without"]), 3))
 
+        # ---- the whole call with a hue shift per output
+        if args.hue:
+            shifts = torch.tensor(factors, device=dev).view(n, 1, 1)
+
+            def torch_hue_route():              # (torchvision's _rgb2hsv / _hsv2rgb on a float tensor: interleaved layouts, components last)
+                x = pdec.decode_device(files, size=(224, 224)).float() / 255.0
+                r, g, b = x.unbind(dim=3)
+                maxc, minc = x.amax(dim=3), x.amin(dim=3)
+                eqc = maxc == minc
+                cr = maxc - minc
+                ones = torch.ones_like(maxc)
+                s = cr / torch.where(eqc, ones, maxc)
+                crd = torch.where(eqc, ones, cr)
+                rc, gc, bc = (maxc - r) / crd, (maxc - g) / crd, (maxc - b) / crd
+                hr = (maxc == r) * (bc - gc)
+                hg = ((maxc == g) & (maxc != r)) * (2.0 + rc - bc)
+                hb = ((maxc != g) & (maxc != r)) * (4.0 + gc - rc)
+                h = (((hr + hg + hb) / 6.0 + 1.0) % 1.0 + shifts) % 1.0
+                i = torch.floor(h * 6.0)
+                f = h * 6.0 - i
+                i = i.to(torch.int64) % 6
+                v = maxc
+                p, q, t = v * (1.0 - s), v * (1.0 - s * f), v * (1.0 - s * (1.0 - f))
+                pick = torch.stack((torch.stack((v, q, p, p, t, v)), torch.stack((t, v, v, q, p, p)), torch.stack((p, p, t, v, v, q))))
+                x = pick.gather(1, i.expand(3, 1, -1, -1, -1)).squeeze(1).movedim(0, 3)
+                return ((x - mean_t) / std_t).half()
+
+            routes = {"hue": lambda: dec.decode_device(files, color_ops=hues["hue"], **kw),
+                      "jitter_hue": lambda: dec.decode_device(files, color_ops=hues["jitter_hue"], **kw),
+                      "without": lambda: dec.decode_device(files, **kw),
+                      "parent_uint8_then_torch_hue": torch_hue_route}
+            times = {name: [] for name in routes}
+            for r in range(args.e2e_reps + 1):
+                for name, fn in routes.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    if r:
+                        times[name].append((time.perf_counter() - t0) * 1e3)
+            emit(layout=lname, point="call_hue", e2e_decode_device_ms={name: summary(xs) for name, xs in times.items()},
+                 hue_cost_ms=round(statistics.median(times["hue"]) - statistics.median(times["without"]), 3),
+                 jitter_hue_cost_ms=round(statistics.median(times["jitter_hue"]) - statistics.median(times["without"]), 3))
+
         # ---- the launches this change did not mean to touch: this build against the parent's, a second parent plan beside the first
         matrix = rotation_matrix(15.0, (W, H))
         for label, pk in (("bilinear", {}), ("bicubic", {"filter": "bicubic"}), ("gap2_bicubic", {"filter": "bicubic", "reducing_gap": 2.0}),
-                          ("affine_bilinear", {"affine": ([matrix] * n, "bilinear", (0, 0, 0))}), ("colour_jitter", {"colour": [JITTER] * n})):
+                          ("affine_bilinear", {"affine": ([matrix] * n, "bilinear", (0, 0, 0))}), ("colour_jitter", {"colour": [JITTER] * n})) + \
+                ((("colour_blur", {"colour": blurs["blur"]}),) if args.hue else ()):
             plans = {"parent": B.Plan(pctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), **pk),
                      "parent_twin": B.Plan(pctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), **pk),
                      "this": B.Plan(ctx, once.to_c(d_once.data_ptr()), keep, size=(224, 224), **pk)}
