@@ -571,6 +571,33 @@ int mj_host_colour_ops(const uint8_t *src, int32_t w, int32_t h, int32_t ncomp, 
 int mj_plan_create_with(mj_context *ctx, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
 /* The plain plan: exactly mj_plan_create_with(ctx, batch, NULL, out). */
 int mj_plan_create(mj_context *ctx, const mj_batch *batch, mj_plan **out);
+/* A plan derived from a plan: several outputs — sizes, views, modes, filters, transforms, colour chains — from ONE decode.
+ * `parent` is a sized plan of mj_plan_create_with (out_width / out_height set; not a window plan — no rois, no placed windows —,
+ * not an own-size oriented plan, not itself derived): it leaves its decoded images, whole, in a buffer of its own, and everything
+ * behind its decode reads them there.  The derived plan is a second set of exactly those launches — reduce / affine / perspective,
+ * resize, colour — with arguments of its own, over the same decoded images into an output of its own.
+ * `batch`: the batch the parent was made from.  Only its image count, the images' sizes and component counts and the layout are
+ * read, and checked against the parent's (MJ_ERR_INVALID: not the parent's batch); no blob, table or segment is looked at.
+ * `request`: out_width / out_height are required and rois must be NULL (a derived plan's windows are views).  Every other field —
+ * orientations, mode, views / n_views, output, filter, reducing_gap, places, fill, slots, affine / perspective with transform_filter /
+ * transform_fill, colour — means what it means to mj_plan_create_with, is checked and refused as there (same codes, same messages),
+ * and is independent of the parent's request: orientation and mode are applied behind the decode, so a derived plan may differ from
+ * its parent in both.  The derived plan's output equals, bit for bit, that of mj_plan_create_with(ctx, batch, request, ..).
+ * MJ_ERR_INVALID besides: a NULL argument; a parent that has no size, is a window plan or is derived; a request without a size or
+ * with rois.
+ * ORDER: mj_plan_execute(derived, stream, out) queues only those launches.  The caller puts it BEHIND an execute of the parent —
+ * the same stream, or an event — and IN FRONT OF the parent's next execute, which overwrites the images it reads; several plans
+ * derived from one parent may follow one execute of it, in any order.  A derived execute is never replayed from a captured graph.
+ * OWNERSHIP: a derived plan owns its tables, records, canvases, reduce / affine buffers and (rgb_device NULL) its output; the buffer
+ * of decoded images stays the parent's.  Plans are counted and a derived plan holds its parent: mj_plan_destroy of the two in either
+ * order is fine — a destroyed parent must not be used again, but its buffers return to the context's cache only when it and every
+ * plan derived from it have been destroyed (each destroy first waits for that plan's own latest execute).
+ * What a derived plan answers: mj_plan_get_info — rgb_bytes / total_pixels of its output, total_blocks / total_mcus /
+ * entropy_bytes 0; mj_plan_read — its output and a status of 0 per image (the files' statuses are the parent's), MJ_ERR_INVALID
+ * for the coefficient and seam pointers; mj_plan_sync, mj_plan_time_resize / _reduce / _affine / _colour and the mj_debug_*_shape
+ * calls as on any sized plan; MJ_ERR_INVALID from mj_plan_execute_stage1 / _stage2, mj_plan_write_coef, mj_plan_fill_coef,
+ * mj_plan_fill_source (fill the parent's), mj_plan_tune_placement, mj_plan_time_stages / _execute and mj_plan_idct_levels. */
+int mj_plan_derive(mj_plan *parent, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
 /* The host twin of the kernels' mode conversion (no context): n_pixels pixels of src_ncomp (1 or 3) interleaved components into
  * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
  * is neither 1 nor 3, NULL with pixels to convert. */

@@ -55,7 +55,7 @@ EXPORTS = (
     "mj_host_resize_table_filtered", "mj_debug_resize_shape", "mj_host_convert_mode",
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
     "mj_plan_time_reduce", "mj_host_affine", "mj_host_perspective", "mj_plan_time_affine", "mj_debug_reduce_launch", "mj_host_colour_ops", "mj_plan_time_colour",
-    "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables",
+    "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables", "mj_plan_derive",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -210,6 +210,7 @@ def load_library():
     L.mj_context_wait_event.argtypes = [vp, vp]
     L.mj_plan_create.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(vp)]
     L.mj_plan_create_with.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(PlanRequestC), ctypes.POINTER(vp)]
+    L.mj_plan_derive.argtypes = [vp, ctypes.POINTER(BatchC), ctypes.POINTER(PlanRequestC), ctypes.POINTER(vp)]
     L.mj_host_convert_mode.argtypes = [i32, vp, i32, i64, vp]
     L.mj_host_resize_table_filtered.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_debug_resize_shape.argtypes = [vp, ctypes.POINTER(i32)]
@@ -746,6 +747,22 @@ class Plan:
         info = PlanInfoC()
         ctx.check(ctx.lib.mj_plan_get_info(h, ctypes.byref(info)))
         self.info = info
+
+    def derive(self, prep, **kwargs) -> "Plan":
+        """mj_plan_derive: a plan of only the launches behind the decode — with a size, views, mode, filter, ... of its own, the
+        keywords of :func:`plan_request`, ``size`` required and no ``rois`` — that reads THIS plan's decoded images.  ``prep``: the
+        prepared batch this plan was made from (or its mj_batch).  Execute it behind an execute of this plan, on the same stream,
+        and in front of this plan's next one; it holds this plan, so the two may be closed in either order."""
+        batch_c = prep.to_c() if hasattr(prep, "to_c") else prep
+        request, _ = plan_request(getattr(batch_c, "n_images", 0), **kwargs)
+        child = Plan.__new__(Plan)
+        child.ctx, child._keep, child.handle = self.ctx, dict(self._keep, prep=prep), None
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.mj_plan_derive(self.handle, ctypes.byref(batch_c), ctypes.byref(request), ctypes.byref(h)))
+        child.handle = h
+        child.info = PlanInfoC()
+        self.ctx.check(self.ctx.lib.mj_plan_get_info(h, ctypes.byref(child.info)))
+        return child
 
     def execute(self, stream: int = 0, rgb_device: int = 0):
         self.ctx.check(self.ctx.lib.mj_plan_execute(self.handle, stream or None, rgb_device or None))

@@ -654,6 +654,89 @@ def select_view_files(files: Sequence[bytes], views, size, rois=None, return_sea
     return kept, [(pos[i], r) for i, r in entries]
 
 
+def select_union_files(files: Sequence[bytes], groups: Sequence[dict]):
+    """:func:`select_view_files` for a call with ``also``: ``groups`` holds the call's own arguments and every extra group's
+    (:func:`normalize_also`), each with ``views`` and ``size``.  Returns the positions, ascending, of the files that SOME group names
+    — a group without views names every file —; the rest are neither parsed nor decoded."""
+    kept, every = set(), False
+    for k, g in enumerate(groups):
+        try:
+            sel = select_view_files(files, g.get("views"), g.get("size"))
+        except ValueError as e:                 # (the call's own group first, then also[0], also[1], ...)
+            if k == 0:
+                raise
+            raise ValueError(f"also[{k - 1}]: {e}") from None
+        if sel is None:
+            every = True
+        else:
+            kept.update(sel[0])
+    return list(range(len(files))) if every else sorted(kept)
+
+
+# the keys of an entry of ``also``: what is per output and never inherited, and what is the call's unless the entry says otherwise
+ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops")
+ALSO_CALL_WIDE = ("dtype", "normalize", "resample", "mode", "reducing_gap", "fill", "affine_resample", "affine_fill")
+
+
+def normalize_also(also, call: dict, size, rois=None, return_seams: bool = False, host: bool = False) -> Optional[List[dict]]:
+    """``also`` of a call, checked as far as no file is needed: None for a call without extra groups (``None`` or ``[]``), else one dict
+    per extra group with ``size`` and every key of ALSO_PER_OUTPUT and ALSO_CALL_WIDE — the keywords of the call that group alone
+    would be.  An entry of ``also`` is a dict: ``size`` is required; ``views``, ``mirror``, ``resize_to``, ``place``, ``affine``,
+    ``perspective`` and ``color_ops`` are the group's own (None when absent, never the call's); ``dtype``, ``normalize``, ``resample``,
+    ``mode``, ``reducing_gap``, ``fill``, ``affine_resample`` and ``affine_fill`` are the call's (``call``) unless the entry names them.
+    ``orientation`` is per file and the call's, ``rois`` are views, and there are no seam outputs: an entry with one of these, or any
+    other key, is refused, as is ``also`` on a call without ``size``, with ``rois`` or with ``return_seams``.  ValueError naming the
+    entry (``also[1]: ...``) otherwise."""
+    if also is None:
+        return None
+    if not isinstance(also, (list, tuple)):
+        raise ValueError(f"also must be None or a list with one dict per extra group of outputs, not {also!r}")
+    if len(also) == 0:
+        return None
+    if size is None:
+        raise ValueError("also needs size=(width, height): every group of outputs is one array at its own size")
+    if rois is not None:
+        raise ValueError("also and rois do not go together: windows are views, which every group has for itself")
+    if return_seams:
+        raise ValueError("also and return_seams do not go together: the seam outputs are whole images, one per file")
+    refused = {"rois": "windows are views, which every group has for itself", "orientation": "it is per file and the call's",
+               "return_seams": "the seam outputs are whole images, one per file", "also": "groups do not nest"}
+    groups = []
+    for k, entry in enumerate(also):
+        if not isinstance(entry, dict):
+            raise ValueError(f"also[{k}]: an entry is a dict of keywords (size=, views=, ...), not {entry!r}")
+        for key in entry:
+            if key in refused:
+                raise ValueError(f"also[{k}]: {key} is not a key of an entry: {refused[key]}")
+            if key != "size" and key not in ALSO_PER_OUTPUT and key not in ALSO_CALL_WIDE:
+                raise ValueError(f"also[{k}]: unknown key {key!r} (size, {', '.join(ALSO_PER_OUTPUT + ALSO_CALL_WIDE)})")
+        if entry.get("size") is None:
+            raise ValueError(f"also[{k}]: size is required: every group of outputs is one array at its own size")
+        g = {key: entry.get(key) for key in ALSO_PER_OUTPUT}
+        g.update({key: entry[key] if key in entry else call.get(key) for key in ALSO_CALL_WIDE})
+        # (what the call says about placing and transforming is inherited by the groups that place and transform)
+        if g["resize_to"] is None and "fill" not in entry:
+            g["fill"] = None
+        if g["affine"] is None and g["perspective"] is None:
+            g.update({key: None for key in ("affine_resample", "affine_fill") if key not in entry})
+        try:                                  # (what needs no file, as the call's own arguments are checked before any is read)
+            g["size"] = normalize_size(entry["size"])
+            normalize_output(g["dtype"], g["normalize"], g["mirror"], g["size"], host=host)
+            normalize_resample(g["resample"], g["size"])
+            gap = normalize_reducing_gap(g["reducing_gap"], g["size"])
+            normalize_mode(g["mode"])
+            normalize_places(g["resize_to"], g["place"], g["size"])
+            normalize_fill(g["fill"], g["resize_to"])
+            normalize_transform(g["affine"], g["perspective"], g["affine_resample"], g["affine_fill"], g["size"], None, gap)
+            normalize_color_ops(g["color_ops"], g["size"])
+            if g["views"] is not None and not isinstance(g["views"], (list, tuple)):
+                normalize_views(g["views"], [], g["size"])
+        except ValueError as e:
+            raise ValueError(f"also[{k}]: {e}") from None
+        groups.append(g)
+    return groups
+
+
 def _per_file_of(value, n_files: int, kept: Sequence[int], what: str):
     """a per-file argument of a call with views — one entry per file of the caller's list — for the files that are read; anything
     that is not such a list (None, one value for all files) as it is"""
@@ -1218,10 +1301,18 @@ class _Request:
     views: Optional[List[Tuple[int, Tuple[int, int, int, int]]]] = None
     affine: Optional[AffineSpec] = None         # :func:`normalize_transform`'s, affine or perspective (None: no transform); always with ``views``
     colour: Optional[List[Optional[tuple]]] = None      # :func:`normalize_color_ops`' chains, one or None per OUTPUT (None: no operations)
+    # the extra groups of a call with ``also``: requests over the SAME files, index and orientations, each with its own size, views, output,
+    # tensor and slots (None: a call without).  A group with views need not name every file here; what it has none of it is left out of.
+    also: Optional[List["_Request"]] = None
 
     @property
     def n_outputs(self) -> int:
         return len(self.views) if self.views is not None else len(self.files)
+
+    @property
+    def groups(self) -> List["_Request"]:
+        """the request's groups of outputs: itself, then the extra ones"""
+        return [self] + list(self.also or [])
 
     @property
     def ncomp(self) -> Optional[int]:
@@ -1242,6 +1333,7 @@ class _Request:
 
         def chains(picked):                 # (outputs without operations: the request of a call without color_ops)
             return picked if picked is not None and any(c is not None for c in picked) else None
+        also = [g.narrow(idxs) for g in self.also] if self.also is not None else None      # (every group follows the files)
         if self.views is not None:
             # a file takes its views with it: they keep their order, and what is per view goes with the view
             pos = {i: k for k, i in enumerate(idxs)}
@@ -1255,19 +1347,29 @@ class _Request:
                 affine = None
             return _Request(pick(self.files), None, self.size, self.output.for_files(vk) if self.output else None, self.dest, pick_view(self.slots),
                             pick(index), orient, self.resample, self.mode, pick_view(self.places), self.fill, self.reducing_gap,
-                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine, chains(pick_view(self.colour)))
+                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine, chains(pick_view(self.colour)), also=also)
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
                         self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap,
-                        colour=chains(pick(self.colour)))
+                        colour=chains(pick(self.colour)), also=also)
 
     def orient_classes(self) -> List[List[int]]:
-        """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation"""
-        if self.orient is None:
+        """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation — and, in a
+        request with extra groups, by the groups that name them: a plan's groups then each name every file of it"""
+        if self.orient is None and self.also is None:
             return [list(range(len(self.files)))]
-        classes: Dict[int, List[int]] = {}
-        for i, o in enumerate(self.orient):
-            classes.setdefault(_orient_class(o, self.size is not None), []).append(i)
+        classes: Dict[tuple, List[int]] = {}
+        for i, key in enumerate(self.plan_keys()):
+            classes.setdefault(key, []).append(i)
         return list(classes.values())
+
+    def plan_keys(self) -> Optional[List[tuple]]:
+        """per file, what keeps it apart from files of its kind: its :func:`_orient_class` and, in a request with extra groups, which
+        of the groups have an output of it (None: nothing does, for any file)"""
+        if self.orient is None and self.also is None:
+            return None
+        named = [None if g.views is None else {f for f, _ in g.views} for g in self.groups] if self.also is not None else []
+        return [(_orient_class(self.orient[i], self.size is not None) if self.orient is not None else 0,) + tuple(s is None or i in s for s in named)
+                for i in range(len(self.files))]
 
     def plan_kwargs(self, native: Optional[int] = None) -> dict:
         """``rois``, ``size``, ``slots``, ``output``, ``orientation``, ``filter`` and ``mode`` of :class:`_binding.Plan` for one plan of all
@@ -1316,6 +1418,17 @@ class _Flight:
     plan: B.Plan
     d_rgb: object = None
     d_blob: object = None
+    # a request with extra groups: the plans derived from ``plan`` — (the group's request for these files, its plan) —, executed
+    # right behind it on its stream, each into its group's tensor; synced and closed with it
+    extra: list = field(default_factory=list)
+
+    def sync(self):
+        for p in [self.plan] + [p for _, p in self.extra]:
+            p.sync()
+
+    def close(self):
+        for p in [p for _, p in self.extra] + [self.plan]:
+            p.close()
 
 
 def _group_by_kind(files: Sequence[bytes], idxs, parsed: Dict[int, ParsedJpeg], headers_only: bool, turn=None, index=None) -> List[List[int]]:
@@ -1439,9 +1552,66 @@ class BatchDecoder:
         native = prep.shapes[0][2] if prep.shapes else None
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
+    def _group_plans(self, req: _Request, prep: PreparedBatch, blob_device_ptr: int = 0) -> list:
+        """The plans of a request whose files are ``prep``'s, in order, as (group's request, plan): the first group that has outputs
+        among these files makes the plan that decodes, every later one that has some derives from it (mj_plan_derive) and reads its
+        decoded images; a group with none is left out.  A request without extra groups: its one plan."""
+        if req.also is None:
+            return [(req, self._plan(req, prep, blob_device_ptr))]
+        native = prep.shapes[0][2] if prep.shapes else None
+        plans = []
+        try:
+            for g in req.groups:
+                if g.n_outputs == 0:
+                    continue
+                if not plans:
+                    plans.append((g, self._plan(g, prep, blob_device_ptr)))
+                    continue
+                kw = g.plan_kwargs(native)
+                kw.pop("rois")                  # (None: an extra group's windows are views)
+                plans.append((g, plans[0][1].derive(prep, **kw)))
+        except BaseException:
+            for _, p in reversed(plans):
+                p.close()
+            raise
+        return plans
+
+    @staticmethod
+    def _merged_request(files: Sequence[bytes], orientation, groups: List[dict], build) -> _Request:
+        """The request of a call with ``also``: ``groups`` are the keywords of the call's own group and of every extra one
+        (:func:`normalize_also`), ``build(files, orientation=, **group)`` the checked request of one group alone.  Every group is
+        built as the call it would be alone; the groups are then put over ONE list of files — those that some group names, each
+        parsed, uploaded and decoded once — with the call's orientations, and the extra groups hang on the first."""
+        kept = select_union_files(files, groups)
+        o = _per_file_of(orientation, len(files), kept, "orientation")
+        ufiles = [files[i] for i in kept]
+        turns = normalize_orientation(o, ufiles)
+        full = None
+        if turns is not None:                   # (one int per file of the caller's list, which every group picks its files' from)
+            full = [1] * len(files)
+            for i, t in zip(kept, turns):
+                full[i] = t
+        pos = {i: k for k, i in enumerate(kept)}
+        merged = []
+        for k, g in enumerate(groups):
+            try:
+                merged.append(build(files, orientation=full, **g))
+            except ValueError as e:
+                if k == 0:
+                    raise
+                raise ValueError(f"also[{k - 1}]: {e}") from None
+        any_views = any(r.views is not None for r in merged)
+        for r in merged:
+            own = r.index if r.index is not None else range(len(r.files))
+            if r.views is not None:
+                r.views = [(pos[own[f]], w) for f, w in r.views]
+            r.files, r.index, r.orient = ufiles, (kept if any_views else None), turns
+        merged[0].also = merged[1:]
+        return merged[0]
+
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1514,7 +1684,19 @@ class BatchDecoder:
         the uint8 canvas the call gives without the argument, without ``mirror`` and with ``dtype="uint8"`` — fill pixels
         included —, as a Pillow image of the output's mode, bit for bit; then the mirror and the element type.  An output whose
         chain is None or empty is the output of the call without the argument.  Not with ``return_seams``; autocontrast's
-        cutoffs and masks, and more than four ops are not offered yet."""
+        cutoffs and masks, and more than four ops are not offered yet.
+        ``also``, with ``size``: several groups of outputs from ONE decode (:func:`normalize_also`) — None or ``[]`` (the call as it
+        is), else a list with one dict per extra group: ``size`` (required) and that group's own ``views``, ``mirror``, ``resize_to``,
+        ``place``, ``affine``, ``perspective`` and ``color_ops`` (None when absent, never the call's); ``dtype``, ``normalize``,
+        ``resample``, ``mode``, ``reducing_gap``, ``fill``, ``affine_resample`` and ``affine_fill`` are the call's unless the entry names
+        them.  The result is then a tuple ``(primary, extra_0, extra_1, ...)``: element g is, bit for bit, what the call returns with
+        group g's arguments alone and the call's ``orientation`` — DINO's 2 x 224 and 8 x 96 crops, or one batch at 224 and at
+        384, from one upload and one decode.  Every file some group names is parsed, uploaded and decoded once; a file no group names
+        is not looked at.  Not with ``rois`` (windows are views) or ``return_seams``; an entry takes no ``rois``, ``orientation`` or
+        ``return_seams``."""
+        main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
+                    reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
+                    perspective=perspective)
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -1530,6 +1712,92 @@ class BatchDecoder:
         reducing_gap = normalize_reducing_gap(reducing_gap, size)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
+        extra = normalize_also(also, main, size, rois, return_seams, host=True)
+        cache: Dict[int, ParsedJpeg] = {}       # the parsed files, by their position in the caller's list
+        if extra is None:
+            req, dense = self._host_request(files, cache, None, rois, return_seams, orientation=orientation, **main)
+            denses = [dense]
+        else:
+            denses = []
+            gpu_segment = self._gpu_segment_for([files[i] for i in select_union_files(files, [main] + extra)])
+
+            def build(fs, **kw):
+                r, d = self._host_request(fs, cache, gpu_segment, **kw)
+                denses.append(d)
+                return r
+            req = self._merged_request(files, orientation, [main] + extra, build)
+        files, index, size, orient = req.files, req.index, req.size, req.orient
+        gpu_segment = self._gpu_segment_for(files)
+        parsed = {i: cache[index[i] if index is not None else i] for i in range(len(files))}
+        turn = req.plan_keys()
+        results: List[Optional[np.ndarray]] = [None] * len(files)
+        seams: List[Optional[dict]] = [None] * len(files)
+        flags = ((B.MJ_FLAG_KEEP_PLANES | B.MJ_FLAG_KEEP_IDCT) if return_seams else 0) | self.base_flags
+        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment, turn, index)]
+        while work:
+            item = work.pop(0)
+            idxs, sub = item.idxs, req.narrow(item.idxs)
+            prep = prepare_batch(sub.files, self.layout, flags | item.flags, [parsed[i] for i in idxs])
+            plans = self._group_plans(sub, prep)
+            plan = plans[0][1]
+            try:
+                for _, p in plans:              # (the derived plans right behind the plan that decodes, on the context's stream)
+                    p.execute()
+                for _, p in plans:
+                    p.sync()
+                out = plan.read(rgb=True, coef=return_seams, planes=return_seams, idct=return_seams)
+                tail, unconverged = _triage(out["status"], idxs, files, parsed, sub.index)
+                if tail:
+                    work.append(_Work(tail, flags=item.flags))
+                if unconverged:
+                    work.append(_Work(unconverged, flags=item.flags | B.MJ_FLAG_NO_SYNC))
+                again = set(tail) | set(unconverged)
+                which = {id(g): j for j, g in enumerate(sub.groups)}
+                for g, p in plans:
+                    dense = denses[which[id(g)]]
+                    rgb = out["rgb"] if p is plan else p.read(rgb=True)["rgb"]
+                    if dense is not None:
+                        imgs = rgb.view(dense.dtype).reshape((g.n_outputs,) + dense.shape[1:])
+                    else:
+                        imgs = self.split_outputs(prep, rgb, wins=g.wins, orient=g.orient, ncomp=g.ncomp)
+                    if g.views is not None:     # (the plan's outputs are its views, each to its place in the array)
+                        for k, (f, _) in enumerate(g.views):
+                            if idxs[f] not in again:
+                                dense[g.slots[k]] = imgs[k]
+                        continue
+                    for k, i in enumerate(idxs):
+                        if i in again:
+                            continue
+                        if dense is not None:
+                            dense[i] = imgs[k]
+                            continue
+                        results[i] = imgs[k]
+                        if return_seams:
+                            b0, _ = plan.image_offsets(k)
+                            b1 = plan.image_offsets(k + 1)[0] if k + 1 < len(idxs) else plan.info.total_blocks
+                            w, h, nc = prep.shapes[k]
+                            po = sum(s[0] * s[1] * s[2] for s in prep.shapes[:k])
+                            seams[i] = {"coef": out["coef"][b0:b1], "idct": out["idct"][b0:b1].reshape(-1, 8, 8),
+                                        "planes": out["planes"][po:po + w * h * nc].reshape(w, h, nc)}
+            finally:
+                for _, p in reversed(plans):
+                    p.close()
+        if extra is not None:
+            return tuple(denses)
+        if denses[0] is not None:
+            return denses[0]
+        return (results, seams) if return_seams else results
+
+    def _host_request(self, files: Sequence[bytes], cache: Dict[int, ParsedJpeg], gpu_segment: Optional[bool], rois=None, return_seams: bool = False,
+                      size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None,
+                      fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None):
+        """The checked request of a :meth:`decode` call, or of one group of it, and the array it fills (None without ``size``).  ``cache``:
+        the parsed files by their position in ``files``, filled with those this request names; ``gpu_segment``: whether they are parsed
+        headers only (None: decided by the files this request names)."""
+        size = normalize_size(size)
+        mode = normalize_mode(mode)
+        resample = normalize_resample(resample, size)
+        reducing_gap = normalize_reducing_gap(reducing_gap, size)
         spec = normalize_transform(affine, perspective, affine_resample, affine_fill, size,
                                    len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap, return_seams)
         colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files), return_seams)
@@ -1541,8 +1809,14 @@ class BatchDecoder:
             index, views = selected
             orientation = _per_file_of(orientation, len(files), index, "orientation")
             files = [files[i] for i in index]
-        gpu_segment = self._gpu_segment_for(files)
-        parsed = {i: _named(index, i, parse_jpeg, f, headers_only=gpu_segment) for i, f in enumerate(files)}
+        if gpu_segment is None:
+            gpu_segment = self._gpu_segment_for(files)
+        parsed = {}
+        for i, f in enumerate(files):
+            at = index[i] if index is not None else i
+            if at not in cache:
+                cache[at] = _named(index, i, parse_jpeg, f, headers_only=gpu_segment)
+            parsed[i] = cache[at]
         orient = normalize_orientation(orientation, files)
         odims = _oriented_dims([(p.image_width, p.image_height) for p in parsed.values()], orient)
         req = _Request(files, normalize_rois(rois, odims), size, orient=orient, resample=resample, mode=mode, reducing_gap=reducing_gap, index=index,
@@ -1553,7 +1827,6 @@ class BatchDecoder:
             check_affine(spec, req.views, odims, index)
         else:
             req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
-        turn = [_orient_class(o, size is not None) for o in orient] if orient is not None else None
         dense = None                            # size=: the one array (every plan's own dense output is copied into it)
         if size is not None:
             nc = req.ncomp or one_component_count([len(p.color_components) for p in parsed.values()])
@@ -1562,52 +1835,7 @@ class BatchDecoder:
             if spec is not None:
                 req.affine = _spec_for_outputs(spec, size, req.n_outputs, nc)
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
-        results: List[Optional[np.ndarray]] = [None] * len(files)
-        seams: List[Optional[dict]] = [None] * len(files)
-        flags = ((B.MJ_FLAG_KEEP_PLANES | B.MJ_FLAG_KEEP_IDCT) if return_seams else 0) | self.base_flags
-        work = [_Work(idxs) for idxs in _group_by_kind(files, range(len(files)), parsed, gpu_segment, turn, index)]
-        while work:
-            item = work.pop(0)
-            idxs, sub = item.idxs, req.narrow(item.idxs)
-            prep = prepare_batch(sub.files, self.layout, flags | item.flags, [parsed[i] for i in idxs])
-            plan = self._plan(sub, prep)
-            try:
-                plan.execute()
-                plan.sync()
-                out = plan.read(rgb=True, coef=return_seams, planes=return_seams, idct=return_seams)
-                tail, unconverged = _triage(out["status"], idxs, files, parsed, sub.index)
-                if tail:
-                    work.append(_Work(tail, flags=item.flags))
-                if unconverged:
-                    work.append(_Work(unconverged, flags=item.flags | B.MJ_FLAG_NO_SYNC))
-                if dense is not None:
-                    imgs = out["rgb"].view(dense.dtype).reshape((sub.n_outputs,) + dense.shape[1:])
-                else:
-                    imgs = self.split_outputs(prep, out["rgb"], wins=sub.wins, orient=sub.orient, ncomp=sub.ncomp)
-                if sub.views is not None:       # (the plan's outputs are its views, each to its place in the array)
-                    for k, (f, _) in enumerate(sub.views):
-                        if idxs[f] not in tail and idxs[f] not in unconverged:
-                            dense[sub.slots[k]] = imgs[k]
-                    continue
-                for k, i in enumerate(idxs):
-                    if i in tail or i in unconverged:
-                        continue
-                    if dense is not None:
-                        dense[i] = imgs[k]
-                        continue
-                    results[i] = imgs[k]
-                    if return_seams:
-                        b0, _ = plan.image_offsets(k)
-                        b1 = plan.image_offsets(k + 1)[0] if k + 1 < len(idxs) else plan.info.total_blocks
-                        w, h, nc = prep.shapes[k]
-                        po = sum(s[0] * s[1] * s[2] for s in prep.shapes[:k])
-                        seams[i] = {"coef": out["coef"][b0:b1], "idct": out["idct"][b0:b1].reshape(-1, 8, 8),
-                                    "planes": out["planes"][po:po + w * h * nc].reshape(w, h, nc)}
-            finally:
-                plan.close()
-        if dense is not None:
-            return dense
-        return (results, seams) if return_seams else results
+        return req, dense
 
     def _staging_for(self, files: Sequence[bytes]) -> np.ndarray:
         """Host buffer the native front end builds the blob in, kept between calls (first touch of a fresh 300 MB
@@ -1670,7 +1898,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1711,7 +1939,10 @@ class BatchDecoder:
         ``perspective`` as in :meth:`decode`, in ``affine``'s place: every such plan runs the perspective launch there instead.
         ``color_ops`` as in :meth:`decode`: every plan of the call whose outputs have operations writes its canvases into a buffer of
         its own and runs the colour launches behind its resize launch — histograms, tables and the operations themselves, all on the
-        GPU —, which store into the one tensor; plans whose outputs have none are the plans of a call without the argument."""
+        GPU —, which store into the one tensor; plans whose outputs have none are the plans of a call without the argument.
+        ``also`` as in :meth:`decode`: a tuple of tensors, one per group.  Every plan of the call (files of several kinds and
+        orientation classes, second rounds, parts) is made by the first group that has outputs among its files; every later group
+        that has some derives a plan from it, executed right behind it on the same stream into that group's tensor."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -1719,19 +1950,30 @@ class BatchDecoder:
         normalize_mode(mode)
         normalize_places(resize_to, place, size)
         normalize_fill(fill, resize_to)
-        req = self._device_request(files, rois, size, dtype, normalize, mirror, orientation, resample, mode, resize_to, place, fill, reducing_gap, views,
-                                   affine, affine_resample, affine_fill, color_ops, perspective)
+        main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
+                    reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
+                    perspective=perspective)
+        extra = normalize_also(also, main, size, rois)
+        if extra is None:
+            req = self._device_request(files, rois, orientation=orientation, **main)
+        else:
+            req = self._merged_request(files, orientation, [main] + extra, lambda fs, **kw: self._device_request(fs, None, **kw))
         files = req.files                       # (with views: the files some view names)
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
-            return self._decode_request(req)
+            return self._result(req, self._decode_request(req))
         cut = [len(files) * i // parts for i in range(parts + 1)]
         out: List["torch.Tensor"] = []
         for part in self._device_iter((req.narrow(range(cut[i], cut[i + 1])) for i in range(parts)), depth=2):
             if req.dest is None:
                 out += part
-        return out if req.dest is None else req.dest
+        return out if req.dest is None else self._result(req, req.dest)
+
+    @staticmethod
+    def _result(req: _Request, out):
+        """what a call returns for a request: ``out``, or — with extra groups — the tuple of every group's tensor, the call's own first"""
+        return out if req.also is None else tuple(g.dest for g in req.groups)
 
     def _decode_request(self, req: _Request):
         """What :meth:`decode_device` returns for a checked request, decoded as one plan per kind of file — the request's
@@ -1795,13 +2037,17 @@ class BatchDecoder:
                             d_blob = torch.from_numpy(prep.blob).to(dev)         # (pageable source: the staging buffer is free on return)
                     else:
                         d_blob = torch.from_numpy(prep.blob).to(dev)
-                    flight = _Flight(sub, item.idxs, prep, self._plan(sub, prep, d_blob.data_ptr()), None, d_blob)
+                    plans = self._group_plans(sub, prep, d_blob.data_ptr())      # (extra groups: the plan that decodes, then the derived ones)
+                    lead = plans[0][0]
+                    flight = _Flight(sub, item.idxs, prep, plans[0][1], None, d_blob, plans[1:])
                     flying.append(flight)
-                    d_rgb = flight.d_rgb = req.dest if req.dest is not None else torch.empty(flight.plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
+                    d_rgb = flight.d_rgb = lead.dest if lead.dest is not None else torch.empty(flight.plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     cur = torch.cuda.current_stream(dev)
                     if streams is None:
                         self._wait_for_current_stream(cur)
                         flight.plan.execute(0, d_rgb.data_ptr())                 # the everyday case: one plan, the context's stream
+                        for g, derived in flight.extra:
+                            derived.execute(0, g.dest.data_ptr())
                     else:
                         # (streams only overlap when they sit on different hardware queues: the package asks the runtime for
                         # eight instead of four, see __init__.py)
@@ -1811,8 +2057,11 @@ class BatchDecoder:
                         d_rgb.record_stream(st)
                         d_blob.record_stream(st)
                         flight.plan.execute(st.cuda_stream, d_rgb.data_ptr())
+                        for g, derived in flight.extra:
+                            g.dest.record_stream(st)
+                            derived.execute(st.cuda_stream, g.dest.data_ptr())
                 for flight in flying:
-                    flight.plan.sync()
+                    flight.sync()
                     tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], flight.idxs, files, parsed, flight.req.index)
                     if tail:
                         work.append(_Work(tail))
@@ -1826,12 +2075,12 @@ class BatchDecoder:
                             results[i] = views[k]
             finally:
                 for flight in flying:
-                    flight.plan.close()
+                    flight.close()
         return results if req.dest is None else req.dest
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None, color_ops=None, perspective=None):
+                           affine_fill=None, color_ops=None, perspective=None, also=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -1855,8 +2104,15 @@ class BatchDecoder:
         that yields, batch by batch, what :meth:`decode_device` takes for that batch; ``affine_resample`` and ``affine_fill`` as
         there, for every batch.  ``perspective``: None, one sequence of eight coefficients for every output of every batch, or an
         iterable that yields one value per batch, as ``affine`` does; not together with ``affine``.  ``color_ops``: None, one chain for every output of every batch, or an iterable that yields, batch by
-        batch, what :meth:`decode_device` takes for that batch."""
+        batch, what :meth:`decode_device` takes for that batch.  ``also``: None, or an iterable that yields, batch by batch, what
+        :meth:`decode_device` takes for that batch — a list with one dict per extra group; every batch is then handed out as a tuple
+        of tensors, one per group."""
         size = normalize_size(size)
+        if also is not None and isinstance(also, (list, tuple)) and len(also) == 0:
+            also = None                                                               # (no extra group: a call without the argument)
+        if also is not None and size is None:
+            raise ValueError("also needs size=(width, height): every group of outputs is one array at its own size")
+        per_batch_also = iter(also) if also is not None else None
         normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
         per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
@@ -1924,6 +2180,19 @@ class BatchDecoder:
                         raise ValueError("color_ops yields fewer entries than there are batches") from None
                 def none(g):
                     return g is None or (isinstance(g, (list, tuple)) and all(e is None for e in g))
+                if per_batch_also is not None:
+                    try:
+                        a = next(per_batch_also)
+                    except StopIteration:
+                        raise ValueError("also yields fewer entries than there are batches") from None
+                    plain = none(t) and none(ps)
+                    main = dict(size=size, dtype=dtype, normalize=normalize, mirror=m, resample=resample, mode=mode, resize_to=resize_to, place=place,
+                                fill=fill, reducing_gap=reducing_gap, views=v, affine=None if none(t) else t, affine_resample=None if plain else affine_resample,
+                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps)
+                    extra = normalize_also(a, dict(main, affine_resample=affine_resample, affine_fill=affine_fill), size)
+                    if extra is not None:
+                        yield self._merged_request(files, o, [main] + extra, lambda fs, **kw: self._device_request(fs, None, **kw))
+                        continue
                 if none(t) and none(ps):                # (a batch without a transform)
                     yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
                                                color_ops=c)
@@ -1947,18 +2216,18 @@ class BatchDecoder:
         def collect(flight):
             req = flight.req
             try:
-                flight.plan.sync()
+                flight.sync()
                 tail, unconverged = _triage(flight.plan.read(rgb=False)["status"], np.arange(len(req.files)), index=req.index)
                 out = flight.d_rgb if req.size is not None else self._views(flight.d_rgb, self._out_shapes(flight.prep, req.wins, req.orient, req.ncomp))
             finally:
-                flight.plan.close()
+                flight.close()
             again = sorted(tail + unconverged)
             if again:                                             # only the files concerned take the long way (host parse)
                 redo = self._decode_request(req.narrow(again))
                 if req.size is None:
                     for i, img in zip(again, redo):
                         out[i] = img
-            return out
+            return self._result(req, out)
 
         try:
             for req in requests:
@@ -1975,30 +2244,34 @@ class BatchDecoder:
                 if not isinstance(prep, PreparedBatch):           # declined, or several plans' worth: the one-call path sorts it out
                     while pending:
                         yield collect(pending.popleft())
-                    yield self._decode_request(req)
+                    yield self._result(req, self._decode_request(req))
                     continue
                 with torch.cuda.stream(copy_stream):
                     d_blob = pinned[buf][:prep.blob.size].to(dev, non_blocking=True)
                     uploaded[buf] = torch.cuda.Event()
                     uploaded[buf].record(copy_stream)
-                plan = self._plan(req, prep, d_blob.data_ptr())
+                plans = self._group_plans(req, prep, d_blob.data_ptr())
+                lead, plan = plans[0]
+                flight = _Flight(req, None, prep, plan, None, d_blob, plans[1:])
                 try:
                     # (both tensors outlive the kernels that touch them: they stay in `pending` until the plan has been collected)
-                    d_rgb = req.dest if req.dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
+                    d_rgb = flight.d_rgb = lead.dest if lead.dest is not None else torch.empty(plan.info.rgb_bytes, dtype=torch.uint8, device=dev)
                     self.ctx.wait_event(uploaded[buf].cuda_event)
                     self._wait_for_current_stream(torch.cuda.current_stream(dev))
                     plan.execute(0, d_rgb.data_ptr())
+                    for g, derived in flight.extra:
+                        derived.execute(0, g.dest.data_ptr())
                 except BaseException:
-                    plan.close()
+                    flight.close()
                     raise
-                pending.append(_Flight(req, None, prep, plan, d_rgb, d_blob))
+                pending.append(flight)
                 while len(pending) > depth:
                     yield collect(pending.popleft())
             while pending:
                 yield collect(pending.popleft())
         finally:
             while pending:                                        # (an error, or a consumer that stopped early: nothing stays open)
-                pending.popleft().plan.close()
+                pending.popleft().close()
 
     def close(self):
         self.ctx.close()

@@ -115,20 +115,31 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event) {
 /* Host-side table export for tests: the IDCT table exactly as the library builds it ([u*8+v][x*8+y]). */
 void mj_host_idct_table(double *tt) { build_idct_tt(tt); }
 
+// one reference less; with the last one the plan's arena and device blocks go back to the context
+static void plan_release(mj_plan *p) {
+    if (--p->refs > 0) return;
+    if (p->arena.base) {
+        if (p->ctx->free_arenas.size() < 4) p->ctx->free_arenas.push_back(p->arena);
+        else (void)hipHostFree(p->arena.base);
+    }
+    for (void *q : p->blocks) p->ctx->cache.put(q);
+    delete p;
+}
+
 void mj_plan_destroy(mj_plan *p) {
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
     // the buffers go back to the context for the next plan: nothing of this plan may still be running on them (other
     // plans' work on the same streams is none of its business: a serving loop destroys batch k while batch k+1 runs)
-    if (p->ready) { (void)hipEventSynchronize(p->ready); (void)hipEventDestroy(p->ready); }
-    if (p->done) { if (p->done_valid) (void)hipEventSynchronize(p->done); (void)hipEventDestroy(p->done); }
-    if (p->arena.base) {
-        if (p->ctx->free_arenas.size() < 4) p->ctx->free_arenas.push_back(p->arena);
-        else (void)hipHostFree(p->arena.base);
-    }
-    if (p->graph_exec) (void)hipGraphExecDestroy(p->graph_exec);
-    for (void *q : p->blocks) p->ctx->cache.put(q);
-    delete p;
+    if (p->ready) { (void)hipEventSynchronize(p->ready); (void)hipEventDestroy(p->ready); p->ready = nullptr; }
+    if (p->done) { if (p->done_valid) (void)hipEventSynchronize(p->done); (void)hipEventDestroy(p->done); p->done = nullptr; }
+    p->done_valid = false;
+    if (p->graph_exec) { (void)hipGraphExecDestroy(p->graph_exec); p->graph_exec = nullptr; }
+    // A plan that others were derived from keeps its buffers until the last of them has gone — a derived execute may still be
+    // reading them —, and a derived plan, whose own work has been waited for above, lets go of its parent behind itself.
+    mj_plan *parent = p->parent;
+    plan_release(p);
+    if (parent) plan_release(parent);
 }
 
 int mj_plan_stage1_form(const mj_plan *p) {
@@ -207,14 +218,19 @@ static mj::ResolvedTables resolved_tables(const mj_plan *p, const uint32_t *lut)
     return mj::ResolvedTables{lut, p->n_ac13, p->n_dc13, p->ac_slot_pk, p->dc_slot_pk, p->dc_tab_pk};
 }
 
+// the decode's entry points on a derived plan, which decodes nothing
+static int no_decode(mj_plan *p, const char *fn) { return fail(p->ctx, MJ_ERR_INVALID, "%s: a derived plan has no decode of its own (mj_plan_derive)", fn); }
+
 int mj_plan_execute_stage1(mj_plan *p, void *stream) {
     if (!p) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_execute_stage1");
     const int rc = stage1_impl(p, stream);
     return rc != MJ_OK ? rc : mark_done(p, stream ? (hipStream_t)stream : p->ctx->stream);
 }
 
 int mj_plan_execute_stage2(mj_plan *p, void *stream, uint8_t *rgb_device) {
     if (!p) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_execute_stage2");
     const int rc = stage2_impl(p, stream, rgb_device);
     return rc != MJ_OK ? rc : mark_done(p, stream ? (hipStream_t)stream : p->ctx->stream);
 }
@@ -468,6 +484,16 @@ int mj_plan_execute(mj_plan *p, void *stream, uint8_t *rgb_device) {
     if (!p) return MJ_ERR_INVALID;
     mj_context *ctx = p->ctx;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (p->derived) {       // only the launches behind the decode, over the parent's decoded images; never a graph
+        if (int rc = plan_ready(p, s)) return rc;
+        if (!rgb_device) {
+            if (!p->d_rgb) MJ_HIP(ctx, alloc(p, &p->d_rgb, (size_t)p->info.rgb_bytes + 16));
+            rgb_device = p->d_rgb;
+        }
+        p->last_rgb = rgb_device;
+        const int rc = resize_launch(p, s);
+        return rc != MJ_OK ? rc : mark_done(p, s);
+    }
     const bool fused = p->use_fused && p->d_blob;
     // fused launches of one context take turns (plan.h): outside any graph — the wait and the record bracket whatever this
     // execute submits, replayed or not
@@ -552,6 +578,11 @@ int mj_plan_read(mj_plan *p, uint8_t *rgb_host, int16_t *coef_host, int16_t *pla
         if (!p->last_rgb) return fail(ctx, MJ_ERR_INVALID, "mj_plan_read: nothing executed yet");
         MJ_HIP(ctx, hipMemcpy(rgb_host, p->last_rgb, (size_t)p->info.rgb_bytes, hipMemcpyDeviceToHost));
     }
+    if (p->derived && (coef_host || planes_host || idct_host)) return no_decode(p, "mj_plan_read");
+    if (p->derived && status_host) {       // (no decode, so nothing to report: the parent's statuses are the files')
+        memset(status_host, 0, (size_t)p->n_images * 4);
+        status_host = nullptr;
+    }
     if (coef_host) {   // the :869 seam is in zig-zag order; the device keeps blocks in natural order
         if (!p->d_tmp_coef) MJ_HIP(ctx, alloc(p, &p->d_tmp_coef, (size_t)p->info.total_blocks * 128 + 16));
         MJ_HIP(ctx, mj::launch_permute_blocks(ctx->stream, p->d_coef, p->d_tmp_coef, p->info.total_blocks, 0, p->transposed ? 1 : 0));
@@ -572,6 +603,7 @@ int mj_plan_read(mj_plan *p, uint8_t *rgb_host, int16_t *coef_host, int16_t *pla
 
 int mj_plan_write_coef(mj_plan *p, const int16_t *coef, int32_t mem) {
     if (!p || !coef) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_write_coef");
     if (int rc = plan_ready(p)) return rc;
     mj_context *ctx = p->ctx;
     const int16_t *src = coef;
@@ -594,10 +626,15 @@ static int fill_buffer(mj_plan *p, void *buf, size_t bytes, int byte_value) {
     MJ_HIP(p->ctx, hipDeviceSynchronize());
     return MJ_OK;
 }
-int mj_plan_fill_coef(mj_plan *p, int byte_value) { return !p ? MJ_ERR_INVALID : fill_buffer(p, p->d_coef, (size_t)p->info.total_blocks * 128, byte_value); }
+int mj_plan_fill_coef(mj_plan *p, int byte_value) {
+    if (!p) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_fill_coef");
+    return fill_buffer(p, p->d_coef, (size_t)p->info.total_blocks * 128, byte_value);
+}
 
 int mj_plan_fill_source(mj_plan *p, int byte_value) {
     if (!p) return MJ_ERR_INVALID;
+    if (p->derived) return fail(p->ctx, MJ_ERR_INVALID, "mj_plan_fill_source: a derived plan's source is its parent's buffer (fill the parent's)");
     if (!p->resized) return fail(p->ctx, MJ_ERR_INVALID, "mj_plan_fill_source: not a resized plan");
     return fill_buffer(p, p->d_src, (size_t)p->src_bytes + 64, byte_value);
 }
@@ -683,6 +720,7 @@ int mj_idct_batch(mj_context *ctx, const mj_batch *batch, const int16_t *coef, u
 
 int mj_plan_idct_levels(mj_plan *p, uint64_t counts[3]) {
     if (!p || !counts) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_idct_levels");
     mj_context *ctx = p->ctx;
     if (p->done_valid) MJ_HIP(ctx, hipEventSynchronize(p->done));
     MJ_HIP(ctx, hipMemcpy(counts, p->d_job_prefix + p->n_images + 3, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -749,6 +787,7 @@ int mj_device_copy_rate(mj_context *ctx, int64_t bytes, int iters, float *ms_per
 // times into one output buffer (a decode service's slot, a benchmark's step); a one-shot decode should not bother.
 int mj_plan_tune_placement(mj_plan *p, void *stream, uint8_t *rgb_device, int32_t candidates, float *ms_out, int32_t *chosen, float *best_out) {
     if (!p || candidates < 1 || candidates > 16) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_tune_placement");
     if (best_out) *best_out = 0.f;
     mj_context *ctx = p->ctx;
     if (chosen) *chosen = 0;
@@ -803,6 +842,7 @@ int mj_plan_tune_placement(mj_plan *p, void *stream, uint8_t *rgb_device, int32_
 
 int mj_plan_time_stages(mj_plan *p, int iters, uint8_t *rgb_device, float *stage1_ms, float *stage2_ms) {
     if (!p || iters <= 0) return MJ_ERR_INVALID;
+    if (p->derived) return no_decode(p, "mj_plan_time_stages");
     mj_context *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     int rc = MJ_OK;

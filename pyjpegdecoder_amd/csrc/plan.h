@@ -325,6 +325,14 @@ struct mj_plan {
     // files' (0: they are) — the orient / resize launch converts —, and every image's byte offset in the output
     int out_ncomp = 0;
     std::vector<int64_t> h_out_off;
+    // plans are counted: the caller holds one reference until mj_plan_destroy, and every derived plan (mj_plan_derive) holds one to
+    // its parent.  The device blocks and the arena go back to the context with the last reference; mj_plan_destroy itself waits for
+    // the plan's own events and gives them up.
+    int refs = 1;
+    // derived plans: only the launches behind the decode (resize_launch), over the parent's d_src, which this plan names and does
+    // not own.  No blob, no coefficient store, no statuses: the decode's entry points refuse it.
+    bool derived = false;
+    mj_plan *parent = nullptr;
 };
 
 // ---- plan_tables.hip: table building (host)
@@ -362,6 +370,8 @@ inline bool perspective_none(const mj_perspective &m) {
 }
 constexpr const char *kCreateFn = "mj_plan_create_with";     // (for the messages)
 int create_resized(const PlanRequest &q);
+// mj_plan_derive's maker (resize_plan.hip): the stages of a sized request on a shell plan that reads `parent`'s decoded images
+int create_derived(const PlanRequest &q, mj_plan *parent);
 // reducing_gap's default rule (normalise_request): whether any image of the request — oriented, its window, to its place's size —
 // gets a factor above 1; images whose sizes the makers will refuse count as none
 bool reduce_applies(const mj_batch *b, const mj_plan_request &r);

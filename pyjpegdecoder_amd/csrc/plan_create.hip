@@ -923,4 +923,27 @@ int mj_plan_create_with(mj_context *ctx, const mj_batch *b, const mj_plan_reques
 
 int mj_plan_create(mj_context *ctx, const mj_batch *b, mj_plan **out) { return mj_plan_create_with(ctx, b, nullptr, out); }
 
+int mj_plan_derive(mj_plan *parent, const mj_batch *b, const mj_plan_request *request, mj_plan **out) {
+    const char *fn = "mj_plan_derive";
+    if (!parent) return fail(nullptr, MJ_ERR_INVALID, "%s: NULL argument", fn);
+    mj_context *ctx = parent->ctx;
+    if (!b || !request || !out) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+    *out = nullptr;
+    if (parent->derived) return fail(ctx, MJ_ERR_INVALID, "%s: the parent is itself derived (derive from the plan that decodes)", fn);
+    if (!parent->resized || parent->orient_only)
+        return fail(ctx, MJ_ERR_INVALID, "%s: the parent has no size (out_width, out_height): only a sized plan keeps its decoded images", fn);
+    if (parent->windowed) return fail(ctx, MJ_ERR_INVALID, "%s: the parent is a window plan: it does not decode whole images", fn);
+    // the batch is the parent's: what the stage builders read of it — image count, sizes, component counts, the layout — is checked
+    bool same = b->n_images == parent->n_images && b->layout == parent->layout && (b->images || b->n_images <= 0);
+    for (int i = 0; same && i < b->n_images; ++i)
+        same = b->images[i].width == parent->h_images[i].width && b->images[i].height == parent->h_images[i].height && b->images[i].ncomp == parent->h_images[i].ncomp;
+    if (!same) return fail(ctx, MJ_ERR_INVALID, "%s: the batch is not the one the parent was made from (image count, sizes, components, layout)", fn);
+    if (!request->out_width && !request->out_height) return fail(ctx, MJ_ERR_INVALID, "%s: the request needs a size (out_width, out_height)", fn);
+    if (request->rois) return fail(ctx, MJ_ERR_INVALID, "%s: rois: a derived plan's windows are views", fn);
+    mj::PlanRequest q{ctx, b, out, *request};
+    if (int rc = normalise_request(q)) return rc;
+    MJ_HIP(ctx, hipSetDevice(ctx->device));
+    return mj::create_derived(q, parent);
+}
+
 }  // extern "C"

@@ -71,7 +71,8 @@ struct Need { int x0, nx, y0, ny, sw, sh; };
 // where the ranges are less than the whole and the rule below says so, the windows of those ranges, as if the caller had asked
 // for them (the plan becomes a window plan: restart segments and MCUs outside are skipped as for a caller's windows, and
 // the tables are rebased to the range); else empty, and every range starts at 0 (tables over the whole image or window).
-int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vector<mj_roi> &derived) {
+// (may_window false — a derived plan, whose decode is its parent's: the ranges are never made windows)
+int placed_source_ranges(const PlanRequest &q, bool may_window, std::vector<Need> &need, std::vector<mj_roi> &derived) {
     const mj_batch *b = q.b;
     const char *fn = mj::kCreateFn;
     const mj_roi *rois = q.r.rois; const uint8_t *orient = q.r.orientations; const mj_place *places = q.r.places;
@@ -132,7 +133,7 @@ int placed_source_ranges(const PlanRequest &q, std::vector<Need> &need, std::vec
     // 1 whenever anything is saved (tests, probes, and crops far smaller than the one measured).
     bool derive = rois != nullptr;
     if (const char *e = mj::opt("MJ_PLACE_WINDOW")) derive = atoi(e) != 0;
-    if (q.r.reducing_gap != 0 || views) derive = false;
+    if (q.r.reducing_gap != 0 || views || !may_window) derive = false;
     if (derive && area_need < area_all) {
         derived.resize((size_t)b->n_images);
         for (int i = 0; i < b->n_images; ++i) {
@@ -566,42 +567,57 @@ bool mj::reduce_applies(const mj_batch *b, const mj_plan_request &r) {
 }
 
 // ---- the plan, from a normalised request with a size ------------------------------------------------------------------------------
-int mj::create_resized(const PlanRequest &q) {
-    const char *fn = kCreateFn;
-    mj_context *ctx = q.ctx; const mj_batch *b = q.b; mj_plan **out = q.out;
-    auto [rois, orient, mode, out_width, out_height, transform_filter, matrices, perspective, slots, n_slots, n_views, views, output, filter,
+namespace {
+
+// What a sized request says before there is a plan: a placed request's source ranges (and the windows derived from them), whether its
+// orientations exchange width and height, and its windows as windows of the stored images (rois: what the decoding plan is given).
+struct Front {
+    std::vector<Need> need;
+    std::vector<mj_roi> derived, stored;
+    const mj_roi *rois = nullptr;
+    bool swapped = false;
+};
+
+int resized_front(const PlanRequest &q, bool may_window, Front &f) {
+    const char *fn = mj::kCreateFn;
+    mj_context *ctx = q.ctx; const mj_batch *b = q.b;
+    const uint8_t *orient = q.r.orientations;
+    f.rois = q.r.rois;
+    if (q.r.places) {
+        if (int rc = placed_source_ranges(q, may_window, f.need, f.derived)) return rc;
+        if (!f.derived.empty()) f.rois = f.derived.data();
+    }
+    // oriented plans: all images transposing (orientations 5..8) or none — the two read their source in different ways, so
+    // they are two launches, i.e. two plans (BatchDecoder sorts the files); windows are given in oriented coordinates
+    if (orient) {
+        if (!b->images) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
+        f.swapped = b->n_images > 0 && (mj::orient_bits(orient[0]) & 4);
+        for (int i = 0; i < b->n_images; ++i)
+            if (((mj::orient_bits(orient[i]) & 4) != 0) != f.swapped)
+                return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: orientations that exchange width and height (5..8) and others do not share a resized plan; split the batch", fn, i);
+        if (f.rois) {
+            if (int rc = stored_windows(q, f.rois, f.stored)) return rc;
+            f.rois = f.stored.data();
+        }
+    }
+    return MJ_OK;
+}
+
+// The stages behind the decode, built on plan p: a plan of plan_create_common's (given_src NULL: it gets its own intermediate buffer)
+// or the shell of a derived plan, whose images are its parent's and whose source is the parent's buffer of given_bytes bytes.
+int resized_stages(const PlanRequest &q, Front &f, mj_plan *p, uint8_t *given_src, int64_t given_bytes) {
+    const char *fn = mj::kCreateFn;
+    mj_context *ctx = q.ctx; const mj_batch *b = q.b;
+    auto [rois_, orient, mode, out_width, out_height, transform_filter, matrices, perspective, slots, n_slots, n_views, views, output, filter,
           reducing_gap, places, fill, chains, transform_fill] = q.r;
+    (void)rois_; (void)transform_filter; (void)transform_fill;
+    std::vector<Need> &need = f.need;
+    bool swapped = f.swapped;
     const bool affine = matrices || perspective;      // (either transform: the launch in front of the resize)
     // a plan with colour operations: the resize launch is that of the uint8, unmirrored, identity-slot request — it writes the
     // canvases —, and the element type, the slots and the mirror flags are the colour launches' (colour_stage)
     const bool colour = chains != nullptr;
     const int dtype = output ? output->dtype : MJ_DTYPE_U8, out_esize = dtype_size(dtype), esize = colour ? 1 : out_esize;
-    std::vector<Need> need;
-    std::vector<mj_roi> derived;
-    if (places) {
-        if (int rc = placed_source_ranges(q, need, derived)) return rc;
-        if (!derived.empty()) rois = derived.data();
-    }
-    // oriented plans: all images transposing (orientations 5..8) or none — the two read their source in different ways, so
-    // they are two launches, i.e. two plans (BatchDecoder sorts the files); windows are given in oriented coordinates
-    bool swapped = false;
-    std::vector<mj_roi> stored;
-    if (orient) {
-        if (!b->images) return fail(ctx, MJ_ERR_INVALID, "%s: NULL argument", fn);
-        swapped = b->n_images > 0 && (mj::orient_bits(orient[0]) & 4);
-        for (int i = 0; i < b->n_images; ++i)
-            if (((mj::orient_bits(orient[i]) & 4) != 0) != swapped)
-                return fail(ctx, MJ_ERR_UNSUPPORTED, "%s: image %d: orientations that exchange width and height (5..8) and others do not share a resized plan; split the batch", fn, i);
-        if (rois) {
-            if (int rc = stored_windows(q, rois, stored)) return rc;
-            rois = stored.data();
-        }
-    }
-    mj_plan *p = nullptr;
-    // (whole images — also under views, which are windows of the DECODED images —: a plain plan, which may take the fused launch;
-    // windows: a window plan)
-    if (int rc = mj::plan_create_common(ctx, b, rois, rois != nullptr, &p)) return rc;
-    PlanGuard guard{p};
     // C: the source's components.  A plan that converts stores CO of them per pixel and runs both passes, and T, on CT = 1:
     // colour becomes L where it is read, grey becomes RGB where it is stored (resize.hip's k_resize_*_mode)
     int C = p->ncomp;
@@ -719,8 +735,11 @@ int mj::create_resized(const PlanRequest &q) {
     }
     // the un-resized pixels: a plan-owned buffer from the context's cache (64 bytes of slack: the kernels' 16-byte loads may
     // start before and end behind the bytes they use)
-    p->src_bytes = p->info.rgb_bytes;
-    MJ_HIP(ctx, alloc(p, &p->d_src, (size_t)p->src_bytes + 64));
+    if (given_src) { p->src_bytes = given_bytes; p->d_src = given_src; }
+    else {
+        p->src_bytes = p->info.rgb_bytes;
+        MJ_HIP(ctx, alloc(p, &p->d_src, (size_t)p->src_bytes + 64));
+    }
     a.images = p->d_rz_images; a.tabs = p->d_rz_tabs; a.src = p->d_src;
     if (reducing) {
         // the reduced images: a second plan-owned buffer with the same slack, which the resize launch reads as it would d_src
@@ -741,8 +760,52 @@ int mj::create_resized(const PlanRequest &q) {
     p->info.rgb_bytes = (int64_t)n_slots * out_image * (colour ? out_esize : 1);
     p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
     p->resized = true;
+    return MJ_OK;
+}
+
+}  // namespace
+
+int mj::create_resized(const PlanRequest &q) {
+    Front f;
+    if (int rc = resized_front(q, true, f)) return rc;
+    mj_plan *p = nullptr;
+    // (whole images — also under views, which are windows of the DECODED images —: a plain plan, which may take the fused launch;
+    // windows: a window plan)
+    if (int rc = mj::plan_create_common(q.ctx, q.b, f.rois, f.rois != nullptr, &p)) return rc;
+    PlanGuard guard{p};
+    if (int rc = resized_stages(q, f, p, nullptr, 0)) return rc;
     guard.p = nullptr;
-    *out = p;
+    *q.out = p;
+    return MJ_OK;
+}
+
+// A derived plan: a shell with the parent's context, layout, images and component count — what the stage builders read of a plan —,
+// an arena and the two events of its own; the stages are built on it over the parent's intermediate buffer, which the parent keeps
+// for as long as this plan holds it (mj_plan_destroy).
+int mj::create_derived(const PlanRequest &q, mj_plan *parent) {
+    mj_context *ctx = q.ctx;
+    Front f;
+    if (int rc = resized_front(q, false, f)) return rc;
+    mj_plan *p = new mj_plan();
+    p->ctx = ctx; p->n_images = parent->n_images; p->layout = parent->layout; p->flags = parent->flags;
+    p->hmax = parent->hmax; p->vmax = parent->vmax; p->ncomp = parent->ncomp; p->generic = parent->generic;
+    p->max_pixels = parent->max_pixels; p->h_images = parent->h_images;
+    p->derived = true;
+    struct Guard { mj_plan *p; mj_context *c; ~Guard() { c->cur = nullptr; if (p) mj_plan_destroy(p); } } guard{p, ctx};
+    if (!ctx->free_arenas.empty()) { p->arena = ctx->free_arenas.back(); ctx->free_arenas.pop_back(); }
+    else if (hipHostMalloc((void **)&p->arena.base, (size_t)8 << 20, hipHostMallocDefault) == hipSuccess) p->arena.cap = (size_t)8 << 20;
+    else { (void)hipGetLastError(); p->arena = mj_context::Arena{}; }
+    p->arena.used = 0;
+    ctx->cur = p->arena.base ? &p->arena : nullptr;
+    if (int rc = resized_stages(q, f, p, parent->d_src, parent->src_bytes)) return rc;
+    // (the uploads above went through the arena on the setup stream: the plan's first use waits for them, as a decoding plan's does)
+    MJ_HIP(ctx, hipEventCreateWithFlags(&p->ready, hipEventDisableTiming));
+    MJ_HIP(ctx, hipEventRecord(p->ready, ctx->setup_stream));
+    MJ_HIP(ctx, hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    p->parent = parent;
+    ++parent->refs;
+    guard.p = nullptr;
+    *q.out = p;
     return MJ_OK;
 }
 
