@@ -195,7 +195,7 @@ int mj_context_wait_event(mj_context *ctx, void *hip_event);
  *
  * Order of operations on an image, whichever fields are set: decode (only what the windows need) -> mode -> orientation ->
  * affine transform -> window -> resize with the filter (to the place's size, onto the canvas) -> colour operations
- * (the `colour` field) -> mirror -> the output's element type.  In Pillow's terms the result is
+ * (the `colour` field) -> mirror -> the output's element type (-> erase: not a field, mj_plan_set_erase).  In Pillow's terms the result is
  * exif_transpose(img.convert(mode))[.transform(img.size, AFFINE or PERSPECTIVE, a, resample, fillcolor)].crop(window).resize(size, filter) —
  * with reducing_gap, Pillow's argument of that name to that resize.
  *
@@ -598,6 +598,53 @@ int mj_plan_create(mj_context *ctx, const mj_batch *batch, mj_plan **out);
  * calls as on any sized plan; MJ_ERR_INVALID from mj_plan_execute_stage1 / _stage2, mj_plan_write_coef, mj_plan_fill_coef,
  * mj_plan_fill_source (fill the parent's), mj_plan_tune_placement, mj_plan_time_stages / _execute and mj_plan_idct_levels. */
 int mj_plan_derive(mj_plan *parent, const mj_batch *batch, const mj_plan_request *request, mj_plan **out);
+/* Erase: boxes of the finished outputs overwritten — torchvision's RandomErasing / F.erase(img, i, j, h, w, v), whose whole body is
+ * img[..., i:i+h, j:j+w] = v, timm's RandomErasing with count > 1 (tools/erase_model.py).  It is the one step of the usual training
+ * recipes that comes AFTER Normalize, so it is not a field of mj_plan_request but a call on a sized plan (derived plans included)
+ * that says what to write over the output the plan's launches leave; the order of operations becomes decode -> mode ->
+ * orientation -> affine / perspective -> window -> resize / place / fill -> colour ops -> mirror -> element type -> ERASE.  Boxes are
+ * in the coordinates of what the caller receives — x along out_width, y along out_height, after the mirror — and the result
+ * equals, bit for bit, that of the plan without the call with those elements overwritten, in all four layouts.
+ *   rects          n records, host memory, copied into a plan-owned device buffer at the call.  The boxes of one output are applied
+ *                  in the order they are listed: where two overlap, the later one's elements stay.
+ *   MJ_ERASE_CONST value[c] for output component c (value[0] alone for one component), a float32 converted to the plan's dtype with
+ *                  one rounding to nearest even — torch.tensor(v) assigned into the tensor; MJ_DTYPE_U8: an integer 0..255
+ *   MJ_ERASE_VALUES  one element per element of the box: element (c, yy, xx) of the box is values_device[offset + (c * height +
+ *                  yy) * width + xx] — (C, height, width) order whatever the plan's layout —, elements of the plan's dtype in
+ *                  DEVICE memory.  values_device is BORROWED: the caller keeps it valid and unchanged until the executes that
+ *                  read it have finished.  Noise (torchvision's value="random", timm's mode="pixel") is the caller's to draw: no
+ *                  bit-exact reference exists for an in-library generator, so none is offered.  CutMix / MixUp, which mix across
+ *                  outputs and plans, are not offered either.
+ * n == 0 takes the erase off the plan again.  The call waits for the plan's latest execute, drops the plan's captured graph — the
+ * next execute launches plainly and a later one may capture again, with the new pointers — and from then on mj_plan_execute (and
+ * mj_plan_execute_stage2) queues the erase launch(es) last, behind the plan's final store, on the same stream, inside a capture
+ * too.  Only bytes inside boxes are written — 16-byte stores in the aligned body of every contiguous run, element stores at its
+ * ends, never a read-modify-write over a box's edge: the neighbouring elements may be another plan's slot, written on another
+ * stream at that moment.  The work is dealt out by a job list over the runs (csrc/erase_addr.h), so the grid follows the sum of
+ * the boxes; it is ONE launch where no two boxes of one output intersect, else one launch per box ordinal (box 0 of every
+ * output, then box 1, ...).  No LDS, no atomics, nothing synchronises with the host.
+ * MJ_ERR_INVALID, naming the box: a plan without a size; n < 0; NULL rects with n > 0; an output outside the plan's outputs; a box
+ * with a width or height below 1 or not inside out_width x out_height; a kind that is neither of the two; a CONST value that is
+ * not finite, or for MJ_DTYPE_U8 not an integer 0..255; a VALUES box with NULL values_device or a negative offset. */
+#define MJ_ERASE_CONST  0
+#define MJ_ERASE_VALUES 1
+typedef struct {
+    int32_t output;                /* the plan's output: view k, else image k; the launch addresses its slot */
+    int32_t x, y, width, height;   /* inside out_width x out_height, after the mirror */
+    int32_t kind;
+    float   value[3];              /* CONST: per output component; converted float32 -> the plan's dtype, nearest even; U8: an integer 0..255 */
+    int64_t offset;                /* VALUES: element offset of this box's (C, height, width) block in `values` */
+} mj_erase_rect;
+int mj_plan_set_erase(mj_plan *plan, int32_t n, const mj_erase_rect *rects, const void *values_device);
+/* The erase launch(es) of a plan alone (after an execute: into where it wrote), `iters` times: ms per run of all of them, and the
+ * bytes one run writes (VALUES boxes read as many).  MJ_ERR_INVALID: no erase set, nothing executed yet. */
+int mj_plan_time_erase(mj_plan *plan, int iters, float *ms, int64_t *bytes_written);
+/* The host twin of the erase launch (no context): the same records over a HOST array of n_slots slots of width x height pixels of
+ * ncomp (1 or 3) components of `dtype` in `layout` — `output` is the slot, `values` host memory —, through the launch's own address
+ * arithmetic (csrc/erase_addr.h).  MJ_ERR_INVALID (mj_last_error(NULL)): what mj_plan_set_erase refuses, an unknown layout or dtype,
+ * ncomp neither 1 nor 3, a size outside 1..65535, n_slots below 1, NULL. */
+int mj_host_erase(void *array, int32_t layout, int32_t dtype, int32_t ncomp, int32_t width, int32_t height, int32_t n_slots, int32_t n,
+                  const mj_erase_rect *rects, const void *values);
 /* The host twin of the kernels' mode conversion (no context): n_pixels pixels of src_ncomp (1 or 3) interleaved components into
  * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
  * is neither 1 nor 3, NULL with pixels to convert. */

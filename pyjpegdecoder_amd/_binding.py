@@ -56,6 +56,7 @@ EXPORTS = (
     "mj_host_resize_table_boxed", "mj_host_reduce_factors", "mj_host_reduce", "mj_debug_reduce_shape", "mj_debug_normalise_request",
     "mj_plan_time_reduce", "mj_host_affine", "mj_host_perspective", "mj_plan_time_affine", "mj_debug_reduce_launch", "mj_host_colour_ops", "mj_plan_time_colour",
     "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables", "mj_plan_derive",
+    "mj_plan_set_erase", "mj_plan_time_erase", "mj_host_erase",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -142,6 +143,50 @@ class ColourOpC(ctypes.Structure):
 class ColourChainC(ctypes.Structure):
     """mj_colour_chain: one output's ops, applied in order (n == 0: none)."""
     _fields_ = [("n", ctypes.c_int32), ("op", ColourOpC * MJ_COLOUR_MAX_OPS)]
+
+
+MJ_ERASE_CONST, MJ_ERASE_VALUES = 0, 1
+
+
+class EraseRectC(ctypes.Structure):
+    """mj_erase_rect: one box of mj_plan_set_erase / mj_host_erase."""
+    _fields_ = [("output", ctypes.c_int32), ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("kind", ctypes.c_int32), ("value", ctypes.c_float * 3), ("offset", ctypes.c_int64)]
+
+
+def erase_rects(rects):
+    """an array of mj_erase_rect from (output, x, y, width, height, value) records — value: up to three numbers (MJ_ERASE_CONST, one
+    per output component) or an int element offset wrapped as ``("values", offset)`` (MJ_ERASE_VALUES) —, from ready EraseRectC's, or
+    from a NumPy array of ERASE_RECT_DTYPE records (made in bulk: batch.py's).  Returns (what the C call takes, what keeps it alive)."""
+    if isinstance(rects, np.ndarray) and rects.dtype == ERASE_RECT_DTYPE:
+        rects = np.ascontiguousarray(rects)
+        return ctypes.cast(rects.ctypes.data, ctypes.POINTER(EraseRectC)), rects
+    arr = (EraseRectC * max(1, len(rects)))()
+    _fill_erase_rects(arr, rects)
+    return arr, arr
+
+
+# mj_erase_rect as a NumPy record: a list of tuples (output, x, y, width, height, kind, value[3], offset) becomes the array in one call
+ERASE_RECT_DTYPE = np.dtype([("output", "<i4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("kind", "<i4"),
+                             ("value", "<f4", (3,)), ("offset", "<i8")], align=True)
+assert ERASE_RECT_DTYPE.itemsize == ctypes.sizeof(EraseRectC)
+
+
+def _fill_erase_rects(arr, rects):
+    for k, r in enumerate(rects):
+        if isinstance(r, EraseRectC):
+            arr[k] = r
+            continue
+        out, x, y, w, h, value = r
+        arr[k].output, arr[k].x, arr[k].y, arr[k].width, arr[k].height = int(out), int(x), int(y), int(w), int(h)
+        if isinstance(value, tuple) and len(value) == 2 and value[0] == "values":
+            arr[k].kind, arr[k].offset = MJ_ERASE_VALUES, int(value[1])
+        else:
+            vals = [float(v) for v in (value if isinstance(value, (list, tuple)) else [value] * 3)]
+            arr[k].kind = MJ_ERASE_CONST
+            for c, v in enumerate(vals[:3]):
+                arr[k].value[c] = v
+    return arr
 
 
 class PlanRequestC(ctypes.Structure):
@@ -232,6 +277,9 @@ def load_library():
     L.mj_host_colour_ops.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ColourChainC), vp]
     L.mj_host_perspective.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_double), i32, vp, i32, i32, i32, i32, vp]
     L.mj_plan_time_affine.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
+    L.mj_plan_set_erase.argtypes = [vp, i32, ctypes.POINTER(EraseRectC), vp]
+    L.mj_plan_time_erase.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
+    L.mj_host_erase.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(EraseRectC), vp]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
@@ -488,6 +536,53 @@ def colour_ops(a: np.ndarray, chain) -> np.ndarray:
     if load_library().mj_host_colour_ops(_ptr(a), w, h, nc, ctypes.byref(c), _ptr(out)) != MJ_OK:
         raise ValueError("mj_host_colour_ops: bad arguments")
     return out
+
+
+def host_erase(a: np.ndarray, layout: int, dtype: str, ncomp: int, width: int, height: int, n_slots: int, rects, values=None,
+               offset: int = 0) -> None:
+    """mj_host_erase (host only): the erase launch's records over the host array ``a``, IN PLACE — ``a`` holds, from element
+    ``offset`` on, ``n_slots`` slots of width x height pixels of ``ncomp`` components of ``dtype`` (bfloat16: uint16 bit patterns)
+    in MJ_LAYOUT_* ``layout``; ``rects``: :func:`erase_rects`' records with the slot as output; ``values``: the array MJ_ERASE_VALUES
+    offsets point into, elements of ``dtype``.  ValueError with the library's message for what it refuses."""
+    if not a.flags["C_CONTIGUOUS"] or a.itemsize != DTYPE_BYTES[dtype]:
+        raise ValueError("mj_host_erase: a contiguous array of the dtype's element size")
+    L = load_library()
+    arr, _keep = erase_rects(rects)
+    base = ctypes.c_void_p(a.ctypes.data + int(offset) * a.itemsize)
+    if L.mj_host_erase(base, int(layout), DTYPES[dtype], int(ncomp), int(width), int(height), int(n_slots), len(rects), arr,
+                       _ptr(values)) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+
+
+class DeviceBytes:
+    """A block of device memory of the HIP runtime's own (hipMalloc), filled from a host array: what the NumPy route keeps the values
+    of ``erase=`` in — no torch there.  ``ptr`` is the device address; close() frees it."""
+
+    def __init__(self, host: np.ndarray):
+        load_library()                          # (the runtime libmijpeg.so bound to is the process's)
+        self._hip = ctypes.CDLL("libamdhip64.so")
+        self._hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        self._hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        self._hip.hipFree.argtypes = [ctypes.c_void_p]
+        host = np.ascontiguousarray(host)
+        p = ctypes.c_void_p()
+        if self._hip.hipMalloc(ctypes.byref(p), max(16, host.nbytes)) != 0:
+            raise BackendError("hipMalloc failed for the values of erase=")
+        self.ptr = p.value
+        if host.nbytes and self._hip.hipMemcpy(p, _ptr(host), host.nbytes, 1) != 0:       # hipMemcpyHostToDevice
+            self.close()
+            raise BackendError("hipMemcpy failed for the values of erase=")
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self._hip.hipFree(ctypes.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def normalize_table(dtype: str, mean: float = 0.0, std: float = 1.0) -> np.ndarray:
@@ -842,6 +937,20 @@ class Plan:
         (mj_plan_time_colour)."""
         ms, nb = ctypes.c_float(), ctypes.c_int64()
         self.ctx.check(self.ctx.lib.mj_plan_time_colour(self.handle, iters, ctypes.byref(ms), ctypes.byref(nb)))
+        return ms.value, nb.value
+
+    def set_erase(self, rects, values_device: int = 0, keep=None):
+        """mj_plan_set_erase: ``rects`` (:func:`erase_rects`' records; ``[]`` takes the erase off again) are what every execute from
+        now on overwrites last; ``values_device``: the device address MJ_ERASE_VALUES offsets point into, elements of the plan's
+        dtype — borrowed: ``keep`` (whatever owns that memory) is held by this plan until the next set_erase or close()."""
+        arr, _keep = erase_rects(rects)
+        self.ctx.check(self.ctx.lib.mj_plan_set_erase(self.handle, len(rects), arr, values_device or None))
+        self._erase_keep = keep
+
+    def time_erase(self, iters: int = 10):
+        """(ms per run of the erase launches, bytes one run writes) of a plan with boxes set that has been executed (mj_plan_time_erase)."""
+        ms, nb = ctypes.c_float(), ctypes.c_int64()
+        self.ctx.check(self.ctx.lib.mj_plan_time_erase(self.handle, iters, ctypes.byref(ms), ctypes.byref(nb)))
         return ms.value, nb.value
 
     def time_reduce(self, iters: int = 10) -> float:

@@ -674,7 +674,7 @@ def select_union_files(files: Sequence[bytes], groups: Sequence[dict]):
 
 
 # the keys of an entry of ``also``: what is per output and never inherited, and what is the call's unless the entry says otherwise
-ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops")
+ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase")
 ALSO_CALL_WIDE = ("dtype", "normalize", "resample", "mode", "reducing_gap", "fill", "affine_resample", "affine_fill")
 
 
@@ -729,6 +729,7 @@ def normalize_also(also, call: dict, size, rois=None, return_seams: bool = False
             normalize_fill(g["fill"], g["resize_to"])
             normalize_transform(g["affine"], g["perspective"], g["affine_resample"], g["affine_fill"], g["size"], None, gap)
             normalize_color_ops(g["color_ops"], g["size"])
+            normalize_erase(g["erase"], g["size"], device=None if host else -1)
             if g["views"] is not None and not isinstance(g["views"], (list, tuple)):
                 normalize_views(g["views"], [], g["size"])
         except ValueError as e:
@@ -1075,6 +1076,174 @@ def normalize_color_ops(color_ops, size, n_outputs: Optional[int] = None, return
     return chains
 
 
+def _is_tensor(v) -> bool:
+    """a torch tensor, told without importing torch (the NumPy route does not need it)"""
+    return type(v).__module__.split(".")[0] == "torch" and hasattr(v, "data_ptr")
+
+
+def _is_erase_box(b) -> bool:
+    """a box is a tuple whose first element is not itself a sequence: that tells one box from a list of boxes"""
+    return isinstance(b, tuple) and len(b) > 0 and not isinstance(b[0], (list, tuple))
+
+
+def normalize_erase(erase, size, n_outputs: Optional[int] = None, ncomp: Optional[int] = None, dtype: Optional[str] = None,
+                    return_seams: bool = False, device: Optional[int] = None):
+    """``erase`` of a call, checked: None for a call without it — ``erase`` None, or entries that are all None or empty, which make
+    the request of a call without the argument — else a list with, per OUTPUT, None or a tuple of boxes ``(x, y, width, height, value)``.
+
+    ``erase``: None, or a list with one entry per output (per file; per view with ``views``); there is no one-for-all form.  An entry
+    is None, one box, or a list of boxes applied in order — a later box wins where two overlap (timm's ``count > 1``).  A box is a
+    tuple ``(x, y, width, height)`` or ``(x, y, width, height, value)``, integers, ``x`` along the width as in ``rois`` (not
+    torchvision's ``(i, j, h, w)``), wholly inside the ``size`` canvas: torchvision's ``F.erase``, ``img[..., y:y+height, x:x+width] =
+    value``, on the finished output — after the mirror, in the output's ``dtype`` (tools/erase_model.py).  ``value``: absent or a
+    number — every component gets it (0 when absent), as float32 first (``torch.tensor(value)``), then the output's type; a sequence
+    of ``ncomp`` numbers — one per output component; an array or tensor of shape ``(ncomp, height, width)`` — one value per element,
+    always in that order whatever the decoder's layout, converted from its own type with one rounding (``v.to(dtype)``): the noise of
+    torchvision's ``value="random"`` / timm's ``mode="pixel"``, which the caller draws.  NumPy arrays everywhere; torch tensors, CPU
+    or on the decoder's GPU (``device``: its index; None: the NumPy route), on the ``decode_device`` calls.  For a uint8 output
+    numbers are integers 0..255 and arrays uint8.  The returned value is a tuple of ``ncomp`` floats (float32 values) or the array —
+    with ``ncomp`` None a lone number stays one float, which :func:`erase_for_components` completes once the count is known.
+
+    ``erase`` needs ``size`` and does not go with ``return_seams``.  ``n_outputs`` / ``ncomp`` / ``dtype`` None: not known yet — what
+    needs them is not checked.  ValueError, naming output and box, otherwise."""
+    if erase is None:
+        return None
+    if size is None:
+        raise ValueError("erase needs size=(width, height): boxes are in the coordinates of the finished canvas")
+    if return_seams:
+        raise ValueError("erase and return_seams do not go together: the seam outputs are the decoded images")
+    if not isinstance(erase, (list, tuple)) or (isinstance(erase, tuple) and len(erase) in (4, 5) and _is_int(erase[0])):
+        raise ValueError(f"erase must be None or a list with, per output, None, one box (x, y, width, height[, value]) or a list of boxes "
+                         f"(there is no one-for-all form), not {erase!r}")
+    if n_outputs is not None and len(erase) != n_outputs:
+        raise ValueError(f"erase has {len(erase)} entries for {n_outputs} outputs")
+    W, H = size
+    u8 = dtype == "uint8"
+
+    def number(v, where) -> float:
+        if type(v) is not float and type(v) is not int and not _is_number(v):
+            raise ValueError(f"erase: {where()}: a value is a number, {ncomp or 'one per component'} numbers or an array of shape (C, height, width), "
+                             f"not {v!r}")
+        f = ctypes.c_float(v).value             # (the nearest float32, as torch.tensor(v) holds it; too large: infinity)
+        if f - f != 0.0:
+            raise ValueError(f"erase: {where()}: value {v!r} is not finite (as float32)")
+        if u8 and (f != int(f) or not 0 <= f <= 255):
+            raise ValueError(f"erase: {where()}: a uint8 output takes integers 0..255, not {v!r}")
+        return f
+
+    def box(b, k, j):
+        def where():
+            return f"output {k}, box {j}"
+        if type(b) is not tuple or not 4 <= len(b) <= 5:
+            raise ValueError(f"erase: {where()}: a box is (x, y, width, height) or (x, y, width, height, value), not {b!r}")
+        x, y, w, h = b[0], b[1], b[2], b[3]
+        if not (type(x) is int and type(y) is int and type(w) is int and type(h) is int):
+            if not all(_is_int(t) for t in b[:4]):
+                raise ValueError(f"erase: {where()}: x, y, width and height must be integers, not {b[:4]!r}")
+            x, y, w, h = int(x), int(y), int(w), int(h)
+        if w < 1 or h < 1:
+            raise ValueError(f"erase: {where()}: width and height must be at least 1, not {w} x {h}")
+        if x < 0 or y < 0 or x + w > W or y + h > H:
+            raise ValueError(f"erase: {where()}: box ({x}, {y}, {w}, {h}) is not inside the {W} x {H} canvas")
+        v = b[4] if len(b) == 5 and b[4] is not None else 0
+        if type(v) is float or type(v) is int:
+            f = number(v, where)
+            return (x, y, w, h, (f,) * ncomp if ncomp else f)
+        if isinstance(v, np.ndarray) and v.ndim == 0:
+            v = v.item()
+        if isinstance(v, np.ndarray) or _is_tensor(v):
+            if _is_tensor(v):
+                if device is None:
+                    raise ValueError(f"erase: {where()}: a torch tensor is accepted on the decode_device calls; decode takes NumPy arrays")
+                if v.device.type != "cpu" and device >= 0 and v.device.index != device:       # (device < 0: some GPU, not known yet)
+                    raise ValueError(f"erase: {where()}: values on {v.device}, not on the CPU or the decoder's GPU cuda:{device}")
+            shape = tuple(v.shape)
+            if len(shape) == 1 and shape[0] <= 3 and not _is_tensor(v):
+                v = v.tolist()                # (a short vector: numbers per component)
+            else:
+                if len(shape) != 3 or shape[1] != h or shape[2] != w or (ncomp is not None and shape[0] != ncomp) or shape[0] not in (1, 3):
+                    raise ValueError(f"erase: {where()}: values of shape {tuple(int(t) for t in shape)} for a box of ({ncomp if ncomp is not None else 'C'}, {h}, {w})")
+                name = str(v.dtype).split(".")[-1]
+                if u8 and name != "uint8":
+                    raise ValueError(f"erase: {where()}: a uint8 output takes uint8 arrays, not {v.dtype}")
+                if not u8 and name not in ("uint8", "float16", "bfloat16", "float32", "float64"):
+                    raise ValueError(f"erase: {where()}: values of type {v.dtype}; uint8, float16, bfloat16, float32 or float64 are taken")
+                return (x, y, w, h, v)
+        if isinstance(v, (list, tuple)):
+            if (ncomp is not None and len(v) != ncomp) or len(v) not in (1, 3):
+                raise ValueError(f"erase: {where()}: {len(v)} values for {ncomp if ncomp is not None else '1 or 3'} component(s)")
+            return (x, y, w, h, tuple(number(t, where) for t in v))
+        f = number(v, where)
+        return (x, y, w, h, (f,) * ncomp if ncomp else f)
+
+    out, some = [], False
+    for k, entry in enumerate(erase):
+        if entry is None:
+            out.append(None)
+            continue
+        if _is_erase_box(entry):
+            boxes = (box(entry, k, 0),)
+        elif isinstance(entry, (list, tuple)):
+            boxes = tuple(box(b, k, j) for j, b in enumerate(entry))
+        else:
+            raise ValueError(f"erase: output {k}: an entry is None, one box or a list of boxes, not {entry!r}")
+        out.append(boxes or None)
+        some = some or bool(boxes)
+    return out if some else None
+
+
+def erase_for_components(erase, ncomp: int):
+    """:func:`normalize_erase`'s boxes, checked before the files' component count was known, for outputs of ``ncomp`` components: a
+    number stands for all of them, and per-component values and arrays must have that many.  ValueError, naming output and box."""
+    if erase is None:
+        return None
+    out = []
+    for k, boxes in enumerate(erase):
+        if boxes is None:
+            out.append(None)
+            continue
+        done = []
+        for j, b in enumerate(boxes):
+            v = b[4]
+            if type(v) is float:                # (one number: every component gets it)
+                done.append(b[:4] + ((v,) * ncomp,))
+                continue
+            n = len(v) if type(v) is tuple else int(v.shape[0])
+            if n != ncomp:
+                if type(v) is tuple:
+                    raise ValueError(f"erase: output {k}, box {j}: {n} values for {ncomp} component(s)")
+                else:
+                    raise ValueError(f"erase: output {k}, box {j}: values of shape {tuple(int(t) for t in v.shape)} for a box of ({ncomp}, {b[3]}, {b[2]})")
+            done.append(b)
+        out.append(tuple(done))
+    return out
+
+
+def random_erasing_rect(size, scale=(0.02, 0.33), ratio=(0.3, 3.3), generator=None) -> Optional[Tuple[int, int, int, int]]:
+    """A box for ``erase=`` drawn as torchvision's ``RandomErasing.get_params`` draws it for a ``size = (width, height)`` canvas:
+    ``(x, y, w, h)``, or None when ten tries find none.  Restated: up to ten tries, each drawing the area — ``H * W`` times a uniform
+    ``torch.empty(1).uniform_(scale[0], scale[1])`` — and then the aspect ratio, log-uniform between ``ratio[0]`` and ``ratio[1]``;
+    ``h = int(round(sqrt(area * aspect)))``, ``w = int(round(sqrt(area / aspect)))``; the box is taken if ``h < H and w < W``, its
+    corner from two ``torch.randint`` draws (the row first).  torchvision is not a dependency here and this function is NOT pinned
+    to its draws: the same seed need not give torchvision's box (it passes no generator, for one).  Whether to erase at all
+    (``p``) and the value are the caller's."""
+    import torch
+    W, H = (int(t) for t in size)
+    area = H * W
+    log_ratio = torch.log(torch.tensor([float(ratio[0]), float(ratio[1])]))
+    for _ in range(10):
+        erase_area = area * torch.empty(1).uniform_(float(scale[0]), float(scale[1]), generator=generator).item()
+        aspect = torch.exp(torch.empty(1).uniform_(log_ratio[0].item(), log_ratio[1].item(), generator=generator)).item()
+        h = int(round(math.sqrt(erase_area * aspect)))
+        w = int(round(math.sqrt(erase_area / aspect)))
+        if not (h < H and w < W) or h < 1 or w < 1:     # (a side that rounds to 0 erases nothing in torchvision; here it is a failed try)
+            continue
+        i = int(torch.randint(0, H - h + 1, size=(1,), generator=generator).item())
+        j = int(torch.randint(0, W - w + 1, size=(1,), generator=generator).item())
+        return (j, i, w, h)
+    return None
+
+
 def rotation_matrix(angle: float, size: Tuple[int, int], center=None, translate=None) -> Tuple[float, ...]:
     """The matrix ``Image.rotate(angle, center=center, translate=translate)`` builds for ``expand=False`` on an image of ``size`` =
     (width, height) — counter-clockwise by ``angle`` degrees around ``center`` (None: the image's centre), then moved by
@@ -1301,6 +1470,7 @@ class _Request:
     views: Optional[List[Tuple[int, Tuple[int, int, int, int]]]] = None
     affine: Optional[AffineSpec] = None         # :func:`normalize_transform`'s, affine or perspective (None: no transform); always with ``views``
     colour: Optional[List[Optional[tuple]]] = None      # :func:`normalize_color_ops`' chains, one or None per OUTPUT (None: no operations)
+    erase: Optional[List[Optional[tuple]]] = None       # :func:`normalize_erase`'s boxes, a tuple or None per OUTPUT (None: no box anywhere)
     # the extra groups of a call with ``also``: requests over the SAME files, index and orientations, each with its own size, views, output,
     # tensor and slots (None: a call without).  A group with views need not name every file here; what it has none of it is left out of.
     also: Optional[List["_Request"]] = None
@@ -1331,7 +1501,7 @@ class _Request:
         if orient is not None and all(o == 1 for o in orient):
             orient = None
 
-        def chains(picked):                 # (outputs without operations: the request of a call without color_ops)
+        def chains(picked):                 # (outputs without operations / boxes: the request of a call without color_ops / erase)
             return picked if picked is not None and any(c is not None for c in picked) else None
         also = [g.narrow(idxs) for g in self.also] if self.also is not None else None      # (every group follows the files)
         if self.views is not None:
@@ -1347,10 +1517,10 @@ class _Request:
                 affine = None
             return _Request(pick(self.files), None, self.size, self.output.for_files(vk) if self.output else None, self.dest, pick_view(self.slots),
                             pick(index), orient, self.resample, self.mode, pick_view(self.places), self.fill, self.reducing_gap,
-                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine, chains(pick_view(self.colour)), also=also)
+                            [(pos[self.views[k][0]], self.views[k][1]) for k in vk], affine, chains(pick_view(self.colour)), chains(pick_view(self.erase)), also=also)
         return _Request(pick(self.files), pick(self.wins), self.size, self.output.for_files(idxs) if self.output else None,
                         self.dest, pick(self.slots), pick(index), orient, self.resample, self.mode, pick(self.places), self.fill, self.reducing_gap,
-                        colour=chains(pick(self.colour)), also=also)
+                        colour=chains(pick(self.colour)), erase=chains(pick(self.erase)), also=also)
 
     def orient_classes(self) -> List[List[int]]:
         """its files (indices) sorted by :func:`_orient_class`: what cannot share a plan because of its orientation — and, in a
@@ -1552,17 +1722,57 @@ class BatchDecoder:
         native = prep.shapes[0][2] if prep.shapes else None
         return B.Plan(self.ctx, prep.to_c(blob_device_ptr), {"prep": prep, "n_images": len(req.files)}, **req.plan_kwargs(native))
 
-    def _group_plans(self, req: _Request, prep: PreparedBatch, blob_device_ptr: int = 0) -> list:
+    def _set_erase(self, g: _Request, plan: B.Plan, native: Optional[int], host: bool) -> None:
+        """Group ``g``'s boxes (:func:`normalize_erase`) onto its plan (mj_plan_set_erase): output k of the plan is output k of ``g``.
+        All blocks of values go into ONE array of the output's type — host arrays converted and concatenated on the host and uploaded
+        once, device tensors converted where they are, one ``torch.cat`` on torch's current stream, which the stream the plan
+        executes on is made to wait for before the execute — that the plan holds until it is closed.  ``host``: the NumPy route,
+        whose array lives in a block of the HIP runtime's own."""
+        dtype = g.output.dtype if g.output else "uint8"
+        # mj_erase_rect records as tuples (output, x, y, width, height, kind, value[3], offset), made into the array in one call
+        rects, blocks = [], []                  # blocks: (record, values), host ones first below
+        for k, boxes in enumerate(g.erase):
+            for (x, y, w, h, v) in boxes or ():
+                if type(v) is tuple:
+                    rects.append((k, x, y, w, h, B.MJ_ERASE_CONST, v + (0.0,) * (3 - len(v)), 0))
+                else:
+                    blocks.append((len(rects), v))
+                    rects.append((k, x, y, w, h, B.MJ_ERASE_VALUES, (0.0, 0.0, 0.0), 0))
+        if not blocks:
+            plan.set_erase(np.array(rects, dtype=B.ERASE_RECT_DTYPE))
+            return
+        on_host = [(r, v) for r, v in blocks if not _is_tensor(v) or v.device.type == "cpu"]
+        on_device = [(r, v) for r, v in blocks if _is_tensor(v) and v.device.type != "cpu"]
+        off = 0
+        for r, v in on_host + on_device:
+            rects[r] = rects[r][:7] + (off,)
+            off += int(v.shape[0]) * int(v.shape[1]) * int(v.shape[2])
+        rects = np.array(rects, dtype=B.ERASE_RECT_DTYPE)
+        if host:
+            flat = np.concatenate([np.ascontiguousarray(v).astype(np.dtype(dtype)).reshape(-1) for _, v in on_host])
+            values = B.DeviceBytes(flat)
+            plan.set_erase(rects, values.ptr, keep=values)
+            return
+        import torch
+        tdt, dev = getattr(torch, dtype), torch.device("cuda", self.ctx.device)
+        parts = []
+        if on_host:
+            cpu = [(v if _is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))).to(tdt).reshape(-1) for _, v in on_host]
+            parts.append((torch.cat(cpu) if len(cpu) > 1 else cpu[0]).to(dev))
+        parts += [v.to(tdt).reshape(-1) for _, v in on_device]
+        values = torch.cat(parts)               # (a copy even of one block: the caller's tensor is free when the call returns)
+        plan.set_erase(rects, values.data_ptr(), keep=values)
+
+    def _group_plans(self, req: _Request, prep: PreparedBatch, blob_device_ptr: int = 0, host: bool = False) -> list:
         """The plans of a request whose files are ``prep``'s, in order, as (group's request, plan): the first group that has outputs
         among these files makes the plan that decodes, every later one that has some derives from it (mj_plan_derive) and reads its
-        decoded images; a group with none is left out.  A request without extra groups: its one plan."""
-        if req.also is None:
-            return [(req, self._plan(req, prep, blob_device_ptr))]
+        decoded images; a group with none is left out.  A request without extra groups: its one plan.  A group with boxes
+        (``erase``) has them put on its plan here (:meth:`_set_erase`); ``host``: for the NumPy route."""
         native = prep.shapes[0][2] if prep.shapes else None
         plans = []
         try:
             for g in req.groups:
-                if g.n_outputs == 0:
+                if g.n_outputs == 0 and req.also is not None:
                     continue
                 if not plans:
                     plans.append((g, self._plan(g, prep, blob_device_ptr)))
@@ -1570,6 +1780,9 @@ class BatchDecoder:
                 kw = g.plan_kwargs(native)
                 kw.pop("rois")                  # (None: an extra group's windows are views)
                 plans.append((g, plans[0][1].derive(prep, **kw)))
+            for g, plan in plans:               # (every plan erases the outputs it writes: second rounds and derived plans too)
+                if g.erase is not None:
+                    self._set_erase(g, plan, native, host)
         except BaseException:
             for _, p in reversed(plans):
                 p.close()
@@ -1611,7 +1824,7 @@ class BatchDecoder:
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1685,6 +1898,14 @@ class BatchDecoder:
         included —, as a Pillow image of the output's mode, bit for bit; then the mirror and the element type.  An output whose
         chain is None or empty is the output of the call without the argument.  Not with ``return_seams``; autocontrast's
         cutoffs and masks, and more than four ops are not offered yet.
+        ``erase``, with ``size``: RandomErasing on the finished outputs (:func:`normalize_erase`, tools/erase_model.py) — None, or a list
+        with one entry per output (per file; per view with ``views``): None, one box ``(x, y, width, height[, value])`` or a list of
+        boxes applied in order.  It comes LAST — decode, mode, orientation, affine, window, resize / place / fill, colour ops, mirror,
+        element type, erase — and is torchvision's ``F.erase``, ``img[..., y:y+height, x:x+width] = value``, on output k in its ``dtype``,
+        boxes in the coordinates of what the call returns: bit for bit the call without the argument with those elements overwritten.
+        ``value``: absent (0) or a number, one number per component, or a ``(C, height, width)`` NumPy array (noise, which the caller
+        draws).  One more launch per plan (csrc/erase.hip), on every plan of the call, second rounds included.  Not with
+        ``return_seams``; an ``also`` entry takes a key ``erase`` of its own.
         ``also``, with ``size``: several groups of outputs from ONE decode (:func:`normalize_also`) — None or ``[]`` (the call as it
         is), else a list with one dict per extra group: ``size`` (required) and that group's own ``views``, ``mirror``, ``resize_to``,
         ``place``, ``affine``, ``perspective`` and ``color_ops`` (None when absent, never the call's); ``dtype``, ``normalize``,
@@ -1696,7 +1917,7 @@ class BatchDecoder:
         ``return_seams``."""
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective)
+                    perspective=perspective, erase=erase)
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -1738,7 +1959,7 @@ class BatchDecoder:
             item = work.pop(0)
             idxs, sub = item.idxs, req.narrow(item.idxs)
             prep = prepare_batch(sub.files, self.layout, flags | item.flags, [parsed[i] for i in idxs])
-            plans = self._group_plans(sub, prep)
+            plans = self._group_plans(sub, prep, host=True)
             plan = plans[0][1]
             try:
                 for _, p in plans:              # (the derived plans right behind the plan that decodes, on the context's stream)
@@ -1790,7 +2011,7 @@ class BatchDecoder:
 
     def _host_request(self, files: Sequence[bytes], cache: Dict[int, ParsedJpeg], gpu_segment: Optional[bool], rois=None, return_seams: bool = False,
                       size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None,
-                      fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None):
+                      fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, erase=None):
         """The checked request of a :meth:`decode` call, or of one group of it, and the array it fills (None without ``size``).  ``cache``:
         the parsed files by their position in ``files``, filled with those this request names; ``gpu_segment``: whether they are parsed
         headers only (None: decided by the files this request names)."""
@@ -1801,6 +2022,9 @@ class BatchDecoder:
         spec = normalize_transform(affine, perspective, affine_resample, affine_fill, size,
                                    len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap, return_seams)
         colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files), return_seams)
+        # (before any file is read: everything but what the files' component count decides)
+        boxes = normalize_erase(erase, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES[mode] if mode else None,
+                                dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None                            # views: where the files that are read sit in the caller's list
@@ -1834,6 +2058,7 @@ class BatchDecoder:
             req.fill = normalize_fill(fill, resize_to, nc)
             if spec is not None:
                 req.affine = _spec_for_outputs(spec, size, req.n_outputs, nc)
+            req.erase = erase_for_components(boxes, nc)
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         return req, dense
 
@@ -1847,13 +2072,18 @@ class BatchDecoder:
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
                         resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                        affine_fill=None, color_ops=None, perspective=None) -> _Request:
+                        affine_fill=None, color_ops=None, perspective=None, erase=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
         spec = normalize_transform(affine, perspective, affine_resample, affine_fill, size,
                                    len(views) if isinstance(views, (list, tuple)) else len(files), reducing_gap)
         colour = normalize_color_ops(color_ops, size, len(views) if isinstance(views, (list, tuple)) else len(files))
+        # (before any file is read: everything but what the files' component count decides)
+        boxes = None
+        if erase is not None:
+            boxes = normalize_erase(erase, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES.get(mode) if isinstance(mode, str) else None,
+                                    dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", device=self.ctx.device)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None
@@ -1880,6 +2110,7 @@ class BatchDecoder:
                 req.places = normalize_places(resize_to, place, size, [w[2:] for w in req.wins] if req.wins is not None else odims)
             req.output = normalize_output(dtype, normalize, mirror, size, req.n_outputs, nc)
             req.fill = normalize_fill(fill, resize_to, nc)
+            req.erase = erase_for_components(boxes, nc)
             req.dest = torch.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
             req.slots = list(range(req.n_outputs))
@@ -1898,7 +2129,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -1942,7 +2173,10 @@ class BatchDecoder:
         GPU —, which store into the one tensor; plans whose outputs have none are the plans of a call without the argument.
         ``also`` as in :meth:`decode`: a tuple of tensors, one per group.  Every plan of the call (files of several kinds and
         orientation classes, second rounds, parts) is made by the first group that has outputs among its files; every later group
-        that has some derives a plan from it, executed right behind it on the same stream into that group's tensor."""
+        that has some derives a plan from it, executed right behind it on the same stream into that group's tensor.
+        ``erase`` as in :meth:`decode`; a box's ``(C, height, width)`` values may also be a torch tensor, on the CPU or on this decoder's
+        GPU.  Every plan of the call erases the outputs it writes as its last launch; its blocks of values go into one tensor of the
+        output's type (host arrays uploaded once, one ``torch.cat``) that the plan holds until it is collected."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -1952,7 +2186,7 @@ class BatchDecoder:
         normalize_fill(fill, resize_to)
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective)
+                    perspective=perspective, erase=erase)
         extra = normalize_also(also, main, size, rois)
         if extra is None:
             req = self._device_request(files, rois, orientation=orientation, **main)
@@ -2080,7 +2314,7 @@ class BatchDecoder:
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None, color_ops=None, perspective=None, also=None):
+                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -2106,13 +2340,17 @@ class BatchDecoder:
         iterable that yields one value per batch, as ``affine`` does; not together with ``affine``.  ``color_ops``: None, one chain for every output of every batch, or an iterable that yields, batch by
         batch, what :meth:`decode_device` takes for that batch.  ``also``: None, or an iterable that yields, batch by batch, what
         :meth:`decode_device` takes for that batch — a list with one dict per extra group; every batch is then handed out as a tuple
-        of tensors, one per group."""
+        of tensors, one per group.  ``erase``: None, or an iterable that yields, batch by batch, what :meth:`decode_device` takes for
+        that batch — a list with one entry per output, or None."""
         size = normalize_size(size)
         if also is not None and isinstance(also, (list, tuple)) and len(also) == 0:
             also = None                                                               # (no extra group: a call without the argument)
         if also is not None and size is None:
             raise ValueError("also needs size=(width, height): every group of outputs is one array at its own size")
         per_batch_also = iter(also) if also is not None else None
+        if erase is not None and size is None:
+            raise ValueError("erase needs size=(width, height): boxes are in the coordinates of the finished canvas")
+        per_batch_erase = iter(erase) if erase is not None else None
         normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
         per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
@@ -2178,6 +2416,12 @@ class BatchDecoder:
                         c = next(per_batch_colour)
                     except StopIteration:
                         raise ValueError("color_ops yields fewer entries than there are batches") from None
+                er = None
+                if per_batch_erase is not None:
+                    try:
+                        er = next(per_batch_erase)
+                    except StopIteration:
+                        raise ValueError("erase yields fewer entries than there are batches") from None
                 def none(g):
                     return g is None or (isinstance(g, (list, tuple)) and all(e is None for e in g))
                 if per_batch_also is not None:
@@ -2188,17 +2432,17 @@ class BatchDecoder:
                     plain = none(t) and none(ps)
                     main = dict(size=size, dtype=dtype, normalize=normalize, mirror=m, resample=resample, mode=mode, resize_to=resize_to, place=place,
                                 fill=fill, reducing_gap=reducing_gap, views=v, affine=None if none(t) else t, affine_resample=None if plain else affine_resample,
-                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps)
+                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er)
                     extra = normalize_also(a, dict(main, affine_resample=affine_resample, affine_fill=affine_fill), size)
                     if extra is not None:
                         yield self._merged_request(files, o, [main] + extra, lambda fs, **kw: self._device_request(fs, None, **kw))
                         continue
                 if none(t) and none(ps):                # (a batch without a transform)
                     yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                               color_ops=c)
+                                               color_ops=c, erase=er)
                     continue
                 yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps)
+                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -396,7 +396,7 @@ static int resize_launch(mj_plan *p, hipStream_t s) {
         c.dst = p->last_rgb;
         MJ_HIP(p->ctx, mj::launch_colour(s, c, p->co_blur, p->co_hue));
     }
-    return MJ_OK;
+    return mj::erase_execute(p, s);     // (mj_plan_set_erase: boxes of the finished output, behind its last store)
 }
 
 static int stage2_impl(mj_plan *p, void *stream, uint8_t *rgb_device) {

@@ -13,6 +13,7 @@
 
 #include "mijpeg_internal.h"
 #include "form_select.h"
+#include "erase_addr.h"
 
 // Device buffers of destroyed plans, kept by the context for the next plan.  A decode service creates one plan per
 // batch; hipMalloc / hipFree of its multi-gigabyte coefficient store every time costs more than the decode (the
@@ -312,6 +313,17 @@ struct mj_plan {
     mj::ColourArgs co{};
     mj::ColourBlurArgs co_blur{};
     mj::ColourHueArgs co_hue{};
+    // erase (mj_plan_set_erase): boxes of the finished outputs overwritten by one more launch — or one per box ordinal where boxes of
+    // one output intersect — behind everything else resize_launch queues (erase.hip).  What a sized plan's maker leaves for it:
+    // the output's components and MJ_DTYPE_*, the array's slots and every output's slot (h_slot); what the call leaves: the
+    // records and job list (plan-owned), the caller's values and the launches as [first job, jobs]
+    int er_C = 0, er_dtype = 0, er_slots = 0;
+    std::vector<int32_t> h_slot;
+    mj::DevEraseRect *d_er_rects = nullptr;
+    mj::DevEraseJob *d_er_jobs = nullptr;
+    const void *er_values = nullptr;
+    std::vector<std::array<int32_t, 2>> er_launches;
+    int64_t er_bytes = 0;                      // bytes the launches write
     int32_t n_views = 0;                       // a plan with views (mj_plan_request.views): its resize and reduce records are per view (0: per image)
     std::vector<std::array<int32_t, 2>> h_view_size;   // ... every view's window, stored axes: width, height (mj_debug_reduce_shape)
     std::vector<std::array<int32_t, 6>> h_rd;  // per image (view), stored axes: fx, fy, phase x, phase y, reduced width, height (mj_debug_reduce_shape)
@@ -377,6 +389,8 @@ int create_derived(const PlanRequest &q, mj_plan *parent);
 bool reduce_applies(const mj_batch *b, const mj_plan_request &r);
 const char *output_fault(int dtype, bool normalize, int ncomp, const float *mean, const float *std);     // (resize_plan.hip)
 int create_oriented(const PlanRequest &q);
+// ---- erase.hip: the erase launches of one execute (mj_plan_set_erase), behind everything else it queued on s; none set: nothing
+int erase_execute(mj_plan *p, hipStream_t s);
 // q.r.rois (oriented coordinates, not NULL) or the windows `rois` given in their place, as windows of the stored images
 int stored_windows(const PlanRequest &q, const mj_roi *rois, std::vector<mj_roi> &stored);
 // destroys a plan under construction unless its maker got to the end (p = nullptr)

@@ -656,6 +656,7 @@ int resized_stages(const PlanRequest &q, Front &f, mj_plan *p, uint8_t *given_sr
         ri[i].src_off = p->h_images[img].rgb_off;
         const int64_t slot_off = (int64_t)(slots ? slots[i] : i) * out_image;
         ri[i].dst_off = colour ? (int64_t)i * out_image : slot_off;      // (canvas i of the plan's own buffer)
+        p->h_slot.push_back(slots ? slots[i] : i);      // (what mj_plan_set_erase addresses an output by)
         if (p->out_ncomp && !views) p->h_out_off.push_back(colour ? slot_off * out_esize : slot_off);
         // the record's size is what the kernels step from row to row by (resize.hip): the decoded image's.  w, h from here on: what
         // the tables are made for — the same, but for a view, whose record starts at its window's origin and whose tables are its window's
@@ -759,6 +760,7 @@ int resized_stages(const PlanRequest &q, Front &f, mj_plan *p, uint8_t *given_sr
         if (int rc = colour_stage(q, p, CO, out_esize)) return rc;
     p->info.rgb_bytes = (int64_t)n_slots * out_image * (colour ? out_esize : 1);
     p->info.total_pixels = (int64_t)n_slots * out_width * out_height;
+    p->er_C = CO; p->er_dtype = dtype; p->er_slots = n_slots;
     p->resized = true;
     return MJ_OK;
 }
