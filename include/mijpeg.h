@@ -614,7 +614,7 @@ int mj_plan_derive(mj_plan *parent, const mj_batch *batch, const mj_plan_request
  *                  DEVICE memory.  values_device is BORROWED: the caller keeps it valid and unchanged until the executes that
  *                  read it have finished.  Noise (torchvision's value="random", timm's mode="pixel") is the caller's to draw: no
  *                  bit-exact reference exists for an in-library generator, so none is offered.  CutMix / MixUp, which mix across
- *                  outputs and plans, are not offered either.
+ *                  outputs and plans, are a call of their own behind the plans: mj_mix, below.
  * n == 0 takes the erase off the plan again.  The call waits for the plan's latest execute, drops the plan's captured graph — the
  * next execute launches plainly and a later one may capture again, with the new pointers — and from then on mj_plan_execute (and
  * mj_plan_execute_stage2) queues the erase launch(es) last, behind the plan's final store, on the same stream, inside a capture
@@ -645,6 +645,47 @@ int mj_plan_time_erase(mj_plan *plan, int iters, float *ms, int64_t *bytes_writt
  * ncomp neither 1 nor 3, a size outside 1..65535, n_slots below 1, NULL. */
 int mj_host_erase(void *array, int32_t layout, int32_t dtype, int32_t ncomp, int32_t width, int32_t height, int32_t n_slots, int32_t n,
                   const mj_erase_rect *rects, const void *values);
+/* Mix: MixUp and CutMix over the finished outputs of a CALL (tools/mix_model.py) — the step the training recipes put in the collate
+ * function, behind RandomErasing: ... -> mirror -> element type -> erase -> MIX.  Output k's partner may be any output of the
+ * array, which another plan may have written on another stream; so this is no field of mj_plan_request and no call on a plan,
+ * but the library's one launch that belongs to the caller's whole batch: it runs over the array once every plan that writes it
+ * has been synchronised, reads `src` and writes `dst`, and every output reads `src` as it stands — the mixing is simultaneous,
+ * as it is where torchvision and timm mix from a roll / flip copy.
+ *   src, dst       n_outputs slots of width x height pixels of ncomp (1 or 3) components of MJ_DTYPE_* `dtype` in MJ_LAYOUT_*
+ *                  `layout`, DEVICE memory; they must not overlap.  dst is written in full.  Any alignment is taken: 16 bytes
+ *                  per lane where src and dst are congruent mod 16 and aligned to their elements, element by element at a
+ *                  slot's ends and otherwise.
+ *   ops            n_outputs records, host memory, copied at the call into a context-owned device buffer; a call that finds the
+ *                  previous mix launch still in flight waits for it before it rewrites that buffer.
+ *   MJ_MIX_NONE    dst[k] = src[k]
+ *   MJ_MIX_CUTMIX  dst[k] = src[k] with the box (x along width, inside the canvas, sides >= 1) taken from src[partner]; any dtype
+ *   MJ_MIX_MIXUP   float dtypes.  With ws = float32(lam), wp = float32(1.0 - lam) (subtracted in double, rounded once), per element
+ *                  dst = T(f32(T(f32(src[partner]) * wp)) + f32(T(f32(src[k]) * ws))), T rounding to nearest even into the dtype,
+ *                  every float32 operation rounded on its own: x.roll(1, 0).mul(1.0 - lam).add_(x.mul(lam)) of torch's CPU ops,
+ *                  bit for bit.  partner == k still runs the arithmetic.  A NaN result is some NaN.
+ *   stream         a hipStream_t, or 0 for the context's, as mj_plan_execute takes it.
+ * One launch (csrc/mix.hip: k_mix); nothing synchronises with the host behind it.  MJ_ERR_INVALID, naming the output: a kind that
+ * is none of the three, a partner outside 0 .. n_outputs - 1, lam not finite or outside 0..1, MIXUP with MJ_DTYPE_U8, a box with
+ * a side below 1 or not inside the canvas; overlapping src / dst; NULL; an unknown layout or dtype; ncomp neither 1 nor 3; a size
+ * outside 1..65535; n_outputs below 1. */
+#define MJ_MIX_NONE   0
+#define MJ_MIX_MIXUP  1
+#define MJ_MIX_CUTMIX 2
+typedef struct {
+    int32_t kind;                  /* MJ_MIX_* */
+    int32_t partner;               /* an output of the same array; may be the output itself */
+    int32_t x, y, width, height;   /* CUTMIX: the box, after the mirror */
+    double  lam;                   /* MIXUP: the output's own weight, 0..1 */
+} mj_mix_op;
+int mj_mix(mj_context *ctx, void *stream, const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp, int32_t width,
+           int32_t height, int32_t n_outputs, const mj_mix_op *ops);
+/* The mix launch alone on the context's stream, `iters` times behind one warm run: ms per launch. */
+int mj_mix_time(mj_context *ctx, int iters, const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp, int32_t width,
+                int32_t height, int32_t n_outputs, const mj_mix_op *ops, float *ms);
+/* The host twin of the mix launch (no context): the same records over HOST arrays, through the launch's own rule and box test
+ * (csrc/mix_rule.h).  MJ_ERR_INVALID (mj_last_error(NULL)): what mj_mix refuses. */
+int mj_host_mix(const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp, int32_t width, int32_t height,
+                int32_t n_outputs, const mj_mix_op *ops);
 /* The host twin of the kernels' mode conversion (no context): n_pixels pixels of src_ncomp (1 or 3) interleaved components into
  * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
  * is neither 1 nor 3, NULL with pixels to convert. */

@@ -57,6 +57,7 @@ EXPORTS = (
     "mj_plan_time_reduce", "mj_host_affine", "mj_host_perspective", "mj_plan_time_affine", "mj_debug_reduce_launch", "mj_host_colour_ops", "mj_plan_time_colour",
     "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables", "mj_plan_derive",
     "mj_plan_set_erase", "mj_plan_time_erase", "mj_host_erase",
+    "mj_mix", "mj_mix_time", "mj_host_mix",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -189,6 +190,48 @@ def _fill_erase_rects(arr, rects):
     return arr
 
 
+MJ_MIX_NONE, MJ_MIX_MIXUP, MJ_MIX_CUTMIX = 0, 1, 2
+
+
+class MixOpC(ctypes.Structure):
+    """mj_mix_op: what mj_mix / mj_host_mix do to one output."""
+    _fields_ = [("kind", ctypes.c_int32), ("partner", ctypes.c_int32), ("x", ctypes.c_int32), ("y", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("lam", ctypes.c_double)]
+
+
+# mj_mix_op as a NumPy record: a list of tuples (kind, partner, x, y, width, height, lam) becomes the array in one call
+MIX_OP_DTYPE = np.dtype([("kind", "<i4"), ("partner", "<i4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("lam", "<f8")], align=True)
+assert MIX_OP_DTYPE.itemsize == ctypes.sizeof(MixOpC)
+
+
+def mix_ops(entries):
+    """what the C calls take as ``ops`` from one entry per output: None, ``("mixup", partner, lam)``, ``("cutmix", partner, (x, y,
+    width, height))`` — or ready MixOpC's, which the tests of the library's refusals pass.  Returns (pointer, what keeps it alive)."""
+    if any(isinstance(e, MixOpC) for e in entries):
+        arr = (MixOpC * max(1, len(entries)))()
+        rest = mix_ops([None if isinstance(e, MixOpC) else e for e in entries])[1]
+        for k, e in enumerate(entries):
+            if isinstance(e, MixOpC):
+                arr[k] = e
+            else:
+                ctypes.memmove(ctypes.byref(arr[k]), rest.ctypes.data + k * MIX_OP_DTYPE.itemsize, MIX_OP_DTYPE.itemsize)
+        return arr, arr
+    arr = np.zeros(max(1, len(entries)), dtype=MIX_OP_DTYPE)
+    # (column by column from plain arrays: a structured array made from a list of tuples costs several times as much)
+    blends = [(k, e[1], e[2]) for k, e in enumerate(entries) if e is not None and e[0] == "mixup"]
+    if blends:
+        cols = np.array(blends, dtype=np.float64)       # (indices are exact in float64)
+        at = cols[:, 0].astype(np.intp)
+        arr["kind"][at], arr["partner"][at], arr["lam"][at] = MJ_MIX_MIXUP, cols[:, 1].astype(np.int32), cols[:, 2]
+    cuts = [(k, e[1]) + tuple(e[2]) for k, e in enumerate(entries) if e is not None and e[0] != "mixup"]
+    if cuts:
+        cols = np.array(cuts, dtype=np.int64)
+        at = cols[:, 0]
+        arr["kind"][at], arr["partner"][at] = MJ_MIX_CUTMIX, cols[:, 1]
+        arr["x"][at], arr["y"][at], arr["width"][at], arr["height"][at] = cols[:, 2], cols[:, 3], cols[:, 4], cols[:, 5]
+    return ctypes.cast(arr.ctypes.data, ctypes.POINTER(MixOpC)), arr
+
+
 class PlanRequestC(ctypes.Structure):
     """mj_plan_request: what a plan's output is to be; zeroed, the plain plan.  Every field of the header's struct, in its order."""
     _fields_ = [("rois", ctypes.POINTER(RoiC)), ("orientations", ctypes.c_void_p), ("mode", ctypes.c_int32),
@@ -280,6 +323,9 @@ def load_library():
     L.mj_plan_set_erase.argtypes = [vp, i32, ctypes.POINTER(EraseRectC), vp]
     L.mj_plan_time_erase.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)]
     L.mj_host_erase.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(EraseRectC), vp]
+    L.mj_mix.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(MixOpC)]
+    L.mj_mix_time.argtypes = [vp, ctypes.c_int, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(MixOpC), ctypes.POINTER(ctypes.c_float)]
+    L.mj_host_mix.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(MixOpC)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
@@ -554,24 +600,45 @@ def host_erase(a: np.ndarray, layout: int, dtype: str, ncomp: int, width: int, h
         raise ValueError(L.mj_last_error(None).decode())
 
 
+def host_mix(src: np.ndarray, layout: int, dtype: str, ncomp: int, width: int, height: int, entries) -> np.ndarray:
+    """mj_host_mix (host only): the mix launch's records over the host array ``src`` — one slot of width x height pixels of
+    ``ncomp`` components of ``dtype`` (bfloat16: uint16 bit patterns) in MJ_LAYOUT_* ``layout`` per entry of ``entries``
+    (:func:`mix_ops`') — into a new array of the same shape.  ValueError with the library's message for what it refuses."""
+    if not src.flags["C_CONTIGUOUS"] or src.itemsize != DTYPE_BYTES[dtype]:
+        raise ValueError("mj_host_mix: a contiguous array of the dtype's element size")
+    L = load_library()
+    dst = np.empty_like(src)
+    ops, _keep = mix_ops(entries)
+    if L.mj_host_mix(_ptr(src), _ptr(dst), int(layout), DTYPES[dtype], int(ncomp), int(width), int(height), len(entries), ops) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+    return dst
+
+
 class DeviceBytes:
     """A block of device memory of the HIP runtime's own (hipMalloc), filled from a host array: what the NumPy route keeps the values
-    of ``erase=`` in — no torch there.  ``ptr`` is the device address; close() frees it."""
+    of ``erase=`` and the arrays of ``mix=`` in — no torch there.  ``ptr`` is the device address; close() frees it."""
 
-    def __init__(self, host: np.ndarray):
+    def __init__(self, host: np.ndarray, nbytes: Optional[int] = None):
+        """``host`` None: ``nbytes`` uninitialised bytes"""
         load_library()                          # (the runtime libmijpeg.so bound to is the process's)
         self._hip = ctypes.CDLL("libamdhip64.so")
         self._hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
         self._hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
         self._hip.hipFree.argtypes = [ctypes.c_void_p]
-        host = np.ascontiguousarray(host)
+        host = np.ascontiguousarray(host) if host is not None else np.empty(0, np.uint8)
         p = ctypes.c_void_p()
-        if self._hip.hipMalloc(ctypes.byref(p), max(16, host.nbytes)) != 0:
-            raise BackendError("hipMalloc failed for the values of erase=")
+        if self._hip.hipMalloc(ctypes.byref(p), max(16, host.nbytes, nbytes or 0)) != 0:
+            raise BackendError("hipMalloc failed for a block of device memory (DeviceBytes)")
         self.ptr = p.value
         if host.nbytes and self._hip.hipMemcpy(p, _ptr(host), host.nbytes, 1) != 0:       # hipMemcpyHostToDevice
             self.close()
-            raise BackendError("hipMemcpy failed for the values of erase=")
+            raise BackendError("hipMemcpy to the device failed (DeviceBytes)")
+
+    def download(self, out: np.ndarray) -> np.ndarray:
+        """the block's first ``out.nbytes`` bytes into the contiguous host array ``out`` (a blocking copy, behind everything queued)"""
+        if self._hip.hipDeviceSynchronize() != 0 or self._hip.hipMemcpy(_ptr(out), ctypes.c_void_p(self.ptr), out.nbytes, 2) != 0:    # hipMemcpyDeviceToHost
+            raise BackendError("hipMemcpy to the host failed")
+        return out
 
     def close(self):
         if getattr(self, "ptr", None):
@@ -779,6 +846,22 @@ class Context:
         """Everything queued on the context's stream from now on runs after `hip_event` (a hipEvent_t handle, e.g.
         ``torch.cuda.Event.cuda_event``) has happened."""
         self.check(self.lib.mj_context_wait_event(self.handle, hip_event))
+
+    def mix(self, src: int, dst: int, layout: int, dtype: str, ncomp: int, width: int, height: int, entries, stream: int = 0):
+        """mj_mix: one launch on ``stream`` (0: the context's) that writes the ``len(entries)`` slots at device address ``dst`` from
+        those at ``src`` — entry k (:func:`mix_ops`') says what output k becomes: a copy, a MixUp with its partner, a CutMix box
+        from it.  BackendError with the library's message, which names the output, for what it refuses."""
+        ops, _keep = mix_ops(entries)
+        self.check(self.lib.mj_mix(self.handle, stream or None, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(width), int(height),
+                                   len(entries), ops))
+
+    def time_mix(self, src: int, dst: int, layout: int, dtype: str, ncomp: int, width: int, height: int, entries, iters: int = 10) -> float:
+        """ms per mix launch alone, on the context's stream (mj_mix_time)."""
+        ms = ctypes.c_float()
+        ops, _keep = mix_ops(entries)
+        self.check(self.lib.mj_mix_time(self.handle, iters, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(width), int(height),
+                                        len(entries), ops, ctypes.byref(ms)))
+        return ms.value
 
     def cache_stats(self):
         """mj_debug_cache_stats: (blocks handed out now, their bytes, requests so far, running hash of the requested sizes)."""

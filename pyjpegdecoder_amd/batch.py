@@ -674,7 +674,7 @@ def select_union_files(files: Sequence[bytes], groups: Sequence[dict]):
 
 
 # the keys of an entry of ``also``: what is per output and never inherited, and what is the call's unless the entry says otherwise
-ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase")
+ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase", "mix")
 ALSO_CALL_WIDE = ("dtype", "normalize", "resample", "mode", "reducing_gap", "fill", "affine_resample", "affine_fill")
 
 
@@ -730,6 +730,7 @@ def normalize_also(also, call: dict, size, rois=None, return_seams: bool = False
             normalize_transform(g["affine"], g["perspective"], g["affine_resample"], g["affine_fill"], g["size"], None, gap)
             normalize_color_ops(g["color_ops"], g["size"])
             normalize_erase(g["erase"], g["size"], device=None if host else -1)
+            normalize_mix(g["mix"], g["size"])
             if g["views"] is not None and not isinstance(g["views"], (list, tuple)):
                 normalize_views(g["views"], [], g["size"])
         except ValueError as e:
@@ -1244,6 +1245,104 @@ def random_erasing_rect(size, scale=(0.02, 0.33), ratio=(0.3, 3.3), generator=No
     return None
 
 
+def normalize_mix(mix, size, n_outputs: Optional[int] = None, dtype: Optional[str] = None, return_seams: bool = False):
+    """``mix`` of a call, checked: None for a call without it — ``mix`` None, or entries that are all None, which make the plans,
+    launches and tensor of a call without the argument — else a list with, per OUTPUT, None, ``("mixup", partner, lam)`` or
+    ``("cutmix", partner, (x, y, width, height))``.
+
+    ``mix``: None, or a list with one entry per output (per file; per view with ``views``); there is no one-for-all form.
+    ``partner``: the index of an output of the same group — any mapping: torchvision's ``roll(1, 0)`` is ``(k - 1) % N``, timm's
+    ``flip(0)`` is ``N - 1 - k``, and an output may be its own partner.  ``("mixup", partner, lam)``, float outputs only: ``out[k] =
+    lam * pre[k] + (1 - lam) * pre[partner]`` as ``pre.roll(1, 0).mul(1.0 - lam).add_(pre.mul(lam))`` computes it with torch's CPU
+    ops, bit for bit (tools/mix_model.py); ``lam`` a finite number in 0..1.  ``("cutmix", partner, box)``, any ``dtype``: ``out[k] =
+    pre[k]`` with ``[..., y:y+height, x:x+width]`` taken from ``pre[partner]``; the box as in ``erase``: integers, ``x`` along the
+    width, wholly inside the ``size`` canvas, sides of at least 1 (:func:`cutmix_box` draws one).  ``pre`` is the call's result
+    without the argument — behind the mirror, the element type and ``erase`` —, and every output reads ``pre``: the mixing is
+    simultaneous.  Per-output ``lam`` and boxes are timm's ``elem`` / ``pair`` modes; labels are the caller's business.
+
+    ``mix`` needs ``size`` and does not go with ``return_seams``.  ``n_outputs`` / ``dtype`` None: not known yet — what needs them
+    is not checked.  ValueError, naming the output, otherwise."""
+    if mix is None:
+        return None
+    if size is None:
+        raise ValueError("mix needs size=(width, height): the outputs of one array are mixed with each other")
+    if return_seams:
+        raise ValueError("mix and return_seams do not go together: the seam outputs are the decoded images")
+    if not isinstance(mix, (list, tuple)) or (isinstance(mix, tuple) and len(mix) == 3 and isinstance(mix[0], str)):
+        raise ValueError(f"mix must be None or a list with, per output, None, (\"mixup\", partner, lam) or (\"cutmix\", partner, (x, y, width, height)) "
+                         f"(there is no one-for-all form), not {mix!r}")
+    if n_outputs is not None and len(mix) != n_outputs:
+        raise ValueError(f"mix has {len(mix)} entries for {n_outputs} outputs")
+    W, H = size
+    n = len(mix)
+    u8 = dtype == "uint8"
+    out, some = [], False
+    for k, e in enumerate(mix):
+        if e is None:
+            out.append(None)
+            continue
+        some = True
+        if type(e) is tuple and len(e) == 3:    # (the everyday entries, told by exact types: a batch has a thousand of them)
+            op, partner, arg = e
+            if type(partner) is int and 0 <= partner < n:
+                if op == "mixup" and type(arg) is float and 0.0 <= arg <= 1.0 and not u8:
+                    out.append(e)
+                    continue
+                if op == "cutmix" and type(arg) is tuple and len(arg) == 4:
+                    x, y, w, h = arg
+                    if (type(x) is int and type(y) is int and type(w) is int and type(h) is int and w >= 1 and h >= 1 and x >= 0 and y >= 0
+                            and x + w <= W and y + h <= H):
+                        out.append(e)
+                        continue
+        if not isinstance(e, (tuple, list)) or len(e) != 3 or not isinstance(e[0], str):
+            raise ValueError(f"mix: output {k}: an entry is None, (\"mixup\", partner, lam) or (\"cutmix\", partner, (x, y, width, height)), not {e!r}")
+        op, partner, arg = e
+        if op not in ("mixup", "cutmix"):
+            raise ValueError(f"mix: output {k}: unknown op {op!r} (\"mixup\", \"cutmix\")")
+        if not _is_int(partner) or not 0 <= int(partner) < n:
+            raise ValueError(f"mix: output {k}: partner {partner!r} is not the index of an output, an integer 0..{n - 1}")
+        partner = int(partner)
+        if op == "mixup":
+            if u8:
+                raise ValueError(f"mix: output {k}: \"mixup\" needs a float output (dtype= or normalize=), not uint8; \"cutmix\" takes any")
+            if not _is_number(arg) or not math.isfinite(float(arg)) or not 0.0 <= float(arg) <= 1.0:
+                raise ValueError(f"mix: output {k}: lam {arg!r} is not a finite number in 0..1")
+            out.append(("mixup", partner, float(arg)))
+        else:
+            if not isinstance(arg, (tuple, list, np.ndarray)) or len(arg) != 4 or not all(_is_int(t) for t in arg):
+                raise ValueError(f"mix: output {k}: a box is four integers (x, y, width, height), not {arg!r}")
+            x, y, w, h = (int(t) for t in arg)
+            if w < 1 or h < 1:
+                raise ValueError(f"mix: output {k}: width and height must be at least 1, not {w} x {h}")
+            if x < 0 or y < 0 or x + w > W or y + h > H:
+                raise ValueError(f"mix: output {k}: box ({x}, {y}, {w}, {h}) is not inside the {W} x {H} canvas")
+            out.append(("cutmix", partner, (x, y, w, h)))
+    return out if some else None
+
+
+def cutmix_box(size, lam: float, generator=None):
+    """A box for ``("cutmix", partner, box)`` drawn as torchvision v2's ``CutMix`` draws it for a ``size = (width, height)`` canvas and
+    a ``lam`` (the caller's Beta draw): ``((x, y, w, h), lam_adjusted)``, or ``(None, 1.0)`` for an empty box.  Restated: ``r = 0.5 *
+    sqrt(1 - lam)``, half sides ``int(r * W)`` and ``int(r * H)``, the centre from two ``torch.randint`` draws (x in 0..W-1 first,
+    then y in 0..H-1), the box ``centre +- half side`` clamped to the canvas; ``lam_adjusted = 1 - w * h / (W * H)`` is the weight
+    of the output's own label.  torchvision is not a dependency here and this function is NOT pinned to its draws."""
+    import torch
+    W, H = (int(t) for t in size)
+    lam = float(lam)
+    if not math.isfinite(lam) or not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lam {lam!r} is not a finite number in 0..1")
+    r = 0.5 * math.sqrt(1.0 - lam)
+    rw, rh = int(r * W), int(r * H)
+    cx = int(torch.randint(0, W, size=(1,), generator=generator).item())
+    cy = int(torch.randint(0, H, size=(1,), generator=generator).item())
+    x1, y1 = max(cx - rw, 0), max(cy - rh, 0)
+    x2, y2 = min(cx + rw, W), min(cy + rh, H)
+    w, h = x2 - x1, y2 - y1
+    if w < 1 or h < 1:
+        return None, 1.0
+    return (x1, y1, w, h), 1.0 - (w * h) / float(W * H)
+
+
 def rotation_matrix(angle: float, size: Tuple[int, int], center=None, translate=None) -> Tuple[float, ...]:
     """The matrix ``Image.rotate(angle, center=center, translate=translate)`` builds for ``expand=False`` on an image of ``size`` =
     (width, height) — counter-clockwise by ``angle`` degrees around ``center`` (None: the image's centre), then moved by
@@ -1471,6 +1570,9 @@ class _Request:
     affine: Optional[AffineSpec] = None         # :func:`normalize_transform`'s, affine or perspective (None: no transform); always with ``views``
     colour: Optional[List[Optional[tuple]]] = None      # :func:`normalize_color_ops`' chains, one or None per OUTPUT (None: no operations)
     erase: Optional[List[Optional[tuple]]] = None       # :func:`normalize_erase`'s boxes, a tuple or None per OUTPUT (None: no box anywhere)
+    # :func:`normalize_mix`'s entries, one or None per OUTPUT of the whole group (None: no mixing).  The CALL's, not a plan's: the
+    # requests of its parts, kinds and rounds (:meth:`narrow`) do not carry it, and it is applied once they have all been collected
+    mix: Optional[List[Optional[tuple]]] = None
     # the extra groups of a call with ``also``: requests over the SAME files, index and orientations, each with its own size, views, output,
     # tensor and slots (None: a call without).  A group with views need not name every file here; what it has none of it is left out of.
     also: Optional[List["_Request"]] = None
@@ -1824,7 +1926,7 @@ class BatchDecoder:
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -1906,6 +2008,13 @@ class BatchDecoder:
         ``value``: absent (0) or a number, one number per component, or a ``(C, height, width)`` NumPy array (noise, which the caller
         draws).  One more launch per plan (csrc/erase.hip), on every plan of the call, second rounds included.  Not with
         ``return_seams``; an ``also`` entry takes a key ``erase`` of its own.
+        ``mix``, with ``size``: MixUp and CutMix over the finished outputs (:func:`normalize_mix`, tools/mix_model.py) — None, or a list
+        with one entry per output: None, ``("mixup", partner, lam)`` or ``("cutmix", partner, (x, y, width, height))``, ``partner`` the
+        index of an output of the same array.  It comes behind ``erase`` — torchvision's order: RandomErasing is a per-sample transform,
+        the mixing is in the collate function — and every output reads the array as it stands before any mixing.  Not a step of any
+        plan: ONE launch (csrc/mix.hip) over the whole array once every plan of the call has been collected, from that array into a
+        second one, which is what the call returns — here the array is uploaded, mixed by the library and downloaded.  Entries that are
+        all None: the call without the argument.  An ``also`` entry takes a key ``mix`` of its own, over its own outputs.
         ``also``, with ``size``: several groups of outputs from ONE decode (:func:`normalize_also`) — None or ``[]`` (the call as it
         is), else a list with one dict per extra group: ``size`` (required) and that group's own ``views``, ``mirror``, ``resize_to``,
         ``place``, ``affine``, ``perspective`` and ``color_ops`` (None when absent, never the call's); ``dtype``, ``normalize``,
@@ -1917,7 +2026,7 @@ class BatchDecoder:
         ``return_seams``."""
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective, erase=erase)
+                    perspective=perspective, erase=erase, mix=mix)
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -2003,6 +2112,9 @@ class BatchDecoder:
             finally:
                 for _, p in reversed(plans):
                     p.close()
+        for j, g in enumerate(req.groups):      # (behind every plan of the call: the groups' arrays mixed, each within itself)
+            if g.mix is not None:
+                denses[j] = self._mix_host(g, denses[j])
         if extra is not None:
             return tuple(denses)
         if denses[0] is not None:
@@ -2011,7 +2123,8 @@ class BatchDecoder:
 
     def _host_request(self, files: Sequence[bytes], cache: Dict[int, ParsedJpeg], gpu_segment: Optional[bool], rois=None, return_seams: bool = False,
                       size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None,
-                      fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, erase=None):
+                      fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, erase=None,
+                      mix=None):
         """The checked request of a :meth:`decode` call, or of one group of it, and the array it fills (None without ``size``).  ``cache``:
         the parsed files by their position in ``files``, filled with those this request names; ``gpu_segment``: whether they are parsed
         headers only (None: decided by the files this request names)."""
@@ -2025,6 +2138,8 @@ class BatchDecoder:
         # (before any file is read: everything but what the files' component count decides)
         boxes = normalize_erase(erase, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES[mode] if mode else None,
                                 dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams)
+        mixes = normalize_mix(mix, size, len(views) if isinstance(views, (list, tuple)) else len(files),
+                              dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None                            # views: where the files that are read sit in the caller's list
@@ -2059,6 +2174,7 @@ class BatchDecoder:
             if spec is not None:
                 req.affine = _spec_for_outputs(spec, size, req.n_outputs, nc)
             req.erase = erase_for_components(boxes, nc)
+            req.mix = mixes
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         return req, dense
 
@@ -2072,7 +2188,7 @@ class BatchDecoder:
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
                         resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                        affine_fill=None, color_ops=None, perspective=None, erase=None) -> _Request:
+                        affine_fill=None, color_ops=None, perspective=None, erase=None, mix=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
@@ -2084,6 +2200,8 @@ class BatchDecoder:
         if erase is not None:
             boxes = normalize_erase(erase, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES.get(mode) if isinstance(mode, str) else None,
                                     dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", device=self.ctx.device)
+        mixes = normalize_mix(mix, size, len(views) if isinstance(views, (list, tuple)) else len(files),
+                              dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8")
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None
@@ -2111,6 +2229,7 @@ class BatchDecoder:
             req.output = normalize_output(dtype, normalize, mirror, size, req.n_outputs, nc)
             req.fill = normalize_fill(fill, resize_to, nc)
             req.erase = erase_for_components(boxes, nc)
+            req.mix = mixes
             req.dest = torch.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
             req.slots = list(range(req.n_outputs))
@@ -2129,7 +2248,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -2176,7 +2295,10 @@ class BatchDecoder:
         that has some derives a plan from it, executed right behind it on the same stream into that group's tensor.
         ``erase`` as in :meth:`decode`; a box's ``(C, height, width)`` values may also be a torch tensor, on the CPU or on this decoder's
         GPU.  Every plan of the call erases the outputs it writes as its last launch; its blocks of values go into one tensor of the
-        output's type (host arrays uploaded once, one ``torch.cat``) that the plan holds until it is collected."""
+        output's type (host arrays uploaded once, one ``torch.cat``) that the plan holds until it is collected.
+        ``mix`` as in :meth:`decode`: once every plan of the call — kinds of files, orientation classes, parts, second rounds — has been
+        collected, each group's tensor is the source of ONE launch on torch's current stream into a new tensor of the same shape, which
+        the caller gets; the source goes back to torch's allocator."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -2186,7 +2308,7 @@ class BatchDecoder:
         normalize_fill(fill, resize_to)
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective, erase=erase)
+                    perspective=perspective, erase=erase, mix=mix)
         extra = normalize_also(also, main, size, rois)
         if extra is None:
             req = self._device_request(files, rois, orientation=orientation, **main)
@@ -2196,18 +2318,74 @@ class BatchDecoder:
         if parts is None:
             parts = min(4, len(files) // 256) if (self.native_host and self._gpu_segment_for(files)) else 1
         if parts <= 1:
-            return self._result(req, self._decode_request(req))
+            return self._mixed(req, self._decode_request(req))
         cut = [len(files) * i // parts for i in range(parts + 1)]
         out: List["torch.Tensor"] = []
         for part in self._device_iter((req.narrow(range(cut[i], cut[i + 1])) for i in range(parts)), depth=2):
             if req.dest is None:
                 out += part
-        return out if req.dest is None else self._result(req, req.dest)
+        return out if req.dest is None else self._mixed(req, req.dest)
 
     @staticmethod
     def _result(req: _Request, out):
         """what a call returns for a request: ``out``, or — with extra groups — the tuple of every group's tensor, the call's own first"""
         return out if req.also is None else tuple(g.dest for g in req.groups)
+
+    def _mixed(self, req: _Request, out):
+        """What a call returns for a request whose plans have all been collected (``out``: :meth:`_decode_request`'s): every group
+        with ``mix`` entries has its tensor mixed into a new one (:meth:`_mix_device`), which takes its place."""
+        if all(g.mix is None for g in req.groups):
+            return self._result(req, out)
+        for g in req.groups:
+            if g.mix is not None:
+                g.dest = self._mix_device(g)
+        return self._result(req, req.dest)
+
+    def _mix_geometry(self, g: _Request, elements_per_output: int):
+        """(dtype name, components, width, height) of a group's outputs"""
+        W, H = g.size
+        return (g.output.dtype if g.output else "uint8"), elements_per_output // (W * H), W, H
+
+    def _mix_device(self, g: _Request):
+        """Group ``g``'s tensor mixed (mj_mix): one launch from ``g.dest`` into a new tensor of its shape, on torch's current stream
+        — the default stream has no handle the library could launch on, so there the launch goes on a side stream between two
+        waits.  Every plan that wrote ``g.dest`` has been synchronised by now.  ``g.dest`` is released to the allocator by the
+        caller's dropping it: the launch that reads it is on the stream it was allocated on, or recorded (``record_stream``)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        src = g.dest
+        dtype, nc, W, H = self._mix_geometry(g, src[0].numel())
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            dst = torch.empty_like(src)
+            if cur.cuda_stream:
+                if src.device == dev:
+                    src.record_stream(cur)      # (allocated on the stream the call was made on, which may be another)
+                self.ctx.mix(src.data_ptr(), dst.data_ptr(), self.layout, dtype, nc, W, H, g.mix, stream=cur.cuda_stream)
+                return dst
+            if getattr(self, "_mix_stream", None) is None:
+                self._mix_stream = torch.cuda.Stream(device=dev)
+            st = self._mix_stream
+            st.wait_stream(cur)
+            src.record_stream(st)
+            dst.record_stream(st)
+            self.ctx.mix(src.data_ptr(), dst.data_ptr(), self.layout, dtype, nc, W, H, g.mix, stream=st.cuda_stream)
+            cur.wait_stream(st)
+        return dst
+
+    def _mix_host(self, g: _Request, dense: np.ndarray) -> np.ndarray:
+        """Group ``g``'s array mixed (mj_mix): uploaded, one launch on the context's stream into a second block, downloaded"""
+        dtype, nc, W, H = self._mix_geometry(g, int(dense[0].size))
+        src = B.DeviceBytes(dense)
+        try:
+            dst = B.DeviceBytes(None, dense.nbytes)
+            try:
+                self.ctx.mix(src.ptr, dst.ptr, self.layout, dtype, nc, W, H, g.mix)
+                return dst.download(np.empty_like(dense))
+            finally:
+                dst.close()
+        finally:
+            src.close()
 
     def _decode_request(self, req: _Request):
         """What :meth:`decode_device` returns for a checked request, decoded as one plan per kind of file — the request's
@@ -2314,7 +2492,7 @@ class BatchDecoder:
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None):
+                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -2341,7 +2519,8 @@ class BatchDecoder:
         batch, what :meth:`decode_device` takes for that batch.  ``also``: None, or an iterable that yields, batch by batch, what
         :meth:`decode_device` takes for that batch — a list with one dict per extra group; every batch is then handed out as a tuple
         of tensors, one per group.  ``erase``: None, or an iterable that yields, batch by batch, what :meth:`decode_device` takes for
-        that batch — a list with one entry per output, or None."""
+        that batch — a list with one entry per output, or None.  ``mix``: None, or an iterable that yields, batch by batch, what
+        :meth:`decode_device` takes for that batch; the batch is mixed when it is collected, before it is handed out."""
         size = normalize_size(size)
         if also is not None and isinstance(also, (list, tuple)) and len(also) == 0:
             also = None                                                               # (no extra group: a call without the argument)
@@ -2351,6 +2530,9 @@ class BatchDecoder:
         if erase is not None and size is None:
             raise ValueError("erase needs size=(width, height): boxes are in the coordinates of the finished canvas")
         per_batch_erase = iter(erase) if erase is not None else None
+        if mix is not None and size is None:
+            raise ValueError("mix needs size=(width, height): the outputs of one array are mixed with each other")
+        per_batch_mix = iter(mix) if mix is not None else None
         normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
         per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
@@ -2422,6 +2604,12 @@ class BatchDecoder:
                         er = next(per_batch_erase)
                     except StopIteration:
                         raise ValueError("erase yields fewer entries than there are batches") from None
+                mx = None
+                if per_batch_mix is not None:
+                    try:
+                        mx = next(per_batch_mix)
+                    except StopIteration:
+                        raise ValueError("mix yields fewer entries than there are batches") from None
                 def none(g):
                     return g is None or (isinstance(g, (list, tuple)) and all(e is None for e in g))
                 if per_batch_also is not None:
@@ -2432,17 +2620,17 @@ class BatchDecoder:
                     plain = none(t) and none(ps)
                     main = dict(size=size, dtype=dtype, normalize=normalize, mirror=m, resample=resample, mode=mode, resize_to=resize_to, place=place,
                                 fill=fill, reducing_gap=reducing_gap, views=v, affine=None if none(t) else t, affine_resample=None if plain else affine_resample,
-                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er)
+                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er, mix=mx)
                     extra = normalize_also(a, dict(main, affine_resample=affine_resample, affine_fill=affine_fill), size)
                     if extra is not None:
                         yield self._merged_request(files, o, [main] + extra, lambda fs, **kw: self._device_request(fs, None, **kw))
                         continue
                 if none(t) and none(ps):                # (a batch without a transform)
                     yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                               color_ops=c, erase=er)
+                                               color_ops=c, erase=er, mix=mx)
                     continue
                 yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er)
+                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er, mx)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):
@@ -2471,7 +2659,7 @@ class BatchDecoder:
                 if req.size is None:
                     for i, img in zip(again, redo):
                         out[i] = img
-            return self._result(req, out)
+            return self._mixed(req, out)
 
         try:
             for req in requests:
@@ -2488,7 +2676,7 @@ class BatchDecoder:
                 if not isinstance(prep, PreparedBatch):           # declined, or several plans' worth: the one-call path sorts it out
                     while pending:
                         yield collect(pending.popleft())
-                    yield self._result(req, self._decode_request(req))
+                    yield self._mixed(req, self._decode_request(req))
                     continue
                 with torch.cuda.stream(copy_stream):
                     d_blob = pinned[buf][:prep.blob.size].to(dev, non_blocking=True)

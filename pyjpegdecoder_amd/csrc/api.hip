@@ -100,6 +100,10 @@ void mj_destroy(mj_context *ctx) {
     for (auto &a : ctx->free_arenas) (void)hipHostFree(a.base);
     if (ctx->h_word) (void)hipHostFree(ctx->h_word);
     if (ctx->fused_done) (void)hipEventDestroy(ctx->fused_done);
+    if (ctx->mix_flying) (void)hipEventSynchronize(ctx->mix_done);
+    if (ctx->mix_done) (void)hipEventDestroy(ctx->mix_done);
+    if (ctx->h_mix) (void)hipHostFree(ctx->h_mix);
+    if (ctx->d_mix) (void)hipFree(ctx->d_mix);
     if (ctx->d_idct_tt) (void)hipFree(ctx->d_idct_tt);
     if (ctx->d_dump) (void)hipFree(ctx->d_dump);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

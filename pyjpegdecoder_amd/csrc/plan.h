@@ -108,6 +108,12 @@ struct mj_context {
     // execute that contains a fused launch waits — its stream does, not the host — for the context's previous one.
     hipEvent_t fused_done = nullptr;
     hipStream_t fused_stream = nullptr;     // where the latest fused execute went (null: none yet)
+    // mj_mix (mix.hip), the one launch that belongs to a call and not to a plan: its per-output records go through a pinned block
+    // into a device block, both the context's; a call waits for the previous launch (mix_done) before it rewrites them
+    void *h_mix = nullptr, *d_mix = nullptr;
+    size_t mix_cap = 0;
+    hipEvent_t mix_done = nullptr;
+    bool mix_flying = false;
     DevBufferCache cache;
     std::string err;
 };
