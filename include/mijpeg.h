@@ -686,6 +686,62 @@ int mj_mix_time(mj_context *ctx, int iters, const void *src, void *dst, int32_t 
  * (csrc/mix_rule.h).  MJ_ERR_INVALID (mj_last_error(NULL)): what mj_mix refuses. */
 int mj_host_mix(const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp, int32_t width, int32_t height,
                 int32_t n_outputs, const mj_mix_op *ops);
+/* Compose: several finished outputs of a CALL pasted onto one canvas (tools/compose_model.py) — Mosaic, image grids, a crop of one
+ * sample in another at another place: ... -> mirror -> element type -> erase -> COMPOSE.  A canvas's tiles may be outputs of
+ * several plans, so, like mj_mix, this is no field of mj_plan_request and no call on a plan but a launch over the caller's whole
+ * batch, once every plan that writes it has been synchronised.  It reads `src` and writes `dst`, an array of another size:
+ *     dst[m] = a dst_width x dst_height canvas of fill
+ *     for every tile with output == m, in the order of `tiles`:     (a later tile wins where two overlap)
+ *         dst[m][dy .. dy + height, dx .. dx + width] = src[source][sy .. sy + height, sx .. sx + width], clipped to the canvas
+ * Elements are copied as bits; a tile that misses the canvas wholly pastes nothing.
+ *   src            n_sources slots of src_width x src_height pixels of ncomp (1 or 3) components of MJ_DTYPE_* `dtype` in
+ *                  MJ_LAYOUT_* `layout`, DEVICE memory, aligned to its elements.
+ *   dst            n_outputs slots of dst_width x dst_height pixels, same components, dtype and layout; DEVICE memory, aligned to
+ *                  its elements; it must not overlap src.  dst is written in full, every element exactly once, and never read.
+ *   fill_bits      one element bit pattern per component, in the low bytes (what a normalised fill byte is stored as is the
+ *                  caller's business: mj_host_normalize_table).
+ *   tiles          n_tiles records, host memory (n_tiles may be 0: all fill), in paste order; the outputs need not be grouped.
+ *                  At most 64 per output.  x runs along the width; the window lies wholly inside the source canvas, sides >= 1;
+ *                  dx and dy may be negative or beyond the canvas, |dx|, |dy| < 2^20.
+ *   stream         a hipStream_t, or 0 for the context's, as mj_plan_execute takes it.
+ * The host resolves every output's tiles into disjoint rectangles that partition the canvas exactly (csrc/compose_addr.h; "later
+ * wins" is decided there) and cuts them into jobs of lines, copied at the call into a context-owned device buffer; a call that
+ * finds the previous compose launch still in flight waits for it before it rewrites that buffer.  One launch (csrc/compose.hip:
+ * k_compose); nothing synchronises with the host behind it.  MJ_ERR_INVALID, naming the tile: an output or source that is none,
+ * a window with a side below 1 or not inside the source canvas, an offset of 2^20 or more, more than 64 tiles in one output;
+ * overlapping src / dst; pointers not aligned to their elements; NULL; an unknown layout or dtype; ncomp neither 1 nor 3; a size
+ * outside 1..65535; n_sources or n_outputs below 1; n_tiles below 0. */
+typedef struct {
+    int32_t output;                /* the canvas the tile is pasted on, 0 .. n_outputs - 1 */
+    int32_t source;                /* the slot it is taken from, 0 .. n_sources - 1 */
+    int32_t sx, sy, width, height; /* the window of the source canvas, after the mirror */
+    int32_t dx, dy;                /* where the window's top-left corner lands on the output canvas */
+} mj_compose_tile;
+int mj_compose(mj_context *ctx, void *stream, const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp,
+               int32_t src_width, int32_t src_height, int32_t n_sources, int32_t dst_width, int32_t dst_height, int32_t n_outputs,
+               const uint32_t fill_bits[3], int32_t n_tiles, const mj_compose_tile *tiles);
+/* The compose launch alone on the context's stream, `iters` times behind one warm run: ms per launch. */
+int mj_compose_time(mj_context *ctx, int iters, const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp,
+                    int32_t src_width, int32_t src_height, int32_t n_sources, int32_t dst_width, int32_t dst_height, int32_t n_outputs,
+                    const uint32_t fill_bits[3], int32_t n_tiles, const mj_compose_tile *tiles, float *ms);
+/* The host twin of the compose launch (no context): the same records over HOST arrays, through the launch's own resolve and job
+ * list (csrc/compose_addr.h), line by line.  MJ_ERR_INVALID (mj_last_error(NULL)): what mj_compose refuses. */
+int mj_host_compose(const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp, int32_t src_width, int32_t src_height,
+                    int32_t n_sources, int32_t dst_width, int32_t dst_height, int32_t n_outputs, const uint32_t fill_bits[3],
+                    int32_t n_tiles, const mj_compose_tile *tiles);
+/* The rectangles the launch resolves the tiles into (host only): per output, in order, disjoint rectangles whose union is the
+ * canvas; `source` -1: fill, else (x, y) of the canvas is (sx, sy) of that source slot.  Cells of one owner are merged along the
+ * layout's contiguous axis first, then across it.  rects NULL: *n_rects is a capacity that always suffices, the sum over the
+ * outputs of (2 * its tiles + 1)^2.  Else *n_rects is the number of rectangles; MJ_ERR_INVALID when `cap` is below it (nothing
+ * is written then), and for what mj_compose refuses of the geometry and the tiles. */
+typedef struct {
+    int32_t output, x, y, width, height;
+    int32_t source;                /* -1: fill */
+    int32_t sx, sy;
+} mj_compose_rect;
+int mj_host_compose_resolve(int32_t layout, int32_t ncomp, int32_t src_width, int32_t src_height, int32_t n_sources, int32_t dst_width,
+                            int32_t dst_height, int32_t n_outputs, int32_t n_tiles, const mj_compose_tile *tiles, mj_compose_rect *rects,
+                            int32_t cap, int32_t *n_rects);
 /* The host twin of the kernels' mode conversion (no context): n_pixels pixels of src_ncomp (1 or 3) interleaved components into
  * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
  * is neither 1 nor 3, NULL with pixels to convert. */

@@ -58,6 +58,7 @@ EXPORTS = (
     "mj_debug_plan_shape", "mj_debug_cache_stats", "mj_debug_resolved_tables", "mj_plan_derive",
     "mj_plan_set_erase", "mj_plan_time_erase", "mj_host_erase",
     "mj_mix", "mj_mix_time", "mj_host_mix",
+    "mj_compose", "mj_compose_time", "mj_host_compose", "mj_host_compose_resolve",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -232,6 +233,36 @@ def mix_ops(entries):
     return ctypes.cast(arr.ctypes.data, ctypes.POINTER(MixOpC)), arr
 
 
+class ComposeTileC(ctypes.Structure):
+    """mj_compose_tile: one window of one source slot pasted onto one output canvas."""
+    _fields_ = [("output", ctypes.c_int32), ("source", ctypes.c_int32), ("sx", ctypes.c_int32), ("sy", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("dx", ctypes.c_int32), ("dy", ctypes.c_int32)]
+
+
+# mj_compose_tile / mj_compose_rect as NumPy records: eight int32 each
+COMPOSE_TILE_DTYPE = np.dtype([(n, "<i4") for n in ("output", "source", "sx", "sy", "width", "height", "dx", "dy")])
+COMPOSE_RECT_DTYPE = np.dtype([(n, "<i4") for n in ("output", "x", "y", "width", "height", "source", "sx", "sy")])
+assert COMPOSE_TILE_DTYPE.itemsize == ctypes.sizeof(ComposeTileC) == COMPOSE_RECT_DTYPE.itemsize
+
+
+def compose_tiles(outputs):
+    """what the C calls take as ``tiles`` from one list per output of tiles ``(source, (dx, dy), (sx, sy, width, height))``, in paste
+    order — or a ready array of COMPOSE_TILE_DTYPE records, which the tests of the library's refusals pass.  Returns (pointer or
+    None, number of tiles, what keeps them alive)."""
+    if isinstance(outputs, np.ndarray):
+        arr = np.ascontiguousarray(outputs, dtype=COMPOSE_TILE_DTYPE)
+    else:
+        rows = [(m, s, w[0], w[1], w[2], w[3], d[0], d[1]) for m, tiles in enumerate(outputs) for s, d, w in tiles]
+        arr = np.zeros(len(rows), dtype=COMPOSE_TILE_DTYPE)
+        if rows:
+            arr.view(np.int32).reshape(-1, 8)[:] = np.array(rows, dtype=np.int64)
+    return (ctypes.cast(arr.ctypes.data, ctypes.POINTER(ComposeTileC)) if len(arr) else None), len(arr), arr
+
+
+def _fill_bits(fill_bits):
+    return (ctypes.c_uint32 * 3)(*([int(v) for v in fill_bits] + [0, 0, 0])[:3])
+
+
 class PlanRequestC(ctypes.Structure):
     """mj_plan_request: what a plan's output is to be; zeroed, the plain plan.  Every field of the header's struct, in its order."""
     _fields_ = [("rois", ctypes.POINTER(RoiC)), ("orientations", ctypes.c_void_p), ("mode", ctypes.c_int32),
@@ -326,6 +357,11 @@ def load_library():
     L.mj_mix.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(MixOpC)]
     L.mj_mix_time.argtypes = [vp, ctypes.c_int, vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(MixOpC), ctypes.POINTER(ctypes.c_float)]
     L.mj_host_mix.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(MixOpC)]
+    u32p, tiles = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ComposeTileC)
+    L.mj_compose.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32p, i32, tiles]
+    L.mj_compose_time.argtypes = [vp, ctypes.c_int, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32p, i32, tiles, ctypes.POINTER(ctypes.c_float)]
+    L.mj_host_compose.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32p, i32, tiles]
+    L.mj_host_compose_resolve.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, tiles, vp, i32, ctypes.POINTER(i32)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
     L.mj_plan_destroy.restype = None
@@ -614,6 +650,42 @@ def host_mix(src: np.ndarray, layout: int, dtype: str, ncomp: int, width: int, h
     return dst
 
 
+def host_compose(src: np.ndarray, layout: int, dtype: str, ncomp: int, src_size, dst_size, fill_bits, outputs, n_outputs: Optional[int] = None) -> np.ndarray:
+    """mj_host_compose (host only): the compose launch's records over the host array ``src`` — ``len(src)`` slots of ``src_size`` =
+    (width, height) pixels of ``ncomp`` components of ``dtype`` (bfloat16: uint16 bit patterns) in MJ_LAYOUT_* ``layout`` — into a
+    new array of ``len(outputs)`` (or ``n_outputs``) slots of ``dst_size``; ``outputs``: :func:`compose_tiles`'; ``fill_bits``: one
+    element bit pattern per component.  ValueError with the library's message for what it refuses."""
+    if not src.flags["C_CONTIGUOUS"] or src.itemsize != DTYPE_BYTES[dtype]:
+        raise ValueError("mj_host_compose: a contiguous array of the dtype's element size")
+    L = load_library()
+    (sw, sh), (dw, dh) = src_size, dst_size
+    tiles, n_tiles, _keep = compose_tiles(outputs)
+    m = int(n_outputs) if n_outputs is not None else len(outputs)
+    dst = np.empty((max(m, 0), max(int(dw) * int(dh) * int(ncomp), 0)), dtype=src.dtype)
+    if L.mj_host_compose(_ptr(src), _ptr(dst), int(layout), DTYPES[dtype], int(ncomp), int(sw), int(sh), len(src), int(dw), int(dh), m,
+                         _fill_bits(fill_bits), n_tiles, tiles) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+    return dst
+
+
+def host_compose_resolve(layout: int, ncomp: int, src_size, n_sources: int, dst_size, outputs, n_outputs: Optional[int] = None):
+    """mj_host_compose_resolve (host only): (the rectangles the launch resolves ``outputs`` into, as an array of COMPOSE_RECT_DTYPE
+    records; the capacity the library reports as always sufficient).  ValueError with the library's message for what it refuses."""
+    L = load_library()
+    (sw, sh), (dw, dh) = src_size, dst_size
+    tiles, n_tiles, _keep = compose_tiles(outputs)
+    m = int(n_outputs) if n_outputs is not None else len(outputs)
+    args = (int(layout), int(ncomp), int(sw), int(sh), int(n_sources), int(dw), int(dh), m, n_tiles, tiles)
+    cap = ctypes.c_int32()
+    if L.mj_host_compose_resolve(*args, None, 0, ctypes.byref(cap)) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+    rects = np.zeros(cap.value, dtype=COMPOSE_RECT_DTYPE)
+    n = ctypes.c_int32()
+    if L.mj_host_compose_resolve(*args, _ptr(rects), cap.value, ctypes.byref(n)) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+    return rects[:n.value].copy(), cap.value
+
+
 class DeviceBytes:
     """A block of device memory of the HIP runtime's own (hipMalloc), filled from a host array: what the NumPy route keeps the values
     of ``erase=`` and the arrays of ``mix=`` in — no torch there.  ``ptr`` is the device address; close() frees it."""
@@ -861,6 +933,27 @@ class Context:
         ops, _keep = mix_ops(entries)
         self.check(self.lib.mj_mix_time(self.handle, iters, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(width), int(height),
                                         len(entries), ops, ctypes.byref(ms)))
+        return ms.value
+
+    def compose(self, src: int, dst: int, layout: int, dtype: str, ncomp: int, src_size, n_sources: int, dst_size, fill_bits, outputs,
+                stream: int = 0, n_outputs: Optional[int] = None):
+        """mj_compose: one launch on ``stream`` (0: the context's) that writes the ``len(outputs)`` (or ``n_outputs``) canvases of
+        ``dst_size`` = (width, height) at device address ``dst`` from the ``n_sources`` slots of ``src_size`` at ``src`` — ``outputs``:
+        :func:`compose_tiles`', ``fill_bits``: one element bit pattern per component.  BackendError with the library's message, which
+        names the tile, for what it refuses."""
+        tiles, n_tiles, _keep = compose_tiles(outputs)
+        m = int(n_outputs) if n_outputs is not None else len(outputs)
+        self.check(self.lib.mj_compose(self.handle, stream or None, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]),
+                                       int(n_sources), int(dst_size[0]), int(dst_size[1]), m, _fill_bits(fill_bits), n_tiles, tiles))
+
+    def time_compose(self, src: int, dst: int, layout: int, dtype: str, ncomp: int, src_size, n_sources: int, dst_size, fill_bits, outputs,
+                     iters: int = 10) -> float:
+        """ms per compose launch alone, on the context's stream (mj_compose_time)."""
+        ms = ctypes.c_float()
+        tiles, n_tiles, _keep = compose_tiles(outputs)
+        self.check(self.lib.mj_compose_time(self.handle, iters, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]),
+                                            int(n_sources), int(dst_size[0]), int(dst_size[1]), len(outputs), _fill_bits(fill_bits), n_tiles, tiles,
+                                            ctypes.byref(ms)))
         return ms.value
 
     def cache_stats(self):

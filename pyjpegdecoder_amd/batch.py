@@ -674,7 +674,7 @@ def select_union_files(files: Sequence[bytes], groups: Sequence[dict]):
 
 
 # the keys of an entry of ``also``: what is per output and never inherited, and what is the call's unless the entry says otherwise
-ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase", "mix")
+ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase", "mix", "compose")
 ALSO_CALL_WIDE = ("dtype", "normalize", "resample", "mode", "reducing_gap", "fill", "affine_resample", "affine_fill")
 
 
@@ -730,7 +730,7 @@ def normalize_also(also, call: dict, size, rois=None, return_seams: bool = False
             normalize_transform(g["affine"], g["perspective"], g["affine_resample"], g["affine_fill"], g["size"], None, gap)
             normalize_color_ops(g["color_ops"], g["size"])
             normalize_erase(g["erase"], g["size"], device=None if host else -1)
-            normalize_mix(g["mix"], g["size"])
+            normalize_compose(g["compose"], g["size"], mix=normalize_mix(g["mix"], g["size"]))
             if g["views"] is not None and not isinstance(g["views"], (list, tuple)):
                 normalize_views(g["views"], [], g["size"])
         except ValueError as e:
@@ -1343,6 +1343,139 @@ def cutmix_box(size, lam: float, generator=None):
     return (x1, y1, w, h), 1.0 - (w * h) / float(W * H)
 
 
+COMPOSE_MAX_TILES = 64          # tiles of one composed output (csrc/compose_addr.h: kComposeMaxTiles)
+COMPOSE_MAX_OFFSET = 1 << 20    # |dx|, |dy| stay below it
+
+
+def normalize_compose(compose, size, n_outputs: Optional[int] = None, ncomp: Optional[int] = None, return_seams: bool = False, mix=None):
+    """``compose`` of a call, checked: None for a call without it, else ``{"size": (W, H), "fill": None or a tuple of bytes,
+    "outputs": [[(source, (dx, dy), (sx, sy, w, h)), ...], ...]}`` with every tile in its full form.
+
+    ``compose``: None, or a dict with ``size`` — (W, H) of the composed canvases, 1..65535 each, independent of the call's ``size``,
+    which stays the size of the tiles —, optionally ``fill`` — None (the call's ``fill``, 0 where that is absent), one byte 0..255
+    or one per output component; it goes through ``dtype`` / ``normalize`` like a pixel — and ``outputs``: a list with one entry
+    per composed output, each a list of at most 64 tiles applied in order (``[]``: a canvas of fill).  A tile is ``(source, (dx,
+    dy))`` or ``(source, (dx, dy), (sx, sy, w, h))``: the window (default: the whole canvas; x along the width, after the mirror)
+    of output ``source`` of the same group lands with its top-left corner at the integers ``(dx, dy)``, which may be negative or
+    beyond the canvas; the paste is clipped as ``Image.paste`` clips it and a later tile wins (tools/compose_model.py).  The call
+    then returns the ``len(outputs)`` composed canvases in place of the tiles.
+
+    ``compose`` needs ``size`` and goes neither with ``return_seams`` nor, for now, with ``mix`` (:func:`normalize_mix`'s result
+    for the same group).  ``n_outputs`` / ``ncomp`` None: not known yet — what needs them is not checked.  ValueError, naming the
+    output and the tile, otherwise."""
+    if compose is None:
+        return None
+    if size is None:
+        raise ValueError("compose needs size=(width, height): the tiles are the outputs of one array")
+    if return_seams:
+        raise ValueError("compose and return_seams do not go together: the seam outputs are the decoded images")
+    if mix is not None:
+        raise ValueError("compose and mix do not go together in one group (for now): mix's entries would have to mean composed outputs")
+    if not isinstance(compose, dict):
+        raise ValueError(f"compose must be None or a dict (size=, fill=, outputs=), not {compose!r}")
+    for key in compose:
+        if key not in ("size", "fill", "outputs"):
+            raise ValueError(f"compose: unknown key {key!r} (size, fill, outputs)")
+    cs = compose.get("size")
+    if not isinstance(cs, (tuple, list)) or len(cs) != 2 or not all(_is_int(v) and 1 <= int(v) <= 65535 for v in cs):
+        raise ValueError(f"compose: size is required: (width, height) of the composed canvases, 1..65535 each, not {cs!r}")
+    fill = compose.get("fill")
+    if fill is not None:
+        if _is_int(fill):
+            fill = (int(fill),) * (ncomp or 1)
+        elif isinstance(fill, (tuple, list, np.ndarray)) and 1 <= len(fill) <= 3 and all(_is_int(v) for v in fill) and (ncomp is None or len(fill) == ncomp):
+            fill = tuple(int(v) for v in fill)
+        else:
+            raise ValueError(f"compose: fill must be None, one byte or one per output component ({ncomp if ncomp is not None else '1 or 3'}), not {fill!r}")
+        if any(v < 0 or v > 255 for v in fill):
+            raise ValueError(f"compose: fill must be 0..255, not {fill!r}")
+    outputs = compose.get("outputs")
+    if not isinstance(outputs, list) or len(outputs) == 0:
+        raise ValueError(f"compose: outputs must be a list with one list of tiles per composed output, at least one, not {outputs!r}")
+    W, H = size
+    whole = (0, 0, W, H)
+    limit = n_outputs if n_outputs is not None else 1 << 31
+    out = []
+    for m, tiles in enumerate(outputs):
+        if not isinstance(tiles, (list, tuple)):
+            raise ValueError(f"compose: output {m}: an entry is a list of tiles, not {tiles!r}")
+        if len(tiles) > COMPOSE_MAX_TILES:
+            raise ValueError(f"compose: output {m}: {len(tiles)} tiles, more than {COMPOSE_MAX_TILES}")
+        entry = []
+        for t, tile in enumerate(tiles):
+            if type(tile) is tuple and len(tile) == 3:      # (the everyday tile, told by exact types: a batch has a thousand of them)
+                s, at, win = tile
+                if type(s) is int and type(at) is tuple and type(win) is tuple and len(at) == 2 and len(win) == 4 and 0 <= s < limit:
+                    (dx, dy), (sx, sy, w, h) = at, win
+                    if (type(dx) is int and type(dy) is int and type(sx) is int and type(sy) is int and type(w) is int and type(h) is int
+                            and -COMPOSE_MAX_OFFSET < dx < COMPOSE_MAX_OFFSET and -COMPOSE_MAX_OFFSET < dy < COMPOSE_MAX_OFFSET
+                            and w >= 1 and h >= 1 and sx >= 0 and sy >= 0 and sx + w <= W and sy + h <= H):
+                        entry.append(tile)
+                        continue
+            where = f"compose: output {m}, tile {t}"
+            if not isinstance(tile, (tuple, list)) or len(tile) not in (2, 3):
+                raise ValueError(f"{where}: a tile is (source, (dx, dy)) or (source, (dx, dy), (sx, sy, w, h)), not {tile!r}")
+            s, at = tile[0], tile[1]
+            win = tile[2] if len(tile) == 3 else whole
+            if not _is_int(s) or int(s) < 0 or (n_outputs is not None and int(s) >= n_outputs):
+                raise ValueError(f"{where}: source {s!r} is not the index of an output, an integer 0..{n_outputs - 1 if n_outputs is not None else 'N-1'}")
+            if not isinstance(at, (tuple, list, np.ndarray)) or len(at) != 2 or not all(_is_int(v) for v in at):
+                raise ValueError(f"{where}: the offset is two integers (dx, dy), not {at!r}")
+            if not isinstance(win, (tuple, list, np.ndarray)) or len(win) != 4 or not all(_is_int(v) for v in win):
+                raise ValueError(f"{where}: the window is four integers (sx, sy, w, h), not {win!r}")
+            dx, dy = (int(v) for v in at)
+            if abs(dx) >= COMPOSE_MAX_OFFSET or abs(dy) >= COMPOSE_MAX_OFFSET:
+                raise ValueError(f"{where}: offset ({dx}, {dy}) is 2**20 or more from the origin")
+            sx, sy, w, h = (int(v) for v in win)
+            if w < 1 or h < 1:
+                raise ValueError(f"{where}: the window's width and height must be at least 1, not {w} x {h}")
+            if sx < 0 or sy < 0 or sx + w > W or sy + h > H:
+                raise ValueError(f"{where}: window ({sx}, {sy}, {w}, {h}) is not inside the {W} x {H} tile canvas")
+            entry.append((int(s), (dx, dy), (sx, sy, w, h)))
+        out.append(entry)
+    return {"size": (int(cs[0]), int(cs[1])), "fill": fill, "outputs": out}
+
+
+def compose_for_components(composed, compose, size, ncomp: int):
+    """:func:`normalize_compose`'s result (``composed``, of ``compose``) once the files' component count is known: its fill checked
+    against it (the tiles are as they were)"""
+    if composed is None:
+        return None
+    fill = normalize_compose({"size": composed["size"], "fill": compose.get("fill"), "outputs": [[]]}, size, None, ncomp)["fill"]
+    return dict(composed, fill=fill)
+
+
+def mosaic_tiles(size, centre, tile_sizes):
+    """The tiles of one four-image mosaic as Ultralytics' ``Mosaic._mosaic4`` places them, for ``compose``'s ``outputs``: ``size`` =
+    (W, H) of the composed canvas, ``centre`` = (xc, yc) on it, ``tile_sizes`` = four (w_i, h_i), the extents of the resized images,
+    each at the top left of its tile canvas (``place=(0, 0)``).  Image 0 goes top-left of the centre, 1 top-right, 2 bottom-left,
+    3 bottom-right, each with its inner corner at the centre, and of each the part next to that corner that the canvas holds is
+    taken.  Returns up to four ``(i, (dx, dy), (sx, sy, w, h))``; an image the canvas does not reach is left out.  The centre is
+    the caller's draw, and this function is NOT pinned to Ultralytics' draws; boxes and labels stay with the caller."""
+    W, H = (int(v) for v in size)
+    xc, yc = (int(v) for v in centre)
+    if len(tile_sizes) != 4:
+        raise ValueError(f"mosaic_tiles takes four (width, height), not {len(tile_sizes)}")
+    out = []
+    for i, (w, h) in enumerate(tile_sizes):
+        w, h = int(w), int(h)
+        if i == 0:
+            x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
+            x1b, y1b = w - (x2a - x1a), h - (y2a - y1a)
+        elif i == 1:
+            x1a, y1a, x2a, y2a = xc, max(yc - h, 0), min(xc + w, W), yc
+            x1b, y1b = 0, h - (y2a - y1a)
+        elif i == 2:
+            x1a, y1a, x2a, y2a = max(xc - w, 0), yc, xc, min(H, yc + h)
+            x1b, y1b = w - (x2a - x1a), 0
+        else:
+            x1a, y1a, x2a, y2a = xc, yc, min(xc + w, W), min(H, yc + h)
+            x1b, y1b = 0, 0
+        if x2a - x1a >= 1 and y2a - y1a >= 1:
+            out.append((i, (x1a, y1a), (x1b, y1b, x2a - x1a, y2a - y1a)))
+    return out
+
+
 def rotation_matrix(angle: float, size: Tuple[int, int], center=None, translate=None) -> Tuple[float, ...]:
     """The matrix ``Image.rotate(angle, center=center, translate=translate)`` builds for ``expand=False`` on an image of ``size`` =
     (width, height) — counter-clockwise by ``angle`` degrees around ``center`` (None: the image's centre), then moved by
@@ -1573,6 +1706,9 @@ class _Request:
     # :func:`normalize_mix`'s entries, one or None per OUTPUT of the whole group (None: no mixing).  The CALL's, not a plan's: the
     # requests of its parts, kinds and rounds (:meth:`narrow`) do not carry it, and it is applied once they have all been collected
     mix: Optional[List[Optional[tuple]]] = None
+    # :func:`normalize_compose`'s dict (None: the outputs as they are).  The CALL's as ``mix`` is: the group's tensor is composed into a
+    # new one of ``compose["size"]`` once every plan has been collected
+    compose: Optional[dict] = None
     # the extra groups of a call with ``also``: requests over the SAME files, index and orientations, each with its own size, views, output,
     # tensor and slots (None: a call without).  A group with views need not name every file here; what it has none of it is left out of.
     also: Optional[List["_Request"]] = None
@@ -1926,7 +2062,7 @@ class BatchDecoder:
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -2015,6 +2151,13 @@ class BatchDecoder:
         plan: ONE launch (csrc/mix.hip) over the whole array once every plan of the call has been collected, from that array into a
         second one, which is what the call returns — here the array is uploaded, mixed by the library and downloaded.  Entries that are
         all None: the call without the argument.  An ``also`` entry takes a key ``mix`` of its own, over its own outputs.
+        ``compose``, with ``size``: several outputs pasted onto one canvas (:func:`normalize_compose`, tools/compose_model.py) — None, or
+        a dict ``size`` (of the composed canvases; the call's ``size`` stays the tiles'), ``fill`` and ``outputs``, one list of tiles
+        ``(source, (dx, dy)[, (sx, sy, w, h)])`` per composed output: Mosaic (:func:`mosaic_tiles`), image grids, a crop of one
+        sample in another.  The last step, behind ``erase``, and like ``mix`` not a step of any plan: ONE launch (csrc/compose.hip)
+        over the tile array once every plan of the call has been collected, into an array of ``len(outputs)`` canvases, which is what
+        the call returns in place of the tiles.  Not together with ``mix`` in one group.  An ``also`` entry takes a key ``compose`` of
+        its own, over its own outputs.
         ``also``, with ``size``: several groups of outputs from ONE decode (:func:`normalize_also`) — None or ``[]`` (the call as it
         is), else a list with one dict per extra group: ``size`` (required) and that group's own ``views``, ``mirror``, ``resize_to``,
         ``place``, ``affine``, ``perspective`` and ``color_ops`` (None when absent, never the call's); ``dtype``, ``normalize``,
@@ -2026,7 +2169,7 @@ class BatchDecoder:
         ``return_seams``."""
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective, erase=erase, mix=mix)
+                    perspective=perspective, erase=erase, mix=mix, compose=compose)
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -2115,6 +2258,8 @@ class BatchDecoder:
         for j, g in enumerate(req.groups):      # (behind every plan of the call: the groups' arrays mixed, each within itself)
             if g.mix is not None:
                 denses[j] = self._mix_host(g, denses[j])
+            if g.compose is not None:
+                denses[j] = self._compose_host(g, denses[j])
         if extra is not None:
             return tuple(denses)
         if denses[0] is not None:
@@ -2124,7 +2269,7 @@ class BatchDecoder:
     def _host_request(self, files: Sequence[bytes], cache: Dict[int, ParsedJpeg], gpu_segment: Optional[bool], rois=None, return_seams: bool = False,
                       size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None,
                       fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, erase=None,
-                      mix=None):
+                      mix=None, compose=None):
         """The checked request of a :meth:`decode` call, or of one group of it, and the array it fills (None without ``size``).  ``cache``:
         the parsed files by their position in ``files``, filled with those this request names; ``gpu_segment``: whether they are parsed
         headers only (None: decided by the files this request names)."""
@@ -2140,6 +2285,7 @@ class BatchDecoder:
                                 dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams)
         mixes = normalize_mix(mix, size, len(views) if isinstance(views, (list, tuple)) else len(files),
                               dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams)
+        composed = normalize_compose(compose, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES[mode] if mode else None, return_seams, mixes)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None                            # views: where the files that are read sit in the caller's list
@@ -2175,6 +2321,7 @@ class BatchDecoder:
                 req.affine = _spec_for_outputs(spec, size, req.n_outputs, nc)
             req.erase = erase_for_components(boxes, nc)
             req.mix = mixes
+            req.compose = compose_for_components(composed, compose, size, nc)
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         return req, dense
 
@@ -2188,7 +2335,7 @@ class BatchDecoder:
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
                         resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                        affine_fill=None, color_ops=None, perspective=None, erase=None, mix=None) -> _Request:
+                        affine_fill=None, color_ops=None, perspective=None, erase=None, mix=None, compose=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
@@ -2202,6 +2349,7 @@ class BatchDecoder:
                                     dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", device=self.ctx.device)
         mixes = normalize_mix(mix, size, len(views) if isinstance(views, (list, tuple)) else len(files),
                               dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8")
+        composed = normalize_compose(compose, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES.get(mode) if isinstance(mode, str) else None, mix=mixes)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None
@@ -2230,6 +2378,7 @@ class BatchDecoder:
             req.fill = normalize_fill(fill, resize_to, nc)
             req.erase = erase_for_components(boxes, nc)
             req.mix = mixes
+            req.compose = compose_for_components(composed, compose, size, nc)
             req.dest = torch.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
             req.slots = list(range(req.n_outputs))
@@ -2248,7 +2397,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -2298,7 +2447,9 @@ class BatchDecoder:
         output's type (host arrays uploaded once, one ``torch.cat``) that the plan holds until it is collected.
         ``mix`` as in :meth:`decode`: once every plan of the call — kinds of files, orientation classes, parts, second rounds — has been
         collected, each group's tensor is the source of ONE launch on torch's current stream into a new tensor of the same shape, which
-        the caller gets; the source goes back to torch's allocator."""
+        the caller gets; the source goes back to torch's allocator.
+        ``compose`` as in :meth:`decode`: likewise once every plan of the call has been collected, one launch on torch's current stream
+        from the group's tile tensor into a new tensor of ``len(outputs)`` composed canvases, which the caller gets."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -2308,7 +2459,7 @@ class BatchDecoder:
         normalize_fill(fill, resize_to)
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective, erase=erase, mix=mix)
+                    perspective=perspective, erase=erase, mix=mix, compose=compose)
         extra = normalize_also(also, main, size, rois)
         if extra is None:
             req = self._device_request(files, rois, orientation=orientation, **main)
@@ -2333,13 +2484,71 @@ class BatchDecoder:
 
     def _mixed(self, req: _Request, out):
         """What a call returns for a request whose plans have all been collected (``out``: :meth:`_decode_request`'s): every group
-        with ``mix`` entries has its tensor mixed into a new one (:meth:`_mix_device`), which takes its place."""
-        if all(g.mix is None for g in req.groups):
+        with ``mix`` entries has its tensor mixed into a new one (:meth:`_mix_device`), every group with ``compose`` its tiles composed
+        into a new one (:meth:`_composed`), which takes its place."""
+        if all(g.mix is None and g.compose is None for g in req.groups):
             return self._result(req, out)
         for g in req.groups:
             if g.mix is not None:
                 g.dest = self._mix_device(g)
+            if g.compose is not None:
+                g.dest = self._composed(g)
         return self._result(req, req.dest)
+
+    def _compose_fill_bits(self, g: _Request, nc: int):
+        """the element bit patterns, one per component, of a group's compose fill: its bytes — ``compose``'s own, else the group's
+        ``fill``, else 0 — as the group's outputs store such a pixel (the table the resize launch stores through)"""
+        fill = g.compose["fill"] if g.compose["fill"] is not None else g.fill if g.fill is not None else (0,) * nc
+        if g.output is None or g.output.dtype == "uint8":
+            return [int(v) for v in fill]
+        mean, std = (g.output.mean, g.output.std) if g.output.mean is not None else ((0.0,) * nc, (1.0,) * nc)
+        return [int(B.normalize_table(g.output.dtype, mean[c], std[c])[fill[c]]) for c in range(nc)]
+
+    def _composed(self, g: _Request):
+        """Group ``g``'s tensor composed (mj_compose): one launch from ``g.dest`` — the tiles, which every plan has finished writing —
+        into a new tensor of ``len(outputs)`` canvases of ``compose``'s size, on torch's current stream as :meth:`_mix_device` does it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        src = g.dest
+        dtype, nc, W, H = self._mix_geometry(g, src[0].numel())
+        cw, ch = g.compose["size"]
+        outputs = g.compose["outputs"]
+        bits = self._compose_fill_bits(g, nc)
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            dst = torch.empty((len(outputs),) + self._shape(cw, ch, nc), dtype=src.dtype, device=dev)
+            args = (self.layout, dtype, nc, (W, H), src.shape[0], (cw, ch), bits, outputs)
+            if cur.cuda_stream:
+                if src.device == dev:
+                    src.record_stream(cur)      # (allocated on the stream the call was made on, which may be another)
+                self.ctx.compose(src.data_ptr(), dst.data_ptr(), *args, stream=cur.cuda_stream)
+                return dst
+            if getattr(self, "_mix_stream", None) is None:
+                self._mix_stream = torch.cuda.Stream(device=dev)
+            st = self._mix_stream
+            st.wait_stream(cur)
+            src.record_stream(st)
+            dst.record_stream(st)
+            self.ctx.compose(src.data_ptr(), dst.data_ptr(), *args, stream=st.cuda_stream)
+            cur.wait_stream(st)
+        return dst
+
+    def _compose_host(self, g: _Request, dense: np.ndarray) -> np.ndarray:
+        """Group ``g``'s array composed (mj_compose): uploaded, one launch on the context's stream into a second block, downloaded"""
+        dtype, nc, W, H = self._mix_geometry(g, int(dense[0].size))
+        cw, ch = g.compose["size"]
+        outputs = g.compose["outputs"]
+        out = np.empty((len(outputs),) + tuple(self._shape(cw, ch, nc)), dtype=dense.dtype)
+        src = B.DeviceBytes(dense)
+        try:
+            dst = B.DeviceBytes(None, out.nbytes)
+            try:
+                self.ctx.compose(src.ptr, dst.ptr, self.layout, dtype, nc, (W, H), dense.shape[0], (cw, ch), self._compose_fill_bits(g, nc), outputs)
+                return dst.download(out)
+            finally:
+                dst.close()
+        finally:
+            src.close()
 
     def _mix_geometry(self, g: _Request, elements_per_output: int):
         """(dtype name, components, width, height) of a group's outputs"""
@@ -2492,7 +2701,7 @@ class BatchDecoder:
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None):
+                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -2520,7 +2729,8 @@ class BatchDecoder:
         :meth:`decode_device` takes for that batch — a list with one dict per extra group; every batch is then handed out as a tuple
         of tensors, one per group.  ``erase``: None, or an iterable that yields, batch by batch, what :meth:`decode_device` takes for
         that batch — a list with one entry per output, or None.  ``mix``: None, or an iterable that yields, batch by batch, what
-        :meth:`decode_device` takes for that batch; the batch is mixed when it is collected, before it is handed out."""
+        :meth:`decode_device` takes for that batch; the batch is mixed when it is collected, before it is handed out.  ``compose``: None, or an
+        iterable that yields, batch by batch, the dict :meth:`decode_device` takes for that batch, or None."""
         size = normalize_size(size)
         if also is not None and isinstance(also, (list, tuple)) and len(also) == 0:
             also = None                                                               # (no extra group: a call without the argument)
@@ -2533,6 +2743,11 @@ class BatchDecoder:
         if mix is not None and size is None:
             raise ValueError("mix needs size=(width, height): the outputs of one array are mixed with each other")
         per_batch_mix = iter(mix) if mix is not None else None
+        if compose is not None and size is None:
+            raise ValueError("compose needs size=(width, height): the tiles are the outputs of one array")
+        if isinstance(compose, dict):
+            raise ValueError("compose must be None or an iterable that yields one dict or None per batch, not a dict")
+        per_batch_compose = iter(compose) if compose is not None else None
         normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
         per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
@@ -2610,6 +2825,12 @@ class BatchDecoder:
                         mx = next(per_batch_mix)
                     except StopIteration:
                         raise ValueError("mix yields fewer entries than there are batches") from None
+                cp = None
+                if per_batch_compose is not None:
+                    try:
+                        cp = next(per_batch_compose)
+                    except StopIteration:
+                        raise ValueError("compose yields fewer entries than there are batches") from None
                 def none(g):
                     return g is None or (isinstance(g, (list, tuple)) and all(e is None for e in g))
                 if per_batch_also is not None:
@@ -2620,17 +2841,17 @@ class BatchDecoder:
                     plain = none(t) and none(ps)
                     main = dict(size=size, dtype=dtype, normalize=normalize, mirror=m, resample=resample, mode=mode, resize_to=resize_to, place=place,
                                 fill=fill, reducing_gap=reducing_gap, views=v, affine=None if none(t) else t, affine_resample=None if plain else affine_resample,
-                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er, mix=mx)
+                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er, mix=mx, compose=cp)
                     extra = normalize_also(a, dict(main, affine_resample=affine_resample, affine_fill=affine_fill), size)
                     if extra is not None:
                         yield self._merged_request(files, o, [main] + extra, lambda fs, **kw: self._device_request(fs, None, **kw))
                         continue
                 if none(t) and none(ps):                # (a batch without a transform)
                     yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                               color_ops=c, erase=er, mix=mx)
+                                               color_ops=c, erase=er, mix=mx, compose=cp)
                     continue
                 yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er, mx)
+                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er, mx, cp)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

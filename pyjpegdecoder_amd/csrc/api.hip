@@ -104,6 +104,10 @@ void mj_destroy(mj_context *ctx) {
     if (ctx->mix_done) (void)hipEventDestroy(ctx->mix_done);
     if (ctx->h_mix) (void)hipHostFree(ctx->h_mix);
     if (ctx->d_mix) (void)hipFree(ctx->d_mix);
+    if (ctx->compose_flying) (void)hipEventSynchronize(ctx->compose_done);
+    if (ctx->compose_done) (void)hipEventDestroy(ctx->compose_done);
+    if (ctx->h_compose) (void)hipHostFree(ctx->h_compose);
+    if (ctx->d_compose) (void)hipFree(ctx->d_compose);
     if (ctx->d_idct_tt) (void)hipFree(ctx->d_idct_tt);
     if (ctx->d_dump) (void)hipFree(ctx->d_dump);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -114,6 +114,11 @@ struct mj_context {
     size_t mix_cap = 0;
     hipEvent_t mix_done = nullptr;
     bool mix_flying = false;
+    // mj_compose (compose.hip), the other launch of a call: its job list goes the same way through blocks and an event of its own
+    void *h_compose = nullptr, *d_compose = nullptr;
+    size_t compose_cap = 0;
+    hipEvent_t compose_done = nullptr;
+    bool compose_flying = false;
     DevBufferCache cache;
     std::string err;
 };
