@@ -742,6 +742,57 @@ typedef struct {
 int mj_host_compose_resolve(int32_t layout, int32_t ncomp, int32_t src_width, int32_t src_height, int32_t n_sources, int32_t dst_width,
                             int32_t dst_height, int32_t n_outputs, int32_t n_tiles, const mj_compose_tile *tiles, mj_compose_rect *rects,
                             int32_t cap, int32_t *n_rects);
+/* Patchify: the finished outputs of a CALL cut into patch x patch patches and packed as the token rows of a native-resolution
+ * vision encoder (tools/patch_model.py) — Qwen2-VL's pixel_values, NaFlex's patches: ... -> erase -> mix | compose -> PATCHES.
+ * Like mj_mix and mj_compose a launch over the caller's whole batch, once every plan that writes it has been synchronised.  It
+ * reads `src` and writes `dst`, a matrix of rows of D = ncomp * repeat * patch * patch elements.  With source k's window
+ * (x, y, width, height), gh = height / patch, gw = width / patch, m = merge, t = repeat, P = patch:
+ *     row = row0[k] + ((py / m) * (gw / m) + px / m) * m * m + (py % m) * m + px % m             patch (py, px) of source k
+ *     MJ_PATCH_CHW:  dst[row][((c * t + r) * P + j) * P + i] = window_k[c][py * P + j][px * P + i]        for r in 0 .. t - 1
+ *     MJ_PATCH_HWC:  dst[row][(j * P + i) * ncomp + c]       = window_k[c][py * P + j][px * P + i]
+ * whatever `layout` is.  Elements are copied as bits.  length 0, the packed form: row0[k] is the number of tokens of the sources
+ * before k and dst has sum(gh_k * gw_k) rows.  length L >= 1, the padded form: row0[k] = k * L, dst has n_sources * L rows and
+ * the rows behind a source's last token hold element bit pattern 0.
+ *   src            n_sources slots of src_width x src_height pixels of ncomp (1 or 3) components of MJ_DTYPE_* `dtype` in
+ *                  MJ_LAYOUT_* `layout`, DEVICE memory, aligned to its elements.
+ *   dst            exactly rows * D elements (mj_host_patchify_count gives the rows); DEVICE memory, aligned to its elements —
+ *                  no more: a row starts wherever it starts —; it must not overlap src.  dst is written in full, every element
+ *                  exactly once, and never read.
+ *   patch, merge, repeat   1..64, 1..8, 1..4; MJ_PATCH_HWC needs repeat 1.  A merge block, merge * merge * D elements, is at
+ *                  most 65536 bytes.
+ *   windows        one record per source, host memory, or NULL: the whole canvas of every source.  x runs along the width; the
+ *                  window lies wholly inside the canvas; width and height are multiples of patch * merge, at least one.
+ *   stream         a hipStream_t, or 0 for the context's, as mj_plan_execute takes it.
+ * The host cuts the output into jobs — runs of merge blocks of one merge band, whose tokens are one contiguous range of dst
+ * (csrc/patch_addr.h) —, copied at the call into a context-owned device buffer; a call that finds the previous patchify launch
+ * still in flight waits for it before it rewrites that buffer.  One launch (csrc/patch.hip: k_patchify); nothing synchronises
+ * with the host behind it.  MJ_ERR_INVALID, naming the source: a window with a side below 1, not inside the canvas or not a
+ * multiple of patch * merge (the whole canvas under NULL likewise); a source of more than `length` tokens; patch, merge or repeat
+ * outside its range; an unknown order, MJ_PATCH_HWC with repeat above 1; length below 0; a merge block of more than 65536 bytes;
+ * overlapping src / dst; pointers not aligned to their elements; NULL; an unknown layout or dtype; ncomp neither 1 nor 3; a size
+ * outside 1..65535; n_sources below 1; more bytes than an address holds. */
+#define MJ_PATCH_CHW 0   /* a token is (C, t, P, P): Qwen2-VL */
+#define MJ_PATCH_HWC 1   /* a token is (P, P, C): SigLIP 2 NaFlex, timm NaFlexVit */
+typedef struct {
+    int32_t x, y, width, height;
+} mj_patch_window;
+int mj_patchify(mj_context *ctx, void *stream, const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp,
+                int32_t src_width, int32_t src_height, int32_t n_sources, int32_t patch, int32_t merge, int32_t repeat, int32_t order,
+                int32_t length, const mj_patch_window *windows);
+/* The patchify launch alone on the context's stream, `iters` times behind one warm run: ms per launch. */
+int mj_patchify_time(mj_context *ctx, int iters, const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp,
+                     int32_t src_width, int32_t src_height, int32_t n_sources, int32_t patch, int32_t merge, int32_t repeat,
+                     int32_t order, int32_t length, const mj_patch_window *windows, float *ms);
+/* The host twin of the patchify launch (no context): the same over HOST arrays, through the launch's own job list and address
+ * rule (csrc/patch_addr.h), element by element.  MJ_ERR_INVALID (mj_last_error(NULL)): what mj_patchify refuses. */
+int mj_host_patchify(const void *src, void *dst, int32_t layout, int32_t dtype, int32_t ncomp, int32_t src_width, int32_t src_height,
+                     int32_t n_sources, int32_t patch, int32_t merge, int32_t repeat, int32_t order, int32_t length,
+                     const mj_patch_window *windows);
+/* The rows of dst (host only): the geometry checked as mj_patchify checks it — MJ_ERR_INVALID for what it refuses of it — and
+ * *rows the number of token rows, n_sources * length in the padded form.  Callers size dst by it. */
+int mj_host_patchify_count(int32_t layout, int32_t dtype, int32_t ncomp, int32_t src_width, int32_t src_height, int32_t n_sources,
+                           int32_t patch, int32_t merge, int32_t repeat, int32_t order, int32_t length, const mj_patch_window *windows,
+                           int64_t *rows);
 /* The host twin of the kernels' mode conversion (no context): n_pixels pixels of src_ncomp (1 or 3) interleaved components into
  * out, which holds n_pixels * (mode, or src_ncomp for MJ_MODE_NATIVE) bytes.  MJ_ERR_INVALID: an unknown mode, a src_ncomp that
  * is neither 1 nor 3, NULL with pixels to convert. */

@@ -18,7 +18,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from .errors import BackendError, CorruptedJpeg, JpegError, NotJpeg, UnsupportedJpeg  # noqa: F401
 from ._parse import ColorComponent, HuffmanTable, exif_orientation, parse_jpeg  # noqa: F401
 from .jpeg_decoder import JpegDecoder  # noqa: F401
-from .batch import BatchDecoder, cutmix_box, mosaic_tiles, normalize_compose, perspective_coeffs, prepare_batch, random_erasing_rect, rotation_matrix  # noqa: F401
+from .batch import BatchDecoder, cutmix_box, mosaic_tiles, normalize_compose, normalize_patches, patch_grids, perspective_coeffs, prepare_batch, random_erasing_rect, rotation_matrix, smart_resize  # noqa: F401
 
-__all__ = ["JpegDecoder", "BatchDecoder", "prepare_batch", "rotation_matrix", "perspective_coeffs", "random_erasing_rect", "cutmix_box", "mosaic_tiles", "normalize_compose", "parse_jpeg", "exif_orientation", "ColorComponent", "HuffmanTable",
+__all__ = ["JpegDecoder", "BatchDecoder", "prepare_batch", "rotation_matrix", "perspective_coeffs", "random_erasing_rect", "cutmix_box", "mosaic_tiles", "normalize_compose", "normalize_patches", "patch_grids", "smart_resize", "parse_jpeg", "exif_orientation", "ColorComponent", "HuffmanTable",
            "JpegError", "NotJpeg", "CorruptedJpeg", "UnsupportedJpeg", "BackendError"]

@@ -59,6 +59,7 @@ EXPORTS = (
     "mj_plan_set_erase", "mj_plan_time_erase", "mj_host_erase",
     "mj_mix", "mj_mix_time", "mj_host_mix",
     "mj_compose", "mj_compose_time", "mj_host_compose", "mj_host_compose_resolve",
+    "mj_patchify", "mj_patchify_time", "mj_host_patchify", "mj_host_patchify_count",
 )
 MJ_FORM_WAVE, MJ_FORM_LANES, MJ_FORM_SYNC, MJ_FORM_SCANS, MJ_FORM_WG_TABLES, MJ_FORM_RESOLVED, MJ_FORM_FUSED, MJ_FORM_COUNT_RESOLVED = 0, 1, 2, 3, 16, 32, 64, 128
 MJ_HOST_DECLINED = 1
@@ -259,6 +260,31 @@ def compose_tiles(outputs):
     return (ctypes.cast(arr.ctypes.data, ctypes.POINTER(ComposeTileC)) if len(arr) else None), len(arr), arr
 
 
+class PatchWindowC(ctypes.Structure):
+    """mj_patch_window: the window of one source that is cut into patches."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+PATCH_ORDERS = {"chw": 0, "hwc": 1}          # MJ_PATCH_*
+
+
+def patch_windows(windows, n_sources: int):
+    """what the C calls take as ``windows``: None (every source's whole canvas), or one ``(x, y, width, height)`` per source — an
+    entry None being the whole ``canvas`` = (width, height), which the caller has put in its place.  Returns (pointer or None,
+    what keeps it alive)."""
+    if windows is None:
+        return None, None
+    arr = np.ascontiguousarray(np.array([tuple(int(v) for v in w) for w in windows], dtype=np.int32).reshape(-1, 4))
+    if len(arr) != n_sources:
+        raise ValueError(f"patches: {len(arr)} windows for {n_sources} sources")
+    return ctypes.cast(arr.ctypes.data, ctypes.POINTER(PatchWindowC)), arr
+
+
+def _patch_args(spec):
+    """(patch, merge, repeat, order, length) of a patch spec as the C calls take them (length None: 0, the packed form)"""
+    return (int(spec["patch"]), int(spec.get("merge", 1)), int(spec.get("repeat", 1)), PATCH_ORDERS[spec.get("order", "chw")], int(spec.get("length") or 0))
+
+
 def _fill_bits(fill_bits):
     return (ctypes.c_uint32 * 3)(*([int(v) for v in fill_bits] + [0, 0, 0])[:3])
 
@@ -361,6 +387,11 @@ def load_library():
     L.mj_compose.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32p, i32, tiles]
     L.mj_compose_time.argtypes = [vp, ctypes.c_int, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32p, i32, tiles, ctypes.POINTER(ctypes.c_float)]
     L.mj_host_compose.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32p, i32, tiles]
+    pw = ctypes.POINTER(PatchWindowC)
+    L.mj_patchify.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, pw]
+    L.mj_patchify_time.argtypes = [vp, ctypes.c_int, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, pw, ctypes.POINTER(ctypes.c_float)]
+    L.mj_host_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, pw]
+    L.mj_host_patchify_count.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, pw, ctypes.POINTER(ctypes.c_int64)]
     L.mj_host_compose_resolve.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, tiles, vp, i32, ctypes.POINTER(i32)]
     L.mj_host_resize_table.argtypes = [i32, i32, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.mj_plan_destroy.argtypes = [vp]
@@ -686,6 +717,37 @@ def host_compose_resolve(layout: int, ncomp: int, src_size, n_sources: int, dst_
     return rects[:n.value].copy(), cap.value
 
 
+def host_patchify_count(layout: int, dtype: str, ncomp: int, src_size, n_sources: int, spec) -> int:
+    """mj_host_patchify_count (host only): the token rows the patchify launch writes for ``spec`` — a dict ``patch``, ``merge``,
+    ``repeat``, ``order``, ``length``, ``windows`` (every entry four integers, or ``windows`` None) — over ``n_sources`` slots of
+    ``src_size`` = (width, height).  ValueError with the library's message, which names the source, for what it refuses."""
+    L = load_library()
+    win, _keep = patch_windows(spec.get("windows"), n_sources)
+    rows = ctypes.c_int64()
+    if L.mj_host_patchify_count(int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]), int(n_sources), *_patch_args(spec), win,
+                                ctypes.byref(rows)) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+    return rows.value
+
+
+def host_patchify(src: np.ndarray, layout: int, dtype: str, ncomp: int, src_size, spec, dst: Optional[np.ndarray] = None) -> np.ndarray:
+    """mj_host_patchify (host only): the patchify launch's jobs over the host array ``src`` — ``len(src)`` slots of ``src_size`` =
+    (width, height) pixels of ``ncomp`` components of ``dtype`` (bfloat16: uint16 bit patterns) in MJ_LAYOUT_* ``layout`` — into a
+    new (rows, D) array, or into ``dst``, which holds exactly that.  ValueError with the library's message for what it refuses."""
+    if not src.flags["C_CONTIGUOUS"] or src.itemsize != DTYPE_BYTES[dtype]:
+        raise ValueError("mj_host_patchify: a contiguous array of the dtype's element size")
+    L = load_library()
+    patch, merge, repeat, order, length = _patch_args(spec)
+    if dst is None:
+        rows = host_patchify_count(layout, dtype, ncomp, src_size, len(src), spec)
+        dst = np.empty((rows, int(ncomp) * repeat * patch * patch), dtype=src.dtype)
+    win, _keep = patch_windows(spec.get("windows"), len(src))
+    if L.mj_host_patchify(_ptr(src), _ptr(dst), int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]), len(src), patch, merge, repeat,
+                          order, length, win) != MJ_OK:
+        raise ValueError(L.mj_last_error(None).decode())
+    return dst
+
+
 class DeviceBytes:
     """A block of device memory of the HIP runtime's own (hipMalloc), filled from a host array: what the NumPy route keeps the values
     of ``erase=`` and the arrays of ``mix=`` in — no torch there.  ``ptr`` is the device address; close() frees it."""
@@ -954,6 +1016,23 @@ class Context:
         self.check(self.lib.mj_compose_time(self.handle, iters, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]),
                                             int(n_sources), int(dst_size[0]), int(dst_size[1]), len(outputs), _fill_bits(fill_bits), n_tiles, tiles,
                                             ctypes.byref(ms)))
+        return ms.value
+
+    def patchify(self, src: int, dst: int, layout: int, dtype: str, ncomp: int, src_size, n_sources: int, spec, stream: int = 0):
+        """mj_patchify: one launch on ``stream`` (0: the context's) that writes the token rows of ``spec`` (as
+        :func:`host_patchify_count` takes it) at device address ``dst`` — exactly rows x D elements — from the ``n_sources`` slots of
+        ``src_size`` = (width, height) at ``src``.  BackendError with the library's message, which names the source, for what it
+        refuses."""
+        win, _keep = patch_windows(spec.get("windows"), n_sources)
+        self.check(self.lib.mj_patchify(self.handle, stream or None, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]),
+                                        int(n_sources), *_patch_args(spec), win))
+
+    def time_patchify(self, src: int, dst: int, layout: int, dtype: str, ncomp: int, src_size, n_sources: int, spec, iters: int = 10) -> float:
+        """ms per patchify launch alone, on the context's stream (mj_patchify_time)."""
+        ms = ctypes.c_float()
+        win, _keep = patch_windows(spec.get("windows"), n_sources)
+        self.check(self.lib.mj_patchify_time(self.handle, iters, src, dst, int(layout), DTYPES[dtype], int(ncomp), int(src_size[0]), int(src_size[1]),
+                                             int(n_sources), *_patch_args(spec), win, ctypes.byref(ms)))
         return ms.value
 
     def cache_stats(self):

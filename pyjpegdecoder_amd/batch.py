@@ -674,7 +674,7 @@ def select_union_files(files: Sequence[bytes], groups: Sequence[dict]):
 
 
 # the keys of an entry of ``also``: what is per output and never inherited, and what is the call's unless the entry says otherwise
-ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase", "mix", "compose")
+ALSO_PER_OUTPUT = ("views", "mirror", "resize_to", "place", "affine", "perspective", "color_ops", "erase", "mix", "compose", "patches")
 ALSO_CALL_WIDE = ("dtype", "normalize", "resample", "mode", "reducing_gap", "fill", "affine_resample", "affine_fill")
 
 
@@ -730,7 +730,8 @@ def normalize_also(also, call: dict, size, rois=None, return_seams: bool = False
             normalize_transform(g["affine"], g["perspective"], g["affine_resample"], g["affine_fill"], g["size"], None, gap)
             normalize_color_ops(g["color_ops"], g["size"])
             normalize_erase(g["erase"], g["size"], device=None if host else -1)
-            normalize_compose(g["compose"], g["size"], mix=normalize_mix(g["mix"], g["size"]))
+            composed = normalize_compose(g["compose"], g["size"], mix=normalize_mix(g["mix"], g["size"]))
+            normalize_patches(g["patches"], g["size"], compose=composed)
             if g["views"] is not None and not isinstance(g["views"], (list, tuple)):
                 normalize_views(g["views"], [], g["size"])
         except ValueError as e:
@@ -1476,6 +1477,144 @@ def mosaic_tiles(size, centre, tile_sizes):
     return out
 
 
+PATCH_MAX_PATCH, PATCH_MAX_MERGE, PATCH_MAX_REPEAT = 64, 8, 4      # (csrc/patch_addr.h)
+PATCH_BLOCK_BYTES = 65536       # a merge block's most: the least a job of the launch holds
+PATCH_KEYS = ("patch", "merge", "repeat", "order", "windows", "length")
+
+
+def normalize_patches(patches, size, n_outputs: Optional[int] = None, ncomp: Optional[int] = None, dtype: Optional[str] = None,
+                      return_seams: bool = False, compose=None):
+    """``patches`` of a call, checked: None for a call without it, else ``{"patch": P, "merge": m, "repeat": t, "order": "chw" or
+    "hwc", "windows": None or one (x, y, width, height) per source, "length": None or L}``.
+
+    ``patches``: None, or a dict with ``patch`` — P, 1..64, patches are square —, ``merge`` — m, 1..8, default 1: tokens are ordered
+    in m x m blocks of patches, Qwen's ``merge_size`` —, ``repeat`` — t, 1..4, default 1: every component's patch is written t times
+    in a row, Qwen's ``temporal_patch_size`` for a still image —, ``order`` — "chw" (default): a token is (C, t, P, P) as in
+    Qwen2-VL; "hwc": (P, P, C) as in SigLIP 2 NaFlex and timm's NaFlexVit, with ``repeat`` 1; the order of a token's elements is
+    this, whatever the decoder's layout —, ``windows`` — None, or one entry per source, None (the whole canvas) or ``(x, y, width,
+    height)`` in the coordinates of what the caller would receive, inside the canvas, ``width`` and ``height`` multiples of P * m —
+    and ``length`` — None: the packed form, ONE (T, D) array with D = C * t * P * P whose rows ``cu[k] .. cu[k + 1]`` are source
+    k's tokens (:func:`patch_grids`); an integer L >= 1: the padded form (N, L, D), the rows behind a source's tokens zero bits.
+    A source is an output of the group, or a composed canvas under ``compose`` (``compose``: :func:`normalize_compose`'s result).
+    The rule: tools/patch_model.py.  ``n_outputs``, ``ncomp`` and ``dtype`` (a name) are checked against where they are known.
+
+    ``patches`` needs ``size`` and does not go with ``return_seams``.  ValueError naming the source otherwise."""
+    if patches is None:
+        return None
+    if size is None:
+        raise ValueError("patches needs size=(width, height): the sources are the outputs of one array")
+    if return_seams:
+        raise ValueError("patches and return_seams do not go together: the seam outputs are the decoded images")
+    if not isinstance(patches, dict):
+        raise ValueError(f"patches must be None or a dict (patch=, merge=, repeat=, order=, windows=, length=), not {patches!r}")
+    for key in patches:
+        if key not in PATCH_KEYS:
+            raise ValueError(f"patches: unknown key {key!r} ({', '.join(PATCH_KEYS)})")
+    out = {}
+    for key, most, default in (("patch", PATCH_MAX_PATCH, None), ("merge", PATCH_MAX_MERGE, 1), ("repeat", PATCH_MAX_REPEAT, 1)):
+        v = patches.get(key, default)
+        if not _is_int(v) or not 1 <= int(v) <= most:
+            raise ValueError(f"patches: {key} must be an integer 1..{most}, not {v!r}")
+        out[key] = int(v)
+    P, m, t = out["patch"], out["merge"], out["repeat"]
+    order = patches.get("order", "chw")
+    if order not in ("chw", "hwc"):
+        raise ValueError(f"patches: order must be 'chw' or 'hwc', not {order!r}")
+    if order == "hwc" and t != 1:
+        raise ValueError(f"patches: order 'hwc' needs repeat 1, not {t}")
+    out["order"] = order
+    length = patches.get("length")
+    if length is not None and (not _is_int(length) or int(length) < 1 or int(length) >= 1 << 31):
+        raise ValueError(f"patches: length must be None or an integer of at least 1, not {length!r}")
+    out["length"] = None if length is None else int(length)
+    esize = B.DTYPE_BYTES[dtype] if dtype is not None else 1
+    block = m * m * (ncomp or 1) * t * P * P * esize
+    if block > PATCH_BLOCK_BYTES:
+        raise ValueError(f"patches: a merge block of {block} bytes (merge {m}, patch {P}, repeat {t}, {ncomp or 1} components of {esize} bytes), "
+                         f"more than {PATCH_BLOCK_BYTES}")
+    if compose is not None:                     # (the sources are the composed canvases)
+        size, n_outputs = compose["size"], len(compose["outputs"])
+    W, H = size
+    u = P * m
+    windows = patches.get("windows")
+    if windows is not None:
+        if not isinstance(windows, (list, tuple)):
+            raise ValueError(f"patches: windows must be None or a list with one entry per source, not {windows!r}")
+        if n_outputs is not None and len(windows) != n_outputs:
+            raise ValueError(f"patches: windows has {len(windows)} entries for {n_outputs} sources")
+    full = []
+    for k in range(len(windows) if windows is not None else 1 if n_outputs is None else n_outputs):
+        win = windows[k] if windows is not None else None
+        if win is None:
+            if W % u or H % u:
+                raise ValueError(f"patches: source {k}: the whole {W} x {H} canvas is not a multiple of patch * merge = {u} per side")
+            x, y, w, h = 0, 0, W, H
+        else:
+            if not isinstance(win, (tuple, list, np.ndarray)) or len(win) != 4 or not all(_is_int(v) for v in win):
+                raise ValueError(f"patches: source {k}: a window is None or four integers (x, y, width, height), not {win!r}")
+            x, y, w, h = (int(v) for v in win)
+            if w < 1 or h < 1 or x < 0 or y < 0 or x + w > W or y + h > H:
+                raise ValueError(f"patches: source {k}: window ({x}, {y}, {w}, {h}) is not inside the {W} x {H} canvas")
+            if w % u or h % u:
+                raise ValueError(f"patches: source {k}: window ({x}, {y}, {w}, {h}) is not a multiple of patch * merge = {u} per side")
+        if out["length"] is not None and (w // P) * (h // P) > out["length"]:
+            raise ValueError(f"patches: source {k}: {(w // P) * (h // P)} tokens, more than length {out['length']}")
+        full.append((x, y, w, h))
+    out["windows"] = full if windows is not None else None
+    return out
+
+
+def patches_for_components(patched, patches, size, n_outputs: int, ncomp: int, dtype: str, compose=None):
+    """:func:`normalize_patches`' result (``patched``, of ``patches``) once the files' component count and so the bytes of a merge
+    block are known"""
+    if patched is None:
+        return None
+    return normalize_patches(patches, size, n_outputs, ncomp, dtype, compose=compose)
+
+
+def patch_grids(patches, n_sources: int, size):
+    """``(grids, cu)`` of a ``patches`` value for ``n_sources`` sources on canvases of ``size`` = (width, height) — the composed
+    canvases' size under ``compose`` —: ``grids``, an int64 array (N, 2) of (gh, gw), the patches down and across of every source
+    (Qwen's ``image_grid_thw`` without the 1, NaFlex's spatial shapes), and ``cu``, an int64 array (N + 1,) of row offsets — source
+    k's tokens are rows ``cu[k] .. cu[k + 1]`` of the packed form: the ``cu_seqlens`` of a variable-length attention call.  In the
+    padded form source k's tokens are rows ``0 .. cu[k + 1] - cu[k]`` of ``out[k]``.  A convenience that restates the rule; NOT
+    pinned to any processor's own arrays."""
+    spec = normalize_patches(patches, normalize_size(size), int(n_sources))
+    if spec is None:
+        raise ValueError("patch_grids takes a patches dict, not None")
+    W, H = normalize_size(size)
+    P = spec["patch"]
+    wins = spec["windows"] if spec["windows"] is not None else [(0, 0, W, H)] * int(n_sources)
+    grids = np.array([(h // P, w // P) for _, _, w, h in wins], dtype=np.int64).reshape(-1, 2)
+    cu = np.zeros(len(grids) + 1, dtype=np.int64)
+    np.cumsum(grids[:, 0] * grids[:, 1], out=cu[1:])
+    return grids, cu
+
+
+def smart_resize(height: int, width: int, factor: int = 28, min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280):
+    """Qwen2-VL's size rule in plain Python, for ``resize_to``: ``(height, width)``, both multiples of ``factor``, their product
+    within ``min_pixels .. max_pixels``, the aspect ratio kept as closely as that allows.  Each side is rounded to the nearest
+    multiple of ``factor``; beyond ``max_pixels`` both are scaled down by sqrt(height * width / max_pixels) and rounded DOWN to
+    multiples, below ``min_pixels`` scaled up and rounded UP.  An aspect ratio beyond 200 is refused, as there.  A restatement; NOT pinned to any release of the processor."""
+    import math
+    height, width, factor = int(height), int(width), int(factor)
+    if height < 1 or width < 1 or factor < 1:
+        raise ValueError(f"smart_resize: height {height}, width {width}, factor {factor}")
+    if max(height, width) / min(height, width) > 200:
+        raise ValueError(f"smart_resize: an aspect ratio beyond 200: {max(height, width) / min(height, width)}")
+    h_bar = max(factor, round(height / factor) * factor)
+    w_bar = max(factor, round(width / factor) * factor)
+    if h_bar * w_bar > max_pixels:
+        beta = math.sqrt((height * width) / max_pixels)
+        h_bar = max(factor, math.floor(height / beta / factor) * factor)
+        w_bar = max(factor, math.floor(width / beta / factor) * factor)
+    elif h_bar * w_bar < min_pixels:
+        beta = math.sqrt(min_pixels / (height * width))
+        h_bar = math.ceil(height * beta / factor) * factor
+        w_bar = math.ceil(width * beta / factor) * factor
+    return h_bar, w_bar
+
+
 def rotation_matrix(angle: float, size: Tuple[int, int], center=None, translate=None) -> Tuple[float, ...]:
     """The matrix ``Image.rotate(angle, center=center, translate=translate)`` builds for ``expand=False`` on an image of ``size`` =
     (width, height) — counter-clockwise by ``angle`` degrees around ``center`` (None: the image's centre), then moved by
@@ -1709,6 +1848,9 @@ class _Request:
     # :func:`normalize_compose`'s dict (None: the outputs as they are).  The CALL's as ``mix`` is: the group's tensor is composed into a
     # new one of ``compose["size"]`` once every plan has been collected
     compose: Optional[dict] = None
+    # :func:`normalize_patches`' dict (None: the outputs as they are).  The CALL's too, and its last step: the group's tensor — mixed or
+    # composed where it is — is packed into a new one of token rows
+    patches: Optional[dict] = None
     # the extra groups of a call with ``also``: requests over the SAME files, index and orientations, each with its own size, views, output,
     # tensor and slots (None: a call without).  A group with views need not name every file here; what it has none of it is left out of.
     also: Optional[List["_Request"]] = None
@@ -2062,7 +2204,7 @@ class BatchDecoder:
 
     def decode(self, files: Sequence[bytes], rois=None, return_seams: bool = False, size=None, dtype=None, normalize=None, mirror=None,
                orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None):
+               affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None, patches=None):
         """Decode files that may mix sampling layouts (one plan per layout).  ``rois``: decode only a window of each image —
         None, one (x, y, width, height) for every file, or one such tuple or None (whole image) per file; every array then has
         the window's shape (see :func:`normalize_rois`).  ``size=(width, height)``: every image (or window) resized to that size
@@ -2158,6 +2300,12 @@ class BatchDecoder:
         over the tile array once every plan of the call has been collected, into an array of ``len(outputs)`` canvases, which is what
         the call returns in place of the tiles.  Not together with ``mix`` in one group.  An ``also`` entry takes a key ``compose`` of
         its own, over its own outputs.
+        ``patches``, with ``size``: the outputs packed into the token rows of a native-resolution vision encoder (:func:`normalize_patches`,
+        tools/patch_model.py) — None, or a dict ``patch``, ``merge``, ``repeat``, ``order``, ``windows`` and ``length``.  The LAST step,
+        behind ``erase``, ``mix`` and ``compose``, and like them not a step of any plan: ONE launch (csrc/patch.hip) once every plan
+        has been collected, from the group's array as it then stands (the composed canvases under ``compose``) into a new one —
+        ``(T, D)`` packed, ``(N, length, D)`` padded —, which the call returns in place of the outputs (:func:`patch_grids` gives the row
+        offsets).  An ``also`` entry takes a key ``patches`` of its own.
         ``also``, with ``size``: several groups of outputs from ONE decode (:func:`normalize_also`) — None or ``[]`` (the call as it
         is), else a list with one dict per extra group: ``size`` (required) and that group's own ``views``, ``mirror``, ``resize_to``,
         ``place``, ``affine``, ``perspective`` and ``color_ops`` (None when absent, never the call's); ``dtype``, ``normalize``,
@@ -2169,7 +2317,7 @@ class BatchDecoder:
         ``return_seams``."""
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective, erase=erase, mix=mix, compose=compose)
+                    perspective=perspective, erase=erase, mix=mix, compose=compose, patches=patches)
         mode = normalize_mode(mode)
         if mode is not None and return_seams:
             raise ValueError("mode and return_seams do not go together: the seam outputs are in the files' own components")
@@ -2260,6 +2408,8 @@ class BatchDecoder:
                 denses[j] = self._mix_host(g, denses[j])
             if g.compose is not None:
                 denses[j] = self._compose_host(g, denses[j])
+            if g.patches is not None:
+                denses[j] = self._patchify_host(g, denses[j])
         if extra is not None:
             return tuple(denses)
         if denses[0] is not None:
@@ -2269,7 +2419,7 @@ class BatchDecoder:
     def _host_request(self, files: Sequence[bytes], cache: Dict[int, ParsedJpeg], gpu_segment: Optional[bool], rois=None, return_seams: bool = False,
                       size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None,
                       fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, erase=None,
-                      mix=None, compose=None):
+                      mix=None, compose=None, patches=None):
         """The checked request of a :meth:`decode` call, or of one group of it, and the array it fills (None without ``size``).  ``cache``:
         the parsed files by their position in ``files``, filled with those this request names; ``gpu_segment``: whether they are parsed
         headers only (None: decided by the files this request names)."""
@@ -2286,6 +2436,8 @@ class BatchDecoder:
         mixes = normalize_mix(mix, size, len(views) if isinstance(views, (list, tuple)) else len(files),
                               dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams)
         composed = normalize_compose(compose, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES[mode] if mode else None, return_seams, mixes)
+        patched = normalize_patches(patches, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES[mode] if mode else None,
+                                    dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", return_seams, composed)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None                            # views: where the files that are read sit in the caller's list
@@ -2322,6 +2474,7 @@ class BatchDecoder:
             req.erase = erase_for_components(boxes, nc)
             req.mix = mixes
             req.compose = compose_for_components(composed, compose, size, nc)
+            req.patches = patches_for_components(patched, patches, size, req.n_outputs, nc, req.output.dtype if req.output else "uint8", req.compose)
             dense = np.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.numpy_dtype if req.output else np.uint8)
         return req, dense
 
@@ -2335,7 +2488,7 @@ class BatchDecoder:
 
     def _device_request(self, files: Sequence[bytes], rois, size, dtype, normalize, mirror, orientation=None, resample=None, mode=None,
                         resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                        affine_fill=None, color_ops=None, perspective=None, erase=None, mix=None, compose=None) -> _Request:
+                        affine_fill=None, color_ops=None, perspective=None, erase=None, mix=None, compose=None, patches=None) -> _Request:
         """The checked request of a :meth:`decode_device` call (``size``: :func:`normalize_size`'s): the windows against the
         files' headers and, with ``size``, the output against their component count and the one tensor they fill on this
         decoder's GPU, one slot per file in order — with ``views``, one slot per view, and only the files some view names."""
@@ -2350,6 +2503,8 @@ class BatchDecoder:
         mixes = normalize_mix(mix, size, len(views) if isinstance(views, (list, tuple)) else len(files),
                               dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8")
         composed = normalize_compose(compose, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES.get(mode) if isinstance(mode, str) else None, mix=mixes)
+        patched = normalize_patches(patches, size, len(views) if isinstance(views, (list, tuple)) else len(files), B.MODES.get(mode) if isinstance(mode, str) else None,
+                                    dtype_name(dtype) if dtype is not None else "float32" if normalize is not None else "uint8", compose=composed)
         if spec is not None and views is None:  # (windows of the TRANSFORMED images: whole files are decoded)
             views, rois = rois_as_views(rois, len(files)), None
         index = None
@@ -2379,6 +2534,7 @@ class BatchDecoder:
             req.erase = erase_for_components(boxes, nc)
             req.mix = mixes
             req.compose = compose_for_components(composed, compose, size, nc)
+            req.patches = patches_for_components(patched, patches, size, req.n_outputs, nc, req.output.dtype if req.output else "uint8", req.compose)
             req.dest = torch.empty((req.n_outputs,) + self._shape(size[0], size[1], nc), dtype=req.output.torch_dtype if req.output else torch.uint8,
                                    device=torch.device("cuda", self.ctx.device))
             req.slots = list(range(req.n_outputs))
@@ -2397,7 +2553,7 @@ class BatchDecoder:
 
     def decode_device(self, files: Sequence[bytes], rois=None, parts: Optional[int] = None, size=None, dtype=None, normalize=None,
                       mirror=None, orientation=None, resample=None, mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None,
-                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None):
+                      affine=None, affine_resample=None, affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None, patches=None):
         """Like :meth:`decode`, but the pixels stay in HBM: a list of ``torch.uint8`` tensors on this decoder's GPU,
         views into one packed buffer per plan (zero-copy for any DLPack consumer via ``tensor.__dlpack__()``).
         torch is only the allocator here; import it before this package.
@@ -2449,7 +2605,9 @@ class BatchDecoder:
         collected, each group's tensor is the source of ONE launch on torch's current stream into a new tensor of the same shape, which
         the caller gets; the source goes back to torch's allocator.
         ``compose`` as in :meth:`decode`: likewise once every plan of the call has been collected, one launch on torch's current stream
-        from the group's tile tensor into a new tensor of ``len(outputs)`` composed canvases, which the caller gets."""
+        from the group's tile tensor into a new tensor of ``len(outputs)`` composed canvases, which the caller gets.
+        ``patches`` as in :meth:`decode`: the last step, one launch on torch's current stream from the group's tensor — mixed or composed
+        where it is — into a new tensor of token rows, which the caller gets."""
         size = normalize_size(size)
         normalize_output(dtype, normalize, mirror, size)                 # (what needs no file: before any is read)
         normalize_resample(resample, size)
@@ -2459,7 +2617,7 @@ class BatchDecoder:
         normalize_fill(fill, resize_to)
         main = dict(size=size, dtype=dtype, normalize=normalize, mirror=mirror, resample=resample, mode=mode, resize_to=resize_to, place=place, fill=fill,
                     reducing_gap=reducing_gap, views=views, affine=affine, affine_resample=affine_resample, affine_fill=affine_fill, color_ops=color_ops,
-                    perspective=perspective, erase=erase, mix=mix, compose=compose)
+                    perspective=perspective, erase=erase, mix=mix, compose=compose, patches=patches)
         extra = normalize_also(also, main, size, rois)
         if extra is None:
             req = self._device_request(files, rois, orientation=orientation, **main)
@@ -2485,15 +2643,74 @@ class BatchDecoder:
     def _mixed(self, req: _Request, out):
         """What a call returns for a request whose plans have all been collected (``out``: :meth:`_decode_request`'s): every group
         with ``mix`` entries has its tensor mixed into a new one (:meth:`_mix_device`), every group with ``compose`` its tiles composed
-        into a new one (:meth:`_composed`), which takes its place."""
-        if all(g.mix is None and g.compose is None for g in req.groups):
+        into a new one (:meth:`_composed`), and every group with ``patches`` its tensor — as it then stands — packed into token
+        rows (:meth:`_patchified`), which takes its place."""
+        if all(g.mix is None and g.compose is None and g.patches is None for g in req.groups):
             return self._result(req, out)
         for g in req.groups:
             if g.mix is not None:
                 g.dest = self._mix_device(g)
             if g.compose is not None:
                 g.dest = self._composed(g)
+            if g.patches is not None:
+                g.dest = self._patchified(g)
         return self._result(req, req.dest)
+
+    def _patch_geometry(self, g: _Request, n_sources: int, elements: int):
+        """(dtype name, components, (width, height) of a source, rows of the output, D) of a group's patchify launch over ``n_sources``
+        sources of ``elements`` elements in all — the group's outputs, or its composed canvases"""
+        W, H = g.compose["size"] if g.compose is not None else g.size
+        dtype = g.output.dtype if g.output else "uint8"
+        nc = elements // (n_sources * W * H)
+        rows = B.host_patchify_count(self.layout, dtype, nc, (W, H), n_sources, g.patches)
+        return dtype, nc, (W, H), rows, nc * g.patches["repeat"] * g.patches["patch"] ** 2
+
+    def _patch_shape(self, g: _Request, n_sources: int, rows: int, D: int):
+        return (rows, D) if g.patches["length"] is None else (n_sources, g.patches["length"], D)
+
+    def _patchified(self, g: _Request):
+        """Group ``g``'s tensor as token rows (mj_patchify): one launch from ``g.dest`` — the outputs, mixed or composed where the group
+        is, which every plan has finished writing — into a new tensor (T, D) or (N, L, D), on torch's current stream as
+        :meth:`_composed` does it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        src = g.dest
+        n = int(src.shape[0])
+        dtype, nc, wh, rows, D = self._patch_geometry(g, n, src.numel())
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            dst = torch.empty(self._patch_shape(g, n, rows, D), dtype=src.dtype, device=dev)
+            args = (self.layout, dtype, nc, wh, n, g.patches)
+            if cur.cuda_stream:
+                if src.device == dev:
+                    src.record_stream(cur)      # (allocated on the stream the call was made on, which may be another)
+                self.ctx.patchify(src.data_ptr(), dst.data_ptr(), *args, stream=cur.cuda_stream)
+                return dst
+            if getattr(self, "_mix_stream", None) is None:
+                self._mix_stream = torch.cuda.Stream(device=dev)
+            st = self._mix_stream
+            st.wait_stream(cur)
+            src.record_stream(st)
+            dst.record_stream(st)
+            self.ctx.patchify(src.data_ptr(), dst.data_ptr(), *args, stream=st.cuda_stream)
+            cur.wait_stream(st)
+        return dst
+
+    def _patchify_host(self, g: _Request, dense: np.ndarray) -> np.ndarray:
+        """Group ``g``'s array as token rows (mj_patchify): uploaded, one launch on the context's stream into a second block, downloaded"""
+        n = int(dense.shape[0])
+        dtype, nc, wh, rows, D = self._patch_geometry(g, n, int(dense.size))
+        out = np.empty(self._patch_shape(g, n, rows, D), dtype=dense.dtype)
+        src = B.DeviceBytes(np.ascontiguousarray(dense))
+        try:
+            dst = B.DeviceBytes(None, out.nbytes)
+            try:
+                self.ctx.patchify(src.ptr, dst.ptr, self.layout, dtype, nc, wh, n, g.patches)
+                return dst.download(out)
+            finally:
+                dst.close()
+        finally:
+            src.close()
 
     def _compose_fill_bits(self, g: _Request, nc: int):
         """the element bit patterns, one per component, of a group's compose fill: its bytes — ``compose``'s own, else the group's
@@ -2701,7 +2918,7 @@ class BatchDecoder:
 
     def decode_device_iter(self, batches, depth=2, size=None, dtype=None, normalize=None, mirror=None, orientation=None, resample=None,
                            mode=None, resize_to=None, place=None, fill=None, reducing_gap=None, views=None, affine=None, affine_resample=None,
-                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None):
+                           affine_fill=None, color_ops=None, perspective=None, also=None, erase=None, mix=None, compose=None, patches=None):
         """Decode a stream of batches (an iterable of lists of file bytes) with the host work and the upload of the next
         batches overlapping the GPU work of the ones before; yields, per batch and in order, what :meth:`decode_device` returns.
 
@@ -2730,7 +2947,8 @@ class BatchDecoder:
         of tensors, one per group.  ``erase``: None, or an iterable that yields, batch by batch, what :meth:`decode_device` takes for
         that batch — a list with one entry per output, or None.  ``mix``: None, or an iterable that yields, batch by batch, what
         :meth:`decode_device` takes for that batch; the batch is mixed when it is collected, before it is handed out.  ``compose``: None, or an
-        iterable that yields, batch by batch, the dict :meth:`decode_device` takes for that batch, or None."""
+        iterable that yields, batch by batch, the dict :meth:`decode_device` takes for that batch, or None.  ``patches``: likewise None, or
+        an iterable that yields one dict or None per batch; a batch with a dict is handed out as its token rows."""
         size = normalize_size(size)
         if also is not None and isinstance(also, (list, tuple)) and len(also) == 0:
             also = None                                                               # (no extra group: a call without the argument)
@@ -2748,6 +2966,11 @@ class BatchDecoder:
         if isinstance(compose, dict):
             raise ValueError("compose must be None or an iterable that yields one dict or None per batch, not a dict")
         per_batch_compose = iter(compose) if compose is not None else None
+        if patches is not None and size is None:
+            raise ValueError("patches needs size=(width, height): the sources are the outputs of one array")
+        if isinstance(patches, dict):
+            raise ValueError("patches must be None or an iterable that yields one dict or None per batch, not a dict")
+        per_batch_patches = iter(patches) if patches is not None else None
         normalize_color_ops(color_ops if color_ops is None or _is_chain(color_ops) else (), size)      # (what needs no file, before any work)
         per_batch_colour = iter(color_ops) if color_ops is not None and not _is_chain(color_ops) else None
         # (what needs no file, before any work: an iterable's matrices are looked at batch by batch)
@@ -2831,6 +3054,12 @@ class BatchDecoder:
                         cp = next(per_batch_compose)
                     except StopIteration:
                         raise ValueError("compose yields fewer entries than there are batches") from None
+                pt = None
+                if per_batch_patches is not None:
+                    try:
+                        pt = next(per_batch_patches)
+                    except StopIteration:
+                        raise ValueError("patches yields fewer entries than there are batches") from None
                 def none(g):
                     return g is None or (isinstance(g, (list, tuple)) and all(e is None for e in g))
                 if per_batch_also is not None:
@@ -2841,17 +3070,17 @@ class BatchDecoder:
                     plain = none(t) and none(ps)
                     main = dict(size=size, dtype=dtype, normalize=normalize, mirror=m, resample=resample, mode=mode, resize_to=resize_to, place=place,
                                 fill=fill, reducing_gap=reducing_gap, views=v, affine=None if none(t) else t, affine_resample=None if plain else affine_resample,
-                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er, mix=mx, compose=cp)
+                                affine_fill=None if plain else affine_fill, color_ops=c, perspective=None if none(ps) else ps, erase=er, mix=mx, compose=cp, patches=pt)
                     extra = normalize_also(a, dict(main, affine_resample=affine_resample, affine_fill=affine_fill), size)
                     if extra is not None:
                         yield self._merged_request(files, o, [main] + extra, lambda fs, **kw: self._device_request(fs, None, **kw))
                         continue
                 if none(t) and none(ps):                # (a batch without a transform)
                     yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                               color_ops=c, erase=er, mix=mx, compose=cp)
+                                               color_ops=c, erase=er, mix=mx, compose=cp, patches=pt)
                     continue
                 yield self._device_request(files, None, size, dtype, normalize, m, o, resample, mode, resize_to, place, fill, reducing_gap, v,
-                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er, mx, cp)
+                                           None if none(t) else t, affine_resample, affine_fill, c, None if none(ps) else ps, er, mx, cp, pt)
         yield from self._device_iter(requests(), depth)
 
     def _device_iter(self, requests, depth=2):

@@ -108,6 +108,10 @@ void mj_destroy(mj_context *ctx) {
     if (ctx->compose_done) (void)hipEventDestroy(ctx->compose_done);
     if (ctx->h_compose) (void)hipHostFree(ctx->h_compose);
     if (ctx->d_compose) (void)hipFree(ctx->d_compose);
+    if (ctx->patch_flying) (void)hipEventSynchronize(ctx->patch_done);
+    if (ctx->patch_done) (void)hipEventDestroy(ctx->patch_done);
+    if (ctx->h_patch) (void)hipHostFree(ctx->h_patch);
+    if (ctx->d_patch) (void)hipFree(ctx->d_patch);
     if (ctx->d_idct_tt) (void)hipFree(ctx->d_idct_tt);
     if (ctx->d_dump) (void)hipFree(ctx->d_dump);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

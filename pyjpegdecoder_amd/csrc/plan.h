@@ -119,6 +119,11 @@ struct mj_context {
     size_t compose_cap = 0;
     hipEvent_t compose_done = nullptr;
     bool compose_flying = false;
+    // mj_patchify (patch.hip), likewise
+    void *h_patch = nullptr, *d_patch = nullptr;
+    size_t patch_cap = 0;
+    hipEvent_t patch_done = nullptr;
+    bool patch_flying = false;
     DevBufferCache cache;
     std::string err;
 };
